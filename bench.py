@@ -28,6 +28,8 @@ Rank 0 prints ONE JSON line with the contract keys plus
                   nvk_refine_alignment_batch call; never `value`
   "cpu_baseline": the CPU oracle (oracle/_ref = the reference compiled in place when present, else the C
                   restatement) timed on this box's host cores on a bounded sample of the same reads.
+  "dump_outputs": (with ``--dump-outputs DIR``) the arrays rank 0's last timed step computed, written as
+                  DIR/<name>.npy by dump_outputs(); the inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import json
@@ -110,6 +112,55 @@ def kernel_source_hash(root):
     return h.hexdigest()
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def _dump_array(a):
+    """A result array as numpy float32 / float64: integers as float32 where every value is exact in it
+    (|x| < 2^24), else as float64."""
+    if hasattr(a, 'detach'):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.dtype in (np.float32, np.float64):
+        return np.ascontiguousarray(a)
+    if a.dtype.kind in 'biu':
+        a = a.astype(np.int64)
+        if a.size == 0 or int(np.abs(a).max()) < (1 << 24):
+            return a.astype(np.float32)
+        return a.astype(np.float64)
+    return a.astype(np.float64)
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write the timed path's results as out_dir/<name>.npy (float32 / float64), at most ``budget`` bytes in
+    all.  Arrays of 1 MB or less are written whole; if the rest does not fit, each larger array keeps a fixed,
+    seeded sample of its rows (the same rows for the same shapes) and their indices go to <name>_rows.npy.
+    -> {name: shape written}."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: _dump_array(v) for k, v in arrays.items()}
+    small = {k for k, a in arrays.items() if a.nbytes <= (1 << 20) or a.ndim == 0}
+    large_bytes = sum(arrays[k].nbytes for k in arrays if k not in small)
+    room = budget - sum(arrays[k].nbytes for k in small) - 4096 * len(arrays)   # (.npy headers)
+    frac = 1.0
+    if large_bytes > room:
+        # every kept row also costs an 8-byte index
+        frac = room / float(sum(arrays[k].nbytes + 8 * arrays[k].shape[0] for k in arrays if k not in small))
+    written = {}
+    for name, a in sorted(arrays.items()):
+        if name not in small and frac < 1.0:
+            n = a.shape[0]
+            keep = max(1, int(n * frac))
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            rows = np.sort(rng.choice(n, size=keep, replace=False))
+            a = np.ascontiguousarray(a[rows])
+            np.save(os.path.join(out_dir, name + '_rows.npy'), rows.astype(np.float64))
+            written[name + '_rows'] = list(rows.shape)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        written[name] = list(a.shape)
+    return written
+
+
 PROFILE_FIGURES_OFF = False  # set for runs the committed counter profiles do not describe (--k: other kernels)
 
 
@@ -151,9 +202,14 @@ def main():
     ap.add_argument('--no-e2e', action='store_true', help='skip the host-pointer legs (profiling runs: their launches '
                     'would be averaged into the kernel statistics)')
     ap.add_argument('--slots', type=int, default=0)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / '
+                    'float64, at most 64 MB in all: a fixed, seeded sample of the rows of larger outputs)')
     ap.add_argument('--k', type=int, default=0, help='use a synthetic k-mer table of this size (e.g. 10: the size of the '
                     "reference's coded default table, 4^10 rows) instead of the packaged 6-mer table")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     global PROFILE_FIGURES_OFF
     PROFILE_FIGURES_OFF = bool(args.k)
 
@@ -205,6 +261,7 @@ def main():
             def step():
                 out = align_signal_batch(None, rb, kmer_model=km, aligner=aligner)
                 extra['reads_ok'] = int(out.n_aligned)
+                extra['result'] = out
         else:
             from nadavca_amd.estimate_snps import estimate_snps_batch
             from nadavca_amd.align_signal import _load_config
@@ -218,6 +275,7 @@ def main():
                 extra['reads_ok'] = last_batch_counts.get('reads_ok')       # status 0 after the log-likelihoods
                 extra['reads_fitted'] = last_batch_counts.get('reads_fitted')
                 extra['chunks'] = len(chunks)
+                extra['result'] = chunks
         stats_of = lambda: ctx.last_batch_stats()
     else:
         # every rank gets its own reads (seed offset by rank): weak scaling over independent reads
@@ -271,9 +329,37 @@ def main():
                 cov.zero_()
                 consensus_accumulate_dev(ctx, dbatch, ll, d_start, d_rev, status, 10.0, ref_len, acc, cov)
                 tot = (acc, cov) if dist is None else D.reduce_consensus_tensors(acc, cov, dst=0)
+                extra['consensus'] = tot
                 if tot is not None and d_pos.numel():
                     extra['posterior'] = posterior_segments_dev(ctx, tot[0][d_pos], d_refnum, d_seg, model[0], 0.001)
         stats_of = lambda: ctx.last_batch_stats()
+
+    def step_outputs():
+        """The arrays a caller of the timed path receives from its last step (rank 0's share)."""
+        if wname == 'api_align_signal':
+            r = extra['result']
+            o = {'live': r.live, 'status': r.status, 'alignment': r.alignment, 'ref_off': r.ref_off,
+                 'normalized_signal': r.normalized}
+            for i, f in enumerate(r.fits):
+                o['fit%d' % i] = f
+            return o
+        if wname == 'api_estimate_snps':
+            chunks = extra['result'] or []
+            return {'chunk_range': np.array([[c.start, c.end] for c in chunks], dtype=np.int64).reshape(-1, 2),
+                    'chunk_values': np.concatenate([np.asarray(c.values, dtype=np.float64) for c in chunks])
+                    if chunks else np.zeros((0, 4)),
+                    'chunk_coverage': np.concatenate([np.asarray(c.coverage) for c in chunks])
+                    if chunks else np.zeros(0)}
+        if is_align:
+            return {'events': events, 'status': status}
+        if wname == 'cfg3_snps':
+            return {'log_likelihoods': ll, 'status': status}
+        o = {'status': status}
+        if extra.get('consensus') is not None:
+            o['consensus_sums'], o['coverage'] = extra['consensus']
+        if extra.get('posterior') is not None:
+            o['posterior'] = extra['posterior']
+        return o
 
     def fence():
         torch.cuda.synchronize(device)
@@ -297,6 +383,9 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
 
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, step_outputs())
     n_ok = extra.get('reads_ok') if is_api else int((status == 0).sum().item())
     timing = ctx.timing_read()
     stats = stats_of()
@@ -340,6 +429,8 @@ def main():
                'higher_is_better': True, 'scaling': 'strong' if wname == 'cfg4_consensus' and not args.reads else 'weak',
                'vs_baseline': None, 'dtype': 'f64',
                'data': 'synthetic', 'config': cfg}
+        if dumped is not None:
+            out['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
         kname = 'align' if (is_align or wname == 'api_align_signal') else 'ell_hyp'
         ms, launches = timing[kname]
         per_kernel = {k: v[0] / max(v[1], 1) for k, v in timing.items() if v[1]}

@@ -19,6 +19,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+from conftest import GOLDEN
+
 pytestmark = pytest.mark.gpu
 
 THREADS = max(1, min(16, os.cpu_count() or 1))
@@ -77,13 +79,18 @@ def test_config2_bench_batch_every_read_equals_the_oracle(oracle_port):
         assert (n_u + n_n) * 100 < n, 'ties on %d of %d reads' % (n_u + n_n, n)
         print('cfg2 transitions=%s: 0 of %d reads differ; reads with tie bits: %d exact, %d ulp, %d near; plateau mark: %d'
               % (tr, n, n_x, n_u, n_n, int(((flags & TIE_PLATEAU) != 0).sum())))
-        # ... and against the reference's OWN code (oracle/_ref, compiled in place from /root/reference and
-        # shipped to the GPU box) on a 500-read slice
+        # ... and against the reference's OWN code on a 500-read slice: its rows' sha1 stored in
+        # tests/golden/ref_checks.npz (oracle/make_golden_ref_checks.py), and oracle/_ref itself where it was built
         from oracle.oracle import Oracle, have_reference
+        from oracle.make_golden_ref_checks import N_CFG2, events_sha1
+        want = np.load(os.path.join(GOLDEN, 'ref_checks.npz'))['cfg2_sha1_t%d' % int(tr)]
+        differ = [i for i in range(N_CFG2) if not np.array_equal(events_sha1(got[i]), want[i])]
+        assert differ == [], 'transitions=%s: reads %s differ from the reference\'s stored rows' % (tr, differ[:5])
+        print('cfg2 transitions=%s: 500-read slice equals the reference\'s stored rows' % tr)
         if have_reference():
             oref = Oracle('reference')
             mr = oref.KmerModel(*model)
-            sl = batch.cases[:500]
+            sl = batch.cases[:N_CFG2]
             expr = _oracle_refine(oref, mr, sl, wl['bandwidth'], 2, tr)
             assert all(_same(got[i], expr[i]) for i in range(len(sl))), 'differs from oracle/_ref'
             print('cfg2 transitions=%s: 500-read slice equals oracle/_ref (the compiled reference)' % tr)
@@ -316,11 +323,9 @@ def test_int16_api_workload_every_read_equals_the_oracle(oracle_port):
 
 
 def test_port_equals_compiled_reference_on_the_gpu_box(oracle_port):
-    """The checker of this suite is the C restatement (oracle/liboracle.so); where oracle/_ref — the reference's
-    own sources compiled in place — travelled to this box, the two must agree bit for bit HERE as well (this
-    box's libm and CPU), not only in the build container (tests/test_oracle_golden.py runs the same check there)."""
-    from oracle.oracle import have_reference
-    if not have_reference():
-        pytest.skip('oracle/_ref did not travel to this box')
+    """The checker of this suite is the C restatement (oracle/liboracle.so); it must agree bit for bit with the
+    reference's own outputs HERE as well (this box's libm and CPU), not only where the reference was compiled: the
+    stored outputs of tests/golden/ref_checks.npz always, oracle/_ref as well where it travelled to this box
+    (tests/test_oracle_golden.py runs the same check on the build machine)."""
     from test_oracle_golden import test_port_bit_identical_to_compiled_reference_when_present as check
     check(oracle_port)

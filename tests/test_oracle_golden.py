@@ -3,10 +3,12 @@
 Fixtures in tests/golden/ were produced by the reference's own C++ compiled in place
 (oracle/make_golden.py); on the same toolchain the restatement is bit-identical, the
 assertions allow 1e-12 relative so that a different libm build still passes."""
+import os
+
 import numpy as np
 import pytest
 
-from conftest import dp_args
+from conftest import GOLDEN, dp_args
 
 
 def _check_group(o, g, ll_rtol=1e-12):
@@ -68,27 +70,29 @@ def test_appendix_c_known_answers(oracle_port):
 
 
 def test_port_bit_identical_to_compiled_reference_when_present(oracle_port):
-    """Where oracle/_ref exists (build container, or shipped to the GPU box) the
-    restatement and the reference agree bit for bit on fresh random cases."""
+    """The restatement and the reference agree bit for bit on six random cases: against the reference's
+    outputs stored in tests/golden/ref_checks.npz (oracle/make_golden_ref_checks.py) and, where oracle/_ref
+    exists, against the compiled reference itself as well."""
     from oracle.oracle import Oracle, have_reference
-    if not have_reference():
-        pytest.skip('oracle/_ref not built')
-    from nadavca_amd import synthetic
-    ref = Oracle('reference')
-    model = synthetic.synth_model_arrays(3, k=4, central=1)
+    from oracle.make_golden_ref_checks import random_cases
+    z = np.load(os.path.join(GOLDEN, 'ref_checks.npz'), allow_pickle=False)
+    model, cases = random_cases()
     mp = oracle_port.KmerModel(*model)
-    mr = ref.KmerModel(*model)
-    for i in range(6):
-        rng = np.random.default_rng([55, i])
-        mel = [2, 1, 3, 0, 2, 2][i]
-        c = synthetic.make_dp_case(rng, model, R=40 + 5 * i, bandwidth=20 + i, dwell=(2, 7), jitter=4)
+    ref = Oracle('reference') if have_reference() else None
+    mr = ref.KmerModel(*model) if ref is not None else None
+    for i, (c, bw, mel) in enumerate(cases):
+        for key in ('signal', 'reference', 'context_before', 'context_after', 'approximate_alignment'):
+            assert np.array_equal(c[key], z['r%d_%s' % (i, key)]), 'synthetic.make_dp_case changed: regenerate'
         a = (c['signal'], c['reference'], c['context_before'], c['context_after'],
-             c['approximate_alignment'], 20 + i, mel)
+             c['approximate_alignment'], bw, mel)
         for flag in (True, False):
-            assert np.array_equal(oracle_port.refine_alignment(*a, mp, flag), ref.refine_alignment(*a, mr, flag))
+            ev = oracle_port.refine_alignment(*a, mp, flag)
             x = oracle_port.estimate_log_likelihoods(*a, mp, flag)
-            y = ref.estimate_log_likelihoods(*a, mr, flag)
-            assert np.array_equal(x, y)
+            assert np.array_equal(ev, z['r%d_refine_f%d' % (i, flag)])
+            assert np.array_equal(x, z['r%d_ell_f%d' % (i, flag)])
+            if ref is not None:
+                assert np.array_equal(ev, ref.refine_alignment(*a, mr, flag))
+                assert np.array_equal(x, ref.estimate_log_likelihoods(*a, mr, flag))
 
 
 def test_long_double_referee_builds_and_disagrees_where_pinned():
