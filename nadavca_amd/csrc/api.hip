@@ -10,7 +10,6 @@
 #include <new>
 #include <vector>
 
-#include "variant_switches.h"
 #include "nvk_internal.h"
 
 static thread_local char g_err[512] = "";
@@ -625,11 +624,7 @@ extern "C" int nvk_refine_alignment_batch_dev(
     if (rc) return rc;
     if ((rc = fetch_counts())) return rc;
     ctx->last_retries = tail[4];
-    bool redo = tail[4] > 0;
-#ifdef NVK_DEBUG_SWITCHES
-    if (getenv("NADAVCA_ALIGN3_NORETRY")) redo = false;  // debug builds only: leave the flags visible
-#endif
-    if (redo) {
+    if (tail[4] > 0) {
       rc = launch_align_retry(ctx, a, model_transitions ? 1 : 0, metas, rows, tot, out_events,
                               out_status);
       if (rc) return rc;

@@ -2,8 +2,6 @@
 #pragma once
 #include <math.h>
 
-#include "variant_switches.h"
-
 namespace dens {
 
 // e(x) * 2^dshift as a plain double.  `ac`/`mc` are the reference's constants
@@ -12,16 +10,9 @@ namespace dens {
 // exact 0.  2^(y/128) = 2^(k) * 2^(j/128) * 2^(g/128), j from a 128-entry LDS table, the last factor
 // a degree-5 Taylor polynomial (|g| <= 1/2: truncation 5e-19, i.e. below rounding level).  A non-finite
 // sample gives NaN, which the caller's range check turns into a retry by the exact kernel.
-#ifndef NVK_ETN_LOG2
-#define NVK_ETN_LOG2 7
-#endif
-constexpr int ETL = NVK_ETN_LOG2;  // log2 of the table size
-constexpr int ETN = 1 << ETL;      // table entries: 2^(j/ETN).  128 (degree-5 polynomial) or 32 (degree 6: a 32-entry
-                                   // table of doubles is exactly one 256-byte bank row, so a gather from it cannot
-                                   // conflict — same address, same bank, broadcast; the 128-entry table puts four
-                                   // entries on every bank and the random gather takes 19-24 % of the LDS cycles as
-                                   // conflicts, profiles/r02i_pmc_summary.txt)
-static_assert(ETL == 7 || ETL == 5, "polynomial coefficients exist for 128 and 32 entries");
+constexpr int ETL = 7;        // log2 of the table size
+constexpr int ETN = 1 << ETL;  // table entries: 2^(j/ETN).  (A conflict-free 32-entry table with a degree-6 polynomial
+                               // was measured and not kept)
 // v_fma_f64 with three VGPR operands: keeps the compiler from choosing v_fmac + a 64-bit register
 // copy of the coefficient per term
 __device__ __forceinline__ double fma_vvv(double a, double b, double c) {
@@ -29,25 +20,17 @@ __device__ __forceinline__ double fma_vvv(double a, double b, double c) {
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
   return r;
 }
-#define DENS_SCALE ((double)(1 << NVK_ETN_LOG2) * 0x1.71547652b82fep+0)
-// 2^(g/ETN), |g| <= 1/2: Taylor polynomial in g (truncation below 2^-57 relative for both table sizes)
+#define DENS_SCALE ((double)ETN * 0x1.71547652b82fep+0)
+// 2^(g/ETN), |g| <= 1/2: Taylor polynomial in g (truncation below 2^-57 relative)
 __device__ __forceinline__ double dens_poly(double gq) {
-#if NVK_ETN_LOG2 == 7
   double p = fma_vvv(gq, 0x1.5d87fe78a6731p-45, 0x1.3b2ab6fba4e77p-35);
   p = fma_vvv(p, gq, 0x1.c6b08d704a0c0p-26);
   p = fma_vvv(p, gq, 0x1.ebfbdff82c58fp-17);
   p = fma_vvv(p, gq, 0x1.62e42fefa39efp-8);
-#else
-  double p = fma_vvv(gq, 0x1.430912f86c787p-43, 0x1.5d87fe78a6731p-35);
-  p = fma_vvv(p, gq, 0x1.3b2ab6fba4e77p-27);
-  p = fma_vvv(p, gq, 0x1.c6b08d704a0c0p-20);
-  p = fma_vvv(p, gq, 0x1.ebfbdff82c58fp-13);
-  p = fma_vvv(p, gq, 0x1.62e42fefa39efp-6);
-#endif
   return fma(p, gq, 1.0);
 }
 // The same without the g^5 term (truncation 1.2e-15): for kernels_ell.hip, whose results are compared at 1e-9 and
-// whose hypothesis loop is bound by its instruction count (128-entry table only)
+// whose hypothesis loop is bound by its instruction count
 __device__ __forceinline__ double dens_poly4(double gq) {
   double p = fma_vvv(gq, 0x1.3b2ab6fba4e77p-35, 0x1.c6b08d704a0c0p-26);
   p = fma_vvv(p, gq, 0x1.ebfbdff82c58fp-17);
@@ -80,11 +63,7 @@ __device__ __forceinline__ DensHalf density_begin(double x, double mean, double 
   const double kk = rint(y);
   const double gq = y - kk;
   h.ki = (int)kk;
-#if NVK_ABL == 1
-  h.tj = 1.0;  // ablation: no table read
-#else
   h.tj = etab[h.ki & (ETN - 1)];
-#endif
   h.p = dens_poly(gq);
   return h;
 }

@@ -64,7 +64,6 @@
 #include <new>
 #include <vector>
 
-#include "variant_switches.h"
 #include "nvk_internal.h"
 #include "xmath.h"
 #include "dens.h"
@@ -80,20 +79,11 @@ using dens::ETN;
 
 constexpr int CH = 64;      // signal refill chunk (samples): one per lane
 static_assert(CH == 64, "a refill is one sample per lane");
-#ifndef NVK_PF
-#define NVK_PF 8
-#endif
-constexpr int PF = NVK_PF;       // forward sweep: spill prefetch depth (steps) = steps per loop trip
-#ifndef NVK_RU
-#define NVK_RU 16
-#endif
-constexpr int RU = NVK_RU;       // reverse sweep: steps per loop trip
-#ifndef NVK_FT
-#define NVK_FT 16
-#endif
+constexpr int PF = 8;       // forward sweep: spill prefetch depth (steps)
+constexpr int RU = 16;      // reverse sweep: steps per loop trip
 // forward sweep: steps per loop trip, a multiple of the prefetch depth (16: with the compiled-in rescale period
 // of 16 the step's position in the period is static; measured 8 -> 16: -2.3 %, 32: slower again — 128 registers)
-constexpr int FT = NVK_FT;
+constexpr int FT = 16;
 static_assert(FT % PF == 0 && 32 % FT == 0, "forward trip");
 static_assert(32 % PF == 0 && PF % 2 == 0 && 32 % RU == 0 && RU % 2 == 0, "the step count is a multiple of 32 (kernels_plan.hip)");
 // rescale period: 2^rsh steps (launch parameter, >= 16); must exceed c + mel so that at most one
@@ -111,13 +101,7 @@ constexpr int DMAX = 1000;  // the density exponent (<= ~3) plus the move must s
 constexpr int TARGET = 250; // exponent the largest live value is moved to
 #define HUGE_V 0x1.0p+900
 #define MASS_TOL 1e-9          // allowed relative spread of the rows' posterior mass
-#ifndef NVK_TIE_BITS
-#define NVK_TIE_BITS 24
-#endif
 #define TIE_FLAG_REL (1.0 / (double)(1ull << NVK_TIE_BITS))  // relative margin of the tie flag (xmath.h: near_tol)
-#ifndef NVK_TIE_ULPS
-#define NVK_TIE_ULPS 64  // NVK_TIE_ULP: the two scores differ by at most this many margins of xm::gt_tol (~ ulps of the log value)
-#endif
 
 // The spill is addressed through a buffer resource: address = resource base (scalar) + scalar byte
 // offset of the step + per-lane byte offset (a constant vector register), so neither the store of the
@@ -177,8 +161,8 @@ struct Align3Args {
   int c_lo, c_cap;  // this launch serves reads with c_lo < c <= c_cap
   int flag_above;   // ... and hands reads with c > c_cap to the exact kernel (last launch only)
   int rsh;          // log2 of the rescale period
-  int2 *rstate;      // two-launch mode: per read (K, suspect) handed from the reverse launch to the forward one
-  int read_lo;       // two-launch mode: positions [read_lo, read_lo + n_reads) of `order` are served, the spill of
+  int2 *rstate;      // per read (K, suspect) handed from the reverse launch to the forward one
+  int read_lo;       // positions [read_lo, read_lo + n_reads) of `order` are served, the spill of
                      // position p lives in slot p - read_lo
   int *n_retry;      // reads handed to the exact kernel
   int32_t *ties;     // per read: NVK_TIE_EXACT | NVK_TIE_NEAR — a path comparison fell inside the tie margin (nvk_last_tie_flags)
@@ -260,23 +244,17 @@ struct Scale {
 // (pm, cq) = (1, 0) on emitting lanes and (0, the row's constant times this step's scale move) on the
 // others — no select.  One density evaluation per lane and TWO steps instead of one per step.
 //
-// PHASE: 0 — a wave runs both sweeps of a read back to back (its spill slot is reused read after read);
-// 1 / 2 — two launches: the reverse sweeps of ALL reads of a chunk, then their forward sweeps, every read
+// PHASE: 1 / 2 — two launches: the reverse sweeps of ALL reads of a chunk, then their forward sweeps, every read
 // with a spill slot of its own (25 GB for 10 000 config-2 reads: what 288 GB of HBM are for).  The memory
 // system then sees a pure write stream followed by a pure read stream instead of a mix (measured with
 // tools/ubench_spill.hip in this access shape: 5.5 and 5.7-6.2 TB/s against 4.3 TB/s mixed), and the
-// reverse sweep — no path search, half the registers — runs with 6 waves per SIMD instead of 4.
-#ifndef NVK_LB
-#define NVK_LB 4
-#endif
-#ifndef NVK_LB_REV
-#define NVK_LB_REV 7  // (73 registers wanted, 72 allowed: two spilled ones outside the step loop; 6.45 against 6.59 ms at 6)
-#endif
-#ifndef NVK_LB_REV_TEAM
-#define NVK_LB_REV_TEAM 6  // (the team's reverse sweep: 80 registers; 5 and 4 measured the same within noise)
-#endif
+// reverse sweep — no path search, half the registers — runs with 6 waves per SIMD instead of 4 (one launch,
+// both sweeps per wave, was measured and not kept: DESIGN.md 5).  Launch bounds, waves per SIMD:
+constexpr int LB = 4;           // forward sweep
+constexpr int LB_REV = 7;       // (73 registers wanted, 72 allowed: two spilled ones outside the step loop; 6.45 against 6.59 ms at 6)
+constexpr int LB_REV_TEAM = 6;  // (the team's reverse sweep: 80 registers; 5 and 4 measured the same within noise)
 //
-// W: waves per read.  1 — the mapping above.  W > 1 (wide bands: ReadMeta::cw != 0, two-launch form only) — a
+// W: waves per read.  1 — the mapping above.  W > 1 (wide bands: ReadMeta::cw != 0) — a
 // TEAM of W waves sweeps one read with one row per lane of its TL = 64 W lanes: a lane's next row lies TL
 // rows on, so the skew a band of given width needs falls roughly W-fold (and with it the history ring per
 // lane, i.e. LDS per wave: BASELINE config 5 reads need skew ~28 and 57 KB of LDS with one wave — 2 waves
@@ -288,8 +266,7 @@ struct Scale {
 // ring has one slot more than the oldest age read (c + mel + 1): within one wave "read the oldest slot,
 // then overwrite it" is program order, across waves it would be a race.
 template <int MEL, int RSHC, bool PAIR, int PHASE, int W>
-__global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK_LB_REV) : NVK_LB) void align3_kernel(Align3Args g) {
-  static_assert(W == 1 || PHASE != 0, "teams exist in the two-launch form only");
+__global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV) : LB) void align3_kernel(Align3Args g) {
   constexpr int TL = 64 * W;  // lanes of the team
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int gl = threadIdx.x;  // lane of the team
@@ -337,26 +314,26 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
     __syncthreads();
     const int pos0 = __builtin_amdgcn_readfirstlane(*s_read);
     if (pos0 >= g.n_reads) break;
-    const int pos = pos0 + ((PHASE == 0) ? 0 : g.read_lo);
+    const int pos = pos0 + g.read_lo;
     const int rd = g.order ? g.order[pos] : pos;
     const ReadMeta m = g.metas[rd];
     if (m.status != NVK_READ_OK) {
-      if (PHASE != 1 && gl == 0) g.out_status[rd] = m.status;
+      if (PHASE == 2 && gl == 0) g.out_status[rd] = m.status;
       continue;
     }
     if ((W > 1) != (m.cw != 0)) continue;  // served by the other launch (one wave per read / a team)
     const int cm = (W > 1) ? m.cw : m.c;
     if (cm > g.c_cap) {           // band too wide for this launch's LDS rings
-      if (PHASE != 1 && g.flag_above && gl == 0) {
+      if (PHASE == 2 && g.flag_above && gl == 0) {
         g.out_status[rd] = NVK_READ_RETRY_INTERNAL;
         atomicAdd(g.n_retry, 1);
       }
       continue;
     }
-    // the spill slot: the wave's own (one-launch mode) or the read's (two launches)
+    // the read's own spill slot
     // (0x00020000: raw 32-bit data format, no swizzle; the range check is left wide open — the slot's size
     // bounds every offset by construction)
-    const size_t slot = (PHASE == 0) ? (size_t)blockIdx.x : (size_t)pos0;
+    const size_t slot = (size_t)pos0;
     const __amdgpu_buffer_rsrc_t spill_rs = __builtin_amdgcn_make_buffer_rsrc(
         g.spill_v + (slot * W + wv) * g.spill_stride, 0, 0x7ffffff0, 0x00020000);
     int32_t *spill_L = g.spill_L + slot * g.L_stride;
@@ -372,14 +349,11 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
     const double *sig = g.signal + m.sig_off;
     const int top = T - 1;
     int K = 0;          // true exponent of the largest suffix[0][.]
-#if NVK_PAIR_DEBUG == 2
-    int dbg_left = 6;
-#endif
     bool suspect = false;  // something left the double range: the exact kernel must redo this read
     const int RSH = RSHC ? RSHC : g.rsh, RS = 1 << RSH;
 
     // =========================== reverse sweep: suffix rows -> spill ===========================
-    if (PHASE != 2) {
+    if (PHASE == 1) {
       int r = top - ((top - gl) & (TL - 1));
       // Lanes without a row keep bs = hi = -big: never active, never finished.  For the other
       // rows `hi` already folds the "predecessor column exists" test (i + mel <= N).
@@ -534,34 +508,14 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
             RING_SYNC();
           }
         }
-#if NVK_PAIR_DEBUG == 2
-        if (PAIR && blockIdx.x == 0 && dbg_left > 0) {
-          const double chk = density(ring[i & RM], mean, ac2, mc2, shift_now, etab);
-          const bool badl = em && r >= 0 && i <= hi && i >= bs && chk != e;
-          if (__any(badl)) {
-            dbg_left--;
-            if (badl) printf("rev rd=%d u=%d lane=%d r=%d i=%d e=%.17g chk=%.17g age=%d shift=%d dnext=%d\n", rd, u, lane, r, i, e, chk, age, shift_now, sc.d_next);
-          }
-        }
-#endif
         // LDS reads first: the neighbour's value and the sample of the next step's density
         // the neighbour's value is D = gap + mel steps old: slot (su - D) mod H
         // outside the predecessor's band: the zero entry
         const int hs = ((unsigned)(i - pA) <= (unsigned)pW) ? ra : HZ2v;
-        const bool evalstep = !PAIR || NVK_PAIR_DEBUG == 1 || (uq & 1);  // (static) PAIR: densities are evaluated on odd steps
+        const bool evalstep = !PAIR || (uq & 1);  // (static) PAIR: densities are evaluated on odd steps
         double xn = 0.0;
-#if NVK_ABL == 6
-        if (evalstep) xn = (double)i * 1e-3;
-#else
-        if (evalstep) xn = ring[((PAIR && NVK_PAIR_DEBUG != 1) ? ia : i - 1) & RM];
-#endif
-#if NVK_ABL == 3
-        const double pv = prev * 0.5;
-#elif NVK_ABL == 10
-        const double pv = (uq & 1) ? prev * 0.5 : hist[hs];
-#else
+        if (evalstep) xn = ring[(PAIR ? ia : i - 1) & RM];
         const double pv = hist[hs];
-#endif
         // scalar shifts that bring a neighbour value from D steps ago to the current scale
         // a rescale lies between the step a neighbour value was produced at and now?  (rare, uniform)
         const bool sh_any = (u < sh_until);
@@ -591,16 +545,10 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
           }
         }
         prev = o;
-#if NVK_ABL == 10
-        if (!(uq & 1)) *reinterpret_cast<double *>(histb + (su * (8 * TL) + gl8)) = o;
-#elif NVK_ABL != 7
         *reinterpret_cast<double *>(histb + (su * (8 * TL) + gl8)) = o;
-#endif
         // (n_steps is even: an odd u is the even step 2p of the forward order, the step before it 2p + 1)
         if (uq & 1) {
-#if NVK_ABL != 4 && NVK_ABL != 8
           spill_store2(spill_rs, lane16, (t - t_min) >> 1, o, o_hold);
-#endif
         } else {
           o_hold = o;
         }
@@ -630,16 +578,12 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
           // (a capped move matters to the step it is applied to: after the sweep's last step — the padding
           // behind row 0, where only cells off the band are alive and collapse — there is none)
           suspect |= (u + 1 < n_steps) && (mx > -0x40000000) && (TARGET - mx > DMAX);
-#ifdef NVK_FLAG_DEBUG
-          if (lane == 0 && (mx > -0x40000000) && (TARGET - mx > DMAX || !(o <= HUGE_V)))
-            printf("flag rev rd=%d u=%d/%d mx=%d L=%d RS=%d c=%d T=%d\n", rd, u, n_steps, mx, sc.L, RS, c, T);
-#endif
           if (PAIR) dsel = em ? sc.d_next : 0;  // (RS - 1 is odd: an evaluation step)
         }
         i -= 1;
         i_old -= 1;
         e3 = e2; e2 = e1; e1 = e;
-        if (!PAIR || NVK_PAIR_DEBUG == 1) {
+        if (!PAIR) {
           e = density_end(dn, sc.d_next);
         } else if (evalstep) {
           e = density_end(dn, dsel);  // emitting lane: its next step; partner: the step after next
@@ -649,11 +593,7 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
         }
         su = (su + 1 == H) ? 0 : su + 1;
         ra = (int)min((unsigned)(ra + TL), (unsigned)(ra + TL - HZ));
-#if NVK_ABL == 10
-        if (uq & 1) STEP_SYNC();
-#elif NVK_ABL != 2
         STEP_SYNC();
-#endif
       }
       }
       K = __builtin_amdgcn_readfirstlane(kmax);
@@ -848,32 +788,13 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
                 RING_SYNC();
               }
             }
-#if NVK_PAIR_DEBUG == 2
-            if (PAIR && blockIdx.x == 0 && dbg_left > 0) {
-              const double chk = density(ring[(i - 1) & RM], mean, ac2, mc2, shift_now, etab);
-              const bool badl = em && r < T && i >= lo && i <= be && chk != e;
-              if (__any(badl)) {
-                dbg_left--;
-                if (badl) printf("fwd rd=%d u=%d lane=%d r=%d i=%d e=%.17g chk=%.17g age=%d shift=%d dnext=%d\n", rd, u, lane, r, i, e, chk, age, shift_now, sc.d_next);
-              }
-            }
-#endif
             // LDS reads first: the neighbour's values and the sample of the next step's density
             const int hs = ((unsigned)(i - pA) <= (unsigned)pW) ? ra : HZv;  // else: the zero entry
-            const bool evalstep = !PAIR || NVK_PAIR_DEBUG == 1 || (q & 1);  // (static) PAIR: densities are evaluated on odd steps
+            const bool evalstep = !PAIR || (q & 1);  // (static) PAIR: densities are evaluated on odd steps
             double xn = 0.0;
-#if NVK_ABL == 6
-            if (evalstep) xn = (double)i * 1e-3;
-#else
-            if (evalstep) xn = ring[((PAIR && NVK_PAIR_DEBUG != 1) ? ia : i) & RM];
-#endif
-#if NVK_ABL == 3
-            const double2 hv = make_double2(prev * 0.5, bestn);
-            const int Gin = G;
-#else
+            if (evalstep) xn = ring[(PAIR ? ia : i) & RM];
             const double2 hv = hist2[hs];
             const int Gin = ghist[hs];
-#endif
             const bool sh_any = (u < sh_until);
             DensHalf dn;
             if (evalstep) dn = density_begin(xn, mean, ac2, mc2, etab);
@@ -908,11 +829,7 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
             // Scores are (double, integer scale): stored = true * 2^scale.  The running maximum is kept
             // normalised (bestn in [0.5,1), scale G); an incoming score is brought onto that scale
             // before comparing (far below -> 0, far above -> inf, both compare correctly).
-#if NVK_ABL == 5
-            const double dva = dv;
-#else
             const double dva = ldexp(dv, G - Gin);  // no maximum yet: G = GBIG, any dv > 0 becomes +inf
-#endif
             const double tdiff = dva - bestn;
             const bool upd = (tdiff > bthr);  // (dv == 0 outside the span: never an update)
             // The tie flag (include/nadavca_hip.h, parity contract): the two scores are closer than 2^-24
@@ -921,7 +838,6 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
             // +inf a first candidate turns into, never qualifies.  Scores of cells thousands of bits below
             // the path would tie by their lost precision: this file is compiled with FP64 denormals
             // flushed, which makes them exact zeros.)
-#if !NVK_NO_TIEFLAG
             {
               const unsigned long long nr = __builtin_amdgcn_ballot_w64(fabs(tdiff) < dva * TIE_FLAG_REL);
               if (nr != 0) {  // (rare, a scalar branch: the classes are sorted out off the usual path)
@@ -933,7 +849,6 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
                 amb_n |= nr & ~ur & ~zr;
               }
             }
-#endif
             if (upd) {
               bestn = __builtin_amdgcn_frexp_mant(dv);         // in [0.5, 1)
               G = Gin - __builtin_amdgcn_frexp_exp(dv);        // its scale; -G = true exponent
@@ -974,10 +889,8 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
             }
             prev = o;
             rsum += post;
-#if NVK_ABL != 7
             *reinterpret_cast<double2 *>(histb + (su * (16 * TL) + gl16)) = make_double2(o, dpv);
             *reinterpret_cast<int *>(ghistb + (su * (4 * TL) + (gl16 >> 2))) = Gd;
-#endif
             if ((u & 31) == 31) {
               int w = u >> 5;
               asm volatile("" : "+s"(w));  // keeps the address arithmetic inside the branch
@@ -985,9 +898,7 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
               bits = 0;
             }
             // refill the prefetch slot just consumed
-#if NVK_ABL != 4 && NVK_ABL != 9
             if (q & 1) cur_v[(q % PF) >> 1] = spill_load2(spill_rs, lane16, (u + PF) >> 1);
-#endif
             // ---- rescale decision for the next step, then the next step's density
             if (W > 1 && age == RS - 2) {  // see the reverse sweep
               const int mxw = wave_max_i((o != 0.0) ? __builtin_amdgcn_frexp_exp(o) : -0x40000000);
@@ -1006,16 +917,12 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
               }
               sc.d_next = (mx > -0x40000000) ? min(TARGET - mx, DMAX) : 0;
               suspect |= (u + 1 < n_steps) && (mx > -0x40000000) && (TARGET - mx > DMAX);
-#ifdef NVK_FLAG_DEBUG
-              if (lane == 0 && (mx > -0x40000000) && (TARGET - mx > DMAX))
-                printf("flag fwd rd=%d u=%d/%d mx=%d L=%d RS=%d c=%d T=%d\n", rd, u, n_steps, mx, sc.L, RS, c, T);
-#endif
               if (PAIR) dsel = em ? sc.d_next : 0;
             }
             i += 1;
             i_old += 1;
             e3 = e2; e2 = e1; e1 = e;
-            if (!PAIR || NVK_PAIR_DEBUG == 1) {
+            if (!PAIR) {
               e = density_end(dn, sc.d_next);
             } else if (evalstep) {
               e = density_end(dn, dsel);
@@ -1025,9 +932,7 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
             }
             su = (su + 1 == H) ? 0 : su + 1;
             ra = (int)min((unsigned)(ra + TL), (unsigned)(ra + TL - HZ));
-#if NVK_ABL != 2
             STEP_SYNC();
-#endif
           }
         }
       }
@@ -1039,10 +944,6 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
         smin = fmin(smin, __shfl_xor(smin, dlt, 64));
         smax = fmax(smax, __shfl_xor(smax, dlt, 64));
       }
-#ifdef NVK_FLAG_DEBUG
-      if (lane == 0 && !(smin > 0.0 && smax <= smin * (1.0 + MASS_TOL)))
-        printf("flag mass rd=%d smin=%g smax=%g c=%d T=%d\n", rd, smin, smax, c, T);
-#endif
       suspect |= !(smin > 0.0 && smax <= smin * (1.0 + MASS_TOL));
     }
     __syncthreads();
@@ -1078,8 +979,7 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
     if (gl == 0 && ((amb_x | amb_n | amb_u) != 0 || m.rsv))
       g.ties[rd] = (amb_x != 0 ? NVK_TIE_EXACT : 0) | (amb_n != 0 ? NVK_TIE_NEAR : 0) | (amb_u != 0 ? NVK_TIE_ULP : 0) |
                    (m.rsv ? NVK_TIE_PLATEAU : 0);
-    if (NVK_ABL != 11 && NVK_ABL != 12) {
-      if (wv == 0) {  // (of a team, its first wave)
+    if (wv == 0) {  // (of a team, its first wave)
       // The walk down the update bits: row r's word tells where row r - 1 starts, a serial chain of ~800 rows per
       // read.  Run by one lane it was ~60 instructions per row — 9 % of everything the wave issues, and a wave that
       // shares its SIMD with three sweeping ones gets an issue slot every ~16 cycles whatever the instruction is.
@@ -1148,39 +1048,7 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? NVK_LB_REV_TEAM : NVK
         }
       }
       if (lane == 0) g.out_status[rd] = st;
-      }  // (a team's other waves have nothing to do here)
-    } else if (gl == 0) {
-      int32_t *ev = g.out_events + 2 * m.ref_off;
-      int st = NVK_READ_OK;
-      int off_r = offs[top];
-      for (int r = (NVK_ABL == 11 ? -1 : top); r >= 0; --r) {   // (ablation 11: no traceback)
-        const int off_c = off_r;
-        if (r > 0) off_r = offs[r - 1];  // next iteration's offset, fetched beside this one's bit words
-        if (g.transitions) {
-          ev[2 * (r >> 1) + (r & 1)] = idx;
-        } else {
-          if (r > 0) ev[2 * (r - 1) + 1] = idx;
-          if (r < top) ev[2 * r] = idx;
-        }
-        if (r == 0) break;
-        const int pm = g.transitions ? ((r - 1) & 1 ? 0 : MEL) : MEL;
-        int u = idx + off_c - t_min;
-        int w = u >> 5;
-        uint32_t v = bp[(size_t)w * TL + (r & (TL - 1))] & (0xffffffffu << (31 - (u & 31)));
-        while (v == 0 && w > 0) {
-          --w;
-          v = bp[(size_t)w * TL + (r & (TL - 1))];
-        }
-        if (v == 0) {
-          st = NVK_READ_RETRY_INTERNAL;
-          atomicAdd(g.n_retry, 1);
-          break;
-        }
-        int uu = (w << 5) + (31 - (__ffs(v) - 1));
-        idx = uu + t_min - off_c - pm;
-      }
-      g.out_status[rd] = st;
-    }
+    }  // (a team's other waves have nothing to do here)
   }
 }
 
@@ -1198,46 +1066,37 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
     return NVK_ERR_UNSUPPORTED;
   }
   const int max_c = tot.max_c < 1 ? 1 : tot.max_c;
-#if !NVK_TWO_PHASE
-  const int max_steps = tot.max_steps < 1 ? 1 : tot.max_steps;
-#endif
   int rc = nvk_ws_reserve(ctx, WS_MISC, 256);
   if (rc) return rc;
   int *counter = (int *)ctx->ws[WS_MISC];
   NVK_HIP(hipMemsetAsync(counter, 0, 2 * sizeof(int), ctx->stream));
   NVK_HIP(hipMemsetAsync(d_retry, 0, sizeof(int), ctx->stream));
 
-  // kernels: [0] both sweeps in one wave, [1] reverse sweeps, [2] forward sweeps; rescale period 16
-  // compiled in (k16) or taken from the arguments (kv).  With transition rows: the paired variant (one
-  // density evaluation per lane pair and step).
-  void (*k16[3])(Align3Args) = {nullptr, nullptr, nullptr};
-  void (*kv[3])(Align3Args) = {nullptr, nullptr, nullptr};
-  void (*kt[3])(Align3Args) = {nullptr, nullptr, nullptr};  // teams of ALIGN3_TEAM_W waves (wide bands)
-  void (*kt16[3])(Align3Args) = {nullptr, nullptr, nullptr};  // ... with the rescale period of 16 compiled in
+  // kernels: [0] reverse sweeps, [1] forward sweeps; rescale period 16 compiled in (k16) or taken from the
+  // arguments (kv).  With transition rows: the paired variant (one density evaluation per lane pair and step).
+  void (*k16[2])(Align3Args) = {nullptr, nullptr};
+  void (*kv[2])(Align3Args) = {nullptr, nullptr};
+  void (*kt[2])(Align3Args) = {nullptr, nullptr};  // teams of ALIGN3_TEAM_W waves (wide bands)
+  void (*kt16[2])(Align3Args) = {nullptr, nullptr};  // ... with the rescale period of 16 compiled in
   // period 8 compiled in: what the sweeps without transition rows use (rsh below); measured on the teams, where a
   // lockstep step is as long as its longest chain: the compiled-in period folds every test on the step's position
   // in the period away — forward sweep -16 %, reverse -10 % on BASELINE config 5 reads
-  void (*k8[3])(Align3Args) = {nullptr, nullptr, nullptr};
-  void (*kt8[3])(Align3Args) = {nullptr, nullptr, nullptr};
-#if NVK_TWO_PHASE
+  void (*k8[2])(Align3Args) = {nullptr, nullptr};
+  void (*kt8[2])(Align3Args) = {nullptr, nullptr};
 #define A3_SET(M, P)                                                                           \
   do {                                                                                         \
-    k16[1] = align3_kernel<M, 4, P, 1, 1>; k16[2] = align3_kernel<M, 4, P, 2, 1>;              \
-    kv[1] = align3_kernel<M, 0, P, 1, 1>; kv[2] = align3_kernel<M, 0, P, 2, 1>;                \
-    kt[1] = align3_kernel<M, 0, P, 1, ALIGN3_TEAM_W>; kt[2] = align3_kernel<M, 0, P, 2, ALIGN3_TEAM_W>; \
-    kt16[1] = align3_kernel<M, 4, P, 1, ALIGN3_TEAM_W>; kt16[2] = align3_kernel<M, 4, P, 2, ALIGN3_TEAM_W>; \
+    k16[0] = align3_kernel<M, 4, P, 1, 1>; k16[1] = align3_kernel<M, 4, P, 2, 1>;              \
+    kv[0] = align3_kernel<M, 0, P, 1, 1>; kv[1] = align3_kernel<M, 0, P, 2, 1>;                \
+    kt[0] = align3_kernel<M, 0, P, 1, ALIGN3_TEAM_W>; kt[1] = align3_kernel<M, 0, P, 2, ALIGN3_TEAM_W>; \
+    kt16[0] = align3_kernel<M, 4, P, 1, ALIGN3_TEAM_W>; kt16[1] = align3_kernel<M, 4, P, 2, ALIGN3_TEAM_W>; \
     if (!P) {                                                                                   \
-      k8[1] = align3_kernel<M, 3, false, 1, 1>; k8[2] = align3_kernel<M, 3, false, 2, 1>;       \
-      kt8[1] = align3_kernel<M, 3, false, 1, ALIGN3_TEAM_W>; kt8[2] = align3_kernel<M, 3, false, 2, ALIGN3_TEAM_W>; \
+      k8[0] = align3_kernel<M, 3, false, 1, 1>; k8[1] = align3_kernel<M, 3, false, 2, 1>;       \
+      kt8[0] = align3_kernel<M, 3, false, 1, ALIGN3_TEAM_W>; kt8[1] = align3_kernel<M, 3, false, 2, ALIGN3_TEAM_W>; \
     }                                                                                           \
   } while (0)
-#else
-#define A3_SET(M, P)                                                                           \
-  do { k16[0] = align3_kernel<M, 4, P, 0, 1>; kv[0] = align3_kernel<M, 0, P, 0, 1>; } while (0)
-#endif
 #define A3_PICK(M)                                                                             \
   do {                                                                                         \
-    if (transitions && !NVK_NO_PAIR) A3_SET(M, true); else A3_SET(M, false);                   \
+    if (transitions) A3_SET(M, true); else A3_SET(M, false);                                   \
   } while (0)
   switch (mel) {
     case 0: A3_PICK(0); break;
@@ -1254,14 +1113,14 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
   // (wide bands: teams of ALIGN3_TEAM_W waves, ReadMeta::cw; their history ring of (cw + mel + 1) slots of
   // 256 lanes x 20 B has to fit the 160 KB of a CU)
   const int C_HARD = 24;
-  struct Cls { int lo, hi; int64_t reads; int W; };
+  struct Cls { int lo, hi; int W; };
   Cls cls[2];
   int ncls = 0;
   const int64_t n_wide = (int64_t)tot.n_wide;
   const int max_cw = tot.max_cw < 1 ? 1 : tot.max_cw;
   if (a.n_reads - n_wide > 0 || max_c <= ALIGN1_C_CAP)
-    cls[ncls++] = Cls{0, max_c < ALIGN1_C_CAP ? max_c : ALIGN1_C_CAP, a.n_reads - n_wide, 1};
-  if (max_c > ALIGN1_C_CAP) cls[ncls++] = Cls{0, max_cw < C_HARD ? max_cw : C_HARD, n_wide, ALIGN3_TEAM_W};
+    cls[ncls++] = Cls{0, max_c < ALIGN1_C_CAP ? max_c : ALIGN1_C_CAP, 1};
+  if (max_c > ALIGN1_C_CAP) cls[ncls++] = Cls{0, max_cw < C_HARD ? max_cw : C_HARD, ALIGN3_TEAM_W};
   rc = nvk_ws_reserve(ctx, WS_RSTATE, (size_t)a.n_reads * sizeof(int2));
   if (rc) return rc;
   TimerScope ts_align(ctx, NVK_K_ALIGN);
@@ -1295,18 +1154,14 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
     const size_t lds_rev = lds_need(c, 8);  // reverse-only launch
     if (lds > 160 * 1024) return NVK_ERR_UNSUPPORTED;
     int per_cu = (int)((160 * 1024) / lds);          // workgroups (waves, or teams of W waves) per CU
-    if (per_cu > 4 * NVK_LB / W) per_cu = 4 * NVK_LB / W;
+    if (per_cu > 4 * LB / W) per_cu = 4 * LB / W;
     if (per_cu < 1) per_cu = 1;
     int per_cu_rev = (int)((160 * 1024) / lds_rev);
-    if (per_cu_rev > 4 * (W > 1 ? NVK_LB_REV_TEAM : NVK_LB_REV) / W) per_cu_rev = 4 * (W > 1 ? NVK_LB_REV_TEAM : NVK_LB_REV) / W;
+    if (per_cu_rev > 4 * (W > 1 ? LB_REV_TEAM : LB_REV) / W) per_cu_rev = 4 * (W > 1 ? LB_REV_TEAM : LB_REV) / W;
     if (per_cu_rev < 1) per_cu_rev = 1;
-#if NVK_TWO_PHASE
     int32_t mxpad = 1;  // the longest read of the batch under the offsets the kernels use (ReadMeta::pad)
     for (int64_t q = 0; q < a.n_reads; q++) mxpad = steps_sorted[q] > mxpad ? steps_sorted[q] : mxpad;
     const int64_t bp_stride = (int64_t)((mxpad + 31) / 32 + 1) * TLk;
-#else
-    const int64_t bp_stride = (int64_t)((max_steps + 31) / 32 + 1) * 64;
-#endif
     const int64_t cap = nvk_spill_cap(ctx, WS_SPILL);
 
     Align3Args g;
@@ -1332,14 +1187,12 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
     g.out_events = out_events;
     g.out_status = out_status;
     // (a team's skew at stride 256 is small: its rescale period is usually the compiled-in 16, BASELINE config 5: 4 + 2)
-    void (**kern)(Align3Args) = (W > 1) ? ((rsh == 4 && kt16[1]) ? kt16 : ((rsh == 3 && kt8[1]) ? kt8 : kt))
-                                        : ((rsh == 4) ? k16 : ((rsh == 3 && k8[1]) ? k8 : kv));
-    if (W > 1 && !kern[1]) return NVK_ERR_UNSUPPORTED;  // (one-launch development build)
-    for (int ph = 0; ph < 3; ph++)
-      if (kern[ph] && (ph == 1 ? lds_rev : lds) > 64 * 1024)
+    void (**kern)(Align3Args) = (W > 1) ? ((rsh == 4) ? kt16 : ((rsh == 3 && kt8[0]) ? kt8 : kt))
+                                        : ((rsh == 4) ? k16 : ((rsh == 3 && k8[0]) ? k8 : kv));
+    for (int ph = 0; ph < 2; ph++)
+      if ((ph == 0 ? lds_rev : lds) > 64 * 1024)
         NVK_HIP(hipFuncSetAttribute((const void *)kern[ph], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(ph == 1 ? lds_rev : lds)));
-#if NVK_TWO_PHASE
+                                    (int)(ph == 0 ? lds_rev : lds)));
     // chunks of launch positions whose spill fits the cap; a chunk's slots are sized by its longest read.
     // The launch order is class-major (launch_order): the teams' reads are positions [0, n_wide), the one-wave
     // reads the rest, so a class's chunks, slots and workgroups count only the reads it sweeps.
@@ -1370,8 +1223,6 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
       if (rc) return rc;
       int64_t slots_f = ctx->slots_override > 0 ? ctx->slots_override : (int64_t)ctx->num_cus * per_cu;
       int64_t slots_r = ctx->slots_override > 0 ? ctx->slots_override : (int64_t)ctx->num_cus * per_cu_rev;
-      if (NVK_SLOTS_F > 0) slots_f = NVK_SLOTS_F;
-      if (NVK_SLOTS_R > 0) slots_r = NVK_SLOTS_R;
       if (slots_f > n_chunk) slots_f = n_chunk;
       if (slots_r > n_chunk) slots_r = n_chunk;
       rc = nvk_ws_reserve(ctx, WS_BP, (size_t)slots_f * bp_stride * 4);
@@ -1384,34 +1235,12 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
       g.n_reads = (int)n_chunk;
       g.read_lo = (int)lo;
       NVK_HIP(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
-      hipLaunchKernelGGL(kern[1], dim3((unsigned)slots_r), dim3(TLk), lds_rev, ctx->stream, g);
+      hipLaunchKernelGGL(kern[0], dim3((unsigned)slots_r), dim3(TLk), lds_rev, ctx->stream, g);
       NVK_HIP(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
-      hipLaunchKernelGGL(kern[2], dim3((unsigned)slots_f), dim3(TLk), lds, ctx->stream, g);
+      hipLaunchKernelGGL(kern[1], dim3((unsigned)slots_f), dim3(TLk), lds, ctx->stream, g);
       NVK_HIP(hipGetLastError());
       lo = hi;
     }
-#else
-    int64_t slots = ctx->slots_override > 0 ? ctx->slots_override : (int64_t)ctx->num_cus * per_cu;
-    if (slots > cls[k].reads) slots = cls[k].reads > 0 ? cls[k].reads : 1;
-    const int64_t spill_stride = ((int64_t)max_steps + 2 * PF) * 64;
-    const int64_t L_stride = (int64_t)(max_steps >> rsh) + 4;
-    if (slots * spill_stride * 8 > cap) slots = cap / (spill_stride * 8) > 1 ? cap / (spill_stride * 8) : 1;
-    rc = nvk_ws_reserve(ctx, WS_SPILL, (size_t)slots * spill_stride * 8);
-    if (rc) return rc;
-    rc = nvk_ws_reserve(ctx, WS_STAGE, (size_t)slots * L_stride * 4);
-    if (rc) return rc;
-    rc = nvk_ws_reserve(ctx, WS_BP, (size_t)slots * bp_stride * 4);
-    if (rc) return rc;
-    NVK_HIP(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
-    g.spill_v = (double *)ctx->ws[WS_SPILL];
-    g.spill_L = (int32_t *)ctx->ws[WS_STAGE];
-    g.bp = (uint32_t *)ctx->ws[WS_BP];
-    g.spill_stride = spill_stride;
-    g.L_stride = L_stride;
-    g.n_reads = (int)a.n_reads;
-    hipLaunchKernelGGL(kern[0], dim3((unsigned)slots), dim3(64), lds, ctx->stream, g);
-    NVK_HIP(hipGetLastError());
-#endif
   }
   // bytes the sweeps stream through HBM: 8 B written + 8 B read per (step, lane) + scales + bits
   ctx->last_spill_bytes = (int64_t)tot.steps * 64 * 16 + (int64_t)tot.steps / 16 * 8 + (int64_t)tot.steps * 8 * 2;

@@ -49,7 +49,6 @@
 #include <math.h>
 
 #include "nvk_internal.h"
-#include "variant_switches.h"
 #include "xmath.h"
 #include "dens.h"
 
@@ -618,8 +617,7 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(EllArgs g) {
       cell_put(suf + rowoff[R] + x - bs[R], xm::one());
     }
     // ---- A, B: the two sweeps
-    if (NVK_ELL_ABL == 2) {
-    } else if (FAST) {
+    if (FAST) {
       SweepLane *ltab = reinterpret_cast<SweepLane *>(tab);  // same window, smaller entries
       if (c == 1) {
         sweep_fast<MEL, true>(g.pl.fwd + m.row_off, R, N, c, sig, false, ring, RM, ltab, etab, hist_m, hist_g,
@@ -659,8 +657,7 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(EllArgs g) {
     const int back = dm.k - dm.central - 1, fwd = dm.central;
     const int n_items = R * (alpha - 1);
     const int grp = lane / GL, gl = lane % GL;
-    if (NVK_ELL_ABL == 1) {
-    } else if (FAST) {
+    if (FAST) {
       // lane roles in a group: 0 = density of the k-mer before `first` (only feeds the mixture of the
       // first position), 1..npos = the positions first..last, npos+1 = the closing lane.
       // Lane role rho is at cell i = base + u - rho at step u, so whatever lane rho-1 produced at step

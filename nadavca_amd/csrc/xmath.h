@@ -13,12 +13,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#ifndef NVK_TIE_BITS
-#define NVK_TIE_BITS 24  // the tie flag's relative margin is 2^-NVK_TIE_BITS (near_tol)
-#endif
-#ifndef NVK_TIE_ULPS
-#define NVK_TIE_ULPS 64  // NVK_TIE_ULP: scores closer than this many margins of gt_tol (~ ulps of the reference's log value)
-#endif
+// the tie margins of the parity contract (include/nadavca_hip.h), shared by the exact and the default align kernel
+constexpr int NVK_TIE_BITS = 24;  // the tie flag's relative margin is 2^-NVK_TIE_BITS (near_tol)
+constexpr int NVK_TIE_ULPS = 64;  // NVK_TIE_ULP: scores closer than this many margins of gt_tol (~ ulps of the reference's log value)
 
 namespace xm {
 
