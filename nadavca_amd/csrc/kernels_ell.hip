@@ -11,22 +11,20 @@
 //
 // Mapping (not the reference's): "fused" lanes.  The reference alternates a wobble row
 // (mixture of the k-mers j-1 and j, min event length 0) with an emitting row (k-mer j).  Both
-// are computed by ONE lane per base position j: the mixture needs the emitting Gaussian anyway,
-// so a lane evaluates two densities and advances two rows per step.  Lanes of consecutive
-// positions form a systolic wavefront (cell i of position j at step i + c*j), handing the
-// emitting row to the neighbour through a small LDS ring.  All probabilities are scaled linear
-// numbers (xmath.h); natural logs are taken once per output value.
+// are computed by ONE lane per base position j, which advances two rows per step.  Lanes of
+// consecutive positions form a systolic wavefront (cell i of position j at step i + c*j), each
+// taking the emitting row from its left neighbour.  All probabilities are scaled linear numbers
+// (xmath.h); natural logs are taken once per output value.
 //
 // Sweep rows are kept row-major in a per-slot row store (16-byte cells: struct Cell) so that phase C reads
-// them with unit stride.  Phase C packs 8 hypotheses per wave step, 8 lanes each: up to k fused
-// positions plus one closing lane that applies the last wobble row and accumulates
-// sum_x cur[x] * suffix[last+1][x].
+// them with unit stride.  Phase C packs 8 hypotheses per wave step in groups of 8 lanes (k-mers longer than 6:
+// 4 in groups of 16): a lane for the k-mer before the first position, up to k fused positions, and one closing
+// lane that applies the last wobble row and accumulates sum_x cur[x] * suffix[last+1][x].
 //
-// The kernel has two variants of the same recurrences (template parameter FAST).  Wrong-base hypotheses routinely couple
-// quantities that are thousands of bits apart (a k-mer 40 sigma off costs ~1000 bits per sample), so
-// every value keeps its own exponent in both; plain doubles under a shared scale were tried and lose
-// exactly the terms that decide such hypotheses.  The default (FAST) variant makes the scaled numbers
-// cheap instead:
+// Wrong-base hypotheses routinely couple quantities that are thousands of bits apart (a k-mer 40 sigma off
+// costs ~1000 bits per sample), so every value keeps its own exponent; plain doubles under a shared scale
+// were tried and lose exactly the terms that decide such hypotheses.  The scaled numbers are made cheap
+// instead:
 //   * sums are not re-normalised (xm-style frexp) on every operation: add_lazy aligns the two
 //     mantissas and adds, the state is normalised once per trip of 12 steps (phase C: a trip is unrolled, so the
 //     history and prefetch slots of a step are constants — fused_step_ring) or every 16 steps (sweeps);
@@ -40,9 +38,6 @@
 //     config-2-shaped read), through an LDS ring otherwise — which is normalised
 //     at EVERY hand-over (a dominating value passes its mantissa on; a systematic factor per hand-over
 //     would compound to 2^-R or 2^+R along the lanes).
-// The exact variant (NADAVCA_ELL_KERNEL=1) is the original formulation with
-// two polynomial densities per lane and LDS hand-over; both agree to ~1e-15 relative
-// (tools/dbg_ell.py, tests/test_gpu_ell.py).
 //
 // Quirks kept on purpose: the mixture is (g1 + g2) * exp(-2), not / 2; the
 // closing wobble row of a hypothesis lives on band row `last`, not `last + 1`.
@@ -60,10 +55,10 @@ constexpr int CH = 128;    // signal refill chunk (samples)
 constexpr int TABN = 128;  // descriptor window (two 64-position blocks)
 constexpr int PF = 4;      // phase C prefetch depth (steps)
 // lanes per hypothesis group (template parameter GL of the kernel): 8 for k-mers up to 6 (8 hypotheses per
-// wave step), 16 for longer ones (4 per step; a group is then one DPP row) — the fast phase needs k + 2
-// lanes per group, the exact one k + 1
-constexpr int HRS = 16;    // fast phase C: steps between mantissa normalisations
-#define EXPM2_D 0x1.152aaa3bf81ccp-3  // exp(-2), see expm2()
+// wave step), 16 for longer ones (4 per step; a group is then one DPP row) — phase C needs k + 2 lanes per group
+constexpr int HRS = 16;    // sweeps: steps between mantissa normalisations
+// exp(-2): the reference divides the mixture by Probability(2) == exp(2) (kmer_model.cpp:59-61)
+#define EXPM2_D 0x1.152aaa3bf81ccp-3
 
 #define WAVE_SYNC()                                        \
   do {                                                     \
@@ -105,9 +100,20 @@ struct EllArgs {
   int32_t *out_status;
 };
 
-// ---- fast phase C ----------------------------------------------------------------------------
+// ---- one fused lane ---------------------------------------------------------------------------
 template <int MEL>
-struct LaneState;
+struct LaneState {
+  X wq[MEL + 1];  // wobble-row values at cells i, i-1, ..., i-MEL
+  X em;           // emitting-row value at the previous cell
+  X gh[MEL > 0 ? MEL : 1];  // emitting densities of the previous MEL-1.. cells
+  __device__ __forceinline__ void reset() {
+#pragma unroll
+    for (int k = 0; k <= MEL; k++) wq[k] = xm::zero();
+    em = xm::zero();
+#pragma unroll
+    for (int k = 0; k < (MEL > 0 ? MEL : 1); k++) gh[k] = xm::one();
+  }
+};
 struct HypDesc {
   double bm, bac, bmc;  // the lane's own density, constants scaled for dens::density
   int wbs, wbe;         // cells of the wobble row (what arrives from the left is taken from wbs on)
@@ -134,7 +140,9 @@ __device__ __forceinline__ X density_x(double x, double mean, double ac, double 
   return X{etab[ki & (dens::ETN - 1)] * dens::dens_poly4(y - kk), ki >> dens::ETL};
 }
 
-// fused_step with lazy sums; gb/ga are the two mixture components at this cell's sample
+// One step of a fused lane at cell i, with lazy sums: gb/ga are the two mixture components at the cell's sample,
+// pred is the predecessor row at cell i.  Returns the emitting-row value at cell i (`alt` outside its range); the
+// wobble value of this cell is left in st.wq[0].
 template <int MEL>
 __device__ __forceinline__ X fused_step_fast(const HypDesc &d, LaneState<MEL> &st, int i, X gb, X ga,
                                              X pred, X alt) {
@@ -228,83 +236,6 @@ __device__ __forceinline__ X dpp_ror1(X v) {
   return X{dpp_ror1(v.m), __builtin_amdgcn_mov_dpp(v.e, 0x13C, 0xf, 0xf, false)};
 }
 
-__device__ __forceinline__ X density(double x, double mean, double ac2, double mc2) {
-  double d = x - mean;
-  return xm::from_log2(ac2 - d * d * mc2);  // kmer_model.cpp:48-50, in base-2 logs
-}
-
-// exp(-2): the reference divides the mixture by Probability(2) == exp(2) (kmer_model.cpp:59-61)
-__device__ __forceinline__ X expm2() { return X{0x1.152aaa3bf81ccp+0, -3}; }
-
-// per-lane description of one fused position
-struct LaneDesc {
-  double am, aac2, amc2, bm, bac2, bmc2;
-  int wbs, wbe;  // wobble-row band (== band the lane starts on)
-  int ebe;       // last cell of the emitting row
-  int pbs, pbe;  // band of the predecessor row (values outside read as zero)
-  int has_wob;
-};
-
-template <int MEL>
-struct LaneState {
-  X wq[MEL + 1];  // wobble-row values at cells i, i-1, ..., i-MEL
-  X em;           // emitting-row value at the previous cell
-  X gh[MEL > 0 ? MEL : 1];  // emitting densities of the previous MEL-1.. cells
-  __device__ __forceinline__ void reset() {
-#pragma unroll
-    for (int k = 0; k <= MEL; k++) wq[k] = xm::zero();
-    em = xm::zero();
-#pragma unroll
-    for (int k = 0; k < (MEL > 0 ? MEL : 1); k++) gh[k] = xm::one();
-  }
-};
-
-// One step of a fused lane at cell i (sample x = s[i-1]); pred = predecessor row at cell i.
-// Returns the emitting-row value at cell i (zero outside its range).  The wobble value of this
-// cell is left in st.wq[0].
-template <int MEL>
-__device__ __forceinline__ X fused_step(const LaneDesc &d, LaneState<MEL> &st, int i, double x,
-                                        X pred, bool on) {
-  X gb = density(x, d.bm, d.bac2, d.bmc2);
-  X ga = density(x, d.am, d.aac2, d.amc2);
-  X mix = xm::mul(xm::add_norm(ga, gb), expm2());
-  X wn = xm::add_norm(pred, xm::mul(mix, st.wq[0]));  // node_next_row.h with mel = 0
-  wn = xm::sel(d.has_wob != 0, wn, pred);
-  wn = xm::sel(on && i >= d.wbs && i <= d.wbe, wn, xm::zero());
-#pragma unroll
-  for (int k = MEL; k >= 1; k--) st.wq[k] = st.wq[k - 1];
-  st.wq[0] = wn;
-  X P = xm::one();
-  if (MEL >= 1) {
-    P = gb;
-#pragma unroll
-    for (int k = 0; k < MEL - 1; k++) P = xm::mul(P, st.gh[k]);
-  }
-  X en = xm::add_norm(xm::mul(P, st.wq[MEL]), xm::mul(gb, st.em));
-  en = xm::sel(on && i >= MEL && i <= d.ebe, en, xm::zero());
-  st.em = en;
-  if (MEL >= 2) {
-#pragma unroll
-    for (int k = MEL - 2; k >= 1; k--) st.gh[k] = st.gh[k - 1];
-    st.gh[0] = gb;
-  }
-  return en;
-}
-
-__device__ __forceinline__ void load_desc(LaneDesc &d, const FusedParam &f) {
-  d.am = f.a_mean; d.aac2 = f.a_ac * xm::LOG2E; d.amc2 = f.a_mc * xm::LOG2E;
-  d.bm = f.b_mean; d.bac2 = f.b_ac * xm::LOG2E; d.bmc2 = f.b_mc * xm::LOG2E;
-  d.wbs = f.wbs; d.wbe = f.wbe; d.ebe = f.ebe;
-  d.pbs = f.wbs; d.pbe = f.wbe;
-  d.has_wob = f.has_wob;
-}
-
-__device__ __forceinline__ void load_tab_block(FusedParam *tab, const FusedParam *src, int blk,
-                                               int R, int lane) {
-  int j = blk * 64 + lane;
-  if (j >= 0 && j < R) tab[j & (TABN - 1)] = src[j];
-}
-
 // k-mer id of position pos with base `p` replaced by `b` (sequence.cpp:31-38, kmer_model.cpp:22-30)
 __device__ __forceinline__ int64_t kmer_id_mod(const DeviceModel &dm, const int32_t *ref, int R,
                                                const int32_t *cb, int nb, const int32_t *ca, int na,
@@ -321,96 +252,11 @@ __device__ __forceinline__ int64_t kmer_id_mod(const DeviceModel &dm, const int3
   return id;
 }
 
-// one sweep over the R fused positions of `desc` (prefix order or mirrored suffix order)
-template <int MEL>
-__device__ void sweep(const FusedParam *desc, int R, int N, int c, const double *sig, bool mirror,
-                      double *ring, int RM, FusedParam *tab, double *hist_m, int *hist_e, int H,
-                      Cell *rows_out, int lane) {
-  // the predecessor of position 0 is the all-ones row on its band (prefix[0] / suffix[R])
-  int r_old = 0, loaded_hi = 0;
-  load_tab_block(tab, desc, 0, R, lane);
-  __syncthreads();
-  int j = lane;
-  LaneDesc d;
-  int ebs = 0, soff = 0;
-  d.wbs = 0x40000000; d.wbe = -0x40000000; d.ebe = -0x40000000; d.pbs = 0; d.pbe = -1;
-  d.has_wob = 0; d.am = d.aac2 = d.amc2 = d.bm = d.bac2 = d.bmc2 = 0.0;
-  if (j < R) {
-    const FusedParam &f = tab[j & (TABN - 1)];
-    load_desc(d, f);
-    ebs = f.ebs; soff = f.store_off;
-  }
-  const int t_min = __shfl(d.wbs, 0, 64);
-  const FusedParam &lastf = desc[R - 1];
-  const int t_max = lastf.ebe + c * (R - 1);
-  const int n_steps = t_max - t_min + 1;
-  LaneState<MEL> st;
-  st.reset();
-  int i = t_min - c * j;
-  int filled_hi = ((t_min - 1) > 0 ? (t_min - 1) / CH : 0) * CH;
-  auto fill = [&](int upto) {
-    while (upto >= filled_hi) {
-      __syncthreads();
-      for (int w = lane; w < CH; w += 64) {
-        int idx = filled_hi + w;
-        int src = mirror ? (N - 1 - idx) : idx;
-        ring[idx & RM] = (idx >= 0 && idx < N) ? sig[src] : 0.0;
-      }
-      filled_hi += CH;
-      __syncthreads();
-    }
-  };
-  fill(t_min);
-  int su = 0, sr = ((-c) % H + H) % H;
-  for (int u = 0; u < n_steps; ++u) {
-    const int t = t_min + u;
-    bool fin = (j < R) && (i > d.ebe);
-    if (__any(fin)) {
-      int nj = j + 64;
-      if (__any(fin && nj < R && (nj >> 6) > loaded_hi)) {
-        loaded_hi++;
-        load_tab_block(tab, desc, loaded_hi, R, lane);
-        __syncthreads();
-      }
-      if (fin) {
-        j = nj;
-        i -= 64 * c;
-        st.reset();
-        if (j < R) {
-          const FusedParam &f = tab[j & (TABN - 1)];
-          load_desc(d, f);
-          ebs = f.ebs; soff = f.store_off;
-        } else {
-          d.wbs = 0x40000000; d.wbe = -0x40000000; d.ebe = -0x40000000;
-        }
-      }
-      while (r_old < R && __shfl(j, r_old & 63, 64) != r_old) r_old++;
-    }
-    if (r_old < R) fill(t - c * r_old);
-    const bool on = (j < R) && (i >= d.wbs) && (i <= d.ebe);
-    const int hs = sr * 64 + ((lane - 1) & 63);
-    X pred{hist_m[hs], hist_e[hs]};
-    pred = xm::sel(i >= d.pbs && i <= d.pbe, pred, xm::zero());
-    if (j == 0) pred = xm::sel(i >= d.pbs && i <= d.pbe, xm::one(), xm::zero());
-    X en = fused_step<MEL>(d, st, i, ring[(i - 1) & RM], pred, on);
-    hist_m[su * 64 + lane] = en.m;
-    hist_e[su * 64 + lane] = en.e;
-    if (on && i >= ebs) {  // row-major store, un-mirrored cell index
-      int off = soff + (mirror ? (d.ebe - i) : (i - ebs));
-      cell_put(rows_out + off, en);
-    }
-    i += 1;
-    su = (su + 1 == H) ? 0 : su + 1;
-    sr = (sr + 1 == H) ? 0 : sr + 1;
-    WAVE_SYNC();
-  }
-}
-
-// The same sweep with the arithmetic of the fast hypothesis phase: lazy sums, one table density per
-// lane; the mixture's other component is the left neighbour's own density at the same cell, which the
-// neighbour evaluated c steps earlier and hands over through the LDS ring together with its emitting
-// value (24 B per lane and slot).
-// what a fast-sweep lane needs of a FusedParam (48 B instead of 80 B in the LDS window)
+// One sweep over the R fused positions of `desc` (prefix order or mirrored suffix order), with the arithmetic of
+// the hypothesis phase: lazy sums, one table density per lane; the mixture's other component is the left
+// neighbour's own density at the same cell, which the neighbour evaluated c steps earlier and hands over through
+// the LDS ring together with its emitting value (24 B per lane and slot).
+// what a sweep lane needs of a FusedParam (48 B instead of 80 B in the LDS window)
 struct __attribute__((aligned(16))) SweepLane {
   double bm, bac, bmc;  // the emitting Gaussian, constants scaled for dens::density
   int32_t wbs, wbe, ebe, ebs, soff, has_wob;
@@ -549,15 +395,14 @@ __device__ void sweep_fast(const FusedParam *desc, int R, int N, int c, const do
   }
 }
 
-template <int MEL, bool FAST, int GL>
+template <int MEL, int GL>
 __global__ __launch_bounds__(64, 3) void ell_kernel(EllArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double *etab = reinterpret_cast<double *>(smem);
   double *ring = etab + dens::ETN;
-  FusedParam *tab = reinterpret_cast<FusedParam *>(ring + g.SR);
-  double *hist_m = FAST ? reinterpret_cast<double *>(reinterpret_cast<SweepLane *>(tab) + TABN)
-                        : reinterpret_cast<double *>(tab + TABN);
-  double *hist_g = hist_m + (size_t)g.H * 64;  // (fast sweeps) the lanes' own densities
+  SweepLane *tab = reinterpret_cast<SweepLane *>(ring + g.SR);
+  double *hist_m = reinterpret_cast<double *>(tab + TABN);
+  double *hist_g = hist_m + (size_t)g.H * 64;  // the lanes' own densities
   int *hist_e = reinterpret_cast<int *>(hist_g + (size_t)g.H * 64);
   int *s_read = hist_e + (size_t)g.H * 64 * 2;
 
@@ -617,25 +462,18 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(EllArgs g) {
       cell_put(suf + rowoff[R] + x - bs[R], xm::one());
     }
     // ---- A, B: the two sweeps
-    if (FAST) {
-      SweepLane *ltab = reinterpret_cast<SweepLane *>(tab);  // same window, smaller entries
-      if (c == 1) {
-        sweep_fast<MEL, true>(g.pl.fwd + m.row_off, R, N, c, sig, false, ring, RM, ltab, etab, hist_m, hist_g,
-                              hist_e, g.H, pre, lane);
-        __syncthreads();
-        sweep_fast<MEL, true>(g.pl.rev + m.row_off, R, N, c, sig, true, ring, RM, ltab, etab, hist_m, hist_g,
-                              hist_e, g.H, suf, lane);
-      } else {
-        sweep_fast<MEL, false>(g.pl.fwd + m.row_off, R, N, c, sig, false, ring, RM, ltab, etab, hist_m, hist_g,
-                               hist_e, g.H, pre, lane);
-        __syncthreads();
-        sweep_fast<MEL, false>(g.pl.rev + m.row_off, R, N, c, sig, true, ring, RM, ltab, etab, hist_m, hist_g,
-                               hist_e, g.H, suf, lane);
-      }
-    } else {
-      sweep<MEL>(g.pl.fwd + m.row_off, R, N, c, sig, false, ring, RM, tab, hist_m, hist_e, g.H, pre, lane);
+    if (c == 1) {
+      sweep_fast<MEL, true>(g.pl.fwd + m.row_off, R, N, c, sig, false, ring, RM, tab, etab, hist_m, hist_g, hist_e,
+                            g.H, pre, lane);
       __syncthreads();
-      sweep<MEL>(g.pl.rev + m.row_off, R, N, c, sig, true, ring, RM, tab, hist_m, hist_e, g.H, suf, lane);
+      sweep_fast<MEL, true>(g.pl.rev + m.row_off, R, N, c, sig, true, ring, RM, tab, etab, hist_m, hist_g, hist_e,
+                            g.H, suf, lane);
+    } else {
+      sweep_fast<MEL, false>(g.pl.fwd + m.row_off, R, N, c, sig, false, ring, RM, tab, etab, hist_m, hist_g, hist_e,
+                             g.H, pre, lane);
+      __syncthreads();
+      sweep_fast<MEL, false>(g.pl.rev + m.row_off, R, N, c, sig, true, ring, RM, tab, etab, hist_m, hist_g, hist_e,
+                             g.H, suf, lane);
     }
     __syncthreads();
 
@@ -657,146 +495,11 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(EllArgs g) {
     const int back = dm.k - dm.central - 1, fwd = dm.central;
     const int n_items = R * (alpha - 1);
     const int grp = lane / GL, gl = lane % GL;
-    if (FAST) {
-      // lane roles in a group: 0 = density of the k-mer before `first` (only feeds the mixture of the
-      // first position), 1..npos = the positions first..last, npos+1 = the closing lane.
-      // Lane role rho is at cell i = base + u - rho at step u, so whatever lane rho-1 produced at step
-      // u-1 (emitting value, density) belongs to the cell lane rho works on at step u.
-      const int smax = 2 * (int)g.half - 1;
-      for (int b0 = 0; b0 < n_items; b0 += 64 / GL) {
-        const int item = b0 + grp;
-        const bool valid = item < n_items;
-        int p = 0, b = 0, first = 0, last = 0, npos = 0;
-        if (valid) {
-          p = item / (alpha - 1);
-          int bi = item % (alpha - 1);
-          b = bi + (bi >= ref[p] ? 1 : 0);
-          first = max(0, p - back);
-          last = min(R - 1, p + fwd);
-          npos = last - first + 1;
-        }
-        const bool is_pos = valid && gl >= 1 && gl <= npos;
-        const bool is_fin = valid && gl == npos + 1;
-        HypDesc d;
-        d.wbs = 0x40000000; d.wbe = -0x40000000; d.elo = 0x40000000; d.ebe = -0x40000000;
-        d.has_wob = 0; d.bm = 0.0; d.bac = 0.0; d.bmc = 0.0;
-        // input stream of the lane: cell i lives at pre[sbase + i] (the suffix rows follow the
-        // prefix rows in the same store, g.half cells on), valid for i in [slo, shi]; every other cell
-        // reads the store's zero cell
-        int sbase = 0, slo = 0x40000000, shi = -0x40000000;
-        int64_t idb = -1;
-        if (valid && gl == 0) {
-          if (first > 0 && g.wobbling) idb = kmer_id_mod(dm, ref, R, cb, nb, ca, na, first - 1, p, b);
-          // this lane also carries prefix[first] to the first position: its rows are empty, so what it keeps as
-          // "emitting value" is the alternative of the band select — its stream at the cell it is on, which is
-          // the cell the lane to its right works on one step later
-          sbase = rowoff[first] - bs[first];
-          slo = bs[first]; shi = be[first];
-        } else if (is_pos) {
-          const int j = first + gl - 1;
-          idb = kmer_id_mod(dm, ref, R, cb, nb, ca, na, j, p, b);
-          d.has_wob = (j > 0 && g.wobbling) ? 1 : 0;
-          d.wbs = bs[j]; d.wbe = be[j]; d.ebe = be[j + 1];
-        } else if (is_fin) {
-          // closing lane: optional wobble row on band `last` (quirk), predecessor = emitting row of
-          // position `last` on band last+1; then the running total against suffix[last+1]
-          d.has_wob = (last + 1 < R && g.wobbling) ? 1 : 0;
-          if (d.has_wob) {
-            idb = kmer_id_mod(dm, ref, R, cb, nb, ca, na, last + 1, p, b);
-            // band `last`; the emitting row of `last` only exists from bs[last+1] on, and nothing
-            // can be in the wobble row before its first value arrives
-            d.wbs = max(bs[last], bs[last + 1]); d.wbe = be[last];
-          } else {
-            d.wbs = bs[last + 1]; d.wbe = be[last + 1];
-          }
-          d.ebe = d.wbe;
-          sbase = (int)g.half + rowoff[last + 1] - bs[last + 1];
-          slo = bs[last + 1]; shi = be[last + 1];
-        }
-        if (idb >= 0) {
-          d.bm = dm.mean[idb];
-          dens::scale_consts(dm.ac[idb], dm.mc[idb], d.bac, d.bmc);
-        }
-        d.elo = max(d.wbs, MEL);
-        d.wmul = d.has_wob ? EXPM2_D : 0.0;
-        d.wexp = d.has_wob ? 0 : xm::XZ;
-        const int base = valid ? bs[first] : 0;
-        int steps = 0;
-        if (is_fin) steps = d.wbe - base + gl + 1;
-        for (int dlt = 32; dlt >= 1; dlt >>= 1) steps = max(steps, __shfl_xor(steps, dlt, 64));
-        steps = __builtin_amdgcn_readfirstlane(steps);  // uniform trip count
-        const int i0 = base - gl;
-        // clamped, unsigned element offsets from uniform base pointers (scalar base + 32-bit offset)
-        // byte offset of the stream's cell i from the slot's (scalar) base; the store's zero cell outside the band
-        const int sb16 = 16 * sbase;
-        auto sload = [&](int i) {
-          const unsigned off = (unsigned)((i >= slo && i <= shi) ? sb16 + 16 * i : 16 * smax);
-          return cell_get(reinterpret_cast<const Cell *>(reinterpret_cast<const char *>(pre) + off));
-        };
-        // sample s[i-1] of cell i, clamped into the read (cells beyond it are outside every band): a byte offset
-        // from the read's uniform base pointer, one v_med3 per load
-        const int xhi = 8 * (N - 1);
-        auto xload = [&](int i) {
-          int off;
-          asm("v_med3_i32 %0, %1, 0, %2" : "=v"(off) : "v"(8 * (i - 1)), "s"(xhi));
-          return *reinterpret_cast<const double *>(sig_u + (unsigned)off);
-        };
-        LaneState<MEL> st;
-        st.reset();
-        X acc = xm::zero(), gb_last = xm::one();
-        double cx[PF];
-        X cs[PF];
-#pragma unroll
-        for (int q = 0; q < PF; q++) {
-          cx[q] = xload(i0 + q);
-          cs[q] = sload(i0 + q);
-        }
-        // a trip = lcm(PF, MEL + 1) steps, unrolled: prefetch slot and history slot of every step are constants.
-        // The steps are rounded up to whole trips (the extra cells lie beyond every band: zeros, zero cell).
-        // (min event length 4: 20 steps per trip are more than the register allocator survives; that variant
-        // keeps PF steps per trip and shifts its history)
-        constexpr int M = MEL + 1;
-        constexpr bool RING = (PF % M == 0) || PF * M <= 12;
-        constexpr int TRIP = (!RING || PF % M == 0) ? PF : PF * M;
-        constexpr int NRM = (11 / TRIP + 1) * TRIP;  // steps between mantissa normalisations: whole trips, >= 12
-        for (int ub = 0; ub < steps; ub += TRIP) {
-#pragma unroll
-          for (int w = 0; w < TRIP; w++) {
-            const int q = w % PF, r = w % M;
-            const int u = ub + w;
-            const int i = i0 + u;
-            const X sv = cs[q];  // zero outside the stream's band (zero cell)
-            const X ga = dpp_shr1(gb_last);
-            // the emitting row of the lane to the left, one step ago: zero beyond its last cell, and only taken
-            // from the wobble row's first cell on; for the first position that lane is role 0, which hands
-            // prefix[first] over.  Outside its emitting row a lane keeps `sv` instead of a zero: the zero cell for
-            // every position lane (they have no stream), the stream for role 0, and nobody reads the closing lane's
-            const X pred = dpp_shr1(st.em);
-            const X gb = density_x(cx[q], d.bm, d.bac, d.bmc, etab);
-            if constexpr (RING)
-              fused_step_ring<MEL>(d, st, r, i, gb, ga, pred, sv);
-            else
-              (void)fused_step_fast<MEL>(d, st, i, gb, ga, pred, sv);
-            gb_last = gb;
-            // node.cpp:31-37; only the closing lane's total is used (the other lanes sum garbage)
-            acc = add_lazy(acc, xm::mul(st.wq[RING ? r : 0], sv));
-            cx[q] = xload(i0 + u + PF);
-            cs[q] = sload(i0 + u + PF);
-          }
-          if ((ub + TRIP) % NRM == 0) {  // keep the lazily summed mantissas near 1
-#pragma unroll
-            for (int k = 0; k <= MEL; k++) st.wq[k] = xm::norm(st.wq[k]);
-            st.em = xm::norm(st.em);
-            acc = xm::norm(acc);
-          }
-        }
-        if (is_fin) {
-          acc = xm::norm(acc);
-          if (RING && acc.e < xm::XZ / 2) acc = xm::zero();  // made of nothing but out-of-band values (fused_step_ring)
-          out[(size_t)p * alpha + b] = xm::to_log(acc);
-        }
-      }
-    } else {
+    // lane roles in a group: 0 = density of the k-mer before `first` (only feeds the mixture of the
+    // first position), 1..npos = the positions first..last, npos+1 = the closing lane.
+    // Lane role rho is at cell i = base + u - rho at step u, so whatever lane rho-1 produced at step
+    // u-1 (emitting value, density) belongs to the cell lane rho works on at step u.
+    const int smax = 2 * (int)g.half - 1;
     for (int b0 = 0; b0 < n_items; b0 += 64 / GL) {
       const int item = b0 + grp;
       const bool valid = item < n_items;
@@ -809,106 +512,126 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(EllArgs g) {
         last = min(R - 1, p + fwd);
         npos = last - first + 1;
       }
-      // role of this lane inside its group
-      const bool is_pos = valid && gl < npos;
-      const bool is_fin = valid && gl == npos;
-      LaneDesc d;
-      d.wbs = 0x40000000; d.wbe = -0x40000000; d.ebe = -0x40000000; d.pbs = 0; d.pbe = -1;
-      d.has_wob = 0; d.am = d.aac2 = d.amc2 = d.bm = d.bac2 = d.bmc2 = 0.0;
-      // input stream of the lane: prefix[first] for the group's first lane, suffix[last+1] for
-      // the closing lane; index of cell i in the row store = sbase + i, valid for i in [slo, shi]
-      const Cell *sc = pre;
+      const bool is_pos = valid && gl >= 1 && gl <= npos;
+      const bool is_fin = valid && gl == npos + 1;
+      HypDesc d;
+      d.wbs = 0x40000000; d.wbe = -0x40000000; d.elo = 0x40000000; d.ebe = -0x40000000;
+      d.has_wob = 0; d.bm = 0.0; d.bac = 0.0; d.bmc = 0.0;
+      // input stream of the lane: cell i lives at pre[sbase + i] (the suffix rows follow the
+      // prefix rows in the same store, g.half cells on), valid for i in [slo, shi]; every other cell
+      // reads the store's zero cell
       int sbase = 0, slo = 0x40000000, shi = -0x40000000;
-      if (is_pos) {
-        const int j = first + gl;
-        int64_t idb = kmer_id_mod(dm, ref, R, cb, nb, ca, na, j, p, b);
-        d.bm = dm.mean[idb]; d.bac2 = dm.ac[idb] * xm::LOG2E; d.bmc2 = dm.mc[idb] * xm::LOG2E;
+      int64_t idb = -1;
+      if (valid && gl == 0) {
+        if (first > 0 && g.wobbling) idb = kmer_id_mod(dm, ref, R, cb, nb, ca, na, first - 1, p, b);
+        // this lane also carries prefix[first] to the first position: its rows are empty, so what it keeps as
+        // "emitting value" is the alternative of the band select — its stream at the cell it is on, which is
+        // the cell the lane to its right works on one step later
+        sbase = rowoff[first] - bs[first];
+        slo = bs[first]; shi = be[first];
+      } else if (is_pos) {
+        const int j = first + gl - 1;
+        idb = kmer_id_mod(dm, ref, R, cb, nb, ca, na, j, p, b);
         d.has_wob = (j > 0 && g.wobbling) ? 1 : 0;
-        if (d.has_wob) {
-          int64_t ida = kmer_id_mod(dm, ref, R, cb, nb, ca, na, j - 1, p, b);
-          d.am = dm.mean[ida]; d.aac2 = dm.ac[ida] * xm::LOG2E; d.amc2 = dm.mc[ida] * xm::LOG2E;
-        }
         d.wbs = bs[j]; d.wbe = be[j]; d.ebe = be[j + 1];
-        d.pbs = d.wbs; d.pbe = d.wbe;
-        if (gl == 0) {
-          sbase = rowoff[first] - bs[first];
-          slo = bs[first]; shi = be[first];
-        }
       } else if (is_fin) {
         // closing lane: optional wobble row on band `last` (quirk), predecessor = emitting row of
         // position `last` on band last+1; then the running total against suffix[last+1]
         d.has_wob = (last + 1 < R && g.wobbling) ? 1 : 0;
         if (d.has_wob) {
-          int64_t ida = kmer_id_mod(dm, ref, R, cb, nb, ca, na, last, p, b);
-          int64_t idb = kmer_id_mod(dm, ref, R, cb, nb, ca, na, last + 1, p, b);
-          d.am = dm.mean[ida]; d.aac2 = dm.ac[ida] * xm::LOG2E; d.amc2 = dm.mc[ida] * xm::LOG2E;
-          d.bm = dm.mean[idb]; d.bac2 = dm.ac[idb] * xm::LOG2E; d.bmc2 = dm.mc[idb] * xm::LOG2E;
-          d.wbs = bs[last]; d.wbe = be[last];
+          idb = kmer_id_mod(dm, ref, R, cb, nb, ca, na, last + 1, p, b);
+          // band `last`; the emitting row of `last` only exists from bs[last+1] on, and nothing
+          // can be in the wobble row before its first value arrives
+          d.wbs = max(bs[last], bs[last + 1]); d.wbe = be[last];
         } else {
           d.wbs = bs[last + 1]; d.wbe = be[last + 1];
         }
-        d.pbs = bs[last + 1]; d.pbe = be[last + 1];
         d.ebe = d.wbe;
-        sc = suf;
-        sbase = rowoff[last + 1] - bs[last + 1];
+        sbase = (int)g.half + rowoff[last + 1] - bs[last + 1];
         slo = bs[last + 1]; shi = be[last + 1];
       }
-      // group-local wavefront: lane gl is at cell i = base + tau - gl
+      if (idb >= 0) {
+        d.bm = dm.mean[idb];
+        dens::scale_consts(dm.ac[idb], dm.mc[idb], d.bac, d.bmc);
+      }
+      d.elo = max(d.wbs, MEL);
+      d.wmul = d.has_wob ? EXPM2_D : 0.0;
+      d.wexp = d.has_wob ? 0 : xm::XZ;
       const int base = valid ? bs[first] : 0;
       int steps = 0;
       if (is_fin) steps = d.wbe - base + gl + 1;
       for (int dlt = 32; dlt >= 1; dlt >>= 1) steps = max(steps, __shfl_xor(steps, dlt, 64));
+      steps = __builtin_amdgcn_readfirstlane(steps);  // uniform trip count
       const int i0 = base - gl;
-      const int smax = (int)g.half - 1;
+      // clamped, unsigned element offsets from uniform base pointers (scalar base + 32-bit offset)
+      // byte offset of the stream's cell i from the slot's (scalar) base; the store's zero cell outside the band
+      const int sb16 = 16 * sbase;
+      auto sload = [&](int i) {
+        const unsigned off = (unsigned)((i >= slo && i <= shi) ? sb16 + 16 * i : 16 * smax);
+        return cell_get(reinterpret_cast<const Cell *>(reinterpret_cast<const char *>(pre) + off));
+      };
+      // sample s[i-1] of cell i, clamped into the read (cells beyond it are outside every band): a byte offset
+      // from the read's uniform base pointer, one v_med3 per load
+      const int xhi = 8 * (N - 1);
+      auto xload = [&](int i) {
+        int off;
+        asm("v_med3_i32 %0, %1, 0, %2" : "=v"(off) : "v"(8 * (i - 1)), "s"(xhi));
+        return *reinterpret_cast<const double *>(sig_u + (unsigned)off);
+      };
       LaneState<MEL> st;
       st.reset();
-      X acc = xm::zero();
-      // prefetch rings: sample s[i-1] and the lane's input stream at cell i
-      double cx[PF], nx[PF], cm[PF], nm[PF];
-      int ce[PF], ne[PF];
-      auto sidx = [&](int i) { return min(max(sbase + i, 0), smax); };
-      auto xidx = [&](int i) { return min(max(i - 1, 0), N - 1); };
+      X acc = xm::zero(), gb_last = xm::one();
+      double cx[PF];
+      X cs[PF];
 #pragma unroll
       for (int q = 0; q < PF; q++) {
-        cx[q] = sig[xidx(i0 + q)];
-        { const X v = cell_get(sc + sidx(i0 + q)); cm[q] = v.m; ce[q] = v.e; }
+        cx[q] = xload(i0 + q);
+        cs[q] = sload(i0 + q);
       }
-      __syncthreads();
-      for (int ub = 0; ub < steps; ub += PF) {
+      // a trip = lcm(PF, MEL + 1) steps, unrolled: prefetch slot and history slot of every step are constants.
+      // The steps are rounded up to whole trips (the extra cells lie beyond every band: zeros, zero cell).
+      // (min event length 4: 20 steps per trip are more than the register allocator survives; that variant
+      // keeps PF steps per trip and shifts its history)
+      constexpr int M = MEL + 1;
+      constexpr bool RING = (PF % M == 0) || PF * M <= 12;
+      constexpr int TRIP = (!RING || PF % M == 0) ? PF : PF * M;
+      constexpr int NRM = (11 / TRIP + 1) * TRIP;  // steps between mantissa normalisations: whole trips, >= 12
+      for (int ub = 0; ub < steps; ub += TRIP) {
 #pragma unroll
-        for (int q = 0; q < PF; q++) {
-          nx[q] = sig[xidx(i0 + ub + PF + q)];
-          { const X v = cell_get(sc + sidx(i0 + ub + PF + q)); nm[q] = v.m; ne[q] = v.e; }
+        for (int w = 0; w < TRIP; w++) {
+          const int q = w % PF, r = w % M;
+          const int u = ub + w;
+          const int i = i0 + u;
+          const X sv = cs[q];  // zero outside the stream's band (zero cell)
+          const X ga = dpp_shr1(gb_last);
+          // the emitting row of the lane to the left, one step ago: zero beyond its last cell, and only taken
+          // from the wobble row's first cell on; for the first position that lane is role 0, which hands
+          // prefix[first] over.  Outside its emitting row a lane keeps `sv` instead of a zero: the zero cell for
+          // every position lane (they have no stream), the stream for role 0, and nobody reads the closing lane's
+          const X pred = dpp_shr1(st.em);
+          const X gb = density_x(cx[q], d.bm, d.bac, d.bmc, etab);
+          if constexpr (RING)
+            fused_step_ring<MEL>(d, st, r, i, gb, ga, pred, sv);
+          else
+            (void)fused_step_fast<MEL>(d, st, i, gb, ga, pred, sv);
+          gb_last = gb;
+          // node.cpp:31-37; only the closing lane's total is used (the other lanes sum garbage)
+          acc = add_lazy(acc, xm::mul(st.wq[RING ? r : 0], sv));
+          cx[q] = xload(i0 + u + PF);
+          cs[q] = sload(i0 + u + PF);
         }
+        if ((ub + TRIP) % NRM == 0) {  // keep the lazily summed mantissas near 1
 #pragma unroll
-        for (int q = 0; q < PF; q++) {
-          const int u = ub + q;
-          if (u < steps) {
-            const int i = i0 + u;
-            const bool on = (is_pos || is_fin) && i >= d.wbs && i <= d.ebe;
-            X sv{cm[q], ce[q]};
-            sv = xm::sel(i >= slo && i <= shi, sv, xm::zero());
-            // predecessor: neighbour lane's emitting row from the previous step (skew 1)
-            const int hs = ((u + 1) & 1) * 64 + ((lane - 1) & 63);
-            X pred{hist_m[hs], hist_e[hs]};
-            pred = xm::sel(i >= d.pbs && i <= d.pbe, pred, xm::zero());
-            if (gl == 0) pred = sv;  // prefix[first] (already masked to its band)
-            X en = fused_step<MEL>(d, st, i, cx[q], pred, on);
-            hist_m[(u & 1) * 64 + lane] = en.m;
-            hist_e[(u & 1) * 64 + lane] = en.e;
-            if (is_fin) acc = xm::add_norm(acc, xm::mul(st.wq[0], sv));  // node.cpp:31-37
-            WAVE_SYNC();
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < PF; q++) {
-          cx[q] = nx[q];
-          cm[q] = nm[q];
-          ce[q] = ne[q];
+          for (int k = 0; k <= MEL; k++) st.wq[k] = xm::norm(st.wq[k]);
+          st.em = xm::norm(st.em);
+          acc = xm::norm(acc);
         }
       }
-      if (is_fin) out[(size_t)p * alpha + b] = xm::to_log(acc);
-    }
+      if (is_fin) {
+        acc = xm::norm(acc);
+        if (RING && acc.e < xm::XZ / 2) acc = xm::zero();  // made of nothing but out-of-band values (fused_step_ring)
+        out[(size_t)p * alpha + b] = xm::to_log(acc);
+      }
     }
     // a read without any valid path has likelihood zero everywhere (the reference returns an
     // all -inf matrix, which its estimator then turns into NaN): report it per read instead
@@ -926,15 +649,11 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
     nvk_set_error("min_event_length %d outside the compiled range 0..4", mel);
     return NVK_ERR_UNSUPPORTED;
   }
-  if (dm.k + 1 > 16) {
-    nvk_set_error("k-mer size %d needs %d lanes per hypothesis, compiled limit is 16", dm.k, dm.k + 1);
+  if (dm.k + 2 > 16) {
+    nvk_set_error("k-mer size %d needs k + 2 = %d lanes per hypothesis, compiled limit is 16", dm.k, dm.k + 2);
     return NVK_ERR_UNSUPPORTED;
   }
-  // default: the fast variant; NADAVCA_ELL_KERNEL=1 (or a k-mer too long for its lane layout)
-  // selects the original formulation
-  const char *force = getenv("NADAVCA_ELL_KERNEL");
-  const bool fast = !(force && force[0] == '1') && dm.k + 2 <= 16;
-  const bool wide_groups = fast ? (dm.k + 2 > 8) : (dm.k + 1 > 8);  // 16 lanes per hypothesis instead of 8
+  const bool wide_groups = dm.k + 2 > 8;  // 16 lanes per hypothesis instead of 8
   // rings sized by the largest skew of the batch that still fits 160 KB of LDS; a read beyond that gets
   // NVK_READ_TOO_WIDE and the others complete
   int H = 2, SR = 256;
@@ -943,7 +662,7 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
     SR = 256;
     while (SR < 64 * cc + CH) SR <<= 1;
     return (size_t)dens::ETN * 8 + (size_t)SR * 8 +
-           (size_t)TABN * (fast ? sizeof(SweepLane) : sizeof(FusedParam)) + (size_t)H * 64 * 24 + 16;
+           (size_t)TABN * sizeof(SweepLane) + (size_t)H * 64 * 24 + 16;
   };
   int c = tot.max_c < 1 ? 1 : tot.max_c;
   while (c > 1 && lds_for(c) > 160 * 1024) c--;
@@ -991,13 +710,8 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
   g.out_status = out_status;
   ctx->last_spill_bytes = (int64_t)tot.cells * 24 * 2;
 
-  void (*kern_fast)(EllArgs) = nullptr;
-  void (*kern_exact)(EllArgs) = nullptr;
-#define ELL_PICK(M)                                                                              \
-  do {                                                                                           \
-    if (wide_groups) { kern_fast = ell_kernel<M, true, 16>; kern_exact = ell_kernel<M, false, 16>; } \
-    else { kern_fast = ell_kernel<M, true, 8>; kern_exact = ell_kernel<M, false, 8>; }           \
-  } while (0)
+  void (*kern)(EllArgs) = nullptr;
+#define ELL_PICK(M) (kern = wide_groups ? ell_kernel<M, 16> : ell_kernel<M, 8>)
   switch (mel) {
     case 0: ELL_PICK(0); break;
     case 1: ELL_PICK(1); break;
@@ -1007,12 +721,11 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
   }
 #undef ELL_PICK
   if (lds > 64 * 1024) {
-    NVK_HIP(hipFuncSetAttribute((const void *)kern_fast, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    NVK_HIP(hipFuncSetAttribute((const void *)kern_exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    NVK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
   {
     TimerScope ts(ctx, NVK_K_ELL_HYP);
-    hipLaunchKernelGGL(fast ? kern_fast : kern_exact, dim3((unsigned)slots), dim3(64), lds, ctx->stream, g);
+    hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(64), lds, ctx->stream, g);
   }
   NVK_HIP(hipGetLastError());
   return NVK_OK;

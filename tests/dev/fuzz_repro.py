@@ -14,7 +14,7 @@ model, k, central, alphabet, mel, bw, cases, tr, w = (fb[x] for x in ('model', '
 mg = dtw.KmerModel(*model); mo = o.KmerModel(*model)
 reads = reads_of(cases)
 print('k', k, 'central', central, 'alphabet', alphabet, 'sigma', model[4][0], 'mel', mel, 'bw', bw, 'tr', tr, 'w', w, 'reads', len(cases),
-      'variant', os.environ.get('NADAVCA_ALIGN_KERNEL'), os.environ.get('NADAVCA_ELL_KERNEL'))
+      'variant', os.environ.get('NADAVCA_ALIGN_KERNEL'))
 if what in ('both', 'align'):
     got = dtw.refine_alignment_batch(reads, bw, mel, mg, tr)
     for ci, (c, ev) in enumerate(zip(cases, got)):

@@ -116,42 +116,6 @@ def test_ell_config_sized_vs_oracle(dtw, oracle_port):
         assert np.mean(np.argmax(ll, axis=1) == ref) > 0.95
 
 
-def test_ell_exact_variant_matches(golden_config):
-    """NADAVCA_ELL_KERNEL=1 selects the original hypothesis phase (two polynomial densities per lane,
-    LDS hand-over); it must reproduce the fixtures like the default one (child process: the variant is
-    read from the environment at call time)."""
-    import os
-    import subprocess
-    import sys
-    from conftest import ROOT
-    code = r"""
-import sys, numpy as np
-sys.path.insert(0, %r); sys.path.insert(0, %r + "/tests")
-from conftest import GoldenFile
-from nadavca_amd import dtw
-for name in ("dp_tiny.npz", "dp_config.npz"):
-    g = GoldenFile(name)
-    k, c, a, mean, sigma = g.model
-    m = dtw.KmerModel(k, c, a, mean, sigma)
-    groups = {}
-    for case in g.cases:
-        groups.setdefault((int(case["bandwidth"]), int(case["min_event_length"])), []).append(case)
-    for (bw, mel), cases in groups.items():
-        reads = [(x["signal"], x["reference"], x["context_before"], x["context_after"], x["approximate_alignment"]) for x in cases]
-        for w in (0, 1):
-            got = dtw.estimate_log_likelihoods_batch(reads, bw, mel, m, bool(w))
-            for case, ll in zip(cases, got):
-                exp = case["ell_w%%d" %% w]
-                assert np.array_equal(np.isneginf(ll), np.isneginf(exp))
-                fin = np.isfinite(exp)
-                assert np.allclose(ll[fin], exp[fin], rtol=1e-9, atol=1e-9)
-print("ELL-EXACT-OK")
-""" % (ROOT, ROOT)
-    env = dict(os.environ, NADAVCA_ELL_KERNEL='1')
-    p = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0 and 'ELL-EXACT-OK' in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
-
-
 @pytest.mark.parametrize('k,central', [(7, 3), (4, 0), (2, 1), (8, 3), (10, 4), (10, 0)])
 def test_ell_other_kmer_sizes(dtw, oracle_port, k, central):
     """k-mer sizes other than the packaged 6: from k = 7 on a hypothesis takes a group of 16 lanes instead of
@@ -180,6 +144,46 @@ def test_ell_other_kmer_sizes(dtw, oracle_port, k, central):
     for c_, ev in zip(cases, got):
         exp = oracle_port.refine_alignment(c_['signal'], c_['reference'], c_['context_before'], c_['context_after'],
                                            c_['approximate_alignment'], 30, 2, mo, True)
+        assert np.array_equal(ev, exp)
+
+
+def test_ell_kmer_size_limit(dtw, oracle_port):
+    """The compiled range of estimate_log_likelihoods is k-mers up to 14 bases: a hypothesis
+    takes k + 2 lanes, and a group is at most 16.  k = 14 fills the group and agrees with the oracle; k = 15 is
+    refused, and the same model still serves refine_alignment.  Alphabet 2 keeps the tables small."""
+    from nadavca_amd import synthetic, _lib
+
+    def cases_for(model):
+        k = model[0]
+        cases = []
+        for i in range(4):
+            rng = np.random.default_rng([92, k, i])
+            R = int(rng.integers(20, 60))
+            cases.append(synthetic.make_dp_case(rng, model, R=R, bandwidth=25, dwell=(2, 8), jitter=4,
+                                                anchor_density=0.6, with_context=bool(i % 2), trim=3))
+        return cases
+
+    model = synthetic.synth_model_arrays(51, k=14, central=6, alphabet=2)
+    mg = dtw.KmerModel(*model)
+    mo = oracle_port.KmerModel(*model)
+    cases = cases_for(model)
+    for w in (False, True):
+        got = dtw.estimate_log_likelihoods_batch(_reads(cases), 25, 2, mg, w)
+        for c_, ll in zip(cases, got):
+            exp = oracle_port.estimate_log_likelihoods(c_['signal'], c_['reference'], c_['context_before'],
+                                                       c_['context_after'], c_['approximate_alignment'], 25, 2, mo, w)
+            _close(ll, np.asarray(exp))
+
+    model = synthetic.synth_model_arrays(52, k=15, central=7, alphabet=2)
+    mg = dtw.KmerModel(*model)
+    mo = oracle_port.KmerModel(*model)
+    cases = cases_for(model)
+    with pytest.raises(_lib.NadavcaHipError, match='k-mer size 15'):
+        dtw.estimate_log_likelihoods_batch(_reads(cases), 25, 2, mg, True)
+    got = dtw.refine_alignment_batch(_reads(cases), 25, 2, mg, True)
+    for c_, ev in zip(cases, got):
+        exp = oracle_port.refine_alignment(c_['signal'], c_['reference'], c_['context_before'], c_['context_after'],
+                                           c_['approximate_alignment'], 25, 2, mo, True)
         assert np.array_equal(ev, exp)
 
 
