@@ -29,28 +29,38 @@ extern "C" int nvk_device_count(void) {
   return n;
 }
 
+int nvk_alloc(void **p, size_t bytes, bool pinned, const char *what) {
+  const hipError_t e = pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
+  if (e == hipSuccess) return NVK_OK;
+  *p = nullptr;
+  (void)hipGetLastError();  // (handled here: the launch checks that follow must not see it)
+  nvk_set_error("%s of %zu bytes (%s) failed: %s", pinned ? "hipHostMalloc" : "hipMalloc", bytes, what,
+                hipGetErrorString(e));
+  return NVK_ERR_NOMEM;
+}
+
+int nvk_grow(void **p, size_t *cap, size_t bytes, bool pinned, const char *what) {
+  if (bytes <= *cap) return NVK_OK;
+  if (*p) NVK_HIP(pinned ? hipHostFree(*p) : hipFree(*p));
+  *p = nullptr;
+  *cap = 0;
+  size_t want = bytes + bytes / 8 + 4096;
+  if (nvk_alloc(p, want, pinned, what)) {
+    want = bytes;
+    const int rc = nvk_alloc(p, want, pinned, what);
+    if (rc) return rc;
+  }
+  *cap = want;
+  return NVK_OK;
+}
+
 int nvk_ws_reserve(nvk_ctx *ctx, int which, size_t bytes) {
   if (bytes <= ctx->ws_bytes[which]) return NVK_OK;
   if (ctx->ws[which]) {
     NVK_HIP(hipStreamSynchronize(ctx->stream));
     NVK_HIP(hipStreamSynchronize(ctx->stream2));
-    NVK_HIP(hipFree(ctx->ws[which]));
-    ctx->ws[which] = nullptr;
-    ctx->ws_bytes[which] = 0;
   }
-  size_t want = bytes + bytes / 8 + 4096;
-  hipError_t e = hipMalloc(&ctx->ws[which], want);
-  if (e != hipSuccess) {
-    want = bytes;
-    e = hipMalloc(&ctx->ws[which], want);
-  }
-  if (e != hipSuccess) {
-    nvk_set_error("hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(e));
-    ctx->ws[which] = nullptr;
-    return NVK_ERR_NOMEM;
-  }
-  ctx->ws_bytes[which] = want;
-  return NVK_OK;
+  return nvk_grow(&ctx->ws[which], &ctx->ws_bytes[which], bytes, false, "workspace");
 }
 
 int64_t nvk_spill_cap(nvk_ctx *ctx, int which_ws) {
@@ -218,7 +228,10 @@ extern "C" int nvk_last_tie_flags(nvk_ctx *ctx, int64_t n_reads, int32_t *out_fl
     return NVK_ERR_INVALID;
   }
   if (n_reads == 0) return NVK_OK;
-  if (nvk_pipe_tie_flags(ctx, n_reads, out_flags)) return NVK_OK;  // the last call came through pipeline.hip
+  if (ctx->ties_host) {
+    memcpy(out_flags, ctx->ties_host, (size_t)n_reads * sizeof(int32_t));
+    return NVK_OK;
+  }
   NVK_HIP(hipSetDevice(ctx->device));
   NVK_HIP(hipMemcpyAsync(out_flags, ctx->ws[WS_TIES], (size_t)n_reads * sizeof(int32_t), hipMemcpyDeviceToHost,
                          ctx->stream));
@@ -280,12 +293,12 @@ extern "C" int nvk_model_create(nvk_ctx *ctx, int k, int central_position, int a
   memset(m, 0, sizeof *m);
   m->ctx = ctx;
   size_t bytes = (size_t)n * sizeof(double);
-  if (hipMalloc((void **)&m->d_mean, bytes) != hipSuccess ||
-      hipMalloc((void **)&m->d_ac, bytes) != hipSuccess ||
-      hipMalloc((void **)&m->d_mc, bytes) != hipSuccess) {
-    nvk_set_error("nvk_model_create: hipMalloc failed");
+  int rc;
+  if ((rc = nvk_alloc((void **)&m->d_mean, bytes, false, "k-mer table")) ||
+      (rc = nvk_alloc((void **)&m->d_ac, bytes, false, "k-mer table")) ||
+      (rc = nvk_alloc((void **)&m->d_mc, bytes, false, "k-mer table"))) {
     nvk_model_destroy(m);
-    return NVK_ERR_NOMEM;
+    return rc;
   }
   if (hipMemcpy(m->d_mean, mean, bytes, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(m->d_ac, ac.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
@@ -323,32 +336,8 @@ extern "C" int nvk_model_info(const nvk_model *m, int *k, int *central_position,
 }
 
 // ---------------------------------------------------------------------------------------------
-// helpers for the host-pointer flavours
+// argument checks (nvk_internal.h) and helpers
 // ---------------------------------------------------------------------------------------------
-namespace {
-
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-      nvk_set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-      return NVK_ERR_NOMEM;
-    }
-    return NVK_OK;
-  }
-  int upload(const void *src, size_t bytes, hipStream_t s) {
-    int rc = alloc(bytes);
-    if (rc) return rc;
-    if (bytes) NVK_HIP(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s));
-    return NVK_OK;
-  }
-};
-
 int check_offsets(const char *what, const int64_t *off, int64_t n) {
   if (!off) {
     nvk_set_error("%s offsets are NULL", what);
@@ -363,59 +352,6 @@ int check_offsets(const char *what, const int64_t *off, int64_t n) {
       nvk_set_error("%s offsets decrease at read %lld", what, (long long)i);
       return NVK_ERR_INVALID;
     }
-  return NVK_OK;
-}
-
-struct StagedBatch {
-  DevBuf signal, sig_off, ref, ref_off, cb, cb_off, ca, ca_off, anc, anc_off;
-  BatchArgs a;
-};
-
-int stage_batch(nvk_ctx *ctx, int64_t n, const double *signal, const int64_t *sig_off,
-                const int32_t *ref, const int64_t *ref_off, const int32_t *cb,
-                const int64_t *cb_off, const int32_t *ca, const int64_t *ca_off,
-                const int32_t *anc, const int64_t *anc_off, int bandwidth, int mel,
-                bool with_signal, StagedBatch &sb) {
-  int rc;
-  if ((rc = check_offsets("reference", ref_off, n))) return rc;
-  if ((rc = check_offsets("context_before", cb_off, n))) return rc;
-  if ((rc = check_offsets("context_after", ca_off, n))) return rc;
-  if (with_signal) {
-    if ((rc = check_offsets("signal", sig_off, n))) return rc;
-    if ((rc = check_offsets("anchors", anc_off, n))) return rc;
-  }
-  hipStream_t s = ctx->stream;
-  size_t no = (size_t)(n + 1) * sizeof(int64_t);
-  BatchArgs &a = sb.a;
-  memset(&a, 0, sizeof a);
-  a.n_reads = n;
-  a.total_ref = ref_off[n];
-  a.bandwidth = bandwidth;
-  a.mel = mel;
-  if ((rc = sb.ref.upload(ref, (size_t)ref_off[n] * 4, s))) return rc;
-  if ((rc = sb.ref_off.upload(ref_off, no, s))) return rc;
-  if ((rc = sb.cb.upload(cb, (size_t)cb_off[n] * 4, s))) return rc;
-  if ((rc = sb.cb_off.upload(cb_off, no, s))) return rc;
-  if ((rc = sb.ca.upload(ca, (size_t)ca_off[n] * 4, s))) return rc;
-  if ((rc = sb.ca_off.upload(ca_off, no, s))) return rc;
-  a.reference = (const int32_t *)sb.ref.p;
-  a.ref_off = (const int64_t *)sb.ref_off.p;
-  a.ctx_before = (const int32_t *)sb.cb.p;
-  a.cb_off = (const int64_t *)sb.cb_off.p;
-  a.ctx_after = (const int32_t *)sb.ca.p;
-  a.ca_off = (const int64_t *)sb.ca_off.p;
-  if (with_signal) {
-    a.total_signal = sig_off[n];
-    a.total_anchors = anc_off[n];
-    if ((rc = sb.signal.upload(signal, (size_t)sig_off[n] * 8, s))) return rc;
-    if ((rc = sb.sig_off.upload(sig_off, no, s))) return rc;
-    if ((rc = sb.anc.upload(anc, (size_t)anc_off[n] * 8, s))) return rc;
-    if ((rc = sb.anc_off.upload(anc_off, no, s))) return rc;
-    a.signal = (const double *)sb.signal.p;
-    a.sig_off = (const int64_t *)sb.sig_off.p;
-    a.anchors = (const int32_t *)sb.anc.p;
-    a.anc_off = (const int64_t *)sb.anc_off.p;
-  }
   return NVK_OK;
 }
 
@@ -436,6 +372,32 @@ int check_common(nvk_model *model, int64_t n_reads, int bandwidth, int mel) {
     nvk_set_error("min_event_length %d is negative", mel);
     return NVK_ERR_INVALID;
   }
+  return NVK_OK;
+}
+
+namespace {
+
+// The prologue of the two device-pointer operators: their argument checks, the device, and the batch as
+// BatchArgs.  An empty batch passes with nothing more to do.
+int dev_batch(nvk_model *model, int64_t n_reads, int64_t total_signal, int64_t total_ref, int64_t total_anchors,
+              const double *signal, const int64_t *sig_off, const int32_t *reference, const int64_t *ref_off,
+              const int32_t *ctx_before, const int64_t *cb_off, const int32_t *ctx_after, const int64_t *ca_off,
+              const int32_t *anchors, const int64_t *anc_off, int bandwidth, int mel, const int32_t *out_status,
+              BatchArgs &a) {
+  int rc = check_common(model, n_reads, bandwidth, mel);
+  if (rc) return rc;
+  if (mel > 4) {
+    nvk_set_error("min_event_length %d outside the compiled range 0..4", mel);
+    return NVK_ERR_UNSUPPORTED;
+  }
+  if (total_signal < 0 || total_ref < 0 || total_anchors < 0 || !sig_off || !ref_off || !cb_off || !ca_off ||
+      !anc_off || !out_status) {
+    nvk_set_error("negative total or NULL offset/status pointer");
+    return NVK_ERR_INVALID;
+  }
+  NVK_HIP(hipSetDevice(model->ctx->device));
+  a = BatchArgs{n_reads, total_signal, total_ref, total_anchors, signal, sig_off, reference, ref_off,
+                ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, mel};
   return NVK_OK;
 }
 
@@ -463,18 +425,9 @@ int plan_batch(nvk_model *model, const BatchArgs &a, int mode, int wobbling, Pla
   if ((rc = nvk_ws_reserve(ctx, WS_LANE_R, (size_t)(rows_total + 1) * 48))) return rc;
   if ((rc = nvk_ws_reserve(ctx, WS_OFFS, (size_t)(rows_total + 1) * sizeof(int32_t)))) return rc;
   if ((rc = nvk_ws_reserve(ctx, WS_STEPS, (size_t)(n + 1) * sizeof(int32_t)))) return rc;
-  const size_t hbytes = sizeof(PlanHost) + (size_t)n * sizeof(int32_t);
-  if (hbytes > ctx->h_plan_cap) {
-    if (ctx->h_plan) (void)hipHostFree(ctx->h_plan);
-    ctx->h_plan = nullptr;
-    ctx->h_plan_cap = 0;
-    if (hipHostMalloc(&ctx->h_plan, hbytes + hbytes / 4, hipHostMallocDefault) != hipSuccess) {
-      ctx->h_plan = nullptr;
-      nvk_set_error("hipHostMalloc of %zu bytes failed", hbytes);
-      return NVK_ERR_NOMEM;
-    }
-    ctx->h_plan_cap = hbytes + hbytes / 4;
-  }
+  if ((rc = nvk_grow(&ctx->h_plan, &ctx->h_plan_cap, sizeof(PlanHost) + (size_t)n * sizeof(int32_t), true,
+                     "planner results")))
+    return rc;
   PlanHost *hp = (PlanHost *)ctx->h_plan;
   PlanTotals *d_tot = (PlanTotals *)((char *)ctx->ws[WS_MISC] + 64);
   rc = launch_plan(ctx, model->dm, a, mode, wobbling, (ReadMeta *)ctx->ws[WS_META],
@@ -526,18 +479,25 @@ extern "C" int nvk_expected_signal_batch(nvk_model *model, int64_t n_reads,
   if (rc) return rc;
   nvk_ctx *ctx = model->ctx;
   NVK_HIP(hipSetDevice(ctx->device));
-  StagedBatch sb;
-  rc = stage_batch(ctx, n_reads, nullptr, nullptr, reference, ref_off, ctx_before, cb_off,
-                   ctx_after, ca_off, nullptr, nullptr, 0, 0, false, sb);
+  if ((rc = check_offsets("reference", ref_off, n_reads))) return rc;
+  if ((rc = check_offsets("context_before", cb_off, n_reads))) return rc;
+  if ((rc = check_offsets("context_after", ca_off, n_reads))) return rc;
+  hipStream_t s = ctx->stream;
+  const size_t no = (size_t)(n_reads + 1) * sizeof(int64_t);
+  const int64_t total_ref = ref_off[n_reads];
+  NvkTmp d_ref, d_ref_off, d_cb, d_cb_off, d_ca, d_ca_off, d_out;
+  if ((rc = d_ref.up(reference, (size_t)total_ref * 4, s))) return rc;
+  if ((rc = d_ref_off.up(ref_off, no, s))) return rc;
+  if ((rc = d_cb.up(ctx_before, (size_t)cb_off[n_reads] * 4, s))) return rc;
+  if ((rc = d_cb_off.up(cb_off, no, s))) return rc;
+  if ((rc = d_ca.up(ctx_after, (size_t)ca_off[n_reads] * 4, s))) return rc;
+  if ((rc = d_ca_off.up(ca_off, no, s))) return rc;
+  if ((rc = d_out.up(nullptr, (size_t)total_ref * 8, s))) return rc;
+  rc = launch_expected(ctx, model->dm, n_reads, total_ref, (const int32_t *)d_ref.p, (const int64_t *)d_ref_off.p,
+                       (const int32_t *)d_cb.p, (const int64_t *)d_cb_off.p, (const int32_t *)d_ca.p,
+                       (const int64_t *)d_ca_off.p, (double *)d_out.p);
   if (rc) return rc;
-  DevBuf d_out;
-  if ((rc = d_out.alloc((size_t)sb.a.total_ref * 8))) return rc;
-  rc = launch_expected(ctx, model->dm, n_reads, sb.a.total_ref, sb.a.reference, sb.a.ref_off,
-                       sb.a.ctx_before, sb.a.cb_off, sb.a.ctx_after, sb.a.ca_off, (double *)d_out.p);
-  if (rc) return rc;
-  if (sb.a.total_ref)
-    NVK_HIP(hipMemcpyAsync(out, d_out.p, (size_t)sb.a.total_ref * 8, hipMemcpyDeviceToHost,
-                           ctx->stream));
+  if (total_ref) NVK_HIP(hipMemcpyAsync(out, d_out.p, (size_t)total_ref * 8, hipMemcpyDeviceToHost, s));
   NVK_HIP(hipStreamSynchronize(ctx->stream));
   return NVK_OK;
 }
@@ -552,38 +512,12 @@ extern "C" int nvk_refine_alignment_batch_dev(
     const int32_t *ctx_after, const int64_t *ca_off, const int32_t *anchors,
     const int64_t *anc_off, int bandwidth, int min_event_length, int model_transitions,
     int32_t *out_events, int32_t *out_status) {
-  int rc = check_common(model, n_reads, bandwidth, min_event_length);
-  if (rc) return rc;
-  if (min_event_length > 4) {
-    nvk_set_error("min_event_length %d outside the compiled range 0..4", min_event_length);
-    return NVK_ERR_UNSUPPORTED;
-  }
-  if (total_signal < 0 || total_ref < 0 || total_anchors < 0 || !sig_off || !ref_off || !cb_off || !ca_off ||
-      !anc_off || !out_status) {
-    nvk_set_error("negative total or NULL offset/status pointer");
-    return NVK_ERR_INVALID;
-  }
-  nvk_ctx *ctx = model->ctx;
-  NVK_HIP(hipSetDevice(ctx->device));
-  if (n_reads == 0) return NVK_OK;
   BatchArgs a;
-  memset(&a, 0, sizeof a);
-  a.n_reads = n_reads;
-  a.total_signal = total_signal;
-  a.total_ref = total_ref;
-  a.total_anchors = total_anchors;
-  a.signal = signal;
-  a.sig_off = sig_off;
-  a.reference = reference;
-  a.ref_off = ref_off;
-  a.ctx_before = ctx_before;
-  a.cb_off = cb_off;
-  a.ctx_after = ctx_after;
-  a.ca_off = ca_off;
-  a.anchors = anchors;
-  a.anc_off = anc_off;
-  a.bandwidth = bandwidth;
-  a.mel = min_event_length;
+  int rc = dev_batch(model, n_reads, total_signal, total_ref, total_anchors, signal, sig_off, reference, ref_off,
+                     ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
+                     out_status, a);
+  if (rc || n_reads == 0) return rc;
+  nvk_ctx *ctx = model->ctx;
   PlanTotals tot;
   // two implementations of the same operator with identical results (both parity-tested):
   //   default                  kernels_align3.hip (plain doubles, wave-uniform scale) with
@@ -592,7 +526,6 @@ extern "C" int nvk_refine_alignment_batch_dev(
   const char *force = getenv("NADAVCA_ALIGN_KERNEL");
   ctx->last_retries = 0;
   ctx->last_ties = ctx->last_ties_exact = ctx->last_ties_near = ctx->last_ties_ulp = 0;
-  nvk_pipe_forget_ties(ctx);
   const int *order = nullptr;
   const int32_t *steps_sorted = nullptr;
   rc = plan_batch(model, a, model_transitions ? PLAN_ALIGN_TRANS : PLAN_ALIGN_PLAIN, 0, tot, &order, &steps_sorted);
@@ -601,6 +534,7 @@ extern "C" int nvk_refine_alignment_batch_dev(
   if ((rc = nvk_ws_reserve(ctx, WS_TIES, (size_t)(n_reads + 8) * sizeof(int32_t)))) return rc;
   NVK_HIP(hipMemsetAsync(ctx->ws[WS_TIES], 0, (size_t)(n_reads + 8) * sizeof(int32_t), ctx->stream));
   ctx->ties_n = n_reads;
+  ctx->ties_host = nullptr;
   int32_t *d_ties = (int32_t *)ctx->ws[WS_TIES];
   int *d_retry = (int *)(d_ties + n_reads + 4);
   const ReadMeta *metas = (const ReadMeta *)ctx->ws[WS_META];
@@ -652,39 +586,12 @@ extern "C" int nvk_estimate_log_likelihoods_batch_dev(
     const int32_t *ctx_after, const int64_t *ca_off, const int32_t *anchors,
     const int64_t *anc_off, int bandwidth, int min_event_length, int model_wobbling,
     double *out_ll, int32_t *out_status) {
-  int rc = check_common(model, n_reads, bandwidth, min_event_length);
-  if (rc) return rc;
-  if (min_event_length > 4) {
-    nvk_set_error("min_event_length %d outside the compiled range 0..4", min_event_length);
-    return NVK_ERR_UNSUPPORTED;
-  }
-  if (total_signal < 0 || total_ref < 0 || total_anchors < 0 || !sig_off || !ref_off || !cb_off || !ca_off ||
-      !anc_off || !out_status) {
-    nvk_set_error("negative total or NULL offset/status pointer");
-    return NVK_ERR_INVALID;
-  }
-  nvk_ctx *ctx = model->ctx;
-  NVK_HIP(hipSetDevice(ctx->device));
-  if (n_reads == 0) return NVK_OK;
   BatchArgs a;
-  memset(&a, 0, sizeof a);
-  a.n_reads = n_reads;
-  a.total_signal = total_signal;
-  a.total_ref = total_ref;
-  a.total_anchors = total_anchors;
-  a.signal = signal;
-  a.sig_off = sig_off;
-  a.reference = reference;
-  a.ref_off = ref_off;
-  a.ctx_before = ctx_before;
-  a.cb_off = cb_off;
-  a.ctx_after = ctx_after;
-  a.ca_off = ca_off;
-  a.anchors = anchors;
-  a.anc_off = anc_off;
-  a.bandwidth = bandwidth;
-  a.mel = min_event_length;
-
+  int rc = dev_batch(model, n_reads, total_signal, total_ref, total_anchors, signal, sig_off, reference, ref_off,
+                     ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
+                     out_status, a);
+  if (rc || n_reads == 0) return rc;
+  nvk_ctx *ctx = model->ctx;
   const int64_t n = n_reads, nrow = total_ref + n;
   if ((rc = nvk_ws_reserve(ctx, WS_META, (size_t)(n + 1) * sizeof(ReadMeta) + 64))) return rc;
   if ((rc = nvk_ws_reserve(ctx, WS_ROWS, (size_t)(total_ref + 1) * sizeof(FusedParam)))) return rc;

@@ -157,24 +157,7 @@ extern "C" int nvk_posterior_segments_dev(nvk_ctx *ctx, int64_t len, int64_t n_s
   return NVK_OK;
 }
 
-// ---- host-pointer conveniences -------------------------------------------------------------------
-namespace {
-struct Tmp {
-  void *p = nullptr;
-  ~Tmp() { if (p) (void)hipFree(p); }
-  int up(const void *src, size_t bytes, hipStream_t s) {
-    if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) {
-      nvk_set_error("hipMalloc(%zu) failed", bytes);
-      return NVK_ERR_NOMEM;
-    }
-    if (bytes && src && hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s) != hipSuccess) {
-      nvk_set_error("H2D copy failed");
-      return NVK_ERR_HIP;
-    }
-    return NVK_OK;
-  }
-};
-}  // namespace
+// ---- host-pointer conveniences (temporaries: NvkTmp, nvk_internal.h) -------------------------------------
 
 extern "C" int nvk_consensus_accumulate(nvk_ctx *ctx, int64_t n_reads, int alphabet, const double *ll,
                                         const int32_t *reference, const int64_t *ref_off,
@@ -188,7 +171,7 @@ extern "C" int nvk_consensus_accumulate(nvk_ctx *ctx, int64_t n_reads, int alpha
   NVK_HIP(hipSetDevice(ctx->device));
   const int64_t total = n_reads > 0 ? ref_off[n_reads] : 0;
   hipStream_t s = ctx->stream;
-  Tmp d_ll, d_ref, d_off, d_cs, d_rev, d_st, d_acc, d_cov;
+  NvkTmp d_ll, d_ref, d_off, d_cs, d_rev, d_st, d_acc, d_cov;
   int rc;
   if ((rc = d_ll.up(ll, (size_t)total * alphabet * 8, s))) return rc;
   if ((rc = d_ref.up(reference, (size_t)total * 4, s))) return rc;
@@ -216,7 +199,7 @@ extern "C" int nvk_posterior(nvk_ctx *ctx, int64_t len, int64_t n_segments, cons
   if (!ctx) return NVK_ERR_INVALID;
   NVK_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  Tmp d_ll, d_ref, d_out, d_seg;
+  NvkTmp d_ll, d_ref, d_out, d_seg;
   int rc;
   if ((rc = d_ll.up(ll, (size_t)len * alphabet * 8, s))) return rc;
   if ((rc = d_ref.up(reference, (size_t)len * 4, s))) return rc;

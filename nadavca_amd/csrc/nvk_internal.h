@@ -95,7 +95,10 @@ struct nvk_ctx {
   int64_t last_retries;  // reads of the last refine batch redone by the exact kernel
   int64_t last_ties;     // reads of the last refine batch with a path decision inside the tie margin
   int64_t last_ties_exact, last_ties_near, last_ties_ulp;  // ... per class (NVK_TIE_EXACT / _NEAR / _ULP)
-  int64_t ties_n;        // number of reads ws[WS_TIES] describes
+  // the tie flags of the last nvk_refine_alignment_batch[_dev] call (nvk_last_tie_flags): its number of reads, and
+  // where they are: null = on the device in ws[WS_TIES], else the host copy of the pipelined path (pipeline.hip)
+  int64_t ties_n;
+  const int32_t *ties_host;
   int64_t ws_limit;      // nvk_ctx_set_workspace_limit: cap on the sweep kernels' spill workspace (0 = default)
   // one pinned host block the planner's results arrive in with ONE copy + synchronisation per batch: the totals,
   // then the reads' step counts in launch order (refine_alignment; sizes the spill slots)
@@ -115,9 +118,17 @@ struct nvk_model {
 void nvk_set_error(const char *fmt, ...);
 // pipeline.hip
 void nvk_pipe_release(nvk_ctx *ctx);
-int nvk_pipe_tie_flags(nvk_ctx *ctx, int64_t n_reads, int32_t *out_flags);
-void nvk_pipe_forget_ties(nvk_ctx *ctx);
 void nvk_pipe_set_ws_limit(nvk_ctx *ctx, int64_t bytes);
+
+// ----- allocation (api.hip) ------------------------------------------------------------------
+// The one place device (pinned = false) and pinned host memory is allocated.  A failure leaves *p null, sets the
+// error text (naming `what`), clears the thread's HIP last error — so that the launch checks after it see only
+// their own errors — and returns NVK_ERR_NOMEM.
+int nvk_alloc(void **p, size_t bytes, bool pinned, const char *what);
+// grow-only buffer: nothing happens if bytes <= *cap; else the old block is freed and bytes + bytes/8 + 4096 are
+// allocated, or exactly bytes if that fails
+int nvk_grow(void **p, size_t *cap, size_t bytes, bool pinned, const char *what);
+// ctx->ws[which] through nvk_grow, after both streams are drained (queued kernels may still use the old block)
 int nvk_ws_reserve(nvk_ctx *ctx, int which, size_t bytes);
 
 struct TimerScope {
@@ -136,6 +147,27 @@ struct TimerScope {
       return NVK_ERR_HIP;                                                              \
     }                                                                                  \
   } while (0)
+
+// scoped temporary device buffer of the host-pointer entry points: max(bytes, 16) bytes, filled from host src
+// (when not null) on stream s, freed when it goes out of scope
+struct NvkTmp {
+  void *p = nullptr;
+  ~NvkTmp() {
+    if (p) (void)hipFree(p);
+  }
+  int up(const void *src, size_t bytes, hipStream_t s) {
+    int rc = nvk_alloc(&p, bytes ? bytes : 16, false, "temporary");
+    if (rc) return rc;
+    if (bytes && src) NVK_HIP(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s));
+    return NVK_OK;
+  }
+};
+
+// ----- argument checks (api.hip) -------------------------------------------------------------
+// off[0..n]: not NULL, starts at 0, never decreases
+int check_offsets(const char *what, const int64_t *off, int64_t n);
+// the model handle and the ranges of n_reads, bandwidth and min_event_length
+int check_common(nvk_model *model, int64_t n_reads, int bandwidth, int mel);
 
 // ----- launchers (kernels_*.hip) ------------------------------------------------------------
 struct BatchArgs {

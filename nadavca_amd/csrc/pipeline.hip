@@ -29,35 +29,6 @@ namespace {
 
 enum { JOB_REFINE = 0, JOB_ELL = 1 };
 
-struct DevGrow {  // grow-only device buffer
-  void *p = nullptr;
-  size_t cap = 0;
-  int reserve(size_t bytes) {
-    if (bytes <= cap) return NVK_OK;
-    if (p) {
-      (void)hipFree(p);
-      p = nullptr;
-      cap = 0;
-    }
-    size_t want = bytes + bytes / 4 + 4096;
-    if (hipMalloc(&p, want) != hipSuccess) {
-      want = bytes;
-      if (hipMalloc(&p, want) != hipSuccess) {
-        p = nullptr;
-        nvk_set_error("hipMalloc of %zu staging bytes failed", want);
-        return NVK_ERR_NOMEM;
-      }
-    }
-    cap = want;
-    return NVK_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
 struct Job {
   int kind = JOB_REFINE;
   int64_t n = 0, total_signal = 0, total_ref = 0, total_anchors = 0;
@@ -87,8 +58,10 @@ struct Lane {
   hipEvent_t uploaded = nullptr;
   // Device staging: the signal on its own (the bulk: one pageable copy), everything else — the five offset
   // arrays rebased to the chunk, reference, contexts, anchors — packed into ONE pinned host buffer and sent with
-  // one asynchronous copy (ten small pageable copies cost ~0.4 ms of fixed overhead per chunk)
-  DevGrow signal, pack, out_a, out_st;
+  // one asynchronous copy (ten small pageable copies cost ~0.4 ms of fixed overhead per chunk).  All grow-only
+  // (nvk_grow), with their capacities in *_cap.
+  void *signal = nullptr, *pack = nullptr, *out_a = nullptr, *out_st = nullptr;
+  size_t signal_cap = 0, pack_cap = 0, out_a_cap = 0, out_st_cap = 0;
   void *hpack = nullptr;   // pinned host image of `pack`
   size_t hpack_cap = 0;
   size_t at[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // byte offsets inside the pack: sig_off, ref_off, cb_off, ca_off, anc_off, ref, cb, ca, anc
@@ -112,8 +85,7 @@ struct nvk_pipe_state {
   int n_lanes = 0;
   Lane *lanes = nullptr;
   hipStream_t copy_in = nullptr, copy_out = nullptr;
-  std::vector<int32_t> ties;  // tie flags of the last refine call that came through here
-  int64_t ties_n = -1;
+  std::vector<int32_t> ties;  // tie flags of the last refine call that came through here (nvk_ctx::ties_host)
 };
 
 namespace {
@@ -127,8 +99,8 @@ void lane_run(Lane *L, Job *j) {
       rc = NVK_ERR_HIP;
       break;
     }
-    const double *d_sig = (const double *)L->signal.p;
-    const char *pk = (const char *)L->pack.p;
+    const double *d_sig = (const double *)L->signal;
+    const char *pk = (const char *)L->pack;
     const int64_t *d_so = (const int64_t *)(pk + L->at[0]), *d_ro = (const int64_t *)(pk + L->at[1]);
     const int64_t *d_bo = (const int64_t *)(pk + L->at[2]), *d_ao = (const int64_t *)(pk + L->at[3]);
     const int64_t *d_no = (const int64_t *)(pk + L->at[4]);
@@ -136,14 +108,14 @@ void lane_run(Lane *L, Job *j) {
     const int32_t *d_ca = (const int32_t *)(pk + L->at[7]), *d_anc = (const int32_t *)(pk + L->at[8]);
     if (j->kind == JOB_REFINE) {
       const size_t evb = (size_t)j->total_ref * 2 * 4;
-      if (hipMemsetAsync(L->out_a.p, 0, evb ? evb : 16, c->stream) != hipSuccess) {
+      if (hipMemsetAsync(L->out_a, 0, evb ? evb : 16, c->stream) != hipSuccess) {
         nvk_set_error("hipMemsetAsync failed");
         rc = NVK_ERR_HIP;
         break;
       }
       rc = nvk_refine_alignment_batch_dev(&L->model, j->n, j->total_signal, j->total_ref, j->total_anchors, d_sig,
                                           d_so, d_ref, d_ro, d_cb, d_bo, d_ca, d_ao, d_anc, d_no, j->bandwidth,
-                                          j->mel, j->flag, (int32_t *)L->out_a.p, (int32_t *)L->out_st.p);
+                                          j->mel, j->flag, (int32_t *)L->out_a, (int32_t *)L->out_st);
       if (rc) break;
       j->retries = c->last_retries;
       if (j->out_ties && j->n > 0) {  // (tiny: 4 B per read; the lane's stream is idle here)
@@ -157,7 +129,7 @@ void lane_run(Lane *L, Job *j) {
       }
     } else {
       const size_t llb = (size_t)j->total_ref * L->alphabet * 8;
-      if (hipMemsetAsync(L->out_a.p, 0, llb ? llb : 16, c->stream) != hipSuccess) {
+      if (hipMemsetAsync(L->out_a, 0, llb ? llb : 16, c->stream) != hipSuccess) {
         nvk_set_error("hipMemsetAsync failed");
         rc = NVK_ERR_HIP;
         break;
@@ -165,7 +137,7 @@ void lane_run(Lane *L, Job *j) {
       rc = nvk_estimate_log_likelihoods_batch_dev(&L->model, j->n, j->total_signal, j->total_ref,
                                                   j->total_anchors, d_sig, d_so, d_ref, d_ro, d_cb, d_bo, d_ca,
                                                   d_ao, d_anc, d_no, j->bandwidth, j->mel, j->flag,
-                                                  (double *)L->out_a.p, (int32_t *)L->out_st.p);
+                                                  (double *)L->out_a, (int32_t *)L->out_st);
       if (rc) break;
     }
     j->cells = c->last_cells;
@@ -206,8 +178,8 @@ void pipe_destroy(nvk_pipe_state *p) {
       L.cv.notify_all();
       L.th.join();
     }
-    DevGrow *bufs[] = {&L.signal, &L.pack, &L.out_a, &L.out_st};
-    for (DevGrow *b : bufs) b->release();
+    for (void *b : {L.signal, L.pack, L.out_a, L.out_st})
+      if (b) (void)hipFree(b);
     if (L.hpack) (void)hipHostFree(L.hpack);
     if (L.uploaded) (void)hipEventDestroy(L.uploaded);
     if (L.ctx) nvk_ctx_destroy(L.ctx);
@@ -293,13 +265,13 @@ int lane_collect(nvk_pipe_state *p, Lane &L, nvk_ctx *main_ctx) {
   }
   if (j.kind == JOB_REFINE) {
     const size_t evb = (size_t)j.total_ref * 2 * 4;
-    if (evb) NVK_HIP(hipMemcpyAsync(j.out_events, L.out_a.p, evb, hipMemcpyDeviceToHost, p->copy_out));
+    if (evb) NVK_HIP(hipMemcpyAsync(j.out_events, L.out_a, evb, hipMemcpyDeviceToHost, p->copy_out));
     main_ctx->last_retries += j.retries;
   } else {
     const size_t llb = (size_t)j.total_ref * L.alphabet * 8;
-    if (llb) NVK_HIP(hipMemcpyAsync(j.out_ll, L.out_a.p, llb, hipMemcpyDeviceToHost, p->copy_out));
+    if (llb) NVK_HIP(hipMemcpyAsync(j.out_ll, L.out_a, llb, hipMemcpyDeviceToHost, p->copy_out));
   }
-  NVK_HIP(hipMemcpyAsync(j.out_status, L.out_st.p, (size_t)j.n * 4, hipMemcpyDeviceToHost, p->copy_out));
+  NVK_HIP(hipMemcpyAsync(j.out_status, L.out_st, (size_t)j.n * 4, hipMemcpyDeviceToHost, p->copy_out));
   NVK_HIP(hipStreamSynchronize(p->copy_out));
   main_ctx->last_cells += j.cells;
   main_ctx->last_steps += j.steps;
@@ -340,18 +312,7 @@ int lane_submit(nvk_pipe_state *p, Lane &L, const nvk_model *model, const HostBa
     if (sizes[q] == 0) total += 64;
   }
   int rc;
-  if (total > L.hpack_cap) {
-    if (L.hpack) (void)hipHostFree(L.hpack);
-    L.hpack = nullptr;
-    L.hpack_cap = 0;
-    const size_t want = total + total / 4 + 4096;
-    if (hipHostMalloc(&L.hpack, want, hipHostMallocDefault) != hipSuccess) {
-      L.hpack = nullptr;
-      nvk_set_error("hipHostMalloc of %zu bytes failed", want);
-      return NVK_ERR_NOMEM;
-    }
-    L.hpack_cap = want;
-  }
+  if ((rc = nvk_grow(&L.hpack, &L.hpack_cap, total, true, "lane staging"))) return rc;
   char *hp = (char *)L.hpack;
   for (int q = 0; q < 5; q++) {  // offsets rebased to the chunk
     int64_t *dst = (int64_t *)(hp + L.at[q]);
@@ -362,13 +323,13 @@ int lane_submit(nvk_pipe_state *p, Lane &L, const nvk_model *model, const HostBa
   if (tb) memcpy(hp + L.at[6], h.cb + h.cb_off[a], (size_t)tb * 4);
   if (ta) memcpy(hp + L.at[7], h.ca + h.ca_off[a], (size_t)ta * 4);
   if (tn) memcpy(hp + L.at[8], h.anc + 2 * h.anc_off[a], (size_t)tn * 8);
-  if ((rc = L.pack.reserve(total))) return rc;
-  NVK_HIP(hipMemcpyAsync(L.pack.p, L.hpack, total, hipMemcpyHostToDevice, p->copy_in));
-  if ((rc = L.signal.reserve(ts ? (size_t)ts * 8 : 16))) return rc;
-  if (ts) NVK_HIP(hipMemcpyAsync(L.signal.p, h.signal + h.sig_off[a], (size_t)ts * 8, hipMemcpyHostToDevice, p->copy_in));
+  if ((rc = nvk_grow(&L.pack, &L.pack_cap, total, false, "lane staging"))) return rc;
+  NVK_HIP(hipMemcpyAsync(L.pack, L.hpack, total, hipMemcpyHostToDevice, p->copy_in));
+  if ((rc = nvk_grow(&L.signal, &L.signal_cap, ts ? (size_t)ts * 8 : 16, false, "lane staging"))) return rc;
+  if (ts) NVK_HIP(hipMemcpyAsync(L.signal, h.signal + h.sig_off[a], (size_t)ts * 8, hipMemcpyHostToDevice, p->copy_in));
   const size_t outb = (kind == JOB_REFINE) ? (size_t)tr * 2 * 4 : (size_t)tr * L.alphabet * 8;
-  if ((rc = L.out_a.reserve(outb ? outb : 16))) return rc;
-  if ((rc = L.out_st.reserve((size_t)n * 4 + 16))) return rc;
+  if ((rc = nvk_grow(&L.out_a, &L.out_a_cap, outb ? outb : 16, false, "lane staging"))) return rc;
+  if ((rc = nvk_grow(&L.out_st, &L.out_st_cap, (size_t)n * 4 + 16, false, "lane staging"))) return rc;
   NVK_HIP(hipEventRecord(L.uploaded, p->copy_in));
   {
     std::lock_guard<std::mutex> g(L.mu);
@@ -393,54 +354,20 @@ int lane_submit(nvk_pipe_state *p, Lane &L, const nvk_model *model, const HostBa
   return NVK_OK;
 }
 
-int check_offsets(const char *what, const int64_t *off, int64_t n) {
-  if (!off) {
-    nvk_set_error("%s offsets are NULL", what);
-    return NVK_ERR_INVALID;
-  }
-  if (off[0] != 0) {
-    nvk_set_error("%s offsets must start at 0", what);
-    return NVK_ERR_INVALID;
-  }
-  for (int64_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) {
-      nvk_set_error("%s offsets decrease at read %lld", what, (long long)i);
-      return NVK_ERR_INVALID;
-    }
-  return NVK_OK;
-}
-
-int validate(nvk_model *model, int kind, int64_t n_reads, const HostBatch &h, int bandwidth, int mel,
-             const void *out_main, const int32_t *out_status) {
-  if (!model) {
-    nvk_set_error("model handle is NULL");
-    return NVK_ERR_INVALID;
-  }
-  if (n_reads < 0 || n_reads > 0x7fffffff) {
-    nvk_set_error("n_reads %lld out of range", (long long)n_reads);
-    return NVK_ERR_INVALID;
-  }
-  if (bandwidth < 0 || bandwidth > (1 << 28)) {
-    nvk_set_error("bandwidth %d out of range", bandwidth);
-    return NVK_ERR_INVALID;
-  }
-  if (mel < 0) {
-    nvk_set_error("min_event_length %d is negative", mel);
-    return NVK_ERR_INVALID;
-  }
-  if (n_reads == 0) return NVK_OK;
+// the checks of the host-pointer entry points
+int validate(nvk_model *model, int64_t n_reads, const HostBatch &h, int bandwidth, int mel, const void *out_main,
+             const int32_t *out_status) {
+  int rc = check_common(model, n_reads, bandwidth, mel);
+  if (rc || n_reads == 0) return rc;
   if (!out_status || !out_main) {
     nvk_set_error("output pointer is NULL");
     return NVK_ERR_INVALID;
   }
-  int rc;
   if ((rc = check_offsets("signal", h.sig_off, n_reads))) return rc;
   if ((rc = check_offsets("reference", h.ref_off, n_reads))) return rc;
   if ((rc = check_offsets("context_before", h.cb_off, n_reads))) return rc;
   if ((rc = check_offsets("context_after", h.ca_off, n_reads))) return rc;
-  if ((rc = check_offsets("anchors", h.anc_off, n_reads))) return rc;
-  (void)kind;
-  return NVK_OK;
+  return check_offsets("anchors", h.anc_off, n_reads);
 }
 
 // results of lane L's job to the caller; its verdict is remembered under its ticket
@@ -467,7 +394,7 @@ int collect_ticketed(nvk_pipe_state *p, Lane &L, nvk_ctx *ctx) {
 
 int run_pipelined(nvk_model *model, int kind, int64_t n_reads, const HostBatch &h, int bandwidth, int mel,
                   int flag, int32_t *out_events, double *out_ll, int32_t *out_status) {
-  int rc = validate(model, kind, n_reads, h, bandwidth, mel,
+  int rc = validate(model, n_reads, h, bandwidth, mel,
                     kind == JOB_REFINE ? (const void *)out_events : (const void *)out_ll, out_status);
   if (rc || n_reads == 0) return rc;
   nvk_ctx *ctx = model->ctx;
@@ -480,13 +407,13 @@ int run_pipelined(nvk_model *model, int kind, int64_t n_reads, const HostBatch &
   ctx->last_retries = 0;
   int32_t *ties = nullptr;
   if (kind == JOB_REFINE) {
+    ctx->ties_n = -1;  // (p->ties is about to change)
     try {
       p->ties.assign((size_t)n_reads, 0);
     } catch (const std::bad_alloc &) {
       nvk_set_error("out of host memory");
       return NVK_ERR_NOMEM;
     }
-    p->ties_n = -1;
     ties = p->ties.data();
   }
   // Chunks.  What a single call can hide is bounded by its first upload (nothing to compute yet) and by how
@@ -558,7 +485,7 @@ int run_pipelined(nvk_model *model, int kind, int64_t n_reads, const HostBatch &
     ctx->last_ties_near = nn;
     ctx->last_ties_ulp = nu;
     ctx->ties_n = n_reads;
-    p->ties_n = n_reads;
+    ctx->ties_host = ties;
   }
   return NVK_OK;
 }
@@ -572,19 +499,9 @@ void nvk_pipe_release(nvk_ctx *ctx) {
   }
 }
 
-// tie flags of the last refine call when it came through the pipelined path: 1 = served from the host copy
-int nvk_pipe_tie_flags(nvk_ctx *ctx, int64_t n_reads, int32_t *out_flags) {
-  nvk_pipe_state *p = ctx->pipe;
-  if (!p || p->ties_n != n_reads || p->ties_n < 0) return 0;
-  memcpy(out_flags, p->ties.data(), (size_t)n_reads * sizeof(int32_t));
-  return 1;
-}
 void nvk_pipe_set_ws_limit(nvk_ctx *ctx, int64_t bytes) {
   if (!ctx || !ctx->pipe) return;
   for (int i = 0; i < ctx->pipe->n_lanes; i++) ctx->pipe->lanes[i].ctx->ws_limit = bytes;
-}
-void nvk_pipe_forget_ties(nvk_ctx *ctx) {
-  if (ctx && ctx->pipe) ctx->pipe->ties_n = -1;
 }
 
 // ---- a stream of batches: upload of batch k+1 and download of batch k-1 behind the kernels of batch k ----------
@@ -602,7 +519,7 @@ extern "C" int nvk_refine_alignment_submit(nvk_model *model, int64_t n_reads, co
     return NVK_ERR_INVALID;
   }
   *ticket = -1;
-  int rc = validate(model, JOB_REFINE, n_reads, h, bandwidth, min_event_length, out_events, out_status);
+  int rc = validate(model, n_reads, h, bandwidth, min_event_length, out_events, out_status);
   if (rc) return rc;
   if (n_reads == 0) {
     nvk_set_error("an empty batch cannot be submitted");
@@ -615,7 +532,6 @@ extern "C" int nvk_refine_alignment_submit(nvk_model *model, int64_t n_reads, co
   const int64_t t = p->next_ticket;
   Lane &L = p->lanes[t % p->n_lanes];
   (void)collect_ticketed(p, L, ctx);  // the batch that used this lane before (its verdict waits under its ticket)
-  nvk_pipe_forget_ties(ctx);
   if ((rc = lane_submit(p, L, model, h, 0, n_reads, JOB_REFINE, bandwidth, min_event_length,
                         model_transitions ? 1 : 0, out_events, nullptr, out_status, out_tie_flags)))
     return rc;

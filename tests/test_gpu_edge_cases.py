@@ -291,9 +291,74 @@ def test_little_free_memory_is_served_in_chunks(dtw):
         ev, st = refine_alignment_dev(db, 150, 2, m, True)
         assert not bool(st.any())
         assert np.array_equal(ev.cpu().numpy(), want)
+        # no cap: the first spill allocation asks for more than is free, fails, and the chunk is halved until one
+        # fits; the handled failure must not surface in the launch checks after it
+        ctx.set_workspace_limit(1 << 40)
+        ev, st = refine_alignment_dev(db, 150, 2, m, True)
+        assert not bool(st.any())
+        assert np.array_equal(ev.cpu().numpy(), want)
     finally:
         del hog
         torch.cuda.empty_cache()
+
+
+def _flat(dtw, b, **replace):
+    arrays = dict(signal=b.signal, sig_off=b.sig_off, reference=b.reference, ref_off=b.ref_off,
+                  context_before=b.context_before, cb_off=b.cb_off, context_after=b.context_after, ca_off=b.ca_off,
+                  anchors=b.anchors, anc_off=b.anc_off)
+    arrays.update(replace)
+    return dtw.FlatBatch.from_arrays(**arrays)
+
+
+def test_stream_form_equals_the_batch_call_and_keeps_the_last_tie_flags(dtw):
+    """nvk_refine_alignment_submit / _wait (dtw.RefineStream) with two batches in flight hand back the events,
+    statuses and tie flags of nvk_refine_alignment_batch on the same batches.  A submit is not a batch call:
+    nvk_last_tie_flags still serves the flags of the last batch call after it (include/nadavca_hip.h)."""
+    from nadavca_amd import synthetic, _lib
+    model = synthetic.load_model_arrays()
+    ctx = _lib.Context(0)
+    m = dtw.KmerModel(*model, context=ctx)
+    flats = [_flat(dtw, synthetic.make_batch(n, model, seed=seed, R=400, R_spread=40, bandwidth=150))
+             for n, seed in ((300, 911), (200, 912), (250, 913))]
+    want = []
+    for f in flats:
+        ev, st = dtw.refine_alignment_flat(f, 150, 2, m, True, on_error='status')
+        want.append((ev, st, ctx.last_tie_flags(f.n)))
+    rs = dtw.RefineStream(m, 150, 2, True)
+    tickets = [rs.submit(flats[0]), rs.submit(flats[1])]
+    got = [rs.wait(tickets[0])]
+    tickets.append(rs.submit(flats[2]))
+    got += [rs.wait(tickets[1]), rs.wait(tickets[2])]
+    for i, (w, g) in enumerate(zip(want, got)):
+        assert all(np.array_equal(a, b) for a, b in zip(w, g)), i
+    assert np.array_equal(ctx.last_tie_flags(flats[2].n), want[2][2])
+
+
+@pytest.mark.parametrize('entry,which', [(e, w) for e in ('refine_alignment_flat', 'estimate_log_likelihoods_flat',
+                                                          'RefineStream.submit')
+                                         for w in ('ref_off', 'sig_off', 'anc_off')]
+                         + [('nvk_expected_signal_batch', 'ref_off')])
+def test_decreasing_offsets_are_refused(dtw, entry, which):
+    """Every host-pointer entry point checks its offset arrays (csrc/api.hip: check_offsets) before it copies."""
+    from nadavca_amd import synthetic, _lib
+    model = synthetic.load_model_arrays()
+    m = dtw.KmerModel(*model)
+    b = synthetic.make_batch(4, model, seed=914, R=120, R_spread=10, bandwidth=60)
+    off = getattr(b, which).copy()
+    off[2] = off[3] + 1
+    flat = _flat(dtw, b, **{which: off})
+    p = dtw._ptr
+    call = {
+        'refine_alignment_flat': lambda: dtw.refine_alignment_flat(flat, 60, 2, m, True),
+        'estimate_log_likelihoods_flat': lambda: dtw.estimate_log_likelihoods_flat(flat, 60, 2, m, True),
+        'RefineStream.submit': lambda: dtw.RefineStream(m, 60, 2, True).submit(flat),
+        'nvk_expected_signal_batch': lambda: _lib.check(_lib.load().nvk_expected_signal_batch(
+            m.handle, flat.n, p(flat.reference), p(flat.ref_off), p(flat.context_before), p(flat.cb_off),
+            p(flat.context_after), p(flat.ca_off), p(np.zeros(b.reference.size))), 'nvk_expected_signal_batch'),
+    }[entry]
+    name = {'ref_off': 'reference', 'sig_off': 'signal', 'anc_off': 'anchors'}[which]
+    with pytest.raises(ValueError, match='%s offsets decrease at read 2' % name):   # (NVK_ERR_INVALID)
+        call()
 
 
 @pytest.mark.parametrize('it,case', [(1630, 2), (2828, 2)])
