@@ -553,8 +553,8 @@ extern "C" int nvk_refine_alignment_batch_dev(
   if (!exact_all) {
     // fast path: plain doubles under a wave-uniform scale (bit-identical while in range);
     // reads it cannot serve come back flagged and are redone by the exact kernel below
-    rc = launch_align3(ctx, a, model_transitions ? 1 : 0, metas, rows, tot, order, steps_sorted, out_events,
-                       out_status, d_retry);
+    rc = launch_align3(ctx, a, model_transitions ? 1 : 0, metas, tot, order, steps_sorted, out_events, out_status,
+                       d_retry);
     if (rc) return rc;
     if ((rc = fetch_counts())) return rc;
     ctx->last_retries = tail[4];

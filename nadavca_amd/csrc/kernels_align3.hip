@@ -35,7 +35,9 @@
 // reads of a chunk, then their forward sweeps (template parameter PHASE: 73 and 115 registers, 24 and 16
 // waves per CU), every read with a spill slot of its own; reads are handed to the persistent waves longest
 // first (launch_order); reads whose band is too wide for one wave's rings (skew above ALIGN1_C_CAP) are swept
-// by teams of four waves (template parameter W, ReadMeta::cw) in a second pair of launches.
+// by teams of four waves (template parameter W, ReadMeta::cw) in a second pair of launches.  The rescale period
+// is compiled in (template parameter RSH): 14 kernels per min event length, the ones a launch can reach
+// (select_sweeps).
 //
 // Time mapping: cell (r, i) is computed at step t = i + off[r] with the planner's per-row offsets
 // (RowParam::off, kernels_plan.hip) instead of one skew per read; a lane record carries the age of the
@@ -52,13 +54,14 @@
 // scalar step offset + constant lane offset) or for the history ring (read index advanced per lane,
 // write address = scalar slot base + constant lane offset); the emission product's row-type select is
 // one FMA with per-row constants; uniform conditions live in scalar registers; no loop end tests (the step
-// count is a multiple of 32) and, with 16 steps per loop trip and the compiled-in rescale period of 16, no
-// test on the step's position in the period; the two rare cases "first row" / "last row" behind one scalar
-// test; the signal ring's refill loaded one chunk ahead; no density re-evaluation at a row switch (the
-// planner keeps the lane idle for the steps on which stale densities pass).  Tried and not kept (DESIGN.md
-// 5.1 has the measurements): 32 forward steps per trip (128 registers), the sample of the next density read
-// one step earlier, update bits shifted in with v_addc, the history-ring read pipelined one step ahead with
-// age-1 values by DPP, lane records prefetched into L2, 5 waves per SIMD in the forward sweep.
+// count is a multiple of 32) and, with 16 steps per loop trip and the rescale period compiled in, no test on
+// the step's position in the period (a period of 32 steps: on the trip's parity); the two rare cases "first
+// row" / "last row" behind one scalar test; the signal ring's refill loaded one chunk ahead; no density
+// re-evaluation at a row switch (the planner keeps the lane idle for the steps on which stale densities
+// pass).  Tried and not kept (DESIGN.md 5.1 has the measurements): 32 forward steps per trip (128 registers),
+// the sample of the next density read one step earlier, update bits shifted in with v_addc, the history-ring
+// read pipelined one step ahead with age-1 values by DPP, lane records prefetched into L2, 5 waves per SIMD in
+// the forward sweep.
 #include <math.h>
 
 #include <new>
@@ -86,7 +89,7 @@ constexpr int RU = 16;      // reverse sweep: steps per loop trip
 constexpr int FT = 16;
 static_assert(FT % PF == 0 && 32 % FT == 0, "forward trip");
 static_assert(32 % PF == 0 && PF % 2 == 0 && 32 % RU == 0 && RU % 2 == 0, "the step count is a multiple of 32 (kernels_plan.hip)");
-// rescale period: 2^rsh steps (launch parameter, >= 16); must exceed c + mel so that at most one
+// rescale period: 2^RSH steps (template parameter RSH, 8, 16 or 32); must exceed c + mel so that at most one
 // rescale lies inside the window a neighbour value travels through
 constexpr int GBIG = 1 << 24;  // scale of an empty running maximum (see the path step)
 // Largest upward move per rescale.  When the wave's largest value collapses by more than this within one
@@ -158,9 +161,8 @@ struct Align3Args {
   const int *order;  // reads in the order they are handed out (longest first), or null
   int H, SR;
   int transitions;
-  int c_lo, c_cap;  // this launch serves reads with c_lo < c <= c_cap
+  int c_cap;        // this launch serves reads with c <= c_cap (its class's skew: ReadMeta::c or ::cw)
   int flag_above;   // ... and hands reads with c > c_cap to the exact kernel (last launch only)
-  int rsh;          // log2 of the rescale period
   int2 *rstate;      // per read (K, suspect) handed from the reverse launch to the forward one
   int read_lo;       // positions [read_lo, read_lo + n_reads) of `order` are served, the spill of
                      // position p lives in slot p - read_lo
@@ -231,8 +233,12 @@ struct Scale {
   int d_next;   // shift of the NEXT step (densities are computed one step ahead)
 };
 
-// RSHC: log2 of the rescale period as a compile-time constant (the usual launch), 0: taken from the
-// launch arguments (wide-band launch)
+// RSH: log2 of the rescale period, 3, 4 or 5 (launch_align3 picks it: the shortest period of at least 16
+// steps, 8 without transition rows, that exceeds c + mel).  Compiled in, it folds the tests on the step's
+// position in the period away.  It divides 32 and so the step count (kernels_plan.hip pads
+// it to a multiple of 32): the reverse sweep's rescale steps, counted from the read's other end, fall on the
+// forward sweep's own.  (The team bands that need a period of 32 steps ran a form with the period taken from
+// the launch arguments; it can be rebuilt from commit db75295.)
 //
 // PAIR (model_transitions): emitting rows and transition rows alternate, so lanes 2m and 2m+1 always hold
 // one of each (64 is even: a lane's rows keep their parity).  A transition row's density is a constant,
@@ -265,9 +271,11 @@ constexpr int LB_REV_TEAM = 6;  // (the team's reverse sweep: 80 registers; 5 an
 // every wave posts its largest exponent one step before the rescale step and all take the maximum.  The
 // ring has one slot more than the oldest age read (c + mel + 1): within one wave "read the oldest slot,
 // then overwrite it" is program order, across waves it would be a race.
-template <int MEL, int RSHC, bool PAIR, int PHASE, int W>
+template <int MEL, int RSH, bool PAIR, int PHASE, int W>
 __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV) : LB) void align3_kernel(Align3Args g) {
   constexpr int TL = 64 * W;  // lanes of the team
+  constexpr int RS = 1 << RSH;  // rescale period (steps)
+  static_assert(32 % RS == 0, "the period must divide the step count, a multiple of 32 (kernels_plan.hip, m.pad)");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int gl = threadIdx.x;  // lane of the team
   const int wv = (W > 1) ? __builtin_amdgcn_readfirstlane(gl >> 6) : 0;
@@ -350,7 +358,6 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
     const int top = T - 1;
     int K = 0;          // true exponent of the largest suffix[0][.]
     bool suspect = false;  // something left the double range: the exact kernel must redo this read
-    const int RSH = RSHC ? RSHC : g.rsh, RS = 1 << RSH;
 
     // =========================== reverse sweep: suffix rows -> spill ===========================
     if (PHASE == 1) {
@@ -816,8 +823,8 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
             // ---- posterior of the cell, on the scale 2^-K:  post = prefix * suffix
             const double suf = (q & 1) ? cur_v[(q % PF) >> 1].y : cur_v[(q % PF) >> 1].x;
             const int ur = n_steps - 1 - u;  // the reverse sweep's step for this anti-diagonal
-            // (a compiled-in period divides n_steps: the reverse sweep's rescale steps are this sweep's age-0 steps)
-            if (RSHC ? (age == 0) : ((ur & (RS - 1)) == RS - 1 || u == 0)) Lrev = sL[ur >> RSH];
+            // (the period divides n_steps: the reverse sweep's rescale steps are this sweep's age-0 steps)
+            if (age == 0) Lrev = sL[ur >> RSH];
             const int kap = -(sc.L + K) - Lrev;  // scalar
             // No band test here: a cell of the lane's warm-up (lo <= i < bs) has suf == 0, because the
             // reverse sweep's lane was idle at this (step, lane) — it leaves row r at bs and the planner
@@ -1052,13 +1059,51 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
   }
 }
 
+typedef void (*Align3Kernel)(Align3Args);
+
+template <int MEL, int RSH, bool PAIR, int W>
+bool set_sweeps(Align3Kernel k[2]) {  // [0] reverse sweeps, [1] forward sweeps
+  k[0] = align3_kernel<MEL, RSH, PAIR, 1, W>;
+  k[1] = align3_kernel<MEL, RSH, PAIR, 2, W>;
+  return true;
+}
+
+// The kernels that are built: one wave per read keeps the base period (see launch_align3), a team takes the
+// period its skew needs.  PAIR (transition rows): the paired variant.  false: no kernel for this combination.
+template <int MEL>
+bool sweeps_of(bool pair, int W, int rsh, Align3Kernel k[2]) {
+  constexpr int TW = ALIGN3_TEAM_W;
+  if (W == 1) {
+    if (pair && rsh == 4) return set_sweeps<MEL, 4, true, 1>(k);
+    if (!pair && rsh == 3) return set_sweeps<MEL, 3, false, 1>(k);
+    return false;
+  }
+  if (W != TW) return false;
+  switch (rsh) {
+    case 3: return !pair && set_sweeps<MEL, 3, false, TW>(k);
+    case 4: return pair ? set_sweeps<MEL, 4, true, TW>(k) : set_sweeps<MEL, 4, false, TW>(k);
+    case 5: return pair ? set_sweeps<MEL, 5, true, TW>(k) : set_sweeps<MEL, 5, false, TW>(k);
+    default: return false;
+  }
+}
+
+bool select_sweeps(int mel, bool pair, int W, int rsh, Align3Kernel k[2]) {
+  switch (mel) {
+    case 0: return sweeps_of<0>(pair, W, rsh, k);
+    case 1: return sweeps_of<1>(pair, W, rsh, k);
+    case 2: return sweeps_of<2>(pair, W, rsh, k);
+    case 3: return sweeps_of<3>(pair, W, rsh, k);
+    case 4: return sweeps_of<4>(pair, W, rsh, k);
+    default: return false;
+  }
+}
+
 }  // namespace
 
-int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadMeta *metas,
-                  const RowParam *rows, const PlanTotals &tot, const int *order, const int32_t *steps_sorted,
-                  int32_t *out_events, int32_t *out_status, int *d_retry) {
+int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadMeta *metas, const PlanTotals &tot,
+                  const int *order, const int32_t *steps_sorted, int32_t *out_events, int32_t *out_status,
+                  int *d_retry) {
   static_assert(WS_OFFS < (int)(sizeof(ctx->ws) / sizeof(ctx->ws[0])), "workspace table too small");
-  (void)rows;  // (the lane records were derived from them by the planner)
   if (a.n_reads == 0) return NVK_OK;
   const int mel = a.mel;
   if (mel < 0 || mel > 4) {
@@ -1072,55 +1117,22 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
   NVK_HIP(hipMemsetAsync(counter, 0, 2 * sizeof(int), ctx->stream));
   NVK_HIP(hipMemsetAsync(d_retry, 0, sizeof(int), ctx->stream));
 
-  // kernels: [0] reverse sweeps, [1] forward sweeps; rescale period 16 compiled in (k16) or taken from the
-  // arguments (kv).  With transition rows: the paired variant (one density evaluation per lane pair and step).
-  void (*k16[2])(Align3Args) = {nullptr, nullptr};
-  void (*kv[2])(Align3Args) = {nullptr, nullptr};
-  void (*kt[2])(Align3Args) = {nullptr, nullptr};  // teams of ALIGN3_TEAM_W waves (wide bands)
-  void (*kt16[2])(Align3Args) = {nullptr, nullptr};  // ... with the rescale period of 16 compiled in
-  // period 8 compiled in: what the sweeps without transition rows use (rsh below); measured on the teams, where a
-  // lockstep step is as long as its longest chain: the compiled-in period folds every test on the step's position
-  // in the period away — forward sweep -16 %, reverse -10 % on BASELINE config 5 reads
-  void (*k8[2])(Align3Args) = {nullptr, nullptr};
-  void (*kt8[2])(Align3Args) = {nullptr, nullptr};
-#define A3_SET(M, P)                                                                           \
-  do {                                                                                         \
-    k16[0] = align3_kernel<M, 4, P, 1, 1>; k16[1] = align3_kernel<M, 4, P, 2, 1>;              \
-    kv[0] = align3_kernel<M, 0, P, 1, 1>; kv[1] = align3_kernel<M, 0, P, 2, 1>;                \
-    kt[0] = align3_kernel<M, 0, P, 1, ALIGN3_TEAM_W>; kt[1] = align3_kernel<M, 0, P, 2, ALIGN3_TEAM_W>; \
-    kt16[0] = align3_kernel<M, 4, P, 1, ALIGN3_TEAM_W>; kt16[1] = align3_kernel<M, 4, P, 2, ALIGN3_TEAM_W>; \
-    if (!P) {                                                                                   \
-      k8[0] = align3_kernel<M, 3, false, 1, 1>; k8[1] = align3_kernel<M, 3, false, 2, 1>;       \
-      kt8[0] = align3_kernel<M, 3, false, 1, ALIGN3_TEAM_W>; kt8[1] = align3_kernel<M, 3, false, 2, ALIGN3_TEAM_W>; \
-    }                                                                                           \
-  } while (0)
-#define A3_PICK(M)                                                                             \
-  do {                                                                                         \
-    if (transitions) A3_SET(M, true); else A3_SET(M, false);                                   \
-  } while (0)
-  switch (mel) {
-    case 0: A3_PICK(0); break;
-    case 1: A3_PICK(1); break;
-    case 2: A3_PICK(2); break;
-    case 3: A3_PICK(3); break;
-    default: A3_PICK(4); break;
-  }
-#undef A3_PICK
-#undef A3_SET
   // Two launches: the LDS rings are sized by the largest skew a launch serves, so the (usual) reads
   // with c <= ALIGN1_C_CAP keep their 16 waves per CU whatever else is in the batch; wide-band reads
   // (long reads, BASELINE config 5) run with larger rings and a longer rescale period.
   // (wide bands: teams of ALIGN3_TEAM_W waves, ReadMeta::cw; their history ring of (cw + mel + 1) slots of
   // 256 lanes x 20 B has to fit the 160 KB of a CU)
-  const int C_HARD = 24;
-  struct Cls { int lo, hi; int W; };
+  constexpr int C_HARD = 24;
+  // (mel <= 4: one wave per read keeps the base period of 8 or 16 steps, a team's stays within 32 — rsh below)
+  static_assert(ALIGN1_C_CAP + 4 < 8 && C_HARD + 4 < 32, "no kernel for the rescale period these skews need");
+  struct Cls { int hi; int W; };
   Cls cls[2];
   int ncls = 0;
   const int64_t n_wide = (int64_t)tot.n_wide;
   const int max_cw = tot.max_cw < 1 ? 1 : tot.max_cw;
   if (a.n_reads - n_wide > 0 || max_c <= ALIGN1_C_CAP)
-    cls[ncls++] = Cls{0, max_c < ALIGN1_C_CAP ? max_c : ALIGN1_C_CAP, 1};
-  if (max_c > ALIGN1_C_CAP) cls[ncls++] = Cls{0, max_cw < C_HARD ? max_cw : C_HARD, ALIGN3_TEAM_W};
+    cls[ncls++] = Cls{max_c < ALIGN1_C_CAP ? max_c : ALIGN1_C_CAP, 1};
+  if (max_c > ALIGN1_C_CAP) cls[ncls++] = Cls{max_cw < C_HARD ? max_cw : C_HARD, ALIGN3_TEAM_W};
   rc = nvk_ws_reserve(ctx, WS_RSTATE, (size_t)a.n_reads * sizeof(int2));
   if (rc) return rc;
   TimerScope ts_align(ctx, NVK_K_ALIGN);
@@ -1143,6 +1155,12 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
     // (a neighbour value is at most c + mel steps old: a period of c + mel + 1 steps already keeps two
     // rescale steps out of its way)
     while ((1 << rsh) <= c + mel) rsh++;
+    Align3Kernel kern[2];
+    if (!select_sweeps(mel, transitions != 0, W, rsh, kern)) {
+      nvk_set_error("no align3 kernel for min_event_length %d, transitions %d, %d waves, rescale period %d", mel,
+                    transitions, W, 1 << rsh);
+      return NVK_ERR_UNSUPPORTED;
+    }
     // history ring: ages 1 .. c+mel are read; the oldest slot is read and then overwritten in the
     // same step (LDS operations of one wave execute in program order)
     // (a team's ring has one slot more: across waves "read the oldest slot, then overwrite it" is a race)
@@ -1176,19 +1194,13 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
     g.H = H;
     g.SR = SR;
     g.transitions = transitions;
-    g.c_lo = cls[k].lo;
     g.c_cap = c;
     g.flag_above = (k == ncls - 1) ? 1 : 0;
-    g.rsh = rsh;
     g.rstate = (int2 *)ctx->ws[WS_RSTATE];
-    g.read_lo = 0;
     g.n_retry = d_retry;
     g.ties = (int32_t *)ctx->ws[WS_TIES];
     g.out_events = out_events;
     g.out_status = out_status;
-    // (a team's skew at stride 256 is small: its rescale period is usually the compiled-in 16, BASELINE config 5: 4 + 2)
-    void (**kern)(Align3Args) = (W > 1) ? ((rsh == 4) ? kt16 : ((rsh == 3 && kt8[0]) ? kt8 : kt))
-                                        : ((rsh == 4) ? k16 : ((rsh == 3 && k8[0]) ? k8 : kv));
     for (int ph = 0; ph < 2; ph++)
       if ((ph == 0 ? lds_rev : lds) > 64 * 1024)
         NVK_HIP(hipFuncSetAttribute((const void *)kern[ph], hipFuncAttributeMaxDynamicSharedMemorySize,

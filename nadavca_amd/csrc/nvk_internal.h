@@ -225,9 +225,9 @@ int launch_align_retry(nvk_ctx *ctx, const BatchArgs &a, int transitions, const 
 // scaled-double kernel (kernels_align3.hip).  order / steps_sorted: launch order (device) and the reads' step counts
 // in that order (host), both from plan_batch; d_retry (device int, zeroed here): reads it hands to the exact kernel.
 // Asynchronous: nothing is waited for.
-int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadMeta *metas,
-                  const RowParam *rows, const PlanTotals &tot, const int *order, const int32_t *steps_sorted,
-                  int32_t *out_events, int32_t *out_status, int *d_retry);
+int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadMeta *metas, const PlanTotals &tot,
+                  const int *order, const int32_t *steps_sorted, int32_t *out_events, int32_t *out_status,
+                  int *d_retry);
 int launch_expected(nvk_ctx *ctx, const DeviceModel &dm, int64_t n_reads, int64_t total_ref,
                     const int32_t *reference, const int64_t *ref_off, const int32_t *cb,
                     const int64_t *cb_off, const int32_t *ca, const int64_t *ca_off, double *out);

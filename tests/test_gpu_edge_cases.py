@@ -124,6 +124,29 @@ def test_mixed_narrow_and_wide_reads_in_one_batch(dtw, oracle_port):
             assert np.array_equal(ev, exp)
 
 
+def test_team_read_beside_a_read_too_wide_for_the_team_rings(dtw, oracle_port):
+    """Exists to reach align3_kernel<2, 5, PAIR, *, 4>: the team sweeps with a rescale period of 32 steps, with and
+    without transition rows.  The team launch sizes its rings by the batch's widest team skew, capped where they fill
+    a CU's LDS (15 at min event length 2).  The first read, 2-3 samples per base under bandwidth 2500, is wider than
+    that: it goes to the exact kernel, which finds it too wide as well.  The rings stay at the cap, a neighbour value
+    can be 17 steps old, and the other read is swept with the period of 32.  (One such read per mode: on bands this
+    wide many reads are handed on to the exact kernel, by the runtime-period form as well.)"""
+    from nadavca_amd import synthetic
+    model = synthetic.load_model_arrays()
+    mg = dtw.KmerModel(*model)
+    mo = oracle_port.KmerModel(*model)
+    case = lambda seed, R, dwell: synthetic.make_dp_case(np.random.default_rng(seed), model, R=R, bandwidth=2500,
+                                                         dwell=dwell, jitter=40, anchor_density=0.5)
+    tup = lambda c: (c['signal'], c['reference'], c['context_before'], c['context_after'], c['approximate_alignment'])
+    wide = case([911, 0], 1500, (2, 3))
+    for tr, c in ((True, case([911, 2], 600, (10, 30))), (False, case([912, 2], 1000, (5, 15)))):
+        out, st = dtw.refine_alignment_batch([tup(wide), tup(c)], 2500, 2, mg, tr, on_error='status',
+                                             return_status=True)
+        assert st.tolist() == [dtw.READ_TOO_WIDE, 0]
+        assert mg.context.last_batch_stats()['reads_redone_exact'] == 1  # the team read was not handed on
+        assert np.array_equal(out[1], oracle_port.refine_alignment(*tup(c), 2500, 2, mo, tr))
+
+
 def _fuzz_batch(seed, it):
     from fuzz_cases import make_fuzz_batch, reads_of
     fb = make_fuzz_batch(seed, it)
