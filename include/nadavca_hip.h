@@ -71,7 +71,8 @@ enum {
   NVK_K_CONSENSUS = 5,   /* normalise + strand flip + scatter-add */
   NVK_K_POSTERIOR = 6,   /* windowed posterior */
   NVK_K_RENORM = 7,      /* normalisation, per-event means, linear re-fit (align_signal's renorm loop) */
-  NVK_K_COUNT = 8
+  NVK_K_METH = 8,        /* pattern occurrences and their scores (detect_meth) */
+  NVK_K_COUNT = 9
 };
 
 const char *nvk_last_error(void); /* thread-local message of the last failing call */
@@ -329,6 +330,34 @@ int nvk_spline_fit_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, const d
  * restated operation for operation: results equal scipy's bit for bit.  out may alias x.  Device pointers. */
 int nvk_splev_groups_dev(nvk_ctx *ctx, int64_t n_groups, const double *x, const int64_t *grp_off,
                          const double *t, const double *c, const int64_t *knot_off, int k, double *out);
+
+/* replaces calculate_meth_scores + maxs3 of detect_meth (the reference's nadavca/detect_meth.py:21-65) for a batch,
+ * in two passes: nvk_meth_count_dev counts, per read, the scorable occurrences of a pattern; the caller turns the
+ * counts into offsets occ_off (exclusive prefix sum, occ_off[0] = 0) and nvk_meth_scores_dev writes them there.
+ * Read j's reference part is reference[ref_off[j] .. ref_off[j+1]) (R_j bases 0..3, in the read's orientation),
+ * with one event mean per base (means, as nvk_event_means_dev writes them: NaN for an empty event and for every
+ * event of a read with status != 0) and one expected level per base (expected, nvk_expected_signal_batch_dev
+ * without contexts).
+ *   occurrence  p with pattern[0 .. pattern_len) == reference part [p .. p + pattern_len), p + pattern_len <= R_j;
+ *               overlapping occurrences count (str.find restarts at pos + 1, detect_meth.py:35-40); pattern_len 0
+ *               makes every position one; a pattern code outside 0..3 never matches
+ *   scorable    p >= 5, p + 5 < R_j and none of the 11 means p-5 .. p+5 is NaN (detect_meth.py:42-50); a read
+ *               with status != 0 has none (status may be NULL: every read counts)
+ *   scores      per event i of the 11: -log(max(1e-50, erfc(z / sqrt 2))), z = |means - expected| / 0.35287208,
+ *               i.e. 2 * Phi(-z) (cdf_scoring, detect_meth.py:23-26)
+ *   aggregate   the largest of the nine sums (s[i] + s[i+1]) + s[i+2] (maxs3, detect_meth.py:63-65)
+ * out_count i64[n_reads].  Occurrence k of read j (ascending position) goes to slot o = occ_off[j] + k:
+ * out_pos[o] = p (position in the reference part), out_scores[11 o .. 11 o + 11), out_aggregate[o]; the outputs hold
+ * occ_off[n_reads] entries; a read gets at most occ_off[j+1] - occ_off[j] of them.  The order is deterministic.
+ * ref_off and occ_off are copied to the host and checked (start at 0, never decrease, ref_off ends at total_ref).
+ * Device pointers. */
+int nvk_meth_count_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, const int32_t *reference,
+                       const int64_t *ref_off, const double *means, const int32_t *status, const int32_t *pattern,
+                       int64_t pattern_len, int64_t *out_count);
+int nvk_meth_scores_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, const int32_t *reference,
+                        const int64_t *ref_off, const double *means, const double *expected, const int32_t *status,
+                        const int32_t *pattern, int64_t pattern_len, const int64_t *occ_off, int64_t *out_pos,
+                        double *out_scores, double *out_aggregate);
 
 #ifdef __cplusplus
 }

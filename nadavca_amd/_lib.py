@@ -28,8 +28,8 @@ TIE_NEAR = 2    # ... two scores closer than 2^-24 relative (beyond the class be
 TIE_PLATEAU = 8  # structural mark: two adjacent bases with the same k-mer level (boundary unidentifiable)
 TIE_ULP = 4     # ... two scores within 64 ulps of the reference's log value, not equal (where its rounding may decide)
 
-K_PLAN, K_ALIGN, K_ELL_SWEEP, K_ELL_HYP, K_EXPECTED, K_CONSENSUS, K_POSTERIOR, K_RENORM = range(8)
-KERNEL_NAMES = ['plan', 'align', 'ell_sweep', 'ell_hyp', 'expected', 'consensus', 'posterior', 'renorm']
+K_PLAN, K_ALIGN, K_ELL_SWEEP, K_ELL_HYP, K_EXPECTED, K_CONSENSUS, K_POSTERIOR, K_RENORM, K_METH = range(9)
+KERNEL_NAMES = ['plan', 'align', 'ell_sweep', 'ell_hyp', 'expected', 'consensus', 'posterior', 'renorm', 'meth']
 
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -77,6 +77,8 @@ SIGNATURES = {
     'nvk_linfit_rescale_dev': (_int, [_vp, _i64] + [_vp] * 7),
     'nvk_splev_groups_dev': (_int, [_vp, _i64] + [_vp] * 5 + [_int, _vp]),
     'nvk_spline_fit_dev': (_int, [_vp, _i64, _i64] + [_vp] * 7),
+    'nvk_meth_count_dev': (_int, [_vp, _i64, _i64] + [_vp] * 5 + [_i64, _vp]),
+    'nvk_meth_scores_dev': (_int, [_vp, _i64, _i64] + [_vp] * 6 + [_i64] + [_vp] * 4),
 }
 
 _lib = None

@@ -101,6 +101,105 @@ def detect_meth(reference_filename, reads, pattern, output, config=defaults.CONF
             out.close()
 
 
+_PATTERN_CODES = {'A': 0, 'C': 1, 'G': 2, 'T': 3}
+_LETTERS = np.frombuffer(b'ACGT', dtype=np.uint8)
+
+
+def pattern_codes(pattern):
+    """``pattern`` as int32 base codes; a character outside ``ACGT`` (lowercase included) becomes -1, which never
+    matches, as ``str.find`` on an upper-case ACGT sequence never finds it."""
+    return np.array([_PATTERN_CODES.get(c, -1) for c in pattern], dtype=np.int32)
+
+
+def contexts_from_codes(codes):
+    """(n, 11) base codes -> n strings of 11 letters (``seq[p-5:p+6]`` of the occurrences), vectorised."""
+    codes = np.asarray(codes).reshape(-1, 2 * FLANK + 1)
+    return _LETTERS[codes].view('S%d' % (2 * FLANK + 1)).reshape(-1).astype('U%d' % (2 * FLANK + 1))
+
+
+class MethBatch:
+    """What ``detect_meth_batch`` returns: one row per scorable pattern occurrence of every read, in read order and
+    ascending position — the rows ``detect_meth`` writes — as flat arrays: ``read`` (index in the ReadBatch),
+    ``position`` (in the read's reference part), ``context`` (``seq[p-5:p+6]``), ``scores`` (n, 11), ``aggregate``
+    (the largest sum of three consecutive scores); and per aligned read (``live``: its index in the ReadBatch) its
+    ``status`` (``_lib.READ_*``; a read with status != 0 has no rows), as in ``AlignedBatch``."""
+
+    def __init__(self, read, position, context, scores, aggregate, status, live):
+        self.read, self.position, self.context = read, position, context
+        self.scores, self.aggregate, self.status, self.live = scores, aggregate, status, live
+
+    @classmethod
+    def empty(cls, status=None, live=None):
+        z = lambda dt: np.zeros(0, dtype=dt)
+        return cls(z(np.int64), z(np.int64), z('U%d' % (2 * FLANK + 1)), np.zeros((0, 2 * FLANK + 1)), z(np.float64),
+                   z(np.int32) if status is None else status, z(np.int64) if live is None else live)
+
+    def __len__(self):
+        return int(self.position.size)
+
+    def write_csv(self, file, names=None):
+        """The CSV ``detect_meth`` writes (header, then one row per occurrence: name, position, context, the 11
+        scores joined by commas, aggregate; floats as ``str`` gives them) to ``file``, a path or a text file.
+        ``names[i]``: the name of ReadBatch read i (default ``'read%d' % i``, as ``detect_meth`` names reads without
+        one)."""
+        out = open(file, 'w', newline='') if isinstance(file, (str, os.PathLike)) else file
+        try:
+            writer = csv.writer(out)
+            writer.writerow(('Filename', 'Position', 'Sequence context', 'Position scores', 'Aggregated score'))
+            name = (lambda i: 'read%d' % i) if names is None else (lambda i: names[i])
+            writer.writerows((name(i), p, c, ','.join(map(str, sc)), a) for i, p, c, sc, a in zip(
+                self.read.tolist(), self.position.tolist(), self.context.tolist(), self.scores.tolist(),
+                self.aggregate.tolist()))
+        finally:
+            if out is not file:
+                out.close()
+
+
+def detect_meth_batch(reference_filename, read_batch, pattern, config=defaults.CONFIG_FILE,
+                      kmer_model=defaults.KMER_MODEL_FILE, renorm_rounds=defaults.RENORM_ROUNDS, aligner=None):
+    """``detect_meth`` for a struct-of-arrays ``ReadBatch`` with no per-read Python: the alignment of
+    ``align_signal_batch`` (the same kernels, the same ``aligner`` contract), then on the device the event means over
+    the signal after the last rescale, the expected levels without contexts and the occurrence scores
+    (include/nadavca_hip.h: nvk_meth_count_dev / nvk_meth_scores_dev), and one copy of the rows to the host.  Reads
+    that did not align produce no rows (``detect_meth`` raises on them) and show in ``status`` / ``live``.
+    -> MethBatch (``write_csv`` gives ``detect_meth``'s CSV)."""
+    import torch
+    from .align_signal import _align_batch_dev, _load_config
+    from .device import event_means_dev, expected_levels_dev, meth_scores_dev, to_host
+    from .kmer_model import KmerModel
+    config = _load_config(config)
+    if isinstance(kmer_model, str):
+        kmer_model = KmerModel.load_from_hdf5(kmer_model)
+    sa, dbatch, events, status, _, _, _ = _align_batch_dev(read_batch, config, kmer_model, renorm_rounds, aligner)
+    if dbatch is None:
+        return MethBatch.empty()
+    context = kmer_model.context
+    live = sa.live.cpu().numpy()
+    # the loop's own means were taken before its last rescale: these are over the final signal (detect_meth.py:106)
+    means = event_means_dev(dbatch, context, events, status)
+    expected = expected_levels_dev(dbatch, kmer_model, with_contexts=False)
+    occ_off, pos, scores, agg = meth_scores_dev(context, dbatch.reference, dbatch.ref_off, means, expected, status,
+                                                pattern_codes(pattern))
+    n_occ = int(pos.numel())
+    if n_occ == 0:
+        return MethBatch.empty(status.cpu().numpy(), live)
+    dev = pos.device
+    owner = torch.repeat_interleave(torch.arange(dbatch.n, dtype=torch.int64, device=dev), occ_off[1:] - occ_off[:-1],
+                                    output_size=n_occ)
+    # the 11 bases around each occurrence, 2 bits each in one integer (exact in a double: 22 bits)
+    first = dbatch.ref_off[:-1][owner] + pos - FLANK
+    shifts = 2 * torch.arange(2 * FLANK, -1, -1, dtype=torch.int64, device=dev)
+    packed = (dbatch.reference[first[:, None] + torch.arange(2 * FLANK + 1, device=dev)].to(torch.int64)
+              << shifts).sum(1)
+    # one device-to-host copy: scores, aggregate, position, read index, packed context as the columns of one table
+    table = to_host(torch.cat([scores, agg[:, None], pos[:, None].double(), sa.live[owner][:, None].double(),
+                               packed[:, None].double()], 1))
+    W = 2 * FLANK + 1
+    codes = (table[:, W + 3].astype(np.int64)[:, None] >> np.arange(2 * (W - 1), -1, -2)) & 3
+    return MethBatch(table[:, W + 2].astype(np.int64), table[:, W + 1].astype(np.int64), contexts_from_codes(codes),
+                     np.ascontiguousarray(table[:, :W]), np.ascontiguousarray(table[:, W]), status.cpu().numpy(), live)
+
+
 def detect_meth_command(args):
     reads = [os.path.join(args.read_basedir, fn) for fn in os.listdir(args.read_basedir) if fn.endswith('.fast5')]
     detect_meth(args.reference, reads, args.pattern, args.output, args.configuration, args.kmer_model,

@@ -273,6 +273,44 @@ def refine_renorm_loop_dev(dbatch, bandwidth, min_event_length, kmer_model, mode
     return events, status, fits
 
 
+def meth_scores_dev(context, reference, ref_off, means, expected, status, pattern):
+    """``calculate_meth_scores`` + ``maxs3`` (detect_meth.py:21-65) for every read of a batch, on the device:
+    the scorable occurrences of ``pattern`` (base codes, a sequence or a tensor; a code outside 0..3 never
+    matches) in the reference parts ``reference`` / ``ref_off`` (int32 / int64 device tensors), scored from the
+    per-base event ``means`` (``event_means_dev``: NaN = empty event) and ``expected`` levels (f64 device tensors,
+    one value per base); ``status``: int32 per read or None.  Count, prefix sum, emit (include/nadavca_hip.h:
+    nvk_meth_count_dev / nvk_meth_scores_dev).
+    -> (occ_off int64 (n+1,), position int64 (n_occ,), scores f64 (n_occ, 11), aggregate f64 (n_occ,)) device
+    tensors; read j's occurrences are [occ_off[j], occ_off[j+1]), in ascending position."""
+    import torch
+    lib = _lib.load()
+    dev = means.device
+    n = int(ref_off.numel()) - 1
+    total_ref = int(means.numel())   # (``reference`` may hold a placeholder element when it is empty)
+    if isinstance(pattern, torch.Tensor):
+        pat = pattern.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    else:
+        pat = torch.from_numpy(np.asarray(pattern, dtype=np.int32).reshape(-1)).to(dev)
+    m = int(pat.numel())
+    if m == 0:
+        pat = torch.zeros(1, dtype=torch.int32, device=dev)
+    st = _dp(status) if status is not None else C.c_void_p(0)
+    count = torch.zeros(max(n, 0), dtype=torch.int64, device=dev)
+    _lib.check(lib.nvk_meth_count_dev(context.handle, n, total_ref, _dp(reference), _dp(ref_off), _dp(means), st,
+                                      _dp(pat), m, _dp(count)), 'nvk_meth_count_dev')
+    occ_off = torch.zeros(max(n, 0) + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(count, 0, out=occ_off[1:])
+    n_occ = int(occ_off[-1])
+    pos = torch.empty(n_occ, dtype=torch.int64, device=dev)
+    scores = torch.empty((n_occ, 11), dtype=torch.float64, device=dev)
+    agg = torch.empty(n_occ, dtype=torch.float64, device=dev)
+    if n_occ:
+        _lib.check(lib.nvk_meth_scores_dev(context.handle, n, total_ref, _dp(reference), _dp(ref_off), _dp(means),
+                                           _dp(expected), st, _dp(pat), m, _dp(occ_off), _dp(pos), _dp(scores),
+                                           _dp(agg)), 'nvk_meth_scores_dev')
+    return occ_off, pos, scores, agg
+
+
 # ---- Chunk score accumulation and posterior, device-resident (estimator.py:199-236) ---------------------
 def consensus_accumulate_dev(context, dbatch, ll, chunk_start, reverse, status, normalization_event_length,
                              ref_len, acc=None, cov=None):
