@@ -72,7 +72,8 @@ enum {
   NVK_K_POSTERIOR = 6,   /* windowed posterior */
   NVK_K_RENORM = 7,      /* normalisation, per-event means, linear re-fit (align_signal's renorm loop) */
   NVK_K_METH = 8,        /* pattern occurrences and their scores (detect_meth) */
-  NVK_K_COUNT = 9
+  NVK_K_SEED = 9,        /* banded local alignment + traceback of the seed aligner (nvk_seed_extend_dev) */
+  NVK_K_COUNT = 10
 };
 
 const char *nvk_last_error(void); /* thread-local message of the last failing call */
@@ -139,7 +140,9 @@ int nvk_last_tie_counts(nvk_ctx *ctx, int64_t *n_exact, int64_t *n_near, int64_t
 int nvk_last_tie_flags(nvk_ctx *ctx, int64_t n_reads, int32_t *out_flags);
 /* Cap, in bytes, on the device memory the sweep kernels take for their per-wave spill (the suffix rows of
  * the reads in flight: 512 B per wavefront step and resident wave).  0 (default): up to 60 % of the memory
- * that is free at the call.  Fewer waves run concurrently when the cap binds; results do not change. */
+ * that is free at the call.  Fewer waves run concurrently when the cap binds; results do not change.
+ * The same cap bounds the traceback store of nvk_seed_extend_dev: when a batch's store is larger, its reads run in
+ * chunks that fit (a single read larger than the cap runs on its own); results do not change. */
 int nvk_ctx_set_workspace_limit(nvk_ctx *ctx, int64_t bytes);
 
 /* replaces dtw.KmerModel(k, central_position, alphabet_size, mean, sigma)
@@ -358,6 +361,37 @@ int nvk_meth_scores_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, const 
                         const int64_t *ref_off, const double *means, const double *expected, const int32_t *status,
                         const int32_t *pattern, int64_t pattern_len, const int64_t *occ_off, int64_t *out_pos,
                         double *out_scores, double *out_aggregate);
+
+/* The extension stage of the seed aligner (nadavca_amd/seedalign.py): per read, a banded affine-gap local alignment
+ * of the query against one strand of the reference, its traceback and the matched pairs.  Read j is
+ * query[q_off[j] .. q_off[j+1]) (m_j base codes); the reference is given forward (ref_len = G codes); strand[j] 0 aligns
+ * it to r = reference, 1 to r[x] = 3 - reference[G-1-x], -1 skips the read; diag[j] is the band centre d*.
+ * Scores: match, mismatch, gap_open, gap_extend in 1..16 (a gap of length l costs gap_open + l * gap_extend).
+ * A base code outside 0..3 on either side is a mismatch.  In int32, NEG = -2^30, O = gap_open + gap_extend,
+ * X = gap_extend:
+ *   cells   (i, j), 0 <= i < m, 0 <= j < G, d* - w <= j - i <= d* + w   (w = band, 1..256)
+ *   D = (i > 0 && j > 0 ? H[i-1][j-1] : 0) + (q[i] == r[j] ? match : -mismatch)
+ *   E = max(H[i][j-1] - O, E[i][j-1] - X) if (i, j-1) is a cell, else NEG     (a step along the reference)
+ *   F = max(H[i-1][j] - O, F[i-1][j] - X) if (i-1, j) is a cell, else NEG     (a step along the read)
+ *   best = max(D, E, F); best <= 0: H = 0, source START; else H = best, source DIAG if D == best, else E if
+ *   E == best, else F.  E-extend bit of (i, j): E[i][j-1] - X > H[i][j-1] - O (opening wins a tie); F alike.
+ *   end cell: largest H, then smallest i, then smallest j; its H is the score.  No cell at all: score 0, end -1.
+ * A read whose score is >= min_score is traced back from its end cell, in state H:
+ *   START: stop.  DIAG: emit (i, j) if q[i] == r[j], step to (i-1, j-1); stop if i or j was 0.
+ *   E / F: go to state E / F at the same cell.  State E at (i, j): j -= 1, then stay in E if the E-extend bit of
+ *   (i, j) before the step was set, else return to H.  State F likewise with i -= 1 and the F-extend bit.
+ * out_hit i32[4 n_reads]: per read (score, i and j of the end cell, pair count).  The pairs, ascending, go to
+ * out_pairs i32[2 total_query] as (i, j) at pair slots q_off[j] .. q_off[j] + count (a read emits at most m_j of
+ * them): i in the read, j on the chosen strand.  A skipped read or one below min_score gets count 0 (its score and
+ * end cell are still written; a skipped read's are 0, -1, -1).
+ * The traceback store takes (2w + 1) / 2 bytes per cell (rounded up to whole strips of 64 rows); its size is bounded
+ * by nvk_ctx_set_workspace_limit's cap.  q_off is copied to the host and checked (starts at 0, never decreases,
+ * ends at total_query, no read above 2^26 bases); ref_len <= 2^30.  NVK_ERR_INVALID for bad arguments,
+ * NVK_ERR_UNSUPPORTED for band > 256.  Device pointers. */
+int nvk_seed_extend_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_query, const int32_t *query,
+                        const int64_t *q_off, const int32_t *reference, int64_t ref_len, const int32_t *strand,
+                        const int32_t *diag, int band, int match, int mismatch, int gap_open, int gap_extend,
+                        int min_score, int32_t *out_hit, int32_t *out_pairs);
 
 #ifdef __cplusplus
 }

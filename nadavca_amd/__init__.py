@@ -8,5 +8,6 @@ does not touch the GPU; every compute entry point goes through the HIP library
 from . import dtw  # noqa: F401
 from .estimate_snps import estimate_snps, estimate_snps_batch  # noqa: F401
 from .align_signal import align_signal, align_signal_batch  # noqa: F401
+from .seedalign import SeedAligner  # noqa: F401
 
-__all__ = ['align_signal', 'align_signal_batch', 'estimate_snps', 'estimate_snps_batch', 'dtw']
+__all__ = ['align_signal', 'align_signal_batch', 'estimate_snps', 'estimate_snps_batch', 'dtw', 'SeedAligner']

@@ -311,6 +311,37 @@ def meth_scores_dev(context, reference, ref_off, means, expected, status, patter
     return occ_off, pos, scores, agg
 
 
+def seed_extend_dev(context, query, q_off, reference, strand, diagonal, band, match, mismatch, gap_open, gap_extend,
+                    min_score):
+    """The extension stage of the seed aligner (nadavca_amd/seedalign.py) for every read of a batch, on the device:
+    banded affine-gap local alignment of read j (``query`` / ``q_off``: int32 codes / int64 offsets) against strand
+    ``strand[j]`` (0 forward, 1 reverse complement, -1 skip) of ``reference`` (int32 codes, forward) around diagonal
+    ``diagonal[j]``, traceback and matched pairs (include/nadavca_hip.h: nvk_seed_extend_dev).  Device tensors.
+    -> (score i32 (n,), end i32 (n, 2), count i32 (n,), pairs i32 (total, 2)); read j's pairs are
+    pairs[q_off[j] : q_off[j] + count[j]], ascending (the other rows are unspecified)."""
+    import torch
+    lib = _lib.load()
+    dev = query.device
+    n = int(q_off.numel()) - 1
+    total = int(query.numel())
+    G = int(reference.numel())
+    i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
+    query, reference, strand, diagonal = i32(query), i32(reference), i32(strand), i32(diagonal)
+    q_off = q_off.to(device=dev, dtype=torch.int64).contiguous()
+    # (a placeholder element where an array is empty: the C-ABI takes no NULL for a batch that has reads)
+    if total == 0:
+        query = torch.zeros(1, dtype=torch.int32, device=dev)
+    if G == 0:
+        reference = torch.zeros(1, dtype=torch.int32, device=dev)
+    hit = torch.zeros((max(n, 0), 4), dtype=torch.int32, device=dev)
+    pairs = torch.empty((max(total, 1), 2), dtype=torch.int32, device=dev)
+    _lib.check(lib.nvk_seed_extend_dev(context.handle, n, total, _dp(query), _dp(q_off), _dp(reference), G,
+                                       _dp(strand), _dp(diagonal), int(band), int(match), int(mismatch),
+                                       int(gap_open), int(gap_extend), int(min_score), _dp(hit), _dp(pairs)),
+               'nvk_seed_extend_dev')
+    return hit[:, 0], hit[:, 1:3], hit[:, 3], pairs[:total]
+
+
 # ---- Chunk score accumulation and posterior, device-resident (estimator.py:199-236) ---------------------
 def consensus_accumulate_dev(context, dbatch, ll, chunk_start, reverse, status, normalization_event_length,
                              ref_len, acc=None, cov=None):

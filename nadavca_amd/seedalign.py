@@ -1,0 +1,239 @@
+"""``SeedAligner`` — a device-resident batch aligner: basecalled reads to matched (read base, reference base) pairs,
+the ``BaseAlignmentBatch`` that ``align_signal_batch``, ``estimate_snps_batch`` and ``detect_meth_batch`` take from
+their ``aligner``, with no BWA and no per-read Python.
+
+It is not BWA and does not reproduce BWA's hits; what it computes is specified exactly, so that a CPU restatement and
+the kernel agree bit for bit.  Scoring defaults to what the reference asks of BWA (``-x ont2d``: match 1, mismatch 1,
+gap open 1, gap extend 1: the reference's nadavca/alignment.py:36), and pairs follow the reference's CIGAR rule:
+only aligned columns whose two bases are equal (alignment.py:118-138, ``alignment._get_base_alignment``).
+
+1. Seeds and vote (torch, on the aligner's device).  Per strand (0: the reference, 1: its reverse complement
+   ``rc[x] = 3 - ref[G-1-x]``) a seed is a pair (i, p) with read k-mer i equal to strand k-mer p; a read k-mer that
+   occurs more than ``max_occ`` times in the strand gives none.  Seed diagonal d = p - i, window c = floor(d / w);
+   window c scores n(c) + n(c+1) seeds (diagonals [c w, (c+2) w)).  Each strand takes its best window (smallest c on a
+   tie), the read its better strand (forward on a tie); below ``min_seeds`` the read is unaligned, else the band
+   centre d* is the lower median of the window's seed diagonals (index (n-1)//2 of them sorted).
+2. Banded affine-gap local alignment around d* and 3. traceback, in the HIP kernel ``nvk_seed_extend_dev``
+   (include/nadavca_hip.h states the rules; nadavca_amd/csrc/kernels_seedext.hip).  A read whose score is below
+   ``min_score`` is unaligned.  There is no CPU form of steps 2 and 3 in the package."""
+import numpy as np
+
+from . import _lib
+from .readbatch import BaseAlignmentBatch
+
+PARAMS = dict(k=14, max_occ=32, band=64, min_seeds=2, match=1, mismatch=1, gap_open=1, gap_extend=1, min_score=30)
+
+
+def _check_params(p):
+    unknown = sorted(set(p) - set(PARAMS))
+    if unknown:
+        raise ValueError('SeedAligner: unknown parameter(s) %s' % ', '.join(unknown))
+    q = dict(PARAMS)
+    q.update(p)
+    ranges = dict(k=(8, 15), max_occ=(1, None), band=(1, 256), min_seeds=(1, None), match=(1, 16),
+                  mismatch=(1, 16), gap_open=(1, 16), gap_extend=(1, 16), min_score=(1, None))
+    for name, (lo, hi) in ranges.items():
+        v = q[name]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+            raise ValueError('SeedAligner: %s = %r is outside %d..%s' % (name, v, lo, hi if hi is not None else ''))
+        q[name] = int(v)
+    return q
+
+
+def _load_reference(reference):
+    import os
+    if isinstance(reference, (str, os.PathLike)):
+        from .genome import Genome
+        records = Genome.load_from_fasta(os.fspath(reference))
+        if len(records) != 1:
+            raise ValueError('SeedAligner: %s holds %d FASTA records, exactly one is supported'
+                             % (os.fspath(reference), len(records)))
+        return np.ascontiguousarray(Genome.to_numerical(records[0].bases), dtype=np.int32)
+    return np.ascontiguousarray(np.asarray(reference).reshape(-1), dtype=np.int32)
+
+
+class SeedHits:
+    """What ``SeedAligner.align`` returns, numpy arrays: per read ``reverse`` (bool: the chosen strand, False for an
+    unaligned read), ``strand`` (int32: 0, 1, or -1 where the seeds did not vote for any), ``diagonal`` (int64 d*,
+    0 without a strand), ``votes`` (int64: the chosen window's seeds), ``score`` (int32), ``end`` (int32 (n, 2): the
+    end cell (i, j), -1 where there was no cell), ``aligned`` (bool); and the pairs of read j,
+    ``read_idx`` / ``ref_idx`` [off[j], off[j+1]), ascending — ``ref_idx`` on the chosen strand, counted from the
+    reference's end on strand 1."""
+
+    def __init__(self, strand, diagonal, votes, score, end, aligned, off, read_idx, ref_idx):
+        self.strand, self.diagonal, self.votes, self.score, self.end = strand, diagonal, votes, score, end
+        self.aligned, self.off, self.read_idx, self.ref_idx = aligned, off, read_idx, ref_idx
+        self.reverse = aligned & (strand == 1)
+
+    @property
+    def n(self):
+        return self.strand.size
+
+    def base_alignments(self):
+        return BaseAlignmentBatch(self.read_idx, self.ref_idx, self.off, self.reverse)
+
+
+class SeedAligner:
+    """``SeedAligner(reference, device=None, **params)``: ``reference`` is base codes 0..3 or the path of a FASTA
+    file with exactly one record; ``params`` as in ``PARAMS`` (``k`` 8..15, ``max_occ`` >= 1, ``band`` (the half-width
+    w, in diagonals) 1..256, ``min_seeds`` >= 1, ``match`` / ``mismatch`` / ``gap_open`` / ``gap_extend`` 1..16 (a
+    gap of length l costs gap_open + l * gap_extend), ``min_score`` >= 1); out of range raises ValueError.
+    ``device``: where the reference, its k-mer index and the seeding live (default: the library's default GPU).  The
+    index of both strands is built once, here.  ``align`` and ``get_base_alignments`` need a GPU device; ``seed``
+    (step 1 alone) runs on any."""
+
+    def __init__(self, reference, device=None, **params):
+        import torch
+        self.params = _check_params(params)
+        self.reference_num = _load_reference(reference)
+        if device is None:
+            device = torch.device('cuda', _lib.default_context().device)
+        self.device = torch.device(device)
+        ref = torch.from_numpy(self.reference_num).to(self.device).to(torch.int64)
+        self._ref = ref.to(torch.int32)
+        G = int(ref.numel())
+        rc = 3 - ref.flip(0) if G else ref
+        self._index = [self._build_index(ref), self._build_index(rc)]
+
+    # ---- step 1 ---------------------------------------------------------------------------------------------
+    def _kmers(self, seq, length):
+        """k-mer codes (2 bits per base) of positions 0 .. length-1 of int64 ``seq`` (which holds at least
+        length + k - 1 elements) and whether all their bases are 0..3."""
+        import torch
+        k = self.params['k']
+        code = torch.zeros(length, dtype=torch.int64, device=self.device)
+        ok = torch.ones(length, dtype=torch.bool, device=self.device)
+        for u in range(k):
+            x = seq[u:u + length]
+            ok &= (x >= 0) & (x <= 3)
+            code = code * 4 + x.clamp(0, 3)
+        return code, ok
+
+    def _build_index(self, strand_seq):
+        import torch
+        n_pos = int(strand_seq.numel()) - self.params['k'] + 1
+        if n_pos <= 0:
+            return (torch.zeros(0, dtype=torch.int64, device=self.device),) * 2
+        code, ok = self._kmers(strand_seq, n_pos)
+        pos = torch.arange(n_pos, dtype=torch.int64, device=self.device)[ok]
+        keys, order = torch.sort(code[ok], stable=True)
+        return keys, pos[order]
+
+    def _check_reads(self, read_batch):
+        seq = read_batch.sequence
+        if seq.size and (int(seq.min()) < 0 or int(seq.max()) > 3):
+            raise ValueError('SeedAligner: read sequences hold base codes outside 0..3')
+
+    def seed(self, read_batch):
+        """Step 1 for every read of ``read_batch``, on the aligner's device: -> (strand int32, diagonal int64,
+        votes int64), torch tensors of n reads; strand -1 (diagonal 0) where the read did not reach ``min_seeds``."""
+        import torch
+        self._check_reads(read_batch)
+        p = self.params
+        k, w, dev, i64 = p['k'], p['band'], self.device, torch.int64
+        n = read_batch.n
+        G = int(self.reference_num.size)
+        q_off = torch.from_numpy(read_batch.seq_off).to(dev)
+        seq = torch.from_numpy(read_batch.sequence).to(dev).to(i64)
+        total = int(seq.numel())
+        lens = q_off[1:] - q_off[:-1]
+        max_m = int(lens.max()) if n else 0
+        owner = torch.repeat_interleave(torch.arange(n, dtype=i64, device=dev), lens, output_size=total)
+        inner = torch.arange(total, dtype=i64, device=dev) - q_off[:-1][owner]
+        code, _ = self._kmers(torch.cat([seq, torch.zeros(k, dtype=i64, device=dev)]), total)
+        starts = torch.nonzero(inner <= lens[owner] - k).reshape(-1)   # read k-mers (codes are checked above)
+        q_code = code[starts]
+        # windows are keyed read * CR + (c + C0): c runs over [-(max_m // w) - 1, (G - 1) // w], so c - 1 and c + 1
+        # stay inside a read's key range
+        C0 = max_m // w + 3
+        CR = C0 + G // w + 3
+        votes, cstar, seeds = [], [], []
+        for keys, pos in self._index:
+            lo = torch.searchsorted(keys, q_code)
+            cnt = torch.searchsorted(keys, q_code, right=True) - lo
+            use = (cnt >= 1) & (cnt <= p['max_occ'])
+            t, lo, cnt = starts[use], lo[use], cnt[use]
+            n_seeds = int(cnt.sum()) if cnt.numel() else 0
+            best = torch.zeros(n, dtype=i64, device=dev)
+            best_c = torch.zeros(n, dtype=i64, device=dev)
+            if n_seeds == 0:
+                votes.append(best)
+                cstar.append(best_c)
+                seeds.append((torch.zeros(0, dtype=i64, device=dev),) * 3)
+                continue
+            sk = torch.repeat_interleave(torch.arange(t.numel(), dtype=i64, device=dev), cnt, output_size=n_seeds)
+            within = torch.arange(n_seeds, dtype=i64, device=dev) - (torch.cumsum(cnt, 0) - cnt)[sk]
+            rd, d = owner[t][sk], pos[lo[sk] + within] - inner[t][sk]
+            c = torch.div(d, w, rounding_mode='floor')
+            uk, un = torch.unique(rd * CR + c + C0, return_counts=True)
+            cand = torch.unique(torch.cat([uk, uk - 1]))
+
+            def n_of(x):
+                j = torch.searchsorted(uk, x).clamp(max=uk.numel() - 1)
+                return torch.where(uk[j] == x, un[j], torch.zeros_like(un[j]))
+
+            score = n_of(cand) + n_of(cand + 1)
+            cread = torch.div(cand, CR, rounding_mode='floor')
+            best.scatter_reduce_(0, cread, score, 'amax')
+            first = torch.full((n,), torch.iinfo(i64).max, dtype=i64, device=dev)
+            first.scatter_reduce_(0, cread, torch.where(score == best[cread], cand, first[cread]), 'amin')
+            best_c = torch.where(best > 0, first - torch.arange(n, dtype=i64, device=dev) * CR - C0, best_c)
+            votes.append(best)
+            cstar.append(best_c)
+            seeds.append((rd, d, c))
+        rev = votes[1] > votes[0]
+        n_votes = torch.where(rev, votes[1], votes[0])
+        c_win = torch.where(rev, cstar[1], cstar[0])
+        aligned = n_votes >= p['min_seeds']
+        strand = torch.where(aligned, rev.to(torch.int32), torch.full_like(rev, -1, dtype=torch.int32))
+        # d*: the lower median of the chosen window's seed diagonals
+        D0 = max_m + 1
+        DR = D0 + G + 1
+        sel_r, sel_d = [], []
+        for s, (rd, d, c) in enumerate(seeds):
+            if rd.numel() == 0:
+                continue
+            keep = (strand[rd] == s) & ((c == c_win[rd]) | (c == c_win[rd] + 1))
+            sel_r.append(rd[keep])
+            sel_d.append(d[keep])
+        diagonal = torch.zeros(n, dtype=i64, device=dev)
+        if sel_r and sum(int(x.numel()) for x in sel_r):
+            rd, d = torch.cat(sel_r), torch.cat(sel_d)
+            key, _ = torch.sort(rd * DR + d + D0)
+            per = torch.bincount(rd, minlength=n)
+            start = torch.cumsum(per, 0) - per
+            mid = (start + torch.div(per - 1, 2, rounding_mode='floor')).clamp(min=0, max=key.numel() - 1)
+            med = key[mid] - torch.arange(n, dtype=i64, device=dev) * DR - D0
+            diagonal = torch.where(aligned, med, diagonal)
+        return strand, diagonal, n_votes
+
+    # ---- steps 2 and 3 ----------------------------------------------------------------------------------------
+    def align(self, read_batch):
+        """-> SeedHits for every read of ``read_batch``: step 1 here, steps 2 and 3 in the kernel."""
+        import torch
+        from .device import seed_extend_dev
+        if self.device.type != 'cuda':
+            raise _lib.NadavcaHipError('SeedAligner.align: the extension stage runs only in the HIP kernel; this '
+                                       'aligner was built on %s' % self.device)
+        p, dev, i64 = self.params, self.device, torch.int64
+        strand, diagonal, votes = self.seed(read_batch)
+        n = read_batch.n
+        q_off = torch.from_numpy(read_batch.seq_off).to(dev)
+        query = torch.from_numpy(read_batch.sequence).to(dev)
+        score, end, count, pairs = seed_extend_dev(_lib.default_context(dev.index or 0), query, q_off, self._ref,
+                                                   strand, diagonal, p['band'], p['match'], p['mismatch'],
+                                                   p['gap_open'], p['gap_extend'], p['min_score'])
+        count = count.to(i64)
+        off = torch.zeros(n + 1, dtype=i64, device=dev)
+        torch.cumsum(count, 0, out=off[1:])
+        n_pairs = int(off[-1])
+        owner = torch.repeat_interleave(torch.arange(n, dtype=i64, device=dev), count, output_size=n_pairs)
+        got = pairs[q_off[:-1][owner] + torch.arange(n_pairs, dtype=i64, device=dev) - off[:-1][owner]]
+        aligned = (strand >= 0) & (score >= p['min_score'])
+        h = lambda t: t.cpu().numpy()
+        return SeedHits(h(strand), h(diagonal), h(votes), h(score), h(end), h(aligned), h(off), h(got[:, 0]),
+                        h(got[:, 1]).astype(np.int64))
+
+    def get_base_alignments(self, read_batch):
+        """The aligner contract of the batch workflows: -> BaseAlignmentBatch."""
+        return self.align(read_batch).base_alignments()

@@ -285,3 +285,81 @@ def make_read_batch(n, model, seed=0, genome_length=10000, raw_dtype=np.int16, *
     ba = BaseAlignmentBatch(np.concatenate([b[:, 0] for b in bms]), np.concatenate([b[:, 1] for b in bms]),
                             off(bms), np.array([s['reverse'] for s in specs], dtype=bool))
     return rb, SyntheticBatchAligner(genome, ba), genome
+
+
+def make_error_read_batch(n, genome_num, seed=0, length=400, spread=40, substitution_rate=0.0, insertion_rate=0.0,
+                          deletion_rate=0.0, random_fraction=0.0, overhang_fraction=0.0, model=None, dwell=(3, 17),
+                          noise=0.35):
+    """``n`` reads of basecalled sequence with substitutions, insertions and deletions against ``genome_num``
+    (base codes), for the seed aligner (nadavca_amd/seedalign.py).  Read i comes from the reverse strand
+    (rc[x] = 3 - genome[G-1-x]) when i is odd; its length before errors is length +- spread (at least 0).  Walking
+    its reference segment, each base is dropped with ``deletion_rate``, else copied (and then replaced by another
+    base with ``substitution_rate``), and a random base follows it with ``insertion_rate``.  A fraction
+    ``random_fraction`` of the reads are uniform random bases; a fraction ``overhang_fraction`` start before the
+    strand's first base or end after its last (random bases stand for what lies beyond).  ``model`` (the tuple of
+    ``load_model_arrays``): when given, each read also gets a simulated signal and a base -> sample table of all its
+    bases; otherwise the signal tables are empty.
+    -> (ReadBatch, truth, info): ``truth`` a BaseAlignmentBatch of the true pairs — read bases copied from the
+    reference and still equal to it, (read index, strand coordinate) — and ``info`` a dict of per-read arrays:
+    ``kind`` (0 from the reference, 1 random, 2 overhanging), ``reverse`` and ``start`` (strand coordinate of the
+    segment's first base)."""
+    from .readbatch import ReadBatch, BaseAlignmentBatch
+    genome_num = np.asarray(genome_num, dtype=np.int64)
+    G = genome_num.size
+    strands = (genome_num, 3 - genome_num[::-1])
+    seqs, pairs, raws, maps, kinds, revs, starts = [], [], [], [], [], [], []
+    for i in range(n):
+        rng = np.random.default_rng([seed, i])
+        L = max(0, int(length + rng.integers(-spread, spread + 1)))
+        reverse = bool(i % 2)
+        u = rng.random()
+        kind = 1 if u < random_fraction else 2 if u < random_fraction + overhang_fraction else 0
+        if kind == 1 or G == 0:
+            seq, pr, x0, kind = rng.integers(0, 4, L), np.zeros((0, 2), dtype=np.int64), 0, 1
+        else:
+            if kind == 2:
+                over = int(rng.integers(1, max(2, L // 2 + 1)))
+                x0 = -over if rng.random() < 0.5 else G - L + over
+            else:
+                x0 = int(rng.integers(0, max(1, G - L + 1)))
+            xs = np.arange(x0, x0 + L)
+            inside = (xs >= 0) & (xs < G)
+            src = np.where(inside, strands[reverse][np.clip(xs, 0, max(G - 1, 0))], rng.integers(0, 4, L))
+            keep = rng.random(L) >= deletion_rate
+            sub = rng.random(L) < substitution_rate
+            base = np.where(sub, (src + rng.integers(1, 4, L)) % 4, src)
+            ins = rng.random(L) < insertion_rate
+            # read layout: every kept base, then (if ins) one random base
+            width = keep.astype(np.int64) + (keep & ins)
+            pos = np.cumsum(width) - width                  # read index of each kept reference base
+            seq = np.zeros(int(width.sum()), dtype=np.int64)
+            seq[pos[keep]] = base[keep]
+            extra = keep & ins
+            seq[pos[extra] + 1] = rng.integers(0, 4, int(extra.sum()))
+            true = keep & ~sub & inside
+            pr = np.stack([pos[true], xs[true]], axis=1).astype(np.int64)
+        seqs.append(np.asarray(seq, dtype=np.int32))
+        pairs.append(pr)
+        kinds.append(kind)
+        revs.append(reverse and kind != 1)
+        starts.append(x0)
+        if model is not None and len(seq):
+            k, central, alphabet, mean, sigma = model
+            ids = kmer_ids(seq, 0, len(seq), k, central, alphabet)
+            dw = rng.integers(dwell[0], dwell[1] + 1, len(seq))
+            sig = np.repeat(mean[ids], dw) + rng.normal(0.0, noise, int(dw.sum()))
+            raws.append(np.rint(12.0 * np.clip(sig, -5.0, 5.0) + 90.0).astype(np.int16))
+            maps.append(np.concatenate([[0], np.cumsum(dw)[:-1]]))
+        else:
+            raws.append(np.zeros(0, dtype=np.int16))
+            maps.append(np.zeros(0, dtype=np.int64))
+    off = lambda xs: np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.int64)
+    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dtype=dt)
+    mbase = [np.arange(len(m)) for m in maps]
+    rb = ReadBatch(cat(raws, np.int16), off(raws), cat(seqs, np.int32), off(seqs), cat(mbase, np.int64),
+                   cat(maps, np.int64), off(maps))
+    truth = BaseAlignmentBatch(cat([p[:, 0] for p in pairs], np.int64), cat([p[:, 1] for p in pairs], np.int64),
+                               off(pairs), np.array(revs, dtype=bool))
+    info = dict(kind=np.array(kinds, dtype=np.int32), reverse=np.array([bool(i % 2) for i in range(n)]),
+                start=np.array(starts, dtype=np.int64))
+    return rb, truth, info
