@@ -67,10 +67,7 @@ SIGNATURES = {
     'nvk_estimate_log_likelihoods_batch': (_int, [_vp, _i64] + [_vp] * 10 + [_int, _int, _int, _vp, _vp]),
     'nvk_estimate_log_likelihoods_batch_dev': (_int, [_vp, _i64, _i64, _i64, _i64] + [_vp] * 10 + [_int, _int, _int, _vp, _vp]),
     'nvk_consensus_accumulate_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 6 + [_dbl, _i64, _vp, _vp]),
-    'nvk_posterior_dev': (_int, [_vp, _i64, _int, _int, _dbl, _vp, _vp, _vp]),
-    'nvk_consensus_accumulate': (_int, [_vp, _i64, _int] + [_vp] * 6 + [_dbl, _i64, _vp, _vp]),
     'nvk_posterior_segments_dev': (_int, [_vp, _i64, _i64, _vp, _int, _int, _dbl, _vp, _vp, _vp]),
-    'nvk_posterior': (_int, [_vp, _i64, _i64, _vp, _int, _int, _dbl, _vp, _vp, _vp]),
     'nvk_normalize_groups_dev': (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
     'nvk_select_hist_dev': (_int, [_vp, _vp, _i64, _int, _dbl, C.c_uint64, _int, _vp]),
     'nvk_normalize_apply_dev': (_int, [_vp, _vp, _i64, _dbl, _dbl, _vp]),

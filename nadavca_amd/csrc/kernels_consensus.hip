@@ -117,25 +117,6 @@ extern "C" int nvk_consensus_accumulate_dev(nvk_ctx *ctx, int64_t n_reads, int64
   return NVK_OK;
 }
 
-extern "C" int nvk_posterior_dev(nvk_ctx *ctx, int64_t len, int alphabet, int k, double snp_prior,
-                                 const double *ll, const int32_t *reference, double *out) {
-  if (!ctx || len < 0 || alphabet < 2 || alphabet > 8 || k < 1) {
-    nvk_set_error("nvk_posterior_dev: bad argument");
-    return NVK_ERR_INVALID;
-  }
-  NVK_HIP(hipSetDevice(ctx->device));
-  if (len == 0) return NVK_OK;
-  {
-    TimerScope ts(ctx, NVK_K_POSTERIOR);
-    unsigned blocks = (unsigned)((len + 127) / 128);
-    hipLaunchKernelGGL(posterior_kernel, dim3(blocks), dim3(128), 0, ctx->stream, len, (int64_t)1,
-                       (const int64_t *)nullptr, alphabet, k, snp_prior, ll, reference, out);
-  }
-  NVK_HIP(hipGetLastError());
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return NVK_OK;
-}
-
 extern "C" int nvk_posterior_segments_dev(nvk_ctx *ctx, int64_t len, int64_t n_segments,
                                           const int64_t *seg_off, int alphabet, int k,
                                           double snp_prior, const double *ll,
@@ -154,66 +135,5 @@ extern "C" int nvk_posterior_segments_dev(nvk_ctx *ctx, int64_t len, int64_t n_s
   }
   NVK_HIP(hipGetLastError());
   NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return NVK_OK;
-}
-
-// ---- host-pointer conveniences (temporaries: NvkTmp, nvk_internal.h) -------------------------------------
-
-extern "C" int nvk_consensus_accumulate(nvk_ctx *ctx, int64_t n_reads, int alphabet, const double *ll,
-                                        const int32_t *reference, const int64_t *ref_off,
-                                        const int64_t *chunk_start, const int32_t *reverse,
-                                        const int32_t *status, double normalization_event_length,
-                                        int64_t ref_len, double *acc, int64_t *coverage) {
-  if (!ctx || !ref_off) {
-    nvk_set_error("nvk_consensus_accumulate: NULL argument");
-    return NVK_ERR_INVALID;
-  }
-  NVK_HIP(hipSetDevice(ctx->device));
-  const int64_t total = n_reads > 0 ? ref_off[n_reads] : 0;
-  hipStream_t s = ctx->stream;
-  NvkTmp d_ll, d_ref, d_off, d_cs, d_rev, d_st, d_acc, d_cov;
-  int rc;
-  if ((rc = d_ll.up(ll, (size_t)total * alphabet * 8, s))) return rc;
-  if ((rc = d_ref.up(reference, (size_t)total * 4, s))) return rc;
-  if ((rc = d_off.up(ref_off, (size_t)(n_reads + 1) * 8, s))) return rc;
-  if ((rc = d_cs.up(chunk_start, (size_t)n_reads * 8, s))) return rc;
-  if ((rc = d_rev.up(reverse, (size_t)n_reads * 4, s))) return rc;
-  if (status && (rc = d_st.up(status, (size_t)n_reads * 4, s))) return rc;
-  if ((rc = d_acc.up(acc, (size_t)ref_len * alphabet * 8, s))) return rc;
-  if ((rc = d_cov.up(coverage, (size_t)ref_len * 8, s))) return rc;
-  rc = nvk_consensus_accumulate_dev(ctx, n_reads, total, alphabet, (const double *)d_ll.p,
-                                    (const int32_t *)d_ref.p, (const int64_t *)d_off.p,
-                                    (const int64_t *)d_cs.p, (const int32_t *)d_rev.p,
-                                    status ? (const int32_t *)d_st.p : nullptr,
-                                    normalization_event_length, ref_len, (double *)d_acc.p,
-                                    (int64_t *)d_cov.p);
-  if (rc) return rc;
-  NVK_HIP(hipMemcpy(acc, d_acc.p, (size_t)ref_len * alphabet * 8, hipMemcpyDeviceToHost));
-  NVK_HIP(hipMemcpy(coverage, d_cov.p, (size_t)ref_len * 8, hipMemcpyDeviceToHost));
-  return NVK_OK;
-}
-
-extern "C" int nvk_posterior(nvk_ctx *ctx, int64_t len, int64_t n_segments, const int64_t *seg_off,
-                             int alphabet, int k, double snp_prior, const double *ll,
-                             const int32_t *reference, double *out) {
-  if (!ctx) return NVK_ERR_INVALID;
-  NVK_HIP(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  NvkTmp d_ll, d_ref, d_out, d_seg;
-  int rc;
-  if ((rc = d_ll.up(ll, (size_t)len * alphabet * 8, s))) return rc;
-  if ((rc = d_ref.up(reference, (size_t)len * 4, s))) return rc;
-  if ((rc = d_out.up(nullptr, (size_t)len * alphabet * 8, s))) return rc;
-  if (seg_off) {
-    if ((rc = d_seg.up(seg_off, (size_t)(n_segments + 1) * 8, s))) return rc;
-    rc = nvk_posterior_segments_dev(ctx, len, n_segments, (const int64_t *)d_seg.p, alphabet, k,
-                                    snp_prior, (const double *)d_ll.p, (const int32_t *)d_ref.p,
-                                    (double *)d_out.p);
-  } else {
-    rc = nvk_posterior_dev(ctx, len, alphabet, k, snp_prior, (const double *)d_ll.p,
-                           (const int32_t *)d_ref.p, (double *)d_out.p);
-  }
-  if (rc) return rc;
-  if (len) NVK_HIP(hipMemcpy(out, d_out.p, (size_t)len * alphabet * 8, hipMemcpyDeviceToHost));
   return NVK_OK;
 }

@@ -41,23 +41,6 @@ def collective_device(like=None, group=None):
     return torch.device('cpu')
 
 
-def reduce_consensus(acc, cov, dst=0, device=None, group=None):
-    """Sum (acc, cov) over all ranks onto ``dst``.  Returns the totals on ``dst`` and None elsewhere.
-    ``device``: torch device for the collective buffer (a cuda device for the nccl/RCCL backend,
-    None/cpu for gloo)."""
-    torch, dist = _torch_dist()
-    packed = np.concatenate([np.asarray(acc, dtype=np.float64),
-                             np.asarray(cov, dtype=np.float64)[:, None]], axis=1)
-    t = torch.from_numpy(np.ascontiguousarray(packed))
-    if device is not None:
-        t = t.to(device)
-    dist.reduce(t, dst=dst, op=dist.ReduceOp.SUM, group=group)
-    if dist.get_rank(group) != dst:
-        return None
-    out = t.cpu().numpy()
-    return out[:, :-1].copy(), np.rint(out[:, -1]).astype(np.int64)
-
-
 def gather_ranges(ranges, device=None, group=None):
     """All ranks' chunk intervals, concatenated in rank order (every rank gets the full list)."""
     torch, dist = _torch_dist()
@@ -86,9 +69,10 @@ def gather_ranges(ranges, device=None, group=None):
 
 
 def reduce_consensus_tensors(acc, cov, dst=0, group=None):
-    """The same exchange for torch tensors that already live where the collective runs (cuda tensors with
-    the nccl/RCCL backend: the per-position sums never leave the device; cpu tensors with gloo): ONE
-    reduce(sum) of the packed (L, alphabet + 1) f64 buffer.  -> (acc, cov) tensors on ``dst``, None elsewhere."""
+    """Sum the per-position sums ``acc`` and the coverage ``cov`` (torch tensors) over all ranks onto ``dst``: ONE
+    reduce(sum) of the packed (L, alphabet + 1) f64 buffer, where the collective runs (on the device with the
+    nccl/RCCL backend: the sums never leave it; on the host with gloo).  -> (acc, cov) tensors on ``dst``, None
+    elsewhere."""
     torch, dist = _torch_dist()
     packed = torch.cat([acc.to(torch.float64), cov.to(torch.float64).unsqueeze(1)], dim=1).contiguous()
     home = packed.device
@@ -176,30 +160,10 @@ def pooled_centre_scale(local_hist, n_local, device=None, group=None):
     return centre, scale
 
 
-def merge_consensus(acc, cov, ranges, dst=0, device=None, group=None):
-    """The exchange step of ``independent=False`` and nothing else (no GPU involved: covered by the gloo
-    tests): every rank contributes its per-position sums, coverage and chunk intervals; ``dst`` receives
-    what the posterior needs — (total acc, total cov, groups, seg_off, ll laid end to end per group) — the
-    other ranks None.  Grouping follows estimator.py:205-220 over the union of all ranks' intervals."""
-    from .estimator import ProbabilityEstimator
-    all_ranges = gather_ranges(ranges, device=device, group=group)
-    total = reduce_consensus(acc, cov, dst=dst, device=device, group=group)
-    if total is None:
-        return None
-    tacc, tcov = total
-    groups = ProbabilityEstimator.group_ranges(all_ranges)
-    seg_off = np.zeros(len(groups) + 1, dtype=np.int64)
-    np.cumsum([e - s for s, e in groups], out=seg_off[1:])
-    ll_cat = np.concatenate([tacc[s:e] for s, e in groups]) if groups else np.zeros((0, tacc.shape[1]))
-    return tacc, tcov, groups, seg_off, ll_cat
-
-
-def estimate_probabilities_distributed(estimator, reference, local_reads, dst=0, device=None, group=None):
+def estimate_probabilities_distributed(estimator, reference, local_reads, dst=0, group=None):
     """``ProbabilityEstimator.estimate_probabilities`` over the union of all ranks' reads.
     Every rank passes its own shard; the Chunk list is returned on ``dst`` (None elsewhere)."""
+    from .estimator import consensus_chunks
     acc, cov, ranges = estimator.local_consensus(reference, local_reads)
-    merged = merge_consensus(acc, cov, ranges, dst=dst, device=device, group=group)
-    if merged is None:
-        return None
-    tacc, tcov, groups, seg_off, ll_cat = merged
-    return estimator.posterior_of_groups(reference, tcov, groups, seg_off, ll_cat)
+    return consensus_chunks(estimator.kmer_model, estimator.snp_prior, reference, acc, cov, ranges,
+                            distributed=True, group=group, dst=dst)

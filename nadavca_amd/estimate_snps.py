@@ -8,7 +8,7 @@ import yaml
 
 from . import defaults
 from .alignment import ApproximateAligner
-from .estimator import ProbabilityEstimator, Chunk  # noqa: F401
+from .estimator import ProbabilityEstimator, Chunk, consensus_chunks, independent_posteriors  # noqa: F401
 from .genome import Genome
 from .kmer_model import KmerModel
 from .read import Read
@@ -200,10 +200,7 @@ def estimate_snps_batch(reference_num, read_batch, config=defaults.CONFIG_FILE,
     import numpy
     import torch
     from . import readbatch
-    from .device import (DeviceBatch, normalize_groups_dev, refine_alignment_dev, expected_levels_dev,
-                         event_means_dev, estimate_log_likelihoods_dev, consensus_accumulate_dev,
-                         posterior_segments_dev)
-    from .estimator import ProbabilityEstimator
+    from .device import DeviceBatch, normalize_groups_dev, estimate_log_likelihoods_dev, consensus_accumulate_dev
     if isinstance(config, str):
         with open(config, 'r') as file:
             config = yaml.safe_load(file)
@@ -250,7 +247,8 @@ def estimate_snps_batch(reference_num, read_batch, config=defaults.CONFIG_FILE,
         # (a rank whose shard aligned nowhere still takes part in the exchange, with empty sums)
         acc = torch.zeros((L, kmer_model.alphabet_size), dtype=torch.float64, device=device)
         cov = torch.zeros(L, dtype=torch.int64, device=device)
-        return _consensus_chunks(context, kmer_model, config, reference_num, acc, cov, [], device, True, group, dst)
+        return consensus_chunks(kmer_model, config['snp_prior_probability'], reference_num, acc, cov, [], True,
+                                group, dst)
     dbatch = DeviceBatch.from_windows(norm, sa, device)
     if config['tweak_signal_normalization']:
         last_batch_counts['reads_fitted'] = _tweak_signal_normalization(context, kmer_model, dbatch, config,
@@ -258,61 +256,21 @@ def estimate_snps_batch(reference_num, read_batch, config=defaults.CONFIG_FILE,
     ll, status = estimate_log_likelihoods_dev(dbatch, bw, mel, kmer_model, config['model_wobbling'])
     _check_status('estimate_log_likelihoods', status, sa.live)
     rev32 = sa.reverse.to(torch.int32)
-    nel = config['normalization_event_length']
-    k, prior = kmer_model.get_k(), config['snp_prior_probability']
-    ref_dev = torch.from_numpy(reference_num).to(device)
+    nel, prior = config['normalization_event_length'], config['snp_prior_probability']
     ok = (status == 0)
     last_batch_counts['reads_ok'] = int(ok.sum())
     if independent:
-        # every read a segment of its own, laid end to end (estimate_snps.py:63-68)
-        acc, _ = consensus_accumulate_dev(context, dbatch, ll, sa.ref_off[:-1].contiguous(), rev32, status, nel,
-                                          dbatch.total_ref)
+        # the reference's base codes over every read's chunk, laid out as ll, gathered on the device
         rlen = sa.ref_off[1:] - sa.ref_off[:-1]
         owner = torch.repeat_interleave(torch.arange(n_live, dtype=torch.int64, device=device), rlen,
                                         output_size=dbatch.total_ref)
         pos = sa.ref_start[owner] + (torch.arange(dbatch.total_ref, dtype=torch.int64, device=device)
                                      - sa.ref_off[:-1][owner])
-        post = posterior_segments_dev(context, acc, ref_dev[pos], sa.ref_off.contiguous(), k, prior)
-        okh = ok.cpu().numpy()
-        off = sa.ref_off.cpu().numpy()
-        return _independent_result(sa, okh, off, post.cpu().numpy())
+        codes = torch.from_numpy(reference_num).to(device)[pos]
+        okh, values, row_off = independent_posteriors(kmer_model, prior, nel, dbatch, ll, status, rev32, codes)
+        return IndependentChunks(sa.live.cpu().numpy()[okh], sa.ref_start.cpu().numpy()[okh],
+                                 sa.ref_end.cpu().numpy()[okh], values, row_off)
     acc, cov = consensus_accumulate_dev(context, dbatch, ll, sa.ref_start.contiguous(), rev32, status, nel, L)
     starts, ends = sa.ref_start[ok].cpu().numpy(), sa.ref_end[ok].cpu().numpy()
-    return _consensus_chunks(context, kmer_model, config, reference_num, acc, cov,
-                             list(zip(starts.tolist(), ends.tolist())), device, distributed, group, dst)
-
-
-def _consensus_chunks(context, kmer_model, config, reference_num, acc, cov, ranges, device, distributed, group, dst):
-    """Per-position sums -> grouped posteriors (estimator.py:205-236).  Distributed: the sums of all ranks meet in
-    ONE reduce of the packed device buffer, the intervals in a small all-gather; the posterior runs on ``dst``."""
-    import numpy
-    import torch
-    from .device import posterior_segments_dev
-    from .estimator import ProbabilityEstimator
-    if distributed:
-        from . import distributed as D
-        ranges = D.gather_ranges(ranges, device=device, group=group)
-        tot = D.reduce_consensus_tensors(acc, cov, dst=dst, group=group)
-        if tot is None:
-            return None
-        acc, cov = tot
-    groups = ProbabilityEstimator.group_ranges(ranges)
-    if not groups:
-        return []
-    k, prior = kmer_model.get_k(), config['snp_prior_probability']
-    ref_dev = torch.from_numpy(numpy.ascontiguousarray(reference_num, dtype=numpy.int32)).to(device)
-    seg = numpy.concatenate([[0], numpy.cumsum([e - s for s, e in groups])]).astype(numpy.int64)
-    pos = torch.from_numpy(numpy.concatenate([numpy.arange(s, e) for s, e in groups])).to(device)
-    post = posterior_segments_dev(context, acc[pos], ref_dev[pos], torch.from_numpy(seg).to(device), k, prior)
-    post_h, cov_h = post.cpu().numpy(), cov.cpu().numpy()
-    return [Chunk(s, e, post_h[seg[g]:seg[g + 1]], cov_h[s:e].copy()) for g, (s, e) in enumerate(groups)]
-
-
-def _independent_result(sa, okh, off, post):
-    import numpy
-    lens = (off[1:] - off[:-1])[okh]
-    row_off = numpy.concatenate([[0], numpy.cumsum(lens)]).astype(numpy.int64)
-    rows = numpy.concatenate([numpy.arange(off[j], off[j + 1]) for j in numpy.nonzero(okh)[0]]) if okh.any() \
-        else numpy.zeros(0, dtype=numpy.int64)
-    return IndependentChunks(sa.live.cpu().numpy()[okh], sa.ref_start.cpu().numpy()[okh],
-                             sa.ref_end.cpu().numpy()[okh], post[rows], row_off)
+    return consensus_chunks(kmer_model, prior, reference_num, acc, cov, list(zip(starts.tolist(), ends.tolist())),
+                            distributed, group, dst)

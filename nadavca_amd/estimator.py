@@ -8,19 +8,16 @@ launch over all reads —
     -> windowed posterior kernel.
 Nothing numerical runs on the CPU except the spline FIT of ``Read.tweak_signal_normalization``
 (FITPACK ``splrep``, a host step of the reference adjacent to the path, the same scipy call); its
-evaluation over the signals is a kernel that restates FITPACK's ``splev`` bit for bit.
+evaluation over the signals is a kernel that restates FITPACK's ``splev`` bit for bit.  From the
+log-likelihoods on, the buffers stay on the device, and the steps after them (``consensus_chunks``,
+``independent_chunks``) are the ones ``estimate_snps_batch`` runs.
 """
-import ctypes as C
-
 import numpy
 
-from . import _lib, dtw
+from . import dtw
 from .alphabet import alphabet
+from .device import DeviceBatch, estimate_log_likelihoods_dev, consensus_accumulate_dev, posterior_segments_dev
 from .genome import Genome
-
-
-def _ptr(a):
-    return C.c_void_p(a.ctypes.data)
 
 
 class Chunk:
@@ -107,24 +104,11 @@ class ProbabilityEstimator:
         events = dtw.refine_alignment_batch(
             [self._dp_tuple(p, p.read.normalized_signal) for p in live], self.bandwidth,
             self.min_event_length, self.kmer_model, self.model_transitions) if live else []
-        out, it = [], iter(events)
-        for p in prepared:
-            if p is None:
-                out.append(None)
-                continue
-            ev = next(it)
-            if len(ev) == 0:  # no valid path in the band
-                out.append(None)
-                continue
-            s0 = p.signal_range[0]
-            start_ref, end_ref = p.apx.reference_range
-            res = numpy.zeros((len(ev), 3), dtype=int)
-            pos = numpy.arange(len(ev))
-            res[:, 0] = (end_ref - pos - 1) if p.apx.reverse_complement else (start_ref + pos)
-            res[:, 1] = ev[:, 0] + s0
-            res[:, 2] = ev[:, 1] + s0
-            out.append((p.apx, res))
-        return out
+        it = iter(events)
+        evs = [None if p is None else next(it) for p in prepared]
+        # None where the read was not aligned or the band holds no valid path
+        return [None if ev is None or len(ev) == 0 else (p.apx, self._alignment_rows(p, ev))
+                for p, ev in zip(prepared, evs)]
 
     def get_refined_alignment(self, read):
         return self.get_refined_alignments([read])[0]
@@ -139,20 +123,23 @@ class ProbabilityEstimator:
         res[:, 2] = ev[:, 1] + s0
         return res
 
+    def _device(self):
+        import torch
+        return torch.device('cuda', self.kmer_model.context.device)
+
     def refine_and_renormalize(self, reads, renorm_rounds):
         """``align_signal``'s per-read loop (align_signal.py:55-80) for all reads at once and without
         leaving the device between rounds: align, then alternately re-fit the normalisation linearly
         against the model's expected levels (even rounds) and align again (odd rounds) —
         ``device.refine_renorm_loop_dev``.  Every read's ``normalized_signal`` ends up rescaled as in
         the reference.  -> list of (approximate_alignment, (R,3) int array) or None per read."""
-        import torch
-        from .device import DeviceBatch, refine_renorm_loop_dev
+        from .device import refine_renorm_loop_dev
         prepared = [self._prepare(r) for r in reads]
         live = [p for p in prepared if p is not None]
         if not live:
             return [None] * len(prepared)
         batch = dtw.FlatBatch([self._dp_tuple(p, p.read.normalized_signal) for p in live])
-        dbatch = DeviceBatch(batch, torch.device('cuda', self.kmer_model.context.device))
+        dbatch = DeviceBatch(batch, self._device())
         events, status, fits = refine_renorm_loop_dev(dbatch, self.bandwidth, self.min_event_length,
                                                       self.kmer_model, self.model_transitions, renorm_rounds)
         events, status = events.cpu().numpy(), status.cpu().numpy()
@@ -178,7 +165,8 @@ class ProbabilityEstimator:
 
     # ---- SNP scoring -----------------------------------------------------------------------------
     def _log_likelihood_batch(self, reference, reads):
-        """Stages shared by both modes: -> (live prepared reads, FlatBatch, ll (sum R, 4), status)."""
+        """Stages shared by both modes: -> (live prepared reads, DeviceBatch, ll (sum R, 4), status), the last
+        three on the device.  A refused read raises (dtw._raise_on_status), as the per-read operators do."""
         prepared = [self._prepare(r, reference) for r in reads]
         live = [p for p in prepared if p is not None]
         if not live:
@@ -204,37 +192,11 @@ class ProbabilityEstimator:
             signals = [p.read.tweaked_normalized_signal for p in live]
         else:
             signals = [p.read.normalized_signal for p in live]
-        batch = dtw.FlatBatch([self._dp_tuple(p, s) for p, s in zip(live, signals)])
-        ll, status = dtw.estimate_log_likelihoods_flat(batch, self.bandwidth, self.min_event_length,
-                                                       self.kmer_model, self.model_wobbling)
-        return live, batch, ll, status
-
-    def _accumulate(self, live, batch, ll, status, chunk_start, length):
-        lib = _lib.load()
-        alpha = self.kmer_model.alphabet_size
-        acc = numpy.zeros((length, alpha), dtype=numpy.float64)
-        cov = numpy.zeros(length, dtype=numpy.int64)
-        reverse = numpy.array([1 if p.apx.reverse_complement else 0 for p in live], dtype=numpy.int32)
-        chunk_start = numpy.ascontiguousarray(chunk_start, dtype=numpy.int64)
-        status = numpy.ascontiguousarray(status, dtype=numpy.int32)
-        _lib.check(lib.nvk_consensus_accumulate(
-            self.kmer_model.context.handle, len(live), alpha, _ptr(ll), _ptr(batch.reference),
-            _ptr(batch.ref_off), _ptr(chunk_start), _ptr(reverse), _ptr(status),
-            float(self.normalization_event_length), length, _ptr(acc), _ptr(cov)),
-            'nvk_consensus_accumulate')
-        return acc, cov
-
-    def _posterior(self, ll, reference_num, seg_off):
-        lib = _lib.load()
-        alpha = self.kmer_model.alphabet_size
-        ll = numpy.ascontiguousarray(ll, dtype=numpy.float64)
-        ref = numpy.ascontiguousarray(reference_num, dtype=numpy.int32)
-        seg = numpy.ascontiguousarray(seg_off, dtype=numpy.int64)
-        out = numpy.zeros_like(ll)
-        _lib.check(lib.nvk_posterior(self.kmer_model.context.handle, ll.shape[0], seg.size - 1, _ptr(seg),
-                                     alpha, self.kmer_model.get_k(), float(self.snp_prior), _ptr(ll),
-                                     _ptr(ref), _ptr(out)), 'nvk_posterior')
-        return out
+        dbatch = DeviceBatch(dtw.FlatBatch([self._dp_tuple(p, s) for p, s in zip(live, signals)]), self._device())
+        ll, status = estimate_log_likelihoods_dev(dbatch, self.bandwidth, self.min_event_length, self.kmer_model,
+                                                  self.model_wobbling)
+        dtw._raise_on_status('estimate_log_likelihoods', status.cpu().numpy())
+        return live, dbatch, ll, status
 
     @staticmethod
     def group_ranges(ranges):
@@ -254,59 +216,96 @@ class ProbabilityEstimator:
     def local_consensus(self, reference, reads):
         """This process's share of the consensus: per-position sums of the normalised,
         strand-corrected log-likelihoods of ``reads`` over the whole reference, the coverage, and
-        the chunk intervals (estimator.py:199-231).  -> (acc (L,4) f64, cov (L,) i64, ranges)."""
-        alpha = self.kmer_model.alphabet_size
-        live, batch, ll, status = self._log_likelihood_batch(reference, reads)
-        keep = [j for j, p in enumerate(live) if status[j] == dtw.READ_OK]
-        if not keep:
-            return (numpy.zeros((len(reference), alpha)), numpy.zeros(len(reference), dtype=numpy.int64), [])
-        chunk_start = [p.apx.reference_range[0] for p in live]
-        acc, cov = self._accumulate(live, batch, ll, status, chunk_start, len(reference))
-        return acc, cov, [tuple(int(v) for v in live[j].apx.reference_range) for j in keep]
-
-    def posterior_of_groups(self, reference, cov, groups, seg_off, ll_cat):
-        """Posterior of already grouped sums (all groups in one launch, laid end to end) -> Chunk list."""
-        if not groups:
-            return []
-        ref_cat = numpy.concatenate([Genome.to_numerical(reference[s:e]) for s, e in groups])
-        post = self._posterior(ll_cat, ref_cat, seg_off)
-        return [Chunk(s, e, post[seg_off[g]:seg_off[g + 1]], cov[s:e].copy())
-                for g, (s, e) in enumerate(groups)]
-
-    def posterior_groups(self, reference, acc, cov, ranges):
-        """Group the chunk intervals and turn the summed log-likelihoods into posteriors
-        (estimator.py:205-235)."""
-        groups = self.group_ranges(ranges)
-        if not groups:
-            return []
-        seg_off = numpy.zeros(len(groups) + 1, dtype=numpy.int64)
-        numpy.cumsum([e - s for s, e in groups], out=seg_off[1:])
-        ll_cat = numpy.concatenate([acc[s:e] for s, e in groups])
-        return self.posterior_of_groups(reference, cov, groups, seg_off, ll_cat)
+        the chunk intervals (estimator.py:199-231).  -> (acc (L,4) f64, cov (L,) i64 device tensors, ranges)."""
+        import torch
+        acc = torch.zeros((len(reference), self.kmer_model.alphabet_size), dtype=torch.float64, device=self._device())
+        cov = torch.zeros(len(reference), dtype=torch.int64, device=self._device())
+        live, dbatch, ll, status = self._log_likelihood_batch(reference, reads)
+        if not live:
+            return acc, cov, []
+        start = _upload([p.apx.reference_range[0] for p in live], numpy.int64, dbatch.device)
+        reverse = _upload([p.apx.reverse_complement for p in live], numpy.int32, dbatch.device)
+        consensus_accumulate_dev(self.kmer_model.context, dbatch, ll, start, reverse, status,
+                                 self.normalization_event_length, len(reference), acc, cov)
+        ok = (status == dtw.READ_OK).cpu().numpy()
+        return acc, cov, [tuple(int(v) for v in p.apx.reference_range) for p, o in zip(live, ok) if o]
 
     def estimate_probabilities(self, reference, reads):
         """Consensus over all reads (estimator.py:199-236) -> list of Chunk(start, end, posterior,
         coverage), one per group of overlapping reads."""
         acc, cov, ranges = self.local_consensus(reference, reads)
-        return self.posterior_groups(reference, acc, cov, ranges)
+        return consensus_chunks(self.kmer_model, self.snp_prior, reference, acc, cov, ranges)
 
     def estimate_probabilities_independent(self, reference, reads):
         """``[estimate_probabilities(reference, [read])[0] for read in reads]`` in batched form
         (estimate_snps.py:63-68); None for a read that yields no chunk."""
-        live, batch, ll, status = self._log_likelihood_batch(reference, reads)
-        result = {}
-        if live:
-            alpha = self.kmer_model.alphabet_size
-            total = int(batch.ref_off[-1])
-            acc, _ = self._accumulate(live, batch, ll, status, batch.ref_off[:-1], total)
-            ref_cat = numpy.zeros(total, dtype=numpy.int32)
-            for j, p in enumerate(live):
-                s, e = p.apx.reference_range
-                ref_cat[batch.ref_off[j]:batch.ref_off[j + 1]] = Genome.to_numerical(reference[s:e])
-            post = self._posterior(acc, ref_cat, batch.ref_off)
-            for j, p in enumerate(live):
-                if status[j] != dtw.READ_OK:
-                    continue
-                s, e = p.apx.reference_range
-                result[id(p.read)] = Chunk(s, e, post[batch.ref_off[j]:batch.ref_off[j + 1]].reshape(-1, alpha))
+        live, dbatch, ll, status = self._log_likelihood_batch(reference, reads)
+        if not live:
+            return [None] * len(reads)
+        # the reference's base codes over every read's chunk, laid out as ll
+        codes = _upload(numpy.concatenate([_codes(reference, *p.apx.reference_range) for p in live]), numpy.int32,
+                        dbatch.device)
+        reverse = _upload([p.apx.reverse_complement for p in live], numpy.int32, dbatch.device)
+        ok, values, row_off = independent_posteriors(self.kmer_model, self.snp_prior, self.normalization_event_length,
+                                                     dbatch, ll, status, reverse, codes)
+        kept = [p for p, o in zip(live, ok) if o]
+        result = {id(p.read): Chunk(*p.apx.reference_range, values[a:b]) for p, a, b in zip(kept, row_off, row_off[1:])}
         return [result.get(id(r)) for r in reads]
+
+
+# ---- the steps after the log-likelihoods, shared by ProbabilityEstimator and estimate_snps_batch ---------------
+def _upload(values, dtype, device):
+    import torch
+    return torch.from_numpy(numpy.ascontiguousarray(values, dtype=dtype)).to(device)
+
+
+def _codes(reference, s, e):
+    """Base codes (i32) of ``reference[s:e]``; bases are converted only here (KeyError on anything but ACGT)."""
+    part = reference[s:e]
+    if numpy.asarray(part).dtype.kind in 'iu':
+        return numpy.asarray(part, dtype=numpy.int32)
+    return Genome.to_numerical(part).astype(numpy.int32)
+
+
+def group_sums(acc, ranges):
+    """Group the chunk intervals (estimator.py:205-220), each group's sums end to end: -> (groups, seg_off, ll_cat)."""
+    groups = ProbabilityEstimator.group_ranges(ranges)
+    seg_off = numpy.cumsum([0] + [e - s for s, e in groups], dtype=numpy.int64)
+    pos = numpy.concatenate([numpy.arange(s, e) for s, e in groups] + [numpy.zeros(0, numpy.int64)])
+    return groups, seg_off, acc[_upload(pos, numpy.int64, acc.device)]
+
+
+def consensus_chunks(kmer_model, snp_prior, reference, acc, cov, ranges, distributed=False, group=None, dst=0):
+    """Per-position sums (``acc``, ``cov``: device tensors) and the chunk intervals of the reads in them -> grouped
+    posteriors (estimator.py:205-236), a Chunk list.  Distributed: the sums of all ranks meet in ONE reduce of the
+    packed device buffer, the intervals in a small all-gather; the posterior runs on ``dst`` (None elsewhere)."""
+    if distributed:
+        from . import distributed as D
+        ranges = D.gather_ranges(ranges, device=acc.device, group=group)
+        total = D.reduce_consensus_tensors(acc, cov, dst=dst, group=group)
+        if total is None:
+            return None
+        acc, cov = total
+    groups, seg_off, ll_cat = group_sums(acc, ranges)
+    if not groups:
+        return []
+    codes = numpy.concatenate([_codes(reference, s, e) for s, e in groups])
+    post = posterior_segments_dev(kmer_model.context, ll_cat, _upload(codes, numpy.int32, acc.device),
+                                  _upload(seg_off, numpy.int64, acc.device), kmer_model.get_k(), snp_prior)
+    post, cov = post.cpu().numpy(), cov.cpu().numpy()
+    return [Chunk(s, e, post[seg_off[g]:seg_off[g + 1]], cov[s:e].copy()) for g, (s, e) in enumerate(groups)]
+
+
+def independent_posteriors(kmer_model, snp_prior, normalization_event_length, dbatch, ll, status, reverse,
+                           ref_codes):
+    """Every read of ``dbatch`` its own segment (estimate_snps.py:63-68): its normalised, strand-corrected rows of
+    ``ll`` and their posterior.  ``ref_codes``: the reference's base codes over the reads' chunks, laid out as
+    ``ll``.  -> (ok: status 0 per read, posterior rows of the ok reads end to end, their row offsets)."""
+    context = kmer_model.context
+    acc, _ = consensus_accumulate_dev(context, dbatch, ll, dbatch.ref_off[:-1].contiguous(), reverse, status,
+                                      normalization_event_length, dbatch.total_ref)
+    post = posterior_segments_dev(context, acc, ref_codes, dbatch.ref_off, kmer_model.get_k(), snp_prior)
+    ok = (status == dtw.READ_OK).cpu().numpy()
+    lens = numpy.diff(dbatch.ref_off.cpu().numpy())
+    rows = numpy.nonzero(numpy.repeat(ok, lens))[0]
+    return ok, post.cpu().numpy()[rows], numpy.cumsum([0] + lens[ok].tolist(), dtype=numpy.int64)

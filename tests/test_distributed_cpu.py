@@ -16,6 +16,7 @@ def _free_port():
 
 
 def _worker(rank, world, port, tmp):
+    import torch
     import torch.distributed as dist
     os.environ['MASTER_ADDR'] = '127.0.0.1'
     os.environ['MASTER_PORT'] = str(port)
@@ -27,16 +28,16 @@ def _worker(rank, world, port, tmp):
     cov = rng.integers(0, 5, L)
     ranges = [(3 + rank, 10 + rank), (20, 30)] if rank == 0 else [(9, 15)]
     allr = D.gather_ranges(ranges)
-    tot = D.reduce_consensus(acc, cov, dst=0)
+    tot = D.reduce_consensus_tensors(torch.from_numpy(acc), torch.from_numpy(cov), dst=0)
     lo, hi = D.shard_bounds(11, rank, world)
     np.savez(os.path.join(tmp, 'r%d.npz' % rank), acc=acc, cov=cov, allr=np.array(allr), lo=lo, hi=hi,
-             tot_acc=tot[0] if tot is not None else np.zeros(0),
-             tot_cov=tot[1] if tot is not None else np.zeros(0))
+             tot_acc=tot[0].numpy() if tot is not None else np.zeros(0),
+             tot_cov=tot[1].numpy() if tot is not None else np.zeros(0))
     dist.barrier()
     dist.destroy_process_group()
 
 
-def test_two_rank_consensus_exchange(tmp_path):
+def test_two_rank_tensor_consensus_exchange(tmp_path):
     import torch.multiprocessing as mp
     port = _free_port()
     mp.spawn(_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
@@ -79,22 +80,24 @@ def _merge_worker(rank, world, port, tmp):
     os.environ['MASTER_PORT'] = str(port)
     dist.init_process_group('gloo', rank=rank, world_size=world)
     from nadavca_amd import distributed as D
+    from nadavca_amd.estimator import group_sums
     chunks, L = _synthetic_chunks()
     mine = D.shard(chunks, rank, world)                      # contiguous blocks of reads per rank
     acc, cov, ranges = _local_sums(mine, L)
-    merged = D.merge_consensus(acc, cov, ranges, dst=0)
-    tens = D.reduce_consensus_tensors(torch.from_numpy(acc), torch.from_numpy(cov), dst=0)
+    # the steps of estimator.consensus_chunks before the posterior kernel
+    all_ranges = D.gather_ranges(ranges)
+    tot = D.reduce_consensus_tensors(torch.from_numpy(acc), torch.from_numpy(cov), dst=0)
     if rank == 0:
-        tacc, tcov, groups, seg_off, ll_cat = merged
-        np.savez(os.path.join(tmp, 'merged.npz'), tacc=tacc, tcov=tcov, groups=np.array(groups), seg_off=seg_off,
-                 ll_cat=ll_cat, t_acc=tens[0].numpy(), t_cov=tens[1].numpy())
+        groups, seg_off, ll_cat = group_sums(tot[0], all_ranges)
+        np.savez(os.path.join(tmp, 'merged.npz'), tacc=tot[0].numpy(), tcov=tot[1].numpy(), groups=np.array(groups),
+                 seg_off=seg_off, ll_cat=ll_cat.numpy())
     else:
-        assert merged is None and tens is None
+        assert tot is None
     dist.barrier()
     dist.destroy_process_group()
 
 
-def test_two_rank_merge_equals_single_rank(tmp_path):
+def test_two_rank_exchange_and_grouping_equal_single_rank(tmp_path):
     """The exchange step of estimate_snps(independent=False) end to end on two gloo ranks — local sums of
     each rank's shard, interval all-gather, ONE packed reduce, grouping, the posterior's inputs — against
     the same over all reads on one rank (estimator.py:205-235): sums to 1e-12, everything else exact."""
@@ -108,7 +111,7 @@ def test_two_rank_merge_equals_single_rank(tmp_path):
     groups = ProbabilityEstimator.group_ranges(ranges)
     seg_off = np.concatenate([[0], np.cumsum([e - s for s, e in groups])])
     assert np.allclose(got['tacc'], acc, rtol=0, atol=1e-12) and np.array_equal(got['tcov'], cov)
-    assert np.allclose(got['t_acc'], acc, rtol=0, atol=1e-12) and np.array_equal(got['t_cov'], cov)
+    assert got['tcov'].dtype == np.int64
     assert [tuple(g) for g in got['groups'].tolist()] == groups and len(groups) >= 2
     assert np.array_equal(got['seg_off'], seg_off)
     assert np.allclose(got['ll_cat'], np.concatenate([acc[s:e] for s, e in groups]), rtol=0, atol=1e-12)

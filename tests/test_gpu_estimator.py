@@ -130,22 +130,20 @@ def test_align_signal_batch_equals_the_per_read_workflow(km):
         assert np.array_equal(out.normalized_signal(j), read.normalized_signal)
 
 
-def test_device_resident_consensus_path_reproduces_estimate_probabilities(fx, km):
+def test_device_resident_steps_reproduce_estimate_probabilities(fx, km):
     """The data path bench.py's cfg4_consensus workload times at N = 1 — log-likelihoods, scatter-add into the
     per-position sums, posterior, all on device-resident buffers (no host round trip of the sums) — against
     ``estimate_probabilities`` (pinned to the reference's Python by the consensus fixture above)."""
     import torch
     from nadavca_amd.estimator import ProbabilityEstimator
     from nadavca_amd.genome import Genome
-    from nadavca_amd.device import (DeviceBatch, estimate_log_likelihoods_dev, consensus_accumulate_dev,
-                                    posterior_segments_dev)
+    from nadavca_amd.device import estimate_log_likelihoods_dev, consensus_accumulate_dev, posterior_segments_dev
     cfg = dict(fx.config, tweak_signal_normalization=False)
     est = ProbabilityEstimator(km, fx.aligner(), cfg)
     reads = fx.reads()
     want = est.estimate_probabilities(fx.genome, reads)
-    live, batch, _, _ = est._log_likelihood_batch(fx.genome, fx.reads())
-    dev = torch.device('cuda', km.context.device)
-    db = DeviceBatch(batch, dev)
+    live, db, _, _ = est._log_likelihood_batch(fx.genome, fx.reads())
+    dev = db.device
     ll, status = estimate_log_likelihoods_dev(db, est.bandwidth, est.min_event_length, km, est.model_wobbling)
     up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
     start = up([p.apx.reference_range[0] for p in live], np.int64)
