@@ -73,7 +73,8 @@ enum {
   NVK_K_RENORM = 7,      /* normalisation, per-event means, linear re-fit (align_signal's renorm loop) */
   NVK_K_METH = 8,        /* pattern occurrences and their scores (detect_meth) */
   NVK_K_SEED = 9,        /* banded local alignment + traceback of the seed aligner (nvk_seed_extend_dev) */
-  NVK_K_COUNT = 10
+  NVK_K_KMER = 10,       /* per-event and per-k-mer sample statistics of k-mer table training (nvk_kmer_*_dev) */
+  NVK_K_COUNT = 11
 };
 
 const char *nvk_last_error(void); /* thread-local message of the last failing call */
@@ -378,6 +379,44 @@ int nvk_seed_extend_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_query, cons
                         const int64_t *q_off, const int32_t *reference, int64_t ref_len, const int32_t *strand,
                         const int32_t *diag, int band, int match, int mismatch, int gap_open, int gap_extend,
                         int min_score, int32_t *out_hit, int32_t *out_pairs);
+
+/* The M-step of k-mer table training (nadavca_amd/kmer_train.py: estimate_kmer_model): per-k-mer sample statistics
+ * over the final events of an aligned batch.  THE CONTRACT.  Inputs are one batch in the flat layout above: signal /
+ * sig_off (the windows), events i32[2 total_ref] in slice coordinates as nvk_refine_alignment_batch_dev writes them,
+ * per-read status, reference / ref_off, ctx_before / cb_off, ctx_after / ca_off, and k, central, alphabet, trim >= 0.
+ *   counted event  base g of read j (0 <= g < R_j) with status[j] == 0 (status may be NULL: every read counts),
+ *                  trim <= g < R_j - trim, a non-empty event after clamping start and end to 0 .. N_j (as
+ *                  nvk_event_means_dev does), and a k-mer window wholly inside the extended sequence
+ *                  ctx_before ++ reference part ++ ctx_after:  -len(cb_j) <= g - central  and
+ *                  g - central + k - 1 < R_j + len(ca_j).  No base is read as 0 (unlike the expected levels).  A window
+ *                  holding a code outside 0..alphabet-1 is not counted (refine_alignment refuses such reads anyway).
+ *   key            id = sum_m b_m * alphabet^(k-1-m), b_m the extended-sequence base at g - central + m (the indexing
+ *                  of the packaged table and of synthetic.kmer_ids)
+ *   order          E_id = the counted events with key id in batch order (read ascending, then g ascending)
+ *   pass 1         s_e = np.sum(x[a:b]) (numpy's pairwise order), n_e = b - a;  per k-mer S = np.sum of the s_e of
+ *                  E_id gathered into one f64 array, N = sum n_e (int64), e = |E_id|; the caller takes m = S / N
+ *   pass 2         q_e = np.sum(d * d), d = x[a:b] - m_id (a rounded subtraction, a rounded square: the library is
+ *                  built with -ffp-contract=off);  per k-mer Q = np.sum of the q_e of E_id; sigma = sqrt(Q / N)
+ * Every floating-point sum is a kernel's loop in numpy's order, with no atomics: the results equal numpy's bit for bit
+ * and are the same on every run.
+ * nvk_kmer_event_stats_dev writes per event (index ref_off[j] + g): out_key i64 (-1 when not counted), out_len i64
+ * (n_e, 0 when not counted) and out_val f64 (0 when not counted): s_e when level is NULL, else q_e against
+ * level[key] (f64[alphabet^k], device).  k >= 1, 0 <= central < k, alphabet >= 1, alphabet^k <= 2^31, trim >= 0;
+ * ref_off, sig_off, cb_off and ca_off are copied to the host and checked (start at 0, never decrease, ref_off ends at
+ * total_ref).
+ * nvk_kmer_reduce_dev: key i64[n_events] is the events' keys sorted ascending by a STABLE sort, val f64 and len i64
+ * [n_events] the events' values and lengths gathered into the same order; for every id in 0 .. n_kmers it writes
+ * out_sum f64 = np.sum of val over the id's run of keys, out_samples i64 = the sum of their len, out_events i64 =
+ * their number (0, 0, 0 where none was counted; keys outside 0 .. n_kmers are skipped).  n_kmers <= 2^31.
+ * NVK_ERR_INVALID for bad arguments or offsets.  Device pointers. */
+int nvk_kmer_event_stats_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, const double *signal,
+                             const int64_t *sig_off, const int32_t *events, const int64_t *ref_off,
+                             const int32_t *reference, const int32_t *ctx_before, const int64_t *cb_off,
+                             const int32_t *ctx_after, const int64_t *ca_off, const int32_t *status, int k, int central,
+                             int alphabet, int trim, const double *level, int64_t *out_key, double *out_val,
+                             int64_t *out_len);
+int nvk_kmer_reduce_dev(nvk_ctx *ctx, int64_t n_events, int64_t n_kmers, const int64_t *key, const double *val,
+                        const int64_t *len, double *out_sum, int64_t *out_samples, int64_t *out_events);
 
 #ifdef __cplusplus
 }

@@ -28,9 +28,10 @@ TIE_NEAR = 2    # ... two scores closer than 2^-24 relative (beyond the class be
 TIE_PLATEAU = 8  # structural mark: two adjacent bases with the same k-mer level (boundary unidentifiable)
 TIE_ULP = 4     # ... two scores within 64 ulps of the reference's log value, not equal (where its rounding may decide)
 
-K_PLAN, K_ALIGN, K_ELL_SWEEP, K_ELL_HYP, K_EXPECTED, K_CONSENSUS, K_POSTERIOR, K_RENORM, K_METH, K_SEED = range(10)
+K_PLAN, K_ALIGN, K_ELL_SWEEP, K_ELL_HYP, K_EXPECTED, K_CONSENSUS, K_POSTERIOR, K_RENORM, K_METH, K_SEED, K_KMER = \
+    range(11)
 KERNEL_NAMES = ['plan', 'align', 'ell_sweep', 'ell_hyp', 'expected', 'consensus', 'posterior', 'renorm', 'meth',
-                'seed']
+                'seed', 'kmer']
 
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -78,6 +79,8 @@ SIGNATURES = {
     'nvk_meth_count_dev': (_int, [_vp, _i64, _i64] + [_vp] * 5 + [_i64, _vp]),
     'nvk_meth_scores_dev': (_int, [_vp, _i64, _i64] + [_vp] * 6 + [_i64] + [_vp] * 4),
     'nvk_seed_extend_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp] + [_int] * 6 + [_vp, _vp]),
+    'nvk_kmer_event_stats_dev': (_int, [_vp, _i64, _i64] + [_vp] * 10 + [_int] * 4 + [_vp] * 4),
+    'nvk_kmer_reduce_dev': (_int, [_vp, _i64, _i64] + [_vp] * 6),
 }
 
 _lib = None

@@ -374,3 +374,39 @@ def posterior_segments_dev(context, ll, reference_num, seg_off, k, snp_prior, ou
         context.handle, int(ll.shape[0]), int(seg_off.numel()) - 1, _dp(seg_off), int(ll.shape[1]), int(k),
         float(snp_prior), _dp(ll), _dp(reference_num), _dp(out)), 'nvk_posterior_segments_dev')
     return out
+
+
+# ---- per-k-mer sample statistics of k-mer table training (nadavca_amd/kmer_train.py) ----------------------------
+def kmer_event_stats_dev(dbatch, context, events, status, k, central, alphabet, trim, level=None):
+    """Per event of ``dbatch``'s reads: (key int64 (sum R,), value f64, length int64) device tensors — the k-mer key of
+    a counted event or -1, its sample count, and np.sum of its samples of ``dbatch.signal`` (``level`` None) or of
+    their squared deviations from ``level[key]`` (include/nadavca_hip.h: nvk_kmer_event_stats_dev)."""
+    torch = dbatch.torch
+    lib = _lib.load()
+    n = max(dbatch.total_ref, 0)
+    key = torch.empty(n, dtype=torch.int64, device=dbatch.device)
+    val = torch.empty(n, dtype=torch.float64, device=dbatch.device)
+    length = torch.empty(n, dtype=torch.int64, device=dbatch.device)
+    _lib.check(lib.nvk_kmer_event_stats_dev(
+        context.handle, dbatch.n, dbatch.total_ref, _dp(dbatch.signal), _dp(dbatch.sig_off), _dp(events),
+        _dp(dbatch.ref_off), _dp(dbatch.reference), _dp(dbatch.context_before), _dp(dbatch.cb_off),
+        _dp(dbatch.context_after), _dp(dbatch.ca_off), _dp(status) if status is not None else C.c_void_p(0),
+        int(k), int(central), int(alphabet), int(trim), _dp(level) if level is not None else C.c_void_p(0),
+        _dp(key), _dp(val), _dp(length)), 'nvk_kmer_event_stats_dev')
+    return key, val, length
+
+
+def kmer_reduce_dev(context, key, val, length, n_kmers):
+    """Per k-mer id 0 .. n_kmers: (np.sum of ``val`` over its run of ``key``, the sum of their ``length``, their
+    number) as (f64, int64, int64) device tensors (nvk_kmer_reduce_dev).  ``key``: the event keys after a stable
+    ascending sort; ``val`` and ``length`` gathered into the same order."""
+    import torch
+    lib = _lib.load()
+    dev = key.device
+    out_sum = torch.empty(int(n_kmers), dtype=torch.float64, device=dev)
+    out_samples = torch.empty(int(n_kmers), dtype=torch.int64, device=dev)
+    out_events = torch.empty(int(n_kmers), dtype=torch.int64, device=dev)
+    _lib.check(lib.nvk_kmer_reduce_dev(context.handle, int(key.numel()), int(n_kmers), _dp(key), _dp(val),
+                                       _dp(length), _dp(out_sum), _dp(out_samples), _dp(out_events)),
+               'nvk_kmer_reduce_dev')
+    return out_sum, out_samples, out_events
