@@ -9,21 +9,14 @@ Extensions over the reference signature, both optional: ``reads`` may hold ``Rea
 fast5 paths), and ``aligner`` injects an approximate aligner (BWA is not available offline)."""
 import sys
 
-import yaml
-
 from . import defaults
 from .alignment import ApproximateAligner
+from .batchflow import align_batch, load_config, load_kmer_model, seg_index
 from .estimator import ProbabilityEstimator
 from .genome import Genome
-from .kmer_model import KmerModel
 from .read import Read
 
-
-def _load_config(config):
-    if isinstance(config, str):
-        with open(config, 'r') as file:
-            return yaml.safe_load(file)
-    return config
+_load_config = load_config   # the name bench.py imports
 
 
 def load_model_and_estimator(reference_filename, config=defaults.CONFIG_FILE, kmer_model=None,
@@ -31,12 +24,11 @@ def load_model_and_estimator(reference_filename, config=defaults.CONFIG_FILE, km
     if kmer_model is None:
         kmer_model = defaults.KMER_MODEL_FILE
     try:
-        config = _load_config(config)
+        config = load_config(config)
     except FileNotFoundError:
         sys.stderr.write('failed to load config: {} not found\n'.format(config))
         return None
-    if isinstance(kmer_model, str):
-        kmer_model = KmerModel.load_from_hdf5(kmer_model)
+    kmer_model = load_kmer_model(kmer_model)
     if aligner is None:
         try:
             references = Genome.load_from_fasta(reference_filename)
@@ -91,39 +83,6 @@ class AlignedBatch:
         return self.normalized[lo:hi].cpu().numpy()
 
 
-def _align_batch_dev(read_batch, config, kmer_model, renorm_rounds, aligner):
-    """The device half of ``align_signal_batch``, shared with ``detect_meth.detect_meth_batch``: per-read
-    normalisation, the approximate-alignment stage, the windows and the renormalise / re-align loop, all on the
-    device.  ``config`` loaded, ``kmer_model`` a KmerModel.  -> (sa, dbatch, events, status, fits, norm, sig_off):
-    the SignalAlignmentBatch, the windows (``dbatch.signal`` rescaled by every fit), the final events and per-read
-    status of the live reads, the fits, the normalised signals of all reads (NOT rescaled) and their offsets, as
-    device tensors; dbatch, events and status are None (fits []) when no read has an anchor."""
-    import torch
-    from . import readbatch
-    from .device import DeviceBatch, normalize_groups_dev, refine_renorm_loop_dev
-    if aligner is None:
-        raise ValueError('align_signal_batch needs a batch aligner (BWA has no batch adapter offline)')
-    context = kmer_model.context
-    device = torch.device('cuda', context.device)
-    rb = read_batch
-    raw = torch.from_numpy(rb.raw_signal).to(device)
-    if raw.dtype != torch.float64:
-        raw = raw.to(torch.float64)
-    sig_off_dev = torch.from_numpy(rb.sig_off).to(device)
-    norm, _ = normalize_groups_dev(context, raw, sig_off_dev, out=raw)   # per read (align_signal.py:54)
-    ba = aligner.get_base_alignments(rb)
-    sa = readbatch.signal_alignments(rb, ba, config['bandwidth'], aligner.reference_num, kmer_model.get_k(),
-                                     kmer_model.get_central_position(), device=device)
-    if int(sa.live.numel()) == 0:
-        return sa, None, None, None, [], norm, sig_off_dev
-    dbatch = DeviceBatch.from_windows(norm, sa, device)
-    events, status, fits = refine_renorm_loop_dev(dbatch, config['bandwidth'], config['min_event_length'],
-                                                  kmer_model, config['model_transitions'], renorm_rounds)
-    from .estimate_snps import _check_status
-    _check_status('refine_alignment', status, sa.live)   # (too-wide reads stay in `status`, like reads without a path)
-    return sa, dbatch, events, status, fits, norm, sig_off_dev
-
-
 def align_signal_batch(reference_filename, read_batch, config=defaults.CONFIG_FILE,
                        kmer_model=defaults.KMER_MODEL_FILE, renorm_rounds=defaults.RENORM_ROUNDS, aligner=None):
     """``align_signal`` for a struct-of-arrays ``ReadBatch`` (nadavca_amd/readbatch.py): the same steps per read
@@ -136,22 +95,18 @@ def align_signal_batch(reference_filename, read_batch, config=defaults.CONFIG_FI
     import numpy
     import torch
     from .device import to_host
-    config = _load_config(config)
-    if isinstance(kmer_model, str):
-        kmer_model = KmerModel.load_from_hdf5(kmer_model)
     rb = read_batch
-    sa, dbatch, events, status, fits, norm, sig_off_dev = _align_batch_dev(rb, config, kmer_model, renorm_rounds,
-                                                                           aligner)
-    if dbatch is None:
+    res = align_batch(rb, load_config(config), load_kmer_model(kmer_model), renorm_rounds, aligner)
+    sa, norm, events, status, fits = res.stage.sa, res.stage.norm, res.events, res.status, res.fits
+    if res.stage.n_live == 0:
         return AlignedBatch(numpy.zeros(0, dtype=numpy.int64), numpy.zeros(0, dtype=numpy.int32),
                             numpy.zeros((0, 3), dtype=numpy.int64), numpy.zeros(1, dtype=numpy.int64), sa, [],
                             norm, rb.sig_off)
     device = norm.device
-    n_live = int(sa.live.numel())
     # the same linear maps for the samples outside the windows (the reference rescales the whole read,
     # align_signal.py:73): per read (x - intercept) / slope, fit after fit, on the device
     total = int(rb.sig_off[-1])
-    lens = sig_off_dev[1:] - sig_off_dev[:-1]
+    lens = res.stage.group_off[1:] - res.stage.group_off[:-1]   # (normalised per read: the groups are the reads)
     okay = (status == 0)
     for f in fits:
         slope = torch.ones(rb.n, dtype=torch.float64, device=device)
@@ -161,10 +116,8 @@ def align_signal_batch(reference_filename, read_batch, config=defaults.CONFIG_FI
         norm -= torch.repeat_interleave(icpt, lens, output_size=total)
         norm /= torch.repeat_interleave(slope, lens, output_size=total)
     # (R, 3) rows: reference position (descending on the reverse strand), events in read coordinates
-    rlen = sa.ref_off[1:] - sa.ref_off[:-1]
-    n_rows = int(sa.ref_off[-1])
-    owner = torch.repeat_interleave(torch.arange(n_live, dtype=torch.int64, device=device), rlen, output_size=n_rows)
-    inner = torch.arange(n_rows, dtype=torch.int64, device=device) - sa.ref_off[:-1][owner]
+    n_rows = res.stage.dbatch.total_ref
+    owner, inner = seg_index(sa.ref_off, n_rows)
     rows = torch.empty((n_rows, 3), dtype=torch.int64, device=device)
     rows[:, 0] = torch.where(sa.reverse[owner], sa.ref_end[owner] - inner - 1, sa.ref_start[owner] + inner)
     start = sa.slice_start[owner]

@@ -17,7 +17,7 @@ import numpy as np
 from scipy.special import ndtr
 
 from . import defaults
-from .align_signal import align_signal
+from .align_signal import align_signal, load_model_and_estimator
 from .genome import Genome
 
 SMALLEST_PVAL = 1e-50
@@ -79,7 +79,6 @@ def detect_meth(reference_filename, reads, pattern, output, config=defaults.CONF
     """CSV of (Filename, Position, Sequence context, Position scores, Aggregated score) rows, one per scorable
     pattern occurrence per read, to ``output`` (a path) or stdout.  ``reads``: fast5 paths or ``Read``
     objects; ``aligner``: optional approximate aligner (extension, as in ``align_signal``)."""
-    from .align_signal import load_model_and_estimator
     loaded = load_model_and_estimator(reference_filename, config, kmer_model, bwa_executable, aligner)
     if loaded is None:
         return
@@ -164,15 +163,13 @@ def detect_meth_batch(reference_filename, read_batch, pattern, config=defaults.C
     that did not align produce no rows (``detect_meth`` raises on them) and show in ``status`` / ``live``.
     -> MethBatch (``write_csv`` gives ``detect_meth``'s CSV)."""
     import torch
-    from .align_signal import _align_batch_dev, _load_config
+    from .batchflow import align_batch, load_config, load_kmer_model, seg_index
     from .device import event_means_dev, expected_levels_dev, meth_scores_dev, to_host
-    from .kmer_model import KmerModel
-    config = _load_config(config)
-    if isinstance(kmer_model, str):
-        kmer_model = KmerModel.load_from_hdf5(kmer_model)
-    sa, dbatch, events, status, _, _, _ = _align_batch_dev(read_batch, config, kmer_model, renorm_rounds, aligner)
-    if dbatch is None:
+    kmer_model = load_kmer_model(kmer_model)
+    res = align_batch(read_batch, load_config(config), kmer_model, renorm_rounds, aligner)
+    if res.stage.n_live == 0:
         return MethBatch.empty()
+    sa, dbatch, events, status = res.stage.sa, res.stage.dbatch, res.events, res.status
     context = kmer_model.context
     live = sa.live.cpu().numpy()
     # the loop's own means were taken before its last rescale: these are over the final signal (detect_meth.py:106)
@@ -184,8 +181,7 @@ def detect_meth_batch(reference_filename, read_batch, pattern, config=defaults.C
     if n_occ == 0:
         return MethBatch.empty(status.cpu().numpy(), live)
     dev = pos.device
-    owner = torch.repeat_interleave(torch.arange(dbatch.n, dtype=torch.int64, device=dev), occ_off[1:] - occ_off[:-1],
-                                    output_size=n_occ)
+    owner, _ = seg_index(occ_off, n_occ)
     # the 11 bases around each occurrence, 2 bits each in one integer (exact in a double: 22 bits)
     first = dbatch.ref_off[:-1][owner] + pos - FLANK
     shifts = 2 * torch.arange(2 * FLANK, -1, -1, dtype=torch.int64, device=dev)

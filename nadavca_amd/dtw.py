@@ -19,6 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .batchflow import check_status
 from ._lib import READ_OK, READ_NO_PATH, READ_BAD_INPUT, READ_BAD_BAND, READ_TOO_WIDE  # noqa: F401
 
 
@@ -161,19 +162,6 @@ class KmerModel:
 # ------------------------------------------------------------------------------------------------
 # batched operators
 # ------------------------------------------------------------------------------------------------
-def _raise_on_status(what, status):
-    """Per-read failures as exceptions (the per-read operators of the reference raise too): invalid input
-    -> ValueError; a band wider than the compiled kernels serve -> NadavcaHipError."""
-    bad = np.nonzero((status < 0) & (status != READ_TOO_WIDE))[0]
-    if bad.size:
-        raise ValueError('%s: invalid input for read(s) %s (status %s)'
-                         % (what, bad[:8].tolist(), status[bad[:8]].tolist()))
-    wide = np.nonzero(status == READ_TOO_WIDE)[0]
-    if wide.size:
-        raise _lib.NadavcaHipError('%s: the band of read(s) %s is wider than the compiled kernels serve '
-                                   '(INTEGRATION.md, limits)' % (what, wide[:8].tolist()))
-
-
 def refine_alignment_flat(batch, bandwidth, min_event_length, kmer_model, model_transitions, on_error='raise'):
     """-> (events int32 (sum R, 2), status int32 (n,)) for a FlatBatch.  on_error='status': per-read
     failures (status < 0) are left to the caller instead of raised."""
@@ -184,7 +172,7 @@ def refine_alignment_flat(batch, bandwidth, min_event_length, kmer_model, model_
                                               int(min_event_length), int(bool(model_transitions)),
                                               _ptr(events), _ptr(status)), 'nvk_refine_alignment_batch')
     if on_error == 'raise':
-        _raise_on_status('refine_alignment', status)
+        check_status('refine_alignment', status)
     return events, status
 
 
@@ -234,7 +222,7 @@ def estimate_log_likelihoods_flat(batch, bandwidth, min_event_length, kmer_model
                                                       int(bool(model_wobbling)), _ptr(ll), _ptr(status)),
                'nvk_estimate_log_likelihoods_batch')
     if on_error == 'raise':
-        _raise_on_status('estimate_log_likelihoods', status)
+        check_status('estimate_log_likelihoods', status)
     return ll, status
 
 

@@ -16,6 +16,7 @@ import numpy
 
 from . import dtw
 from .alphabet import alphabet
+from .batchflow import check_status
 from .device import DeviceBatch, estimate_log_likelihoods_dev, consensus_accumulate_dev, posterior_segments_dev
 from .genome import Genome
 
@@ -144,9 +145,8 @@ class ProbabilityEstimator:
                                                       self.kmer_model, self.model_transitions, renorm_rounds)
         events, status = events.cpu().numpy(), status.cpu().numpy()
         fits = [f.cpu().numpy() for f in fits]
-        if (status < 0).any():
-            bad = numpy.nonzero(status < 0)[0]
-            raise ValueError('refine_alignment: invalid input for read(s) %s' % bad[:8].tolist())
+        # (a too-wide band is a ValueError here, not the NadavcaHipError of the dtw operators: kept as it was)
+        check_status('refine_alignment', status, too_wide='invalid')
         out, j = [], 0
         for p in prepared:
             if p is None:
@@ -166,7 +166,7 @@ class ProbabilityEstimator:
     # ---- SNP scoring -----------------------------------------------------------------------------
     def _log_likelihood_batch(self, reference, reads):
         """Stages shared by both modes: -> (live prepared reads, DeviceBatch, ll (sum R, 4), status), the last
-        three on the device.  A refused read raises (dtw._raise_on_status), as the per-read operators do."""
+        three on the device.  A refused read raises (batchflow.check_status), as the per-read operators do."""
         prepared = [self._prepare(r, reference) for r in reads]
         live = [p for p in prepared if p is not None]
         if not live:
@@ -195,7 +195,7 @@ class ProbabilityEstimator:
         dbatch = DeviceBatch(dtw.FlatBatch([self._dp_tuple(p, s) for p, s in zip(live, signals)]), self._device())
         ll, status = estimate_log_likelihoods_dev(dbatch, self.bandwidth, self.min_event_length, self.kmer_model,
                                                   self.model_wobbling)
-        dtw._raise_on_status('estimate_log_likelihoods', status.cpu().numpy())
+        check_status('estimate_log_likelihoods', status)
         return live, dbatch, ll, status
 
     @staticmethod

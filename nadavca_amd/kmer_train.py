@@ -2,8 +2,8 @@
 
 Every score of the engine rests on the table's ``mean[A^k]`` and ``sigma[A^k]``, in the units the kernels read
 (samples normalised by median/MAD, then linearly re-fitted by the renorm loop).  This module produces a table in those
-units from a ReadBatch and a batch aligner, by hard EM: align the batch with the current table (``_align_batch_dev``,
-the device half of ``align_signal_batch``, unchanged), take per-k-mer sample statistics over the final events and the
+units from a ReadBatch and a batch aligner, by hard EM: align the batch with the current table (``align_batch``, the
+device half of ``align_signal_batch``, unchanged), take per-k-mer sample statistics over the final events and the
 finally rescaled signal, update the k-mers seen often enough, and align again.
 
 The statistics (the M-step) are two device passes, exact and deterministic; their contract is in
@@ -121,7 +121,7 @@ def estimate_kmer_model(read_batch, aligner, kmer_model=defaults.KMER_MODEL_FILE
     the last rescale with the final events and status, then gives every k-mer with at least ``min_events`` counted
     events ``mean = m`` and ``sigma = max(sigma, min_sigma)``; every other k-mer keeps its values bit for bit.  Bases
     within ``trim`` of either end of a read's aligned part are not counted.  -> KmerModelEstimate."""
-    from .align_signal import _align_batch_dev, _load_config
+    from .batchflow import align_batch, load_config, load_kmer_model
     from .kmer_model import KmerModel
     for name, v, lo in (('rounds', rounds, 1), ('renorm_rounds', renorm_rounds, 0), ('min_events', min_events, 1),
                         ('trim', trim, 0)):
@@ -129,9 +129,7 @@ def estimate_kmer_model(read_batch, aligner, kmer_model=defaults.KMER_MODEL_FILE
             raise ValueError('%s must be an integer >= %d, not %r' % (name, lo, v))
     if not (np.isfinite(min_sigma) and min_sigma > 0):
         raise ValueError('min_sigma must be a finite number > 0, not %r' % (min_sigma,))
-    config = _load_config(config)
-    if isinstance(kmer_model, (str, os.PathLike)):
-        kmer_model = KmerModel.load_from_hdf5(os.fspath(kmer_model))
+    config, kmer_model = load_config(config), load_kmer_model(kmer_model)
     k, central, alphabet = _check_kmer_args(kmer_model.get_k(), kmer_model.get_central_position(),
                                             kmer_model.get_alphabet_size())
     context = kmer_model.context
@@ -143,23 +141,20 @@ def estimate_kmer_model(read_batch, aligner, kmer_model=defaults.KMER_MODEL_FILE
     history = []
     n_kmers = alphabet ** k
     for _ in range(int(rounds)):
-        sa, dbatch, events, status, _, _, _ = _align_batch_dev(read_batch, config, current, int(renorm_rounds),
-                                                               aligner)
-        aligned = int(sa.live.numel())
-        if dbatch is None:
+        res = align_batch(read_batch, config, current, int(renorm_rounds), aligner)
+        aligned = res.stage.n_live
+        stats = lambda level=None: kmer_stats_dev(context, res.stage.dbatch, res.events, res.status, k, central,
+                                                  alphabet, trim, level)
+        if aligned == 0:
             S, N, e = np.zeros(n_kmers), np.zeros(n_kmers, dtype=np.int64), np.zeros(n_kmers, dtype=np.int64)
             status_ok = 0
         else:
-            status_ok = int((status == 0).sum())
-            S, N, e = (t.cpu().numpy() for t in kmer_stats_dev(context, dbatch, events, status, k, central, alphabet,
-                                                               trim))
+            status_ok = int((res.status == 0).sum())
+            S, N, e = (t.cpu().numpy() for t in stats())
         seen = N > 0
         m = np.zeros(n_kmers)
         m[seen] = S[seen] / N[seen]
-        if dbatch is None:
-            Q = np.zeros(n_kmers)
-        else:
-            Q = kmer_stats_dev(context, dbatch, events, status, k, central, alphabet, trim, level=m)[0].cpu().numpy()
+        Q = stats(m)[0].cpu().numpy() if aligned else np.zeros(n_kmers)
         updated = e >= int(min_events)
         new_mean, new_sigma = mean.copy(), sigma.copy()
         new_mean[updated] = m[updated]

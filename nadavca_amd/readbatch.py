@@ -17,6 +17,9 @@ Nothing here computes the alignment itself; the arrays go to the device and thro
 (nadavca_amd/align_signal.py: ``align_signal_batch``)."""
 import numpy as np
 
+from .batchflow import seg_index
+
+
 def _offsets(lengths):
     off = np.zeros(len(lengths) + 1, dtype=np.int64)
     np.cumsum(lengths, out=off[1:])
@@ -114,13 +117,6 @@ def signal_alignments(rb, ba, bandwidth, reference_num, k, central, device='cpu'
 
     def offsets(lengths):
         return torch.cat([torch.zeros(1, dtype=i64, device=dev), torch.cumsum(lengths, 0)])
-
-    def seg_index(off):  # owner segment and position inside it, for flat positions 0..off[-1]
-        lens = off[1:] - off[:-1]
-        total = int(off[-1])
-        owner = torch.repeat_interleave(torch.arange(lens.numel(), dtype=i64, device=dev), lens, output_size=total)
-        inner = torch.arange(total, dtype=i64, device=dev) - off[:-1][owner]
-        return owner, inner
 
     seq_len_all = seq_off[1:] - seq_off[:-1]
     # base -> sample look-up for all reads at once: a dense table over the concatenated sequences

@@ -19,6 +19,7 @@ only aligned columns whose two bases are equal (alignment.py:118-138, ``alignmen
 import numpy as np
 
 from . import _lib
+from .batchflow import seg_index
 from .readbatch import BaseAlignmentBatch
 
 PARAMS = dict(k=14, max_occ=32, band=64, min_seeds=2, match=1, mismatch=1, gap_open=1, gap_extend=1, min_score=30)
@@ -138,8 +139,7 @@ class SeedAligner:
         total = int(seq.numel())
         lens = q_off[1:] - q_off[:-1]
         max_m = int(lens.max()) if n else 0
-        owner = torch.repeat_interleave(torch.arange(n, dtype=i64, device=dev), lens, output_size=total)
-        inner = torch.arange(total, dtype=i64, device=dev) - q_off[:-1][owner]
+        owner, inner = seg_index(q_off, total)
         code, _ = self._kmers(torch.cat([seq, torch.zeros(k, dtype=i64, device=dev)]), total)
         starts = torch.nonzero(inner <= lens[owner] - k).reshape(-1)   # read k-mers (codes are checked above)
         q_code = code[starts]
@@ -226,9 +226,8 @@ class SeedAligner:
         count = count.to(i64)
         off = torch.zeros(n + 1, dtype=i64, device=dev)
         torch.cumsum(count, 0, out=off[1:])
-        n_pairs = int(off[-1])
-        owner = torch.repeat_interleave(torch.arange(n, dtype=i64, device=dev), count, output_size=n_pairs)
-        got = pairs[q_off[:-1][owner] + torch.arange(n_pairs, dtype=i64, device=dev) - off[:-1][owner]]
+        owner, inner = seg_index(off)
+        got = pairs[q_off[:-1][owner] + inner]
         aligned = (strand >= 0) & (score >= p['min_score'])
         h = lambda t: t.cpu().numpy()
         return SeedHits(h(strand), h(diagonal), h(votes), h(score), h(end), h(aligned), h(off), h(got[:, 0]),

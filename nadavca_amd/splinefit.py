@@ -1,11 +1,13 @@
-"""The FIT half of ``Read.tweak_signal_normalization`` (/root/reference/nadavca/read.py:83-93) for many reads ON
-THE HOST, with scipy: per read, keep the events whose mean lies within 1 of the model's expected level, sort the
-pairs by mean and fit FITPACK's smoothing spline (``scipy.interpolate.splrep(means, expected, s=len(means))``).
-Since round 3 the batch path fits on the device (``nvk_spline_fit_dev``, csrc/splfit.h: under that filter and
-that ``s`` FITPACK never gets past its first trial, the least-squares cubic); this module is what serves a read the
-kernel reports as outside that case, the per-read ``Read.tweak_signal_normalization``, and
+"""``Read.tweak_signal_normalization`` (/root/reference/nadavca/read.py:83-94) for many reads.
+
+The FIT on the host, with scipy: per read, keep the events whose mean lies within 1 of the model's expected level,
+sort the pairs by mean and fit FITPACK's smoothing spline (``scipy.interpolate.splrep(means, expected,
+s=len(means))``).  Since round 3 the batch path fits on the device (``nvk_spline_fit_dev``, csrc/splfit.h: under that
+filter and that ``s`` FITPACK never gets past its first trial, the least-squares cubic); the host fit is what serves a
+read the kernel reports as outside that case, the per-read ``Read.tweak_signal_normalization``, and
 ``estimate_snps_batch(spline_fit='host')`` — the cross-check of the kernel (~0.25 ms per read; the reads are
-independent, so the fits are spread over worker processes: scipy holds the GIL inside the call)."""
+independent, so the fits are spread over worker processes: scipy holds the GIL inside the call).  At the end, the
+whole step for a device.DeviceBatch (``tweak_signal_normalization``) and the one place that applies splines to it."""
 import numpy as np
 
 
@@ -131,3 +133,65 @@ def fit_splines(means, expected, ref_off, usable, workers=0):
     and coefficients of the fitted reads end to end (read j's at [knot_off[j], knot_off[j+1]), empty when not
     fitted).  ``workers`` > 1: that many processes."""
     return submit_fits(means, expected, ref_off, usable, workers).result()
+
+
+def apply_splines_dev(context, dbatch, t, c, knot_off, unfitted):
+    """``signal = splev(signal, spline of its read)`` in place on ``dbatch.signal`` (read.py:94; the kernel restates
+    FITPACK's evaluation).  Device tensors: read j's knots and coefficients at [knot_off[j], knot_off[j+1]) of ``t``
+    and ``c`` — a valid spline for EVERY read, a placeholder where ``unfitted[j]`` (bool): those reads keep their
+    samples (the reference would fail on them), saved before the kernel and put back after it."""
+    import torch
+    from .device import splev_groups_dev
+    keep = saved = None
+    if bool(unfitted.any()):
+        keep = torch.repeat_interleave(unfitted, dbatch.sig_off[1:] - dbatch.sig_off[:-1],
+                                       output_size=dbatch.total_signal)
+        saved = dbatch.signal[keep]
+    splev_groups_dev(context, dbatch.signal, dbatch.sig_off, t, c, knot_off, 3, out=dbatch.signal)
+    if keep is not None:
+        dbatch.signal[keep] = saved
+
+
+def apply_host_fits(context, dbatch, fits):
+    """``apply_splines_dev`` for fits made on the host (``fits`` as ``fit_splines`` returns them): uploaded with the
+    identity on [-5, 5] as the placeholder of the reads without a fit."""
+    import torch
+    t, c, knot_off, fitted = fits
+    ident = np.array([-5.0] * 4 + [5.0] * 4), np.array([-5.0, -5.0 / 3, 5.0 / 3, 5.0, 0.0, 0.0, 0.0, 0.0])
+    parts = [(t[a:b], c[a:b]) if f else ident for a, b, f in zip(knot_off, knot_off[1:], fitted)]
+    koff2 = np.cumsum([0] + [len(p[0]) for p in parts], dtype=np.int64)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dbatch.device)
+    apply_splines_dev(context, dbatch, up(np.concatenate([p[0] for p in parts])),
+                      up(np.concatenate([p[1] for p in parts])), up(koff2), up(~fitted))
+
+
+def tweak_signal_normalization(context, kmer_model, dbatch, config, fit_workers=0, spline_fit='device'):
+    """``Read.tweak_signal_normalization`` (read.py:83-94) for the batch, in place on its signal: pre-alignment
+    without transition rows, expected levels, per-event means, the fit, the evaluation — five kernels, nothing on
+    the host (``spline_fit='device'``: nvk_spline_fit_dev restates the pass of FITPACK's ``curfit`` that decides
+    these fits and checks per read that it does).  A read the kernel reports as outside that case (fit == 2: NaN
+    levels, all means equal) is fitted by FITPACK itself, as is everything with ``spline_fit='host'`` (scipy in
+    ``fit_workers`` processes — the path of rounds 1-2, kept as the cross-check of the kernel).
+    -> number of reads fitted."""
+    import torch
+    from .device import refine_alignment_dev, expected_levels_dev, event_means_dev, spline_fit_dev
+    bw, mel = config['bandwidth'], config['min_event_length']
+    ev0, st0 = refine_alignment_dev(dbatch, bw, mel, kmer_model, False)
+    expected = expected_levels_dev(dbatch, kmer_model, with_contexts=True)
+    means = event_means_dev(dbatch, context, ev0, st0)
+    if spline_fit == 'device':
+        t, c, fit = spline_fit_dev(context, means, expected, dbatch.ref_off, st0)
+        if not bool((fit == 2).any()):
+            # the splines as the kernel left them: 8 knots + 8 coefficients per read, placeholders included
+            knot_off = torch.arange(dbatch.n + 1, dtype=torch.int64, device=dbatch.device) * 8
+            apply_splines_dev(context, dbatch, t.reshape(-1), c.reshape(-1), knot_off, fit != 0)
+            return int((fit == 0).sum())
+        fits = merge_host_fits(means.cpu().numpy(), expected.cpu().numpy(), dbatch.ref_off.cpu().numpy(),
+                               t.cpu().numpy(), c.cpu().numpy(), fit.cpu().numpy())
+    elif spline_fit == 'host':
+        fits = fit_splines(means.cpu().numpy(), expected.cpu().numpy(), dbatch.ref_off.cpu().numpy(),
+                           st0.cpu().numpy() == 0, workers=fit_workers)
+    else:
+        raise ValueError("spline_fit: 'device' or 'host'")
+    apply_host_fits(context, dbatch, fits)
+    return int(fits[3].sum())

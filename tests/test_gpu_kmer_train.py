@@ -94,13 +94,13 @@ def test_kernels_equal_the_restatement_on_refined_events(tables, mel, with_conte
 def test_kernels_equal_the_restatement_on_the_batch_workflow(tables):
     """The final events and the finally rescaled signal of align_signal_batch's device half, both strands, int16."""
     from nadavca_amd import synthetic
-    from nadavca_amd.align_signal import _align_batch_dev, _load_config
+    from nadavca_amd.batchflow import align_batch, load_config
     from nadavca_amd import defaults
     for k in (6, 3, 8):
         model = tables['models'][k]
         rb, aligner, _ = synthetic.make_read_batch(50, tables[k], seed=30 + k)
-        sa, dbatch, events, status, _, _, _ = _align_batch_dev(rb, _load_config(defaults.CONFIG_FILE), model, 3,
-                                                               aligner)
+        res = align_batch(rb, load_config(defaults.CONFIG_FILE), model, 3, aligner)
+        sa, dbatch, events, status = res.stage.sa, res.stage.dbatch, res.events, res.status
         assert bool(sa.reverse.any()) and not bool(sa.reverse.all())
         got = _check(dbatch, model.context, events, status, k, model.central_position, 5)
         assert got['e'].sum() > 1000
@@ -173,7 +173,8 @@ def test_recovery_from_a_perturbed_table(tables, tmp_path):
     RMS error and the scatter shrink from round to round; after round 3 the RMS error is at most 1/2 of the start's and
     the scatter at most 1/4 of it.  These bounds were set after the first GPU run."""
     from nadavca_amd import defaults, estimate_kmer_model
-    from nadavca_amd.align_signal import _align_batch_dev, _load_config, align_signal_batch
+    from nadavca_amd.align_signal import align_signal_batch
+    from nadavca_amd.batchflow import align_batch, load_config
     from nadavca_amd.kmer_model import KmerModel
     from nadavca_amd.kmer_train import kmer_stats_dev
     rb, aligner, _ = _recovery_batch(tables)
@@ -191,8 +192,8 @@ def test_recovery_from_a_perturbed_table(tables, tmp_path):
     assert np.array_equal(chain[-1].mean.view(np.int64), est.mean.view(np.int64))
     assert np.array_equal(chain[-1].sigma.view(np.int64), est.sigma.view(np.int64))
     # round 3 from its own alignment: the updated k-mers hold m and max(sigma, min_sigma) of its statistics
-    _, dbatch, events, status, _, _, _ = _align_batch_dev(rb, _load_config(defaults.CONFIG_FILE), chain[1].model,
-                                                          defaults.RENORM_ROUNDS, aligner)
+    res = align_batch(rb, load_config(defaults.CONFIG_FILE), chain[1].model, defaults.RENORM_ROUNDS, aligner)
+    dbatch, events, status = res.stage.dbatch, res.events, res.status
     ctx = start.context
     S, N, e = (t.cpu().numpy() for t in kmer_stats_dev(ctx, dbatch, events, status, 6, 2, 4, 5))
     m = np.where(N > 0, S / np.maximum(N, 1), 0.0)

@@ -12,7 +12,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nadavca_amd import dtw, synthetic, defaults  # noqa: E402
-from nadavca_amd.align_signal import _align_batch_dev, _load_config  # noqa: E402
+from nadavca_amd.batchflow import align_batch, load_config  # noqa: E402
 from nadavca_amd.kmer_train import kmer_stats_dev  # noqa: E402
 
 args = [a for a in sys.argv[1:] if not a.startswith('--')]
@@ -27,12 +27,13 @@ print('built %d reads (%.0f samples each on average) in %.1f s' % (n_reads, rb.s
 rng = np.random.default_rng(8)
 km = dtw.KmerModel(k, central, alphabet, mean + rng.normal(0.0, 0.25, mean.size), sigma * 1.5)
 ctx = km.context
-config = _load_config(defaults.CONFIG_FILE)
-_align_batch_dev(rb, config, km, defaults.RENORM_ROUNDS, aligner)   # warm-up: workspaces, first touch
+config = load_config(defaults.CONFIG_FILE)
+align_batch(rb, config, km, defaults.RENORM_ROUNDS, aligner)   # warm-up: workspaces, first touch
 for r in range(rounds):
     ctx.synchronize()
     t = time.perf_counter()
-    sa, dbatch, events, status, _, _, _ = _align_batch_dev(rb, config, km, defaults.RENORM_ROUNDS, aligner)
+    res = align_batch(rb, config, km, defaults.RENORM_ROUNDS, aligner)
+    dbatch, events, status = res.stage.dbatch, res.events, res.status
     ctx.synchronize()
     t_align = time.perf_counter() - t
     ctx.timing_reset()

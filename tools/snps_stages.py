@@ -11,7 +11,7 @@ import torch
 from nadavca_amd import synthetic, dtw, _lib, device, readbatch, defaults
 import nadavca_amd.estimate_snps  # noqa: F401 (the package re-exports the function under the same name)
 ES = sys.modules['nadavca_amd.estimate_snps']
-from nadavca_amd.align_signal import _load_config
+from nadavca_amd.batchflow import load_config
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
 what = sys.argv[2] if len(sys.argv) > 2 else 'snps'
@@ -19,7 +19,7 @@ model = synthetic.load_model_arrays()
 ctx = _lib.default_context()
 km = dtw.KmerModel(*model, context=ctx)
 rb, aligner, genome = synthetic.make_read_batch(n, model, seed=1000, genome_length=10000)
-cfg = dict(_load_config(defaults.CONFIG_FILE), tweak_signal_normalization=True)
+cfg = dict(load_config(defaults.CONFIG_FILE), tweak_signal_normalization=True)
 acc = collections.OrderedDict()
 
 
