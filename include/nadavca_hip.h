@@ -380,6 +380,25 @@ int nvk_seed_extend_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_query, cons
                         const int32_t *diag, int band, int match, int mismatch, int gap_open, int gap_extend,
                         int min_score, int32_t *out_hit, int32_t *out_pairs);
 
+/* nvk_seed_extend_dev with a reference range per read, for a reference of several contigs laid end to end
+ * (nadavca_amd/refset.py): ref_lo, ref_hi i32[n_reads], in coordinates of the strand read j is aligned to (on strand 1
+ * contig [a, b) of the forward reference is [G - b, G - a)).  The same kernel and the same rules, with
+ * the read's lo = ref_lo, hi = ref_hi:
+ *   cells   (i, j), 0 <= i < m, lo <= j < hi, d* - w <= j - i <= d* + w
+ * and lo wherever the rules above compare j with 0: D takes H[i-1][j-1] where i > 0 && j > lo; (i, j-1) is a cell only
+ * for j > lo; the traceback's DIAG step stops if i was 0 or j was lo.  j is reported on the strand,
+ * as above (not relative to ref_lo).  Equivalently: score, end cell, count and pairs are those of nvk_seed_extend_dev
+ * on the reference cut to the range (for strand 1 the forward slice [G - ref_hi, G - ref_lo)) with diag - ref_lo, every
+ * j moved back by ref_lo.  An empty range gives score 0, end -1, -1, no pairs.  With ref_lo = 0 and ref_hi = G for
+ * every read the outputs are nvk_seed_extend_dev's.  ref_lo and ref_hi are copied to the host and checked like q_off:
+ * for a read that is not skipped (strand != -1), ref_lo < 0, ref_hi > G or ref_lo > ref_hi is NVK_ERR_INVALID.  The
+ * limit is G <= 2^30 over all contigs.  Device pointers. */
+int nvk_seed_extend_bounded_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_query, const int32_t *query,
+                                const int64_t *q_off, const int32_t *reference, int64_t ref_len, const int32_t *strand,
+                                const int32_t *diag, const int32_t *ref_lo, const int32_t *ref_hi, int band, int match,
+                                int mismatch, int gap_open, int gap_extend, int min_score, int32_t *out_hit,
+                                int32_t *out_pairs);
+
 /* The M-step of k-mer table training (nadavca_amd/kmer_train.py: estimate_kmer_model): per-k-mer sample statistics
  * over the final events of an aligned batch.  THE CONTRACT.  Inputs are one batch in the flat layout above: signal /
  * sig_off (the windows), events i32[2 total_ref] in slice coordinates as nvk_refine_alignment_batch_dev writes them,

@@ -9,7 +9,8 @@ from . import dtw  # noqa: F401
 from .estimate_snps import estimate_snps, estimate_snps_batch  # noqa: F401
 from .align_signal import align_signal, align_signal_batch  # noqa: F401
 from .seedalign import SeedAligner  # noqa: F401
+from .refset import ReferenceSet  # noqa: F401
 from .kmer_train import estimate_kmer_model  # noqa: F401
 
 __all__ = ['align_signal', 'align_signal_batch', 'estimate_snps', 'estimate_snps_batch', 'dtw', 'SeedAligner',
-           'estimate_kmer_model']
+           'ReferenceSet', 'estimate_kmer_model']

@@ -9,6 +9,8 @@ Extensions over the reference signature, both optional: ``reads`` may hold ``Rea
 fast5 paths), and ``aligner`` injects an approximate aligner (BWA is not available offline)."""
 import sys
 
+import numpy
+
 from . import defaults
 from .alignment import ApproximateAligner
 from .batchflow import align_batch, load_config, load_kmer_model, seg_index
@@ -65,10 +67,15 @@ class AlignedBatch:
     ReadBatch), the (reference position, event start, event end) rows of all reads end to end — read
     ``live[j]`` at rows [ref_off[j], ref_off[j+1]) — the approximate alignment they started from
     (``approximate``: a readbatch.SignalAlignmentBatch) and the per-round linear fits.  The reads' rescaled
-    ``normalized_signal`` stays on the device (``normalized``) until ``normalized_signal(j)`` asks for it."""
+    ``normalized_signal`` stays on the device (``normalized``) until ``normalized_signal(j)`` asks for it.
+    With an aligner over a ``refset.ReferenceSet``: ``contig`` (int32 per live read, an index into ``contig_names``)
+    and reference positions inside that contig; otherwise ``contig`` is 0 and ``contig_names`` None."""
 
-    def __init__(self, live, status, alignment, ref_off, approximate, fits, normalized, sig_off):
+    def __init__(self, live, status, alignment, ref_off, approximate, fits, normalized, sig_off, contig=None,
+                 contig_names=None):
         self.live, self.status, self.alignment, self.ref_off = live, status, alignment, ref_off
+        self.contig = numpy.zeros(len(live), dtype=numpy.int32) if contig is None else contig
+        self.contig_names = contig_names
         self.approximate, self.fits, self.normalized, self.sig_off = approximate, fits, normalized, sig_off
         self.n_aligned = int((status == 0).sum())
 
@@ -92,16 +99,18 @@ def align_signal_batch(reference_filename, read_batch, config=defaults.CONFIG_FI
     the window cutting are tensor operations on the device, and everything between stays there.  ``aligner``: an object with
     ``get_base_alignments(read_batch) -> BaseAlignmentBatch`` and ``reference_num`` (the reference as base
     codes).  -> AlignedBatch."""
-    import numpy
     import torch
     from .device import to_host
+    from .readbatch import contig_local_range
+    from .refset import ReferenceSet
     rb = read_batch
     res = align_batch(rb, load_config(config), load_kmer_model(kmer_model), renorm_rounds, aligner)
     sa, norm, events, status, fits = res.stage.sa, res.stage.norm, res.events, res.status, res.fits
+    names = list(res.stage.reference.names) if isinstance(res.stage.reference, ReferenceSet) else None
     if res.stage.n_live == 0:
         return AlignedBatch(numpy.zeros(0, dtype=numpy.int64), numpy.zeros(0, dtype=numpy.int32),
                             numpy.zeros((0, 3), dtype=numpy.int64), numpy.zeros(1, dtype=numpy.int64), sa, [],
-                            norm, rb.sig_off)
+                            norm, rb.sig_off, contig_names=names)
     device = norm.device
     # the same linear maps for the samples outside the windows (the reference rescales the whole read,
     # align_signal.py:73): per read (x - intercept) / slope, fit after fit, on the device
@@ -119,10 +128,11 @@ def align_signal_batch(reference_filename, read_batch, config=defaults.CONFIG_FI
     n_rows = res.stage.dbatch.total_ref
     owner, inner = seg_index(sa.ref_off, n_rows)
     rows = torch.empty((n_rows, 3), dtype=torch.int64, device=device)
-    rows[:, 0] = torch.where(sa.reverse[owner], sa.ref_end[owner] - inner - 1, sa.ref_start[owner] + inner)
+    ref_start, ref_end = contig_local_range(sa, res.stage.reference)
+    rows[:, 0] = torch.where(sa.reverse[owner], ref_end[owner] - inner - 1, ref_start[owner] + inner)
     start = sa.slice_start[owner]
     rows[:, 1] = events[:, 0] + start
     rows[:, 2] = events[:, 1] + start
     rb.normalized = norm
     return AlignedBatch(sa.live.cpu().numpy(), status.cpu().numpy(), to_host(rows), sa.ref_off.cpu().numpy(),
-                        sa, [f.cpu().numpy() for f in fits], norm, rb.sig_off)
+                        sa, [f.cpu().numpy() for f in fits], norm, rb.sig_off, sa.contig.cpu().numpy(), names)

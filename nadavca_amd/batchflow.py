@@ -72,15 +72,17 @@ class DeviceStage:
     """What ``device_stage`` leaves on the device.  ``norm``: the normalised signals of all reads (f64, layout of
     ``raw_signal``); ``group_off``: the offsets of the groups they were normalised in ('read': the reads' ``sig_off``;
     'pooled': [0, total]; 'ranks': None); ``sa``: the readbatch.SignalAlignmentBatch; ``n_live``: the reads with an
-    anchor; ``dbatch``: their windows as a device.DeviceBatch (None when ``n_live == 0``)."""
-    __slots__ = ('norm', 'group_off', 'sa', 'n_live', 'dbatch')
+    anchor; ``dbatch``: their windows as a device.DeviceBatch (None when ``n_live == 0``); ``reference``: what ``sa``
+    was made against, base codes or a refset.ReferenceSet."""
+    __slots__ = ('norm', 'group_off', 'sa', 'n_live', 'dbatch', 'reference')
 
 
 def device_stage(read_batch, reference_num, config, kmer_model, aligner, mode, group=None):
     """The raw signals of ``read_batch`` to the device in their own dtype, widened and normalised there in place —
     ``mode`` 'read': per read (align_signal.py:54); 'pooled': one median / MAD over all reads (estimate_snps.py:61);
     'ranks': the same over the shards of all ranks of ``group`` — then the approximate-alignment stage
-    (``get_base_alignments``, ``signal_alignments`` against ``reference_num``) and the windows.  -> DeviceStage."""
+    (``get_base_alignments``, ``signal_alignments`` against ``reference_num``, or against the aligner's
+    ``reference_set`` when it has one: its pairs are contig-local then) and the windows.  -> DeviceStage."""
     import torch
     from . import readbatch
     from .device import DeviceBatch, normalize_groups_dev
@@ -105,7 +107,10 @@ def device_stage(read_batch, reference_num, config, kmer_model, aligner, mode, g
     else:
         raise ValueError("device_stage: mode 'read', 'pooled' or 'ranks'")
     ba = aligner.get_base_alignments(rb)
-    st.sa = readbatch.signal_alignments(rb, ba, config['bandwidth'], reference_num, kmer_model.get_k(),
+    st.reference = reference_num
+    if getattr(aligner, 'reference_set', None) is not None:
+        st.reference = aligner.reference_set
+    st.sa = readbatch.signal_alignments(rb, ba, config['bandwidth'], st.reference, kmer_model.get_k(),
                                         kmer_model.get_central_position(), device=device)
     st.n_live = int(st.sa.live.numel())
     st.dbatch = DeviceBatch.from_windows(st.norm, st.sa, device) if st.n_live else None

@@ -15,6 +15,12 @@
 // Lane 0 then walks the traceback; the pairs are written backwards from the read's last slot and the wave moves
 // them down to start at q_off[j].  Nothing here depends on which reads share a launch, so the host may cut a batch
 // into chunks when the store does not fit (nvk_seed_extend_dev).
+//
+// nvk_seed_extend_bounded_dev runs the same kernel with a reference range [ref_lo, ref_hi) per read, in coordinates of
+// the read's strand (a contig of a multi-contig reference, nadavca_amd/refset.py): the two bounds are scalars of the
+// wave like the read itself, and the sweep counts its columns from ref_lo, so its inner loop is the same for both
+// entries.  The one kernel body is compiled twice (seedext_kernel<BOUNDED>): without bounds it is, instruction for
+// instruction, the kernel it was before there were any.
 #include <vector>
 
 #include "nvk_internal.h"
@@ -40,6 +46,7 @@ struct SeedArgs {
   const int64_t *tb_off;     // per read, its first dword in the batch-wide numbering
   int r0, r1;                // the chunk's reads
   int *counter;
+  const int32_t *ref_lo, *ref_hi;  // seedext_kernel<true>: per read, the range of its cells' j on its strand
 };
 
 __device__ __forceinline__ int dpp_ror1(int v) { return __builtin_amdgcn_mov_dpp(v, 0x13C, 0xf, 0xf, false); }
@@ -55,6 +62,9 @@ __device__ __forceinline__ int ref_code(const int32_t *ref, int G, int st, int j
   return c >= 0 && c <= 3 ? (st ? 3 - c : c) : -1;
 }
 
+// BOUNDED: every read has its own column range (nvk_seed_extend_bounded_dev); otherwise the range is the whole strand
+// and the compiled kernel is the one nvk_seed_extend_dev always ran.
+template <bool BOUNDED>
 __global__ __launch_bounds__(64) void seedext_kernel(SeedArgs a) {
   __shared__ int32_t s_ref[64 + 2 * SEED_WMAX];     // r[jbase + x], x = lane + b
   __shared__ int32_t s_h[2 * SEED_WMAX + 2];        // H and F of the previous strip's last row, by band offset
@@ -80,9 +90,16 @@ __global__ __launch_bounds__(64) void seedext_kernel(SeedArgs a) {
     const int G = a.G;
     int bh = -1, bi = -1, bj = -1;  // this lane's best cell: largest H, then smallest i, then smallest j
     const int64_t dd = a.diag[rd];
-    // any cell at all: the band [d* - w, d* + w] meets the diagonals -(m-1) .. G-1 of the matrix
-    const bool run = (st == 0 || st == 1) && m > 0 && G > 0 && dd - w <= G - 1 && dd + w >= -(int64_t)(m - 1);
-    const int lo = run ? (int)(dd - w) : 0;
+    // the read's columns [rlo, rlo + Gr) on its strand: wave-uniform, as the read is.  Below, j counts columns from
+    // rlo, so that the sweep and the traceback compare it with 0 and Gr exactly as they do for the whole reference
+    // (rlo = 0, Gr = G); only the staging of the strand and what is reported add rlo back.
+    const int rlo = BOUNDED ? __builtin_amdgcn_readfirstlane(a.ref_lo[rd]) : 0;
+    const int Gr = BOUNDED ? __builtin_amdgcn_readfirstlane(a.ref_hi[rd]) - rlo : G;
+    // any cell at all: the band [d* - w, d* + w] meets the diagonals rlo-(m-1) .. rlo+Gr-1 of the matrix
+    const bool run = (st == 0 || st == 1) && m > 0 && Gr > 0 && dd - w <= rlo + Gr - 1 &&
+                     dd + w >= rlo - (int64_t)(m - 1);
+    const int lo = run ? (int)(dd - w) : 0;  // the band's first diagonal on the strand
+    const int lor = lo - rlo;                // and counted from rlo
     uint32_t *tb = a.tb + a.tb_off[rd];
     const int n_strips = run ? (m + 63) / 64 : 0;
     for (int s = 0; s < n_strips; s++) {
@@ -106,8 +123,8 @@ __global__ __launch_bounds__(64) void seedext_kernel(SeedArgs a) {
         fu = lane == 0 ? lf : fu;
         const int hd = hu_prev;                  // (i-1, b): what arrived one step ago
         hu_prev = hu;
-        const int j = i + lo + b;
-        const bool cell = b >= 0 && b <= W2 && i < m && j >= 0 && j < G;
+        const int j = i + lor + b;
+        const bool cell = b >= 0 && b <= W2 && i < m && j >= 0 && j < Gr;
         const int rj = s_ref[min(max(lane + b, 0), 63 + W2)];
         const int D = ((i > 0 && j > 0) ? hd : 0) + (qi == rj ? a.match : -a.mismatch);
         const bool lok = b >= 1 && j >= 1;       // (i, j-1) is a cell
@@ -161,7 +178,7 @@ __global__ __launch_bounds__(64) void seedext_kernel(SeedArgs a) {
       // q0 + m - 1 - k, so they end up ascending
       int i = bi, j = bj, state = 0;  // 0: H, 1: E, 2: F
       for (;;) {
-        const int b = j - i - lo;
+        const int b = j - i - lor;
         // (the rules keep the walk on cells of the band; the guard keeps every access in bounds regardless)
         if (i < 0 || j < 0 || b < 0 || b > W2 || cnt >= m) break;
         const uint32_t nib = (tb[((int64_t)(i >> 6) * C + (b >> 3)) * 64 + (i & 63)] >> (4 * (b & 7))) & 15u;
@@ -169,8 +186,8 @@ __global__ __launch_bounds__(64) void seedext_kernel(SeedArgs a) {
           const uint32_t src = nib & 3u;
           if (src == 0) break;
           if (src == 1) {
-            if (query_code(a.query, q0 + i) == ref_code(a.reference, G, st, j)) {
-              if (lane == 0) a.out_pairs[q0 + m - 1 - cnt] = make_int2(i, j);
+            if (query_code(a.query, q0 + i) == ref_code(a.reference, G, st, j + rlo)) {
+              if (lane == 0) a.out_pairs[q0 + m - 1 - cnt] = make_int2(i, j + rlo);
               cnt++;
             }
             if (i == 0 || j == 0) break;
@@ -202,18 +219,19 @@ __global__ __launch_bounds__(64) void seedext_kernel(SeedArgs a) {
         if (x < cnt) a.out_pairs[q0 + x] = p;
         __syncthreads();
       }
-    if (lane == 0) *(int4 *)(a.out_hit + 4 * rd) = make_int4(score, bh >= 0 ? bi : -1, bh >= 0 ? bj : -1, cnt);
+    if (lane == 0)
+      *(int4 *)(a.out_hit + 4 * rd) = make_int4(score, bh >= 0 ? bi : -1, bh >= 0 ? bj + rlo : -1, cnt);
   }
 }
 
 }  // namespace
 
-extern "C" int nvk_seed_extend_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_query, const int32_t *query,
-                                   const int64_t *q_off, const int32_t *reference, int64_t ref_len,
-                                   const int32_t *strand, const int32_t *diag, int band, int match, int mismatch,
-                                   int gap_open, int gap_extend, int min_score, int32_t *out_hit,
-                                   int32_t *out_pairs) {
-  const char *what = "nvk_seed_extend_dev";
+// both entries: ``bounded`` takes ref_lo / ref_hi (checked on the host, as q_off is), the other passes none
+static int seed_extend(const char *what, bool bounded, nvk_ctx *ctx, int64_t n_reads, int64_t total_query,
+                       const int32_t *query, const int64_t *q_off, const int32_t *reference, int64_t ref_len,
+                       const int32_t *strand, const int32_t *diag, const int32_t *ref_lo, const int32_t *ref_hi,
+                       int band, int match, int mismatch, int gap_open, int gap_extend, int min_score,
+                       int32_t *out_hit, int32_t *out_pairs) {
   if (!ctx) {
     nvk_set_error("%s: ctx is NULL", what);
     return NVK_ERR_INVALID;
@@ -259,10 +277,26 @@ extern "C" int nvk_seed_extend_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_
     nvk_set_error("%s: NULL strand, diagonal or output", what);
     return NVK_ERR_INVALID;
   }
+  if (bounded && (!ref_lo || !ref_hi)) {
+    nvk_set_error("%s: NULL ref_lo or ref_hi", what);
+    return NVK_ERR_INVALID;
+  }
   // the traceback store: per read ceil(m / 64) strips of ceil((2w + 1) / 8) dwords per lane, for the reads that run
   std::vector<int32_t> st((size_t)n_reads);
   NVK_HIP(hipMemcpyAsync(st.data(), strand, st.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   NVK_HIP(hipStreamSynchronize(ctx->stream));
+  if (bounded) {
+    std::vector<int32_t> lo((size_t)n_reads), hi((size_t)n_reads);
+    NVK_HIP(hipMemcpyAsync(lo.data(), ref_lo, lo.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    NVK_HIP(hipMemcpyAsync(hi.data(), ref_hi, hi.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    NVK_HIP(hipStreamSynchronize(ctx->stream));
+    for (int64_t r = 0; r < n_reads; r++)
+      if (st[r] != -1 && (lo[r] < 0 || hi[r] > ref_len || lo[r] > hi[r])) {
+        nvk_set_error("%s: read %lld has the reference range [%d, %d), outside 0 <= lo <= hi <= %lld", what,
+                      (long long)r, lo[r], hi[r], (long long)ref_len);
+        return NVK_ERR_INVALID;
+      }
+  }
   const int64_t row_dw = (2 * band + 8) / 8 * 64;
   std::vector<int64_t> tb_off((size_t)n_reads + 1, 0);
   for (int64_t r = 0; r < n_reads; r++) {
@@ -295,6 +329,8 @@ extern "C" int nvk_seed_extend_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_
   a.G = (int)ref_len;
   a.strand = strand;
   a.diag = diag;
+  a.ref_lo = bounded ? ref_lo : nullptr;
+  a.ref_hi = bounded ? ref_hi : nullptr;
   a.w = band;
   a.match = match;
   a.mismatch = mismatch;
@@ -313,11 +349,34 @@ extern "C" int nvk_seed_extend_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_
       a.tb = (uint32_t *)ctx->ws[WS_SEED_TB] - tb_off[cut[c]];
       const int64_t want = a.r1 - a.r0, resident = (int64_t)(ctx->num_cus > 0 ? ctx->num_cus : 256) * 16;
       NVK_HIP(hipMemsetAsync(d_counter, 0, sizeof(int), ctx->stream));
-      hipLaunchKernelGGL(seedext_kernel, dim3((unsigned)(want < resident ? want : resident)), dim3(64), 0,
-                         ctx->stream, a);
+      const dim3 grid((unsigned)(want < resident ? want : resident));
+      if (bounded)
+        hipLaunchKernelGGL(seedext_kernel<true>, grid, dim3(64), 0, ctx->stream, a);
+      else
+        hipLaunchKernelGGL(seedext_kernel<false>, grid, dim3(64), 0, ctx->stream, a);
       NVK_HIP(hipGetLastError());
     }
   }
   NVK_HIP(hipStreamSynchronize(ctx->stream));
   return NVK_OK;
+}
+
+extern "C" int nvk_seed_extend_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_query, const int32_t *query,
+                                   const int64_t *q_off, const int32_t *reference, int64_t ref_len,
+                                   const int32_t *strand, const int32_t *diag, int band, int match, int mismatch,
+                                   int gap_open, int gap_extend, int min_score, int32_t *out_hit,
+                                   int32_t *out_pairs) {
+  return seed_extend("nvk_seed_extend_dev", false, ctx, n_reads, total_query, query, q_off, reference, ref_len, strand,
+                     diag, nullptr, nullptr, band, match, mismatch, gap_open, gap_extend, min_score, out_hit,
+                     out_pairs);
+}
+
+extern "C" int nvk_seed_extend_bounded_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_query, const int32_t *query,
+                                           const int64_t *q_off, const int32_t *reference, int64_t ref_len,
+                                           const int32_t *strand, const int32_t *diag, const int32_t *ref_lo,
+                                           const int32_t *ref_hi, int band, int match, int mismatch, int gap_open,
+                                           int gap_extend, int min_score, int32_t *out_hit, int32_t *out_pairs) {
+  return seed_extend("nvk_seed_extend_bounded_dev", true, ctx, n_reads, total_query, query, q_off, reference, ref_len,
+                     strand, diag, ref_lo, ref_hi, band, match, mismatch, gap_open, gap_extend, min_score, out_hit,
+                     out_pairs);
 }

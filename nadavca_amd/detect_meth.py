@@ -121,17 +121,23 @@ class MethBatch:
     ascending position — the rows ``detect_meth`` writes — as flat arrays: ``read`` (index in the ReadBatch),
     ``position`` (in the read's reference part), ``context`` (``seq[p-5:p+6]``), ``scores`` (n, 11), ``aggregate``
     (the largest sum of three consecutive scores); and per aligned read (``live``: its index in the ReadBatch) its
-    ``status`` (``_lib.READ_*``; a read with status != 0 has no rows), as in ``AlignedBatch``."""
+    ``status`` (``_lib.READ_*``; a read with status != 0 has no rows), as in ``AlignedBatch``.  ``contig`` (int32 per
+    row): the contig of the row's read, an index into ``contig_names`` with an aligner over a ``refset.ReferenceSet``
+    (0 and None otherwise); ``position`` is relative to the read's reference part either way, and ``write_csv`` keeps
+    ``detect_meth``'s columns."""
 
-    def __init__(self, read, position, context, scores, aggregate, status, live):
+    def __init__(self, read, position, context, scores, aggregate, status, live, contig=None, contig_names=None):
         self.read, self.position, self.context = read, position, context
+        self.contig = np.zeros(len(read), dtype=np.int32) if contig is None else contig
+        self.contig_names = contig_names
         self.scores, self.aggregate, self.status, self.live = scores, aggregate, status, live
 
     @classmethod
-    def empty(cls, status=None, live=None):
+    def empty(cls, status=None, live=None, contig_names=None):
         z = lambda dt: np.zeros(0, dtype=dt)
         return cls(z(np.int64), z(np.int64), z('U%d' % (2 * FLANK + 1)), np.zeros((0, 2 * FLANK + 1)), z(np.float64),
-                   z(np.int32) if status is None else status, z(np.int64) if live is None else live)
+                   z(np.int32) if status is None else status, z(np.int64) if live is None else live,
+                   contig_names=contig_names)
 
     def __len__(self):
         return int(self.position.size)
@@ -165,10 +171,12 @@ def detect_meth_batch(reference_filename, read_batch, pattern, config=defaults.C
     import torch
     from .batchflow import align_batch, load_config, load_kmer_model, seg_index
     from .device import event_means_dev, expected_levels_dev, meth_scores_dev, to_host
+    from .refset import ReferenceSet
     kmer_model = load_kmer_model(kmer_model)
     res = align_batch(read_batch, load_config(config), kmer_model, renorm_rounds, aligner)
+    names = list(res.stage.reference.names) if isinstance(res.stage.reference, ReferenceSet) else None
     if res.stage.n_live == 0:
-        return MethBatch.empty()
+        return MethBatch.empty(contig_names=names)
     sa, dbatch, events, status = res.stage.sa, res.stage.dbatch, res.events, res.status
     context = kmer_model.context
     live = sa.live.cpu().numpy()
@@ -179,7 +187,7 @@ def detect_meth_batch(reference_filename, read_batch, pattern, config=defaults.C
                                                 pattern_codes(pattern))
     n_occ = int(pos.numel())
     if n_occ == 0:
-        return MethBatch.empty(status.cpu().numpy(), live)
+        return MethBatch.empty(status.cpu().numpy(), live, names)
     dev = pos.device
     owner, _ = seg_index(occ_off, n_occ)
     # the 11 bases around each occurrence, 2 bits each in one integer (exact in a double: 22 bits)
@@ -193,7 +201,8 @@ def detect_meth_batch(reference_filename, read_batch, pattern, config=defaults.C
     W = 2 * FLANK + 1
     codes = (table[:, W + 3].astype(np.int64)[:, None] >> np.arange(2 * (W - 1), -1, -2)) & 3
     return MethBatch(table[:, W + 2].astype(np.int64), table[:, W + 1].astype(np.int64), contexts_from_codes(codes),
-                     np.ascontiguousarray(table[:, :W]), np.ascontiguousarray(table[:, W]), status.cpu().numpy(), live)
+                     np.ascontiguousarray(table[:, :W]), np.ascontiguousarray(table[:, W]), status.cpu().numpy(), live,
+                     sa.contig[owner].cpu().numpy(), names)
 
 
 def detect_meth_command(args):

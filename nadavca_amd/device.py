@@ -312,11 +312,13 @@ def meth_scores_dev(context, reference, ref_off, means, expected, status, patter
 
 
 def seed_extend_dev(context, query, q_off, reference, strand, diagonal, band, match, mismatch, gap_open, gap_extend,
-                    min_score):
+                    min_score, ref_lo=None, ref_hi=None):
     """The extension stage of the seed aligner (nadavca_amd/seedalign.py) for every read of a batch, on the device:
     banded affine-gap local alignment of read j (``query`` / ``q_off``: int32 codes / int64 offsets) against strand
     ``strand[j]`` (0 forward, 1 reverse complement, -1 skip) of ``reference`` (int32 codes, forward) around diagonal
     ``diagonal[j]``, traceback and matched pairs (include/nadavca_hip.h: nvk_seed_extend_dev).  Device tensors.
+    ``ref_lo`` / ``ref_hi`` (int32 per read, both or neither): the read's cells lie in the columns
+    ref_lo[j] <= j < ref_hi[j] of its strand (nvk_seed_extend_bounded_dev); None: the whole reference.
     -> (score i32 (n,), end i32 (n, 2), count i32 (n,), pairs i32 (total, 2)); read j's pairs are
     pairs[q_off[j] : q_off[j] + count[j]], ascending (the other rows are unspecified)."""
     import torch
@@ -335,10 +337,20 @@ def seed_extend_dev(context, query, q_off, reference, strand, diagonal, band, ma
         reference = torch.zeros(1, dtype=torch.int32, device=dev)
     hit = torch.zeros((max(n, 0), 4), dtype=torch.int32, device=dev)
     pairs = torch.empty((max(total, 1), 2), dtype=torch.int32, device=dev)
-    _lib.check(lib.nvk_seed_extend_dev(context.handle, n, total, _dp(query), _dp(q_off), _dp(reference), G,
-                                       _dp(strand), _dp(diagonal), int(band), int(match), int(mismatch),
-                                       int(gap_open), int(gap_extend), int(min_score), _dp(hit), _dp(pairs)),
-               'nvk_seed_extend_dev')
+    scoring = (int(band), int(match), int(mismatch), int(gap_open), int(gap_extend), int(min_score))
+    if ref_lo is None and ref_hi is None:
+        _lib.check(lib.nvk_seed_extend_dev(context.handle, n, total, _dp(query), _dp(q_off), _dp(reference), G,
+                                           _dp(strand), _dp(diagonal), *scoring, _dp(hit), _dp(pairs)),
+                   'nvk_seed_extend_dev')
+    else:
+        if ref_lo is None or ref_hi is None or int(ref_lo.numel()) != n or int(ref_hi.numel()) != n:
+            raise ValueError('seed_extend_dev: ref_lo and ref_hi go together, one value per read each')
+        ref_lo, ref_hi = i32(ref_lo), i32(ref_hi)
+        if n == 0:
+            ref_lo = ref_hi = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.nvk_seed_extend_bounded_dev(context.handle, n, total, _dp(query), _dp(q_off), _dp(reference),
+                                                   G, _dp(strand), _dp(diagonal), _dp(ref_lo), _dp(ref_hi), *scoring,
+                                                   _dp(hit), _dp(pairs)), 'nvk_seed_extend_bounded_dev')
     return hit[:, 0], hit[:, 1:3], hit[:, 3], pairs[:total]
 
 

@@ -60,16 +60,20 @@ last_batch_counts = {}
 class IndependentChunks:
     """``estimate_snps(independent=True)`` for a batch: one chunk per read that produced one, as arrays —
     read ``reads[j]`` covers reference positions [start[j], end[j]) and has posterior rows
-    values[row_off[j]:row_off[j+1]] (coverage is 1 everywhere, as in the reference's per-read call)."""
+    values[row_off[j]:row_off[j+1]] (coverage is 1 everywhere, as in the reference's per-read call).  For a
+    ``refset.ReferenceSet``: ``contig[j]`` (an index into ``contig_names``) is the read's contig and ``start`` / ``end``
+    are positions inside it; for a plain array ``contig`` is None."""
 
-    def __init__(self, reads, start, end, values, row_off):
+    def __init__(self, reads, start, end, values, row_off, contig=None, contig_names=None):
         self.reads, self.start, self.end, self.values, self.row_off = reads, start, end, values, row_off
+        self.contig, self.contig_names = contig, contig_names
 
     def __len__(self):
         return len(self.reads)
 
     def chunk(self, j):
-        return Chunk(int(self.start[j]), int(self.end[j]), self.values[self.row_off[j]:self.row_off[j + 1]])
+        return Chunk(int(self.start[j]), int(self.end[j]), self.values[self.row_off[j]:self.row_off[j + 1]],
+                     contig=None if self.contig is None else self.contig_names[int(self.contig[j])])
 
 
 def estimate_snps_batch(reference_num, read_batch, config=defaults.CONFIG_FILE,
@@ -81,7 +85,10 @@ def estimate_snps_batch(reference_num, read_batch, config=defaults.CONFIG_FILE,
     ``spline_fit='host'`` sends its fit to scipy in ``fit_workers`` processes instead), log-likelihoods, normalise /
     strand-flip / per-position sum, grouping, posterior — with the signals, the sums and everything between them
     resident on the device.
-    ``reference_num``: the reference as base codes; ``aligner``: as for ``align_signal_batch``.
+    ``reference_num``: the reference as base codes, or a ``refset.ReferenceSet`` (it must hold the aligner's
+    ``reference_num`` as its concatenation, else ValueError): the median / MAD and the consensus then run over all
+    contigs at once, no chunk spans two contigs (touching chunks do not merge), and every Chunk carries its contig's
+    name in ``.contig`` with ``start`` / ``end`` inside that contig.  ``aligner``: as for ``align_signal_batch``.
     -> list of Chunk (consensus) or IndependentChunks.
 
     Several GPUs (``distributed=True``, or a ``group``; default: whenever torch.distributed is initialised with
@@ -100,15 +107,32 @@ def estimate_snps_batch(reference_num, read_batch, config=defaults.CONFIG_FILE,
         raise ValueError('estimate_snps_batch needs a batch aligner (BWA has no batch adapter offline)')
     context = kmer_model.context
     device = torch.device('cuda', context.device)
+    from .readbatch import contig_local_range
+    from .refset import ReferenceSet
+    refset = reference_num if isinstance(reference_num, ReferenceSet) else None
+    if refset is not None:
+        if not numpy.array_equal(refset.codes, numpy.asarray(aligner.reference_num).reshape(-1)):
+            raise ValueError("estimate_snps_batch: the ReferenceSet's concatenation differs from the aligner's "
+                             'reference_num')
+        reference_num = refset.codes
     reference_num = numpy.ascontiguousarray(reference_num, dtype=numpy.int32)
     L = reference_num.size
+
+    def localise(chunks):
+        # consensus chunks in global positions -> inside their contig, named (every rank holds the same set)
+        if refset is None or chunks is None:
+            return chunks
+        for ch in chunks:
+            c, s = refset.locate(ch.start)
+            ch.start, ch.end, ch.contig = int(s), int(s + (ch.end - ch.start)), refset.names[int(c)]
+        return chunks
     if distributed is None:
         distributed = group is not None
         if not distributed:
             import torch.distributed as tdist
             distributed = tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1
     # all reads pooled, of ALL ranks when distributed (estimate_snps.py:61)
-    stage = device_stage(read_batch, reference_num, config, kmer_model, aligner,
+    stage = device_stage(read_batch, reference_num if refset is None else refset, config, kmer_model, aligner,
                          'ranks' if distributed else 'pooled', group)
     sa, dbatch, n_live = stage.sa, stage.dbatch, stage.n_live
     last_batch_counts.clear()
@@ -116,14 +140,16 @@ def estimate_snps_batch(reference_num, read_batch, config=defaults.CONFIG_FILE,
     if n_live == 0:
         if independent:
             return IndependentChunks(numpy.zeros(0, dtype=numpy.int64), *[numpy.zeros(0)] * 3,
-                                     numpy.zeros(1, dtype=numpy.int64))
+                                     numpy.zeros(1, dtype=numpy.int64),
+                                     None if refset is None else numpy.zeros(0, dtype=numpy.int32),
+                                     None if refset is None else list(refset.names))
         if not distributed:
             return []
         # (a rank whose shard aligned nowhere still takes part in the exchange, with empty sums)
         acc = torch.zeros((L, kmer_model.alphabet_size), dtype=torch.float64, device=device)
         cov = torch.zeros(L, dtype=torch.int64, device=device)
-        return consensus_chunks(kmer_model, config['snp_prior_probability'], reference_num, acc, cov, [], True,
-                                group, dst)
+        return localise(consensus_chunks(kmer_model, config['snp_prior_probability'], reference_num, acc, cov, [],
+                                         True, group, dst))
     if config['tweak_signal_normalization']:
         last_batch_counts['reads_fitted'] = tweak_signal_normalization(context, kmer_model, dbatch, config,
                                                                        fit_workers, spline_fit)
@@ -139,9 +165,11 @@ def estimate_snps_batch(reference_num, read_batch, config=defaults.CONFIG_FILE,
         owner, inner = seg_index(sa.ref_off, dbatch.total_ref)
         codes = torch.from_numpy(reference_num).to(device)[sa.ref_start[owner] + inner]
         okh, values, row_off = independent_posteriors(kmer_model, prior, nel, dbatch, ll, status, rev32, codes)
-        return IndependentChunks(sa.live.cpu().numpy()[okh], sa.ref_start.cpu().numpy()[okh],
-                                 sa.ref_end.cpu().numpy()[okh], values, row_off)
+        start, end = contig_local_range(sa, reference_num if refset is None else refset)
+        return IndependentChunks(sa.live.cpu().numpy()[okh], start.cpu().numpy()[okh], end.cpu().numpy()[okh], values,
+                                 row_off, None if refset is None else sa.contig.cpu().numpy()[okh],
+                                 None if refset is None else list(refset.names))
     acc, cov = consensus_accumulate_dev(context, dbatch, ll, sa.ref_start.contiguous(), rev32, status, nel, L)
     starts, ends = sa.ref_start[ok].cpu().numpy(), sa.ref_end[ok].cpu().numpy()
-    return consensus_chunks(kmer_model, prior, reference_num, acc, cov, list(zip(starts.tolist(), ends.tolist())),
-                            distributed, group, dst)
+    return localise(consensus_chunks(kmer_model, prior, reference_num, acc, cov,
+                                     list(zip(starts.tolist(), ends.tolist())), distributed, group, dst))

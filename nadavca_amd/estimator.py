@@ -22,11 +22,12 @@ from .genome import Genome
 
 
 class Chunk:
-    def __init__(self, start, end, values, coverage=None):
+    def __init__(self, start, end, values, coverage=None, contig=None):
         self.start = start
         self.end = end
         self.values = values
         self.coverage = coverage
+        self.contig = contig   # the contig's name where the reference was a refset.ReferenceSet (start / end local)
         if coverage is None:
             self.coverage = numpy.ones(end - start, dtype=int)
 

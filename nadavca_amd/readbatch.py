@@ -66,20 +66,29 @@ class BaseAlignmentBatch:
     """Matched bases of all reads: pair p of read j (pairs [off[j], off[j+1])) says read base
     ``read_idx[p]`` sits on reference base ``ref_idx[p]``, both in the READ's orientation (for a
     reverse-complement hit the reference index counts from the reference's end, alignment.py:128-134).
-    ``reverse[j]``: the read is on the reverse strand; a read without pairs did not align."""
+    ``reverse[j]``: the read is on the reverse strand; a read without pairs did not align.
+    ``contig`` (optional, int32 per read): the read's contig in a ``refset.ReferenceSet``; ``ref_idx`` is then
+    contig-local (for a reverse-complement hit counted from the contig's end: what the reference's aligner returns
+    per contig, alignment.py:116-140).  None: one sequence, as before."""
 
-    def __init__(self, read_idx, ref_idx, off, reverse):
+    def __init__(self, read_idx, ref_idx, off, reverse, contig=None):
         self.read_idx = np.ascontiguousarray(read_idx, dtype=np.int32)   # a position inside one read
         self.ref_idx = np.ascontiguousarray(ref_idx, dtype=np.int64)
         self.off = np.ascontiguousarray(off, dtype=np.int64)
         self.reverse = np.ascontiguousarray(reverse, dtype=bool)
+        self.contig = None if contig is None else np.ascontiguousarray(contig, dtype=np.int32)
+        if self.contig is not None and self.contig.shape != self.reverse.shape:
+            raise ValueError('BaseAlignmentBatch: contig holds %d entries for %d reads'
+                             % (self.contig.size, self.reverse.size))
 
 
 class SignalAlignmentBatch:
     """The per-read results of ``get_signal_alignment`` (alignment.py:142-186) and ``_get_read_context``
     (estimator.py:49-57) for the ``live`` reads (those with at least one anchor), flat; torch tensors on the
-    device the stage ran on (``host()`` -> the same with numpy arrays)."""
-    FIELDS = ('live', 'anchors', 'anc_off', 'win_start', 'win_len', 'slice_start', 'ref_start', 'ref_end',
+    device the stage ran on (``host()`` -> the same with numpy arrays).  ``ref_start`` / ``ref_end`` are forward
+    positions of the whole reference — of the concatenation for a ``refset.ReferenceSet``, where ``contig`` (int32)
+    says which contig the read lies in (0 for one sequence) and ``contig_local_range`` gives the range inside it."""
+    FIELDS = ('live', 'contig', 'anchors', 'anc_off', 'win_start', 'win_len', 'slice_start', 'ref_start', 'ref_end',
               'reverse', 'read_seq_start', 'read_seq_end', 'reference', 'ref_off', 'context_before',
               'cb_off', 'context_after', 'ca_off')
     __slots__ = FIELDS
@@ -92,8 +101,22 @@ class SignalAlignmentBatch:
         return out
 
 
+def contig_local_range(sa, reference):
+    """``sa.ref_start`` / ``sa.ref_end`` inside the reads' contigs: -> (start, end), tensors like them.  ``reference``:
+    what ``signal_alignments`` was given (a plain array: the range itself)."""
+    import torch
+    from .refset import ReferenceSet
+    if not isinstance(reference, ReferenceSet):
+        return sa.ref_start, sa.ref_end
+    first = torch.from_numpy(reference.offsets).to(sa.ref_start.device)[sa.contig.to(torch.int64)]
+    return sa.ref_start - first, sa.ref_end - first
+
+
 def signal_alignments(rb, ba, bandwidth, reference_num, k, central, device='cpu'):
-    """-> SignalAlignmentBatch.  ``reference_num``: the reference as base codes.  Per read, exactly the
+    """-> SignalAlignmentBatch.  ``reference_num``: the reference as base codes, or a ``refset.ReferenceSet``: the pairs
+    of a ``ba`` that carries ``contig`` are then lifted from contig-local to the set's global oriented coordinates
+    first (refset.py) and everything below runs on the concatenation (a ``contig`` without a ReferenceSet, a contig
+    index outside the set on a read with pairs, or pairs outside their contig raise ValueError).  Per read, exactly the
     arithmetic of the reference: anchors = matched bases the basecaller placed on the signal; reference range
     from the first and last anchor (reported on the forward strand); signal window = anchors' sample span
     +- bandwidth, clipped to the read; reference part = that range, reverse-complemented for a reverse-strand
@@ -106,7 +129,11 @@ def signal_alignments(rb, ba, bandwidth, reference_num, k, central, device='cpu'
     # (each table crosses to the device in the dtype it is kept in and is widened there)
     T = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(dev).to(dt)
     i64 = torch.int64
-    ref_num = T(reference_num, torch.int32)
+    from .refset import ReferenceSet
+    refset = reference_num if isinstance(reference_num, ReferenceSet) else None
+    if refset is None and ba.contig is not None:
+        raise ValueError('signal_alignments: the base alignments carry contigs, the reference is not a ReferenceSet')
+    ref_num = T(reference_num if refset is None else refset.codes, torch.int32)
     L = int(ref_num.numel())
     n = rb.n
     seq_off, sig_off_r, map_off, ba_off = T(rb.seq_off, i64), T(rb.sig_off, i64), T(rb.map_off, i64), T(ba.off, i64)
@@ -125,6 +152,18 @@ def signal_alignments(rb, ba, bandwidth, reference_num, k, central, device='cpu'
     ok = (map_base >= 0) & (map_base < seq_len_all[m_owner])
     sig_of_base[(seq_off[:-1][m_owner] + map_base)[ok]] = map_sig[ok]
     p_owner, _ = seg_index(ba_off)
+    contig_all = None
+    if ba.contig is not None:
+        contig_all = T(ba.contig, i64)
+        c_off = T(refset.offsets, i64)
+        n_contigs = refset.n_contigs
+        has_pairs = ba_off[1:] > ba_off[:-1]
+        if bool((has_pairs & ((contig_all < 0) | (contig_all >= n_contigs))).any()):
+            raise ValueError('signal_alignments: a read with pairs has a contig index outside 0..%d' % (n_contigs - 1))
+        pc = contig_all[p_owner]           # (only reads with pairs own one: every index is valid)
+        if bool(((ref_idx < 0) | (ref_idx >= c_off[pc + 1] - c_off[pc])).any()):
+            raise ValueError('signal_alignments: a pair lies outside its contig')
+        ref_idx = ref_idx + torch.where(reverse_all[p_owner], L - c_off[pc + 1], c_off[pc])
     inside = (read_idx >= 0) & (read_idx < seq_len_all[p_owner])
     g = torch.where(inside, seq_off[:-1][p_owner] + read_idx, seq_off[-1])
     sig = sig_of_base[g]
@@ -142,6 +181,12 @@ def signal_alignments(rb, ba, bandwidth, reference_num, k, central, device='cpu'
     out.ref_start = torch.where(rev, L - end_ref_o, start_ref_o)
     out.ref_end = torch.where(rev, L - start_ref_o, end_ref_o)
     out.reverse = rev
+    if contig_all is not None:
+        out.contig = contig_all[live].to(torch.int32)
+    elif refset is not None:
+        out.contig = refset.locate(out.ref_start)[0].to(torch.int32)
+    else:
+        out.contig = torch.zeros(live.numel(), dtype=torch.int32, device=dev)
     start_sig, end_sig = k_sig[first], k_sig[last] + 1
     sig_len = (sig_off_r[1:] - sig_off_r[:-1])[live]
     out.slice_start = torch.clamp(start_sig - bandwidth, min=0)

@@ -13,14 +13,21 @@ only aligned columns whose two bases are equal (alignment.py:118-138, ``alignmen
    window c scores n(c) + n(c+1) seeds (diagonals [c w, (c+2) w)).  Each strand takes its best window (smallest c on a
    tie), the read its better strand (forward on a tie); below ``min_seeds`` the read is unaligned, else the band
    centre d* is the lower median of the window's seed diagonals (index (n-1)//2 of them sorted).
+   Several contigs (a ``refset.ReferenceSet``): the strands are those of the concatenation, in its global coordinates;
+   a strand k-mer whose k bases do not lie in one contig is not indexed, and seeding and the vote are otherwise the
+   same, on global diagonals.  The read's contig: on the chosen strand x* = clamp(d* + (m - 1) // 2, 0, G - 1), m the
+   read's length — where its middle base lands on the voted diagonal — and the contig is the one whose range on that
+   strand, [lo, hi), contains x* (``contig_of``).  The extension sees only the columns lo <= j < hi.
 2. Banded affine-gap local alignment around d* and 3. traceback, in the HIP kernel ``nvk_seed_extend_dev``
-   (include/nadavca_hip.h states the rules; nadavca_amd/csrc/kernels_seedext.hip).  A read whose score is below
+   (include/nadavca_hip.h states the rules; nadavca_amd/csrc/kernels_seedext.hip; with a ReferenceSet
+   ``nvk_seed_extend_bounded_dev``, the same kernel held to the read's contig).  A read whose score is below
    ``min_score`` is unaligned.  There is no CPU form of steps 2 and 3 in the package."""
 import numpy as np
 
 from . import _lib
 from .batchflow import seg_index
 from .readbatch import BaseAlignmentBatch
+from .refset import ReferenceSet
 
 PARAMS = dict(k=14, max_occ=32, band=64, min_seeds=2, match=1, mismatch=1, gap_open=1, gap_extend=1, min_score=30)
 
@@ -47,8 +54,8 @@ def _load_reference(reference):
         from .genome import Genome
         records = Genome.load_from_fasta(os.fspath(reference))
         if len(records) != 1:
-            raise ValueError('SeedAligner: %s holds %d FASTA records, exactly one is supported'
-                             % (os.fspath(reference), len(records)))
+            raise ValueError('SeedAligner: %s holds %d FASTA records; a path stands for exactly one, several go in as '
+                             'ReferenceSet.from_fasta(path)' % (os.fspath(reference), len(records)))
         return np.ascontiguousarray(Genome.to_numerical(records[0].bases), dtype=np.int32)
     return np.ascontiguousarray(np.asarray(reference).reshape(-1), dtype=np.int32)
 
@@ -59,26 +66,35 @@ class SeedHits:
     0 without a strand), ``votes`` (int64: the chosen window's seeds), ``score`` (int32), ``end`` (int32 (n, 2): the
     end cell (i, j), -1 where there was no cell), ``aligned`` (bool); and the pairs of read j,
     ``read_idx`` / ``ref_idx`` [off[j], off[j+1]), ascending — ``ref_idx`` on the chosen strand, counted from the
-    reference's end on strand 1."""
+    reference's end on strand 1.  ``contig`` (int32): 0 for an aligned read, -1 for an unaligned one.
+    From an aligner over a ReferenceSet (``reference_set``, else None): ``contig`` is the read's contig, ``ref_idx``
+    is contig-local — the strand coordinate less the contig's first one, i.e. counted from the contig's end on strand
+    1 — while ``diagonal`` and ``end`` stay in the concatenation's strand coordinates."""
 
-    def __init__(self, strand, diagonal, votes, score, end, aligned, off, read_idx, ref_idx):
+    def __init__(self, strand, diagonal, votes, score, end, aligned, off, read_idx, ref_idx, contig=None,
+                 reference_set=None):
         self.strand, self.diagonal, self.votes, self.score, self.end = strand, diagonal, votes, score, end
         self.aligned, self.off, self.read_idx, self.ref_idx = aligned, off, read_idx, ref_idx
         self.reverse = aligned & (strand == 1)
+        self.contig = np.where(aligned, 0, -1).astype(np.int32) if contig is None else contig
+        self.reference_set = reference_set
 
     @property
     def n(self):
         return self.strand.size
 
     def base_alignments(self):
-        return BaseAlignmentBatch(self.read_idx, self.ref_idx, self.off, self.reverse)
+        return BaseAlignmentBatch(self.read_idx, self.ref_idx, self.off, self.reverse,
+                                  contig=None if self.reference_set is None else self.contig)
 
 
 class SeedAligner:
-    """``SeedAligner(reference, device=None, **params)``: ``reference`` is base codes 0..3 or the path of a FASTA
-    file with exactly one record; ``params`` as in ``PARAMS`` (``k`` 8..15, ``max_occ`` >= 1, ``band`` (the half-width
-    w, in diagonals) 1..256, ``min_seeds`` >= 1, ``match`` / ``mismatch`` / ``gap_open`` / ``gap_extend`` 1..16 (a
-    gap of length l costs gap_open + l * gap_extend), ``min_score`` >= 1); out of range raises ValueError.
+    """``SeedAligner(reference, device=None, **params)``: ``reference`` is base codes 0..3, the path of a FASTA
+    file with exactly one record, or a ``refset.ReferenceSet`` (several contigs: ``reference_set`` is then that set,
+    else None, and ``reference_num`` its concatenation; a FASTA file of several records goes in as
+    ``ReferenceSet.from_fasta(path)``); ``params`` as in ``PARAMS`` (``k`` 8..15, ``max_occ`` >= 1, ``band`` (the
+    half-width w, in diagonals) 1..256, ``min_seeds`` >= 1, ``match`` / ``mismatch`` / ``gap_open`` / ``gap_extend``
+    1..16 (a gap of length l costs gap_open + l * gap_extend), ``min_score`` >= 1); out of range raises ValueError.
     ``device``: where the reference, its k-mer index and the seeding live (default: the library's default GPU).  The
     index of both strands is built once, here.  ``align`` and ``get_base_alignments`` need a GPU device; ``seed``
     (step 1 alone) runs on any."""
@@ -86,7 +102,8 @@ class SeedAligner:
     def __init__(self, reference, device=None, **params):
         import torch
         self.params = _check_params(params)
-        self.reference_num = _load_reference(reference)
+        self.reference_set = reference if isinstance(reference, ReferenceSet) else None
+        self.reference_num = _load_reference(reference if self.reference_set is None else reference.codes)
         if device is None:
             device = torch.device('cuda', _lib.default_context().device)
         self.device = torch.device(device)
@@ -94,7 +111,13 @@ class SeedAligner:
         self._ref = ref.to(torch.int32)
         G = int(ref.numel())
         rc = 3 - ref.flip(0) if G else ref
-        self._index = [self._build_index(ref), self._build_index(rc)]
+        if self.reference_set is None:
+            self._offsets = None
+            self._index = [self._build_index(ref), self._build_index(rc)]
+        else:
+            # the contigs' boundaries on each strand, ascending (on strand 1 the contigs run backwards)
+            self._offsets = torch.from_numpy(self.reference_set.offsets).to(self.device)
+            self._index = [self._build_index(ref, self._offsets), self._build_index(rc, (G - self._offsets).flip(0))]
 
     # ---- step 1 ---------------------------------------------------------------------------------------------
     def _kmers(self, seq, length):
@@ -110,13 +133,18 @@ class SeedAligner:
             code = code * 4 + x.clamp(0, 3)
         return code, ok
 
-    def _build_index(self, strand_seq):
+    def _build_index(self, strand_seq, bounds=None):
+        """``bounds``: the contigs' boundaries on this strand, ascending; a k-mer that crosses one is left out."""
         import torch
-        n_pos = int(strand_seq.numel()) - self.params['k'] + 1
+        k = self.params['k']
+        n_pos = int(strand_seq.numel()) - k + 1
         if n_pos <= 0:
             return (torch.zeros(0, dtype=torch.int64, device=self.device),) * 2
         code, ok = self._kmers(strand_seq, n_pos)
-        pos = torch.arange(n_pos, dtype=torch.int64, device=self.device)[ok]
+        pos = torch.arange(n_pos, dtype=torch.int64, device=self.device)
+        if bounds is not None:
+            ok &= torch.searchsorted(bounds, pos, right=True) == torch.searchsorted(bounds, pos + (k - 1), right=True)
+        pos = pos[ok]
         keys, order = torch.sort(code[ok], stable=True)
         return keys, pos[order]
 
@@ -207,6 +235,29 @@ class SeedAligner:
             diagonal = torch.where(aligned, med, diagonal)
         return strand, diagonal, n_votes
 
+    def contig_of(self, read_batch, strand, diagonal):
+        """The contig rule of step 1 for a ReferenceSet aligner, on the aligner's device: ``strand`` / ``diagonal`` as
+        ``seed`` returns them -> (contig int32, -1 without a strand; ref_lo, ref_hi int32: the contig's range on the
+        read's strand, [0, G) without one)."""
+        import torch
+        dev, i64 = self.device, torch.int64
+        off = self._offsets
+        G = int(self.reference_num.size)
+        n = read_batch.n
+        m = torch.from_numpy(np.diff(read_batch.seq_off)).to(dev)
+        has = (strand >= 0) & (G > 0)
+        x = (diagonal + torch.div(m - 1, 2, rounding_mode='floor')).clamp(min=0, max=max(G - 1, 0))
+        fwd = torch.where(strand == 1, G - 1 - x, x)       # x* as a forward position
+        c = (torch.searchsorted(off, fwd.contiguous(), right=True) - 1).clamp(min=0, max=max(off.numel() - 2, 0))
+        if off.numel() < 2:
+            has = torch.zeros(n, dtype=torch.bool, device=dev)
+            off = torch.zeros(2, dtype=i64, device=dev)
+        lo = torch.where(strand == 1, G - off[c + 1], off[c])
+        hi = torch.where(strand == 1, G - off[c], off[c + 1])
+        zero = torch.zeros_like(lo)
+        return (torch.where(has, c, zero - 1).to(torch.int32), torch.where(has, lo, zero).to(torch.int32),
+                torch.where(has, hi, zero + G).to(torch.int32))
+
     # ---- steps 2 and 3 ----------------------------------------------------------------------------------------
     def align(self, read_batch):
         """-> SeedHits for every read of ``read_batch``: step 1 here, steps 2 and 3 in the kernel."""
@@ -220,9 +271,12 @@ class SeedAligner:
         n = read_batch.n
         q_off = torch.from_numpy(read_batch.seq_off).to(dev)
         query = torch.from_numpy(read_batch.sequence).to(dev)
+        contig = ref_lo = ref_hi = None
+        if self.reference_set is not None:
+            contig, ref_lo, ref_hi = self.contig_of(read_batch, strand, diagonal)
         score, end, count, pairs = seed_extend_dev(_lib.default_context(dev.index or 0), query, q_off, self._ref,
                                                    strand, diagonal, p['band'], p['match'], p['mismatch'],
-                                                   p['gap_open'], p['gap_extend'], p['min_score'])
+                                                   p['gap_open'], p['gap_extend'], p['min_score'], ref_lo, ref_hi)
         count = count.to(i64)
         off = torch.zeros(n + 1, dtype=i64, device=dev)
         torch.cumsum(count, 0, out=off[1:])
@@ -230,8 +284,12 @@ class SeedAligner:
         got = pairs[q_off[:-1][owner] + inner]
         aligned = (strand >= 0) & (score >= p['min_score'])
         h = lambda t: t.cpu().numpy()
+        ref_idx = got[:, 1].to(i64)
+        if contig is not None:
+            ref_idx = ref_idx - ref_lo.to(i64)[owner]
+            contig = h(torch.where(aligned, contig, torch.full_like(contig, -1)))
         return SeedHits(h(strand), h(diagonal), h(votes), h(score), h(end), h(aligned), h(off), h(got[:, 0]),
-                        h(got[:, 1]).astype(np.int64))
+                        h(ref_idx), contig, self.reference_set)
 
     def get_base_alignments(self, read_batch):
         """The aligner contract of the batch workflows: -> BaseAlignmentBatch."""

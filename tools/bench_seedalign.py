@@ -2,7 +2,9 @@
 simulated signal of ``synthetic.make_read_batch``): ``SeedAligner.align`` with the seeding (torch) and the extension
 kernel (``nvk_seed_extend_dev``) timed apart, and ``align_signal_batch`` with ``SeedAligner`` against the same call with
 ``SyntheticBatchAligner``.  HIP events after a warm-up; the figures are the median of ``--reps`` runs.
-`python tools/bench_seedalign.py [N] [--reps R]`."""
+``--contigs C`` cuts the same genome into C equal contigs (a ``ReferenceSet``: the bounded entry of the kernel, the
+contig rule, k-mers across the joins left out) for the same reads; reads that cross a join then align to one side.
+`python tools/bench_seedalign.py [N] [--reps R] [--contigs C]`."""
 import os
 import sys
 
@@ -15,18 +17,26 @@ from nadavca_amd.align_signal import align_signal_batch  # noqa: E402
 from nadavca_amd.kmer_model import KmerModel  # noqa: E402
 from nadavca_amd.seedalign import SeedAligner  # noqa: E402
 
-args = [a for a in sys.argv[1:] if not a.startswith('--')]
-n_reads = int(args[0]) if args else 10000
-reps = int(sys.argv[sys.argv.index('--reps') + 1]) if '--reps' in sys.argv else 5
-if '--reps' in sys.argv:
-    args = [a for a in args if a != sys.argv[sys.argv.index('--reps') + 1]]
+import argparse  # noqa: E402
+parser = argparse.ArgumentParser()
+parser.add_argument('n_reads', nargs='?', type=int, default=10000)
+parser.add_argument('--reps', type=int, default=5)
+parser.add_argument('--contigs', type=int, default=0)
+opts = parser.parse_args()
+n_reads, reps = opts.n_reads, opts.reps
 
 km = KmerModel.load_from_hdf5(defaults.KMER_MODEL_FILE)
 ctx = km.context
 rb, syn, genome = synthetic.make_read_batch(n_reads, synthetic.load_model_arrays(), seed=7)
 dev = torch.device('cuda', ctx.device)
-al = SeedAligner(genome, device=dev)
-print('%d reads, %.0f bases each on average, reference %d bases' % (n_reads, rb.seq_off[-1] / n_reads, genome.size))
+reference = genome
+if opts.contigs:
+    from nadavca_amd.refset import ReferenceSet  # noqa: E402
+    cuts = np.linspace(0, genome.size, opts.contigs + 1).astype(np.int64)
+    reference = ReferenceSet(['contig%d' % c for c in range(opts.contigs)], cuts, genome)
+al = SeedAligner(reference, device=dev)
+print('%d reads, %.0f bases each on average, reference %d bases%s' % (
+    n_reads, rb.seq_off[-1] / n_reads, genome.size, ' in %d contigs' % opts.contigs if opts.contigs else ''))
 
 
 def timed(fn):
@@ -61,13 +71,14 @@ for _ in range(reps):
     rows['asb_syn'].append(ms)
 med = {k: float(np.median(v)) for k, v in rows.items()}
 ba = syn.get_base_alignments(rb)
-same = all(np.array_equal(getattr(hits.base_alignments(), f), getattr(ba, f))
-           for f in ('read_idx', 'ref_idx', 'off', 'reverse'))
+same = not opts.contigs and all(np.array_equal(getattr(hits.base_alignments(), f), getattr(ba, f))
+                                for f in ('read_idx', 'ref_idx', 'off', 'reverse'))
 cells = int(np.diff(rb.seq_off).sum()) * (2 * al.params['band'] + 1)
 print('SeedAligner.seed (step 1, torch)              %8.2f ms' % med['seed'])
 print('SeedAligner.align (seed + kernel + gathers)   %8.2f ms  (%.0f k reads/s)' % (med['align'], n_reads / med['align']))
-print('  of which nvk_seed_extend_dev                %8.2f ms  (%.2f G band cells/s)' % (
+print('  of which the extension kernel               %8.2f ms  (%.2f G band cells/s)' % (
     med['kernel'], cells / med['kernel'] / 1e6))
 print('align_signal_batch, SeedAligner               %8.2f ms' % med['asb_seed'])
 print('align_signal_batch, SyntheticBatchAligner     %8.2f ms' % med['asb_syn'])
-print('pairs equal to the simulated truth: %s; aligned %d / %d' % (same, int(hits.aligned.sum()), n_reads))
+print('pairs equal to the simulated truth: %s; aligned %d / %d' % (
+    same if not opts.contigs else 'n/a (reads across a join keep one side)', int(hits.aligned.sum()), n_reads))
