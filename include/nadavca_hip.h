@@ -230,6 +230,32 @@ int nvk_estimate_log_likelihoods_batch_dev(
     const int32_t *anchors, const int64_t *anc_off, int bandwidth, int min_event_length,
     int model_wobbling, double *out_ll, int32_t *out_status);
 
+/* The same operator for a LIST of substitutions instead of all (alphabet-1)*R of a read (dtw.cpp:83-85,93-129):
+ * same flat batch layout and leading arguments as nvk_estimate_log_likelihoods_batch_dev, device pointers.
+ *   hyp_off     i64[n+1]        read j owns the hypotheses hyp_off[j] .. hyp_off[j+1], in any order, duplicates
+ *                               allowed, possibly none; copied to the host and checked (starts at 0, never
+ *                               decreases, ends at total_hyp, at most 2^31 - 1 per read; else NVK_ERR_INVALID)
+ *   hyp_pos     i32[total_hyp]  base position p of the read, 0 .. R-1
+ *   hyp_base    i32[total_hyp]  substituted base b, 0 .. alphabet-1; b == reference[p] is allowed and gives the
+ *                               no-substitution total
+ *   out_hyp     f64[total_hyp]  out_hyp[h] = what the full entry writes to out_ll[(ref_off[j] + p) * alphabet + b]
+ *                               (dtw.cpp:93-129); the hypotheses that are not listed are never run
+ *   out_total   f64[n]          the read's likelihood without a substitution (dtw.cpp:83-85), for every read that
+ *                               ran, also one without hypotheses
+ *   out_status  i32[n]          as the full entry; a read with a p or b outside its range gets NVK_READ_BAD_INPUT
+ *                               before any table is indexed and the rest of the batch completes.
+ *                               NVK_READ_NO_PATH: the values are the -inf the sweeps give.  Outputs of a read
+ *                               with a negative status are left untouched.
+ * Compiled limits as the full entry: min_event_length 0..4, k <= 14, alphabet <= 8, skew <= 62. */
+int nvk_estimate_hypotheses_batch_dev(
+    nvk_model *model, int64_t n_reads, int64_t total_signal, int64_t total_ref,
+    int64_t total_anchors, const double *signal, const int64_t *sig_off,
+    const int32_t *reference, const int64_t *ref_off, const int32_t *ctx_before,
+    const int64_t *cb_off, const int32_t *ctx_after, const int64_t *ca_off,
+    const int32_t *anchors, const int64_t *anc_off, int bandwidth, int min_event_length,
+    int model_wobbling, int64_t total_hyp, const int64_t *hyp_off, const int32_t *hyp_pos,
+    const int32_t *hyp_base, double *out_total, double *out_hyp, int32_t *out_status);
+
 /* replaces the Chunk score accumulation of ProbabilityEstimator
  * (/root/reference/nadavca/estimator.py:45-47,112-119,226-231): for every read j,
  *   ll' = (ll - ll[0][reference[0]]) / normalization_event_length,

@@ -579,18 +579,12 @@ extern "C" int nvk_refine_alignment_batch_dev(
 // ---------------------------------------------------------------------------------------------
 // estimate_log_likelihoods
 // ---------------------------------------------------------------------------------------------
-extern "C" int nvk_estimate_log_likelihoods_batch_dev(
-    nvk_model *model, int64_t n_reads, int64_t total_signal, int64_t total_ref,
-    int64_t total_anchors, const double *signal, const int64_t *sig_off, const int32_t *reference,
-    const int64_t *ref_off, const int32_t *ctx_before, const int64_t *cb_off,
-    const int32_t *ctx_after, const int64_t *ca_off, const int32_t *anchors,
-    const int64_t *anc_off, int bandwidth, int min_event_length, int model_wobbling,
-    double *out_ll, int32_t *out_status) {
-  BatchArgs a;
-  int rc = dev_batch(model, n_reads, total_signal, total_ref, total_anchors, signal, sig_off, reference, ref_off,
-                     ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
-                     out_status, a);
-  if (rc || n_reads == 0) return rc;
+namespace {
+// plan + launch of both entries: the full matrix (hyp == nullptr) or the listed hypotheses
+int ell_run(nvk_model *model, const BatchArgs &a, int model_wobbling, double *out_ll, int32_t *out_status,
+            const EllHyp *hyp) {
+  int rc;
+  const int64_t n_reads = a.n_reads, total_ref = a.total_ref;
   nvk_ctx *ctx = model->ctx;
   const int64_t n = n_reads, nrow = total_ref + n;
   if ((rc = nvk_ws_reserve(ctx, WS_META, (size_t)(n + 1) * sizeof(ReadMeta) + 64))) return rc;
@@ -615,8 +609,68 @@ extern "C" int nvk_estimate_log_likelihoods_batch_dev(
   NVK_HIP(hipStreamSynchronize(ctx->stream));
   ctx->last_cells = (int64_t)tot.cells;
   ctx->last_steps = (int64_t)tot.steps;
-  rc = launch_ell(ctx, model->dm, a, model_wobbling ? 1 : 0, pl, tot, out_ll, out_status);
+  rc = launch_ell(ctx, model->dm, a, model_wobbling ? 1 : 0, pl, tot, out_ll, out_status, hyp);
   if (rc) return rc;
   NVK_HIP(hipStreamSynchronize(ctx->stream));
   return NVK_OK;
+}
+}  // namespace
+
+extern "C" int nvk_estimate_log_likelihoods_batch_dev(
+    nvk_model *model, int64_t n_reads, int64_t total_signal, int64_t total_ref,
+    int64_t total_anchors, const double *signal, const int64_t *sig_off, const int32_t *reference,
+    const int64_t *ref_off, const int32_t *ctx_before, const int64_t *cb_off,
+    const int32_t *ctx_after, const int64_t *ca_off, const int32_t *anchors,
+    const int64_t *anc_off, int bandwidth, int min_event_length, int model_wobbling,
+    double *out_ll, int32_t *out_status) {
+  BatchArgs a;
+  int rc = dev_batch(model, n_reads, total_signal, total_ref, total_anchors, signal, sig_off, reference, ref_off,
+                     ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
+                     out_status, a);
+  if (rc || n_reads == 0) return rc;
+  return ell_run(model, a, model_wobbling, out_ll, out_status, nullptr);
+}
+
+extern "C" int nvk_estimate_hypotheses_batch_dev(
+    nvk_model *model, int64_t n_reads, int64_t total_signal, int64_t total_ref,
+    int64_t total_anchors, const double *signal, const int64_t *sig_off, const int32_t *reference,
+    const int64_t *ref_off, const int32_t *ctx_before, const int64_t *cb_off,
+    const int32_t *ctx_after, const int64_t *ca_off, const int32_t *anchors,
+    const int64_t *anc_off, int bandwidth, int min_event_length, int model_wobbling,
+    int64_t total_hyp, const int64_t *hyp_off, const int32_t *hyp_pos, const int32_t *hyp_base,
+    double *out_total, double *out_hyp, int32_t *out_status) {
+  BatchArgs a;
+  int rc = dev_batch(model, n_reads, total_signal, total_ref, total_anchors, signal, sig_off, reference, ref_off,
+                     ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
+                     out_status, a);
+  if (rc) return rc;
+  if (total_hyp < 0 || !hyp_off || !out_total || (total_hyp > 0 && (!hyp_pos || !hyp_base || !out_hyp))) {
+    nvk_set_error("negative total_hyp or NULL hypothesis / output pointer");
+    return NVK_ERR_INVALID;
+  }
+  if (n_reads == 0) {
+    if (total_hyp != 0) {
+      nvk_set_error("hypothesis offsets end at 0, total_hyp is %lld", (long long)total_hyp);
+      return NVK_ERR_INVALID;
+    }
+    return NVK_OK;
+  }
+  // the kernel walks hyp_off[j] .. hyp_off[j+1] of three arrays of total_hyp entries: checked here, on a host copy
+  nvk_ctx *ctx = model->ctx;
+  std::vector<int64_t> h_off((size_t)n_reads + 1);
+  NVK_HIP(hipMemcpyAsync(h_off.data(), hyp_off, h_off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  NVK_HIP(hipStreamSynchronize(ctx->stream));
+  if ((rc = check_offsets("hypothesis", h_off.data(), n_reads))) return rc;
+  if (h_off[(size_t)n_reads] != total_hyp) {
+    nvk_set_error("hypothesis offsets end at %lld, total_hyp is %lld", (long long)h_off[(size_t)n_reads],
+                  (long long)total_hyp);
+    return NVK_ERR_INVALID;
+  }
+  for (int64_t j = 0; j < n_reads; j++)
+    if (h_off[(size_t)j + 1] - h_off[(size_t)j] > 0x7fffffff) {
+      nvk_set_error("read %lld lists more than 2^31 - 1 hypotheses", (long long)j);
+      return NVK_ERR_INVALID;
+    }
+  const EllHyp hyp{hyp_off, hyp_pos, hyp_base, out_total, out_hyp};
+  return ell_run(model, a, model_wobbling, nullptr, out_status, &hyp);
 }

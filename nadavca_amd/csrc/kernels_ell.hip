@@ -8,6 +8,8 @@
 //   C. hypotheses      for every position p and every substituted base b != ref[p]: re-run the
 //                      <= k rows the substitution influences, starting from prefix[first] and
 //                      closing against suffix[last+1] (dtw.cpp:93-129)
+//                      — or, in the LISTED variant (nvk_estimate_hypotheses_batch_dev), only for the (p, b) of the
+//                      read's list: the same lanes and arithmetic, the unlisted hypotheses are never run
 //
 // Mapping (not the reference's): "fused" lanes.  The reference alternates a wobble row
 // (mixture of the k-mers j-1 and j, min event length 0) with an emitting row (k-mer j).  Both
@@ -99,6 +101,19 @@ struct EllArgs {
   double *out_ll;
   int32_t *out_status;
 };
+// The listed variant (nvk_estimate_hypotheses_batch_dev): the hypotheses of read j are hyp_off[j] .. hyp_off[j+1] of
+// (hyp_pos, hyp_base) instead of all (p, b != ref[p]); out_ll is not used.  A struct of its own, so that the full
+// variant's kernel arguments stay what they are.
+struct EllListArgs : EllArgs {
+  const int64_t *hyp_off;
+  const int32_t *hyp_pos, *hyp_base;
+  double *out_total;  // [n_reads]
+  double *out_hyp;    // [total_hyp]
+};
+template <bool LISTED>
+struct EllArgsOf { typedef EllArgs type; };
+template <>
+struct EllArgsOf<true> { typedef EllListArgs type; };
 
 // ---- one fused lane ---------------------------------------------------------------------------
 template <int MEL>
@@ -395,8 +410,8 @@ __device__ void sweep_fast(const FusedParam *desc, int R, int N, int c, const do
   }
 }
 
-template <int MEL, int GL>
-__global__ __launch_bounds__(64, 3) void ell_kernel(EllArgs g) {
+template <int MEL, int GL, bool LISTED>
+__global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED>::type g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double *etab = reinterpret_cast<double *>(smem);
   double *ring = etab + dens::ETN;
@@ -427,10 +442,26 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(EllArgs g) {
     const int rd = g.order ? g.order[pos] : pos;
     const ReadMeta m = g.pl.metas[rd];
     const int R = __builtin_amdgcn_readfirstlane(m.R);
-    double *out = g.out_ll + (size_t)m.ref_off * alpha;
+    double *out = LISTED ? nullptr : g.out_ll + (size_t)m.ref_off * alpha;
     if (m.status != NVK_READ_OK) {
       if (lane == 0) g.out_status[rd] = m.status;
       continue;
+    }
+    // LISTED: the read's hypotheses; one outside the read or the alphabet fails the read before any table is indexed
+    int64_t h0 = 0;
+    int n_list = 0;
+    if constexpr (LISTED) {
+      h0 = g.hyp_off[rd];
+      n_list = __builtin_amdgcn_readfirstlane((int)(g.hyp_off[rd + 1] - h0));
+      bool bad = false;
+      for (int q = lane; q < n_list; q += 64) {
+        const int hp = g.hyp_pos[h0 + q], hb = g.hyp_base[h0 + q];
+        bad = bad || hp < 0 || hp >= R || hb < 0 || hb >= alpha;
+      }
+      if (__any(bad)) {
+        if (lane == 0) g.out_status[rd] = NVK_READ_BAD_INPUT;
+        continue;
+      }
     }
     const int N = __builtin_amdgcn_readfirstlane(m.N);
     const int c = __builtin_amdgcn_readfirstlane(m.c);
@@ -489,11 +520,15 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(EllArgs g) {
       tot = xm::add_norm(tot, o);
     }
     const double no_snp = xm::to_log(tot);
-    for (int p = lane; p < R; p += 64) out[(size_t)p * alpha + ref[p]] = no_snp;
+    if constexpr (LISTED) {
+      if (lane == 0) g.out_total[rd] = no_snp;
+    } else {
+      for (int p = lane; p < R; p += 64) out[(size_t)p * alpha + ref[p]] = no_snp;
+    }
 
     // ---- C: substitution hypotheses, 8 per wave step
     const int back = dm.k - dm.central - 1, fwd = dm.central;
-    const int n_items = R * (alpha - 1);
+    const int n_items = LISTED ? n_list : R * (alpha - 1);
     const int grp = lane / GL, gl = lane % GL;
     // lane roles in a group: 0 = density of the k-mer before `first` (only feeds the mixture of the
     // first position), 1..npos = the positions first..last, npos+1 = the closing lane.
@@ -505,9 +540,14 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(EllArgs g) {
       const bool valid = item < n_items;
       int p = 0, b = 0, first = 0, last = 0, npos = 0;
       if (valid) {
-        p = item / (alpha - 1);
-        int bi = item % (alpha - 1);
-        b = bi + (bi >= ref[p] ? 1 : 0);
+        if constexpr (LISTED) {
+          p = g.hyp_pos[h0 + item];
+          b = g.hyp_base[h0 + item];
+        } else {
+          p = item / (alpha - 1);
+          int bi = item % (alpha - 1);
+          b = bi + (bi >= ref[p] ? 1 : 0);
+        }
         first = max(0, p - back);
         last = min(R - 1, p + fwd);
         npos = last - first + 1;
@@ -630,7 +670,9 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(EllArgs g) {
       if (is_fin) {
         acc = xm::norm(acc);
         if (RING && acc.e < xm::XZ / 2) acc = xm::zero();  // made of nothing but out-of-band values (fused_step_ring)
-        out[(size_t)p * alpha + b] = xm::to_log(acc);
+        // LISTED: b == ref[p] is no substitution — the total of the two sweeps, as the full matrix holds it there
+        if constexpr (LISTED) g.out_hyp[h0 + item] = (b == ref[p]) ? no_snp : xm::to_log(acc);
+        else out[(size_t)p * alpha + b] = xm::to_log(acc);
       }
     }
     // a read without any valid path has likelihood zero everywhere (the reference returns an
@@ -642,7 +684,7 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(EllArgs g) {
 }  // namespace
 
 int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobbling,
-               const EllPlan &pl, const PlanTotals &tot, double *out_ll, int32_t *out_status) {
+               const EllPlan &pl, const PlanTotals &tot, double *out_ll, int32_t *out_status, const EllHyp *hyp) {
   if (a.n_reads == 0) return NVK_OK;
   const int mel = a.mel;
   if (mel < 0 || mel > 4) {
@@ -686,7 +728,7 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
   int *counter = (int *)ctx->ws[WS_MISC];
   NVK_HIP(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
 
-  EllArgs g;
+  EllListArgs g;
   g.dm = dm;
   g.a = a;
   g.pl = pl;
@@ -711,7 +753,12 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
   ctx->last_spill_bytes = (int64_t)tot.cells * 24 * 2;
 
   void (*kern)(EllArgs) = nullptr;
-#define ELL_PICK(M) (kern = wide_groups ? ell_kernel<M, 16> : ell_kernel<M, 8>)
+  void (*kern_l)(EllListArgs) = nullptr;
+#define ELL_PICK(M)                                                               \
+  do {                                                                            \
+    if (hyp) kern_l = wide_groups ? ell_kernel<M, 16, true> : ell_kernel<M, 8, true>; \
+    else kern = wide_groups ? ell_kernel<M, 16, false> : ell_kernel<M, 8, false>;     \
+  } while (0)
   switch (mel) {
     case 0: ELL_PICK(0); break;
     case 1: ELL_PICK(1); break;
@@ -720,12 +767,21 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
     default: ELL_PICK(4); break;
   }
 #undef ELL_PICK
+  if (hyp) {
+    g.hyp_off = hyp->off;
+    g.hyp_pos = hyp->pos;
+    g.hyp_base = hyp->base;
+    g.out_total = hyp->out_total;
+    g.out_hyp = hyp->out_hyp;
+  }
+  const void *kfn = hyp ? (const void *)kern_l : (const void *)kern;
   if (lds > 64 * 1024) {
-    NVK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    NVK_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
   {
     TimerScope ts(ctx, NVK_K_ELL_HYP);
-    hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(64), lds, ctx->stream, g);
+    if (hyp) hipLaunchKernelGGL(kern_l, dim3((unsigned)slots), dim3(64), lds, ctx->stream, g);
+    else hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(64), lds, ctx->stream, static_cast<const EllArgs &>(g));
   }
   NVK_HIP(hipGetLastError());
   return NVK_OK;

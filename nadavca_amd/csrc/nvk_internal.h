@@ -209,8 +209,17 @@ struct EllPlan {
 };
 int launch_plan_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobbling,
                     const EllPlan &pl, unsigned long long *bandtmp, PlanTotals *totals);
+// listed hypotheses (nvk_estimate_hypotheses_batch_dev): read j owns off[j] .. off[j+1] of (pos, base)
+struct EllHyp {
+  const int64_t *off;
+  const int32_t *pos, *base;
+  double *out_total;  // [n_reads]
+  double *out_hyp;    // [off[n_reads]]
+};
+// hyp == nullptr: the full matrix into out_ll; else the listed hypotheses into hyp->out_* (out_ll unused)
 int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobbling,
-               const EllPlan &pl, const PlanTotals &tot, double *out_ll, int32_t *out_status);
+               const EllPlan &pl, const PlanTotals &tot, double *out_ll, int32_t *out_status,
+               const EllHyp *hyp = nullptr);
 // out_count[0..4) = number of entries of flags[0..n) that are nonzero / have bit 0 / bit 1 / bit 2 set
 int launch_count_flags(nvk_ctx *ctx, const int32_t *flags, int64_t n, int32_t *out_count);
 // bytes the resident waves' spill may take: the ctx limit if set, else a default share of the free memory

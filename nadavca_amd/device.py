@@ -133,6 +133,38 @@ def estimate_log_likelihoods_dev(dbatch, bandwidth, min_event_length, kmer_model
     return ll, status
 
 
+def estimate_hypotheses_dev(dbatch, bandwidth, min_event_length, kmer_model, model_wobbling, hyp_off, hyp_pos,
+                            hyp_base):
+    """``estimate_log_likelihoods_dev`` for a LIST of substitutions: read j's hypotheses are entries
+    ``hyp_off[j] .. hyp_off[j+1]`` (int64 (n+1,)) of ``hyp_pos`` / ``hyp_base`` (int32: position in the read's
+    reference part, substituted base) — device tensors.  -> (total f64 (n,), hyp f64 (n_hyp,), status int32 (n,)):
+    ``hyp[h]`` is the entry ``[p, b]`` of the read's full matrix, ``total[j]`` the read's log-likelihood without a
+    substitution.  The unlisted hypotheses are never run; a read with a position or base out of range gets
+    READ_BAD_INPUT (include/nadavca_hip.h: nvk_estimate_hypotheses_batch_dev).  Values of reads with a negative
+    status are NaN."""
+    torch = dbatch.torch
+    lib = _lib.load()
+    dev = dbatch.device
+    hyp_off = hyp_off.to(device=dev, dtype=torch.int64).contiguous()
+    hyp_pos = hyp_pos.to(device=dev, dtype=torch.int32).contiguous()
+    hyp_base = hyp_base.to(device=dev, dtype=torch.int32).contiguous()
+    n_hyp = int(hyp_pos.numel())
+    if int(hyp_base.numel()) != n_hyp or int(hyp_off.numel()) != dbatch.n + 1:
+        raise ValueError('estimate_hypotheses_dev: hyp_pos and hyp_base go together, hyp_off has one entry per read '
+                         'and one more')
+    total = torch.full((dbatch.n,), float('nan'), dtype=torch.float64, device=dev)
+    hyp = torch.full((n_hyp,), float('nan'), dtype=torch.float64, device=dev)
+    status = torch.zeros(dbatch.n, dtype=torch.int32, device=dev)
+    if n_hyp == 0:  # (a placeholder element: the C-ABI's pointers of an empty list are never read)
+        hyp_pos = hyp_base = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.nvk_estimate_hypotheses_batch_dev(
+        kmer_model.handle, dbatch.n, dbatch.total_signal, dbatch.total_ref, dbatch.total_anchors,
+        *dbatch.pointers(), int(bandwidth), int(min_event_length), int(bool(model_wobbling)),
+        n_hyp, _dp(hyp_off), _dp(hyp_pos), _dp(hyp_base), _dp(total), _dp(hyp if n_hyp else total), _dp(status)),
+        'nvk_estimate_hypotheses_batch_dev')
+    return total, hyp, status
+
+
 # ---- host steps adjacent to the path, on the device (include/nadavca_hip.h, SURVEY.md §8 f1/f2) --------
 def normalize_groups_dev(context, raw, grp_off, out=None):
     """``Read.normalize_reads`` for groups of samples laid end to end (torch f64 / int64 tensors on the

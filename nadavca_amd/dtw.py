@@ -11,6 +11,7 @@ Per-read surface (same names, keywords and return shapes as the reference):
 Batched surface (what the estimator uses; one launch for many reads):
     refine_alignment_batch(reads, ...)            reads = list of per-read argument tuples
     estimate_log_likelihoods_batch(reads, ...)
+    estimate_hypotheses_batch(reads, hypotheses, ...)   listed substitutions only
 
 All compute goes through libnadavca_hip.so; nothing here computes on the CPU.
 """
@@ -247,6 +248,39 @@ def estimate_log_likelihoods_batch(reads, bandwidth, min_event_length, kmer_mode
     batch = reads if isinstance(reads, FlatBatch) else FlatBatch(reads)
     ll, _ = estimate_log_likelihoods_flat(batch, bandwidth, min_event_length, kmer_model, model_wobbling)
     return [ll[batch.ref_off[j]:batch.ref_off[j + 1]] for j in range(batch.n)]
+
+
+def estimate_hypotheses_batch(reads, hypotheses, bandwidth, min_event_length, kmer_model, model_wobbling,
+                              on_error='raise', return_status=False):
+    """``estimate_log_likelihoods_batch`` for a list of substitutions per read instead of the whole matrix.  reads:
+    as there (or a FlatBatch); hypotheses: per read an (m, 2) integer array of (position, substituted base) rows, in
+    any order, duplicates allowed, possibly empty.  -> (total f64 (n,), list of f64 (m,) arrays): ``total[j]`` the
+    read's log-likelihood without a substitution, entry h of read j the value ``[p, b]`` of its full matrix (the
+    hypotheses that are not listed are never run; nvk_estimate_hypotheses_batch_dev).  A position or base out of
+    range fails its read (READ_BAD_INPUT: ValueError, or with on_error='status' NaN values and, with
+    return_status=True, the status array as a third result)."""
+    import torch
+    from .device import DeviceBatch, estimate_hypotheses_dev
+    batch = reads if isinstance(reads, FlatBatch) else FlatBatch(reads)
+    if len(hypotheses) != batch.n:
+        raise ValueError('estimate_hypotheses_batch: %d hypothesis lists for %d reads' % (len(hypotheses), batch.n))
+    hyps = [np.asarray(h, dtype=np.int64).reshape(-1, 2) for h in hypotheses]
+    off = _offsets([h.shape[0] for h in hyps])
+    if batch.n == 0:
+        out = (np.zeros(0), [])
+        return out + (np.zeros(0, dtype=np.int32),) if return_status else out
+    flat = np.concatenate(hyps)
+    if flat.size and (flat.min() < -(1 << 31) or flat.max() >= (1 << 31)):
+        raise ValueError('estimate_hypotheses_batch: a position or base does not fit 32 bits')
+    dbatch = DeviceBatch(batch, torch.device('cuda', kmer_model.context.device))
+    total, hyp, status = estimate_hypotheses_dev(
+        dbatch, bandwidth, min_event_length, kmer_model, model_wobbling, torch.from_numpy(off),
+        torch.from_numpy(flat[:, 0].astype(np.int32)), torch.from_numpy(flat[:, 1].astype(np.int32)))
+    total, hyp, status = total.cpu().numpy(), hyp.cpu().numpy(), status.cpu().numpy()
+    if on_error == 'raise':
+        check_status('estimate_hypotheses', status)
+    out = (total, [hyp[off[j]:off[j + 1]] for j in range(batch.n)])
+    return out + (status,) if return_status else out
 
 
 # ------------------------------------------------------------------------------------------------

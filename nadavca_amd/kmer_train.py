@@ -96,6 +96,42 @@ def expand_kmer_model(k0, central0, alphabet, mean0, sigma0, k, central):
     return mean0[sub], sigma0[sub]
 
 
+def extend_kmer_model(k, central, mean, sigma, base=1, levels=None):
+    """The 4-letter table ``mean`` / ``sigma`` (4^k entries) laid out as a 5-letter one (id = sum b_m * 5^(k-1-m), the
+    indexing of ``synthetic.kmer_ids`` with alphabet 5): a k-mer over codes 0..3 keeps its values, a k-mer containing
+    code 4 (the modified base) takes those of the k-mer with ``base`` (default 1: C) in place of every 4.  ``levels``:
+    known levels that override, ``{id5: (mean, sigma)}`` or a tuple of arrays ``(ids5, means, sigmas)``.
+    -> (mean5, sigma5) float64 arrays of 5^k entries — the table ``call_mods_batch`` takes (``save_kmer_model_npz``
+    writes it)."""
+    k, central, _ = _check_kmer_args(k, central, 5)
+    if int(base) != base or not 0 <= base <= 3:
+        raise ValueError('base = %r outside 0..3' % (base,))
+    mean = np.asarray(mean, dtype=np.float64).reshape(-1)
+    sigma = np.asarray(sigma, dtype=np.float64).reshape(-1)
+    if mean.size != 4 ** k or sigma.size != 4 ** k:
+        raise ValueError('mean / sigma hold %d / %d values, the 4-letter table %d' % (mean.size, sigma.size, 4 ** k))
+    ids = np.arange(5 ** k, dtype=np.int64)
+    id4 = np.zeros_like(ids)
+    for m in range(k):
+        d = (ids // 5 ** (k - 1 - m)) % 5
+        id4 = id4 * 4 + np.where(d == 4, int(base), d)
+    mean5, sigma5 = mean[id4], sigma[id4]
+    if levels is not None:
+        if isinstance(levels, dict):
+            at = np.array(list(levels.keys()), dtype=np.int64)
+            vals = np.array([levels[i] for i in levels], dtype=np.float64).reshape(-1, 2)
+            lm, ls = vals[:, 0], vals[:, 1]
+        else:
+            at, lm, ls = (np.asarray(x).reshape(-1) for x in levels)
+            at = at.astype(np.int64)
+        if at.size and (at.min() < 0 or at.max() >= 5 ** k):
+            raise ValueError('levels: a k-mer id outside 0..%d' % (5 ** k - 1))
+        if lm.size != at.size or ls.size != at.size:
+            raise ValueError('levels: ids, means and sigmas differ in length')
+        mean5[at], sigma5[at] = lm, ls
+    return mean5, sigma5
+
+
 class KmerModelEstimate:
     """What ``estimate_kmer_model`` returns.  ``model``: the final KmerModel; numpy arrays of the final table
     (``mean``, ``sigma``) and of the last round (``events``, ``samples``: counted per k-mer; ``updated``: the k-mers

@@ -287,6 +287,68 @@ def make_read_batch(n, model, seed=0, genome_length=10000, raw_dtype=np.int16, *
     return rb, SyntheticBatchAligner(genome, ba), genome
 
 
+def make_modified_read_batch(n, model5, seed=0, pattern='CG', mod_offset=0, modified_fraction=0.5, mod_code=4,
+                             genome_length=10000, raw_dtype=np.int16, **kw):
+    """``make_read_batch`` with modified bases: ``model5`` is a table whose alphabet holds ``mod_code`` (the tuple of
+    ``load_model_arrays``; ``kmer_train.extend_kmer_model`` makes one).  On each strand of a random genome a fraction
+    ``modified_fraction`` of the occurrences of ``pattern`` (over ACGT) is modified at ``pattern[mod_offset]``; a read's
+    signal is drawn from the TRUTH sequence of its strand (``mod_code`` at the modified sites), its basecalled
+    sequence and the aligner's reference stay canonical.  ``**kw`` as ``make_read_spec`` (no substitutions).
+    -> (ReadBatch, SyntheticBatchAligner, genome codes, truth): ``truth`` = {'forward', 'reverse'}: bool masks over
+    FORWARD genome coordinates of the modified bases of each strand (a reverse-strand site at forward coordinate x is
+    the base 3 - genome[x] of the reverse strand)."""
+    from .readbatch import ReadBatch, BaseAlignmentBatch, SyntheticBatchAligner
+    k, central, alphabet, mean, sigma = model5
+    if not 4 <= mod_code < alphabet:
+        raise ValueError('make_modified_read_batch: the table has no code %d' % mod_code)
+    if kw.get('substitution_rate', 0.0):
+        raise ValueError('make_modified_read_batch: reads without substitutions only')
+    rng = np.random.default_rng(seed)
+    genome = rng.integers(0, 4, genome_length).astype(np.int32)
+    G = genome.size
+    pat = np.array([{'A': 0, 'C': 1, 'G': 2, 'T': 3}[c] for c in pattern], dtype=np.int64)
+    strands = (genome.astype(np.int64), 3 - genome[::-1].astype(np.int64))
+    truth_seq, masks = [], []
+    for s in strands:
+        hit = np.ones(max(G - pat.size + 1, 0), dtype=bool)
+        for t, c in enumerate(pat):
+            hit &= s[t:t + hit.size] == c
+        at = np.nonzero(hit)[0] + mod_offset
+        at = at[rng.random(at.size) < modified_fraction]
+        m = np.zeros(G, dtype=bool)
+        m[at] = True
+        masks.append(m)
+        truth_seq.append(np.where(m, mod_code, s))
+    truth = dict(forward=masks[0], reverse=masks[1][::-1].copy())
+    specs = []
+    for i in range(n):
+        r = np.random.default_rng([seed, i])
+        # the canonical read of make_read_spec, then its signal re-drawn from the truth sequence with the same dwells
+        spec = make_read_spec(r, genome, (k, central, alphabet, mean, sigma), i, **kw)
+        L, g0, rev = spec['length'], spec['g0'], spec['reverse']
+        o0 = G - g0 - L if rev else g0           # the read's first base on its own strand
+        tseq = truth_seq[1 if rev else 0][o0:o0 + L]
+        ids = kmer_ids(tseq, 0, L, k, central, alphabet)
+        dw = np.diff(spec['true_starts'])
+        noise = kw.get('noise', 0.35)
+        x = np.clip(np.repeat(mean[ids], dw) + r.normal(0.0, noise, int(dw.sum())), -5.0, 5.0)
+        spec['raw_signal'] = kw.get('raw_scale', 12.0) * x + kw.get('raw_shift', 90.0)
+        specs.append(spec)
+    inv = {'A': 0, 'C': 1, 'G': 2, 'T': 3}
+    off = lambda xs: np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.int64)
+    raws = [np.rint(s['raw_signal']).astype(raw_dtype) if np.issubdtype(raw_dtype, np.integer)
+            else np.asarray(s['raw_signal'], dtype=raw_dtype) for s in specs]
+    seqs = [np.array([inv[b] for b in s['sequence']], dtype=np.int32) for s in specs]
+    maps = [sorted(s['sequence_to_signal_mapping'].items()) for s in specs]
+    rb = ReadBatch(np.concatenate(raws), off(raws), np.concatenate(seqs), off(seqs),
+                   np.array([k_ for m in maps for k_, _ in m], dtype=np.int64),
+                   np.array([v for m in maps for _, v in m], dtype=np.int64), off(maps))
+    bms = [np.asarray(s['base_mapping'], dtype=np.int64).reshape(-1, 2) for s in specs]
+    ba = BaseAlignmentBatch(np.concatenate([b[:, 0] for b in bms]), np.concatenate([b[:, 1] for b in bms]),
+                            off(bms), np.array([s['reverse'] for s in specs], dtype=bool))
+    return rb, SyntheticBatchAligner(genome, ba), genome, truth
+
+
 def make_error_read_batch(n, genome_num, seed=0, length=400, spread=40, substitution_rate=0.0, insertion_rate=0.0,
                           deletion_rate=0.0, random_fraction=0.0, overhang_fraction=0.0, model=None, dwell=(3, 17),
                           noise=0.35):
