@@ -256,6 +256,48 @@ int nvk_estimate_hypotheses_batch_dev(
     int model_wobbling, int64_t total_hyp, const int64_t *hyp_off, const int32_t *hyp_pos,
     const int32_t *hyp_base, double *out_total, double *out_hyp, int32_t *out_status);
 
+/* The same for JOINT hypotheses: a hypothesis is a SET of substitutions (p_1, b_1) .. (p_m, b_m) of one read with
+ * strictly ascending positions, scored as a whole.  Entries with b_i == reference[p_i] change nothing and are
+ * dropped; if none remain the value is the read's no-substitution total (the listed operator's rule for
+ * b == reference[p]).  Otherwise, with back = k - central - 1 and fwd = central, the rows
+ * first = max(0, p_1 - back) .. last = min(R - 1, p_m + fwd) are re-run from prefix[first], every k-mer read from the
+ * sequence with ALL substitutions applied, and closed exactly as dtw.cpp:116-126 closes a single substitution: the
+ * closing wobble row on band `last` (the kept quirk), then the total against suffix[last + 1].  With one effective
+ * substitution this is nvk_estimate_hypotheses_batch_dev's value, bit for bit.  The reference's counterpart: with
+ * ref' = the read's reference with the substitutions 1 .. m-1 applied and b_m != reference[p_m], the value is the
+ * entry [p_m, b_m] of EstimateLogLikelihoods on ref' — its prefix' rows between p_1 - back and p_m - back are the
+ * same NextRow calls on the same bands as the hypothesis loop's interior rows (dtw.cpp:51-64 against 103-115), and
+ * prefix[first] and suffix[last + 1] see none of the substituted bases.
+ * Same flat batch layout and leading arguments as nvk_estimate_hypotheses_batch_dev, device pointers.
+ *   hyp_off     i64[n+1]          read j owns the hypotheses hyp_off[j] .. hyp_off[j+1] (any order, duplicates
+ *                                 allowed, possibly none)
+ *   sub_off     i64[total_hyp+1]  hypothesis h owns the substitutions sub_off[h] .. sub_off[h+1], possibly none
+ *                                 (the total).  Both offset arrays are copied to the host and checked (start at 0,
+ *                                 never decrease, end at total_hyp / total_sub, at most 2^31 - 1 hypotheses per
+ *                                 read; else NVK_ERR_INVALID)
+ *   sub_pos     i32[total_sub]    base position of the read, 0 .. R-1, strictly ascending within a hypothesis
+ *   sub_base    i32[total_sub]    substituted base, 0 .. alphabet-1 (a letter takes 3 bits of the kernel's item
+ *                                 code: nvk_model_create builds no table of more than 8 letters, and this entry
+ *                                 answers NVK_ERR_UNSUPPORTED for one)
+ *   out_hyp     f64[total_hyp], out_total f64[n], out_status i32[n]: as the listed operator.  A read gets
+ *                                 NVK_READ_BAD_INPUT before any table is indexed — its outputs left untouched, the
+ *                                 rest of the batch completes — when one of its hypotheses has a position or base
+ *                                 out of range, positions that do not strictly ascend, or effective substitutions
+ *                                 that re-run more than 14 rows (last - first + 1 > 14, that is p_m - p_1 > 14 - k
+ *                                 away from the read's ends: a hypothesis takes one DPP row of 16 lanes, two of
+ *                                 which are not rows).
+ * Hypotheses of at most 6 rows run 8 per wave step like the listed ones, the others 4 per step, in one launch
+ * after one pair of sweeps per read.  Compiled limits otherwise as the full entry. */
+int nvk_estimate_joint_hypotheses_batch_dev(
+    nvk_model *model, int64_t n_reads, int64_t total_signal, int64_t total_ref,
+    int64_t total_anchors, const double *signal, const int64_t *sig_off,
+    const int32_t *reference, const int64_t *ref_off, const int32_t *ctx_before,
+    const int64_t *cb_off, const int32_t *ctx_after, const int64_t *ca_off,
+    const int32_t *anchors, const int64_t *anc_off, int bandwidth, int min_event_length,
+    int model_wobbling, int64_t total_hyp, const int64_t *hyp_off, int64_t total_sub,
+    const int64_t *sub_off, const int32_t *sub_pos, const int32_t *sub_base, double *out_total,
+    double *out_hyp, int32_t *out_status);
+
 /* replaces the Chunk score accumulation of ProbabilityEstimator
  * (/root/reference/nadavca/estimator.py:45-47,112-119,226-231): for every read j,
  *   ll' = (ll - ll[0][reference[0]]) / normalization_event_length,

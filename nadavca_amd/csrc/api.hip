@@ -631,6 +631,31 @@ extern "C" int nvk_estimate_log_likelihoods_batch_dev(
   return ell_run(model, a, model_wobbling, out_ll, out_status, nullptr);
 }
 
+namespace {
+// off[0..n] on the device: copied to the host and checked (check_offsets, ends at `total`, the argument named
+// total_name); hyp_per_read: off is a read's hypothesis list, which the kernel counts in an int
+int check_dev_offsets(nvk_ctx *ctx, const char *what, const int64_t *off, int64_t n, int64_t total,
+                      const char *total_name, bool hyp_per_read, std::vector<int64_t> &h_off) {
+  int rc;
+  h_off.resize((size_t)n + 1);
+  NVK_HIP(hipMemcpyAsync(h_off.data(), off, h_off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  NVK_HIP(hipStreamSynchronize(ctx->stream));
+  if ((rc = check_offsets(what, h_off.data(), n))) return rc;
+  if (h_off[(size_t)n] != total) {
+    nvk_set_error("%s offsets end at %lld, %s is %lld", what, (long long)h_off[(size_t)n], total_name,
+                  (long long)total);
+    return NVK_ERR_INVALID;
+  }
+  if (hyp_per_read)
+    for (int64_t j = 0; j < n; j++)
+      if (h_off[(size_t)j + 1] - h_off[(size_t)j] > 0x7fffffff) {
+        nvk_set_error("read %lld lists more than 2^31 - 1 hypotheses", (long long)j);
+        return NVK_ERR_INVALID;
+      }
+  return NVK_OK;
+}
+}  // namespace
+
 extern "C" int nvk_estimate_hypotheses_batch_dev(
     nvk_model *model, int64_t n_reads, int64_t total_signal, int64_t total_ref,
     int64_t total_anchors, const double *signal, const int64_t *sig_off, const int32_t *reference,
@@ -656,21 +681,49 @@ extern "C" int nvk_estimate_hypotheses_batch_dev(
     return NVK_OK;
   }
   // the kernel walks hyp_off[j] .. hyp_off[j+1] of three arrays of total_hyp entries: checked here, on a host copy
-  nvk_ctx *ctx = model->ctx;
-  std::vector<int64_t> h_off((size_t)n_reads + 1);
-  NVK_HIP(hipMemcpyAsync(h_off.data(), hyp_off, h_off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  if ((rc = check_offsets("hypothesis", h_off.data(), n_reads))) return rc;
-  if (h_off[(size_t)n_reads] != total_hyp) {
-    nvk_set_error("hypothesis offsets end at %lld, total_hyp is %lld", (long long)h_off[(size_t)n_reads],
-                  (long long)total_hyp);
+  std::vector<int64_t> h_off;
+  if ((rc = check_dev_offsets(model->ctx, "hypothesis", hyp_off, n_reads, total_hyp, "total_hyp", true, h_off)))
+    return rc;
+  const EllHyp hyp{hyp_off, hyp_pos, hyp_base, out_total, out_hyp};
+  return ell_run(model, a, model_wobbling, nullptr, out_status, &hyp);
+}
+
+extern "C" int nvk_estimate_joint_hypotheses_batch_dev(
+    nvk_model *model, int64_t n_reads, int64_t total_signal, int64_t total_ref,
+    int64_t total_anchors, const double *signal, const int64_t *sig_off, const int32_t *reference,
+    const int64_t *ref_off, const int32_t *ctx_before, const int64_t *cb_off,
+    const int32_t *ctx_after, const int64_t *ca_off, const int32_t *anchors,
+    const int64_t *anc_off, int bandwidth, int min_event_length, int model_wobbling,
+    int64_t total_hyp, const int64_t *hyp_off, int64_t total_sub, const int64_t *sub_off, const int32_t *sub_pos,
+    const int32_t *sub_base, double *out_total, double *out_hyp, int32_t *out_status) {
+  BatchArgs a;
+  int rc = dev_batch(model, n_reads, total_signal, total_ref, total_anchors, signal, sig_off, reference, ref_off,
+                     ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
+                     out_status, a);
+  if (rc) return rc;
+  if (total_hyp < 0 || total_sub < 0 || !hyp_off || !sub_off || !out_total || (total_hyp > 0 && !out_hyp) ||
+      (total_sub > 0 && (!sub_pos || !sub_base))) {
+    nvk_set_error("negative total_hyp / total_sub or NULL hypothesis / substitution / output pointer");
     return NVK_ERR_INVALID;
   }
-  for (int64_t j = 0; j < n_reads; j++)
-    if (h_off[(size_t)j + 1] - h_off[(size_t)j] > 0x7fffffff) {
-      nvk_set_error("read %lld lists more than 2^31 - 1 hypotheses", (long long)j);
+  if (n_reads == 0) {
+    if (total_hyp != 0 || total_sub != 0) {
+      nvk_set_error("hypothesis offsets end at 0, total_hyp is %lld and total_sub %lld", (long long)total_hyp,
+                    (long long)total_sub);
       return NVK_ERR_INVALID;
     }
-  const EllHyp hyp{hyp_off, hyp_pos, hyp_base, out_total, out_hyp};
+    return NVK_OK;
+  }
+  // the kernel walks both levels of the list: both offset arrays are checked here, on host copies
+  nvk_ctx *ctx = model->ctx;
+  std::vector<int64_t> h_off;
+  if ((rc = check_dev_offsets(ctx, "hypothesis", hyp_off, n_reads, total_hyp, "total_hyp", true, h_off))) return rc;
+  if ((rc = check_dev_offsets(ctx, "substitution", sub_off, total_hyp, total_sub, "total_sub", false, h_off)))
+    return rc;
+  EllHyp hyp{hyp_off, nullptr, nullptr, out_total, out_hyp};
+  hyp.sub_off = sub_off;
+  hyp.sub_pos = sub_pos;
+  hyp.sub_base = sub_base;
+  hyp.total_hyp = total_hyp;
   return ell_run(model, a, model_wobbling, nullptr, out_status, &hyp);
 }

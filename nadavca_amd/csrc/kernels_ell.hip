@@ -10,6 +10,10 @@
 //                      closing against suffix[last+1] (dtw.cpp:93-129)
 //                      — or, in the LISTED variant (nvk_estimate_hypotheses_batch_dev), only for the (p, b) of the
 //                      read's list: the same lanes and arithmetic, the unlisted hypotheses are never run
+//                      — or, in the JOINT variant (nvk_estimate_joint_hypotheses_batch_dev), for listed SETS of
+//                      substitutions: the rows first = max(0, p1 - back) .. last = min(R - 1, pm + fwd) of the set's
+//                      first and last substituted position, every k-mer read with all of them applied, closed at
+//                      `last` as a single one is (see "joint items" below)
 //
 // Mapping (not the reference's): "fused" lanes.  The reference alternates a wobble row
 // (mixture of the k-mers j-1 and j, min event length 0) with an emitting row (k-mer j).  Both
@@ -110,10 +114,25 @@ struct EllListArgs : EllArgs {
   double *out_total;  // [n_reads]
   double *out_hyp;    // [total_hyp]
 };
-template <bool LISTED>
+// The joint variant (nvk_estimate_joint_hypotheses_batch_dev): hypothesis h of the batch is the SET of substitutions
+// sub_off[h] .. sub_off[h+1] of (sub_pos, sub_base), positions strictly ascending; hyp_pos / hyp_base are not used.
+// items: total_hyp records the read's wave fills before its sweeps and takes the hypothesis loops' work from.
+struct EllJointArgs : EllListArgs {
+  const int64_t *sub_off;
+  const int32_t *sub_pos, *sub_base;
+  int4 *items;
+};
+template <bool LISTED, bool JOINT>
 struct EllArgsOf { typedef EllArgs type; };
 template <>
-struct EllArgsOf<true> { typedef EllListArgs type; };
+struct EllArgsOf<true, false> { typedef EllListArgs type; };
+template <>
+struct EllArgsOf<true, true> { typedef EllJointArgs type; };
+// joint items: the effective substitutions (b != ref[p]) of a hypothesis as its first position p1 and one nibble per
+// offset from p1 (bit 3: substituted, bits 0-2: the letter) — at most 14 rows are re-run, so the offsets stay below
+// 14 and the alphabet below 8: two registers per lane, with the last offset in the top nibble.  A hypothesis without
+// an effective substitution is 0.
+constexpr int JOINT_ROWS = 14;  // rows a 16-lane group re-runs at most: role 0 and the closing lane take the other two
 
 // ---- one fused lane ---------------------------------------------------------------------------
 template <int MEL>
@@ -267,6 +286,24 @@ __device__ __forceinline__ int64_t kmer_id_mod(const DeviceModel &dm, const int3
   return id;
 }
 
+// kmer_id_mod for a joint item: the bases at p1 + o are those of `code`'s nibbles
+__device__ __forceinline__ int64_t kmer_id_joint(const DeviceModel &dm, const int32_t *ref, int R,
+                                                 const int32_t *cb, int nb, const int32_t *ca, int na,
+                                                 int pos, int p1, unsigned long long code) {
+  int64_t id = 0;
+  for (int j = pos - dm.central; j < pos - dm.central + dm.k; j++) {
+    const unsigned o = (unsigned)(j - p1);
+    const int nib = o < (unsigned)JOINT_ROWS ? (int)(code >> (4 * o)) & 15 : 0;
+    int v;
+    if (nib & 8) v = nib & 7;
+    else if (j < 0) v = (j + nb >= 0) ? cb[j + nb] : 0;
+    else if (j < R) v = ref[j];
+    else v = (j - R < na) ? ca[j - R] : 0;
+    id = id * dm.alphabet + v;
+  }
+  return id;
+}
+
 // One sweep over the R fused positions of `desc` (prefix order or mirrored suffix order), with the arithmetic of
 // the hypothesis phase: lazy sums, one table density per lane; the mixture's other component is the left
 // neighbour's own density at the same cell, which the neighbour evaluated c steps earlier and hands over through
@@ -410,8 +447,9 @@ __device__ void sweep_fast(const FusedParam *desc, int R, int N, int c, const do
   }
 }
 
-template <int MEL, int GL, bool LISTED>
-__global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED>::type g) {
+template <int MEL, int GL, bool LISTED, bool JOINT = false>
+__global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, JOINT>::type g) {
+  static_assert(LISTED || !JOINT, "the joint variant is a listed one");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double *etab = reinterpret_cast<double *>(smem);
   double *ring = etab + dens::ETN;
@@ -450,7 +488,59 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED>::
     // LISTED: the read's hypotheses; one outside the read or the alphabet fails the read before any table is indexed
     int64_t h0 = 0;
     int n_list = 0;
-    if constexpr (LISTED) {
+    int n_small = 0;  // JOINT: the items that fit a group of GL lanes come first in g.items, the others after them
+    if constexpr (JOINT) {
+      // one lane per hypothesis: check its substitutions, pack the effective ones (b != ref[p]) and file the item
+      // under the lanes it needs — those of at most GL - 2 rows from the front, the others from the back
+      h0 = g.hyp_off[rd];
+      n_list = __builtin_amdgcn_readfirstlane((int)(g.hyp_off[rd + 1] - h0));
+      const int back_ = dm.k - dm.central - 1, fwd_ = dm.central;
+      int n_big = 0;
+      bool bad = false;
+      for (int q0 = 0; q0 < n_list; q0 += 64) {
+        const int q = q0 + lane;
+        const bool have = q < n_list;
+        int p1 = 0, rows = 1;
+        unsigned long long code = 0;
+        if (have) {
+          const int64_t s1 = g.sub_off[h0 + q + 1];
+          int prev = -1, plast = 0;
+          for (int64_t s = g.sub_off[h0 + q]; s < s1; s++) {
+            const int sp = g.sub_pos[s], sb = g.sub_base[s];
+            // (prev >= -1: also sp < 0; launch_ell refuses an alphabet above 8, so a letter fits its 3 bits)
+            if (sp <= prev || sp >= R || sb < 0 || sb >= alpha) {
+              bad = true;
+              break;
+            }
+            prev = sp;
+            if (sb == g.a.reference[m.ref_off + sp]) continue;  // changes nothing: dropped
+            if (code == 0) p1 = sp;
+            if (sp - p1 >= JOINT_ROWS) {  // more rows than a group has lanes for, wherever the read ends
+              bad = true;
+              break;
+            }
+            code |= (unsigned long long)(8 | sb) << (4 * (sp - p1));
+            plast = sp;
+          }
+          if (code != 0) {
+            rows = min(R - 1, plast + fwd_) - max(0, p1 - back_) + 1;
+            code |= (unsigned long long)(plast - p1) << 60;  // (the offsets stay below 14: nibble 15 is free)
+          }
+          bad = bad || rows > JOINT_ROWS;
+        }
+        const bool small = GL == 16 || rows + 2 <= GL;
+        const unsigned long long ms = __ballot(have && small), mb = __ballot(have && !small);
+        const unsigned long long below = (1ull << lane) - 1;
+        const int slot = small ? n_small + __popcll(ms & below) : n_list - 1 - n_big - __popcll(mb & below);
+        if (have) g.items[h0 + slot] = make_int4(p1, q, (int)(unsigned)code, (int)(unsigned)(code >> 32));
+        n_small += __popcll(ms);
+        n_big += __popcll(mb);
+      }
+      if (__any(bad)) {
+        if (lane == 0) g.out_status[rd] = NVK_READ_BAD_INPUT;
+        continue;
+      }
+    } else if constexpr (LISTED) {
       h0 = g.hyp_off[rd];
       n_list = __builtin_amdgcn_readfirstlane((int)(g.hyp_off[rd + 1] - h0));
       bool bad = false;
@@ -529,17 +619,40 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED>::
     // ---- C: substitution hypotheses, 8 per wave step
     const int back = dm.k - dm.central - 1, fwd = dm.central;
     const int n_items = LISTED ? n_list : R * (alpha - 1);
-    const int grp = lane / GL, gl = lane % GL;
     // lane roles in a group: 0 = density of the k-mer before `first` (only feeds the mixture of the
     // first position), 1..npos = the positions first..last, npos+1 = the closing lane.
     // Lane role rho is at cell i = base + u - rho at step u, so whatever lane rho-1 produced at step
     // u-1 (emitting value, density) belongs to the cell lane rho works on at step u.
     const int smax = 2 * (int)g.half - 1;
-    for (int b0 = 0; b0 < n_items; b0 += 64 / GL) {
+    if constexpr (JOINT) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");  // g.items: other lanes wrote them
+    // JOINT with groups of 8 lanes: the items [0, n_small) 8 per wave step as in the listed variant, then the others
+    // in groups of 16 lanes, 4 per step — one loop, the group width a uniform of the step.  No step mixes widths:
+    // a narrow step advances b0 by 64 / GL items but never past n_small, so b0 lands on n_small exactly, the last
+    // narrow step serves only the items below it (`valid`), and every step from there on is wide
+    constexpr bool TWO_WIDTHS = JOINT && GL < 16;
+    const int grp_gl = lane / GL, gl_gl = lane % GL;
+    for (int b0 = 0; b0 < n_items;) {
+      const bool wide = TWO_WIDTHS && b0 >= n_small;
+      const int grp = wide ? lane / 16 : grp_gl, gl = wide ? lane % 16 : gl_gl;
       const int item = b0 + grp;
-      const bool valid = item < n_items;
+      const bool valid = item < (TWO_WIDTHS && !wide ? n_small : n_items);
+      if constexpr (TWO_WIDTHS) b0 = wide ? b0 + 4 : min(b0 + 64 / GL, n_small);
+      else b0 += 64 / GL;
       int p = 0, b = 0, first = 0, last = 0, npos = 0;
-      if (valid) {
+      [[maybe_unused]] int hidx = 0;
+      [[maybe_unused]] unsigned long long code = 0;
+      if constexpr (JOINT) {
+        if (valid) {
+          const int4 it = g.items[h0 + item];
+          p = it.x;
+          hidx = it.y;
+          code = ((unsigned long long)(unsigned)it.w << 32) | (unsigned)it.z;
+          const int plast = p + (int)(code >> 60);
+          first = max(0, p - back);
+          last = min(R - 1, plast + fwd);
+          npos = last - first + 1;
+        }
+      } else if (valid) {
         if constexpr (LISTED) {
           p = g.hyp_pos[h0 + item];
           b = g.hyp_base[h0 + item];
@@ -552,6 +665,10 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED>::
         last = min(R - 1, p + fwd);
         npos = last - first + 1;
       }
+      auto kid = [&](int at) {
+        if constexpr (JOINT) return kmer_id_joint(dm, ref, R, cb, nb, ca, na, at, p, code);
+        else return kmer_id_mod(dm, ref, R, cb, nb, ca, na, at, p, b);
+      };
       const bool is_pos = valid && gl >= 1 && gl <= npos;
       const bool is_fin = valid && gl == npos + 1;
       HypDesc d;
@@ -563,7 +680,7 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED>::
       int sbase = 0, slo = 0x40000000, shi = -0x40000000;
       int64_t idb = -1;
       if (valid && gl == 0) {
-        if (first > 0 && g.wobbling) idb = kmer_id_mod(dm, ref, R, cb, nb, ca, na, first - 1, p, b);
+        if (first > 0 && g.wobbling) idb = kid(first - 1);
         // this lane also carries prefix[first] to the first position: its rows are empty, so what it keeps as
         // "emitting value" is the alternative of the band select — its stream at the cell it is on, which is
         // the cell the lane to its right works on one step later
@@ -571,7 +688,7 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED>::
         slo = bs[first]; shi = be[first];
       } else if (is_pos) {
         const int j = first + gl - 1;
-        idb = kmer_id_mod(dm, ref, R, cb, nb, ca, na, j, p, b);
+        idb = kid(j);
         d.has_wob = (j > 0 && g.wobbling) ? 1 : 0;
         d.wbs = bs[j]; d.wbe = be[j]; d.ebe = be[j + 1];
       } else if (is_fin) {
@@ -579,7 +696,7 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED>::
         // position `last` on band last+1; then the running total against suffix[last+1]
         d.has_wob = (last + 1 < R && g.wobbling) ? 1 : 0;
         if (d.has_wob) {
-          idb = kmer_id_mod(dm, ref, R, cb, nb, ca, na, last + 1, p, b);
+          idb = kid(last + 1);
           // band `last`; the emitting row of `last` only exists from bs[last+1] on, and nothing
           // can be in the wobble row before its first value arrives
           d.wbs = max(bs[last], bs[last + 1]); d.wbe = be[last];
@@ -671,7 +788,8 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED>::
         acc = xm::norm(acc);
         if (RING && acc.e < xm::XZ / 2) acc = xm::zero();  // made of nothing but out-of-band values (fused_step_ring)
         // LISTED: b == ref[p] is no substitution — the total of the two sweeps, as the full matrix holds it there
-        if constexpr (LISTED) g.out_hyp[h0 + item] = (b == ref[p]) ? no_snp : xm::to_log(acc);
+        if constexpr (JOINT) g.out_hyp[h0 + hidx] = code == 0 ? no_snp : xm::to_log(acc);
+        else if constexpr (LISTED) g.out_hyp[h0 + item] = (b == ref[p]) ? no_snp : xm::to_log(acc);
         else out[(size_t)p * alpha + b] = xm::to_log(acc);
       }
     }
@@ -693,6 +811,10 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
   }
   if (dm.k + 2 > 16) {
     nvk_set_error("k-mer size %d needs k + 2 = %d lanes per hypothesis, compiled limit is 16", dm.k, dm.k + 2);
+    return NVK_ERR_UNSUPPORTED;
+  }
+  if (hyp && hyp->sub_off && dm.alphabet > 8) {  // (nvk_model_create builds no such table: the limit of the item code)
+    nvk_set_error("joint hypotheses pack a letter in 3 bits: alphabet %d, compiled limit is 8", dm.alphabet);
     return NVK_ERR_UNSUPPORTED;
   }
   const bool wide_groups = dm.k + 2 > 8;  // 16 lanes per hypothesis instead of 8
@@ -728,7 +850,7 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
   int *counter = (int *)ctx->ws[WS_MISC];
   NVK_HIP(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
 
-  EllListArgs g;
+  EllJointArgs g;
   g.dm = dm;
   g.a = a;
   g.pl = pl;
@@ -754,9 +876,12 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
 
   void (*kern)(EllArgs) = nullptr;
   void (*kern_l)(EllListArgs) = nullptr;
+  void (*kern_j)(EllJointArgs) = nullptr;
+  const bool joint = hyp && hyp->sub_off;
 #define ELL_PICK(M)                                                               \
   do {                                                                            \
-    if (hyp) kern_l = wide_groups ? ell_kernel<M, 16, true> : ell_kernel<M, 8, true>; \
+    if (joint) kern_j = wide_groups ? ell_kernel<M, 16, true, true> : ell_kernel<M, 8, true, true>; \
+    else if (hyp) kern_l = wide_groups ? ell_kernel<M, 16, true> : ell_kernel<M, 8, true>; \
     else kern = wide_groups ? ell_kernel<M, 16, false> : ell_kernel<M, 8, false>;     \
   } while (0)
   switch (mel) {
@@ -774,13 +899,21 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
     g.out_total = hyp->out_total;
     g.out_hyp = hyp->out_hyp;
   }
-  const void *kfn = hyp ? (const void *)kern_l : (const void *)kern;
+  if (joint) {
+    if ((rc = nvk_ws_reserve(ctx, WS_JOINT, (size_t)(hyp->total_hyp + 1) * sizeof(int4)))) return rc;
+    g.sub_off = hyp->sub_off;
+    g.sub_pos = hyp->sub_pos;
+    g.sub_base = hyp->sub_base;
+    g.items = (int4 *)ctx->ws[WS_JOINT];
+  }
+  const void *kfn = joint ? (const void *)kern_j : hyp ? (const void *)kern_l : (const void *)kern;
   if (lds > 64 * 1024) {
     NVK_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
   {
     TimerScope ts(ctx, NVK_K_ELL_HYP);
-    if (hyp) hipLaunchKernelGGL(kern_l, dim3((unsigned)slots), dim3(64), lds, ctx->stream, g);
+    if (joint) hipLaunchKernelGGL(kern_j, dim3((unsigned)slots), dim3(64), lds, ctx->stream, g);
+    else if (hyp) hipLaunchKernelGGL(kern_l, dim3((unsigned)slots), dim3(64), lds, ctx->stream, static_cast<const EllListArgs &>(g));
     else hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(64), lds, ctx->stream, static_cast<const EllArgs &>(g));
   }
   NVK_HIP(hipGetLastError());

@@ -74,7 +74,7 @@ struct DeviceModel {
 // ----- host-side objects ------------------------------------------------------------------
 enum { WS_META = 0, WS_ROWS = 1, WS_BANDTMP = 2, WS_SPILL = 3, WS_BP = 4, WS_MISC = 5, WS_ROWS2 = 6, WS_STAGE = 7,
        WS_SPILL_B = 8, WS_STAGE_B = 9, WS_BP_B = 10, WS_LANE_F = 11, WS_LANE_R = 12, WS_ORDER = 13, WS_OFFS = 14, WS_TIES = 15, WS_RSTATE = 16, WS_STEPS = 17,
-       WS_SEED_TB = 18, WS_SEED_OFF = 19, WS_COUNT = 20 };
+       WS_SEED_TB = 18, WS_SEED_OFF = 19, WS_JOINT = 20, WS_COUNT = 21 };
 
 struct nvk_ctx {
   int device;
@@ -215,6 +215,11 @@ struct EllHyp {
   const int32_t *pos, *base;
   double *out_total;  // [n_reads]
   double *out_hyp;    // [off[n_reads]]
+  // joint hypotheses (nvk_estimate_joint_hypotheses_batch_dev; pos / base are then unused): hypothesis h is the set
+  // of substitutions sub_off[h] .. sub_off[h+1] of (sub_pos, sub_base); total_hyp = off[n_reads]
+  const int64_t *sub_off = nullptr;
+  const int32_t *sub_pos = nullptr, *sub_base = nullptr;
+  int64_t total_hyp = 0;
 };
 // hyp == nullptr: the full matrix into out_ll; else the listed hypotheses into hyp->out_* (out_ll unused)
 int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobbling,

@@ -165,6 +165,41 @@ def estimate_hypotheses_dev(dbatch, bandwidth, min_event_length, kmer_model, mod
     return total, hyp, status
 
 
+def estimate_joint_hypotheses_dev(dbatch, bandwidth, min_event_length, kmer_model, model_wobbling, hyp_off, sub_off,
+                                  sub_pos, sub_base):
+    """``estimate_hypotheses_dev`` for hypotheses of SEVERAL substitutions: read j's hypotheses are
+    ``hyp_off[j] .. hyp_off[j+1]`` (int64 (n+1,)), hypothesis h's substitutions the entries ``sub_off[h] ..
+    sub_off[h+1]`` (int64 (n_hyp+1,)) of ``sub_pos`` / ``sub_base`` (int32, positions strictly ascending within a
+    hypothesis) — device tensors.  -> (total f64 (n,), hyp f64 (n_hyp,), status int32 (n,)): ``hyp[h]`` is the read's
+    log-likelihood with all of h's substitutions applied (rows first .. last of the first and last one re-run and
+    closed as one substitution is; a hypothesis without an effective substitution gives ``total``).  A read with a
+    position or base out of range, positions that do not ascend or a hypothesis that re-runs more than 14 rows gets
+    READ_BAD_INPUT (include/nadavca_hip.h: nvk_estimate_joint_hypotheses_batch_dev).  Values of reads with a negative
+    status are NaN."""
+    torch = dbatch.torch
+    lib = _lib.load()
+    dev = dbatch.device
+    hyp_off = hyp_off.to(device=dev, dtype=torch.int64).contiguous()
+    sub_off = sub_off.to(device=dev, dtype=torch.int64).contiguous()
+    sub_pos = sub_pos.to(device=dev, dtype=torch.int32).contiguous()
+    sub_base = sub_base.to(device=dev, dtype=torch.int32).contiguous()
+    n_hyp, n_sub = int(sub_off.numel()) - 1, int(sub_pos.numel())
+    if int(sub_base.numel()) != n_sub or int(hyp_off.numel()) != dbatch.n + 1 or n_hyp < 0:
+        raise ValueError('estimate_joint_hypotheses_dev: sub_pos and sub_base go together, hyp_off has one entry per '
+                         'read and one more, sub_off one per hypothesis and one more')
+    total = torch.full((dbatch.n,), float('nan'), dtype=torch.float64, device=dev)
+    hyp = torch.full((n_hyp,), float('nan'), dtype=torch.float64, device=dev)
+    status = torch.zeros(dbatch.n, dtype=torch.int32, device=dev)
+    if n_sub == 0:  # (a placeholder element: the C-ABI's pointers of an empty list are never read)
+        sub_pos = sub_base = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.nvk_estimate_joint_hypotheses_batch_dev(
+        kmer_model.handle, dbatch.n, dbatch.total_signal, dbatch.total_ref, dbatch.total_anchors,
+        *dbatch.pointers(), int(bandwidth), int(min_event_length), int(bool(model_wobbling)),
+        n_hyp, _dp(hyp_off), n_sub, _dp(sub_off), _dp(sub_pos), _dp(sub_base), _dp(total),
+        _dp(hyp if n_hyp else total), _dp(status)), 'nvk_estimate_joint_hypotheses_batch_dev')
+    return total, hyp, status
+
+
 # ---- host steps adjacent to the path, on the device (include/nadavca_hip.h, SURVEY.md §8 f1/f2) --------
 def normalize_groups_dev(context, raw, grp_off, out=None):
     """``Read.normalize_reads`` for groups of samples laid end to end (torch f64 / int64 tensors on the

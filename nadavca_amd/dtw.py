@@ -12,6 +12,7 @@ Batched surface (what the estimator uses; one launch for many reads):
     refine_alignment_batch(reads, ...)            reads = list of per-read argument tuples
     estimate_log_likelihoods_batch(reads, ...)
     estimate_hypotheses_batch(reads, hypotheses, ...)   listed substitutions only
+    estimate_joint_hypotheses_batch(reads, hypotheses, ...)   listed SETS of substitutions, each scored as a whole
 
 All compute goes through libnadavca_hip.so; nothing here computes on the CPU.
 """
@@ -279,6 +280,43 @@ def estimate_hypotheses_batch(reads, hypotheses, bandwidth, min_event_length, km
     total, hyp, status = total.cpu().numpy(), hyp.cpu().numpy(), status.cpu().numpy()
     if on_error == 'raise':
         check_status('estimate_hypotheses', status)
+    out = (total, [hyp[off[j]:off[j + 1]] for j in range(batch.n)])
+    return out + (status,) if return_status else out
+
+
+def estimate_joint_hypotheses_batch(reads, hypotheses, bandwidth, min_event_length, kmer_model, model_wobbling,
+                                    on_error='raise', return_status=False):
+    """``estimate_hypotheses_batch`` for hypotheses that hold several substitutions.  hypotheses: per read a list of
+    (m, 2) integer arrays of (position, substituted base) rows with strictly ascending positions, m >= 0 (no row: the
+    read's total), in any order, duplicates allowed.  -> (total f64 (n,), list of f64 (number of hypotheses,) arrays):
+    entry h of read j is its log-likelihood with ALL of h's substitutions applied: the rows the first to the last of
+    them influence are re-run once and closed as a single substitution's are (nvk_estimate_joint_hypotheses_batch_dev;
+    rows with b == reference[p] change nothing).  A position or base out of range, positions that do not ascend or a
+    hypothesis that re-runs more than 14 rows fails its read (READ_BAD_INPUT: ValueError, or with on_error='status'
+    NaN values and, with return_status=True, the status array as a third result)."""
+    import torch
+    from .device import DeviceBatch, estimate_joint_hypotheses_dev
+    batch = reads if isinstance(reads, FlatBatch) else FlatBatch(reads)
+    if len(hypotheses) != batch.n:
+        raise ValueError('estimate_joint_hypotheses_batch: %d hypothesis lists for %d reads'
+                         % (len(hypotheses), batch.n))
+    hyps = [[np.asarray(h, dtype=np.int64).reshape(-1, 2) for h in hs] for hs in hypotheses]
+    off = _offsets([len(hs) for hs in hyps])
+    if batch.n == 0:
+        out = (np.zeros(0), [])
+        return out + (np.zeros(0, dtype=np.int32),) if return_status else out
+    sub_off = _offsets([h.shape[0] for hs in hyps for h in hs])
+    flat = np.concatenate([h for hs in hyps for h in hs] + [np.zeros((0, 2), dtype=np.int64)])
+    if flat.size and (flat.min() < -(1 << 31) or flat.max() >= (1 << 31)):
+        raise ValueError('estimate_joint_hypotheses_batch: a position or base does not fit 32 bits')
+    dbatch = DeviceBatch(batch, torch.device('cuda', kmer_model.context.device))
+    total, hyp, status = estimate_joint_hypotheses_dev(
+        dbatch, bandwidth, min_event_length, kmer_model, model_wobbling, torch.from_numpy(off),
+        torch.from_numpy(sub_off), torch.from_numpy(flat[:, 0].astype(np.int32)),
+        torch.from_numpy(flat[:, 1].astype(np.int32)))
+    total, hyp, status = total.cpu().numpy(), hyp.cpu().numpy(), status.cpu().numpy()
+    if on_error == 'raise':
+        check_status('estimate_joint_hypotheses', status)
     out = (total, [hyp[off[j]:off[j + 1]] for j in range(batch.n)])
     return out + (status,) if return_status else out
 
