@@ -355,6 +355,22 @@ int check_offsets(const char *what, const int64_t *off, int64_t n) {
   return NVK_OK;
 }
 
+int nvk_fetch_offsets(nvk_ctx *ctx, const char *what, const int64_t *off, int64_t n, std::vector<int64_t> &h_off,
+                      const char *total_name, int64_t total) {
+  if (!off) return check_offsets(what, off, n);
+  h_off.resize((size_t)n + 1);
+  NVK_HIP(hipMemcpyAsync(h_off.data(), off, h_off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  NVK_HIP(hipStreamSynchronize(ctx->stream));
+  int rc = check_offsets(what, h_off.data(), n);
+  if (rc) return rc;
+  if (total_name && h_off[(size_t)n] != total) {
+    nvk_set_error("%s offsets end at %lld, %s is %lld", what, (long long)h_off[(size_t)n], total_name,
+                  (long long)total);
+    return NVK_ERR_INVALID;
+  }
+  return NVK_OK;
+}
+
 int check_common(nvk_model *model, int64_t n_reads, int bandwidth, int mel) {
   if (!model) {
     nvk_set_error("model handle is NULL");
@@ -411,7 +427,7 @@ struct PlanHost {
 // plan a batch: metas + row table (+ for refine_alignment the lane records of kernels_align3, the launch order
 // and the step counts in that order) in ctx workspaces; ONE copy + synchronisation brings the totals and the
 // step counts to the host (ctx->h_plan)
-int plan_batch(nvk_model *model, const BatchArgs &a, int mode, int wobbling, PlanTotals &tot, const int **order,
+int plan_batch(nvk_model *model, const BatchArgs &a, int mode, PlanTotals &tot, const int **order,
                const int32_t **steps_sorted) {
   nvk_ctx *ctx = model->ctx;
   int64_t n = a.n_reads;
@@ -429,8 +445,8 @@ int plan_batch(nvk_model *model, const BatchArgs &a, int mode, int wobbling, Pla
                      "planner results")))
     return rc;
   PlanHost *hp = (PlanHost *)ctx->h_plan;
-  PlanTotals *d_tot = (PlanTotals *)((char *)ctx->ws[WS_MISC] + 64);
-  rc = launch_plan(ctx, model->dm, a, mode, wobbling, (ReadMeta *)ctx->ws[WS_META],
+  PlanTotals *d_tot = nvk_plan_totals(ctx);
+  rc = launch_plan(ctx, model->dm, a, mode, (ReadMeta *)ctx->ws[WS_META],
                    (RowParam *)ctx->ws[WS_ROWS], (unsigned long long *)ctx->ws[WS_BANDTMP], d_tot,
                    ctx->ws[WS_LANE_F], ctx->ws[WS_LANE_R], (int32_t *)ctx->ws[WS_OFFS]);
   if (rc) return rc;
@@ -528,7 +544,7 @@ extern "C" int nvk_refine_alignment_batch_dev(
   ctx->last_ties = ctx->last_ties_exact = ctx->last_ties_near = ctx->last_ties_ulp = 0;
   const int *order = nullptr;
   const int32_t *steps_sorted = nullptr;
-  rc = plan_batch(model, a, model_transitions ? PLAN_ALIGN_TRANS : PLAN_ALIGN_PLAIN, 0, tot, &order, &steps_sorted);
+  rc = plan_batch(model, a, model_transitions ? PLAN_ALIGN_TRANS : PLAN_ALIGN_PLAIN, tot, &order, &steps_sorted);
   if (rc) return rc;
   // WS_TIES: per-read tie bits, then 4 class counts, then the number of reads handed to the exact kernel
   if ((rc = nvk_ws_reserve(ctx, WS_TIES, (size_t)(n_reads + 8) * sizeof(int32_t)))) return rc;
@@ -600,7 +616,7 @@ int ell_run(nvk_model *model, const BatchArgs &a, int model_wobbling, double *ou
   pl.bs = (int32_t *)ctx->ws[WS_BP];
   pl.be = pl.bs + nrow;
   pl.rowoff = pl.be + nrow;
-  PlanTotals *d_tot = (PlanTotals *)((char *)ctx->ws[WS_MISC] + 64);
+  PlanTotals *d_tot = nvk_plan_totals(ctx);
   rc = launch_plan_ell(ctx, model->dm, a, model_wobbling ? 1 : 0, pl,
                        (unsigned long long *)ctx->ws[WS_BANDTMP], d_tot);
   if (rc) return rc;
@@ -632,26 +648,13 @@ extern "C" int nvk_estimate_log_likelihoods_batch_dev(
 }
 
 namespace {
-// off[0..n] on the device: copied to the host and checked (check_offsets, ends at `total`, the argument named
-// total_name); hyp_per_read: off is a read's hypothesis list, which the kernel counts in an int
-int check_dev_offsets(nvk_ctx *ctx, const char *what, const int64_t *off, int64_t n, int64_t total,
-                      const char *total_name, bool hyp_per_read, std::vector<int64_t> &h_off) {
-  int rc;
-  h_off.resize((size_t)n + 1);
-  NVK_HIP(hipMemcpyAsync(h_off.data(), off, h_off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  if ((rc = check_offsets(what, h_off.data(), n))) return rc;
-  if (h_off[(size_t)n] != total) {
-    nvk_set_error("%s offsets end at %lld, %s is %lld", what, (long long)h_off[(size_t)n], total_name,
-                  (long long)total);
-    return NVK_ERR_INVALID;
-  }
-  if (hyp_per_read)
-    for (int64_t j = 0; j < n; j++)
-      if (h_off[(size_t)j + 1] - h_off[(size_t)j] > 0x7fffffff) {
-        nvk_set_error("read %lld lists more than 2^31 - 1 hypotheses", (long long)j);
-        return NVK_ERR_INVALID;
-      }
+// a read's hypothesis list is counted in an int by the kernel
+int check_hyp_counts(const std::vector<int64_t> &h_off, int64_t n) {
+  for (int64_t j = 0; j < n; j++)
+    if (h_off[(size_t)j + 1] - h_off[(size_t)j] > 0x7fffffff) {
+      nvk_set_error("read %lld lists more than 2^31 - 1 hypotheses", (long long)j);
+      return NVK_ERR_INVALID;
+    }
   return NVK_OK;
 }
 }  // namespace
@@ -682,8 +685,8 @@ extern "C" int nvk_estimate_hypotheses_batch_dev(
   }
   // the kernel walks hyp_off[j] .. hyp_off[j+1] of three arrays of total_hyp entries: checked here, on a host copy
   std::vector<int64_t> h_off;
-  if ((rc = check_dev_offsets(model->ctx, "hypothesis", hyp_off, n_reads, total_hyp, "total_hyp", true, h_off)))
-    return rc;
+  if ((rc = nvk_fetch_offsets(model->ctx, "hypothesis", hyp_off, n_reads, h_off, "total_hyp", total_hyp))) return rc;
+  if ((rc = check_hyp_counts(h_off, n_reads))) return rc;
   const EllHyp hyp{hyp_off, hyp_pos, hyp_base, out_total, out_hyp};
   return ell_run(model, a, model_wobbling, nullptr, out_status, &hyp);
 }
@@ -717,9 +720,9 @@ extern "C" int nvk_estimate_joint_hypotheses_batch_dev(
   // the kernel walks both levels of the list: both offset arrays are checked here, on host copies
   nvk_ctx *ctx = model->ctx;
   std::vector<int64_t> h_off;
-  if ((rc = check_dev_offsets(ctx, "hypothesis", hyp_off, n_reads, total_hyp, "total_hyp", true, h_off))) return rc;
-  if ((rc = check_dev_offsets(ctx, "substitution", sub_off, total_hyp, total_sub, "total_sub", false, h_off)))
-    return rc;
+  if ((rc = nvk_fetch_offsets(ctx, "hypothesis", hyp_off, n_reads, h_off, "total_hyp", total_hyp))) return rc;
+  if ((rc = check_hyp_counts(h_off, n_reads))) return rc;
+  if ((rc = nvk_fetch_offsets(ctx, "substitution", sub_off, total_hyp, h_off, "total_sub", total_sub))) return rc;
   EllHyp hyp{hyp_off, nullptr, nullptr, out_total, out_hyp};
   hyp.sub_off = sub_off;
   hyp.sub_pos = sub_pos;

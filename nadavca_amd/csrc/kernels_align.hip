@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include "nvk_internal.h"
+#include "wave.h"
 #include "xmath.h"
 
 namespace {
@@ -34,15 +35,6 @@ using xm::X;
 constexpr int CH = 128;    // signal refill chunk (samples)
 constexpr int TABN = 128;  // row-table window (two 64-row blocks)
 constexpr int PF = 4;      // forward sweep: spill prefetch depth (steps)
-
-// One wave per workgroup: LDS traffic of a wave is executed in program order, so ordering
-// between lanes only needs the compiler not to reorder the accesses.  (__syncthreads() would
-// also drain vmcnt, i.e. wait for the spill stores of every step.)
-#define WAVE_SYNC()                                        \
-  do {                                                     \
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); \
-    __builtin_amdgcn_wave_barrier();                       \
-  } while (0)
 
 struct AlignArgs {
   const ReadMeta *metas;

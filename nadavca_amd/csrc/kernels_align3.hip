@@ -71,6 +71,7 @@
 #include "xmath.h"
 #include "dens.h"
 #include "lane3.h"
+#include "wave.h"
 
 namespace {
 
@@ -124,11 +125,6 @@ __device__ __forceinline__ double2 spill_load2(__amdgpu_buffer_rsrc_t rs, int la
   return __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, pair * 1024, 0));
 }
 
-#define WAVE_SYNC()                                        \
-  do {                                                     \
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); \
-    __builtin_amdgcn_wave_barrier();                       \
-  } while (0)
 // end of a step: the history ring's writes of this step before the next step's reads.  A team of waves
 // (W > 1) meets at a workgroup barrier behind a wait for its LDS operations ONLY — __syncthreads() would
 // also wait for the spill stores / the spill prefetch in flight, which is the traffic the step overlaps.

@@ -15,12 +15,7 @@ __global__ void consensus_kernel(int64_t n_reads, int64_t total_ref, int alpha, 
                                  long long *coverage) {
   int64_t gidx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (gidx >= total_ref) return;
-  int64_t lo = 0, hi = n_reads;  // ref_off[lo] <= gidx < ref_off[hi]
-  while (hi - lo > 1) {
-    int64_t mid = (lo + hi) >> 1;
-    if (ref_off[mid] <= gidx) lo = mid; else hi = mid;
-  }
-  const int64_t rd = lo;
+  const int64_t rd = owner_of(ref_off, n_reads, gidx);
   if (status && status[rd] != NVK_READ_OK) return;
   const int64_t r0 = ref_off[rd];
   const int R = (int)(ref_off[rd + 1] - r0);
@@ -49,13 +44,9 @@ __global__ void posterior_kernel(int64_t len, int64_t n_seg, const int64_t *seg_
   if (i >= len) return;
   int64_t s0 = 0, s1 = len;
   if (seg_off) {
-    int64_t lo = 0, hi = n_seg;
-    while (hi - lo > 1) {
-      int64_t mid = (lo + hi) >> 1;
-      if (seg_off[mid] <= i) lo = mid; else hi = mid;
-    }
-    s0 = seg_off[lo];
-    s1 = seg_off[lo + 1];
+    const int64_t sg = owner_of(seg_off, n_seg, i);
+    s0 = seg_off[sg];
+    s1 = seg_off[sg + 1];
   }
   const int64_t cs = (i - k + 1 > s0) ? i - k + 1 : s0;
   const int64_t ce = (i + k < s1) ? i + k : s1;

@@ -50,6 +50,8 @@
 #include <math.h>
 
 #include "nvk_internal.h"
+#include "kmer.h"
+#include "wave.h"
 #include "xmath.h"
 #include "dens.h"
 
@@ -65,12 +67,6 @@ constexpr int PF = 4;      // phase C prefetch depth (steps)
 constexpr int HRS = 16;    // sweeps: steps between mantissa normalisations
 // exp(-2): the reference divides the mixture by Probability(2) == exp(2) (kmer_model.cpp:59-61)
 #define EXPM2_D 0x1.152aaa3bf81ccp-3
-
-#define WAVE_SYNC()                                        \
-  do {                                                     \
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); \
-    __builtin_amdgcn_wave_barrier();                       \
-  } while (0)
 
 // One cell of the row store: 16 bytes, one store / one load (round 3; before: 8 + 4 bytes in two arrays — two
 // accesses per cell, and twice as many partly written lines open per wave than the L2 holds: the HBM write traffic
@@ -247,68 +243,18 @@ __device__ __forceinline__ void fused_step_ring(const HypDesc &d, LaneState<MEL>
   }
 }
 
-// value of the previous lane (DPP row_shr:1 with bound_ctrl: the first lane of each 16-lane row
-// reads 0 — those lanes are role 0 of a group and never use what arrives from the left)
-__device__ __forceinline__ double dpp_shr1(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_mov_dpp(lo, 0x111, 0xf, 0xf, true);
-  hi = __builtin_amdgcn_mov_dpp(hi, 0x111, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
+// the DPP moves of wave.h for a scaled number.  dpp_shr1: the first lane of each 16-lane row reads 0 — those lanes
+// are role 0 of a group and never use what arrives from the left; dpp_ror1: the sweeps' hand-over at skew 1
 __device__ __forceinline__ X dpp_shr1(X v) {
-  return X{dpp_shr1(v.m), __builtin_amdgcn_mov_dpp(v.e, 0x111, 0xf, 0xf, true)};
+  return X{::dpp_shr1(v.m), __builtin_amdgcn_mov_dpp(v.e, 0x111, 0xf, 0xf, true)};
 }
-
-// value of lane (l - 1) mod 64 (DPP wave_ror:1, GFX9): the sweeps' hand-over at skew 1
-__device__ __forceinline__ double dpp_ror1(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_mov_dpp(lo, 0x13C, 0xf, 0xf, false);
-  hi = __builtin_amdgcn_mov_dpp(hi, 0x13C, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ X dpp_ror1(X v) {
-  return X{dpp_ror1(v.m), __builtin_amdgcn_mov_dpp(v.e, 0x13C, 0xf, 0xf, false)};
-}
-
-// k-mer id of position pos with base `p` replaced by `b` (sequence.cpp:31-38, kmer_model.cpp:22-30)
-__device__ __forceinline__ int64_t kmer_id_mod(const DeviceModel &dm, const int32_t *ref, int R,
-                                               const int32_t *cb, int nb, const int32_t *ca, int na,
-                                               int pos, int p, int b) {
-  int64_t id = 0;
-  for (int j = pos - dm.central; j < pos - dm.central + dm.k; j++) {
-    int v;
-    if (j == p) v = b;
-    else if (j < 0) v = (j + nb >= 0) ? cb[j + nb] : 0;
-    else if (j < R) v = ref[j];
-    else v = (j - R < na) ? ca[j - R] : 0;
-    id = id * dm.alphabet + v;
-  }
-  return id;
-}
-
-// kmer_id_mod for a joint item: the bases at p1 + o are those of `code`'s nibbles
-__device__ __forceinline__ int64_t kmer_id_joint(const DeviceModel &dm, const int32_t *ref, int R,
-                                                 const int32_t *cb, int nb, const int32_t *ca, int na,
-                                                 int pos, int p1, unsigned long long code) {
-  int64_t id = 0;
-  for (int j = pos - dm.central; j < pos - dm.central + dm.k; j++) {
-    const unsigned o = (unsigned)(j - p1);
-    const int nib = o < (unsigned)JOINT_ROWS ? (int)(code >> (4 * o)) & 15 : 0;
-    int v;
-    if (nib & 8) v = nib & 7;
-    else if (j < 0) v = (j + nb >= 0) ? cb[j + nb] : 0;
-    else if (j < R) v = ref[j];
-    else v = (j - R < na) ? ca[j - R] : 0;
-    id = id * dm.alphabet + v;
-  }
-  return id;
-}
+__device__ __forceinline__ X dpp_ror1(X v) { return X{::dpp_ror1(v.m), ::dpp_ror1(v.e)}; }
 
 // One sweep over the R fused positions of `desc` (prefix order or mirrored suffix order), with the arithmetic of
 // the hypothesis phase: lazy sums, one table density per lane; the mixture's other component is the left
 // neighbour's own density at the same cell, which the neighbour evaluated c steps earlier and hands over through
 // the LDS ring together with its emitting value (24 B per lane and slot).
-// what a sweep lane needs of a FusedParam (48 B instead of 80 B in the LDS window)
+// a FusedParam as a sweep lane holds it in the LDS window: the constants scaled
 struct __attribute__((aligned(16))) SweepLane {
   double bm, bac, bmc;  // the emitting Gaussian, constants scaled for dens::density
   int32_t wbs, wbe, ebe, ebs, soff, has_wob;
@@ -665,9 +611,18 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
         last = min(R - 1, p + fwd);
         npos = last - first + 1;
       }
+      // k-mer id of position `at` under the hypothesis: base p replaced by b, or (joint) the bases at p + o by those
+      // of `code`'s nibbles
       auto kid = [&](int at) {
-        if constexpr (JOINT) return kmer_id_joint(dm, ref, R, cb, nb, ca, na, at, p, code);
-        else return kmer_id_mod(dm, ref, R, cb, nb, ca, na, at, p, b);
+        if constexpr (JOINT)
+          return kmer_id(dm, ref, R, cb, nb, ca, na, at, [&](int j, int &v) {
+            const unsigned o = (unsigned)(j - p);
+            const int nib = o < (unsigned)JOINT_ROWS ? (int)(code >> (4 * o)) & 15 : 0;
+            v = nib & 7;
+            return (nib & 8) != 0;
+          });
+        else
+          return kmer_id(dm, ref, R, cb, nb, ca, na, at, [&](int j, int &v) { v = b; return j == p; });
       };
       const bool is_pos = valid && gl >= 1 && gl <= npos;
       const bool is_fin = valid && gl == npos + 1;
@@ -861,8 +816,7 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
   g.counter = counter;
   {
     int *order = nullptr;
-    // (the planner's totals are still where launch_plan_ell left them: ws[WS_MISC] + 64, api.hip)
-    rc = launch_order(ctx, pl.metas, a.n_reads, (const PlanTotals *)((const char *)ctx->ws[WS_MISC] + 64), &order, nullptr);
+    rc = launch_order(ctx, pl.metas, a.n_reads, nvk_plan_totals(ctx), &order, nullptr);  // (as launch_plan_ell left them)
     if (rc) return rc;
     g.order = order;
   }

@@ -31,103 +31,13 @@
 #include <vector>
 
 #include "nvk_internal.h"
+#include "kmer.h"
+#include "npsum.h"
 
 namespace {
 
 constexpr int NT = 256;
 constexpr int MAX_K = 16;  // longest k-mer whose key fits the checks below (alphabet^k <= 2^31)
-
-// ---- numpy's pairwise summation (numpy/_core/src/umath/loops_utils.h.src, @TYPE@_pairwise_sum) ------
-// The same order as np_sum in kernels_renorm.hip, over a generated sequence f(0 .. n) instead of an array (the
-// squared deviations of pass 2 and the values of the reduction are never stored), and with the walk's stack in
-// registers: every access to it is an unrolled select over its 8 frames, so it needs no scratch memory.
-// Resource use (gfx950, -Rpass-analysis=kernel-resource-usage): kmer_event_kernel 72 / 74 VGPRs and 72 / 74 SGPRs
-// (pass 1 / pass 2), long_event_kernel 82 / 84 VGPRs and 99 / 101 SGPRs, kmer_reduce_kernel 86 VGPRs and 99 SGPRs;
-// no LDS, no scratch, no spills.
-template <class F>
-__device__ __forceinline__ double np_block_sum(const F &f, int o, int n) {  // n <= 128
-  if (n < 8) {
-    double res = 0.0;
-    for (int i = 0; i < n; i++) res += f(o + i);
-    return res;
-  }
-  double r0 = f(o + 0), r1 = f(o + 1), r2 = f(o + 2), r3 = f(o + 3);
-  double r4 = f(o + 4), r5 = f(o + 5), r6 = f(o + 6), r7 = f(o + 7);
-  int i = 8;
-  for (; i < n - (n % 8); i += 8) {
-    r0 += f(o + i + 0); r1 += f(o + i + 1); r2 += f(o + i + 2); r3 += f(o + i + 3);
-    r4 += f(o + i + 4); r5 += f(o + i + 5); r6 += f(o + i + 6); r7 += f(o + i + 7);
-  }
-  double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-  for (; i < n; i++) res += f(o + i);
-  return res;
-}
-
-__device__ __forceinline__ int np_split(int m) {  // left half of a node of m > 128 elements
-  int n2 = m / 2;
-  return n2 - n2 % 8;
-}
-
-// sum(a, n) = sum(a, n2) + sum(a + n2, n - n2) down to blocks of <= 128, n <= 8192: a node of m elements has
-// children of at most m/2 + 8, so a path from the root holds at most 7 internal nodes.  The walk keeps the path as
-// bits (bit i: the node at depth i + 1 is a right child), rebuilds a node's offset and size from them when it needs
-// them, and keeps the left sums of the path's nodes in sv.
-template <class F>
-__device__ double np_pairwise_sum(const F &f, int o0, int n) {
-  if (n <= 128) return np_block_sum(f, o0, n);
-  constexpr int D = 8;
-  double sv[D];
-#pragma unroll
-  for (int i = 0; i < D; i++) sv[i] = 0.0;
-  unsigned path = 0;
-  int d = 0, o = o0, m = n;  // the current node and its depth
-  for (;;) {
-    while (m > 128) {  // descend left
-      m = np_split(m);
-      path &= ~(1u << d);
-      d++;
-    }
-    double ret = np_block_sum(f, o, m);
-    for (;;) {  // ascend until a node still has its right child to do
-      if (d == 0) return ret;
-      d--;
-      if (!((path >> d) & 1u)) {  // the left child of the node at depth d is done: keep it, go right
-#pragma unroll
-        for (int i = 0; i < D; i++)
-          if (i == d) sv[i] = ret;
-        int po = o0, pm = n;
-        for (int i = 0; i < d; i++) {
-          const int n2 = np_split(pm);
-          if ((path >> i) & 1u) { po += n2; pm -= n2; } else { pm = n2; }
-        }
-        const int n2 = np_split(pm);
-        path |= 1u << d;
-        d++;
-        o = po + n2;
-        m = pm - n2;
-        break;
-      }
-      double pv = 0.0;
-#pragma unroll
-      for (int i = 0; i < D; i++)
-        if (i == d) pv = sv[i];
-      ret = pv + ret;
-    }
-  }
-}
-
-// numpy.add.reduce of a contiguous float64 vector: pieces of 8192 (numpy's buffer), each summed pairwise and added to
-// the running result, which starts at 0 (as np_sum in kernels_renorm.hip; tests/test_renorm_cpu.py)
-template <class F>
-__device__ double np_sum(const F &f, int64_t n) {
-  double res = 0.0;
-  for (int64_t o = 0; o < n; o += 8192) {
-    const int64_t base = o;
-    auto g = [&](int i) { return f(base + i); };
-    res = res + np_pairwise_sum(g, 0, (int)(n - o < 8192 ? n - o : 8192));
-  }
-  return res;
-}
 
 // the value of one counted event of n samples at xs: np.sum of the samples (pass 1) or of their squared deviations
 // from the k-mer's level (pass 2)
@@ -155,6 +65,7 @@ __global__ __launch_bounds__(NT) void kmer_event_kernel(int64_t n_reads, const d
                                                         int64_t *out_key, double *out_val, int64_t *out_len) {
   const int lane = threadIdx.x & 63;
   const int64_t waves = (int64_t)gridDim.x * (NT / 64);
+  const DeviceModel dm{k, central, alphabet, 0, nullptr, nullptr, nullptr};  // (kmer.h reads the window's shape only)
   for (int64_t rd = (int64_t)blockIdx.x * (NT / 64) + threadIdx.x / 64; rd < n_reads; rd += waves) {
     if (status && status[rd] != 0) {
       for (int64_t g = ref_off[rd] + lane; g < ref_off[rd + 1]; g += 64) {
@@ -171,7 +82,7 @@ __global__ __launch_bounds__(NT) void kmer_event_kernel(int64_t n_reads, const d
     const int N = (int)(sig_off[rd + 1] - sig_off[rd]);
     const int B = (int)(cb_off[rd + 1] - cb_off[rd]);
     const int A = (int)(ca_off[rd + 1] - ca_off[rd]);
-    const int32_t *ref = reference + r0, *cb = ctx_before + cb_off[rd] + B, *ca = ctx_after + ca_off[rd] - R;
+    const int32_t *ref = reference + r0, *cb = ctx_before + cb_off[rd], *ca = ctx_after + ca_off[rd];
     const int32_t *ev = events + 2 * r0;
     for (int g = lane; g < R; g += 64) {
       int64_t key = -1;
@@ -182,18 +93,7 @@ __global__ __launch_bounds__(NT) void kmer_event_kernel(int64_t n_reads, const d
         int s = ev[2 * g], e = ev[2 * g + 1];
         s = s < 0 ? 0 : (s > N ? N : s);  // numpy slice clamping, as event_means_kernel
         e = e < 0 ? 0 : (e > N ? N : e);
-        if (e > s) {
-          key = 0;
-          for (int m = 0; m < k; m++) {
-            const int p = p0 + m;
-            const int32_t b = p < 0 ? cb[p] : (p < R ? ref[p] : ca[p]);
-            if (b < 0 || b >= alphabet) {
-              key = -1;
-              break;
-            }
-            key = key * alphabet + b;
-          }
-        }
+        if (e > s) key = kmer_id_checked(dm, ref, R, cb, B, ca, A, g);
         if (key >= 0) {
           len = e - s;
           if (len <= 128) val = event_value<PASS2>(x + s, len, level, key);  // else: long_event_kernel
@@ -214,11 +114,7 @@ __global__ __launch_bounds__(NT) void long_event_kernel(int64_t n_reads, int64_t
                                                         const int64_t *key, const int64_t *len, double *out_val) {
   for (int64_t g = (int64_t)blockIdx.x * NT + threadIdx.x; g < total_ref; g += (int64_t)gridDim.x * NT) {
     if (key[g] < 0 || len[g] <= 128) continue;
-    int64_t lo = 0, hi = n_reads;  // ref_off[lo] <= g < ref_off[hi]
-    while (hi - lo > 1) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (ref_off[mid] <= g) lo = mid; else hi = mid;
-    }
+    const int64_t lo = owner_of(ref_off, n_reads, g);
     const int64_t N = sig_off[lo + 1] - sig_off[lo];
     int64_t s = events[2 * g];
     s = s < 0 ? 0 : (s > N ? N : s);
@@ -254,11 +150,6 @@ __global__ __launch_bounds__(NT) void kmer_reduce_kernel(int64_t n_events, int64
   }
 }
 
-unsigned grid_of(int64_t items, int64_t per_block) {
-  const int64_t want = (items + per_block - 1) / per_block;
-  return (unsigned)(want < 65535 * 16 ? want : 65535 * 16);
-}
-
 // alphabet^k, or -1 when k / alphabet are outside the served range
 int64_t table_size(int k, int alphabet) {
   if (k < 1 || k > MAX_K || alphabet < 1 || alphabet > 64) return -1;
@@ -268,13 +159,6 @@ int64_t table_size(int k, int alphabet) {
     if (n > ((int64_t)1 << 31)) return -1;
   }
   return n;
-}
-
-int copy_check(nvk_ctx *ctx, const char *what, const int64_t *d_off, int64_t n_reads, std::vector<int64_t> &off) {
-  off.resize((size_t)n_reads + 1);
-  NVK_HIP(hipMemcpyAsync(off.data(), d_off, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return check_offsets(what, off.data(), n_reads);
 }
 
 }  // namespace
@@ -309,26 +193,16 @@ extern "C" int nvk_kmer_event_stats_dev(nvk_ctx *ctx, int64_t n_reads, int64_t t
   NVK_HIP(hipSetDevice(ctx->device));
   std::vector<int64_t> off;
   int rc;
-  if ((rc = copy_check(ctx, "reference", ref_off, n_reads, off))) return rc;
-  if (off[n_reads] != total_ref) {
-    nvk_set_error("%s: reference offsets end at %lld, total_ref is %lld", what, (long long)off[n_reads],
-                  (long long)total_ref);
-    return NVK_ERR_INVALID;
-  }
-  if ((rc = copy_check(ctx, "signal", sig_off, n_reads, off))) return rc;
-  if (off[n_reads] > 0 && !signal) {
-    nvk_set_error("%s: signal is NULL", what);
-    return NVK_ERR_INVALID;
-  }
-  if ((rc = copy_check(ctx, "context_before", cb_off, n_reads, off))) return rc;
-  if (off[n_reads] > 0 && !ctx_before) {
-    nvk_set_error("%s: context_before is NULL", what);
-    return NVK_ERR_INVALID;
-  }
-  if ((rc = copy_check(ctx, "context_after", ca_off, n_reads, off))) return rc;
-  if (off[n_reads] > 0 && !ctx_after) {
-    nvk_set_error("%s: context_after is NULL", what);
-    return NVK_ERR_INVALID;
+  if ((rc = nvk_fetch_offsets(ctx, "reference", ref_off, n_reads, off, "total_ref", total_ref))) return rc;
+  // (a data array may be NULL only when its offsets end at 0)
+  const struct { const char *name; const int64_t *off; const void *data; } arr[3] = {
+      {"signal", sig_off, signal}, {"context_before", cb_off, ctx_before}, {"context_after", ca_off, ctx_after}};
+  for (const auto &x : arr) {
+    if ((rc = nvk_fetch_offsets(ctx, x.name, x.off, n_reads, off))) return rc;
+    if (off[n_reads] > 0 && !x.data) {
+      nvk_set_error("%s: %s is NULL", what, x.name);
+      return NVK_ERR_INVALID;
+    }
   }
   if (total_ref == 0) return NVK_OK;
   if (!events || !reference || !out_key || !out_val || !out_len) {

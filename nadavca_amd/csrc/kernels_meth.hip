@@ -107,22 +107,8 @@ int meth_check(const char *what, nvk_ctx *ctx, int64_t n_reads, int64_t total_re
     return NVK_ERR_INVALID;
   }
   NVK_HIP(hipSetDevice(ctx->device));
-  std::vector<int64_t> off((size_t)n_reads + 1);
-  NVK_HIP(hipMemcpyAsync(off.data(), ref_off, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  int rc = check_offsets("reference", off.data(), n_reads);
-  if (rc) return rc;
-  if (off[n_reads] != total_ref) {
-    nvk_set_error("%s: reference offsets end at %lld, total_ref is %lld", what, (long long)off[n_reads],
-                  (long long)total_ref);
-    return NVK_ERR_INVALID;
-  }
-  return NVK_OK;
-}
-
-unsigned meth_blocks(int64_t n_reads) {
-  const int64_t want = (n_reads + NT / 64 - 1) / (NT / 64);
-  return (unsigned)(want < 65535 * 16 ? want : 65535 * 16);
+  std::vector<int64_t> off;
+  return nvk_fetch_offsets(ctx, "reference", ref_off, n_reads, off, "total_ref", total_ref);
 }
 
 }  // namespace
@@ -140,7 +126,7 @@ extern "C" int nvk_meth_count_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_r
   }
   {
     TimerScope ts(ctx, NVK_K_METH);
-    hipLaunchKernelGGL(meth_kernel<false>, dim3(meth_blocks(n_reads)), dim3(NT), 0, ctx->stream, n_reads,
+    hipLaunchKernelGGL(meth_kernel<false>, dim3(grid_of(n_reads, NT / 64)), dim3(NT), 0, ctx->stream, n_reads,
                        reference, ref_off, means, (const double *)nullptr, status, pattern, pattern_len, out_count,
                        (const int64_t *)nullptr, (int64_t *)nullptr, (double *)nullptr, (double *)nullptr);
   }
@@ -161,14 +147,8 @@ extern "C" int nvk_meth_scores_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_
     nvk_set_error("nvk_meth_scores_dev: expected is NULL");
     return NVK_ERR_INVALID;
   }
-  if (!occ_off) {
-    nvk_set_error("nvk_meth_scores_dev: occurrence offsets are NULL");
-    return NVK_ERR_INVALID;
-  }
-  std::vector<int64_t> off((size_t)n_reads + 1);
-  NVK_HIP(hipMemcpyAsync(off.data(), occ_off, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  if ((rc = check_offsets("occurrence", off.data(), n_reads))) return rc;
+  std::vector<int64_t> off;
+  if ((rc = nvk_fetch_offsets(ctx, "occurrence", occ_off, n_reads, off))) return rc;
   if (off[n_reads] == 0) return NVK_OK;
   if (!out_pos || !out_scores || !out_aggregate) {
     nvk_set_error("nvk_meth_scores_dev: NULL output");
@@ -176,7 +156,7 @@ extern "C" int nvk_meth_scores_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_
   }
   {
     TimerScope ts(ctx, NVK_K_METH);
-    hipLaunchKernelGGL(meth_kernel<true>, dim3(meth_blocks(n_reads)), dim3(NT), 0, ctx->stream, n_reads,
+    hipLaunchKernelGGL(meth_kernel<true>, dim3(grid_of(n_reads, NT / 64)), dim3(NT), 0, ctx->stream, n_reads,
                        reference, ref_off, means, expected, status, pattern, pattern_len, (int64_t *)nullptr,
                        occ_off, out_pos, out_scores, out_aggregate);
   }

@@ -10,30 +10,11 @@
 #include <math.h>
 
 #include "nvk_internal.h"
+#include "kmer.h"
 #include "lane3.h"
+#include "wave.h"
 
 namespace {
-
-__device__ __forceinline__ int seq_at(const int32_t *ref, int R, const int32_t *cb, int nb,
-                                      const int32_t *ca, int na, int idx) {
-  // ExtendedSequence::operator[] : context_before | reference | context_after, 0 outside
-  if (idx < 0) {
-    int j = idx + nb;
-    return j >= 0 ? cb[j] : 0;
-  }
-  if (idx < R) return ref[idx];
-  int j = idx - R;
-  return j < na ? ca[j] : 0;
-}
-
-__device__ __forceinline__ int64_t kmer_id(const DeviceModel &dm, const int32_t *ref, int R,
-                                           const int32_t *cb, int nb, const int32_t *ca, int na,
-                                           int pos) {
-  int64_t id = 0;
-  for (int j = pos - dm.central; j < pos - dm.central + dm.k; j++)
-    id = id * dm.alphabet + seq_at(ref, R, cb, nb, ca, na, j);
-  return id;
-}
 
 // What the reference leaves undefined and the C-ABI must refuse (sanitizers): a read whose
 // slices leave the batch's arrays, an anchor outside the band rows, a base code that would index the
@@ -66,29 +47,6 @@ __device__ __forceinline__ int read_is_bad(const DeviceModel &dm, const BatchArg
   for (int j = tid; j < na && !bad; j += nthreads)
     if ((unsigned)ca[j] >= alpha) bad = 1;
   return bad;
-}
-
-__device__ __forceinline__ int wave_scan_max(int v, int lane) {
-  for (int d = 1; d < 64; d <<= 1) {
-    int o = __shfl_up(v, d, 64);
-    if (lane >= d) v = max(v, o);
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_scan_min_rev(int v, int lane) {
-  for (int d = 1; d < 64; d <<= 1) {
-    int o = __shfl_down(v, d, 64);
-    if (lane + d < 64) v = min(v, o);
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-  for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-  return v;
-}
-__device__ __forceinline__ long long wave_sum(long long v) {
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
 }
 
 // bands of the R+1 boundary rows (dtw.cpp:7-35): "later anchor overwrites", then
@@ -354,12 +312,7 @@ __global__ __launch_bounds__(PLAN_T) void plan_kernel(DeviceModel dm, BatchArgs 
       int carry = 0;
       for (int b0 = 0; b0 < T; b0 += 64) {
         const int r = b0 + lane;
-        int v = r < T ? sh_S[r] : 0;
-        for (int d = 1; d < 64; d <<= 1) {
-          const int o = __shfl_up(v, d, 64);
-          if (lane >= d) v += o;
-        }
-        v += carry;
+        const int v = wave_scan_add(r < T ? sh_S[r] : 0, lane) + carry;
         if (r < T) sh_S[r] = v;
         carry = __shfl(v, 63, 64);
       }
@@ -381,11 +334,7 @@ __global__ __launch_bounds__(PLAN_T) void plan_kernel(DeviceModel dm, BatchArgs 
           const int cur = r < T ? sh_x[r] : NEG;
           int v = cur;
           if (r < T && r >= 64) v = max(v, sh_x[r - 64] + sh_k[r]);
-          for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(v, d, 64);
-            if (lane >= d) v = max(v, o);
-          }
-          v = max(v, carry);
+          v = max(wave_scan_max(v, lane), carry);
           if (r < T) {
             changed |= (v != cur);
             sh_x[r] = v;
@@ -398,11 +347,7 @@ __global__ __launch_bounds__(PLAN_T) void plan_kernel(DeviceModel dm, BatchArgs 
           const int cur = r < T ? sh_x[r] : 0;
           const int U = r < T ? c * r - sh_S[r] : 0;  // off[r] - c*r = x[r] - U[r]
           int z = r < T ? cur - U : NEG;
-          for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_down(z, d, 64);
-            if (lane + d < 64) z = max(z, o);
-          }
-          z = max(z, carryz);
+          z = max(-wave_scan_min_rev(-z, lane), carryz);  // (the maximum of lanes l .. 63)
           if (r < T) {
             const int nx = z + U;
             changed |= (nx != cur);
@@ -460,13 +405,6 @@ __global__ __launch_bounds__(PLAN_T) void plan_kernel(DeviceModel dm, BatchArgs 
 // planner for estimate_log_likelihoods (dtw.cpp:37-131): bands, row-store offsets and the fused
 // per-position descriptors of the prefix sweep and of the (mirrored) suffix sweep.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void gauss_params(const DeviceModel &dm, int64_t id, double *mean,
-                                             double *ac, double *mc) {
-  *mean = dm.mean[id];
-  *ac = dm.ac[id];
-  *mc = dm.mc[id];
-}
-
 __global__ __launch_bounds__(64) void plan_ell_kernel(DeviceModel dm, BatchArgs a, int wobbling,
                                                       EllPlan pl, unsigned long long *bandtmp,
                                                       PlanTotals *totals) {
@@ -529,11 +467,7 @@ __global__ __launch_bounds__(64) void plan_ell_kernel(DeviceModel dm, BatchArgs 
       }
     }
     // exclusive prefix sum of the row widths
-    int inc = w;
-    for (int d = 1; d < 64; d <<= 1) {
-      int o = __shfl_up(inc, d, 64);
-      if (lane >= d) inc += o;
-    }
+    const int inc = wave_scan_add(w, lane);
     if (r <= R) rowoff[r] = carry + inc - w;
     carry += __shfl(inc, 63, 64);
   }
@@ -545,30 +479,30 @@ __global__ __launch_bounds__(64) void plan_ell_kernel(DeviceModel dm, BatchArgs 
   for (int j = lane; j < R; j += 64) {
     FusedParam f;
     f.has_wob = (j > 0 && wobbling) ? 1 : 0;
-    f.a_mean = f.a_ac = f.a_mc = 0.0;
-    if (f.has_wob) gauss_params(dm, kmer_id(dm, ref, R, cb, nb, ca, na, j - 1), &f.a_mean, &f.a_ac, &f.a_mc);
-    gauss_params(dm, kmer_id(dm, ref, R, cb, nb, ca, na, j), &f.b_mean, &f.b_ac, &f.b_mc);
+    int64_t id = kmer_id(dm, ref, R, cb, nb, ca, na, j);
+    f.b_mean = dm.mean[id];
+    f.b_ac = dm.ac[id];
+    f.b_mc = dm.mc[id];
     f.wbs = bs[j];
     f.wbe = be[j];
     f.ebs = bs[j + 1];
     f.ebe = be[j + 1];
     f.store_off = rowoff[j + 1];
-    f.pad0 = f.pad1 = 0;
     fw[j] = f;
     // suffix sweep, lane jj handles boundary i = R - jj: input suffix[i] (band i), wobble with the
     // mixture of k-mers (i, i-1), emit with k-mer i-1 into suffix[i-1] (band i-1); mirrored i' = N - i
     const int jj = j, i = R - jj;
     FusedParam g;
     g.has_wob = (i < R && wobbling) ? 1 : 0;
-    g.a_mean = g.a_ac = g.a_mc = 0.0;
-    if (g.has_wob) gauss_params(dm, kmer_id(dm, ref, R, cb, nb, ca, na, i), &g.a_mean, &g.a_ac, &g.a_mc);
-    gauss_params(dm, kmer_id(dm, ref, R, cb, nb, ca, na, i - 1), &g.b_mean, &g.b_ac, &g.b_mc);
+    id = kmer_id(dm, ref, R, cb, nb, ca, na, i - 1);
+    g.b_mean = dm.mean[id];
+    g.b_ac = dm.ac[id];
+    g.b_mc = dm.mc[id];
     g.wbs = N - be[i];
     g.wbe = N - bs[i];
     g.ebs = N - be[i - 1];
     g.ebe = N - bs[i - 1];
     g.store_off = rowoff[i - 1];
-    g.pad0 = g.pad1 = 0;
     rv[jj] = g;
   }
   __syncthreads();
@@ -602,26 +536,18 @@ __global__ void expected_kernel(DeviceModel dm, int64_t n_reads, int64_t total_r
                                 const int32_t *reference, const int64_t *ref_off,
                                 const int32_t *cbs, const int64_t *cb_off, const int32_t *cas,
                                 const int64_t *ca_off, double *out) {
-  // one thread per base; the read is found by binary search over ref_off
+  // one thread per base
   int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= total_ref) return;
-  int64_t lo = 0, hi = n_reads;  // ref_off[lo] <= g < ref_off[hi]
-  while (hi - lo > 1) {
-    int64_t mid = (lo + hi) >> 1;
-    if (ref_off[mid] <= g) lo = mid; else hi = mid;
-  }
-  int64_t rd = lo;
+  const int64_t rd = owner_of(ref_off, n_reads, g);
   int R = (int)(ref_off[rd + 1] - ref_off[rd]);
   int nb = (int)(cb_off[rd + 1] - cb_off[rd]);
   int na = (int)(ca_off[rd + 1] - ca_off[rd]);
   int pos = (int)(g - ref_off[rd]);
-  // a base code outside 0..alphabet-1 anywhere in the k-mer's window: no table entry exists (the reference
-  // indexes out of bounds there, kmer_model.cpp:22-30); the level is reported as NaN
+  // a base code outside the alphabet in the k-mer's window (kmer.h): the level is reported as NaN
   const int32_t *ref = reference + ref_off[rd], *cb = cbs + cb_off[rd], *ca = cas + ca_off[rd];
-  bool ok = true;
-  for (int j = pos - dm.central; j < pos - dm.central + dm.k; j++)
-    ok = ok && ((unsigned)seq_at(ref, R, cb, nb, ca, na, j) < (unsigned)dm.alphabet);
-  out[g] = ok ? dm.mean[kmer_id(dm, ref, R, cb, nb, ca, na, pos)] : (double)NAN;
+  const int64_t id = kmer_id_checked(dm, ref, R, cb, nb, ca, na, pos);
+  out[g] = id >= 0 ? dm.mean[id] : (double)NAN;
 }
 
 
@@ -650,11 +576,7 @@ __global__ void order_count_kernel(const ReadMeta *metas, int n, const PlanTotal
 }
 __global__ void order_scan_kernel(int *cnt) {  // one wave, two buckets per lane: cnt[b] -> first position of bucket b; cnt[ORD_N+b] = 0
   int lane = threadIdx.x;
-  int v0 = cnt[2 * lane], v1 = cnt[2 * lane + 1], s = v0 + v1;
-  for (int d = 1; d < 64; d <<= 1) {
-    int o = __shfl_up(s, d, 64);
-    if (lane >= d) s += o;
-  }
+  const int v0 = cnt[2 * lane], v1 = cnt[2 * lane + 1], s = wave_scan_add(v0 + v1, lane);
   cnt[2 * lane] = s - v0 - v1;
   cnt[2 * lane + 1] = s - v1;
   cnt[ORD_N + 2 * lane] = 0;
@@ -682,12 +604,7 @@ __global__ void count_flags_kernel(const int32_t *flags, int64_t n, int32_t *out
   const int f = (g < n) ? flags[g] : 0;
   // (three counts of at most 2^20 each would fit one word; kept apart for n up to 2^31)
   int v = ((f & 7) != 0) ? 1 : 0, v0 = f & 1, v1 = (f >> 1) & 1, v2 = (f >> 2) & 1;  // (bit 3, the plateau mark, is not a tie class)
-  for (int d = 32; d >= 1; d >>= 1) {
-    v += __shfl_xor(v, d, 64);
-    v0 += __shfl_xor(v0, d, 64);
-    v1 += __shfl_xor(v1, d, 64);
-    v2 += __shfl_xor(v2, d, 64);
-  }
+  v = wave_sum(v), v0 = wave_sum(v0), v1 = wave_sum(v1), v2 = wave_sum(v2);
   if ((threadIdx.x & 63) == 0 && v) {
     atomicAdd(out, v);
     if (v0) atomicAdd(out + 1, v0);
@@ -729,10 +646,9 @@ int launch_order(nvk_ctx *ctx, const ReadMeta *metas, int64_t n_reads, const Pla
   return NVK_OK;
 }
 
-int launch_plan(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int mode, int wobbling,
+int launch_plan(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int mode,
                 ReadMeta *metas, RowParam *rows, unsigned long long *bandtmp, PlanTotals *totals,
                 void *lane_f, void *lane_r, int32_t *lane_offs) {
-  (void)wobbling;
   NVK_HIP(hipMemsetAsync(totals, 0, sizeof(PlanTotals), ctx->stream));
   if (a.n_reads == 0) return NVK_OK;
   {

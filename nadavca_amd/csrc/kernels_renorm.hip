@@ -10,13 +10,14 @@
 // All three are byte/HBM-bound passes over the signal (8 B per sample) — no MFMA, no LDS tiling.
 // Exactness: the medians are exact selections (radix select on the order-preserving integer image of
 // the doubles); the event means follow numpy's pairwise summation order for contiguous float64 data
-// (8 accumulators up to 128 elements, halving above, pieces of 8192), so they equal numpy.mean bit for
+// (npsum.h: 8 accumulators up to 128 elements, halving above, pieces of 8192), so they equal numpy.mean bit for
 // bit; the regression sums are taken in numpy's order for the two means and in index order for the centred
 // products (numpy hands those to BLAS, whose order is not specified): slope and intercept agree with
 // scipy to a few ulp, not bitwise.
 #include <math.h>
 
 #include "nvk_internal.h"
+#include "npsum.h"
 
 namespace {
 
@@ -213,81 +214,13 @@ __global__ __launch_bounds__(NT) void shard_clip_kernel(const double *x, int64_t
   }
 }
 
-// ---- numpy's pairwise summation (numpy/_core/src/umath/loops_utils.h.src, @TYPE@_pairwise_sum) ------
-__device__ double np_block_sum(const double *a, int64_t n) {  // n <= 128
-  if (n < 8) {
-    double res = 0.0;
-    for (int64_t i = 0; i < n; i++) res += a[i];
-    return res;
-  }
-  double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
-  int64_t i = 8;
-  for (; i < n - (n % 8); i += 8) {
-    r0 += a[i + 0]; r1 += a[i + 1]; r2 += a[i + 2]; r3 += a[i + 3];
-    r4 += a[i + 4]; r5 += a[i + 5]; r6 += a[i + 6]; r7 += a[i + 7];
-  }
-  double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-  for (; i < n; i++) res += a[i];
-  return res;
-}
-// the recursion  sum(a, n) = sum(a, n2) + sum(a + n2, n - n2),  n2 = n/2 rounded down to a multiple
-// of 8, without a call stack: post-order walk with an explicit stack of (offset, length, state);
-// n <= 8192 (np_sum below), so the walk is at most 7 levels deep
-__device__ double np_pairwise_sum(const double *a, int64_t n) {
-  if (n <= 128) return np_block_sum(a, n);
-  int so[12], sn[12];
-  double sv[12];
-  int st[12];
-  int top = 0;
-  so[0] = 0; sn[0] = (int)n; st[0] = 0; sv[0] = 0.0;
-  double ret = 0.0;
-  while (top >= 0) {
-    const int o = so[top], m = sn[top];
-    if (m <= 128) {
-      ret = np_block_sum(a + o, m);
-      top--;
-      continue;
-    }
-    int n2 = m / 2;
-    n2 -= n2 % 8;
-    if (st[top] == 0) {  // descend into the left half
-      st[top] = 1;
-      top++;
-      so[top] = o; sn[top] = n2; st[top] = 0;
-    } else if (st[top] == 1) {  // left half done: keep it, descend into the right half
-      sv[top] = ret;
-      st[top] = 2;
-      top++;
-      so[top] = o + n2; sn[top] = m - n2; st[top] = 0;
-    } else {
-      ret = sv[top] + ret;
-      top--;
-    }
-  }
-  return ret;
-}
-
-// numpy.add.reduce of a contiguous float64 vector: the reduction loop receives the data in pieces of
-// 8192 elements (numpy's buffer size), each summed pairwise and added to the running result, which
-// starts at 0 (tests/test_renorm_cpu.py checks this restatement against numpy itself)
-__device__ double np_sum(const double *a, int64_t n) {
-  double res = 0.0;
-  for (int64_t o = 0; o < n; o += 8192) res = res + np_pairwise_sum(a + o, (n - o < 8192) ? n - o : 8192);
-  return res;
-}
-
 // one thread per event (base): mean of signal[start:end] of the read's slice
 __global__ void event_means_kernel(int64_t n_reads, int64_t total_ref, const double *signal,
                                    const int64_t *sig_off, const int32_t *events, const int64_t *ref_off,
                                    const int32_t *status, double *out) {
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= total_ref) return;
-  int64_t lo = 0, hi = n_reads;  // ref_off[lo] <= g < ref_off[hi]
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (ref_off[mid] <= g) lo = mid; else hi = mid;
-  }
-  const int64_t rd = lo;
+  const int64_t rd = owner_of(ref_off, n_reads, g);
   double m = nan("");
   if (!status || status[rd] == 0) {
     const int64_t N = sig_off[rd + 1] - sig_off[rd];
@@ -415,7 +348,7 @@ extern "C" int nvk_splev_groups_dev(nvk_ctx *ctx, int64_t n_groups, const double
   NVK_HIP(hipSetDevice(ctx->device));
   {
     TimerScope ts(ctx, NVK_K_RENORM);
-    const unsigned blocks = (unsigned)(n_groups < 65535 * 16 ? n_groups : 65535 * 16);
+    const unsigned blocks = grid_of(n_groups, 1);
     hipLaunchKernelGGL(splev_groups_kernel, dim3(blocks), dim3(NT), 0, ctx->stream, n_groups, x, grp_off, t, c,
                        knot_off, k, out);
   }
@@ -471,7 +404,7 @@ extern "C" int nvk_normalize_groups_dev(nvk_ctx *ctx, int64_t n_groups, const do
   }
   {
     TimerScope ts(ctx, NVK_K_RENORM);
-    const unsigned blocks = (unsigned)(n_groups < 65535 * 16 ? n_groups : 65535 * 16);
+    const unsigned blocks = grid_of(n_groups, 1);
     hipLaunchKernelGGL(normalize_groups_kernel, dim3(blocks), dim3(NT), 0, ctx->stream, n_groups, raw,
                        grp_off, out, centre_scale);
   }
@@ -562,7 +495,7 @@ extern "C" int nvk_linfit_rescale_dev(nvk_ctx *ctx, int64_t n_reads, const doubl
     TimerScope ts(ctx, NVK_K_RENORM);
     hipLaunchKernelGGL(linfit_kernel, dim3((unsigned)((n_reads + 63) / 64)), dim3(64), 0, ctx->stream, n_reads,
                        expected, means, ref_off, status, out_fit);
-    const unsigned blocks = (unsigned)(n_reads < 65535 * 16 ? n_reads : 65535 * 16);
+    const unsigned blocks = grid_of(n_reads, 1);
     hipLaunchKernelGGL(rescale_kernel, dim3(blocks), dim3(NT), 0, ctx->stream, n_reads, (const double *)out_fit,
                        ref_off, status, signal, sig_off);
   }

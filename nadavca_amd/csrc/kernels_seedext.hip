@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "nvk_internal.h"
+#include "wave.h"
 
 namespace {
 
@@ -48,8 +49,6 @@ struct SeedArgs {
   int *counter;
   const int32_t *ref_lo, *ref_hi;  // seedext_kernel<true>: per read, the range of its cells' j on its strand
 };
-
-__device__ __forceinline__ int dpp_ror1(int v) { return __builtin_amdgcn_mov_dpp(v, 0x13C, 0xf, 0xf, false); }
 
 // a base code outside 0..3 never equals anything: -2 in the read, -1 in the reference
 __device__ __forceinline__ int query_code(const int32_t *q, int64_t x) {
@@ -256,16 +255,9 @@ static int seed_extend(const char *what, bool bounded, nvk_ctx *ctx, int64_t n_r
     return NVK_ERR_INVALID;
   }
   NVK_HIP(hipSetDevice(ctx->device));
-  std::vector<int64_t> off((size_t)n_reads + 1);
-  NVK_HIP(hipMemcpyAsync(off.data(), q_off, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  int rc = check_offsets("query", off.data(), n_reads);
+  std::vector<int64_t> off;
+  int rc = nvk_fetch_offsets(ctx, "query", q_off, n_reads, off, "total_query", total_query);
   if (rc) return rc;
-  if (off[n_reads] != total_query) {
-    nvk_set_error("%s: query offsets end at %lld, total_query is %lld", what, (long long)off[n_reads],
-                  (long long)total_query);
-    return NVK_ERR_INVALID;
-  }
   for (int64_t r = 0; r < n_reads; r++)
     if (off[r + 1] - off[r] > SEED_MAX_READ) {
       nvk_set_error("%s: read %lld has %lld bases, above %d", what, (long long)r, (long long)(off[r + 1] - off[r]),

@@ -1,0 +1,51 @@
+// The k-mer id of a position of a read: the one restatement of the reference's extended-sequence lookup
+// (nadavca/dtw/sequence.cpp:6-38) and of KmerModel's index (kmer_model.cpp:22-30) that every kernel uses.
+// Of `dm` only the window's shape is read: k, central, alphabet.
+#pragma once
+#include "nvk_internal.h"
+
+// ExtendedSequence::operator[] : context_before | reference | context_after, 0 outside
+__device__ __forceinline__ int seq_at(const int32_t *ref, int R, const int32_t *cb, int nb,
+                                      const int32_t *ca, int na, int idx) {
+  if (idx < 0) {
+    int j = idx + nb;
+    return j >= 0 ? cb[j] : 0;
+  }
+  if (idx < R) return ref[idx];
+  int j = idx - R;
+  return j < na ? ca[j] : 0;
+}
+
+// k-mer id of position pos; where sub(j, v) is true, v replaces the base at position j of the window (a hypothesis'
+// substitutions, sequence.cpp:31-38)
+template <class Sub>
+__device__ __forceinline__ int64_t kmer_id(const DeviceModel &dm, const int32_t *ref, int R,
+                                           const int32_t *cb, int nb, const int32_t *ca, int na,
+                                           int pos, const Sub &sub) {
+  int64_t id = 0;
+  for (int j = pos - dm.central; j < pos - dm.central + dm.k; j++) {
+    int v;
+    if (!sub(j, v)) v = seq_at(ref, R, cb, nb, ca, na, j);
+    id = id * dm.alphabet + v;
+  }
+  return id;
+}
+__device__ __forceinline__ int64_t kmer_id(const DeviceModel &dm, const int32_t *ref, int R,
+                                           const int32_t *cb, int nb, const int32_t *ca, int na,
+                                           int pos) {
+  return kmer_id(dm, ref, R, cb, nb, ca, na, pos, [](int, int &) { return false; });
+}
+
+// kmer_id, or -1 when a base code anywhere in the window is outside 0 .. alphabet-1: no table entry exists (the
+// reference indexes out of bounds there)
+__device__ __forceinline__ int64_t kmer_id_checked(const DeviceModel &dm, const int32_t *ref, int R,
+                                                   const int32_t *cb, int nb, const int32_t *ca, int na,
+                                                   int pos) {
+  int64_t id = 0;
+  for (int j = pos - dm.central; j < pos - dm.central + dm.k; j++) {
+    const int b = seq_at(ref, R, cb, nb, ca, na, j);
+    if ((unsigned)b >= (unsigned)dm.alphabet) return -1;
+    id = id * dm.alphabet + b;
+  }
+  return id;
+}

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/nadavca_hip.h"
 
 // ----- device-side tables ---------------------------------------------------------------
@@ -25,15 +27,13 @@ static_assert(sizeof(RowParam) == 48, "RowParam layout");
 // dtw.cpp:53-59 / 70-76) on band "w", then the emitting row (Gaussian, dtw.cpp:60-63 / 77-80)
 // on band "e".  Coordinates are those of the sweep (mirrored for the suffix sweep).
 struct __attribute__((aligned(16))) FusedParam {
-  double a_mean, a_ac, a_mc;  // the mixture's other component
-  double b_mean, b_ac, b_mc;  // the emitting Gaussian (also a mixture component)
+  double b_mean, b_ac, b_mc;  // the emitting Gaussian; the mixture's other component is the left neighbour's
   int32_t wbs, wbe;           // band of the wobble row == band of the predecessor row
   int32_t ebs, ebe;           // band of the emitting row
   int32_t has_wob;            // 0: no wobble row, the predecessor feeds the emitting row directly
   int32_t store_off;          // first cell of the emitting row in the slot's row store
-  int32_t pad0, pad1;
 };
-static_assert(sizeof(FusedParam) == 80, "FusedParam layout");
+static_assert(sizeof(FusedParam) == 48, "FusedParam layout");
 
 struct ReadMeta {
   int64_t sig_off;   // first sample of the read's signal slice
@@ -164,9 +164,33 @@ struct NvkTmp {
   }
 };
 
+// the planner's totals on the device: in ws[WS_MISC] (at least 256 bytes once reserved), behind the launchers'
+// 64 bytes of counters
+inline PlanTotals *nvk_plan_totals(nvk_ctx *ctx) { return (PlanTotals *)((char *)ctx->ws[WS_MISC] + 64); }
+
+// blocks for `items` work items at per_block each, clamped to a grid the grid-stride kernels cover any size with
+inline unsigned grid_of(int64_t items, int64_t per_block) {
+  const int64_t want = (items + per_block - 1) / per_block;
+  return (unsigned)(want < 65535 * 16 ? want : 65535 * 16);
+}
+
+// the read that owns flat position g: the rd with off[rd] <= g < off[rd + 1], by binary search over off[0..n]
+__device__ __forceinline__ int64_t owner_of(const int64_t *off, int64_t n, int64_t g) {
+  int64_t lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (off[mid] <= g) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 // ----- argument checks (api.hip) -------------------------------------------------------------
 // off[0..n]: not NULL, starts at 0, never decreases
 int check_offsets(const char *what, const int64_t *off, int64_t n);
+// off[0..n] on the DEVICE: copied to h_off over ctx->stream (which is waited for) and checked there with
+// check_offsets; with total_name, the offsets must also end at `total`, the argument of that name
+int nvk_fetch_offsets(nvk_ctx *ctx, const char *what, const int64_t *off, int64_t n, std::vector<int64_t> &h_off,
+                      const char *total_name = nullptr, int64_t total = 0);
 // the model handle and the ranges of n_reads, bandwidth and min_event_length
 int check_common(nvk_model *model, int64_t n_reads, int bandwidth, int mel);
 
@@ -186,11 +210,11 @@ struct BatchArgs {
   int bandwidth, mel;
 };
 
-enum { PLAN_ALIGN_TRANS = 0, PLAN_ALIGN_PLAIN = 1, PLAN_ELL = 2 };
+enum { PLAN_ALIGN_TRANS = 0, PLAN_ALIGN_PLAIN = 1 };
 
 // lane_f / lane_r / lane_offs: where the planner leaves the per-sweep lane records of kernels_align3.hip (lane3.h),
 // or null
-int launch_plan(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int mode, int wobbling,
+int launch_plan(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int mode,
                 ReadMeta *metas, RowParam *rows, unsigned long long *bandtmp, PlanTotals *totals,
                 void *lane_f, void *lane_r, int32_t *lane_offs);
 // order[0..n) = read indices in launch order (class-major, longest first; ctx->ws[WS_ORDER]); tot_dev: the planner's

@@ -384,6 +384,79 @@ def test_decreasing_offsets_are_refused(dtw, entry, which):
         call()
 
 
+@pytest.mark.parametrize('entry,which,has_total', [
+    ('nvk_meth_count_dev', 'ref_off', True), ('nvk_meth_scores_dev', 'occ_off', False),
+    ('nvk_kmer_event_stats_dev', 'ref_off', True), ('nvk_kmer_event_stats_dev', 'sig_off', False),
+    ('nvk_kmer_event_stats_dev', 'cb_off', False), ('nvk_kmer_event_stats_dev', 'ca_off', False),
+    ('nvk_seed_extend_dev', 'q_off', True), ('nvk_estimate_hypotheses_batch_dev', 'hyp_off', True),
+    ('nvk_estimate_joint_hypotheses_batch_dev', 'sub_off', True)])
+def test_device_offsets_are_refused(dtw, entry, which, has_total):
+    """Every device-pointer entry point that walks an offset array copies it to the host and checks it there
+    (csrc/api.hip: nvk_fetch_offsets) before any launch: offsets that decrease, or that end elsewhere than at the
+    stated total, are NVK_ERR_INVALID."""
+    import ctypes as C
+    import torch
+    from nadavca_amd import synthetic, _lib
+    from nadavca_amd.device import DeviceBatch, estimate_hypotheses_dev, estimate_joint_hypotheses_dev
+    lib = _lib.load()
+    model = synthetic.load_model_arrays()
+    m = dtw.KmerModel(*model)
+    ctx = m.context.handle
+    dev = torch.device('cuda', m.context.device)
+    db = DeviceBatch(synthetic.make_batch(4, model, seed=914, R=120, R_spread=10, bandwidth=60), dev)
+    n, tr = db.n, db.total_ref
+    Z = lambda count, dt: torch.zeros(count, dtype=dt, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    i32, i64, f64 = torch.int32, torch.int64, torch.float64
+    # (the good calls do no work to speak of: a pattern that occurs nowhere, empty events, reads without a seed)
+    means, no_cpg, pat = Z(tr, f64), Z(tr, i32), torch.tensor([1, 2], dtype=i32, device=dev)
+    events, no_seed, genome = Z(2 * tr, i32), Z(n, i32) - 1, Z(100, i32)
+    hyp_off = torch.tensor([0, 2, 4, 6, 8], dtype=i64, device=dev)
+    out_i32, out_i64, out_f64, out2_i64 = Z(2 * tr + 4 * n, i32), Z(tr, i64), Z(tr, f64), Z(tr, i64)
+    torch.cuda.synchronize(dev)
+
+    def raising(fn):  # the Python wrappers turn NVK_ERR_INVALID into ValueError (_lib.check)
+        try:
+            fn()
+        except ValueError:
+            return _lib.NVK_ERR_INVALID
+        return _lib.NVK_OK
+
+    def kmer(**offs):
+        o = dict(sig_off=db.sig_off, ref_off=db.ref_off, cb_off=db.cb_off, ca_off=db.ca_off)
+        o.update(offs)
+        return lib.nvk_kmer_event_stats_dev(
+            ctx, n, tr, p(db.signal), p(o['sig_off']), p(events), p(o['ref_off']), p(db.reference),
+            p(db.context_before), p(o['cb_off']), p(db.context_after), p(o['ca_off']), p(None), 6, 2, 4, 0, p(None),
+            p(out_i64), p(out_f64), p(out2_i64))
+
+    good, call = {
+        'nvk_meth_count_dev': (db.ref_off, lambda off: lib.nvk_meth_count_dev(
+            ctx, n, tr, p(no_cpg), p(off), p(means), p(None), p(pat), 2, p(out_i64))),
+        'nvk_meth_scores_dev': (hyp_off, lambda off: lib.nvk_meth_scores_dev(
+            ctx, n, tr, p(no_cpg), p(db.ref_off), p(means), p(means), p(None), p(pat), 2, p(off), p(out_i64),
+            p(out_f64), p(out2_i64))),
+        'nvk_kmer_event_stats_dev': (getattr(db, which, None), lambda off: kmer(**{which: off})),
+        'nvk_seed_extend_dev': (db.ref_off, lambda off: lib.nvk_seed_extend_dev(
+            ctx, n, tr, p(db.reference), p(off), p(genome), 100, p(no_seed), p(events), 8, 1, 1, 1, 1, 30,
+            p(out_i32), p(out_i32[4 * n:]))),
+        'nvk_estimate_hypotheses_batch_dev': (hyp_off, lambda off: raising(lambda: estimate_hypotheses_dev(
+            db, 60, 2, m, True, off, Z(8, i32), Z(8, i32)))),
+        'nvk_estimate_joint_hypotheses_batch_dev': (torch.arange(0, 18, 2), lambda off: raising(
+            lambda: estimate_joint_hypotheses_dev(db, 60, 2, m, True, hyp_off, off, torch.arange(16) % 2, Z(16, i32)))),
+    }[entry]
+    good = good.to(device=dev, dtype=i64)
+    decreasing, long_end = good.clone(), good.clone()
+    decreasing[2] = decreasing[3] + 1
+    long_end[-1] += 1
+    torch.cuda.synchronize(dev)
+    assert call(good) == _lib.NVK_OK
+    assert call(decreasing) == _lib.NVK_ERR_INVALID
+    assert b'offsets decrease at read 2' in lib.nvk_last_error()
+    if has_total:
+        assert call(long_end) == _lib.NVK_ERR_INVALID and lib.nvk_last_error()
+
+
 @pytest.mark.parametrize('it,case', [(1630, 2), (2828, 2)])
 def test_tiny_posteriors_at_the_end_of_a_short_wide_band_read(dtw, oracle_port, it, case):
     """tests/dev/fuzz_team.py seed 31415: reads of 85 and 92 bases whose band is wider than the read, min event

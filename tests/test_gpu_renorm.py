@@ -136,6 +136,54 @@ def test_linfit_rescale_matches_linregress(env):
         assert np.array_equal(after[s0:s1], (before[s0:s1] - fit[j, 1]) / fit[j, 0])
 
 
+def _flat(env, signals, ref_lens):
+    """the part of a DeviceBatch that event_means_dev and linfit_rescale_dev read"""
+    from types import SimpleNamespace
+    sig_off = np.concatenate([[0], np.cumsum([len(s) for s in signals])]).astype(np.int64)
+    ref_off = np.concatenate([[0], np.cumsum(ref_lens)]).astype(np.int64)
+    return SimpleNamespace(torch=env['torch'], device=env['dev'], n=len(signals), total_ref=int(ref_off[-1]),
+                           signal=_up(env, np.concatenate(signals), np.float64), sig_off=_up(env, sig_off, np.int64),
+                           ref_off=_up(env, ref_off, np.int64))
+
+
+def test_event_means_across_numpy_pieces(env):
+    """events on both sides of numpy's blocks of 8 and 128 and of its 8192-element pieces (npsum.h)"""
+    from nadavca_amd.device import event_means_dev
+    rng = np.random.default_rng(15)
+    N = 20000
+    sig = rng.normal(0, 3, N) * 10.0 ** rng.integers(-3, 4, N)
+    lengths = np.array([0, 7, 8, 9, 128, 129, 1000, 8192, 8193, 16385])
+    start = rng.integers(0, N - lengths + 1)
+    events = np.stack([start, start + lengths], axis=1)
+    got = event_means_dev(_flat(env, [sig], [len(lengths)]), env['ctx'], _up(env, events, np.int32)).cpu().numpy()
+    assert np.isnan(got[0])
+    for g in range(1, len(lengths)):
+        s, e = events[g]
+        assert got[g] == np.mean(sig[s:e]), lengths[g]
+
+
+def test_linfit_across_numpy_pieces(env):
+    """reads whose two means take numpy's pairwise walk (130 bases) and a second 8192-element piece (8 200)"""
+    from scipy.stats import linregress
+    from nadavca_amd.device import linfit_rescale_dev
+    rng = np.random.default_rng(16)
+    ref_lens = [130, 8200]
+    signals = [rng.normal(0, 1, 300), rng.normal(0, 1, 257)]
+    x = rng.normal(0, 1.2, sum(ref_lens))
+    y = 1.07 * x + 0.13 + rng.normal(0, 0.2, sum(ref_lens))
+    flat = _flat(env, signals, ref_lens)
+    fit = linfit_rescale_dev(flat, env['ctx'], _up(env, x, np.float64), _up(env, y, np.float64)).cpu().numpy()
+    after = flat.signal.cpu().numpy()
+    before = np.concatenate(signals)
+    r0 = s0 = 0
+    for j, (R, sig) in enumerate(zip(ref_lens, signals)):
+        slope, intercept = linregress(x[r0:r0 + R], y[r0:r0 + R])[:2]
+        assert np.isclose(fit[j, 0], slope, rtol=1e-13, atol=0) and np.isclose(fit[j, 1], intercept, rtol=1e-12, atol=1e-15)
+        assert np.array_equal(after[s0:s0 + len(sig)], (before[s0:s0 + len(sig)] - fit[j, 1]) / fit[j, 0])
+        r0 += R
+        s0 += len(sig)
+
+
 def test_renorm_loop_on_device_equals_host_loop(env):
     """align, re-fit, re-align, re-fit on the device vs the same rounds on the host with numpy.mean and
     scipy.stats.linregress (align_signal.py:55-80) around the same alignment kernel."""

@@ -1,6 +1,6 @@
 """CPU checks behind nadavca_amd/csrc/kernels_renorm.hip: the summation order its per-event means
-restate (numpy's pairwise scheme for contiguous float64) really is what ``numpy.mean`` does on this
-numpy, and the median rule (middle element / mean of the two middle ones) is numpy's and
+restate (nadavca_amd/csrc/npsum.h: numpy's pairwise scheme for contiguous float64, also behind the k-mer
+statistics of kernels_kmerstats.hip) really is what ``numpy.mean`` does on this numpy, and the median rule (middle element / mean of the two middle ones) is numpy's and
 ``statistics.median``'s.  The device code itself is compared with numpy in tests/test_gpu_renorm.py."""
 import statistics
 
