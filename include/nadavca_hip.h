@@ -298,6 +298,58 @@ int nvk_estimate_joint_hypotheses_batch_dev(
     const int64_t *sub_off, const int32_t *sub_pos, const int32_t *sub_base, double *out_total,
     double *out_hyp, int32_t *out_status);
 
+/* The same for EDIT hypotheses — insertions and deletions, which no substitution operator can express.  An edit
+ * (p, d, s) of a read with reference ref[0..R) deletes ref[p .. p+d) and puts the i = len(s) letters of s in its
+ * place: ref' = ref[:p] + s + ref[p+d:], of length R' = R - d + i; the contexts stay.  out_hyp[h] is the read's
+ * likelihood under ref': the no-substitution total of EstimateLogLikelihoods (dtw.cpp:83-85) on ref'.
+ * The band of ref' is NOT recomputed from anchors; it is the read's own band (bs, be) through an index map.  Boundary
+ * row r' = 0 .. R' of ref' has the band
+ *     (bs[r'], be[r'])                  for r' < p,
+ *     (bs[p-1], be[p+d])                for p <= r' < p + i (the inserted rows),
+ *     (bs[r'-i+d], be[r'-i+d])          for r' >= p + i,
+ * which is monotone and never empty.  It equals what ComputeBandStarts / ComputeBandEnds (dtw.cpp:7-35) give for ref'
+ * with the anchors behind the edit shifted by i - d whenever no anchor sits on a deleted base (for a pure insertion:
+ * always); where a deleted base carries an anchor, the mapped band is the definition.
+ * With back = k - central - 1 and fwd = central, only the rows first' = max(0, min(p - 1, p - back)) ..
+ * last' = min(R' - 1, p + i - 1 + fwd) of ref' are re-run (k - 1 + i rows in the interior; row p - 1 is taken also when
+ * back = 0, because the band of boundary row p changes), from the stored prefix[first'], every k-mer and band read
+ * through the map, and closed against the stored suffix row last' + 1 - i + d.  The close differs from the
+ * substitution operators': the closing wobble row between last' and last' + 1 lives on band last' + 1, where the prefix
+ * sweep puts it (dtw.cpp:53-58), not on band last' (dtw.cpp:116-123) — the reference has no edit behaviour to
+ * preserve, and closed this way the value is the true total of ref', so out_hyp[h] - out_total[j] is an unbiased
+ * log-likelihood ratio.  The substitution operators keep their quirk.
+ * Same flat batch layout and leading arguments as nvk_estimate_joint_hypotheses_batch_dev, device pointers.
+ *   hyp_off     i64[n+1]          read j owns the hypotheses hyp_off[j] .. hyp_off[j+1] (any order, duplicates
+ *                                 allowed, possibly none)
+ *   edit_pos    i32[total_hyp]    p: 1 <= p, so a base of the read stays in front of the edit
+ *   edit_del    i32[total_hyp]    d: 0 <= d <= 255 (the item code keeps d in 8 bits) and p + d <= R - 1, so a base
+ *                                 stays behind it
+ *   ins_off     i64[total_hyp+1]  hypothesis h inserts the letters ins_off[h] .. ins_off[h+1] of ins_base, possibly
+ *                                 none.  Both offset arrays are copied to the host and checked (start at 0, never
+ *                                 decrease, end at total_hyp / total_ins, at most 2^31 - 1 hypotheses per read; else
+ *                                 NVK_ERR_INVALID)
+ *   ins_base    i32[total_ins]    letters 0 .. alphabet-1 (3 bits of the item code each: NVK_ERR_UNSUPPORTED for a
+ *                                 table of more than 8 letters, as the joint entry); at most 13 per hypothesis
+ *   out_hyp     f64[total_hyp], out_total f64[n], out_status i32[n]: as the listed operator.  (d, i) = (0, 0) gives
+ *                                 the read's total, bit-equal to out_total.  A read gets NVK_READ_BAD_INPUT before
+ *                                 any table is indexed — its outputs left untouched, the rest of the batch completes
+ *                                 — when one of its edits has p < 1, d < 0, d > 255, p + d > R - 1, a letter out of
+ *                                 range or re-runs more than 14 rows (last' - first' + 1 > 14: a hypothesis takes one
+ *                                 DPP row of 16 lanes, two of which are not rows).  NVK_READ_NO_PATH: the values are
+ *                                 the -inf the sweeps give.
+ * Hypotheses of at most 6 rows run 8 per wave step, the others 4 per step (with the packaged 6-mer table a one-base
+ * deletion re-runs 5 rows and a one-base insertion 6: both 8 per step), in one launch after one pair of sweeps per
+ * read.  Compiled limits otherwise as the full entry. */
+int nvk_estimate_edit_hypotheses_batch_dev(
+    nvk_model *model, int64_t n_reads, int64_t total_signal, int64_t total_ref,
+    int64_t total_anchors, const double *signal, const int64_t *sig_off,
+    const int32_t *reference, const int64_t *ref_off, const int32_t *ctx_before,
+    const int64_t *cb_off, const int32_t *ctx_after, const int64_t *ca_off,
+    const int32_t *anchors, const int64_t *anc_off, int bandwidth, int min_event_length,
+    int model_wobbling, int64_t total_hyp, const int64_t *hyp_off, const int32_t *edit_pos,
+    const int32_t *edit_del, int64_t total_ins, const int64_t *ins_off, const int32_t *ins_base,
+    double *out_total, double *out_hyp, int32_t *out_status);
+
 /* replaces the Chunk score accumulation of ProbabilityEstimator
  * (/root/reference/nadavca/estimator.py:45-47,112-119,226-231): for every read j,
  *   ll' = (ll - ll[0][reference[0]]) / normalization_event_length,

@@ -12,6 +12,7 @@ from .seedalign import SeedAligner  # noqa: F401
 from .refset import ReferenceSet  # noqa: F401
 from .kmer_train import estimate_kmer_model  # noqa: F401
 from .call_mods import call_mods_batch  # noqa: F401
+from .call_indels import call_indels_batch  # noqa: F401
 
 __all__ = ['align_signal', 'align_signal_batch', 'estimate_snps', 'estimate_snps_batch', 'dtw', 'SeedAligner',
-           'ReferenceSet', 'estimate_kmer_model', 'call_mods_batch']
+           'ReferenceSet', 'estimate_kmer_model', 'call_mods_batch', 'call_indels_batch']

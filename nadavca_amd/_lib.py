@@ -71,6 +71,8 @@ SIGNATURES = {
                                           + [_vp] * 6),
     'nvk_estimate_joint_hypotheses_batch_dev': (_int, [_vp, _i64, _i64, _i64, _i64] + [_vp] * 10
                                                 + [_int, _int, _int, _i64, _vp, _i64] + [_vp] * 6),
+    'nvk_estimate_edit_hypotheses_batch_dev': (_int, [_vp, _i64, _i64, _i64, _i64] + [_vp] * 10
+                                               + [_int, _int, _int, _i64, _vp, _vp, _vp, _i64] + [_vp] * 5),
     'nvk_consensus_accumulate_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 6 + [_dbl, _i64, _vp, _vp]),
     'nvk_posterior_segments_dev': (_int, [_vp, _i64, _i64, _vp, _int, _int, _dbl, _vp, _vp, _vp]),
     'nvk_normalize_groups_dev': (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),

@@ -730,3 +730,44 @@ extern "C" int nvk_estimate_joint_hypotheses_batch_dev(
   hyp.total_hyp = total_hyp;
   return ell_run(model, a, model_wobbling, nullptr, out_status, &hyp);
 }
+
+extern "C" int nvk_estimate_edit_hypotheses_batch_dev(
+    nvk_model *model, int64_t n_reads, int64_t total_signal, int64_t total_ref,
+    int64_t total_anchors, const double *signal, const int64_t *sig_off, const int32_t *reference,
+    const int64_t *ref_off, const int32_t *ctx_before, const int64_t *cb_off,
+    const int32_t *ctx_after, const int64_t *ca_off, const int32_t *anchors,
+    const int64_t *anc_off, int bandwidth, int min_event_length, int model_wobbling,
+    int64_t total_hyp, const int64_t *hyp_off, const int32_t *edit_pos, const int32_t *edit_del, int64_t total_ins,
+    const int64_t *ins_off, const int32_t *ins_base, double *out_total, double *out_hyp, int32_t *out_status) {
+  BatchArgs a;
+  int rc = dev_batch(model, n_reads, total_signal, total_ref, total_anchors, signal, sig_off, reference, ref_off,
+                     ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
+                     out_status, a);
+  if (rc) return rc;
+  if (total_hyp < 0 || total_ins < 0 || !hyp_off || !ins_off || !out_total ||
+      (total_hyp > 0 && (!edit_pos || !edit_del || !out_hyp)) || (total_ins > 0 && !ins_base)) {
+    nvk_set_error("negative total_hyp / total_ins or NULL hypothesis / insertion / output pointer");
+    return NVK_ERR_INVALID;
+  }
+  if (n_reads == 0) {
+    if (total_hyp != 0 || total_ins != 0) {
+      nvk_set_error("hypothesis offsets end at 0, total_hyp is %lld and total_ins %lld", (long long)total_hyp,
+                    (long long)total_ins);
+      return NVK_ERR_INVALID;
+    }
+    return NVK_OK;
+  }
+  // the kernel walks both levels of the list: both offset arrays are checked here, on host copies
+  nvk_ctx *ctx = model->ctx;
+  std::vector<int64_t> h_off;
+  if ((rc = nvk_fetch_offsets(ctx, "hypothesis", hyp_off, n_reads, h_off, "total_hyp", total_hyp))) return rc;
+  if ((rc = check_hyp_counts(h_off, n_reads))) return rc;
+  if ((rc = nvk_fetch_offsets(ctx, "insertion", ins_off, total_hyp, h_off, "total_ins", total_ins))) return rc;
+  EllHyp hyp{hyp_off, nullptr, nullptr, out_total, out_hyp};
+  hyp.edit_pos = edit_pos;
+  hyp.edit_del = edit_del;
+  hyp.ins_off = ins_off;
+  hyp.ins_base = ins_base;
+  hyp.total_hyp = total_hyp;
+  return ell_run(model, a, model_wobbling, nullptr, out_status, &hyp);
+}

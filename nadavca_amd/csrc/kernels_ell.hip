@@ -14,6 +14,9 @@
 //                      substitutions: the rows first = max(0, p1 - back) .. last = min(R - 1, pm + fwd) of the set's
 //                      first and last substituted position, every k-mer read with all of them applied, closed at
 //                      `last` as a single one is (see "joint items" below)
+//                      — or, in the EDIT variant (nvk_estimate_edit_hypotheses_batch_dev), for listed insertions /
+//                      deletions (p, d, s): the rows around the edit of the EDITED reference, its k-mers, bands and
+//                      closing suffix row read through an index map, closed on band last + 1 (see "edit items" below)
 //
 // Mapping (not the reference's): "fused" lanes.  The reference alternates a wobble row
 // (mixture of the k-mers j-1 and j, min event length 0) with an emitting row (k-mer j).  Both
@@ -118,17 +121,32 @@ struct EllJointArgs : EllListArgs {
   const int32_t *sub_pos, *sub_base;
   int4 *items;
 };
-template <bool LISTED, bool JOINT>
+// The edit variant (nvk_estimate_edit_hypotheses_batch_dev): hypothesis h of the batch deletes edit_del[h] bases from
+// edit_pos[h] on and puts the letters ins_off[h] .. ins_off[h+1] of ins_base in their place; items as the joint variant.
+struct EllEditArgs : EllListArgs {
+  const int32_t *edit_pos, *edit_del;
+  const int64_t *ins_off;
+  const int32_t *ins_base;
+  int4 *items;
+};
+template <bool LISTED, bool JOINT, bool EDIT>
 struct EllArgsOf { typedef EllArgs type; };
 template <>
-struct EllArgsOf<true, false> { typedef EllListArgs type; };
+struct EllArgsOf<true, false, false> { typedef EllListArgs type; };
 template <>
-struct EllArgsOf<true, true> { typedef EllJointArgs type; };
+struct EllArgsOf<true, true, false> { typedef EllJointArgs type; };
+template <>
+struct EllArgsOf<true, true, true> { typedef EllEditArgs type; };
 // joint items: the effective substitutions (b != ref[p]) of a hypothesis as its first position p1 and one nibble per
 // offset from p1 (bit 3: substituted, bits 0-2: the letter) — at most 14 rows are re-run, so the offsets stay below
 // 14 and the alphabet below 8: two registers per lane, with the last offset in the top nibble.  A hypothesis without
 // an effective substitution is 0.
 constexpr int JOINT_ROWS = 14;  // rows a 16-lane group re-runs at most: role 0 and the closing lane take the other two
+// edit items: the hypothesis (p, d, s) with i = len(s) as its position p and a code of one nibble per inserted letter
+// (at most 13: an insertion of i letters re-runs at least i + 1 rows), i in bits 52-55 and d in bits 56-63 (so d <= 255).
+// The edited reference ref' = ref[:p] + s + ref[p+d:] has R' = R - d + i bases; its position / boundary row j comes from
+// j itself before p, from the letters for p <= j < p + i, and from j - i + d behind them.  (d, i) = (0, 0) is code 0.
+constexpr int EDIT_MAX_INS = 13, EDIT_MAX_DEL = 255;
 
 // ---- one fused lane ---------------------------------------------------------------------------
 template <int MEL>
@@ -393,9 +411,10 @@ __device__ void sweep_fast(const FusedParam *desc, int R, int N, int c, const do
   }
 }
 
-template <int MEL, int GL, bool LISTED, bool JOINT = false>
-__global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, JOINT>::type g) {
+template <int MEL, int GL, bool LISTED, bool JOINT = false, bool EDIT = false>
+__global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, JOINT, EDIT>::type g) {
   static_assert(LISTED || !JOINT, "the joint variant is a listed one");
+  static_assert(JOINT || !EDIT, "the edit variant takes its work from items, as the joint one");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double *etab = reinterpret_cast<double *>(smem);
   double *ring = etab + dens::ETN;
@@ -448,7 +467,27 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
         const bool have = q < n_list;
         int p1 = 0, rows = 1;
         unsigned long long code = 0;
-        if (have) {
+        if constexpr (EDIT) {
+          if (have) {
+            // (host-checked offsets: ni >= 0, and the letters read below lie inside ins_base)
+            const int64_t s0 = g.ins_off[h0 + q], ni = g.ins_off[h0 + q + 1] - s0;
+            const int d = g.edit_del[h0 + q];
+            p1 = g.edit_pos[h0 + q];
+            // a base of the read stays on either side: 1 <= p and p + d <= R - 1
+            bad = bad || p1 < 1 || d < 0 || d > EDIT_MAX_DEL || ni > EDIT_MAX_INS || p1 > R - 1 - d;
+            if (!bad) {
+              for (int t = 0; t < (int)ni; t++) {
+                const int sb = g.ins_base[s0 + t];
+                bad = bad || sb < 0 || sb >= alpha;  // (launch_ell refuses an alphabet above 8: a letter fits its nibble)
+                code |= (unsigned long long)(sb & 7) << (4 * t);
+              }
+              code |= (unsigned long long)ni << 52 | (unsigned long long)d << 56;
+              // back = 0: row p - 1 too, the band of its emitting row (boundary row p) changes
+              rows = min(R - d + (int)ni - 1, p1 + (int)ni - 1 + fwd_) - max(0, min(p1 - 1, p1 - back_)) + 1;
+              bad = bad || rows > JOINT_ROWS;
+            }
+          }
+        } else if (have) {
           const int64_t s1 = g.sub_off[h0 + q + 1];
           int prev = -1, plast = 0;
           for (int64_t s = g.sub_off[h0 + q]; s < s1; s++) {
@@ -587,15 +626,23 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
       int p = 0, b = 0, first = 0, last = 0, npos = 0;
       [[maybe_unused]] int hidx = 0;
       [[maybe_unused]] unsigned long long code = 0;
+      [[maybe_unused]] int ed_i = 0, ed_d = 0;  // EDIT: inserted letters, deleted bases
       if constexpr (JOINT) {
         if (valid) {
           const int4 it = g.items[h0 + item];
           p = it.x;
           hidx = it.y;
           code = ((unsigned long long)(unsigned)it.w << 32) | (unsigned)it.z;
-          const int plast = p + (int)(code >> 60);
-          first = max(0, p - back);
-          last = min(R - 1, plast + fwd);
+          if constexpr (EDIT) {
+            ed_i = (int)(code >> 52) & 15;
+            ed_d = (int)(code >> 56);
+            first = max(0, min(p - 1, p - back));
+            last = min(R - ed_d + ed_i - 1, p + ed_i - 1 + fwd);
+          } else {
+            const int plast = p + (int)(code >> 60);
+            first = max(0, p - back);
+            last = min(R - 1, plast + fwd);
+          }
           npos = last - first + 1;
         }
       } else if (valid) {
@@ -612,9 +659,17 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
         npos = last - first + 1;
       }
       // k-mer id of position `at` under the hypothesis: base p replaced by b, or (joint) the bases at p + o by those
-      // of `code`'s nibbles
+      // of `code`'s nibbles, or (edit) position `at` of the edited reference: its letters at p .. p + ed_i - 1, the
+      // read's bases ed_d - ed_i further on behind them
       auto kid = [&](int at) {
-        if constexpr (JOINT)
+        if constexpr (EDIT)
+          return kmer_id_mapped(dm, ref, R, cb, nb, ca, na, at, [&](int &j, int &v) {
+            const unsigned o = (unsigned)(j - p);
+            v = (int)(code >> (4 * (o & 15))) & 7;
+            if (j >= p) j += ed_d - ed_i;
+            return o < (unsigned)ed_i;
+          });
+        else if constexpr (JOINT)
           return kmer_id(dm, ref, R, cb, nb, ca, na, at, [&](int j, int &v) {
             const unsigned o = (unsigned)(j - p);
             const int nib = o < (unsigned)JOINT_ROWS ? (int)(code >> (4 * o)) & 15 : 0;
@@ -623,6 +678,17 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
           });
         else
           return kmer_id(dm, ref, R, cb, nb, ca, na, at, [&](int j, int &v) { v = b; return j == p; });
+      };
+      // boundary row r of the hypothesis' reference as a row of the read's band arrays (bs / be): itself, except EDIT,
+      // where an inserted row takes its start from the last row before the edit and its end from the first one behind
+      // it, and the rows behind the edit are the read's rows ed_d - ed_i further on
+      auto row_s = [&](int r) {
+        if constexpr (EDIT) return r < p ? r : r < p + ed_i ? p - 1 : r - ed_i + ed_d;
+        else return r;
+      };
+      auto row_e = [&](int r) {
+        if constexpr (EDIT) return r < p ? r : r < p + ed_i ? p + ed_d : r - ed_i + ed_d;
+        else return r;
       };
       const bool is_pos = valid && gl >= 1 && gl <= npos;
       const bool is_fin = valid && gl == npos + 1;
@@ -645,7 +711,18 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
         const int j = first + gl - 1;
         idb = kid(j);
         d.has_wob = (j > 0 && g.wobbling) ? 1 : 0;
-        d.wbs = bs[j]; d.wbe = be[j]; d.ebe = be[j + 1];
+        d.wbs = bs[row_s(j)]; d.wbe = be[row_e(j)]; d.ebe = be[row_e(j + 1)];
+      } else if (is_fin && EDIT) {
+        // closing lane of an edit: no quirk — the wobble row lives on band last + 1, where the prefix sweep puts it
+        // (dtw.cpp:53-58), so the value is the total of the edited reference.  Boundary row last + 1 lies behind the
+        // edit: it is the read's row `close`, whose band it has and whose suffix row closes the hypothesis
+        const int close = last + 1 - ed_i + ed_d;
+        d.has_wob = (close < R && g.wobbling) ? 1 : 0;
+        if (d.has_wob) idb = kid(last + 1);
+        d.wbs = bs[close]; d.wbe = be[close];
+        d.ebe = d.wbe;
+        sbase = (int)g.half + rowoff[close] - bs[close];
+        slo = bs[close]; shi = be[close];
       } else if (is_fin) {
         // closing lane: optional wobble row on band `last` (quirk), predecessor = emitting row of
         // position `last` on band last+1; then the running total against suffix[last+1]
@@ -768,8 +845,10 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
     nvk_set_error("k-mer size %d needs k + 2 = %d lanes per hypothesis, compiled limit is 16", dm.k, dm.k + 2);
     return NVK_ERR_UNSUPPORTED;
   }
-  if (hyp && hyp->sub_off && dm.alphabet > 8) {  // (nvk_model_create builds no such table: the limit of the item code)
-    nvk_set_error("joint hypotheses pack a letter in 3 bits: alphabet %d, compiled limit is 8", dm.alphabet);
+  // (nvk_model_create builds no such table: the limit of the item code)
+  if (hyp && (hyp->sub_off || hyp->ins_off) && dm.alphabet > 8) {
+    nvk_set_error("%s hypotheses pack a letter in 3 bits: alphabet %d, compiled limit is 8",
+                  hyp->sub_off ? "joint" : "edit", dm.alphabet);
     return NVK_ERR_UNSUPPORTED;
   }
   const bool wide_groups = dm.k + 2 > 8;  // 16 lanes per hypothesis instead of 8
@@ -831,10 +910,12 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
   void (*kern)(EllArgs) = nullptr;
   void (*kern_l)(EllListArgs) = nullptr;
   void (*kern_j)(EllJointArgs) = nullptr;
-  const bool joint = hyp && hyp->sub_off;
+  void (*kern_e)(EllEditArgs) = nullptr;
+  const bool joint = hyp && hyp->sub_off, edit = hyp && hyp->ins_off;
 #define ELL_PICK(M)                                                               \
   do {                                                                            \
-    if (joint) kern_j = wide_groups ? ell_kernel<M, 16, true, true> : ell_kernel<M, 8, true, true>; \
+    if (edit) kern_e = wide_groups ? ell_kernel<M, 16, true, true, true> : ell_kernel<M, 8, true, true, true>; \
+    else if (joint) kern_j = wide_groups ? ell_kernel<M, 16, true, true> : ell_kernel<M, 8, true, true>; \
     else if (hyp) kern_l = wide_groups ? ell_kernel<M, 16, true> : ell_kernel<M, 8, true>; \
     else kern = wide_groups ? ell_kernel<M, 16, false> : ell_kernel<M, 8, false>;     \
   } while (0)
@@ -853,20 +934,31 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
     g.out_total = hyp->out_total;
     g.out_hyp = hyp->out_hyp;
   }
-  if (joint) {
+  if (joint || edit) {
     if ((rc = nvk_ws_reserve(ctx, WS_JOINT, (size_t)(hyp->total_hyp + 1) * sizeof(int4)))) return rc;
     g.sub_off = hyp->sub_off;
     g.sub_pos = hyp->sub_pos;
     g.sub_base = hyp->sub_base;
     g.items = (int4 *)ctx->ws[WS_JOINT];
   }
-  const void *kfn = joint ? (const void *)kern_j : hyp ? (const void *)kern_l : (const void *)kern;
+  EllEditArgs ge;
+  if (edit) {
+    static_cast<EllListArgs &>(ge) = g;
+    ge.edit_pos = hyp->edit_pos;
+    ge.edit_del = hyp->edit_del;
+    ge.ins_off = hyp->ins_off;
+    ge.ins_base = hyp->ins_base;
+    ge.items = g.items;
+  }
+  const void *kfn = edit ? (const void *)kern_e : joint ? (const void *)kern_j : hyp ? (const void *)kern_l
+                                                                                     : (const void *)kern;
   if (lds > 64 * 1024) {
     NVK_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
   {
     TimerScope ts(ctx, NVK_K_ELL_HYP);
-    if (joint) hipLaunchKernelGGL(kern_j, dim3((unsigned)slots), dim3(64), lds, ctx->stream, g);
+    if (edit) hipLaunchKernelGGL(kern_e, dim3((unsigned)slots), dim3(64), lds, ctx->stream, ge);
+    else if (joint) hipLaunchKernelGGL(kern_j, dim3((unsigned)slots), dim3(64), lds, ctx->stream, g);
     else if (hyp) hipLaunchKernelGGL(kern_l, dim3((unsigned)slots), dim3(64), lds, ctx->stream, static_cast<const EllListArgs &>(g));
     else hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(64), lds, ctx->stream, static_cast<const EllArgs &>(g));
   }

@@ -36,6 +36,22 @@ __device__ __forceinline__ int64_t kmer_id(const DeviceModel &dm, const int32_t 
   return kmer_id(dm, ref, R, cb, nb, ca, na, pos, [](int, int &) { return false; });
 }
 
+// k-mer id of position pos of an EDITED sequence (an insertion / deletion hypothesis): map(j, v) either gives the
+// letter v at position j of the edited sequence and returns true (an inserted base), or rewrites j to the position of
+// the unedited sequence that base comes from (contexts included: before 0, from R on) and returns false
+template <class Map>
+__device__ __forceinline__ int64_t kmer_id_mapped(const DeviceModel &dm, const int32_t *ref, int R,
+                                                  const int32_t *cb, int nb, const int32_t *ca, int na,
+                                                  int pos, const Map &map) {
+  int64_t id = 0;
+  for (int j = pos - dm.central; j < pos - dm.central + dm.k; j++) {
+    int v, src = j;
+    if (!map(src, v)) v = seq_at(ref, R, cb, nb, ca, na, src);
+    id = id * dm.alphabet + v;
+  }
+  return id;
+}
+
 // kmer_id, or -1 when a base code anywhere in the window is outside 0 .. alphabet-1: no table entry exists (the
 // reference indexes out of bounds there)
 __device__ __forceinline__ int64_t kmer_id_checked(const DeviceModel &dm, const int32_t *ref, int R,

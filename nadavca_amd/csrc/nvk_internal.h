@@ -244,6 +244,11 @@ struct EllHyp {
   const int64_t *sub_off = nullptr;
   const int32_t *sub_pos = nullptr, *sub_base = nullptr;
   int64_t total_hyp = 0;
+  // edit hypotheses (nvk_estimate_edit_hypotheses_batch_dev; pos / base and sub_* are then unused): hypothesis h deletes
+  // edit_del[h] bases from edit_pos[h] on and inserts the letters ins_off[h] .. ins_off[h+1] of ins_base
+  const int32_t *edit_pos = nullptr, *edit_del = nullptr;
+  const int64_t *ins_off = nullptr;
+  const int32_t *ins_base = nullptr;
 };
 // hyp == nullptr: the full matrix into out_ll; else the listed hypotheses into hyp->out_* (out_ll unused)
 int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobbling,

@@ -200,6 +200,42 @@ def estimate_joint_hypotheses_dev(dbatch, bandwidth, min_event_length, kmer_mode
     return total, hyp, status
 
 
+def estimate_edit_hypotheses_dev(dbatch, bandwidth, min_event_length, kmer_model, model_wobbling, hyp_off, edit_pos,
+                                 edit_del, ins_off, ins_base):
+    """``estimate_hypotheses_dev`` for insertions and deletions: read j's hypotheses are ``hyp_off[j] .. hyp_off[j+1]``
+    (int64 (n+1,)); hypothesis h deletes ``edit_del[h]`` bases of the read's reference part from ``edit_pos[h]`` on
+    and puts the letters ``ins_off[h] .. ins_off[h+1]`` (int64 (n_hyp+1,)) of ``ins_base`` in their place (int32) —
+    device tensors.  -> (total f64 (n,), hyp f64 (n_hyp,), status int32 (n,)): ``hyp[h]`` is the read's
+    log-likelihood under the edited part (its rows around the edit re-run with k-mers and bands read through the
+    edit's index map, closed on band last + 1; no deletion and no letter gives ``total``).  A read with an edit that
+    leaves no base in front of it (p < 1) or behind it (p + d > R - 1), a negative d or one above 255, a letter out of
+    range or a re-run of more than 14 rows gets READ_BAD_INPUT (include/nadavca_hip.h:
+    nvk_estimate_edit_hypotheses_batch_dev).  Values of reads with a negative status are NaN."""
+    torch = dbatch.torch
+    lib = _lib.load()
+    dev = dbatch.device
+    hyp_off = hyp_off.to(device=dev, dtype=torch.int64).contiguous()
+    ins_off = ins_off.to(device=dev, dtype=torch.int64).contiguous()
+    edit_pos = edit_pos.to(device=dev, dtype=torch.int32).contiguous()
+    edit_del = edit_del.to(device=dev, dtype=torch.int32).contiguous()
+    ins_base = ins_base.to(device=dev, dtype=torch.int32).contiguous()
+    n_hyp, n_ins = int(edit_pos.numel()), int(ins_base.numel())
+    if int(edit_del.numel()) != n_hyp or int(ins_off.numel()) != n_hyp + 1 or int(hyp_off.numel()) != dbatch.n + 1:
+        raise ValueError('estimate_edit_hypotheses_dev: edit_pos and edit_del go together, hyp_off has one entry per '
+                         'read and one more, ins_off one per hypothesis and one more')
+    total = torch.full((dbatch.n,), float('nan'), dtype=torch.float64, device=dev)
+    hyp = torch.full((n_hyp,), float('nan'), dtype=torch.float64, device=dev)
+    status = torch.zeros(dbatch.n, dtype=torch.int32, device=dev)
+    one = torch.zeros(1, dtype=torch.int32, device=dev)  # (a placeholder: pointers of an empty list are never read)
+    _lib.check(lib.nvk_estimate_edit_hypotheses_batch_dev(
+        kmer_model.handle, dbatch.n, dbatch.total_signal, dbatch.total_ref, dbatch.total_anchors,
+        *dbatch.pointers(), int(bandwidth), int(min_event_length), int(bool(model_wobbling)),
+        n_hyp, _dp(hyp_off), _dp(edit_pos if n_hyp else one), _dp(edit_del if n_hyp else one), n_ins, _dp(ins_off),
+        _dp(ins_base if n_ins else one), _dp(total), _dp(hyp if n_hyp else total), _dp(status)),
+        'nvk_estimate_edit_hypotheses_batch_dev')
+    return total, hyp, status
+
+
 # ---- host steps adjacent to the path, on the device (include/nadavca_hip.h, SURVEY.md §8 f1/f2) --------
 def normalize_groups_dev(context, raw, grp_off, out=None):
     """``Read.normalize_reads`` for groups of samples laid end to end (torch f64 / int64 tensors on the

@@ -13,6 +13,7 @@ Batched surface (what the estimator uses; one launch for many reads):
     estimate_log_likelihoods_batch(reads, ...)
     estimate_hypotheses_batch(reads, hypotheses, ...)   listed substitutions only
     estimate_joint_hypotheses_batch(reads, hypotheses, ...)   listed SETS of substitutions, each scored as a whole
+    estimate_edit_hypotheses_batch(reads, edits, ...)   listed insertions / deletions (p, d, s)
 
 All compute goes through libnadavca_hip.so; nothing here computes on the CPU.
 """
@@ -317,6 +318,45 @@ def estimate_joint_hypotheses_batch(reads, hypotheses, bandwidth, min_event_leng
     total, hyp, status = total.cpu().numpy(), hyp.cpu().numpy(), status.cpu().numpy()
     if on_error == 'raise':
         check_status('estimate_joint_hypotheses', status)
+    out = (total, [hyp[off[j]:off[j + 1]] for j in range(batch.n)])
+    return out + (status,) if return_status else out
+
+
+def estimate_edit_hypotheses_batch(reads, edits, bandwidth, min_event_length, kmer_model, model_wobbling,
+                                   on_error='raise', return_status=False):
+    """``estimate_hypotheses_batch`` for insertions and deletions.  edits: per read a list of ``(p, d, s)``: delete
+    ``reference[p .. p+d)`` and put the letters ``s`` (a sequence of base codes, possibly empty) in its place; any
+    order, duplicates allowed.  -> (total f64 (n,), list of f64 (number of edits,) arrays): entry h of read j is its
+    log-likelihood under the edited reference, the total ``estimate_log_likelihoods`` has for it — with the band of
+    the edited reference mapped from the read's own, not recomputed, and ``(p, 0, ())`` the read's total
+    (nvk_estimate_edit_hypotheses_batch_dev).  An edit without a base of the read on either side (p < 1 or
+    p + d > R - 1), d outside 0 .. 255, a letter out of range or an edit that re-runs more than 14 rows fails its read
+    (READ_BAD_INPUT: ValueError, or with on_error='status' NaN values and, with return_status=True, the status array
+    as a third result)."""
+    import torch
+    from .device import DeviceBatch, estimate_edit_hypotheses_dev
+    batch = reads if isinstance(reads, FlatBatch) else FlatBatch(reads)
+    if len(edits) != batch.n:
+        raise ValueError('estimate_edit_hypotheses_batch: %d edit lists for %d reads' % (len(edits), batch.n))
+    off = _offsets([len(es) for es in edits])
+    if batch.n == 0:
+        out = (np.zeros(0), [])
+        return out + (np.zeros(0, dtype=np.int32),) if return_status else out
+    flat = [e for es in edits for e in es]
+    letters = [np.asarray(s, dtype=np.int64).reshape(-1) for _, _, s in flat]
+    pd = np.array([[p, d] for p, d, _ in flat], dtype=np.int64).reshape(-1, 2)
+    ins = np.concatenate(letters + [np.zeros(0, dtype=np.int64)])
+    for a in (pd, ins):
+        if a.size and (a.min() < -(1 << 31) or a.max() >= (1 << 31)):
+            raise ValueError('estimate_edit_hypotheses_batch: a position, length or letter does not fit 32 bits')
+    dbatch = DeviceBatch(batch, torch.device('cuda', kmer_model.context.device))
+    total, hyp, status = estimate_edit_hypotheses_dev(
+        dbatch, bandwidth, min_event_length, kmer_model, model_wobbling, torch.from_numpy(off),
+        torch.from_numpy(pd[:, 0].astype(np.int32)), torch.from_numpy(pd[:, 1].astype(np.int32)),
+        torch.from_numpy(_offsets([s.size for s in letters])), torch.from_numpy(ins.astype(np.int32)))
+    total, hyp, status = total.cpu().numpy(), hyp.cpu().numpy(), status.cpu().numpy()
+    if on_error == 'raise':
+        check_status('estimate_edit_hypotheses', status)
     out = (total, [hyp[off[j]:off[j + 1]] for j in range(batch.n)])
     return out + (status,) if return_status else out
 

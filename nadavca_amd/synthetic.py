@@ -349,6 +349,20 @@ def make_modified_read_batch(n, model5, seed=0, pattern='CG', mod_offset=0, modi
     return rb, SyntheticBatchAligner(genome, ba), genome, truth
 
 
+def apply_edits(genome_num, edits):
+    """The genome with a list of forward-frame edits applied: each ``(x, d, s)`` deletes ``genome_num[x .. x+d)`` and
+    puts the letters ``s`` in its place.  Positions are those of the ORIGINAL genome; the edits must lie inside it and
+    not overlap (ValueError otherwise).  -> the mutated genome, same dtype."""
+    genome_num = np.asarray(genome_num)
+    out, at = [], 0
+    for x, d, s in sorted((int(x), int(d), list(s)) for x, d, s in edits):
+        if x < at or d < 0 or x + d > genome_num.size:
+            raise ValueError('apply_edits: edit (%d, %d) overlaps the one before it or leaves the genome' % (x, d))
+        out += [genome_num[at:x], np.asarray(s, dtype=genome_num.dtype)]
+        at = x + d
+    return np.concatenate(out + [genome_num[at:]]).astype(genome_num.dtype, copy=False)
+
+
 def make_error_read_batch(n, genome_num, seed=0, length=400, spread=40, substitution_rate=0.0, insertion_rate=0.0,
                           deletion_rate=0.0, random_fraction=0.0, overhang_fraction=0.0, model=None, dwell=(3, 17),
                           noise=0.35):
