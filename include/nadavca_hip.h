@@ -74,7 +74,8 @@ enum {
   NVK_K_METH = 8,        /* pattern occurrences and their scores (detect_meth) */
   NVK_K_SEED = 9,        /* banded local alignment + traceback of the seed aligner (nvk_seed_extend_dev) */
   NVK_K_KMER = 10,       /* per-event and per-k-mer sample statistics of k-mer table training (nvk_kmer_*_dev) */
-  NVK_K_COUNT = 11
+  NVK_K_ALLELE = 11,     /* per-site allele mixtures: rows and the per-position solve (nvk_allele_*_dev) */
+  NVK_K_COUNT = 12
 };
 
 const char *nvk_last_error(void); /* thread-local message of the last failing call */
@@ -556,6 +557,46 @@ int nvk_kmer_event_stats_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, c
                              int64_t *out_len);
 int nvk_kmer_reduce_dev(nvk_ctx *ctx, int64_t n_events, int64_t n_kmers, const int64_t *key, const double *val,
                         const int64_t *len, double *out_sum, int64_t *out_samples, int64_t *out_events);
+
+/* Per-site allele mixtures (nadavca_amd/allele_fractions.py: estimate_allele_fractions_batch): which share of the reads
+ * that cover a reference position carries a base other than the reference's.  THE CONTRACT.  Take a global reference
+ * position P with reference base r = ref_codes[P], and a base b != r.
+ *   covering reads  the reads i with status[i] == 0 (status may be NULL: every read counts) whose reference part
+ *                   covers P, in ascending read index
+ *   per-read value  d_i = (ll_i[p, c] - ll_i[0, reference_i[0]]) / event_length, with (p, c) the read-frame row and
+ *                   column of (P, b) as nvk_consensus_accumulate_dev maps them: a forward read has p = P - chunk_start,
+ *                   c = b; a reverse read p = R - 1 - (P - chunk_start), c = alphabet - 1 - b.  The shift is the read's
+ *                   total without a substitution.  d_i may be -inf.
+ *   likelihood      L(f) = sum_i t(f, d_i);  t(f, d) = d + log(f + (1 - f) exp(-d)) for d > 0, else
+ *                   log((1 - f) + f exp(d));  L(0) = 0.  exp(d) is never formed for a positive d.
+ *   derivative      g(f) = sum_i u(f, d_i);  u(f, d) = (1 - exp(-d)) / (exp(-d) (1 - f) + f) for d > 0, else
+ *                   (exp(d) - 1) / (1 + f (exp(d) - 1));  g does not increase on [0, 1].
+ *   estimate        f^ = 0 unless g(0) > 0;  f^ = 1 if g(1) >= 0;  otherwise 52 bisection steps on [0, 1] (lo = m when
+ *                   g(m) > 0, else hi = m) and f^ = (lo + hi) / 2
+ *   outputs         per (P, b): fraction = f^, lrt = 2 L(f^) (0 when f^ = 0), ll_half = L(1/2), ll_full = L(1) =
+ *                   sum_i d_i (the consensus sum when event_length is the configuration's normalization_event_length);
+ *                   per P: coverage.  At b = r, where the coverage is 0, and where r is outside 0 .. alphabet-1, the
+ *                   four values are 0.
+ * nvk_allele_rows_dev takes nvk_consensus_accumulate_dev's inputs and event_length (> 0, finite) and writes, per
+ * read-major row g = ref_off[i] + p: out_key i64[total_ref] = P, or -1 for a read with status != 0, a position outside
+ * [0, ref_len), a read whose shift is not finite and a read whose reference[0] is outside 0 .. alphabet-1; out_val
+ * f64[total_ref * alphabet] = the row's d in FORWARD columns (0 where the key is -1).  ref_off is copied to the host and
+ * checked (starts at 0, never decreases, ends at total_ref).
+ * nvk_allele_solve_dev: key i64[n_rows] is the rows' keys sorted ascending by a STABLE sort (keys < 0 come first and are
+ * skipped, keys >= ref_len are skipped too), val f64[n_rows * alphabet] the rows gathered into the same order,
+ * ref_codes i32[ref_len]; it writes out_fraction, out_lrt, out_ll_half, out_ll_full f64[ref_len * alphabet] and
+ * out_coverage i64[ref_len], every entry.  Sums run over a position's rows in key order, 64 interleaved partial sums
+ * (row j of the position goes to sum j mod 64) that a fixed butterfly adds up: no atomics, the same bits on every run;
+ * L(f) is evaluated as (the sum of the positive d_i) + (the sum of the logarithms).  2 <= alphabet <= 8.
+ * NVK_ERR_INVALID for bad arguments or offsets; a data pointer may be NULL only where its array is empty.  Device
+ * pointers. */
+int nvk_allele_rows_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, int alphabet, const double *ll,
+                        const int32_t *reference, const int64_t *ref_off, const int64_t *chunk_start,
+                        const int32_t *reverse, const int32_t *status, double event_length, int64_t ref_len,
+                        int64_t *out_key, double *out_val);
+int nvk_allele_solve_dev(nvk_ctx *ctx, int64_t n_rows, int64_t ref_len, int alphabet, const int64_t *key,
+                         const double *val, const int32_t *ref_codes, double *out_fraction, double *out_lrt,
+                         double *out_ll_half, double *out_ll_full, int64_t *out_coverage);
 
 #ifdef __cplusplus
 }

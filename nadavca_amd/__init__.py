@@ -13,6 +13,8 @@ from .refset import ReferenceSet  # noqa: F401
 from .kmer_train import estimate_kmer_model  # noqa: F401
 from .call_mods import call_mods_batch  # noqa: F401
 from .call_indels import call_indels_batch  # noqa: F401
+from .allele_fractions import estimate_allele_fractions_batch  # noqa: F401
 
 __all__ = ['align_signal', 'align_signal_batch', 'estimate_snps', 'estimate_snps_batch', 'dtw', 'SeedAligner',
-           'ReferenceSet', 'estimate_kmer_model', 'call_mods_batch', 'call_indels_batch']
+           'ReferenceSet', 'estimate_kmer_model', 'call_mods_batch', 'call_indels_batch',
+           'estimate_allele_fractions_batch']

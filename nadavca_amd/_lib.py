@@ -28,10 +28,10 @@ TIE_NEAR = 2    # ... two scores closer than 2^-24 relative (beyond the class be
 TIE_PLATEAU = 8  # structural mark: two adjacent bases with the same k-mer level (boundary unidentifiable)
 TIE_ULP = 4     # ... two scores within 64 ulps of the reference's log value, not equal (where its rounding may decide)
 
-K_PLAN, K_ALIGN, K_ELL_SWEEP, K_ELL_HYP, K_EXPECTED, K_CONSENSUS, K_POSTERIOR, K_RENORM, K_METH, K_SEED, K_KMER = \
-    range(11)
+K_PLAN, K_ALIGN, K_ELL_SWEEP, K_ELL_HYP, K_EXPECTED, K_CONSENSUS, K_POSTERIOR, K_RENORM, K_METH, K_SEED, K_KMER, \
+    K_ALLELE = range(12)
 KERNEL_NAMES = ['plan', 'align', 'ell_sweep', 'ell_hyp', 'expected', 'consensus', 'posterior', 'renorm', 'meth',
-                'seed', 'kmer']
+                'seed', 'kmer', 'allele']
 
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -89,6 +89,8 @@ SIGNATURES = {
                                     + [_vp, _vp]),
     'nvk_kmer_event_stats_dev': (_int, [_vp, _i64, _i64] + [_vp] * 10 + [_int] * 4 + [_vp] * 4),
     'nvk_kmer_reduce_dev': (_int, [_vp, _i64, _i64] + [_vp] * 6),
+    'nvk_allele_rows_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 6 + [_dbl, _i64, _vp, _vp]),
+    'nvk_allele_solve_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 8),
 }
 
 _lib = None

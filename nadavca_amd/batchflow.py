@@ -1,7 +1,8 @@
 """What the batch workflows over a ``ReadBatch`` share (``align_signal_batch``, ``estimate_snps_batch``,
 ``detect_meth_batch``, ``estimate_kmer_model``): loading of their arguments, the device stage in front of the kernels
 (``device_stage``: upload, normalise, approximate alignment, windows), the alignment on top of it (``align_batch``),
-the one policy for per-read kernel status (``check_status``) and the segment index of flat layouts (``seg_index``)."""
+the likelihood rows of the SNP-style workflows (``likelihood_rows``), the one policy for per-read kernel status
+(``check_status``) and the segment index of flat layouts (``seg_index``)."""
 import os
 import sys
 
@@ -115,6 +116,23 @@ def device_stage(read_batch, reference_num, config, kmer_model, aligner, mode, g
     st.n_live = int(st.sa.live.numel())
     st.dbatch = DeviceBatch.from_windows(st.norm, st.sa, device) if st.n_live else None
     return st
+
+
+def likelihood_rows(stage, config, kmer_model, fit_workers=0, spline_fit='device'):
+    """What ``estimate_snps_batch`` and ``estimate_allele_fractions_batch`` run on a 'pooled' (or 'ranks') stage with
+    live reads: the spline tweak of the signal normalisation when ``config`` asks for it, then the per-read
+    log-likelihood rows, a band wider than the kernels serve skipped (``check_status``).
+    -> (ll f64 (sum R, alphabet), status int32 (n_live,), reads the tweak fitted or None): device tensors."""
+    from .device import estimate_log_likelihoods_dev
+    fitted = None
+    if config['tweak_signal_normalization']:
+        from .splinefit import tweak_signal_normalization
+        fitted = tweak_signal_normalization(kmer_model.context, kmer_model, stage.dbatch, config, fit_workers,
+                                            spline_fit)
+    ll, status = estimate_log_likelihoods_dev(stage.dbatch, config['bandwidth'], config['min_event_length'],
+                                              kmer_model, config['model_wobbling'])
+    check_status('estimate_log_likelihoods', status, stage.sa.live, too_wide='skip')
+    return ll, status, fitted
 
 
 class BatchAlignment:

@@ -122,17 +122,6 @@ __global__ __launch_bounds__(NT) void long_event_kernel(int64_t n_reads, int64_t
   }
 }
 
-// lo + the first i in [0, n) with key[lo + i] >= want (lo + n if none); key ascending.  Stays in [lo, lo + n] for any
-// key, sorted or not.
-__device__ int64_t lower_bound(const int64_t *key, int64_t lo, int64_t n, int64_t want) {
-  int64_t hi = lo + n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (key[mid] < want) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 // one thread per k-mer: np.sum of its events' values (contiguous, in sorted order), the sample and event counts
 __global__ __launch_bounds__(NT) void kmer_reduce_kernel(int64_t n_events, int64_t n_kmers, const int64_t *key,
                                                          const double *val, const int64_t *len, double *out_sum,

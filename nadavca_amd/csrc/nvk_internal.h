@@ -184,6 +184,17 @@ __device__ __forceinline__ int64_t owner_of(const int64_t *off, int64_t n, int64
   return lo;
 }
 
+// lo + the first i in [0, n) with key[lo + i] >= want (lo + n if none); key ascending.  Stays in [lo, lo + n] for any
+// key, sorted or not.
+__device__ __forceinline__ int64_t lower_bound(const int64_t *key, int64_t lo, int64_t n, int64_t want) {
+  int64_t hi = lo + n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (key[mid] < want) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
 // ----- argument checks (api.hip) -------------------------------------------------------------
 // off[0..n]: not NULL, starts at 0, never decreases
 int check_offsets(const char *what, const int64_t *off, int64_t n);

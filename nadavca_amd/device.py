@@ -525,3 +525,49 @@ def kmer_reduce_dev(context, key, val, length, n_kmers):
                                        _dp(length), _dp(out_sum), _dp(out_samples), _dp(out_events)),
                'nvk_kmer_reduce_dev')
     return out_sum, out_samples, out_events
+
+
+# ---- per-site allele mixtures (nadavca_amd/allele_fractions.py) -------------------------------------------------
+def allele_rows_dev(context, dbatch, ll, chunk_start, reverse, status, event_length, ref_len):
+    """Per read-major row of ``ll``: (key int64 (sum R,), val f64 (sum R, alphabet)) device tensors — the row's global
+    reference position (-1 where it does not count) and its normalised, strand-corrected log-likelihood ratios in
+    forward columns (include/nadavca_hip.h: nvk_allele_rows_dev)."""
+    torch = dbatch.torch
+    lib = _lib.load()
+    alpha = int(ll.shape[1])
+    n = max(dbatch.total_ref, 0)
+    key = torch.empty(n, dtype=torch.int64, device=dbatch.device)
+    val = torch.empty((n, alpha), dtype=torch.float64, device=dbatch.device)
+    _lib.check(lib.nvk_allele_rows_dev(
+        context.handle, dbatch.n, dbatch.total_ref, alpha, _dp(ll), _dp(dbatch.reference), _dp(dbatch.ref_off),
+        _dp(chunk_start), _dp(reverse), _dp(status) if status is not None else C.c_void_p(0), float(event_length),
+        int(ref_len), _dp(key), _dp(val)), 'nvk_allele_rows_dev')
+    return key, val
+
+
+def allele_solve_dev(context, key, val, ref_codes):
+    """Per position of ``ref_codes`` (int32 device tensor) and base: (fraction, lrt, ll_half, ll_full f64 (L, alphabet),
+    coverage int64 (L,)) device tensors (nvk_allele_solve_dev).  ``key``: the rows' keys after a stable ascending
+    sort; ``val`` (rows, alphabet) gathered into the same order."""
+    import torch
+    lib = _lib.load()
+    dev = ref_codes.device
+    L, alpha = int(ref_codes.numel()), int(val.shape[1])
+    out = [torch.empty((L, alpha), dtype=torch.float64, device=dev) for _ in range(4)]
+    cov = torch.empty(L, dtype=torch.int64, device=dev)
+    _lib.check(lib.nvk_allele_solve_dev(context.handle, int(key.numel()), L, alpha, _dp(key), _dp(val),
+                                        _dp(ref_codes), *[_dp(t) for t in out], _dp(cov)), 'nvk_allele_solve_dev')
+    return out[0], out[1], out[2], out[3], cov
+
+
+def allele_fractions_dev(context, dbatch, ll, chunk_start, reverse, status, event_length, ref_codes):
+    """The allele mixture of every reference position from the per-read rows ``ll`` (as written by
+    ``estimate_log_likelihoods_dev``): rows and keys from one kernel, a stable sort by position and a gather (torch:
+    plumbing), the per-position solve in another (include/nadavca_hip.h: nvk_allele_rows_dev has the contract).
+    chunk_start i64 (n,), reverse i32 (n,), status i32 (n,) or None, ref_codes i32 (L,): device tensors.
+    -> (fraction, lrt, ll_half, ll_full f64 (L, alphabet), coverage int64 (L,)) device tensors."""
+    import torch
+    key, val = allele_rows_dev(context, dbatch, ll, chunk_start, reverse, status, event_length,
+                               int(ref_codes.numel()))
+    key, order = torch.sort(key, stable=True)
+    return allele_solve_dev(context, key, val[order], ref_codes)

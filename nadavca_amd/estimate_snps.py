@@ -6,7 +6,7 @@ import sys
 
 from . import defaults
 from .alignment import ApproximateAligner
-from .batchflow import check_status, device_stage, load_config, load_kmer_model, seg_index
+from .batchflow import device_stage, likelihood_rows, load_config, load_kmer_model, seg_index
 from .estimator import ProbabilityEstimator, Chunk, consensus_chunks, independent_posteriors  # noqa: F401
 from .genome import Genome
 from .read import Read
@@ -100,8 +100,7 @@ def estimate_snps_batch(reference_num, read_batch, config=defaults.CONFIG_FILE,
     elsewhere); ``independent=True`` returns every rank's own IndependentChunks."""
     import numpy
     import torch
-    from .device import estimate_log_likelihoods_dev, consensus_accumulate_dev
-    from .splinefit import tweak_signal_normalization
+    from .device import consensus_accumulate_dev
     config, kmer_model = load_config(config), load_kmer_model(kmer_model)
     if aligner is None:
         raise ValueError('estimate_snps_batch needs a batch aligner (BWA has no batch adapter offline)')
@@ -150,12 +149,8 @@ def estimate_snps_batch(reference_num, read_batch, config=defaults.CONFIG_FILE,
         cov = torch.zeros(L, dtype=torch.int64, device=device)
         return localise(consensus_chunks(kmer_model, config['snp_prior_probability'], reference_num, acc, cov, [],
                                          True, group, dst))
-    if config['tweak_signal_normalization']:
-        last_batch_counts['reads_fitted'] = tweak_signal_normalization(context, kmer_model, dbatch, config,
-                                                                       fit_workers, spline_fit)
-    ll, status = estimate_log_likelihoods_dev(dbatch, config['bandwidth'], config['min_event_length'], kmer_model,
-                                              config['model_wobbling'])
-    check_status('estimate_log_likelihoods', status, sa.live, too_wide='skip')
+    ll, status, last_batch_counts['reads_fitted'] = likelihood_rows(stage, config, kmer_model, fit_workers,
+                                                                    spline_fit)
     rev32 = sa.reverse.to(torch.int32)
     nel, prior = config['normalization_event_length'], config['snp_prior_probability']
     ok = (status == 0)

@@ -439,3 +439,65 @@ def make_error_read_batch(n, genome_num, seed=0, length=400, spread=40, substitu
     info = dict(kind=np.array(kinds, dtype=np.int32), reverse=np.array([bool(i % 2) for i in range(n)]),
                 start=np.array(starts, dtype=np.int64))
     return rb, truth, info
+
+
+def make_mixed_read_batch(n, haplotypes, weights, seed=0, model=None, length=400, spread=40, dwell=(3, 17), noise=0.35,
+                          anchor_density=1.0, jitter=0, both_strands=True, raw_scale=12.0, raw_shift=90.0,
+                          raw_dtype=np.int16):
+    """``n`` error-free reads of a MIXTURE: ``haplotypes`` are base-code sequences of one length G that differ by
+    substitutions only (the first one is the reference), read i is drawn from haplotype h with probability
+    ``weights[h]`` (normalised to sum 1) and comes from the reverse strand (rc[x] = 3 - hap[G-1-x]) when i is odd and
+    ``both_strands``.  Its length is length +- spread, its start uniform; its signal is simulated from its own bases
+    with ``model`` (the tuple of ``load_model_arrays``; default: the packaged table) as ``make_read_spec`` does
+    (levels x as raw_scale * x + raw_shift, rounded for an integer ``raw_dtype``), its
+    base -> sample table holds a share ``anchor_density`` of its bases, moved by up to ``jitter`` samples and kept
+    monotone.
+    -> (ReadBatch, truth, info): ``truth`` a BaseAlignmentBatch of the true pairs in the coordinates of the FIRST
+    haplotype's strand — (read index, strand coordinate) of every read base that equals the first haplotype there
+    (where a read's haplotype differs, an aligner reports a mismatch, not a pair) — and ``info`` a dict of per-read
+    arrays: ``haplotype``, ``reverse`` and ``start`` (strand coordinate of the read's first base)."""
+    from .readbatch import ReadBatch, BaseAlignmentBatch
+    haps = [np.asarray(h, dtype=np.int64).reshape(-1) for h in haplotypes]
+    if not haps or any(h.size != haps[0].size for h in haps):
+        raise ValueError('make_mixed_read_batch: the haplotypes must be of one length')
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.size != len(haps) or not (w >= 0).all() or not w.sum() > 0:
+        raise ValueError('make_mixed_read_batch: one non-negative weight per haplotype, not all zero')
+    w = w / w.sum()
+    k, central, alphabet, mean, sigma = load_model_arrays() if model is None else model
+    G = haps[0].size
+    strands = [(h, 3 - h[::-1]) for h in haps]
+    seqs, pairs, raws, mbase, msig, which, revs, starts = [], [], [], [], [], [], [], []
+    for i in range(n):
+        rng = np.random.default_rng([seed, i])
+        h = int(rng.choice(len(haps), p=w))
+        L = int(min(G, max(1, length + rng.integers(-spread, spread + 1))))
+        x0 = int(rng.integers(0, G - L + 1))
+        reverse = bool(both_strands and i % 2)
+        seq = strands[h][reverse][x0:x0 + L]
+        ids = kmer_ids(seq, 0, L, k, central, alphabet)
+        dw = rng.integers(dwell[0], dwell[1] + 1, L)
+        first = np.concatenate([[0], np.cumsum(dw)])
+        x = np.clip(np.repeat(mean[ids], dw) + rng.normal(0.0, noise, int(first[-1])), -5.0, 5.0)
+        raw = raw_scale * x + raw_shift
+        raws.append(np.rint(raw).astype(raw_dtype) if np.issubdtype(raw_dtype, np.integer)
+                    else raw.astype(raw_dtype))
+        keep = np.nonzero(rng.random(L) < anchor_density)[0]
+        at = np.clip(first[keep] + rng.integers(-jitter, jitter + 1, keep.size), 0, int(first[-1]) - 1)
+        mbase.append(keep)
+        msig.append(np.maximum.accumulate(at) if at.size else at)
+        same = np.nonzero(seq == strands[0][reverse][x0:x0 + L])[0]
+        pairs.append(np.stack([same, x0 + same], axis=1).astype(np.int64))
+        seqs.append(seq.astype(np.int32))
+        which.append(h)
+        revs.append(reverse)
+        starts.append(x0)
+    off = lambda xs: np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.int64)
+    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dtype=dt)
+    rb = ReadBatch(cat(raws, raw_dtype), off(raws), cat(seqs, np.int32), off(seqs), cat(mbase, np.int64),
+                   cat(msig, np.int64), off(mbase))
+    truth = BaseAlignmentBatch(cat([p[:, 0] for p in pairs], np.int64), cat([p[:, 1] for p in pairs], np.int64),
+                               off(pairs), np.array(revs, dtype=bool))
+    info = dict(haplotype=np.array(which, dtype=np.int32), reverse=np.array(revs, dtype=bool),
+                start=np.array(starts, dtype=np.int64))
+    return rb, truth, info
