@@ -38,6 +38,10 @@ _i64 = C.c_int64
 _int = C.c_int
 _dbl = C.c_double
 
+# what the *_batch_dev operators on a device batch start with: model, n_reads, 3 totals, 10 array pointers, bandwidth,
+# min_event_length and the operator's switch
+_BATCH_DEV = [_vp, _i64, _i64, _i64, _i64] + [_vp] * 10 + [_int, _int, _int]
+
 # every symbol include/nadavca_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     'nvk_last_error': (C.c_char_p, []),
@@ -64,15 +68,12 @@ SIGNATURES = {
     'nvk_refine_alignment_batch': (_int, [_vp, _i64] + [_vp] * 10 + [_int, _int, _int, _vp, _vp]),
     'nvk_refine_alignment_submit': (_int, [_vp, _i64] + [_vp] * 10 + [_int, _int, _int, _vp, _vp, _vp, C.POINTER(_i64)]),
     'nvk_refine_alignment_wait': (_int, [_vp, _i64]),
-    'nvk_refine_alignment_batch_dev': (_int, [_vp, _i64, _i64, _i64, _i64] + [_vp] * 10 + [_int, _int, _int, _vp, _vp]),
+    'nvk_refine_alignment_batch_dev': (_int, _BATCH_DEV + [_vp, _vp]),
     'nvk_estimate_log_likelihoods_batch': (_int, [_vp, _i64] + [_vp] * 10 + [_int, _int, _int, _vp, _vp]),
-    'nvk_estimate_log_likelihoods_batch_dev': (_int, [_vp, _i64, _i64, _i64, _i64] + [_vp] * 10 + [_int, _int, _int, _vp, _vp]),
-    'nvk_estimate_hypotheses_batch_dev': (_int, [_vp, _i64, _i64, _i64, _i64] + [_vp] * 10 + [_int, _int, _int, _i64]
-                                          + [_vp] * 6),
-    'nvk_estimate_joint_hypotheses_batch_dev': (_int, [_vp, _i64, _i64, _i64, _i64] + [_vp] * 10
-                                                + [_int, _int, _int, _i64, _vp, _i64] + [_vp] * 6),
-    'nvk_estimate_edit_hypotheses_batch_dev': (_int, [_vp, _i64, _i64, _i64, _i64] + [_vp] * 10
-                                               + [_int, _int, _int, _i64, _vp, _vp, _vp, _i64] + [_vp] * 5),
+    'nvk_estimate_log_likelihoods_batch_dev': (_int, _BATCH_DEV + [_vp, _vp]),
+    'nvk_estimate_hypotheses_batch_dev': (_int, _BATCH_DEV + [_i64] + [_vp] * 6),
+    'nvk_estimate_joint_hypotheses_batch_dev': (_int, _BATCH_DEV + [_i64, _vp, _i64] + [_vp] * 6),
+    'nvk_estimate_edit_hypotheses_batch_dev': (_int, _BATCH_DEV + [_i64, _vp, _vp, _vp, _i64] + [_vp] * 5),
     'nvk_consensus_accumulate_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 6 + [_dbl, _i64, _vp, _vp]),
     'nvk_posterior_segments_dev': (_int, [_vp, _i64, _i64, _vp, _int, _int, _dbl, _vp, _vp, _vp]),
     'nvk_normalize_groups_dev': (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),

@@ -102,11 +102,10 @@ def align_signal_batch(reference_filename, read_batch, config=defaults.CONFIG_FI
     import torch
     from .device import to_host
     from .readbatch import contig_local_range
-    from .refset import ReferenceSet
     rb = read_batch
     res = align_batch(rb, load_config(config), load_kmer_model(kmer_model), renorm_rounds, aligner)
     sa, norm, events, status, fits = res.stage.sa, res.stage.norm, res.events, res.status, res.fits
-    names = list(res.stage.reference.names) if isinstance(res.stage.reference, ReferenceSet) else None
+    names = res.stage.contig_names()
     if res.stage.n_live == 0:
         return AlignedBatch(numpy.zeros(0, dtype=numpy.int64), numpy.zeros(0, dtype=numpy.int32),
                             numpy.zeros((0, 3), dtype=numpy.int64), numpy.zeros(1, dtype=numpy.int64), sa, [],

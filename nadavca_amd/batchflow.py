@@ -1,8 +1,9 @@
 """What the batch workflows over a ``ReadBatch`` share (``align_signal_batch``, ``estimate_snps_batch``,
 ``detect_meth_batch``, ``estimate_kmer_model``): loading of their arguments, the device stage in front of the kernels
 (``device_stage``: upload, normalise, approximate alignment, windows), the alignment on top of it (``align_batch``),
-the likelihood rows of the SNP-style workflows (``likelihood_rows``), the one policy for per-read kernel status
-(``check_status``) and the segment index of flat layouts (``seg_index``)."""
+the likelihood rows of the SNP-style workflows (``likelihood_rows``), the closing step of the workflows that score
+listed hypotheses on an alignment (``hypothesis_rows``), the one policy for per-read kernel status (``check_status``)
+and the segment index of flat layouts (``seg_index``)."""
 import os
 import sys
 
@@ -77,6 +78,11 @@ class DeviceStage:
     was made against, base codes or a refset.ReferenceSet."""
     __slots__ = ('norm', 'group_off', 'sa', 'n_live', 'dbatch', 'reference')
 
+    def contig_names(self):
+        """The contigs' names where ``reference`` is a ReferenceSet (the batch results' ``contig_names``), else None."""
+        from .refset import ReferenceSet
+        return list(self.reference.names) if isinstance(self.reference, ReferenceSet) else None
+
 
 def device_stage(read_batch, reference_num, config, kmer_model, aligner, mode, group=None):
     """The raw signals of ``read_batch`` to the device in their own dtype, widened and normalised there in place —
@@ -133,6 +139,18 @@ def likelihood_rows(stage, config, kmer_model, fit_workers=0, spline_fit='device
                                               kmer_model, config['model_wobbling'])
     check_status('estimate_log_likelihoods', status, stage.sa.live, too_wide='skip')
     return ll, status, fitted
+
+
+def hypothesis_rows(what, res, status, owner):
+    """What ``call_mods_batch`` and ``call_indels_batch`` do once operator ``what`` has scored their hypotheses on the
+    BatchAlignment ``res``.  ``status``: the operator's per live read; ``owner``: the live read of every hypothesis
+    (device tensors).  A read that did not align keeps the alignment's status, a band wider than the kernels serve is
+    skipped (``check_status``).  -> (status int32 (n_live,) device tensor, live as a numpy array, mask of the
+    hypotheses whose read is READ_OK)."""
+    import torch
+    status = torch.where(res.status != _lib.READ_OK, res.status, status)
+    check_status(what, status, res.stage.sa.live, too_wide='skip')
+    return status, res.stage.sa.live.cpu().numpy(), (status == _lib.READ_OK)[owner]
 
 
 class BatchAlignment:

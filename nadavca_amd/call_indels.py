@@ -213,10 +213,9 @@ def call_indels_batch(read_batch, aligner, kmer_model, max_del=1, trim=5, thresh
     if threshold != threshold:
         raise ValueError('call_indels_batch: threshold is NaN')
     import torch
-    from .batchflow import align_batch, check_status, load_config, load_kmer_model
+    from .batchflow import align_batch, hypothesis_rows, load_config, load_kmer_model
     from .device import estimate_edit_hypotheses_dev, kmer_reduce_dev, to_host
     from .readbatch import contig_local_range
-    from .refset import ReferenceSet
     kmer_model = load_kmer_model(kmer_model)
     config = load_config(config)
     max_del, trim = int(max_del), int(trim)
@@ -226,7 +225,7 @@ def call_indels_batch(read_batch, aligner, kmer_model, max_del=1, trim=5, thresh
                          % (MAX_ROWS, k))
     res = align_batch(read_batch, config, kmer_model, renorm_rounds, aligner)
     stage = res.stage
-    names = list(stage.reference.names) if isinstance(stage.reference, ReferenceSet) else None
+    names = stage.contig_names()
     if stage.n_live == 0:
         return IndelCallBatch.empty(threshold, contig_names=names)
     sa, dbatch = stage.sa, stage.dbatch
@@ -236,11 +235,8 @@ def call_indels_batch(read_batch, aligner, kmer_model, max_del=1, trim=5, thresh
     total, hyp, status = estimate_edit_hypotheses_dev(
         dbatch, config['bandwidth'], config['min_event_length'], kmer_model, config['model_wobbling'], hyp_off,
         edit_pos, edit_del, ins_off, ins_base)
-    status = torch.where(res.status != _lib.READ_OK, res.status, status)   # a read that did not align stays that
-    check_status('estimate_edit_hypotheses', status, sa.live, too_wide='skip')
-    live = sa.live.cpu().numpy()
+    status, live, ok = hypothesis_rows('estimate_edit_hypotheses', res, status, owner)
     per_read = (hyp_off[1:] - hyp_off[:-1]).cpu().numpy()
-    ok = (status == _lib.READ_OK)[owner]
     owner = owner[ok]
     if int(owner.numel()) == 0:
         return IndelCallBatch.empty(threshold, status.cpu().numpy(), live, total.cpu().numpy(), names)

@@ -279,10 +279,9 @@ def call_mods_batch(read_batch, aligner, kmer_model, pattern='CG', mod_offset=0,
     if not 0.0 < float(site_prior) < 1.0:
         raise ValueError('call_mods_batch: site_prior %r outside the open interval (0, 1)' % (site_prior,))
     import torch
-    from .batchflow import align_batch, check_status, load_config, load_kmer_model
+    from .batchflow import align_batch, hypothesis_rows, load_config, load_kmer_model
     from .device import estimate_hypotheses_dev, estimate_joint_hypotheses_dev, to_host
     from .readbatch import contig_local_range
-    from .refset import ReferenceSet
     kmer_model = load_kmer_model(kmer_model)
     config = load_config(config)
     alphabet = kmer_model.get_alphabet_size()
@@ -295,7 +294,7 @@ def call_mods_batch(read_batch, aligner, kmer_model, pattern='CG', mod_offset=0,
         raise ValueError('call_mods_batch: mod_offset %r outside the pattern %r' % (mod_offset, pattern))
     res = align_batch(read_batch, config, kmer_model, renorm_rounds, aligner)
     stage = res.stage
-    names = list(stage.reference.names) if isinstance(stage.reference, ReferenceSet) else None
+    names = stage.contig_names()
     if stage.n_live == 0:
         return ModCallBatch.empty(contig_names=names, joint=joint)
     sa, dbatch = stage.sa, stage.dbatch
@@ -322,10 +321,8 @@ def call_mods_batch(read_batch, aligner, kmer_model, pattern='CG', mod_offset=0,
         crowded = cut
     else:
         total, hyp, status = estimate_hypotheses_dev(*hyp_args, site_off, pos, torch.full_like(pos, int(mod_code)))
-    status = torch.where(res.status != _lib.READ_OK, res.status, status)   # a read that did not align stays that
-    check_status('estimate_joint_hypotheses' if joint else 'estimate_hypotheses', status, sa.live, too_wide='skip')
-    live = sa.live.cpu().numpy()
-    ok = (status == _lib.READ_OK)[owner]
+    status, live, ok = hypothesis_rows('estimate_joint_hypotheses' if joint else 'estimate_hypotheses', res, status,
+                                       owner)
     owner = owner[ok]
     if int(owner.numel()) == 0:
         return ModCallBatch.empty(status.cpu().numpy(), live, total.cpu().numpy(), names, joint=joint)

@@ -596,9 +596,9 @@ extern "C" int nvk_refine_alignment_batch_dev(
 // estimate_log_likelihoods
 // ---------------------------------------------------------------------------------------------
 namespace {
-// plan + launch of both entries: the full matrix (hyp == nullptr) or the listed hypotheses
+// plan + launch of the full matrix (hyp.kind Full, into out_ll) or of listed hypotheses (into hyp.out_*)
 int ell_run(nvk_model *model, const BatchArgs &a, int model_wobbling, double *out_ll, int32_t *out_status,
-            const EllHyp *hyp) {
+            const EllHyp &hyp) {
   int rc;
   const int64_t n_reads = a.n_reads, total_ref = a.total_ref;
   nvk_ctx *ctx = model->ctx;
@@ -644,7 +644,7 @@ extern "C" int nvk_estimate_log_likelihoods_batch_dev(
                      ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
                      out_status, a);
   if (rc || n_reads == 0) return rc;
-  return ell_run(model, a, model_wobbling, out_ll, out_status, nullptr);
+  return ell_run(model, a, model_wobbling, out_ll, out_status, EllHyp{});
 }
 
 namespace {
@@ -656,6 +656,50 @@ int check_hyp_counts(const std::vector<int64_t> &h_off, int64_t n) {
       return NVK_ERR_INVALID;
     }
   return NVK_OK;
+}
+
+// the second level of a two-level list: hypothesis h owns off[h] .. off[h+1] of arrays of `total` entries
+struct HypLevel {
+  const char *what;        // "substitution", "insertion": the entries, as messages name them
+  const char *total_name;  // the C argument that holds `total`
+  int64_t total;
+  const int64_t *off;
+};
+
+// What the listed-hypothesis entry points do after dev_batch, the same for every kind: the checks of the list (read j
+// owns hyp.off[j] .. hyp.off[j+1] of hyp.total_hyp hypotheses; `level`: their second level, or null) and the launch.
+// lists_present: the kind's own arrays are there wherever their level's total is positive.
+int hyp_run(nvk_model *model, const BatchArgs &a, int model_wobbling, int32_t *out_status, const EllHyp &hyp,
+            const HypLevel *level, bool lists_present) {
+  const int64_t total_hyp = hyp.total_hyp;
+  if (total_hyp < 0 || !hyp.off || !hyp.out_total || (total_hyp > 0 && !hyp.out_hyp) ||
+      (level && (level->total < 0 || !level->off)) || !lists_present) {
+    if (level)
+      nvk_set_error("negative total_hyp / %s or NULL hypothesis / %s / output pointer", level->total_name,
+                    level->what);
+    else
+      nvk_set_error("negative total_hyp or NULL hypothesis / output pointer");
+    return NVK_ERR_INVALID;
+  }
+  if (a.n_reads == 0) {
+    if (level && (total_hyp != 0 || level->total != 0))
+      nvk_set_error("hypothesis offsets end at 0, total_hyp is %lld and %s %lld", (long long)total_hyp,
+                    level->total_name, (long long)level->total);
+    else if (total_hyp != 0)
+      nvk_set_error("hypothesis offsets end at 0, total_hyp is %lld", (long long)total_hyp);
+    else
+      return NVK_OK;
+    return NVK_ERR_INVALID;
+  }
+  // the kernel walks every level of the list: each offsets array is checked here, on a host copy
+  int rc;
+  std::vector<int64_t> h_off;
+  if ((rc = nvk_fetch_offsets(model->ctx, "hypothesis", hyp.off, a.n_reads, h_off, "total_hyp", total_hyp))) return rc;
+  if ((rc = check_hyp_counts(h_off, a.n_reads))) return rc;
+  if (level &&
+      (rc = nvk_fetch_offsets(model->ctx, level->what, level->off, total_hyp, h_off, level->total_name, level->total)))
+    return rc;
+  return ell_run(model, a, model_wobbling, nullptr, out_status, hyp);
 }
 }  // namespace
 
@@ -672,23 +716,9 @@ extern "C" int nvk_estimate_hypotheses_batch_dev(
                      ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
                      out_status, a);
   if (rc) return rc;
-  if (total_hyp < 0 || !hyp_off || !out_total || (total_hyp > 0 && (!hyp_pos || !hyp_base || !out_hyp))) {
-    nvk_set_error("negative total_hyp or NULL hypothesis / output pointer");
-    return NVK_ERR_INVALID;
-  }
-  if (n_reads == 0) {
-    if (total_hyp != 0) {
-      nvk_set_error("hypothesis offsets end at 0, total_hyp is %lld", (long long)total_hyp);
-      return NVK_ERR_INVALID;
-    }
-    return NVK_OK;
-  }
-  // the kernel walks hyp_off[j] .. hyp_off[j+1] of three arrays of total_hyp entries: checked here, on a host copy
-  std::vector<int64_t> h_off;
-  if ((rc = nvk_fetch_offsets(model->ctx, "hypothesis", hyp_off, n_reads, h_off, "total_hyp", total_hyp))) return rc;
-  if ((rc = check_hyp_counts(h_off, n_reads))) return rc;
-  const EllHyp hyp{hyp_off, hyp_pos, hyp_base, out_total, out_hyp};
-  return ell_run(model, a, model_wobbling, nullptr, out_status, &hyp);
+  EllHyp hyp{EllKind::Listed, hyp_off, out_total, out_hyp, total_hyp};
+  hyp.listed = {hyp_pos, hyp_base};
+  return hyp_run(model, a, model_wobbling, out_status, hyp, nullptr, total_hyp <= 0 || (hyp_pos && hyp_base));
 }
 
 extern "C" int nvk_estimate_joint_hypotheses_batch_dev(
@@ -704,31 +734,10 @@ extern "C" int nvk_estimate_joint_hypotheses_batch_dev(
                      ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
                      out_status, a);
   if (rc) return rc;
-  if (total_hyp < 0 || total_sub < 0 || !hyp_off || !sub_off || !out_total || (total_hyp > 0 && !out_hyp) ||
-      (total_sub > 0 && (!sub_pos || !sub_base))) {
-    nvk_set_error("negative total_hyp / total_sub or NULL hypothesis / substitution / output pointer");
-    return NVK_ERR_INVALID;
-  }
-  if (n_reads == 0) {
-    if (total_hyp != 0 || total_sub != 0) {
-      nvk_set_error("hypothesis offsets end at 0, total_hyp is %lld and total_sub %lld", (long long)total_hyp,
-                    (long long)total_sub);
-      return NVK_ERR_INVALID;
-    }
-    return NVK_OK;
-  }
-  // the kernel walks both levels of the list: both offset arrays are checked here, on host copies
-  nvk_ctx *ctx = model->ctx;
-  std::vector<int64_t> h_off;
-  if ((rc = nvk_fetch_offsets(ctx, "hypothesis", hyp_off, n_reads, h_off, "total_hyp", total_hyp))) return rc;
-  if ((rc = check_hyp_counts(h_off, n_reads))) return rc;
-  if ((rc = nvk_fetch_offsets(ctx, "substitution", sub_off, total_hyp, h_off, "total_sub", total_sub))) return rc;
-  EllHyp hyp{hyp_off, nullptr, nullptr, out_total, out_hyp};
-  hyp.sub_off = sub_off;
-  hyp.sub_pos = sub_pos;
-  hyp.sub_base = sub_base;
-  hyp.total_hyp = total_hyp;
-  return ell_run(model, a, model_wobbling, nullptr, out_status, &hyp);
+  EllHyp hyp{EllKind::Joint, hyp_off, out_total, out_hyp, total_hyp};
+  hyp.joint = {sub_off, sub_pos, sub_base};
+  const HypLevel subs{"substitution", "total_sub", total_sub, sub_off};
+  return hyp_run(model, a, model_wobbling, out_status, hyp, &subs, total_sub <= 0 || (sub_pos && sub_base));
 }
 
 extern "C" int nvk_estimate_edit_hypotheses_batch_dev(
@@ -744,30 +753,9 @@ extern "C" int nvk_estimate_edit_hypotheses_batch_dev(
                      ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
                      out_status, a);
   if (rc) return rc;
-  if (total_hyp < 0 || total_ins < 0 || !hyp_off || !ins_off || !out_total ||
-      (total_hyp > 0 && (!edit_pos || !edit_del || !out_hyp)) || (total_ins > 0 && !ins_base)) {
-    nvk_set_error("negative total_hyp / total_ins or NULL hypothesis / insertion / output pointer");
-    return NVK_ERR_INVALID;
-  }
-  if (n_reads == 0) {
-    if (total_hyp != 0 || total_ins != 0) {
-      nvk_set_error("hypothesis offsets end at 0, total_hyp is %lld and total_ins %lld", (long long)total_hyp,
-                    (long long)total_ins);
-      return NVK_ERR_INVALID;
-    }
-    return NVK_OK;
-  }
-  // the kernel walks both levels of the list: both offset arrays are checked here, on host copies
-  nvk_ctx *ctx = model->ctx;
-  std::vector<int64_t> h_off;
-  if ((rc = nvk_fetch_offsets(ctx, "hypothesis", hyp_off, n_reads, h_off, "total_hyp", total_hyp))) return rc;
-  if ((rc = check_hyp_counts(h_off, n_reads))) return rc;
-  if ((rc = nvk_fetch_offsets(ctx, "insertion", ins_off, total_hyp, h_off, "total_ins", total_ins))) return rc;
-  EllHyp hyp{hyp_off, nullptr, nullptr, out_total, out_hyp};
-  hyp.edit_pos = edit_pos;
-  hyp.edit_del = edit_del;
-  hyp.ins_off = ins_off;
-  hyp.ins_base = ins_base;
-  hyp.total_hyp = total_hyp;
-  return ell_run(model, a, model_wobbling, nullptr, out_status, &hyp);
+  EllHyp hyp{EllKind::Edit, hyp_off, out_total, out_hyp, total_hyp};
+  hyp.edit = {edit_pos, edit_del, ins_off, ins_base};
+  const HypLevel letters{"insertion", "total_ins", total_ins, ins_off};
+  return hyp_run(model, a, model_wobbling, out_status, hyp, &letters,
+                 (total_hyp <= 0 || (edit_pos && edit_del)) && (total_ins <= 0 || ins_base));
 }

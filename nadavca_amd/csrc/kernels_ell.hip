@@ -833,8 +833,57 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
 
 }  // namespace
 
+namespace {
+// One variant's launch: its argument struct from the common part `base` and the variant's lists in `hyp`, the
+// instantiation for the batch's min event length and group width, `slots` blocks of one wave with `lds` bytes.
+template <bool LISTED, bool JOINT, bool EDIT>
+int ell_dispatch(nvk_ctx *ctx, const EllArgs &base, const EllHyp &hyp, bool wide_groups, int64_t slots, size_t lds) {
+  typedef typename EllArgsOf<LISTED, JOINT, EDIT>::type Args;
+  Args g;
+  static_cast<EllArgs &>(g) = base;
+  if constexpr (LISTED) {
+    g.hyp_off = hyp.off;
+    g.hyp_pos = hyp.listed.pos;    // (null for the variants that take their work from items)
+    g.hyp_base = hyp.listed.base;
+    g.out_total = hyp.out_total;
+    g.out_hyp = hyp.out_hyp;
+  }
+  if constexpr (JOINT) g.items = (int4 *)ctx->ws[WS_JOINT];
+  if constexpr (JOINT && !EDIT) {
+    g.sub_off = hyp.joint.sub_off;
+    g.sub_pos = hyp.joint.sub_pos;
+    g.sub_base = hyp.joint.sub_base;
+  }
+  if constexpr (EDIT) {
+    g.edit_pos = hyp.edit.pos;
+    g.edit_del = hyp.edit.del;
+    g.ins_off = hyp.edit.ins_off;
+    g.ins_base = hyp.edit.ins_base;
+  }
+  void (*kern)(Args) = nullptr;
+#define ELL_PICK(M) kern = wide_groups ? ell_kernel<M, 16, LISTED, JOINT, EDIT> : ell_kernel<M, 8, LISTED, JOINT, EDIT>
+  switch (base.a.mel) {
+    case 0: ELL_PICK(0); break;
+    case 1: ELL_PICK(1); break;
+    case 2: ELL_PICK(2); break;
+    case 3: ELL_PICK(3); break;
+    default: ELL_PICK(4); break;
+  }
+#undef ELL_PICK
+  if (lds > 64 * 1024) {
+    NVK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+  {
+    TimerScope ts(ctx, NVK_K_ELL_HYP);
+    hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(64), lds, ctx->stream, g);
+  }
+  NVK_HIP(hipGetLastError());
+  return NVK_OK;
+}
+}  // namespace
+
 int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobbling,
-               const EllPlan &pl, const PlanTotals &tot, double *out_ll, int32_t *out_status, const EllHyp *hyp) {
+               const EllPlan &pl, const PlanTotals &tot, double *out_ll, int32_t *out_status, const EllHyp &hyp) {
   if (a.n_reads == 0) return NVK_OK;
   const int mel = a.mel;
   if (mel < 0 || mel > 4) {
@@ -846,9 +895,10 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
     return NVK_ERR_UNSUPPORTED;
   }
   // (nvk_model_create builds no such table: the limit of the item code)
-  if (hyp && (hyp->sub_off || hyp->ins_off) && dm.alphabet > 8) {
+  const bool items = hyp.kind == EllKind::Joint || hyp.kind == EllKind::Edit;  // one packed item per hypothesis
+  if (items && dm.alphabet > 8) {
     nvk_set_error("%s hypotheses pack a letter in 3 bits: alphabet %d, compiled limit is 8",
-                  hyp->sub_off ? "joint" : "edit", dm.alphabet);
+                  hyp.kind == EllKind::Joint ? "joint" : "edit", dm.alphabet);
     return NVK_ERR_UNSUPPORTED;
   }
   const bool wide_groups = dm.k + 2 > 8;  // 16 lanes per hypothesis instead of 8
@@ -884,7 +934,7 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
   int *counter = (int *)ctx->ws[WS_MISC];
   NVK_HIP(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
 
-  EllJointArgs g;
+  EllArgs g;
   g.dm = dm;
   g.a = a;
   g.pl = pl;
@@ -906,62 +956,15 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
   g.out_ll = out_ll;
   g.out_status = out_status;
   ctx->last_spill_bytes = (int64_t)tot.cells * 24 * 2;
-
-  void (*kern)(EllArgs) = nullptr;
-  void (*kern_l)(EllListArgs) = nullptr;
-  void (*kern_j)(EllJointArgs) = nullptr;
-  void (*kern_e)(EllEditArgs) = nullptr;
-  const bool joint = hyp && hyp->sub_off, edit = hyp && hyp->ins_off;
-#define ELL_PICK(M)                                                               \
-  do {                                                                            \
-    if (edit) kern_e = wide_groups ? ell_kernel<M, 16, true, true, true> : ell_kernel<M, 8, true, true, true>; \
-    else if (joint) kern_j = wide_groups ? ell_kernel<M, 16, true, true> : ell_kernel<M, 8, true, true>; \
-    else if (hyp) kern_l = wide_groups ? ell_kernel<M, 16, true> : ell_kernel<M, 8, true>; \
-    else kern = wide_groups ? ell_kernel<M, 16, false> : ell_kernel<M, 8, false>;     \
-  } while (0)
-  switch (mel) {
-    case 0: ELL_PICK(0); break;
-    case 1: ELL_PICK(1); break;
-    case 2: ELL_PICK(2); break;
-    case 3: ELL_PICK(3); break;
-    default: ELL_PICK(4); break;
+  if (items) {
+    if ((rc = nvk_ws_reserve(ctx, WS_JOINT, (size_t)(hyp.total_hyp + 1) * sizeof(int4)))) return rc;
   }
-#undef ELL_PICK
-  if (hyp) {
-    g.hyp_off = hyp->off;
-    g.hyp_pos = hyp->pos;
-    g.hyp_base = hyp->base;
-    g.out_total = hyp->out_total;
-    g.out_hyp = hyp->out_hyp;
+  switch (hyp.kind) {
+    case EllKind::Full: return ell_dispatch<false, false, false>(ctx, g, hyp, wide_groups, slots, lds);
+    case EllKind::Listed: return ell_dispatch<true, false, false>(ctx, g, hyp, wide_groups, slots, lds);
+    case EllKind::Joint: return ell_dispatch<true, true, false>(ctx, g, hyp, wide_groups, slots, lds);
+    case EllKind::Edit: return ell_dispatch<true, true, true>(ctx, g, hyp, wide_groups, slots, lds);
   }
-  if (joint || edit) {
-    if ((rc = nvk_ws_reserve(ctx, WS_JOINT, (size_t)(hyp->total_hyp + 1) * sizeof(int4)))) return rc;
-    g.sub_off = hyp->sub_off;
-    g.sub_pos = hyp->sub_pos;
-    g.sub_base = hyp->sub_base;
-    g.items = (int4 *)ctx->ws[WS_JOINT];
-  }
-  EllEditArgs ge;
-  if (edit) {
-    static_cast<EllListArgs &>(ge) = g;
-    ge.edit_pos = hyp->edit_pos;
-    ge.edit_del = hyp->edit_del;
-    ge.ins_off = hyp->ins_off;
-    ge.ins_base = hyp->ins_base;
-    ge.items = g.items;
-  }
-  const void *kfn = edit ? (const void *)kern_e : joint ? (const void *)kern_j : hyp ? (const void *)kern_l
-                                                                                     : (const void *)kern;
-  if (lds > 64 * 1024) {
-    NVK_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  {
-    TimerScope ts(ctx, NVK_K_ELL_HYP);
-    if (edit) hipLaunchKernelGGL(kern_e, dim3((unsigned)slots), dim3(64), lds, ctx->stream, ge);
-    else if (joint) hipLaunchKernelGGL(kern_j, dim3((unsigned)slots), dim3(64), lds, ctx->stream, g);
-    else if (hyp) hipLaunchKernelGGL(kern_l, dim3((unsigned)slots), dim3(64), lds, ctx->stream, static_cast<const EllListArgs &>(g));
-    else hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(64), lds, ctx->stream, static_cast<const EllArgs &>(g));
-  }
-  NVK_HIP(hipGetLastError());
-  return NVK_OK;
+  nvk_set_error("launch_ell: unknown hypothesis kind %d", (int)hyp.kind);
+  return NVK_ERR_INVALID;
 }

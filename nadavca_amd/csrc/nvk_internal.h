@@ -244,27 +244,27 @@ struct EllPlan {
 };
 int launch_plan_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobbling,
                     const EllPlan &pl, unsigned long long *bandtmp, PlanTotals *totals);
-// listed hypotheses (nvk_estimate_hypotheses_batch_dev): read j owns off[j] .. off[j+1] of (pos, base)
+// What a launch of ell_kernel scores.  Full: every substitution of every position, into out_ll; nothing below `kind`
+// is read.  The other kinds: read j's hypotheses off[j] .. off[j+1] of a list, into out_total / out_hyp (out_ll
+// unused), the list being the members of the kind's own group.
+enum class EllKind { Full, Listed, Joint, Edit };
 struct EllHyp {
-  const int64_t *off;
-  const int32_t *pos, *base;
-  double *out_total;  // [n_reads]
-  double *out_hyp;    // [off[n_reads]]
-  // joint hypotheses (nvk_estimate_joint_hypotheses_batch_dev; pos / base are then unused): hypothesis h is the set
-  // of substitutions sub_off[h] .. sub_off[h+1] of (sub_pos, sub_base); total_hyp = off[n_reads]
-  const int64_t *sub_off = nullptr;
-  const int32_t *sub_pos = nullptr, *sub_base = nullptr;
-  int64_t total_hyp = 0;
-  // edit hypotheses (nvk_estimate_edit_hypotheses_batch_dev; pos / base and sub_* are then unused): hypothesis h deletes
-  // edit_del[h] bases from edit_pos[h] on and inserts the letters ins_off[h] .. ins_off[h+1] of ins_base
-  const int32_t *edit_pos = nullptr, *edit_del = nullptr;
-  const int64_t *ins_off = nullptr;
-  const int32_t *ins_base = nullptr;
+  EllKind kind = EllKind::Full;
+  const int64_t *off = nullptr;
+  double *out_total = nullptr;  // [n_reads]
+  double *out_hyp = nullptr;    // [off[n_reads]]
+  int64_t total_hyp = 0;        // off[n_reads]; Joint and Edit keep one item per hypothesis in WS_JOINT
+  // Listed (nvk_estimate_hypotheses_batch_dev): hypothesis h is the substitution (pos[h], base[h])
+  struct { const int32_t *pos, *base; } listed = {};
+  // Joint (nvk_estimate_joint_hypotheses_batch_dev): hypothesis h is the set of substitutions sub_off[h] ..
+  // sub_off[h+1] of (sub_pos, sub_base)
+  struct { const int64_t *sub_off; const int32_t *sub_pos, *sub_base; } joint = {};
+  // Edit (nvk_estimate_edit_hypotheses_batch_dev): hypothesis h deletes del[h] bases from pos[h] on and inserts the
+  // letters ins_off[h] .. ins_off[h+1] of ins_base
+  struct { const int32_t *pos, *del; const int64_t *ins_off; const int32_t *ins_base; } edit = {};
 };
-// hyp == nullptr: the full matrix into out_ll; else the listed hypotheses into hyp->out_* (out_ll unused)
 int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobbling,
-               const EllPlan &pl, const PlanTotals &tot, double *out_ll, int32_t *out_status,
-               const EllHyp *hyp = nullptr);
+               const EllPlan &pl, const PlanTotals &tot, double *out_ll, int32_t *out_status, const EllHyp &hyp);
 // out_count[0..4) = number of entries of flags[0..n) that are nonzero / have bit 0 / bit 1 / bit 2 set
 int launch_count_flags(nvk_ctx *ctx, const int32_t *flags, int64_t n, int32_t *out_count);
 // bytes the resident waves' spill may take: the ctx limit if set, else a default share of the free memory

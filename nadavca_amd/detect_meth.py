@@ -171,10 +171,9 @@ def detect_meth_batch(reference_filename, read_batch, pattern, config=defaults.C
     import torch
     from .batchflow import align_batch, load_config, load_kmer_model, seg_index
     from .device import event_means_dev, expected_levels_dev, meth_scores_dev, to_host
-    from .refset import ReferenceSet
     kmer_model = load_kmer_model(kmer_model)
     res = align_batch(read_batch, load_config(config), kmer_model, renorm_rounds, aligner)
-    names = list(res.stage.reference.names) if isinstance(res.stage.reference, ReferenceSet) else None
+    names = res.stage.contig_names()
     if res.stage.n_live == 0:
         return MethBatch.empty(contig_names=names)
     sa, dbatch, events, status = res.stage.sa, res.stage.dbatch, res.events, res.status

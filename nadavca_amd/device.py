@@ -133,6 +133,32 @@ def estimate_log_likelihoods_dev(dbatch, bandwidth, min_event_length, kmer_model
     return ll, status
 
 
+def _listed_hypotheses_dev(name, dbatch, bandwidth, min_event_length, kmer_model, model_wobbling, n_hyp, hyp_off,
+                           lists):
+    """The C-ABI call ``name`` of a listed-hypothesis operator.  ``lists``: what it takes between ``hyp_off`` and
+    ``out_total``, in that order: an int (a second level's total) as it is, a (tensor, dtype) pair as a contiguous
+    tensor of that dtype on the batch's device.  -> (total f64 (n,), hyp f64 (n_hyp,), status int32 (n,)), the values
+    NaN wherever the kernel writes none."""
+    torch = dbatch.torch
+    lib = _lib.load()
+    dev = dbatch.device
+
+    def coerce(t, dtype):
+        t = t.to(device=dev, dtype=dtype).contiguous()
+        # (a placeholder element: the C-ABI's pointers of an empty list are never read)
+        return t if t.numel() else torch.zeros(1, dtype=dtype, device=dev)
+    lists = [x if isinstance(x, int) else coerce(*x) for x in [(hyp_off, torch.int64)] + list(lists)]
+    total = torch.full((dbatch.n,), float('nan'), dtype=torch.float64, device=dev)
+    hyp = torch.full((n_hyp,), float('nan'), dtype=torch.float64, device=dev)
+    status = torch.zeros(dbatch.n, dtype=torch.int32, device=dev)
+    _lib.check(getattr(lib, name)(
+        kmer_model.handle, dbatch.n, dbatch.total_signal, dbatch.total_ref, dbatch.total_anchors,
+        *dbatch.pointers(), int(bandwidth), int(min_event_length), int(bool(model_wobbling)),
+        n_hyp, *[x if isinstance(x, int) else _dp(x) for x in lists], _dp(total), _dp(hyp if n_hyp else total),
+        _dp(status)), name)
+    return total, hyp, status
+
+
 def estimate_hypotheses_dev(dbatch, bandwidth, min_event_length, kmer_model, model_wobbling, hyp_off, hyp_pos,
                             hyp_base):
     """``estimate_log_likelihoods_dev`` for a LIST of substitutions: read j's hypotheses are entries
@@ -142,27 +168,13 @@ def estimate_hypotheses_dev(dbatch, bandwidth, min_event_length, kmer_model, mod
     substitution.  The unlisted hypotheses are never run; a read with a position or base out of range gets
     READ_BAD_INPUT (include/nadavca_hip.h: nvk_estimate_hypotheses_batch_dev).  Values of reads with a negative
     status are NaN."""
-    torch = dbatch.torch
-    lib = _lib.load()
-    dev = dbatch.device
-    hyp_off = hyp_off.to(device=dev, dtype=torch.int64).contiguous()
-    hyp_pos = hyp_pos.to(device=dev, dtype=torch.int32).contiguous()
-    hyp_base = hyp_base.to(device=dev, dtype=torch.int32).contiguous()
     n_hyp = int(hyp_pos.numel())
     if int(hyp_base.numel()) != n_hyp or int(hyp_off.numel()) != dbatch.n + 1:
         raise ValueError('estimate_hypotheses_dev: hyp_pos and hyp_base go together, hyp_off has one entry per read '
                          'and one more')
-    total = torch.full((dbatch.n,), float('nan'), dtype=torch.float64, device=dev)
-    hyp = torch.full((n_hyp,), float('nan'), dtype=torch.float64, device=dev)
-    status = torch.zeros(dbatch.n, dtype=torch.int32, device=dev)
-    if n_hyp == 0:  # (a placeholder element: the C-ABI's pointers of an empty list are never read)
-        hyp_pos = hyp_base = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.nvk_estimate_hypotheses_batch_dev(
-        kmer_model.handle, dbatch.n, dbatch.total_signal, dbatch.total_ref, dbatch.total_anchors,
-        *dbatch.pointers(), int(bandwidth), int(min_event_length), int(bool(model_wobbling)),
-        n_hyp, _dp(hyp_off), _dp(hyp_pos), _dp(hyp_base), _dp(total), _dp(hyp if n_hyp else total), _dp(status)),
-        'nvk_estimate_hypotheses_batch_dev')
-    return total, hyp, status
+    i32 = dbatch.torch.int32
+    return _listed_hypotheses_dev('nvk_estimate_hypotheses_batch_dev', dbatch, bandwidth, min_event_length, kmer_model,
+                                  model_wobbling, n_hyp, hyp_off, [(hyp_pos, i32), (hyp_base, i32)])
 
 
 def estimate_joint_hypotheses_dev(dbatch, bandwidth, min_event_length, kmer_model, model_wobbling, hyp_off, sub_off,
@@ -176,28 +188,14 @@ def estimate_joint_hypotheses_dev(dbatch, bandwidth, min_event_length, kmer_mode
     position or base out of range, positions that do not ascend or a hypothesis that re-runs more than 14 rows gets
     READ_BAD_INPUT (include/nadavca_hip.h: nvk_estimate_joint_hypotheses_batch_dev).  Values of reads with a negative
     status are NaN."""
-    torch = dbatch.torch
-    lib = _lib.load()
-    dev = dbatch.device
-    hyp_off = hyp_off.to(device=dev, dtype=torch.int64).contiguous()
-    sub_off = sub_off.to(device=dev, dtype=torch.int64).contiguous()
-    sub_pos = sub_pos.to(device=dev, dtype=torch.int32).contiguous()
-    sub_base = sub_base.to(device=dev, dtype=torch.int32).contiguous()
     n_hyp, n_sub = int(sub_off.numel()) - 1, int(sub_pos.numel())
     if int(sub_base.numel()) != n_sub or int(hyp_off.numel()) != dbatch.n + 1 or n_hyp < 0:
         raise ValueError('estimate_joint_hypotheses_dev: sub_pos and sub_base go together, hyp_off has one entry per '
                          'read and one more, sub_off one per hypothesis and one more')
-    total = torch.full((dbatch.n,), float('nan'), dtype=torch.float64, device=dev)
-    hyp = torch.full((n_hyp,), float('nan'), dtype=torch.float64, device=dev)
-    status = torch.zeros(dbatch.n, dtype=torch.int32, device=dev)
-    if n_sub == 0:  # (a placeholder element: the C-ABI's pointers of an empty list are never read)
-        sub_pos = sub_base = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.nvk_estimate_joint_hypotheses_batch_dev(
-        kmer_model.handle, dbatch.n, dbatch.total_signal, dbatch.total_ref, dbatch.total_anchors,
-        *dbatch.pointers(), int(bandwidth), int(min_event_length), int(bool(model_wobbling)),
-        n_hyp, _dp(hyp_off), n_sub, _dp(sub_off), _dp(sub_pos), _dp(sub_base), _dp(total),
-        _dp(hyp if n_hyp else total), _dp(status)), 'nvk_estimate_joint_hypotheses_batch_dev')
-    return total, hyp, status
+    i32, i64 = dbatch.torch.int32, dbatch.torch.int64
+    return _listed_hypotheses_dev('nvk_estimate_joint_hypotheses_batch_dev', dbatch, bandwidth, min_event_length,
+                                  kmer_model, model_wobbling, n_hyp, hyp_off,
+                                  [n_sub, (sub_off, i64), (sub_pos, i32), (sub_base, i32)])
 
 
 def estimate_edit_hypotheses_dev(dbatch, bandwidth, min_event_length, kmer_model, model_wobbling, hyp_off, edit_pos,
@@ -211,29 +209,14 @@ def estimate_edit_hypotheses_dev(dbatch, bandwidth, min_event_length, kmer_model
     leaves no base in front of it (p < 1) or behind it (p + d > R - 1), a negative d or one above 255, a letter out of
     range or a re-run of more than 14 rows gets READ_BAD_INPUT (include/nadavca_hip.h:
     nvk_estimate_edit_hypotheses_batch_dev).  Values of reads with a negative status are NaN."""
-    torch = dbatch.torch
-    lib = _lib.load()
-    dev = dbatch.device
-    hyp_off = hyp_off.to(device=dev, dtype=torch.int64).contiguous()
-    ins_off = ins_off.to(device=dev, dtype=torch.int64).contiguous()
-    edit_pos = edit_pos.to(device=dev, dtype=torch.int32).contiguous()
-    edit_del = edit_del.to(device=dev, dtype=torch.int32).contiguous()
-    ins_base = ins_base.to(device=dev, dtype=torch.int32).contiguous()
     n_hyp, n_ins = int(edit_pos.numel()), int(ins_base.numel())
     if int(edit_del.numel()) != n_hyp or int(ins_off.numel()) != n_hyp + 1 or int(hyp_off.numel()) != dbatch.n + 1:
         raise ValueError('estimate_edit_hypotheses_dev: edit_pos and edit_del go together, hyp_off has one entry per '
                          'read and one more, ins_off one per hypothesis and one more')
-    total = torch.full((dbatch.n,), float('nan'), dtype=torch.float64, device=dev)
-    hyp = torch.full((n_hyp,), float('nan'), dtype=torch.float64, device=dev)
-    status = torch.zeros(dbatch.n, dtype=torch.int32, device=dev)
-    one = torch.zeros(1, dtype=torch.int32, device=dev)  # (a placeholder: pointers of an empty list are never read)
-    _lib.check(lib.nvk_estimate_edit_hypotheses_batch_dev(
-        kmer_model.handle, dbatch.n, dbatch.total_signal, dbatch.total_ref, dbatch.total_anchors,
-        *dbatch.pointers(), int(bandwidth), int(min_event_length), int(bool(model_wobbling)),
-        n_hyp, _dp(hyp_off), _dp(edit_pos if n_hyp else one), _dp(edit_del if n_hyp else one), n_ins, _dp(ins_off),
-        _dp(ins_base if n_ins else one), _dp(total), _dp(hyp if n_hyp else total), _dp(status)),
-        'nvk_estimate_edit_hypotheses_batch_dev')
-    return total, hyp, status
+    i32, i64 = dbatch.torch.int32, dbatch.torch.int64
+    return _listed_hypotheses_dev('nvk_estimate_edit_hypotheses_batch_dev', dbatch, bandwidth, min_event_length,
+                                  kmer_model, model_wobbling, n_hyp, hyp_off,
+                                  [(edit_pos, i32), (edit_del, i32), n_ins, (ins_off, i64), (ins_base, i32)])
 
 
 # ---- host steps adjacent to the path, on the device (include/nadavca_hip.h, SURVEY.md §8 f1/f2) --------

@@ -252,6 +252,30 @@ def estimate_log_likelihoods_batch(reads, bandwidth, min_event_length, kmer_mode
     return [ll[batch.ref_off[j]:batch.ref_off[j + 1]] for j in range(batch.n)]
 
 
+def _listed_hypotheses(what, dev_fn, batch, off, lists, unfit, params, on_error, return_status):
+    """What ``<what>_batch`` does once its Python lists are flat.  ``off``: the reads' offsets into the hypotheses;
+    ``lists``: what ``dev_fn`` (the operator in nadavca_amd/device.py) takes behind ``hyp_off``, as (int64 array, dtype)
+    pairs — np.int64: offsets, passed as they are; np.int32: values, which must fit 32 bits (ValueError naming
+    ``unfit``); ``params``: (bandwidth, min_event_length, kmer_model, model_wobbling).
+    -> (total, list of the reads' slices of hyp[, status])."""
+    if batch.n == 0:
+        out = (np.zeros(0), [])
+        return out + (np.zeros(0, dtype=np.int32),) if return_status else out
+    for a, dtype in lists:
+        if dtype == np.int32 and a.size and (a.min() < -(1 << 31) or a.max() >= (1 << 31)):
+            raise ValueError('%s_batch: %s does not fit 32 bits' % (what, unfit))
+    import torch
+    from .device import DeviceBatch
+    dbatch = DeviceBatch(batch, torch.device('cuda', params[2].context.device))
+    total, hyp, status = dev_fn(dbatch, *params, torch.from_numpy(off),
+                                *[torch.from_numpy(a.astype(dtype, copy=False)) for a, dtype in lists])
+    total, hyp, status = total.cpu().numpy(), hyp.cpu().numpy(), status.cpu().numpy()
+    if on_error == 'raise':
+        check_status(what, status)
+    out = (total, [hyp[off[j]:off[j + 1]] for j in range(batch.n)])
+    return out + (status,) if return_status else out
+
+
 def estimate_hypotheses_batch(reads, hypotheses, bandwidth, min_event_length, kmer_model, model_wobbling,
                               on_error='raise', return_status=False):
     """``estimate_log_likelihoods_batch`` for a list of substitutions per read instead of the whole matrix.  reads:
@@ -261,28 +285,16 @@ def estimate_hypotheses_batch(reads, hypotheses, bandwidth, min_event_length, km
     hypotheses that are not listed are never run; nvk_estimate_hypotheses_batch_dev).  A position or base out of
     range fails its read (READ_BAD_INPUT: ValueError, or with on_error='status' NaN values and, with
     return_status=True, the status array as a third result)."""
-    import torch
-    from .device import DeviceBatch, estimate_hypotheses_dev
+    from .device import estimate_hypotheses_dev
     batch = reads if isinstance(reads, FlatBatch) else FlatBatch(reads)
     if len(hypotheses) != batch.n:
         raise ValueError('estimate_hypotheses_batch: %d hypothesis lists for %d reads' % (len(hypotheses), batch.n))
     hyps = [np.asarray(h, dtype=np.int64).reshape(-1, 2) for h in hypotheses]
-    off = _offsets([h.shape[0] for h in hyps])
-    if batch.n == 0:
-        out = (np.zeros(0), [])
-        return out + (np.zeros(0, dtype=np.int32),) if return_status else out
-    flat = np.concatenate(hyps)
-    if flat.size and (flat.min() < -(1 << 31) or flat.max() >= (1 << 31)):
-        raise ValueError('estimate_hypotheses_batch: a position or base does not fit 32 bits')
-    dbatch = DeviceBatch(batch, torch.device('cuda', kmer_model.context.device))
-    total, hyp, status = estimate_hypotheses_dev(
-        dbatch, bandwidth, min_event_length, kmer_model, model_wobbling, torch.from_numpy(off),
-        torch.from_numpy(flat[:, 0].astype(np.int32)), torch.from_numpy(flat[:, 1].astype(np.int32)))
-    total, hyp, status = total.cpu().numpy(), hyp.cpu().numpy(), status.cpu().numpy()
-    if on_error == 'raise':
-        check_status('estimate_hypotheses', status)
-    out = (total, [hyp[off[j]:off[j + 1]] for j in range(batch.n)])
-    return out + (status,) if return_status else out
+    flat = np.concatenate(hyps + [np.zeros((0, 2), dtype=np.int64)])
+    return _listed_hypotheses('estimate_hypotheses', estimate_hypotheses_dev, batch,
+                              _offsets([h.shape[0] for h in hyps]), [(flat[:, 0], np.int32), (flat[:, 1], np.int32)],
+                              'a position or base', (bandwidth, min_event_length, kmer_model, model_wobbling),
+                              on_error, return_status)
 
 
 def estimate_joint_hypotheses_batch(reads, hypotheses, bandwidth, min_event_length, kmer_model, model_wobbling,
@@ -295,31 +307,19 @@ def estimate_joint_hypotheses_batch(reads, hypotheses, bandwidth, min_event_leng
     rows with b == reference[p] change nothing).  A position or base out of range, positions that do not ascend or a
     hypothesis that re-runs more than 14 rows fails its read (READ_BAD_INPUT: ValueError, or with on_error='status'
     NaN values and, with return_status=True, the status array as a third result)."""
-    import torch
-    from .device import DeviceBatch, estimate_joint_hypotheses_dev
+    from .device import estimate_joint_hypotheses_dev
     batch = reads if isinstance(reads, FlatBatch) else FlatBatch(reads)
     if len(hypotheses) != batch.n:
         raise ValueError('estimate_joint_hypotheses_batch: %d hypothesis lists for %d reads'
                          % (len(hypotheses), batch.n))
     hyps = [[np.asarray(h, dtype=np.int64).reshape(-1, 2) for h in hs] for hs in hypotheses]
-    off = _offsets([len(hs) for hs in hyps])
-    if batch.n == 0:
-        out = (np.zeros(0), [])
-        return out + (np.zeros(0, dtype=np.int32),) if return_status else out
     sub_off = _offsets([h.shape[0] for hs in hyps for h in hs])
     flat = np.concatenate([h for hs in hyps for h in hs] + [np.zeros((0, 2), dtype=np.int64)])
-    if flat.size and (flat.min() < -(1 << 31) or flat.max() >= (1 << 31)):
-        raise ValueError('estimate_joint_hypotheses_batch: a position or base does not fit 32 bits')
-    dbatch = DeviceBatch(batch, torch.device('cuda', kmer_model.context.device))
-    total, hyp, status = estimate_joint_hypotheses_dev(
-        dbatch, bandwidth, min_event_length, kmer_model, model_wobbling, torch.from_numpy(off),
-        torch.from_numpy(sub_off), torch.from_numpy(flat[:, 0].astype(np.int32)),
-        torch.from_numpy(flat[:, 1].astype(np.int32)))
-    total, hyp, status = total.cpu().numpy(), hyp.cpu().numpy(), status.cpu().numpy()
-    if on_error == 'raise':
-        check_status('estimate_joint_hypotheses', status)
-    out = (total, [hyp[off[j]:off[j + 1]] for j in range(batch.n)])
-    return out + (status,) if return_status else out
+    return _listed_hypotheses('estimate_joint_hypotheses', estimate_joint_hypotheses_dev, batch,
+                              _offsets([len(hs) for hs in hyps]),
+                              [(sub_off, np.int64), (flat[:, 0], np.int32), (flat[:, 1], np.int32)],
+                              'a position or base', (bandwidth, min_event_length, kmer_model, model_wobbling),
+                              on_error, return_status)
 
 
 def estimate_edit_hypotheses_batch(reads, edits, bandwidth, min_event_length, kmer_model, model_wobbling,
@@ -333,32 +333,20 @@ def estimate_edit_hypotheses_batch(reads, edits, bandwidth, min_event_length, km
     p + d > R - 1), d outside 0 .. 255, a letter out of range or an edit that re-runs more than 14 rows fails its read
     (READ_BAD_INPUT: ValueError, or with on_error='status' NaN values and, with return_status=True, the status array
     as a third result)."""
-    import torch
-    from .device import DeviceBatch, estimate_edit_hypotheses_dev
+    from .device import estimate_edit_hypotheses_dev
     batch = reads if isinstance(reads, FlatBatch) else FlatBatch(reads)
     if len(edits) != batch.n:
         raise ValueError('estimate_edit_hypotheses_batch: %d edit lists for %d reads' % (len(edits), batch.n))
-    off = _offsets([len(es) for es in edits])
-    if batch.n == 0:
-        out = (np.zeros(0), [])
-        return out + (np.zeros(0, dtype=np.int32),) if return_status else out
     flat = [e for es in edits for e in es]
     letters = [np.asarray(s, dtype=np.int64).reshape(-1) for _, _, s in flat]
     pd = np.array([[p, d] for p, d, _ in flat], dtype=np.int64).reshape(-1, 2)
     ins = np.concatenate(letters + [np.zeros(0, dtype=np.int64)])
-    for a in (pd, ins):
-        if a.size and (a.min() < -(1 << 31) or a.max() >= (1 << 31)):
-            raise ValueError('estimate_edit_hypotheses_batch: a position, length or letter does not fit 32 bits')
-    dbatch = DeviceBatch(batch, torch.device('cuda', kmer_model.context.device))
-    total, hyp, status = estimate_edit_hypotheses_dev(
-        dbatch, bandwidth, min_event_length, kmer_model, model_wobbling, torch.from_numpy(off),
-        torch.from_numpy(pd[:, 0].astype(np.int32)), torch.from_numpy(pd[:, 1].astype(np.int32)),
-        torch.from_numpy(_offsets([s.size for s in letters])), torch.from_numpy(ins.astype(np.int32)))
-    total, hyp, status = total.cpu().numpy(), hyp.cpu().numpy(), status.cpu().numpy()
-    if on_error == 'raise':
-        check_status('estimate_edit_hypotheses', status)
-    out = (total, [hyp[off[j]:off[j + 1]] for j in range(batch.n)])
-    return out + (status,) if return_status else out
+    return _listed_hypotheses('estimate_edit_hypotheses', estimate_edit_hypotheses_dev, batch,
+                              _offsets([len(es) for es in edits]),
+                              [(pd[:, 0], np.int32), (pd[:, 1], np.int32),
+                               (_offsets([s.size for s in letters]), np.int64), (ins, np.int32)],
+                              'a position, length or letter',
+                              (bandwidth, min_event_length, kmer_model, model_wobbling), on_error, return_status)
 
 
 # ------------------------------------------------------------------------------------------------
