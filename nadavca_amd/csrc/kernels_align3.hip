@@ -1109,8 +1109,13 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
   const int max_c = tot.max_c < 1 ? 1 : tot.max_c;
   int rc = nvk_ws_reserve(ctx, WS_MISC, 256);
   if (rc) return rc;
+  // One work counter per sweep launch, so that nothing has to be zeroed between a chunk's reverse and forward
+  // launch: the first 64 bytes of WS_MISC are 16 counters, zeroed together up front and again (in stream order,
+  // before a reverse launch) whenever a batch of many chunks has used them all.
+  constexpr int N_COUNTERS = 16;
+  static_assert(N_COUNTERS % 2 == 0, "a chunk's reverse / forward pair of counters must not straddle a re-zero");
   int *counter = (int *)ctx->ws[WS_MISC];
-  NVK_HIP(hipMemsetAsync(counter, 0, 2 * sizeof(int), ctx->stream));
+  int launches = 0;
   NVK_HIP(hipMemsetAsync(d_retry, 0, sizeof(int), ctx->stream));
 
   // Two launches: the LDS rings are sized by the largest skew a launch serves, so the (usual) reads
@@ -1185,7 +1190,6 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
     g.offs = (const int32_t *)ctx->ws[WS_OFFS];
     g.signal = a.signal;
     g.bp_stride = bp_stride;
-    g.counter = counter;
     g.order = order;
     g.H = H;
     g.SR = SR;
@@ -1242,10 +1246,12 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
       g.L_stride = L_stride;
       g.n_reads = (int)n_chunk;
       g.read_lo = (int)lo;
-      NVK_HIP(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
+      if (launches % N_COUNTERS == 0) NVK_HIP(hipMemsetAsync(counter, 0, N_COUNTERS * sizeof(int), ctx->stream));
+      g.counter = counter + launches % N_COUNTERS;
       hipLaunchKernelGGL(kern[0], dim3((unsigned)slots_r), dim3(TLk), lds_rev, ctx->stream, g);
-      NVK_HIP(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
+      g.counter = counter + (launches + 1) % N_COUNTERS;
       hipLaunchKernelGGL(kern[1], dim3((unsigned)slots_f), dim3(TLk), lds, ctx->stream, g);
+      launches += 2;
       NVK_HIP(hipGetLastError());
       lo = hi;
     }

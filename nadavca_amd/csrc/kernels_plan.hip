@@ -1,5 +1,5 @@
 // Planner: per read, the band of every DP row, the per-row step densities gathered from
-// the k-mer table, the lane-occupancy intervals and the wavefront skew.  One wave per read.
+// the k-mer table, the lane-occupancy intervals and the wavefront skew.  One block per read.
 //
 // Reference behaviour restated here:
 //   bands                 nadavca/dtw/dtw.cpp:7-35   (ComputeBandStarts / ComputeBandEnds)
@@ -105,69 +105,375 @@ __device__ void plan_bands(const int32_t *anc, int A, int R, int N, int bw,
 
 }
 
-// bandtmp: per read 2*(R+1) u64 scratch words at bandtmp[2*(ref_off+j) ...]
-// One block of PLAN_T threads per read: the band scans run on wave 0, the per-row work (k-mer ids,
-// model gathers, row records) on all waves — it is a latency chain of ~13 dependent rounds per lane
-// with 64 threads.
+// One block of PLAN_T threads per read.  What the planner keeps between its phases — the bands, the spans, the row
+// offsets — is integers of one read, so for a read of up to PLAN_BCAP band rows it stays in LDS (plan_rows_lds) and
+// the row table and the lane records are written once, complete, at the end; a longer read goes through global
+// scratch and the row table (plan_rows_global).  The choice is per read, so it is uniform for the block and every
+// wave takes every barrier of the path.
 constexpr int PLAN_T = 256;
-__global__ __launch_bounds__(PLAN_T) void plan_kernel(DeviceModel dm, BatchArgs a, int mode,
-                                                  double log_p_in, int c_cap, ReadMeta *metas,
-                                                  RowParam *rows, unsigned long long *bandtmp,
-                                                  PlanTotals *totals, Lane3 *lane_f, Lane3 *lane_r,
-                                                  int32_t *lane_offs) {
-  const int rd = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63;
-  __shared__ unsigned long long sh_cells;
-  __shared__ int sh_c;
-  if (rd >= a.n_reads) return;
+constexpr int PLAN_VT = 2048;    // rows whose per-row offsets fit the LDS arrays (more: uniform offsets)
+constexpr int PLAN_BCAP = 1024;  // band rows (R + 1) of a read planned in LDS
+
+struct PlanShared {
+  // plan_rows_global: k | x | S of the offsets, PLAN_VT ints each.
+  // plan_rows_lds:    x | S | bs, be (PLAN_BCAP ints each); the u64 tag|payload words of the bands, dead once bs / be
+  //                   are written, lie under x and S, which are born after them.
+  unsigned long long pool[3 * PLAN_VT / 2];
+  unsigned int ids[PLAN_BCAP];  // plan_rows_lds: the k-mer id of every base (ids below 2^32: plan_kernel)
+  unsigned long long cells;
+  int c, cw, var;
+};
+static_assert(2 * PLAN_BCAP * 8 <= 2 * PLAN_VT * 4 && 2 * PLAN_BCAP <= PLAN_VT, "LDS layout of plan_rows_lds");
+
+// one read as the planner's phases see it
+struct PlanRead {
+  const int32_t *ref, *cb, *ca, *anc;
+  int64_t r0;
+  int N, R, A, T, nb, na, bw, mel;
+};
+
+// plan_bands for a block of PLAN_T threads, in LDS: the same tag|payload words and scans, the bands left as int32
+// in bs[0..R] / be[0..R].  The two scans are independent: waves 0 and 1 run one each.
+__device__ __forceinline__ void plan_bands_lds(const int32_t *anc, int A, int R, int N, int bw,
+                                               unsigned long long *tbs, unsigned long long *tbe, int *bs, int *be,
+                                               int tid) {
+  const int lane = tid & 63, wv = tid >> 6;
+  for (int j = tid; j <= R; j += PLAN_T) {
+    tbs[j] = 0ull;
+    tbe[j] = 0ull;
+  }
+  __syncthreads();
+  for (int j = tid; j < A; j += PLAN_T) {
+    int s = anc[2 * j], ri = anc[2 * j + 1];
+    long long lo = (long long)s - bw;
+    long long hi = (long long)s + bw;
+    unsigned int vbs = (unsigned int)(lo > 0 ? lo : 0);  // max(0, s - bw)
+    // min(N, s + bw); a negative value cannot be packed: clamp to -1 -> flagged as bad band
+    unsigned int vbe = (unsigned int)((hi < N ? (hi < -1 ? -1 : hi) : N) + 1);
+    unsigned long long tag = ((unsigned long long)(j + 1)) << 32;
+    atomicMax(&tbs[ri], tag | vbs);
+    atomicMax(&tbe[ri], tag | vbe);
+  }
+  __syncthreads();
+  if (wv == 0) {
+    int carry = 0;
+    for (int base = 0; base <= R; base += 64) {
+      int j = base + lane;
+      int v = 0;
+      if (j <= R) {
+        unsigned long long w = tbs[j];
+        v = (w >> 32) ? (int)(unsigned int)(w & 0xffffffffu) : 0;
+      }
+      v = max(wave_scan_max_dpp(v), carry);
+      carry = __builtin_amdgcn_readlane(v, 63);
+      if (j <= R) bs[j] = v;
+    }
+  } else if (wv == 1) {
+    int carry = N;
+    for (int base = (R / 64) * 64; base >= 0; base -= 64) {
+      int j = base + 63 - lane;  // descending rows over the lanes: the suffix minimum is a prefix scan
+      int v = N;
+      if (j <= R) {
+        unsigned long long w = tbe[j];
+        v = (w >> 32) ? (int)(unsigned int)(w & 0xffffffffu) - 1 : N;
+      } else {
+        v = 0x7fffffff;
+      }
+      v = min(wave_scan_min_dpp(v), carry);
+      carry = __builtin_amdgcn_readlane(v, 63);
+      if (j <= R) be[j] = v;
+    }
+  }
+  __syncthreads();
+}
+
+// A read of at most PLAN_BCAP band rows.  A row's integers are functions of the bands next to it and of its min
+// event length (with transition rows: of its parity), so every phase takes them from the bands in LDS:
+//   bs, be   the band of the row's boundary
+//   lo, hi   the lane's span: band + warm-up / pre-roll of the steps into and out of the row
+//   off      sh_x / sh_S once the offsets are fixed
+// The table constants are gathered once per row, in the last phase, which writes the row's RowParam and its two lane
+// records; the constants of the row above come from the neighbouring lane.
+__device__ __forceinline__ void plan_rows_lds(const DeviceModel &dm, const PlanRead &q, int mode, double log_p_in,
+                                              int c_cap, int rd, ReadMeta m, ReadMeta *metas, RowParam *rows,
+                                              Lane3 *lane_f, Lane3 *lane_r, int32_t *lane_offs, PlanShared &sh) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int32_t *ref = q.ref, *cb = q.cb, *ca = q.ca;
+  const int N = q.N, R = q.R, T = q.T, nb = q.nb, na = q.na, mel = q.mel;
+  const bool trans = (mode == PLAN_ALIGN_TRANS);
+  constexpr int VT = PLAN_VT;
+  int *sh_x = (int *)sh.pool, *sh_S = sh_x + VT;
+  int *sh_bs = sh_S + VT, *sh_be = sh_bs + PLAN_BCAP;
+  plan_bands_lds(q.anc, q.A, R, N, q.bw, sh.pool, sh.pool + PLAN_BCAP, sh_bs, sh_be, tid);
+
+  // min event length of step r -> r + 1 (RowParam::mel)
+  auto rmel = [=](int r) { return (r + 1 < T && !(trans && (r & 1))) ? mel : 0; };
+  auto BS = [=](int r) { return sh_bs[trans ? (r + 1) >> 1 : r]; };
+  auto BE = [=](int r) { return sh_be[trans ? (r + 1) >> 1 : r]; };
+  // forward lane of row r runs i = lo_r .. be_r, reverse lane i = hi_r .. bs_r  (see kernels_align.hip)
+  auto LO = [=](int r) {
+    int lo = BS(r);
+    if (r > 0) {
+      const int pm = rmel(r - 1);
+      lo = min(lo, BS(r - 1) + pm) - max(pm - 1, 0);
+    }
+    return lo;
+  };
+  auto HI = [=](int r) {
+    int hi = BE(r);
+    if (r + 1 < T) {
+      const int pm = rmel(r);
+      hi = max(hi, BE(r + 1) - pm) + max(pm - 1, 0);
+    }
+    return hi;
+  };
+
+  // --- band checks, cell count and skew (the `idle` rule: plan_rows_global) ------------------------------------
+  const int idle = trans ? 2 : 1;
+  int badband = 0;
+  long long cells = 0;
+  int cneed = 1;
+  for (int r = tid; r < T; r += PLAN_T) {
+    const int b0 = BS(r), b1 = BE(r);
+    if (b1 < b0) badband = 1;
+    cells += (long long)(b1 - b0 + 1);
+    if (r >= 64) {
+      int d = HI(r - 64) - LO(r) + idle;  // need 64*c > d
+      if (d >= 0) cneed = max(cneed, d / 64 + 1);
+    }
+  }
+  cneed = max(cneed, max(mel - 1, 1));
+  badband = __syncthreads_or(badband);
+  cells = wave_sum(cells);
+  cneed = wave_max(cneed);
+  if (lane == 0) {
+    atomicAdd(&sh.cells, (unsigned long long)cells);
+    atomicMax(&sh.c, cneed);
+  }
+  __syncthreads();
+  const int c = sh.c;
+  cells = (long long)sh.cells;
+  const bool team = (c > c_cap);  // (teams of waves: plan_rows_global)
+  int cw = 0;
+  if (team) {
+    constexpr int TL = 64 * ALIGN3_TEAM_W;
+    if (tid == 0) sh.cw = max(mel - 1, 1);
+    __syncthreads();
+    int need = 1;
+    for (int r = TL + tid; r < T; r += PLAN_T) {
+      int d = HI(r - TL) - LO(r) + idle;  // need TL * cw > d
+      if (d >= 0) need = max(need, d / TL + 1);
+    }
+    need = wave_max(need);
+    if (lane == 0) atomicMax(&sh.cw, need);
+    __syncthreads();
+    cw = sh.cw;
+  }
+
+  // --- per-row time offsets: the fixed point of plan_rows_global, its constraint k[r] taken from the bands ------
+  const int gmin = max(mel - 1, 1);
+  const bool neg_gaps = trans && mel <= 2;
+  const bool fixp = !team && T <= VT && T > 64 && (neg_gaps || c > gmin);
+  if (tid == 0) sh.var = 0;
+  if (fixp) {
+    for (int r = tid; r < T; r += PLAN_T) {
+      int g = 0;
+      if (r > 0) {
+        g = gmin;
+        if (neg_gaps) g = max(1 - rmel(r - 1), max(LO(r - 1) - LO(r), HI(r - 1) - HI(r)));
+        g = min(g, c);
+      }
+      sh_S[r] = g;
+      sh_x[r] = 0;
+    }
+  }
+  __syncthreads();
+  // The fixed point is wave 0's alone.  Beside it the other waves work out the k-mer id of every base, once: a
+  // base's id serves its own row and, with transition rows, the two transition rows next to it, and the last phase
+  // then starts at the table gathers instead of at the reference loads.
+  const int t0 = fixp ? 64 : 0;
+  if (tid >= t0) {
+    for (int i = tid - t0; i < R; i += PLAN_T - t0) sh.ids[i] = (unsigned int)kmer_id(dm, ref, R, cb, nb, ca, na, i);
+  }
+  {
+    if (fixp && tid < 64) {  // S: inclusive prefix sum, block by block
+      int carry = 0;
+      for (int b0 = 0; b0 < T; b0 += 64) {
+        const int r = b0 + lane;
+        const int v = wave_scan_add_dpp(r < T ? sh_S[r] : 0) + carry;
+        if (r < T) sh_S[r] = v;
+        carry = __builtin_amdgcn_readlane(v, 63);
+      }
+      const int NEG = -0x20000000;
+      bool changed = true;
+      int iter = 0;
+      while (changed && iter < 64) {
+        changed = false;
+        ++iter;
+        int carry = 0;
+        int xup = 0, Sup = 0;  // x and S of row r - 64: this lane's row of the previous block
+        // (the next block's words are asked for ahead of this block's scan: a block's stores go to other rows)
+        int cur_n = lane < T ? sh_x[lane] : NEG, Sr_n = lane < T ? sh_S[lane] : 0, d_n = 0;
+        for (int b0 = 0; b0 < T; b0 += 64) {  // lower bounds, ascending
+          const int r = b0 + lane;
+          const int cur = cur_n, Sr = Sr_n, d = d_n;
+          if (r + 64 < T) {
+            cur_n = sh_x[r + 64];
+            Sr_n = sh_S[r + 64];
+            d_n = HI(r) - LO(r + 64) + 1 + idle;
+          } else {
+            cur_n = NEG;
+            Sr_n = 0;
+          }
+          int v = cur;
+          if (r < T && r >= 64) {
+            const int k = d - (Sr - Sup);
+            v = max(v, xup + k);
+          }
+          v = max(wave_scan_max_dpp(v), carry);
+          if (r < T) {
+            changed |= (v != cur);
+            sh_x[r] = v;
+          }
+          carry = __builtin_amdgcn_readlane(v, 63);
+          xup = v;
+          Sup = Sr;
+        }
+        WAVE_SYNC();  // (the descending pass takes its rows on other lanes)
+        int carryz = NEG;
+        const int rz = ((T - 1) / 64) * 64 + 63 - lane;
+        int curz_n = rz < T ? sh_x[rz] : 0, Sz_n = rz < T ? sh_S[rz] : 0;
+        for (int b0 = ((T - 1) / 64) * 64; b0 >= 0; b0 -= 64) {  // gap limit, descending: rows over the lanes too
+          const int r = b0 + 63 - lane;
+          const int cur = curz_n;
+          const int U = r < T ? c * r - Sz_n : 0;  // off[r] - c*r = x[r] - U[r]
+          if (b0 >= 64) {
+            curz_n = sh_x[r - 64];
+            Sz_n = sh_S[r - 64];
+          }
+          int z = r < T ? cur - U : NEG;
+          z = max(wave_scan_max_dpp(z), carryz);  // (the maximum over the rows from r up)
+          if (r < T) {
+            const int nx = z + U;
+            changed |= (nx != cur);
+            sh_x[r] = nx;
+          }
+          carryz = __builtin_amdgcn_readlane(z, 63);
+        }
+        WAVE_SYNC();
+        changed = __any(changed);
+      }
+      if (lane == 0) sh.var = changed ? 0 : 1;  // not converged (never seen): uniform offsets
+    }
+    __syncthreads();
+  }
+  const bool var_ok = (sh.var != 0);
+  const int x0 = var_ok ? sh_x[0] : 0;
+  const int cu = team ? cw : c;  // uniform offsets
+  auto OFF = [=](int r) { return var_ok ? sh_x[r] - x0 + sh_S[r] : cu * r; };
+
+  // --- the row table and the lane records, one complete store per row ---------------------------------------------
+  // A wave takes 63 consecutive rows on lanes 1..63; lane 0 gathers the constants of the row above them once more
+  // and only hands them to lane 1, so the constants of row r - 1 are always one lane down.
+  RowParam *rp = rows + m.row_off;
+  const bool records = lane_f && !badband;
+  const int top = T - 1;
+  const int ST = cw ? 64 * ALIGN3_TEAM_W : 64;  // rows between a lane's consecutive rows (lane3.h)
+  int plateau = 0;  // two adjacent bases with the same k-mer level (NVK_TIE_PLATEAU)
+  for (int base = 0; base < T; base += 63 * (PLAN_T / 64)) {
+    const int r = base + 63 * wv + lane - 1;
+    const bool have = (r >= 0 && r < T);
+    RowParam o;
+    o.mean = 0.0;
+    o.ac = 0.0;
+    o.mc = 0.0;
+    o.mel = 0;
+    o.bs = o.be = o.lo = o.hi = o.off = 0;
+    if (have && r + 1 < T) {
+      if (trans && (r & 1)) {
+        // transition step between base r/2 and r/2+1: constant log(0.01), -inf on equal means
+        int i = r / 2;
+        double m1 = dm.mean[sh.ids[i]];
+        double m2 = dm.mean[sh.ids[i + 1]];
+        o.ac = (m1 == m2) ? -INFINITY : log_p_in;
+        plateau |= (m1 == m2) ? 1 : 0;
+      } else {
+        int i = trans ? r / 2 : r;
+        const unsigned int id = sh.ids[i];
+        o.mean = dm.mean[id];
+        o.ac = dm.ac[id];
+        o.mc = dm.mc[id];
+        o.mel = mel;
+      }
+    }
+    RowParam p, nx;
+    p.mean = __shfl_up(o.mean, 1, 64);
+    p.ac = __shfl_up(o.ac, 1, 64);
+    p.mc = __shfl_up(o.mc, 1, 64);
+    p.bs = p.be = p.lo = p.hi = p.mel = p.off = 0;
+    nx.mean = nx.ac = nx.mc = 0.0;
+    nx.bs = nx.be = nx.lo = nx.hi = nx.mel = nx.off = 0;
+    if (have && lane > 0) {
+      o.bs = BS(r);
+      o.be = BE(r);
+      o.lo = LO(r);
+      o.hi = HI(r);
+      o.off = OFF(r);
+      // (without transition rows: steps r - 1 and r are consecutive bases)
+      if (!trans && r > 0 && r + 1 < T) plateau |= (p.mean == o.mean) ? 1 : 0;
+      rp[r] = o;
+      if (records) {
+        if (r > 0) {  // (lane3_row reads neither lo nor hi of the rows above and below)
+          p.bs = BS(r - 1);
+          p.be = BE(r - 1);
+          p.mel = rmel(r - 1);
+          p.off = OFF(r - 1);
+        }
+        if (r < top) {
+          nx.bs = BS(r + 1);
+          nx.be = BE(r + 1);
+          nx.off = OFF(r + 1);
+        }
+        const int adv_f = (r >= ST) ? o.off - OFF(r - ST) : 0;
+        const int adv_b = (r + ST <= top) ? OFF(r + ST) - o.off : 0;
+        Lane3 f, b;
+        lane3_row(o, p, r > 0, nx, r < top, N, adv_f, adv_b, f, b);
+        (lane_f + m.row_off)[r] = f;
+        (lane_r + m.row_off)[r] = b;
+        (lane_offs + m.row_off)[r] = o.off;
+      }
+    }
+  }
+  plateau = __syncthreads_or(plateau);
+
   if (tid == 0) {
-    sh_cells = 0ull;
-    sh_c = 1;
+    const int hi_top = HI(T - 1);
+    int t_min = LO(0);
+    int t_max = hi_top + c * (T - 1);
+    m.c = c;
+    m.cw = cw;
+    m.t_min = t_min;
+    m.n_steps = t_max - t_min + 1;
+    m.pad = hi_top + OFF(T - 1) - t_min + 1;  // steps under the per-row offsets ...
+    m.pad = (m.pad + 31) & ~31;               // ... in whole blocks of 32 (plan_rows_global)
+    m.cells = cells;
+    m.rsv = plateau ? 1 : 0;
+    if (badband) m.status = NVK_READ_BAD_BAND;
+    metas[rd] = m;  // (the batch totals: plan_totals_kernel)
   }
-  const int64_t s0 = a.sig_off[rd], r0 = a.ref_off[rd], a0 = a.anc_off[rd];
-  const int64_t N64 = a.sig_off[rd + 1] - s0;
-  const int64_t R64 = a.ref_off[rd + 1] - r0;
-  const int64_t A64 = a.anc_off[rd + 1] - a0;
-  const int nb = (int)(a.cb_off[rd + 1] - a.cb_off[rd]);
-  const int na = (int)(a.ca_off[rd + 1] - a.ca_off[rd]);
-  const int32_t *ref = a.reference + r0;
-  const int32_t *cb = a.ctx_before + a.cb_off[rd];
-  const int32_t *ca = a.ctx_after + a.ca_off[rd];
-  const int32_t *anc = a.anchors + 2 * a0;
-  const int N = (int)N64, R = (int)R64, A = (int)A64;
-  const int bw = a.bandwidth, mel = a.mel;
+}
 
-  ReadMeta m;
-  m.sig_off = s0;
-  m.ref_off = r0;
-  m.N = N;
-  m.R = R;
-  m.status = NVK_READ_OK;
-  m.pad = 0;
-  m.cells = 0;
-  m.cw = 0;
-  m.rsv = 0;
-  int T;
-  if (mode == PLAN_ALIGN_TRANS) {
-    T = 2 * R;
-    m.row_off = 2 * r0;
-  } else {
-    T = R + 1;
-    m.row_off = r0 + rd;
-  }
-  m.T = T;
-  m.c = 1;
-  m.t_min = 0;
-  m.n_steps = 0;
-
-  int bad = read_is_bad(dm, a, rd, tid, PLAN_T);
-  bad = __syncthreads_or(bad);
-  if (bad) {
-    m.status = NVK_READ_BAD_INPUT;
-    if (tid == 0) metas[rd] = m;
-    return;
-  }
-
+// A read of more band rows than the LDS arrays hold: the bands go through bandtmp (per read 2*(R+1) u64 scratch words
+// at bandtmp[2*(ref_off+j) ...]), the rows' integers through the row table.  The band scans run on wave 0, the
+// per-row work (k-mer ids, model gathers, row records) on all waves.
+__device__ __forceinline__ void plan_rows_global(const DeviceModel &dm, const PlanRead &q, int mode, double log_p_in,
+                                                 int c_cap, int rd, ReadMeta m, ReadMeta *metas, RowParam *rows,
+                                                 unsigned long long *bandtmp, Lane3 *lane_f, Lane3 *lane_r,
+                                                 int32_t *lane_offs, PlanShared &sh) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int32_t *ref = q.ref, *cb = q.cb, *ca = q.ca, *anc = q.anc;
+  const int64_t r0 = q.r0;
+  const int N = q.N, R = q.R, A = q.A, T = q.T, nb = q.nb, na = q.na, bw = q.bw, mel = q.mel;
   unsigned long long *tbs = bandtmp + 2 * (r0 + rd);
   unsigned long long *tbe = tbs + (R + 1);
   plan_bands(anc, A, R, N, bw, tbs, tbe, lane, tid < 64);
@@ -216,7 +522,7 @@ __global__ __launch_bounds__(PLAN_T) void plan_kernel(DeviceModel dm, BatchArgs 
     for (int r = tid; r + 2 < T; r += PLAN_T) plateau |= (rp[r].mean == rp[r + 1].mean) ? 1 : 0;
   plateau = __syncthreads_or(plateau);
   cells = wave_sum(cells);
-  if (lane == 0) atomicAdd(&sh_cells, (unsigned long long)cells);
+  if (lane == 0) atomicAdd(&sh.cells, (unsigned long long)cells);
   __syncthreads();
 
   // --- occupancy intervals (band + warm-up + pre-roll) and skew ---------------------------------
@@ -247,10 +553,10 @@ __global__ __launch_bounds__(PLAN_T) void plan_kernel(DeviceModel dm, BatchArgs 
   }
   cneed = max(cneed, max(mel - 1, 1));
   cneed = wave_max(cneed);
-  if (lane == 0) atomicMax(&sh_c, cneed);
+  if (lane == 0) atomicMax(&sh.c, cneed);
   __syncthreads();
-  const int c = sh_c;
-  cells = (long long)sh_cells;
+  const int c = sh.c;
+  cells = (long long)sh.cells;
   // A band this wide for its row spacing (skew above the main launch's cap) is served by a TEAM of waves
   // (kernels_align3.hip): 64 * ALIGN3_TEAM_W lanes, one row each, so a lane's next row lies that many rows
   // on and the skew it needs is that of the row pair (r - 64 W, r) — on long reads with wide bands the band
@@ -259,8 +565,7 @@ __global__ __launch_bounds__(PLAN_T) void plan_kernel(DeviceModel dm, BatchArgs 
   int cw = 0;
   if (team) {
     constexpr int TL = 64 * ALIGN3_TEAM_W;
-    __shared__ int sh_cw;
-    if (tid == 0) sh_cw = max(mel - 1, 1);
+    if (tid == 0) sh.cw = max(mel - 1, 1);
     __syncthreads();
     int need = 1;
     for (int r = TL + tid; r < T; r += PLAN_T) {
@@ -268,9 +573,9 @@ __global__ __launch_bounds__(PLAN_T) void plan_kernel(DeviceModel dm, BatchArgs 
       if (d >= 0) need = max(need, d / TL + 1);
     }
     need = wave_max(need);
-    if (lane == 0) atomicMax(&sh_cw, need);
+    if (lane == 0) atomicMax(&sh.cw, need);
     __syncthreads();
-    cw = sh_cw;
+    cw = sh.cw;
   }
 
   // --- per-row time offsets (variable skew, used by kernels_align3.hip) ---------------------------
@@ -289,12 +594,11 @@ __global__ __launch_bounds__(PLAN_T) void plan_kernel(DeviceModel dm, BatchArgs 
   // prefix maximum per block of 64 rows, and the upper bound is a suffix maximum of off[r] - c*r; both
   // are iterated to the fixed point by wave 0 (2-4 rounds on config-shaped reads).  Reads with more
   // rows than the LDS arrays hold keep the uniform offsets.
-  constexpr int VT = 2048;
-  __shared__ int sh_k[VT], sh_x[VT], sh_S[VT];
-  __shared__ int sh_var;
+  constexpr int VT = PLAN_VT;
+  int *sh_k = (int *)sh.pool, *sh_x = sh_k + VT, *sh_S = sh_x + VT;
   const int gmin = max(mel - 1, 1);
   const bool neg_gaps = (mode == PLAN_ALIGN_TRANS) && mel <= 2;
-  if (tid == 0) sh_var = 0;
+  if (tid == 0) sh.var = 0;
   __syncthreads();
   if (!team && T <= VT && T > 64 && (neg_gaps || c > gmin)) {
     for (int r = tid; r < T; r += PLAN_T) {
@@ -357,11 +661,11 @@ __global__ __launch_bounds__(PLAN_T) void plan_kernel(DeviceModel dm, BatchArgs 
         }
         changed = __any(changed);
       }
-      if (lane == 0) sh_var = changed ? 0 : 1;  // not converged (never seen): uniform offsets
+      if (lane == 0) sh.var = changed ? 0 : 1;  // not converged (never seen): uniform offsets
     }
     __syncthreads();
   }
-  const bool var_ok = (sh_var != 0);
+  const bool var_ok = (sh.var != 0);
   const int x0 = var_ok ? sh_x[0] : 0;
   const int cu = team ? cw : c;  // uniform offsets
   for (int r = tid; r < T; r += PLAN_T) rp[r].off = var_ok ? sh_x[r] - x0 + sh_S[r] : cu * r;
@@ -387,16 +691,112 @@ __global__ __launch_bounds__(PLAN_T) void plan_kernel(DeviceModel dm, BatchArgs 
     m.cells = cells;
     m.rsv = plateau ? 1 : 0;
     if (badband) m.status = NVK_READ_BAD_BAND;
-    metas[rd] = m;
-    if (!badband) {
-      atomicMax(&totals->max_steps, m.n_steps);
-      atomicMax(&totals->max_c, c);
-      atomicMax(&totals->max_cw, cw);
-      if (c > c_cap) atomicAdd(&totals->n_wide, 1);
-      atomicMax(&totals->max_T, T);
-      atomicAdd(&totals->cells, (unsigned long long)cells);
-      atomicAdd(&totals->steps, (unsigned long long)m.pad);
+    metas[rd] = m;  // (the batch totals: plan_totals_kernel)
+  }
+}
+
+__global__ __launch_bounds__(PLAN_T, 5) void plan_kernel(DeviceModel dm, BatchArgs a, int mode,
+                                                  double log_p_in, int c_cap, ReadMeta *metas,
+                                                  RowParam *rows, unsigned long long *bandtmp,
+                                                  Lane3 *lane_f, Lane3 *lane_r, int32_t *lane_offs) {
+  const int rd = blockIdx.x;
+  const int tid = threadIdx.x;
+  __shared__ PlanShared sh;
+  if (rd >= a.n_reads) return;
+  if (tid == 0) {
+    sh.cells = 0ull;
+    sh.c = 1;
+  }
+  const int64_t s0 = a.sig_off[rd], r0 = a.ref_off[rd], a0 = a.anc_off[rd];
+  const int64_t N64 = a.sig_off[rd + 1] - s0;
+  const int64_t R64 = a.ref_off[rd + 1] - r0;
+  const int64_t A64 = a.anc_off[rd + 1] - a0;
+  PlanRead q;
+  q.nb = (int)(a.cb_off[rd + 1] - a.cb_off[rd]);
+  q.na = (int)(a.ca_off[rd + 1] - a.ca_off[rd]);
+  q.ref = a.reference + r0;
+  q.cb = a.ctx_before + a.cb_off[rd];
+  q.ca = a.ctx_after + a.ca_off[rd];
+  q.anc = a.anchors + 2 * a0;
+  q.r0 = r0;
+  q.N = (int)N64;
+  q.R = (int)R64;
+  q.A = (int)A64;
+  q.bw = a.bandwidth;
+  q.mel = a.mel;
+
+  ReadMeta m;
+  m.sig_off = s0;
+  m.ref_off = r0;
+  m.N = q.N;
+  m.R = q.R;
+  m.status = NVK_READ_OK;
+  m.pad = 0;
+  m.cells = 0;
+  m.cw = 0;
+  m.rsv = 0;
+  if (mode == PLAN_ALIGN_TRANS) {
+    q.T = 2 * q.R;
+    m.row_off = 2 * r0;
+  } else {
+    q.T = q.R + 1;
+    m.row_off = r0 + rd;
+  }
+  m.T = q.T;
+  m.c = 1;
+  m.t_min = 0;
+  m.n_steps = 0;
+
+  int bad = read_is_bad(dm, a, rd, tid, PLAN_T);
+  bad = __syncthreads_or(bad);
+  if (bad) {
+    m.status = NVK_READ_BAD_INPUT;
+    if (tid == 0) metas[rd] = m;
+    return;
+  }
+  if (q.R + 1 <= PLAN_BCAP && dm.n <= 0x100000000ll)  // (plan_rows_lds keeps the k-mer ids as 32-bit words)
+    plan_rows_lds(dm, q, mode, log_p_in, c_cap, rd, m, metas, rows, lane_f, lane_r, lane_offs, sh);
+  else
+    plan_rows_global(dm, q, mode, log_p_in, c_cap, rd, m, metas, rows, bandtmp, lane_f, lane_r, lane_offs, sh);
+}
+
+// The batch totals of plan_kernel, reduced from the reads' metas.  (Every block of plan_kernel used to add its read
+// to them itself: seven atomics on ONE cache line from each of 10 000 blocks are served one after the other, and
+// those 0.7 ms were the kernel's run time whatever else it did.)  Here a block reduces 256 reads and adds once.
+__global__ __launch_bounds__(256) void plan_totals_kernel(const ReadMeta *metas, int n, int c_cap, PlanTotals *totals) {
+  const int rd = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int steps = 0, c = 0, cw = 0, T = 0, wide = 0;
+  unsigned long long cells = 0ull, pad = 0ull;
+  if (rd < n) {
+    const ReadMeta m = metas[rd];
+    if (m.status == NVK_READ_OK) {
+      steps = max(m.n_steps, 0), c = max(m.c, 0), cw = max(m.cw, 0), T = max(m.T, 0);
+      wide = (m.c > c_cap) ? 1 : 0;
+      cells = (unsigned long long)m.cells;
+      pad = (unsigned long long)m.pad;
     }
+  }
+  __shared__ int sh_i[4][5];
+  __shared__ unsigned long long sh_u[4][2];
+  steps = wave_max(steps), c = wave_max(c), cw = wave_max(cw), T = wave_max(T), wide = wave_sum(wide);
+  cells = wave_sum(cells), pad = wave_sum(pad);
+  if (lane == 0) {
+    sh_i[wv][0] = steps, sh_i[wv][1] = c, sh_i[wv][2] = cw, sh_i[wv][3] = T, sh_i[wv][4] = wide;
+    sh_u[wv][0] = cells, sh_u[wv][1] = pad;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; w++) {
+      steps = max(steps, sh_i[w][0]), c = max(c, sh_i[w][1]), cw = max(cw, sh_i[w][2]), T = max(T, sh_i[w][3]);
+      wide += sh_i[w][4], cells += sh_u[w][0], pad += sh_u[w][1];
+    }
+    if (steps) atomicMax(&totals->max_steps, steps);
+    if (c) atomicMax(&totals->max_c, c);
+    if (cw) atomicMax(&totals->max_cw, cw);
+    if (wide) atomicAdd(&totals->n_wide, wide);
+    if (T) atomicMax(&totals->max_T, T);
+    if (cells) atomicAdd(&totals->cells, cells);
+    if (pad) atomicAdd(&totals->steps, pad);
   }
 }
 
@@ -582,20 +982,17 @@ __global__ void order_scan_kernel(int *cnt) {  // one wave, two buckets per lane
   cnt[ORD_N + 2 * lane] = 0;
   cnt[ORD_N + 2 * lane + 1] = 0;
 }
-__global__ void order_fill_kernel(const ReadMeta *metas, int n, const PlanTotals *tot, int *cnt, int *order) {
+// steps_out (or null): the steps of the reads in the order they are handed out (sizes the per-read spill slots of
+// kernels_align3.hip)
+__global__ void order_fill_kernel(const ReadMeta *metas, int n, const PlanTotals *tot, int *cnt, int *order,
+                                  int32_t *steps_out) {
   int rd = blockIdx.x * blockDim.x + threadIdx.x;
   if (rd < n) {
-    int b = order_bucket(metas[rd], tot->max_steps);
-    order[cnt[b] + atomicAdd(&cnt[ORD_N + b], 1)] = rd;
-  }
-}
-
-// steps of the reads in the order they are handed out (sizes the per-read spill slots of kernels_align3.hip)
-__global__ void gather_steps_kernel(const ReadMeta *metas, const int *order, int n, int32_t *out) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p < n) {
-    const ReadMeta m = metas[order[p]];
-    out[p] = (m.status == NVK_READ_OK) ? m.pad : 0;
+    const ReadMeta m = metas[rd];
+    int b = order_bucket(m, tot->max_steps);
+    const int pos = cnt[b] + atomicAdd(&cnt[ORD_N + b], 1);
+    order[pos] = rd;
+    if (steps_out) steps_out[pos] = (m.status == NVK_READ_OK) ? m.pad : 0;
   }
 }
 
@@ -638,9 +1035,8 @@ int launch_order(nvk_ctx *ctx, const ReadMeta *metas, int64_t n_reads, const Pla
   TimerScope ts(ctx, NVK_K_PLAN);
   hipLaunchKernelGGL(order_count_kernel, dim3(blocks), dim3(256), 0, ctx->stream, metas, (int)n_reads, tot_dev, cnt);
   hipLaunchKernelGGL(order_scan_kernel, dim3(1), dim3(64), 0, ctx->stream, cnt);
-  hipLaunchKernelGGL(order_fill_kernel, dim3(blocks), dim3(256), 0, ctx->stream, metas, (int)n_reads, tot_dev, cnt, ord);
-  if (steps_out)
-    hipLaunchKernelGGL(gather_steps_kernel, dim3(blocks), dim3(256), 0, ctx->stream, metas, ord, (int)n_reads, steps_out);
+  hipLaunchKernelGGL(order_fill_kernel, dim3(blocks), dim3(256), 0, ctx->stream, metas, (int)n_reads, tot_dev, cnt, ord,
+                     steps_out);
   NVK_HIP(hipGetLastError());
   *order = ord;
   return NVK_OK;
@@ -656,8 +1052,9 @@ int launch_plan(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int mod
     // the transition constant comes from the host libm, like the model's ac/mc (kmer_model.cpp:77)
     const double log_p_in = log(0.01);
     hipLaunchKernelGGL(plan_kernel, dim3((unsigned)a.n_reads), dim3(PLAN_T), 0, ctx->stream, dm, a, mode,
-                       log_p_in, ALIGN1_C_CAP, metas, rows, bandtmp, totals, (Lane3 *)lane_f, (Lane3 *)lane_r,
-                       lane_offs);
+                       log_p_in, ALIGN1_C_CAP, metas, rows, bandtmp, (Lane3 *)lane_f, (Lane3 *)lane_r, lane_offs);
+    hipLaunchKernelGGL(plan_totals_kernel, dim3((unsigned)((a.n_reads + 255) / 256)), dim3(256), 0, ctx->stream,
+                       metas, (int)a.n_reads, ALIGN1_C_CAP, totals);
   }
   NVK_HIP(hipGetLastError());
   return NVK_OK;

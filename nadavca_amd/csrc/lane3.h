@@ -1,6 +1,7 @@
-// Per-sweep lane records of kernels_align3.hip, derived from the planner's RowParam table.  Shared by the planner
-// (kernels_plan.hip writes them at the tail of plan_kernel, while the read's rows are still in L2 — they used to
-// be a kernel of their own that re-read the whole row table) and the sweep kernels that consume them.
+// Per-sweep lane records of kernels_align3.hip, one pair per DP row.  Shared by the planner, which writes them in
+// the last phase of plan_kernel (kernels_plan.hip: from the bands and offsets it holds in LDS through lane3_row, or,
+// for a read above PLAN_BCAP, from the row table through lane3_rows while the rows are still in L2 — they used to be a
+// kernel of their own that re-read the whole row table) and the sweep kernels that consume them.
 #pragma once
 #include "nvk_internal.h"
 #include "dens.h"
@@ -41,8 +42,43 @@ __device__ __forceinline__ void set_density_consts(Lane3 &l, const RowParam &o) 
 }
 
 
-// the records of one read: `nthreads` threads of one block cooperate (tid = this thread).  rw: the read's rows,
-// fwdl / revl / offs: where its records go (already offset to the read's first row).
+// the two records of one row.  o: the row, p / q: the rows above and below it (read only where they exist: has_p,
+// has_q; of q only bs, be and off), adv_f / adv_b: the offset between the row and the lane's previous row of the
+// forward / reverse sweep (0 where there is none).
+__device__ __forceinline__ void lane3_row(const RowParam &o, const RowParam &p, bool has_p, const RowParam &q,
+                                          bool has_q, int N, int adv_f, int adv_b, Lane3 &f, Lane3 &b) {
+  // forward: applies step r-1 -> r
+  f.bs = o.bs; f.end = o.be; f.lo = o.lo;
+  if (has_p) {
+    set_density_consts(f, p);
+    f.lo = max(o.lo, p.mel);
+    {
+      const int a = max(f.lo, p.bs + p.mel), z = min(o.be, p.be + p.mel);
+      f.pA = (z >= a) ? a : 0x40000000; f.pW = (z >= a) ? z - a : 0;
+    }
+    f.mg = lane3_pack(p.mel, o.off - p.off + p.mel, adv_f);
+  } else {
+    f.mean = 1.0; f.ac = 0.0; f.mc = 0.0; f.mg = lane3_pack(0, 1, 0); f.pA = 0x40000000; f.pW = 0;
+  }
+  // reverse: applies step r -> r+1
+  set_density_consts(b, o);
+  b.bs = o.bs; b.lo = 0;
+  if (has_q) {
+    b.end = min(o.hi, N - o.mel);
+    {
+      const int a = max(o.bs, q.bs - o.mel), z = min(b.end, q.be - o.mel);
+      b.pA = (z >= a) ? a : 0x40000000; b.pW = (z >= a) ? z - a : 0;
+    }
+    b.mg = lane3_pack(o.mel, q.off - o.off + o.mel, adv_b);
+  } else {
+    b.pA = 0x40000000; b.pW = 0;
+    b.end = o.hi;
+    b.mg = lane3_pack(o.mel, 1 + o.mel, adv_b);
+  }
+}
+
+// the records of one read from its row table in memory: `nthreads` threads of one block cooperate (tid = this
+// thread).  rw: the read's rows, fwdl / revl / offs: where its records go (already offset to the read's first row).
 __device__ __forceinline__ void lane3_rows(const RowParam *rw, int T, int N, int cw, Lane3 *fwdl, Lane3 *revl,
                                            int32_t *offs, int tid, int nthreads) {
   const int top = T - 1;
@@ -50,38 +86,9 @@ __device__ __forceinline__ void lane3_rows(const RowParam *rw, int T, int N, int
   for (int r = tid; r < T; r += nthreads) {
     const RowParam o = rw[r];
     Lane3 f, b;
-    // forward: applies step r-1 -> r
-    f.bs = o.bs; f.end = o.be; f.lo = o.lo;
     const int adv_f = (r >= ST) ? o.off - rw[r - ST].off : 0;
     const int adv_b = (r + ST <= top) ? rw[r + ST].off - o.off : 0;
-    if (r > 0) {
-      const RowParam p = rw[r - 1];
-      set_density_consts(f, p);
-      f.lo = max(o.lo, p.mel);
-      {
-        const int a = max(f.lo, p.bs + p.mel), z = min(o.be, p.be + p.mel);
-        f.pA = (z >= a) ? a : 0x40000000; f.pW = (z >= a) ? z - a : 0;
-      }
-      f.mg = lane3_pack(p.mel, o.off - p.off + p.mel, adv_f);
-    } else {
-      f.mean = 1.0; f.ac = 0.0; f.mc = 0.0; f.mg = lane3_pack(0, 1, 0); f.pA = 0x40000000; f.pW = 0;
-    }
-    // reverse: applies step r -> r+1
-    set_density_consts(b, o);
-    b.bs = o.bs; b.lo = 0;
-    if (r < top) {
-      const RowParam q = rw[r + 1];
-      b.end = min(o.hi, N - o.mel);
-      {
-        const int a = max(o.bs, q.bs - o.mel), z = min(b.end, q.be - o.mel);
-        b.pA = (z >= a) ? a : 0x40000000; b.pW = (z >= a) ? z - a : 0;
-      }
-      b.mg = lane3_pack(o.mel, q.off - o.off + o.mel, adv_b);
-    } else {
-      b.pA = 0x40000000; b.pW = 0;
-      b.end = o.hi;
-      b.mg = lane3_pack(o.mel, 1 + o.mel, adv_b);
-    }
+    lane3_row(o, rw[r > 0 ? r - 1 : r], r > 0, rw[r < top ? r + 1 : r], r < top, N, adv_f, adv_b, f, b);
     fwdl[r] = f;
     revl[r] = b;
     offs[r] = o.off;

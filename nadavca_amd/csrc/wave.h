@@ -62,3 +62,28 @@ __device__ __forceinline__ int wave_scan_min_rev(int v, int lane) {
   }
   return v;
 }
+
+// The same inclusive scans on the DPP path: row shifts inside the 16-lane rows, then the two row broadcasts of GFX9
+// (lane 15 of a row to the next row, lane 31 to the upper half).  No trip through the LDS crossbar, which is what a
+// serial chain of scans waits for.  `ident`: the operation's neutral element, taken by lanes without a source.
+#define WAVE_SCAN_DPP_STEP(ctrl, rows) v = op(v, __builtin_amdgcn_update_dpp(ident, v, ctrl, rows, 0xf, false))
+template <class Op>
+__device__ __forceinline__ int wave_scan_dpp(int v, const int ident, Op op) {
+  WAVE_SCAN_DPP_STEP(0x111, 0xf);  // row_shr:1
+  WAVE_SCAN_DPP_STEP(0x112, 0xf);  // row_shr:2
+  WAVE_SCAN_DPP_STEP(0x114, 0xf);  // row_shr:4
+  WAVE_SCAN_DPP_STEP(0x118, 0xf);  // row_shr:8
+  WAVE_SCAN_DPP_STEP(0x142, 0xa);  // row_bcast:15 into rows 1 and 3
+  WAVE_SCAN_DPP_STEP(0x143, 0xc);  // row_bcast:31 into rows 2 and 3
+  return v;
+}
+#undef WAVE_SCAN_DPP_STEP
+__device__ __forceinline__ int wave_scan_add_dpp(int v) {
+  return wave_scan_dpp(v, 0, [](int a, int b) { return a + b; });
+}
+__device__ __forceinline__ int wave_scan_max_dpp(int v) {
+  return wave_scan_dpp(v, (int)0x80000000, [](int a, int b) { return max(a, b); });
+}
+__device__ __forceinline__ int wave_scan_min_dpp(int v) {
+  return wave_scan_dpp(v, 0x7fffffff, [](int a, int b) { return min(a, b); });
+}
