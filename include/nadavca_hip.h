@@ -75,7 +75,8 @@ enum {
   NVK_K_SEED = 9,        /* banded local alignment + traceback of the seed aligner (nvk_seed_extend_dev) */
   NVK_K_KMER = 10,       /* per-event and per-k-mer sample statistics of k-mer table training (nvk_kmer_*_dev) */
   NVK_K_ALLELE = 11,     /* per-site allele mixtures: rows and the per-position solve (nvk_allele_*_dev) */
-  NVK_K_COUNT = 12
+  NVK_K_SITE = 12,       /* per-site event-level pile-up: rows and the per-key moments (nvk_site_*_dev) */
+  NVK_K_COUNT = 13
 };
 
 const char *nvk_last_error(void); /* thread-local message of the last failing call */
@@ -597,6 +598,44 @@ int nvk_allele_rows_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, int al
 int nvk_allele_solve_dev(nvk_ctx *ctx, int64_t n_rows, int64_t ref_len, int alphabet, const int64_t *key,
                          const double *val, const int32_t *ref_codes, double *out_fraction, double *out_lrt,
                          double *out_ll_half, double *out_ll_full, int64_t *out_coverage);
+
+/* Model-free per-site summaries (nadavca_amd/site_levels.py: site_levels_batch): the pile-up of the reads' event levels
+ * over every reference position and strand.  THE CONTRACT.  The library is built with -ffp-contract=off: every
+ * expression below is a rounded operation in the order written.  Inputs are one aligned batch in the flat layout above:
+ * signal / sig_off (the windows), events i32[2 total_ref] in slice coordinates as nvk_refine_alignment_batch_dev writes
+ * them, expected f64[total_ref] (one level per base, as nvk_expected_signal_batch_dev writes it), per read chunk_start
+ * i64 and reverse i32 as nvk_allele_rows_dev uses them, and status (may be NULL: every read counts).
+ *   counted base   base g of read j (R = R_j bases, N = N_j samples) with status[j] == 0, trim <= g < R - trim, a
+ *                  non-empty event a < b after clamping start and end to 0 .. N (as nvk_event_means_dev does), and a
+ *                  global position P = chunk_start[j] + (reverse[j] ? R - 1 - g : g) in [0, ref_len)
+ *   key            2 P + (reverse[j] != 0)
+ *   values         four doubles, x = the read's window:
+ *                    level = np.mean(x[a:b]): numpy's pairwise sum, then one division by n = b - a (the bits of
+ *                            nvk_event_means_dev)
+ *                    stdv  = np.std(x[a:b]): d = x - level, d * d, numpy's pairwise sum of the squares, / n, sqrt
+ *                    dwell = (double)(b - a)
+ *                    resid = level - expected[ref_off[j] + g]
+ * nvk_site_level_rows_dev writes per base (index ref_off[j] + g): out_key i64[total_ref] (-1 when not counted) and
+ * out_val f64[4 total_ref] in the column order above (0.0 four times when not counted).  Events of any length are
+ * served.  trim >= 0, 0 <= ref_len <= 2^61; ref_off and sig_off are copied to the host and checked (start at 0, never
+ * decrease, ref_off ends at total_ref).
+ * nvk_site_moments_dev: key i64[n_rows] is the rows' keys sorted ascending by a STABLE sort (keys < 0 and keys >= n_keys
+ * are skipped), val f64[n_rows * n_val] the rows gathered into the same order, 1 <= n_val <= 8.  For every key q in
+ * 0 .. n_keys, whose run holds c rows 0 .. c-1 in order, and per column:
+ *   S       64 partial sums starting at 0.0, row i added to sum i mod 64 in ascending i, then combined by the butterfly
+ *           p[l] = p[l] + p[l xor d] for d = 32, 16, 8, 4, 2, 1 (every lane ends with the same S)
+ *   mean    S / c
+ *   m2      the same sum of (v - mean) * (v - mean)
+ * out_count i64[n_keys] = c, out_mean and out_m2 f64[n_keys * n_val]; mean = m2 = 0.0 where c == 0; every entry of the
+ * three is written.  A NaN stays inside its own column.  No atomics: the same bits on every run.
+ * NVK_ERR_INVALID for bad arguments or offsets; a data pointer may be NULL only where its array is empty.  Device
+ * pointers. */
+int nvk_site_level_rows_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, const double *signal,
+                            const int64_t *sig_off, const int32_t *events, const int64_t *ref_off,
+                            const double *expected, const int64_t *chunk_start, const int32_t *reverse,
+                            const int32_t *status, int trim, int64_t ref_len, int64_t *out_key, double *out_val);
+int nvk_site_moments_dev(nvk_ctx *ctx, int64_t n_rows, int64_t n_keys, int n_val, const int64_t *key, const double *val,
+                         int64_t *out_count, double *out_mean, double *out_m2);
 
 #ifdef __cplusplus
 }

@@ -29,9 +29,9 @@ TIE_PLATEAU = 8  # structural mark: two adjacent bases with the same k-mer level
 TIE_ULP = 4     # ... two scores within 64 ulps of the reference's log value, not equal (where its rounding may decide)
 
 K_PLAN, K_ALIGN, K_ELL_SWEEP, K_ELL_HYP, K_EXPECTED, K_CONSENSUS, K_POSTERIOR, K_RENORM, K_METH, K_SEED, K_KMER, \
-    K_ALLELE = range(12)
+    K_ALLELE, K_SITE = range(13)
 KERNEL_NAMES = ['plan', 'align', 'ell_sweep', 'ell_hyp', 'expected', 'consensus', 'posterior', 'renorm', 'meth',
-                'seed', 'kmer', 'allele']
+                'seed', 'kmer', 'allele', 'site']
 
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -92,6 +92,8 @@ SIGNATURES = {
     'nvk_kmer_reduce_dev': (_int, [_vp, _i64, _i64] + [_vp] * 6),
     'nvk_allele_rows_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 6 + [_dbl, _i64, _vp, _vp]),
     'nvk_allele_solve_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 8),
+    'nvk_site_level_rows_dev': (_int, [_vp, _i64, _i64] + [_vp] * 8 + [_int, _i64, _vp, _vp]),
+    'nvk_site_moments_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 5),
 }
 
 _lib = None

@@ -97,18 +97,6 @@ __device__ __forceinline__ double log_term(double f, double se) {
   return log(!signbit(se) ? f + (1.0 - f) * e : (1.0 - f) + f * e);
 }
 
-// wave_sum of N values at once, their butterflies interleaved (each value's additions in wave_sum's order)
-template <int N>
-__device__ __forceinline__ void wave_sum_n(double (&v)[N]) {
-  for (int d = 32; d >= 1; d >>= 1) {
-    double o[N];
-#pragma unroll
-    for (int a = 0; a < N; a++) o[a] = __shfl_xor(v[a], d, 64);
-#pragma unroll
-    for (int a = 0; a < N; a++) v[a] += o[a];
-  }
-}
-
 // One position: n rows of A values at v, reference base r in 0 .. A-1; out_*: the position's A entries.  Every lane of
 // the wave calls it with the same arguments; lane 0 writes.
 template <int A, bool CACHED>

@@ -1,7 +1,7 @@
 // numpy's pairwise summation (numpy/_core/src/umath/loops_utils.h.src, @TYPE@_pairwise_sum), restated for one GPU
 // thread: np_sum equals numpy.add.reduce of a contiguous float64 vector bit for bit (tests/test_renorm_cpu.py checks
 // this order against numpy itself).  Used by the event means and the linear fit (kernels_renorm.hip) and by the k-mer
-// statistics (kernels_kmerstats.hip).
+// statistics (kernels_kmerstats.hip) and the site levels (kernels_sitelevels.hip).
 //
 // The sums run over a generated sequence f(0 .. n), not over an array: the squared deviations and the gathered values
 // of the k-mer statistics are never stored.  The walk's stack is in registers: every access to it is an unrolled

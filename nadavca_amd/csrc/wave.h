@@ -39,6 +39,17 @@ __device__ __forceinline__ T wave_sum(T v) {
   for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
   return v;
 }
+// wave_sum of N values at once, their butterflies interleaved (each value's additions in wave_sum's order)
+template <int N>
+__device__ __forceinline__ void wave_sum_n(double (&v)[N]) {
+  for (int d = 32; d >= 1; d >>= 1) {
+    double o[N];
+#pragma unroll
+    for (int a = 0; a < N; a++) o[a] = __shfl_xor(v[a], d, 64);
+#pragma unroll
+    for (int a = 0; a < N; a++) v[a] += o[a];
+  }
+}
 
 // inclusive scans: lane l gets the sum / maximum of lanes 0 .. l, or the minimum of lanes l .. 63
 __device__ __forceinline__ int wave_scan_add(int v, int lane) {

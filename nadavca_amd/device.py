@@ -554,3 +554,55 @@ def allele_fractions_dev(context, dbatch, ll, chunk_start, reverse, status, even
                                int(ref_codes.numel()))
     key, order = torch.sort(key, stable=True)
     return allele_solve_dev(context, key, val[order], ref_codes)
+
+
+# ---- per-site event-level pile-up (nadavca_amd/site_levels.py) --------------------------------------------------
+SITE_COLUMNS = ('level', 'stdv', 'dwell', 'resid')
+
+
+def site_level_rows_dev(context, dbatch, events, expected, chunk_start, reverse, status, trim, ref_len):
+    """Per base of ``dbatch``'s reads: (key int64 (sum R,), val f64 (sum R, 4)) device tensors — 2 * global position +
+    strand of a counted base or -1, and np.mean, np.std and the length of its event over ``dbatch.signal`` and the
+    mean's distance from ``expected`` (include/nadavca_hip.h: nvk_site_level_rows_dev)."""
+    torch = dbatch.torch
+    lib = _lib.load()
+    n = max(dbatch.total_ref, 0)
+    key = torch.empty(n, dtype=torch.int64, device=dbatch.device)
+    val = torch.empty((n, len(SITE_COLUMNS)), dtype=torch.float64, device=dbatch.device)
+    _lib.check(lib.nvk_site_level_rows_dev(
+        context.handle, dbatch.n, dbatch.total_ref, _dp(dbatch.signal), _dp(dbatch.sig_off), _dp(events),
+        _dp(dbatch.ref_off), _dp(expected), _dp(chunk_start), _dp(reverse),
+        _dp(status) if status is not None else C.c_void_p(0), int(trim), int(ref_len), _dp(key), _dp(val)),
+        'nvk_site_level_rows_dev')
+    return key, val
+
+
+def site_moments_dev(context, key, val, n_keys):
+    """Per key 0 .. n_keys: (count int64 (n_keys,), mean f64 (n_keys, n_val), m2 f64 (n_keys, n_val)) device tensors:
+    the rows of the key, and per column their mean and their sum of squared deviations from it
+    (nvk_site_moments_dev).  ``key``: the rows' keys after a stable ascending sort; ``val`` (rows, n_val) gathered into
+    the same order."""
+    import torch
+    lib = _lib.load()
+    dev = val.device
+    n_keys, n_val = int(n_keys), int(val.shape[1])
+    count = torch.empty(n_keys, dtype=torch.int64, device=dev)
+    mean = torch.empty((n_keys, n_val), dtype=torch.float64, device=dev)
+    m2 = torch.empty((n_keys, n_val), dtype=torch.float64, device=dev)
+    _lib.check(lib.nvk_site_moments_dev(context.handle, int(key.numel()), n_keys, n_val, _dp(key), _dp(val),
+                                        _dp(count), _dp(mean), _dp(m2)), 'nvk_site_moments_dev')
+    return count, mean, m2
+
+
+def site_levels_dev(context, dbatch, events, expected, chunk_start, reverse, status, trim, ref_len):
+    """The pile-up of the reads' event levels per (reference position, strand): rows and keys from one kernel, a stable
+    sort by key and a gather (torch: plumbing), the per-key moments in another (include/nadavca_hip.h:
+    nvk_site_level_rows_dev has the contract).  events i32 (sum R, 2), expected f64 (sum R,), chunk_start i64 (n,),
+    reverse i32 (n,), status i32 (n,) or None: device tensors.
+    -> (count int64 (2 ref_len,), mean, m2 f64 (2 ref_len, 4), key, val): key 2 P + strand; ``key`` / ``val``: the
+    rows in read order, before the sort."""
+    import torch
+    key, val = site_level_rows_dev(context, dbatch, events, expected, chunk_start, reverse, status, trim, ref_len)
+    skey, order = torch.sort(key, stable=True)
+    count, mean, m2 = site_moments_dev(context, skey, val[order], 2 * int(ref_len))
+    return count, mean, m2, key, val

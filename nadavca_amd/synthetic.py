@@ -288,12 +288,14 @@ def make_read_batch(n, model, seed=0, genome_length=10000, raw_dtype=np.int16, *
 
 
 def make_modified_read_batch(n, model5, seed=0, pattern='CG', mod_offset=0, modified_fraction=0.5, mod_code=4,
-                             genome_length=10000, raw_dtype=np.int16, **kw):
+                             genome_length=10000, raw_dtype=np.int16, read_seed=None, **kw):
     """``make_read_batch`` with modified bases: ``model5`` is a table whose alphabet holds ``mod_code`` (the tuple of
     ``load_model_arrays``; ``kmer_train.extend_kmer_model`` makes one).  On each strand of a random genome a fraction
     ``modified_fraction`` of the occurrences of ``pattern`` (over ACGT) is modified at ``pattern[mod_offset]``; a read's
     signal is drawn from the TRUTH sequence of its strand (``mod_code`` at the modified sites), its basecalled
-    sequence and the aligner's reference stay canonical.  ``**kw`` as ``make_read_spec`` (no substitutions).
+    sequence and the aligner's reference stay canonical.  ``read_seed``: when given, read i is drawn from
+    ``default_rng([read_seed, i])`` while the genome and the modified sites still come from ``seed`` (two samples over
+    one genome); None: from ``default_rng([seed, i])``.  ``**kw`` as ``make_read_spec`` (no substitutions).
     -> (ReadBatch, SyntheticBatchAligner, genome codes, truth): ``truth`` = {'forward', 'reverse'}: bool masks over
     FORWARD genome coordinates of the modified bases of each strand (a reverse-strand site at forward coordinate x is
     the base 3 - genome[x] of the reverse strand)."""
@@ -322,7 +324,7 @@ def make_modified_read_batch(n, model5, seed=0, pattern='CG', mod_offset=0, modi
     truth = dict(forward=masks[0], reverse=masks[1][::-1].copy())
     specs = []
     for i in range(n):
-        r = np.random.default_rng([seed, i])
+        r = np.random.default_rng([seed if read_seed is None else read_seed, i])
         # the canonical read of make_read_spec, then its signal re-drawn from the truth sequence with the same dwells
         spec = make_read_spec(r, genome, (k, central, alphabet, mean, sigma), i, **kw)
         L, g0, rev = spec['length'], spec['g0'], spec['reverse']
