@@ -637,6 +637,38 @@ int nvk_site_level_rows_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, co
 int nvk_site_moments_dev(nvk_ctx *ctx, int64_t n_rows, int64_t n_keys, int n_val, const int64_t *key, const double *val,
                          int64_t *out_count, double *out_mean, double *out_m2);
 
+/* Per-site rank tests between two samples (nadavca_amd/site_ranks.py: compare_site_ranks, site_rank_tests_batch): the
+ * two-sample Kolmogorov-Smirnov and Mann-Whitney statistics of ONE event column over the pile-ups of every listed key,
+ * as exact integers, and the exact two-sided p-value of the KS statistic.  THE CONTRACT.  The library is built with
+ * -ffp-contract=off: every expression below is a rounded operation in the order written.
+ * Inputs, per sample: key i64[n_rows] and val f64[n_rows], the rows of one column sorted ascending by (key, value) (the
+ * caller sorts; the order among equal values does not matter; sortedness is the caller's promise and is not checked).
+ * Keys are >= 0.  Values hold no NaN; +-inf and -0.0 == 0.0 behave as in C comparisons.  site_key i64[n_sites]: distinct
+ * keys, ascending.  Per listed key q, with A the n values of q's run in val_a, B the m values in val_b, and A_lt(x) /
+ * A_le(x) (B_lt / B_le) the numbers of A's (B's) values < x / <= x:
+ *   n_a, n_b   n and m
+ *   ks_plus    the maximum over every x in A u B of A_le(x) m - B_le(x) n: >= 0, and 0 at the largest x; over n m it is
+ *              the one-sided statistic D+ of the empirical distribution functions
+ *   ks_minus   the same maximum of B_le(x) n - A_le(x) m (D-); the two-sided numerator is h = max(ks_plus, ks_minus)
+ *   u2         the sum over x in A of B_lt(x) + B_le(x): twice the Mann-Whitney U of A, ties counting half
+ *   tie        the sum over the distinct values of A u B of t^3 - t, t the value's multiplicity in the pooled sample;
+ *              this needs n + m < 2^20 per site, which the CALLER guarantees (it is not checked here)
+ *   ks_p       the exact two-sided p-value of h under the null hypothesis, ties ignored: the share of the C(n + m, n)
+ *              lattice paths from (0, 0) to (n, m) that touch a point with |i m - j n| >= h.  V(i, j) = 1.0 where
+ *              |i m - j n| >= h; otherwise V(0, 0) = 0.0 and
+ *                V(i, j) = (V(i-1, j) * (double)i + V(i, j-1) * (double)j) / (double)(i + j),
+ *              a missing neighbour being 0.0; ks_p = V(n, m).  Computed iff min(n, m) <= 255 and n m <= exact_cells;
+ *              NaN otherwise.
+ * Where n or m is 0 the four statistics are 0 and ks_p is NaN (n_a and n_b are still the counts).  All outputs i64[n_sites]
+ * but out_ks_p f64[n_sites]; every entry of the seven is written.  No atomics and no order-dependent sums: the same bits
+ * on every run.  The launch is timed under NVK_K_SITE.  NVK_ERR_INVALID for a negative count, exact_cells < 0, or a NULL
+ * pointer where an array is not empty; n_sites == 0 returns NVK_OK.  Device pointers. */
+int nvk_site_rank_tests_dev(nvk_ctx *ctx, int64_t n_rows_a, const int64_t *key_a, const double *val_a,
+                            int64_t n_rows_b, const int64_t *key_b, const double *val_b, int64_t n_sites,
+                            const int64_t *site_key, int64_t exact_cells, int64_t *out_n_a, int64_t *out_n_b,
+                            int64_t *out_ks_plus, int64_t *out_ks_minus, int64_t *out_u2, int64_t *out_tie,
+                            double *out_ks_p);
+
 #ifdef __cplusplus
 }
 #endif

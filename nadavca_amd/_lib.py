@@ -94,6 +94,7 @@ SIGNATURES = {
     'nvk_allele_solve_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 8),
     'nvk_site_level_rows_dev': (_int, [_vp, _i64, _i64] + [_vp] * 8 + [_int, _i64, _vp, _vp]),
     'nvk_site_moments_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 5),
+    'nvk_site_rank_tests_dev': (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64] + [_vp] * 7),
 }
 
 _lib = None

@@ -606,3 +606,67 @@ def site_levels_dev(context, dbatch, events, expected, chunk_start, reverse, sta
     skey, order = torch.sort(key, stable=True)
     count, mean, m2 = site_moments_dev(context, skey, val[order], 2 * int(ref_len))
     return count, mean, m2, key, val
+
+
+# ---- per-site rank tests between two samples (nadavca_amd/site_ranks.py) -----------------------------------------
+MAX_SITE_ROWS = 1 << 20          # n + m per site stays below this: the tie sum of t^3 - t is an exact int64
+
+
+def sort_site_rows(key, val):
+    """The rows of one sample for nvk_site_rank_tests_dev: rows with key < 0 or a NaN value dropped, the rest sorted
+    ascending by (key, value) — a stable argsort by value, then a stable argsort by key (torch: plumbing).
+    -> (key int64, val f64) contiguous device tensors."""
+    import torch
+    keep = (key >= 0) & ~torch.isnan(val)
+    key, val = key[keep], val[keep]
+    by_val = torch.argsort(val, stable=True)
+    key, val = key[by_val], val[by_val]
+    by_key = torch.argsort(key, stable=True)
+    return key[by_key].contiguous(), val[by_key].contiguous()
+
+
+def common_sites(key_a, key_b, min_coverage):
+    """The ascending keys with at least ``min_coverage`` rows in BOTH sorted key tensors, on the device, and the
+    largest n + m among them (0 when there is none; one number crosses to the host, and only where the two samples
+    together hold MAX_SITE_ROWS rows or more)."""
+    import torch
+    ua, ca = torch.unique_consecutive(key_a, return_counts=True)
+    ub, cb = torch.unique_consecutive(key_b, return_counts=True)
+    ua, ca, ub, cb = ua[ca >= min_coverage], ca[ca >= min_coverage], ub[cb >= min_coverage], cb[cb >= min_coverage]
+    in_b = torch.isin(ua, ub, assume_unique=True)
+    site_key = ua[in_b].contiguous()
+    largest = 0
+    if int(key_a.numel()) + int(key_b.numel()) >= MAX_SITE_ROWS and int(site_key.numel()) > 0:
+        largest = int((ca[in_b] + cb[torch.isin(ub, ua, assume_unique=True)]).max())
+    return site_key, largest
+
+
+def site_rank_tests_dev(context, key_a, val_a, key_b, val_b, min_coverage, exact_cells):
+    """Per-site rank tests between two samples' rows of ONE event column (include/nadavca_hip.h:
+    nvk_site_rank_tests_dev has the contract).  key int64 (rows,) (a key < 0: not counted) and val f64 (rows,) per
+    sample, unsorted device tensors.  Rows with key < 0 or a NaN value are dropped; the rest are sorted by (key,
+    value); the sites are the keys with at least ``min_coverage`` rows in both samples; a site whose two pile-ups hold
+    2^20 rows or more together is a ValueError (the kernel's tie sum is an exact int64 below that); then ONE kernel
+    call.  ``exact_cells``: the exact KS p-value is computed where min(n, m) <= 255 and n m <= exact_cells.
+    -> (site_key, n_a, n_b, ks_plus, ks_minus, u2, tie int64 (sites,), ks_p f64 (sites,)) device tensors, site_key
+    ascending."""
+    import torch
+    lib = _lib.load()
+    if int(min_coverage) != min_coverage or min_coverage < 1:
+        raise ValueError('site_rank_tests_dev: min_coverage %r is not an integer >= 1' % (min_coverage,))
+    if int(exact_cells) != exact_cells or exact_cells < 0:
+        raise ValueError('site_rank_tests_dev: exact_cells %r is not an integer >= 0' % (exact_cells,))
+    key_a, val_a = sort_site_rows(key_a, val_a)
+    key_b, val_b = sort_site_rows(key_b, val_b)
+    site_key, largest = common_sites(key_a, key_b, int(min_coverage))
+    if largest >= MAX_SITE_ROWS:
+        raise ValueError('site_rank_tests_dev: a site holds %d rows in the two samples together; the rank tests serve '
+                         'fewer than 2^20 per site' % largest)
+    n_sites = int(site_key.numel())
+    dev = val_a.device
+    ints = [torch.empty(n_sites, dtype=torch.int64, device=dev) for _ in range(6)]
+    ks_p = torch.empty(n_sites, dtype=torch.float64, device=dev)
+    _lib.check(lib.nvk_site_rank_tests_dev(
+        context.handle, int(key_a.numel()), _dp(key_a), _dp(val_a), int(key_b.numel()), _dp(key_b), _dp(val_b),
+        n_sites, _dp(site_key), int(exact_cells), *[_dp(t) for t in ints], _dp(ks_p)), 'nvk_site_rank_tests_dev')
+    return (site_key, *ints, ks_p)
