@@ -669,6 +669,51 @@ int nvk_site_rank_tests_dev(nvk_ctx *ctx, int64_t n_rows_a, const int64_t *key_a
                             int64_t *out_ks_plus, int64_t *out_ks_minus, int64_t *out_u2, int64_t *out_tie,
                             double *out_ks_p);
 
+/* Per-site two-sample Gaussian mixture tests (nadavca_amd/site_mixtures.py: compare_site_mixtures,
+ * site_mixture_tests_batch): per listed key a two-component Gaussian mixture over the pooled values of ONE event column
+ * of two samples, the components shared by both: first with one mixing weight (stage 0; the labels are not looked at),
+ * then from that solution with one weight per sample (stage 1).  THE CONTRACT.  The library is built with
+ * -ffp-contract=off: every expression below is a rounded operation in the order written.
+ * Inputs: as nvk_site_rank_tests_dev (rows sorted by (key, value) per sample, site_key distinct and ascending); the
+ * values are FINITE (the caller drops the others).  iterations: EM steps per stage, 1 .. 1024; min_sd_ratio in (0, 1].
+ * Per listed key q, A the n values of q's run in val_a, B the m values in val_b, N = n + m, fN = (double)N, the pooled
+ * rows x_i = A[i] for i < n and B[i - n] beyond.
+ *   SUM(f)     64 partial sums starting at 0.0, f(row i) added to sum i mod 64 in ascending i, then combined by the
+ *              butterfly p[l] = p[l] + p[l xor d] for d = 32, 16, 8, 4, 2, 1 (nvk_site_moments_dev's sum over the
+ *              pooled rows).  Every sum below is one.
+ *   one component   mu = SUM(x) / fN; y_i = x_i - mu (every later expression is in y); s = sqrt(SUM(y y) / fN);
+ *              ll_one = -fN (log(s) + (C + 0.5)), C = 0.9189385332046727 (log(2 pi) / 2).  c1 = SUM(y > 0 ? 1 : 0),
+ *              c0 = fN - c1.  Unless 0 < s < inf, c0 > 0 and c1 > 0 the site is NOT FITTED (see below).
+ *              sd_min = min_sd_ratio s.
+ *   start      m0 = SUM(y > 0 ? 0 : y) / c0, m1 = SUM(y > 0 ? y : 0) / c1; with d = y - (y > 0 ? m1 : m0):
+ *              sd0 = fmax(sqrt(SUM(y > 0 ? 0 : d d) / c0), sd_min), sd1 = fmax(sqrt(SUM(y > 0 ? d d : 0) / c1), sd_min);
+ *              wa = wb = c1 / fN.
+ *   r(y, w)    i0 = 1 / sd0, i1 = 1 / sd1, ls0 = log(sd0), ls1 = log(sd1); z0 = (y - m0) i0, z1 = (y - m1) i1;
+ *              l0 = -0.5 (z0 z0) - ls0, l1 = -0.5 (z1 z1) - ls1; q = l1 - l0; e = exp(-|q|); u = 1 - w;
+ *              q > 0: num = w, den = w + u e; otherwise num = w e, den = w e + u; r = num / den where den > 0, else 0
+ *              for q > 0 and 1 otherwise.  The row's log density is ld = (q > 0 ? l1 : l0) + log(den) (- C).
+ *              A row of A takes w = wa, a row of B w = wb.
+ *   EM step    with r_i at the step's parameters: Ra = SUM(i < n ? r : 0), Rb = SUM(i < n ? 0 : r), R0 = SUM(1 - r),
+ *              T1 = SUM(r y), T0 = SUM((1 - r) y); R1 = Ra + Rb.  Unless R1 > 0 and R0 > 0 the stage ENDS here, the
+ *              parameters unchanged.  Otherwise m0' = T0 / R0, m1' = T1 / R1, with the SAME r_i
+ *              sd0' = fmax(sqrt(SUM((1 - r) ((y - m0') (y - m0'))) / R0), sd_min) and sd1' likewise from r, m1', R1;
+ *              stage 0: wa' = wb' = R1 / fN; stage 1: wa' = Ra / (double)n, wb' = Rb / (double)m.
+ *   a stage    up to `iterations` EM steps, then at its final parameters ll = SUM(ld) - fN C, and in stage 0 also
+ *              Ra, Rb as above, rbar = (Ra + Rb) / fN and Q = SUM((r - rbar) (r - rbar)).  Stage 1 starts from stage
+ *              0's final parameters.
+ * out_counts i64[5 n_sites], per site: n, m, fitted (0 / 1), the EM steps run in stage 0 and in stage 1.
+ * out_fit f64[17 n_sites], per site: ll_one | stage 0: mu + m0, sd0, mu + m1, sd1, w, ll_shared, Ra, Rb, Q | stage 1:
+ * mu + m0, sd0, mu + m1, sd1, wa, wb, ll_free.  A site that is not fitted has fitted = 0, no steps, ll_shared = ll_free
+ * = ll_one (+inf where every value is the same) and NaN in the other fourteen; where n or m is 0 all seventeen are NaN.
+ * Every entry is written.  Sites of up to 128 rows keep y and r in registers, larger ones recompute them: the same
+ * expressions and the same bits.  No atomics: the same bits on every run.  The launch is timed under NVK_K_SITE.
+ * NVK_ERR_INVALID for a negative count, iterations or min_sd_ratio outside their ranges, or a NULL pointer where an
+ * array is not empty; n_sites == 0 returns NVK_OK and writes nothing.  Device pointers. */
+int nvk_site_mixture_tests_dev(nvk_ctx *ctx, int64_t n_rows_a, const int64_t *key_a, const double *val_a,
+                               int64_t n_rows_b, const int64_t *key_b, const double *val_b, int64_t n_sites,
+                               const int64_t *site_key, int iterations, double min_sd_ratio, int64_t *out_counts,
+                               double *out_fit);
+
 #ifdef __cplusplus
 }
 #endif

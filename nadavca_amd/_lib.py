@@ -95,6 +95,7 @@ SIGNATURES = {
     'nvk_site_level_rows_dev': (_int, [_vp, _i64, _i64] + [_vp] * 8 + [_int, _i64, _vp, _vp]),
     'nvk_site_moments_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 5),
     'nvk_site_rank_tests_dev': (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64] + [_vp] * 7),
+    'nvk_site_mixture_tests_dev': (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _int, _dbl, _vp, _vp]),
 }
 
 _lib = None

@@ -670,3 +670,42 @@ def site_rank_tests_dev(context, key_a, val_a, key_b, val_b, min_coverage, exact
         context.handle, int(key_a.numel()), _dp(key_a), _dp(val_a), int(key_b.numel()), _dp(key_b), _dp(val_b),
         n_sites, _dp(site_key), int(exact_cells), *[_dp(t) for t in ints], _dp(ks_p)), 'nvk_site_rank_tests_dev')
     return (site_key, *ints, ks_p)
+
+
+# ---- per-site mixture tests between two samples (nadavca_amd/site_mixtures.py) -----------------------------------
+SITE_MIX_COUNTS, SITE_MIX_FIT = 5, 17        # the columns of nvk_site_mixture_tests_dev's two tables
+
+
+def site_mixture_tests_dev(context, key_a, val_a, key_b, val_b, min_coverage, iterations, min_sd_ratio):
+    """Per-site two-component mixture fits over two samples' rows of ONE event column (include/nadavca_hip.h:
+    nvk_site_mixture_tests_dev has the contract).  key int64 (rows,) (a key < 0: not counted) and val f64 (rows,) per
+    sample, unsorted device tensors.  Rows with key < 0 or a value that is not finite are dropped (a mixture cannot
+    hold +-inf, which the rank tests keep); the rest are sorted by (key, value) (``sort_site_rows``); the sites are the
+    keys with at least ``min_coverage`` rows in both samples (``common_sites``); a site whose two pile-ups hold 2^20
+    rows or more together is a ValueError, as for the rank tests; then ONE kernel call.
+    -> (site_key int64 (sites,), counts int64 (sites, 5), fit f64 (sites, 17)) device tensors, site_key ascending; the
+    columns as the contract lists them."""
+    import torch
+    lib = _lib.load()
+    if int(min_coverage) != min_coverage or min_coverage < 1:
+        raise ValueError('site_mixture_tests_dev: min_coverage %r is not an integer >= 1' % (min_coverage,))
+    if int(iterations) != iterations or not 1 <= iterations <= 1024:
+        raise ValueError('site_mixture_tests_dev: iterations %r is not an integer in 1 .. 1024' % (iterations,))
+    if not 0.0 < min_sd_ratio <= 1.0:
+        raise ValueError('site_mixture_tests_dev: min_sd_ratio %r is not in (0, 1]' % (min_sd_ratio,))
+    finite_a, finite_b = torch.isfinite(val_a), torch.isfinite(val_b)
+    key_a, val_a = sort_site_rows(key_a[finite_a], val_a[finite_a])
+    key_b, val_b = sort_site_rows(key_b[finite_b], val_b[finite_b])
+    site_key, largest = common_sites(key_a, key_b, int(min_coverage))
+    if largest >= MAX_SITE_ROWS:
+        raise ValueError('site_mixture_tests_dev: a site holds %d rows in the two samples together; the mixture tests '
+                         'serve fewer than 2^20 per site' % largest)
+    n_sites = int(site_key.numel())
+    dev = val_a.device
+    counts = torch.empty((n_sites, SITE_MIX_COUNTS), dtype=torch.int64, device=dev)
+    fit = torch.empty((n_sites, SITE_MIX_FIT), dtype=torch.float64, device=dev)
+    _lib.check(lib.nvk_site_mixture_tests_dev(
+        context.handle, int(key_a.numel()), _dp(key_a), _dp(val_a), int(key_b.numel()), _dp(key_b), _dp(val_b),
+        n_sites, _dp(site_key), int(iterations), float(min_sd_ratio), _dp(counts), _dp(fit)),
+        'nvk_site_mixture_tests_dev')
+    return site_key, counts, fit
