@@ -391,6 +391,20 @@ int check_common(nvk_model *model, int64_t n_reads, int bandwidth, int mel) {
   return NVK_OK;
 }
 
+int check_site_samples(const char *what, nvk_ctx *ctx, int64_t n_rows_a, const int64_t *key_a, const double *val_a,
+                       int64_t n_rows_b, const int64_t *key_b, const double *val_b, int64_t n_sites,
+                       const int64_t *site_key) {
+  if (!ctx || n_rows_a < 0 || n_rows_b < 0 || n_sites < 0) {
+    nvk_set_error("%s: invalid argument (ctx, n_rows_a >= 0, n_rows_b >= 0, n_sites >= 0)", what);
+    return NVK_ERR_INVALID;
+  }
+  if (n_sites > 0 && (!site_key || (n_rows_a > 0 && (!key_a || !val_a)) || (n_rows_b > 0 && (!key_b || !val_b)))) {
+    nvk_set_error("%s: NULL site_key, or NULL key or values of a sample that has rows", what);
+    return NVK_ERR_INVALID;
+  }
+  return NVK_OK;
+}
+
 namespace {
 
 // The prologue of the two device-pointer operators: their argument checks, the device, and the batch as

@@ -23,8 +23,7 @@
 // Resources on gfx950: no LDS, no scratch, no atomics; the register counts are in DESIGN.md 4.7.
 #include <math.h>
 
-#include "nvk_internal.h"
-#include "wave.h"
+#include "site_runs.h"
 
 namespace {
 
@@ -32,13 +31,6 @@ constexpr int NT = 256;
 constexpr int CACHE = 2;  // rows per lane whose y and r stay in registers: sites of up to 64 * CACHE rows
 constexpr int N_COUNTS = 5, N_FIT = 17;             // the columns of out_counts and out_fit
 constexpr double HALF_LOG_2PI = 0.9189385332046727;  // log(2 pi) / 2
-
-// a value that is the same in every lane, as one the compiler knows to be
-__device__ __forceinline__ int64_t uniform64(int64_t v) {
-  const unsigned lo = __builtin_amdgcn_readfirstlane((int)(unsigned)(uint64_t)v);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((int)(unsigned)((uint64_t)v >> 32));
-  return (int64_t)(((uint64_t)hi << 32) | lo);
-}
 
 // The butterfly of wave_sum_n (every lane ends with p[l] + p[l xor d] for d = 32, 16, 8, 4, 2, 1, the same additions in
 // the same order, so the same bits) with the four distances inside a 16-lane row on DPP moves instead of trips through
@@ -283,11 +275,7 @@ __global__ __launch_bounds__(NT) void site_mixture_tests_kernel(int64_t n_rows_a
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t waves = (int64_t)gridDim.x * (NT / 64);
   for (int64_t t = (int64_t)blockIdx.x * (NT / 64) + wave; t < n_sites; t += waves) {
-    const int64_t q = site_key[t];
-    const int64_t la = lower_bound(key_a, 0, n_rows_a, q);
-    const int64_t n = uniform64(lower_bound(key_a, la, n_rows_a - la, q + 1) - la);
-    const int64_t lb = lower_bound(key_b, 0, n_rows_b, q);
-    const int64_t m = uniform64(lower_bound(key_b, lb, n_rows_b - lb, q + 1) - lb);
+    const auto [la, n, lb, m] = site_runs(key_a, n_rows_a, key_b, n_rows_b, site_key[t]);
     int64_t *counts = out_counts + (size_t)t * N_COUNTS;
     double *fit = out_fit + (size_t)t * N_FIT;
     if (lane == 0) {
@@ -313,19 +301,16 @@ extern "C" int nvk_site_mixture_tests_dev(nvk_ctx *ctx, int64_t n_rows_a, const 
                                           const int64_t *site_key, int iterations, double min_sd_ratio,
                                           int64_t *out_counts, double *out_fit) {
   const char *what = "nvk_site_mixture_tests_dev";
-  if (!ctx || n_rows_a < 0 || n_rows_b < 0 || n_sites < 0) {
-    nvk_set_error("%s: invalid argument (n_rows_a >= 0, n_rows_b >= 0, n_sites >= 0)", what);
-    return NVK_ERR_INVALID;
-  }
+  int rc = check_site_samples(what, ctx, n_rows_a, key_a, val_a, n_rows_b, key_b, val_b, n_sites, site_key);
+  if (rc) return rc;
   if (iterations < 1 || iterations > 1024 || !(min_sd_ratio > 0.0) || !(min_sd_ratio <= 1.0)) {
     nvk_set_error("%s: iterations %d, min_sd_ratio %g outside the served range (1 <= iterations <= 1024, 0 < "
                   "min_sd_ratio <= 1)", what, iterations, min_sd_ratio);
     return NVK_ERR_INVALID;
   }
   if (n_sites == 0) return NVK_OK;
-  if (!site_key || !out_counts || !out_fit || (n_rows_a > 0 && (!key_a || !val_a)) ||
-      (n_rows_b > 0 && (!key_b || !val_b))) {
-    nvk_set_error("%s: NULL input or output", what);
+  if (!out_counts || !out_fit) {
+    nvk_set_error("%s: NULL output", what);
     return NVK_ERR_INVALID;
   }
   NVK_HIP(hipSetDevice(ctx->device));

@@ -21,8 +21,7 @@
 // costs.  Resources on gfx950: no LDS, no scratch, no atomics; the register counts are in DESIGN.md 4.6.
 #include <math.h>
 
-#include "nvk_internal.h"
-#include "wave.h"
+#include "site_runs.h"
 
 namespace {
 
@@ -46,13 +45,6 @@ __device__ __forceinline__ int64_t count_le(const double *v, int64_t n, double x
     if (v[mid] <= x) lo = mid + 1; else hi = mid;
   }
   return lo;
-}
-
-// a value that is the same in every lane, as one the compiler knows to be (loop bounds in scalar registers)
-__device__ __forceinline__ int64_t uniform64(int64_t v) {
-  const unsigned lo = __builtin_amdgcn_readfirstlane((int)(unsigned)(uint64_t)v);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((int)(unsigned)((uint64_t)v >> 32));
-  return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
 __device__ __forceinline__ int64_t wave_max64(int64_t v) {
@@ -113,11 +105,7 @@ __global__ __launch_bounds__(NT) void site_rank_tests_kernel(int64_t n_rows_a, c
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t waves = (int64_t)gridDim.x * (NT / 64);
   for (int64_t t = (int64_t)blockIdx.x * (NT / 64) + wave; t < n_sites; t += waves) {
-    const int64_t q = site_key[t];
-    const int64_t la = lower_bound(key_a, 0, n_rows_a, q);
-    const int64_t n = uniform64(lower_bound(key_a, la, n_rows_a - la, q + 1) - la);
-    const int64_t lb = lower_bound(key_b, 0, n_rows_b, q);
-    const int64_t m = uniform64(lower_bound(key_b, lb, n_rows_b - lb, q + 1) - lb);
+    const auto [la, n, lb, m] = site_runs(key_a, n_rows_a, key_b, n_rows_b, site_key[t]);
     const double *A = val_a + la, *B = val_b + lb;
     int64_t ks_plus = 0, ks_minus = 0, u2 = 0, tie = 0;
     double ks_p = NAN;
@@ -166,14 +154,15 @@ extern "C" int nvk_site_rank_tests_dev(nvk_ctx *ctx, int64_t n_rows_a, const int
                                        int64_t *out_n_b, int64_t *out_ks_plus, int64_t *out_ks_minus, int64_t *out_u2,
                                        int64_t *out_tie, double *out_ks_p) {
   const char *what = "nvk_site_rank_tests_dev";
-  if (!ctx || n_rows_a < 0 || n_rows_b < 0 || n_sites < 0 || exact_cells < 0) {
-    nvk_set_error("%s: invalid argument (n_rows_a >= 0, n_rows_b >= 0, n_sites >= 0, exact_cells >= 0)", what);
+  int rc = check_site_samples(what, ctx, n_rows_a, key_a, val_a, n_rows_b, key_b, val_b, n_sites, site_key);
+  if (rc) return rc;
+  if (exact_cells < 0) {
+    nvk_set_error("%s: invalid argument (exact_cells >= 0)", what);
     return NVK_ERR_INVALID;
   }
   if (n_sites == 0) return NVK_OK;
-  if (!site_key || !out_n_a || !out_n_b || !out_ks_plus || !out_ks_minus || !out_u2 || !out_tie || !out_ks_p ||
-      (n_rows_a > 0 && (!key_a || !val_a)) || (n_rows_b > 0 && (!key_b || !val_b))) {
-    nvk_set_error("%s: NULL input or output", what);
+  if (!out_n_a || !out_n_b || !out_ks_plus || !out_ks_minus || !out_u2 || !out_tie || !out_ks_p) {
+    nvk_set_error("%s: NULL output", what);
     return NVK_ERR_INVALID;
   }
   NVK_HIP(hipSetDevice(ctx->device));

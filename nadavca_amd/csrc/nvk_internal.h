@@ -204,6 +204,11 @@ int nvk_fetch_offsets(nvk_ctx *ctx, const char *what, const int64_t *off, int64_
                       const char *total_name = nullptr, int64_t total = 0);
 // the model handle and the ranges of n_reads, bandwidth and min_event_length
 int check_common(nvk_model *model, int64_t n_reads, int bandwidth, int mel);
+// the per-site two-sample entries (nvk_site_rank_tests_dev, nvk_site_mixture_tests_dev): ctx, the three counts >= 0
+// and, with n_sites > 0 only, site_key and the key and values of a sample that has rows (an empty sample may be NULL)
+int check_site_samples(const char *what, nvk_ctx *ctx, int64_t n_rows_a, const int64_t *key_a, const double *val_a,
+                       int64_t n_rows_b, const int64_t *key_b, const double *val_b, int64_t n_sites,
+                       const int64_t *site_key);
 
 // ----- launchers (kernels_*.hip) ------------------------------------------------------------
 struct BatchArgs {

@@ -1,5 +1,5 @@
-// Wave64 helpers shared by the kernels: the wave-local barrier, DPP moves of a neighbour's value, butterfly
-// reductions and inclusive scans over the 64 lanes.
+// Wave64 helpers shared by the kernels: the wave-local barrier, DPP moves of a neighbour's value, a wave-uniform
+// value, butterfly reductions and inclusive scans over the 64 lanes.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,6 +27,13 @@ __device__ __forceinline__ double dpp_ror1(double v) {
   lo = __builtin_amdgcn_mov_dpp(lo, 0x13C, 0xf, 0xf, false);
   hi = __builtin_amdgcn_mov_dpp(hi, 0x13C, 0xf, 0xf, false);
   return __hiloint2double(hi, lo);
+}
+
+// a value that is the same in every lane, as one the compiler knows to be (loop bounds in scalar registers)
+__device__ __forceinline__ int64_t uniform64(int64_t v) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((int)(unsigned)(uint64_t)v);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((int)(unsigned)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
 // reductions over the wave, the result in every lane

@@ -641,6 +641,26 @@ def common_sites(key_a, key_b, min_coverage):
     return site_key, largest
 
 
+def _two_sample_sites(entry, noun, finite_only, key_a, val_a, key_b, val_b, min_coverage):
+    """What ``site_rank_tests_dev`` and ``site_mixture_tests_dev`` do before their kernel: the check of
+    ``min_coverage``, ``sort_site_rows`` per sample (``finite_only``: rows with +-inf dropped too), ``common_sites`` and
+    the 2^20 guard (``entry`` and ``noun`` name the caller and its tests in the messages).
+    -> (key_a, val_a, key_b, val_b, site_key), sorted."""
+    import torch
+    if int(min_coverage) != min_coverage or min_coverage < 1:
+        raise ValueError('%s: min_coverage %r is not an integer >= 1' % (entry, min_coverage))
+    if finite_only:
+        finite_a, finite_b = torch.isfinite(val_a), torch.isfinite(val_b)
+        key_a, val_a, key_b, val_b = key_a[finite_a], val_a[finite_a], key_b[finite_b], val_b[finite_b]
+    key_a, val_a = sort_site_rows(key_a, val_a)
+    key_b, val_b = sort_site_rows(key_b, val_b)
+    site_key, largest = common_sites(key_a, key_b, int(min_coverage))
+    if largest >= MAX_SITE_ROWS:
+        raise ValueError('%s: a site holds %d rows in the two samples together; the %s tests serve fewer than 2^20 '
+                         'per site' % (entry, largest, noun))
+    return key_a, val_a, key_b, val_b, site_key
+
+
 def site_rank_tests_dev(context, key_a, val_a, key_b, val_b, min_coverage, exact_cells):
     """Per-site rank tests between two samples' rows of ONE event column (include/nadavca_hip.h:
     nvk_site_rank_tests_dev has the contract).  key int64 (rows,) (a key < 0: not counted) and val f64 (rows,) per
@@ -652,16 +672,10 @@ def site_rank_tests_dev(context, key_a, val_a, key_b, val_b, min_coverage, exact
     ascending."""
     import torch
     lib = _lib.load()
-    if int(min_coverage) != min_coverage or min_coverage < 1:
-        raise ValueError('site_rank_tests_dev: min_coverage %r is not an integer >= 1' % (min_coverage,))
     if int(exact_cells) != exact_cells or exact_cells < 0:
         raise ValueError('site_rank_tests_dev: exact_cells %r is not an integer >= 0' % (exact_cells,))
-    key_a, val_a = sort_site_rows(key_a, val_a)
-    key_b, val_b = sort_site_rows(key_b, val_b)
-    site_key, largest = common_sites(key_a, key_b, int(min_coverage))
-    if largest >= MAX_SITE_ROWS:
-        raise ValueError('site_rank_tests_dev: a site holds %d rows in the two samples together; the rank tests serve '
-                         'fewer than 2^20 per site' % largest)
+    key_a, val_a, key_b, val_b, site_key = _two_sample_sites('site_rank_tests_dev', 'rank', False, key_a, val_a, key_b,
+                                                             val_b, min_coverage)
     n_sites = int(site_key.numel())
     dev = val_a.device
     ints = [torch.empty(n_sites, dtype=torch.int64, device=dev) for _ in range(6)]
@@ -687,19 +701,12 @@ def site_mixture_tests_dev(context, key_a, val_a, key_b, val_b, min_coverage, it
     columns as the contract lists them."""
     import torch
     lib = _lib.load()
-    if int(min_coverage) != min_coverage or min_coverage < 1:
-        raise ValueError('site_mixture_tests_dev: min_coverage %r is not an integer >= 1' % (min_coverage,))
     if int(iterations) != iterations or not 1 <= iterations <= 1024:
         raise ValueError('site_mixture_tests_dev: iterations %r is not an integer in 1 .. 1024' % (iterations,))
     if not 0.0 < min_sd_ratio <= 1.0:
         raise ValueError('site_mixture_tests_dev: min_sd_ratio %r is not in (0, 1]' % (min_sd_ratio,))
-    finite_a, finite_b = torch.isfinite(val_a), torch.isfinite(val_b)
-    key_a, val_a = sort_site_rows(key_a[finite_a], val_a[finite_a])
-    key_b, val_b = sort_site_rows(key_b[finite_b], val_b[finite_b])
-    site_key, largest = common_sites(key_a, key_b, int(min_coverage))
-    if largest >= MAX_SITE_ROWS:
-        raise ValueError('site_mixture_tests_dev: a site holds %d rows in the two samples together; the mixture tests '
-                         'serve fewer than 2^20 per site' % largest)
+    key_a, val_a, key_b, val_b, site_key = _two_sample_sites('site_mixture_tests_dev', 'mixture', True, key_a, val_a,
+                                                             key_b, val_b, min_coverage)
     n_sites = int(site_key.numel())
     dev = val_a.device
     counts = torch.empty((n_sites, SITE_MIX_COUNTS), dtype=torch.int64, device=dev)

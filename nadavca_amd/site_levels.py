@@ -10,30 +10,13 @@ level; a stable sort by (position, strand); per site the count, the means and th
 contract in include/nadavca_hip.h (nvk_site_level_rows_dev) and the kernels in csrc/kernels_sitelevels.hip.  The
 statistics are numpy on the host, from moments that can be saved, merged (``SiteLevelBatch.merge``: the hook for several
 batches or ranks) and reused: a control sample is summarised once.  Single process only."""
-import os
-
 import numpy as np
 
 from . import defaults
+from .site_tests import SiteTable, _open, _same_reference, _site_key, check_site_test, contig_label, site_coordinates
 
 COLUMNS = ('level', 'stdv', 'dwell', 'resid')
 EVENT_COLUMNS = ('read', 'contig', 'position', 'strand', 'level', 'stdv', 'dwell', 'expected')
-
-
-def _open(file):
-    return open(file, 'w', newline='') if isinstance(file, (str, os.PathLike)) else file
-
-
-def _site_key(contig, position, strand, ref_len):
-    """One sortable integer per (contig, position, strand): contig-local positions are below ``ref_len``."""
-    return (np.asarray(contig, dtype=np.int64) * max(int(ref_len), 1) + np.asarray(position, dtype=np.int64)) * 2 \
-        + np.asarray(strand, dtype=np.int64)
-
-
-def _same_reference(what, a, b):
-    if a.ref_len != b.ref_len or a.contig_names != b.contig_names:
-        raise ValueError('%s: the two batches are over different references (ref_len %d / %d, contig_names %r / %r)'
-                         % (what, a.ref_len, b.ref_len, a.contig_names, b.contig_names))
 
 
 class SiteLevelBatch:
@@ -84,16 +67,12 @@ class SiteLevelBatch:
         with np.errstate(invalid='ignore', divide='ignore'):
             return np.where(self.count >= 2, np.sqrt(self.m2[:, j] / np.maximum(self.count - 1, 1)), np.nan)
 
-    def _label(self):
-        return (lambda c: str(c)) if self.contig_names is None else (lambda c: self.contig_names[c])
-
     def write_tsv(self, file):
         """Header, then one tab-separated row per site: contig (by name where the batch has names), position, strand
         (+ / -), ref, count, then mean and sd of every column (floats as ``repr`` gives them), to ``file``, a path or
         a text file."""
-        out, label = _open(file), self._label()
-        sds = [self.sd(c) for c in COLUMNS]
-        try:
+        label, sds = contig_label(self.contig_names), [self.sd(c) for c in COLUMNS]
+        with _open(file) as out:
             out.write('contig\tposition\tstrand\tref\tcount\t'
                       + '\t'.join('%s_mean\t%s_sd' % (c, c) for c in COLUMNS) + '\n')
             for t in range(len(self)):
@@ -101,9 +80,6 @@ class SiteLevelBatch:
                 out.write('%s\t%d\t%s\t%s\t%d\t%s\n' % (label(int(self.contig[t])), self.position[t],
                                                         '+-'[self.strand[t]], 'ACGT'[self.ref_base[t]],
                                                         self.count[t], stats))
-        finally:
-            if out is not file:
-                out.close()
 
     def write_events_tsv(self, file, names=None):
         """The per-read event table of a ``rows=True`` batch in the style of nanopolish ``eventalign``: header, then
@@ -111,17 +87,14 @@ class SiteLevelBatch:
         expected.  ``names[i]``: the name of ReadBatch read i (default ``'read%d' % i``)."""
         if self.events is None:
             raise ValueError('write_events_tsv: the batch carries no event table (site_levels_batch(rows=True))')
-        out, label, ev = _open(file), self._label(), self.events
+        label, ev = contig_label(self.contig_names), self.events
         name = (lambda i: 'read%d' % i) if names is None else (lambda i: names[i])
-        try:
+        with _open(file) as out:
             out.write('\t'.join(EVENT_COLUMNS) + '\n')
             out.writelines('%s\t%s\t%d\t%s\t%r\t%r\t%d\t%r\n'
                            % (name(int(ev['read'][t])), label(int(ev['contig'][t])), ev['position'][t],
                               '+-'[ev['strand'][t]], float(ev['level'][t]), float(ev['stdv'][t]), ev['dwell'][t],
                               float(ev['expected'][t])) for t in range(int(ev['read'].size)))
-        finally:
-            if out is not file:
-                out.close()
 
     def save(self, path):
         """Everything into one ``.npz`` (``load`` reads it back): a control sample is summarised once."""
@@ -222,21 +195,12 @@ def site_levels_batch(read_batch, aligner, kmer_model=defaults.KMER_MODEL_FILE, 
     flat = to_host(torch.cat(parts))
     table = flat[:n_sites * (2 + 2 * V)].reshape(n_sites, 2 + 2 * V)
     rest = flat[table.size:]
-
-    def coordinates(keys):
-        P = keys >> 1
-        contig = np.zeros(P.size, dtype=np.int32)
-        if refset is not None:
-            c, P = refset.locate(P)
-            contig = c.astype(np.int32)
-        return contig, P, (keys & 1).astype(np.int8)
-
     site_key = table[:, 0].astype(np.int64)
-    contig, position, strand = coordinates(site_key)
+    contig, position, strand = site_coordinates(site_key, refset)
     events = None
     if rows:
         et = rest[:n_events * 6].reshape(n_events, 6)
-        e_contig, e_position, e_strand = coordinates(et[:, 1].astype(np.int64))
+        e_contig, e_position, e_strand = site_coordinates(et[:, 1].astype(np.int64), refset)
         col = lambda j: np.ascontiguousarray(et[:, j])
         events = dict(read=et[:, 0].astype(np.int64), contig=e_contig, position=e_position, strand=e_strand,
                       level=col(2), stdv=col(3), dwell=et[:, 4].astype(np.int64), expected=col(5))
@@ -246,38 +210,20 @@ def site_levels_batch(read_batch, aligner, kmer_model=defaults.KMER_MODEL_FILE, 
                           np.ascontiguousarray(table[:, 2 + V:]), L, names, status, sa.live.cpu().numpy(), events)
 
 
-class SiteComparison:
+class SiteComparison(SiteTable):
     """What ``compare_site_levels`` returns.  Row arrays, one row per (contig, position, strand) that both batches
     hold with count >= min_coverage, in the batches' order: ``contig``, ``position``, ``strand``, ``ref_base``,
     ``n_a``, ``n_b``, ``mean_a``, ``mean_b``, ``delta`` = mean_b - mean_a, Welch's ``t``, its Welch-Satterthwaite
     ``df``, the two-sided ``p`` and ``peak``; ``column``: what was compared; ``contig_names`` as the batches'."""
 
+    _FIELDS = ('contig', 'position', 'strand', 'ref_base', 'n_a', 'n_b', 'mean_a', 'mean_b', 'delta', 't', 'df', 'p',
+               'peak')
+    _INTS = ('n_a', 'n_b', 'peak')
+
     def __init__(self, contig, position, strand, ref_base, n_a, n_b, mean_a, mean_b, delta, t, df, p, peak, column,
                  contig_names=None):
-        self.contig, self.position, self.strand, self.ref_base = contig, position, strand, ref_base
-        self.n_a, self.n_b, self.mean_a, self.mean_b, self.delta = n_a, n_b, mean_a, mean_b, delta
-        self.t, self.df, self.p, self.peak = t, df, p, peak
-        self.column, self.contig_names = column, contig_names
-
-    def __len__(self):
-        return int(self.position.size)
-
-    def write_tsv(self, file):
-        """Header, then one tab-separated row per site: contig, position, strand (+ / -), ref, n_a, n_b, mean_a,
-        mean_b, delta, t, df, p (floats as ``repr`` gives them) and peak (0 / 1), to ``file``, a path or a text
-        file."""
-        out = _open(file)
-        label = (lambda c: str(c)) if self.contig_names is None else (lambda c: self.contig_names[c])
-        try:
-            out.write('contig\tposition\tstrand\tref\tn_a\tn_b\tmean_a\tmean_b\tdelta\tt\tdf\tp\tpeak\n')
-            out.writelines('%s\t%d\t%s\t%s\t%d\t%d\t%r\t%r\t%r\t%r\t%r\t%r\t%d\n'
-                           % (label(int(self.contig[i])), self.position[i], '+-'[self.strand[i]],
-                              'ACGT'[self.ref_base[i]], self.n_a[i], self.n_b[i], float(self.mean_a[i]),
-                              float(self.mean_b[i]), float(self.delta[i]), float(self.t[i]), float(self.df[i]),
-                              float(self.p[i]), self.peak[i]) for i in range(len(self)))
-        finally:
-            if out is not file:
-                out.close()
+        super().__init__(column, contig_names, **dict(zip(self._FIELDS, (
+            contig, position, strand, ref_base, n_a, n_b, mean_a, mean_b, delta, t, df, p, peak))))
 
 
 def local_peaks(score, contig, position, strand, reach):
@@ -315,11 +261,7 @@ def compare_site_levels(a, b, column='level', min_coverage=5, reach=5):
     -> SiteComparison."""
     from scipy.special import stdtr
     _same_reference('compare_site_levels', a, b)
-    j = SiteLevelBatch.column_index(column)
-    if int(min_coverage) != min_coverage or min_coverage < 1:
-        raise ValueError('compare_site_levels: min_coverage %r is not an integer >= 1' % (min_coverage,))
-    if int(reach) != reach or reach < 0:
-        raise ValueError('compare_site_levels: reach %r is not an integer >= 0' % (reach,))
+    j = check_site_test('compare_site_levels', column, min_coverage, reach)
     ka = _site_key(a.contig, a.position, a.strand, a.ref_len)
     kb = _site_key(b.contig, b.position, b.strand, b.ref_len)
     _, ia, ib = np.intersect1d(ka, kb, assume_unique=True, return_indices=True)

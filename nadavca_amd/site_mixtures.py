@@ -18,18 +18,19 @@ likelihood ratio does not follow chi^2_1.  Measured with the numpy restatement (
 samples N(0, 0.35^2), 3 000 sites per coverage, iterations 32): the chi^2_1 p-value of ``lrt`` is below 0.01 on 0.035
 to 0.062 of the null sites, 3 to 6 times the nominal level, where the score test gives p <= 0.01 on 0.0077 to 0.0083
 of them at 10, 20 and 40 events per sample (p <= 0.05 on 0.045 to 0.055, p <= 0.001 on at most 0.0007)."""
+import sys
+
 import numpy as np
 
 from . import defaults
-from .site_levels import SiteLevelBatch, _open, _same_reference, _site_key, local_peaks
-from .site_ranks import _event_column, _sample_rows
+from .device import SITE_MIX_COUNTS, SITE_MIX_FIT
+from .site_levels import local_peaks
+from .site_tests import SiteTable, copy_back, host_table_tests, resident_tests, upload_rows
 
-_FIELDS = ('contig', 'position', 'strand', 'ref_base', 'n_a', 'n_b', 'fitted', 'mean_0', 'sd_0', 'mean_1', 'sd_1',
-           'rate_a', 'rate_b', 'delta_rate', 'll_one', 'll_shared', 'll_free', 'lrt', 'z', 'p', 'peak')
-N_COUNTS, N_FIT = 5, 17
+_THIS = sys.modules[__name__]        # what the shared layer takes as ``op``
 
 
-class SiteMixtureComparison:
+class SiteMixtureComparison(SiteTable):
     """What ``compare_site_mixtures`` and ``site_mixture_tests_batch`` return.  Row arrays, one row per (contig,
     position, strand) with at least ``min_coverage`` finite events in both samples, ascending in (contig, position,
     strand): ``contig``, ``position``, ``strand``, ``ref_base``, ``n_a``, ``n_b``;
@@ -46,45 +47,21 @@ class SiteMixtureComparison:
     ``steps_shared``, ``steps_free``: the EM steps run.  ``column``: what was compared; ``contig_names`` as the
     batches'."""
 
+    _FIELDS = ('contig', 'position', 'strand', 'ref_base', 'n_a', 'n_b', 'fitted', 'mean_0', 'sd_0', 'mean_1', 'sd_1',
+               'rate_a', 'rate_b', 'delta_rate', 'll_one', 'll_shared', 'll_free', 'lrt', 'z', 'p', 'peak')
+    _INTS = ('n_a', 'n_b', 'fitted', 'peak')
+
     def __init__(self, column, contig_names=None, steps_shared=None, steps_free=None, **rows):
-        for f in _FIELDS:
-            setattr(self, f, rows[f])
-        self.column, self.contig_names = column, contig_names
+        super().__init__(column, contig_names, **rows)
         self.steps_shared, self.steps_free = steps_shared, steps_free
 
-    def __len__(self):
-        return int(self.position.size)
 
-    def write_tsv(self, file):
-        """Header, then one tab-separated row per site: contig, position, strand (+ / -), ref, n_a, n_b, fitted
-        (0 / 1), mean_0, sd_0, mean_1, sd_1, rate_a, rate_b, delta_rate, ll_one, ll_shared, ll_free, lrt, z, p (floats
-        as ``repr`` gives them), peak (0 / 1), to ``file``, a path or a text file."""
-        out = _open(file)
-        label = (lambda c: str(c)) if self.contig_names is None else (lambda c: self.contig_names[c])
-        floats = _FIELDS[7:20]
-        try:
-            out.write('contig\tposition\tstrand\tref\tn_a\tn_b\tfitted\t' + '\t'.join(floats) + '\tpeak\n')
-            out.writelines('%s\t%d\t%s\t%s\t%d\t%d\t%d\t%s\t%d\n'
-                           % (label(int(self.contig[i])), self.position[i], '+-'[self.strand[i]],
-                              'ACGT'[self.ref_base[i]], self.n_a[i], self.n_b[i], self.fitted[i],
-                              '\t'.join(repr(float(getattr(self, f)[i])) for f in floats), self.peak[i])
-                           for i in range(len(self)))
-        finally:
-            if out is not file:
-                out.close()
-
-
-def _check(what, column, min_coverage, reach, iterations, min_sd_ratio):
-    j = SiteLevelBatch.column_index(column)
-    if int(min_coverage) != min_coverage or min_coverage < 1:
-        raise ValueError('%s: min_coverage %r is not an integer >= 1' % (what, min_coverage))
-    if int(reach) != reach or reach < 0:
-        raise ValueError('%s: reach %r is not an integer >= 0' % (what, reach))
+def _check(what, iterations, min_sd_ratio):
     if int(iterations) != iterations or not 1 <= iterations <= 1024:
         raise ValueError('%s: iterations %r is not an integer in 1 .. 1024' % (what, iterations))
     if not 0.0 < min_sd_ratio <= 1.0:
         raise ValueError('%s: min_sd_ratio %r is not in (0, 1]' % (what, min_sd_ratio))
-    return j
+    return int(iterations), float(min_sd_ratio)
 
 
 def _statistics(counts, fit):
@@ -121,32 +98,21 @@ def _comparison(column, contig_names, contig, position, strand, ref_base, reach,
 def _empty(column, contig_names):
     z = lambda dt: np.zeros(0, dtype=dt)
     return _comparison(column, contig_names, z(np.int32), z(np.int64), z(np.int8), z(np.int8), 0,
-                       np.zeros((0, N_COUNTS), dtype=np.int64), np.zeros((0, N_FIT)))
+                       np.zeros((0, SITE_MIX_COUNTS), dtype=np.int64), np.zeros((0, SITE_MIX_FIT)))
 
 
 def _on_device(context, key_a, val_a, key_b, val_b, min_coverage, iterations, min_sd_ratio):
     """One ``device.site_mixture_tests_dev`` call over device tensors and one copy back: -> (site_key int64 (sites,),
     counts int64 (sites, 5), fit f64 (sites, 17)) numpy arrays (the floats cross as their bits beside the integers:
     184 B per site)."""
-    import torch
-    from .device import site_mixture_tests_dev, to_host
-    site_key, counts, fit = site_mixture_tests_dev(context, key_a, val_a, key_b, val_b, min_coverage, iterations,
-                                                   min_sd_ratio)
-    n = int(site_key.numel())
-    flat = to_host(torch.cat([site_key, counts.reshape(-1), fit.reshape(-1).view(torch.int64)]))
-    return (np.ascontiguousarray(flat[:n]), np.ascontiguousarray(flat[n:n + N_COUNTS * n]).reshape(n, N_COUNTS),
-            np.ascontiguousarray(flat[n + N_COUNTS * n:]).view(np.float64).reshape(n, N_FIT))
+    from .device import site_mixture_tests_dev
+    return copy_back(site_mixture_tests_dev(context, key_a, val_a, key_b, val_b, min_coverage, iterations,
+                                            min_sd_ratio))
 
 
 def _upload_and_test(key_a, val_a, key_b, val_b, min_coverage, iterations, min_sd_ratio):
     """Host rows (key int64, one f64 column) of the two samples to the default context's GPU, then ``_on_device``."""
-    import torch
-    from . import _lib
-    context = _lib.default_context()
-    dev = torch.device('cuda', context.device)
-    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
-    return _on_device(context, up(key_a, np.int64), up(val_a, np.float64), up(key_b, np.int64), up(val_b, np.float64),
-                      min_coverage, iterations, min_sd_ratio)
+    return _on_device(*upload_rows(key_a, val_a, key_b, val_b), min_coverage, iterations, min_sd_ratio)
 
 
 def compare_site_mixtures(a, b, column='level', min_coverage=5, reach=5, iterations=32, min_sd_ratio=0.1):
@@ -164,28 +130,8 @@ def compare_site_mixtures(a, b, column='level', min_coverage=5, reach=5, iterati
     deviations, 40 events per sample give p <= 1e-3 on 0.99 of the sites, 10 give p <= 1e-2 on about a third.  A batch
     without an event table, different ``ref_len`` or ``contig_names``, a column that is not one, min_coverage < 1,
     reach < 0, iterations or min_sd_ratio outside their ranges: ValueError.  -> SiteMixtureComparison."""
-    what = 'compare_site_mixtures'
-    for x in (a, b):
-        if x.events is None:
-            raise ValueError('%s: a batch carries no event table (site_levels_batch(rows=True))' % what)
-    _same_reference(what, a, b)
-    _check(what, column, min_coverage, reach, iterations, min_sd_ratio)
-    if a.events['read'].size == 0 or b.events['read'].size == 0:
-        return _empty(column, a.contig_names)
-    key = lambda x: _site_key(x.events['contig'], x.events['position'], x.events['strand'], x.ref_len)
-    site_key, counts, fit = _upload_and_test(key(a), _event_column(a, column), key(b), _event_column(b, column),
-                                             int(min_coverage), int(iterations), float(min_sd_ratio))
-    L = max(a.ref_len, 1)
-    contig, position, strand = ((site_key >> 1) // L).astype(np.int32), (site_key >> 1) % L, \
-        (site_key & 1).astype(np.int8)
-    rows_key = _site_key(a.contig, a.position, a.strand, a.ref_len)
-    order = np.argsort(rows_key, kind='stable')
-    at = np.minimum(np.searchsorted(rows_key[order], site_key), max(rows_key.size - 1, 0))
-    if site_key.size and (rows_key.size == 0 or not np.array_equal(rows_key[order][at], site_key)):
-        raise ValueError('%s: the event table of the first batch holds sites that its rows do not' % what)
-    ref_base = a.ref_base[order][at].astype(np.int8) if site_key.size else np.zeros(0, dtype=np.int8)
-    return _comparison(column, a.contig_names, contig, position.astype(np.int64), strand, ref_base, int(reach), counts,
-                       fit)
+    return host_table_tests(_THIS, 'compare_site_mixtures', a, b, column, min_coverage, reach, iterations,
+                            min_sd_ratio)
 
 
 def site_mixture_tests_batch(read_batch_a, read_batch_b, aligner, kmer_model=defaults.KMER_MODEL_FILE,
@@ -199,34 +145,5 @@ def site_mixture_tests_batch(read_batch_a, read_batch_b, aligner, kmer_model=def
     ``trim``: as for ``site_levels_batch``.  The rows equal those of ``compare_site_mixtures(site_levels_batch(a,
     rows=True), site_levels_batch(b, rows=True))``; what its docstring says about calls, the normal approximation,
     ``lrt``, coverage and independence holds here too.  -> SiteMixtureComparison."""
-    what = 'site_mixture_tests_batch'
-    if int(trim) != trim or trim < 0:
-        raise ValueError('%s: trim %r is not an integer >= 0' % (what, trim))
-    j = _check(what, column, min_coverage, reach, iterations, min_sd_ratio)
-    from .batchflow import load_config, load_kmer_model
-    from .refset import ReferenceSet
-    aligner_a, aligner_b = aligner if isinstance(aligner, (tuple, list)) and len(aligner) == 2 else (aligner, aligner)
-    reference_num = np.ascontiguousarray(aligner_a.reference_num, dtype=np.int32).reshape(-1)
-    if aligner_b is not aligner_a and not np.array_equal(reference_num, np.asarray(aligner_b.reference_num).reshape(-1)):
-        raise ValueError('%s: the two aligners are over different references' % what)
-    kmer_model, config = load_kmer_model(kmer_model), load_config(config)
-    key_a, val_a, stage_a = _sample_rows(read_batch_a, aligner_a, kmer_model, config, renorm_rounds, trim, j)
-    key_b, val_b, stage = _sample_rows(read_batch_b, aligner_b, kmer_model, config, renorm_rounds, trim, j)
-    names = stage.contig_names()
-    if stage_a.contig_names() != names:
-        raise ValueError('%s: the two aligners are over different references (contig names %r / %r)'
-                         % (what, stage_a.contig_names(), names))
-    del stage_a
-    if key_a is None or key_b is None:
-        return _empty(column, names)
-    refset = stage.reference if isinstance(stage.reference, ReferenceSet) else None
-    del stage
-    site_key, counts, fit = _on_device(kmer_model.context, key_a, val_a, key_b, val_b, int(min_coverage),
-                                       int(iterations), float(min_sd_ratio))
-    position = site_key >> 1
-    contig = np.zeros(position.size, dtype=np.int32)
-    if refset is not None:
-        c, position = refset.locate(position)
-        contig = c.astype(np.int32)
-    return _comparison(column, names, contig, position.astype(np.int64), (site_key & 1).astype(np.int8),
-                       reference_num[site_key >> 1].astype(np.int8), int(reach), counts, fit)
+    return resident_tests(_THIS, 'site_mixture_tests_batch', read_batch_a, read_batch_b, aligner, kmer_model, config,
+                          renorm_rounds, trim, column, min_coverage, reach, iterations, min_sd_ratio)

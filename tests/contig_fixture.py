@@ -1,7 +1,9 @@
 """The multi-contig fixture of tests/test_contigs_cpu.py and tests/test_gpu_contigs.py: five contigs — 10 000, 4 000
 and 400 bases with 48 simulated reads each (``synthetic.make_read_batch``, seeds 31, 32, 33; the reads of the 400-base
 contig cover it end to end, so they sit flush against both of its joins), then one of 9 bases (shorter than k) and one
-of length 0, which no read comes from.  Truth: each read's contig and the per-contig ``SyntheticBatchAligner`` pairs."""
+of length 0, which no read comes from.  Truth: each read's contig and the per-contig ``SyntheticBatchAligner`` pairs.
+Also ``two_contig_samples``, the two samples over two contigs of tests/test_gpu_site_ranks.py and
+tests/test_gpu_site_mixtures.py."""
 import numpy as np
 
 NAMES = ['chrA', 'chrB', 'flush400', 'tiny9', 'empty']
@@ -32,6 +34,23 @@ def concat_alignments(bas, contig=None, shift=None):
     c = None if contig is None else np.concatenate([np.full(b.reverse.size, ci, np.int32) for ci, b in zip(contig, bas)])
     return BaseAlignmentBatch(np.concatenate([b.read_idx for b in bas]), np.concatenate(ref), off,
                               np.concatenate([b.reverse for b in bas]), contig=c)
+
+
+def two_contig_samples(model5):
+    """The input of the site tests' two-contig cases: per sample (unmodified; 0.3 of the CG sites modified) 150 reads
+    of a 2 000-base contig and 100 of a 1 200-base one in one ReadBatch, and ONE ``SeedAligner`` over the
+    ``ReferenceSet`` of the two.  -> ([ReadBatch A, ReadBatch B], the contigs' codes, their names, the aligner)"""
+    from nadavca_amd import ReferenceSet, SeedAligner, synthetic
+    shapes = ((150, 41, 2000), (100, 42, 1200))                  # reads per sample, genome seed, bases
+    samples, contigs = [], None
+    for fraction, read_seed in ((0.0, 111), (0.3, 211)):
+        parts = [synthetic.make_modified_read_batch(n, model5, seed=seed, modified_fraction=fraction, genome_length=g,
+                                                    length=200, spread=20, read_seed=read_seed + seed)
+                 for n, seed, g in shapes]
+        contigs = [p[2] for p in parts]
+        samples.append(concat_batches([p[0] for p in parts]))
+    names = ['chrA', 'chrB']
+    return samples, contigs, names, SeedAligner(ReferenceSet.from_arrays(names, contigs))
 
 
 class ContigFixture:

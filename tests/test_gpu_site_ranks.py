@@ -113,20 +113,9 @@ def test_planted_sites_are_found(world, compared):
 def test_two_contigs_with_one_seed_aligner(world):
     """Both samples through ONE ``SeedAligner`` over a ``ReferenceSet`` of two contigs: named, contig-local rows, and
     the resident path equal to the host-table path in every array."""
-    from contig_fixture import concat_batches
-    from nadavca_amd import ReferenceSet, SeedAligner, compare_site_ranks, site_levels_batch, site_rank_tests_batch, \
-        synthetic
-    model5 = site_levels_ref.model5()
-    shapes = ((150, 41, 2000), (100, 42, 1200))                  # reads per sample, genome seed, bases
-    samples, contigs = [], None
-    for fraction, read_seed in ((0.0, 111), (0.3, 211)):
-        parts = [synthetic.make_modified_read_batch(n, model5, seed=seed, modified_fraction=fraction, genome_length=g,
-                                                    length=200, spread=20, read_seed=read_seed + seed)
-                 for n, seed, g in shapes]
-        contigs = [p[2] for p in parts]
-        samples.append(concat_batches([p[0] for p in parts]))
-    names = ['chrA', 'chrB']
-    aligner = SeedAligner(ReferenceSet.from_arrays(names, contigs))
+    from contig_fixture import two_contig_samples
+    from nadavca_amd import compare_site_ranks, site_levels_batch, site_rank_tests_batch
+    samples, contigs, names, aligner = two_contig_samples(site_levels_ref.model5())
     km, config = world['km'], world['config']
     got = site_rank_tests_batch(samples[0], samples[1], aligner, km, config, trim=TRIM, column='resid', min_coverage=5)
     a, b = (site_levels_batch(rb, aligner, km, config, trim=TRIM, rows=True) for rb in samples)

@@ -18,7 +18,7 @@ from nadavca_amd import (compare_site_ranks, defaults, dtw, kmer_train, site_lev
                          site_rank_tests_batch, synthetic)
 from nadavca_amd.batchflow import load_config  # noqa: E402
 from nadavca_amd.device import common_sites, site_rank_tests_dev, sort_site_rows  # noqa: E402
-from nadavca_amd.site_ranks import _sample_rows  # noqa: E402
+from nadavca_amd.site_tests import sample_rows  # noqa: E402
 
 n_reads = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
 G = int(sys.argv[2]) if len(sys.argv) > 2 else 100000
@@ -91,7 +91,7 @@ print('%d sites tested, median coverage %d / %d, largest %d / %d; %d with KS p <
 del a, b
 
 j = 0       # column 'level'
-(key_a, val_a, _), (key_b, val_b, _) = (_sample_rows(rb, al, km, config, defaults.RENORM_ROUNDS, TRIM, j)
+(key_a, val_a, _), (key_b, val_b, _) = (sample_rows(rb, al, km, config, defaults.RENORM_ROUNDS, TRIM, j)
                                         for rb, al in ((rb_a, al_a), (rb_b, al_b)))
 rows = int(key_a.numel() + key_b.numel())
 for rep in range(3):
