@@ -599,6 +599,63 @@ int nvk_allele_solve_dev(nvk_ctx *ctx, int64_t n_rows, int64_t ref_len, int alph
                          const double *val, const int32_t *ref_codes, double *out_fraction, double *out_lrt,
                          double *out_ll_half, double *out_ll_full, int64_t *out_coverage);
 
+/* Phasing of heterozygous sites and haplotype tags of reads (nadavca_amd/phase.py: phase_reads_batch).  THE CONTRACT.
+ * The library is built with -ffp-contract=off: every expression below is a rounded operation in the order written.
+ *   sites      s = 0 .. S-1, each a global position P_s (strictly ascending) and ONE alternative base b_s, chosen by
+ *              the caller on the host
+ *   evidence   e_is = min(max(d_is, -clip), clip), d_is the value nvk_allele_rows_dev writes for (read i, P_s, forward
+ *              column b_s); -inf (and a value that is not a number) gives -clip.  Read i has evidence at s only where
+ *              the key of its read-major row of P_s equals P_s.
+ *   links      for s >= 1 with chain_s != 0: over the reads with evidence at both s - 1 and s (the shared reads), in
+ *              ascending read index, link_s = sum [ lae(e1 + e2, 0) - lae(e1, e2) ], lae(a, b) = max(a, b) +
+ *              log1p(exp(-|a - b|)): the log-likelihood ratio of "both alternatives on one haplotype" against "on
+ *              different ones" with the read's haplotype summed out at 1/2 : 1/2.  shared_s = their number.  The sum
+ *              runs over the rows of site s in key order, 64 interleaved partial sums (row j of the site goes to sum
+ *              j mod 64, ascending j; a row that is not shared adds +0.0) which wave_sum's butterfly adds up.  Site 0
+ *              and every site with chain_s == 0 (the caller clears it at a contig's first site) get link 0, shared 0.
+ *   blocks     (integer work, done by the caller on the device) s is joined to s - 1 iff chain_s, shared_s >=
+ *              min_shared and |link_s| >= min_link; otherwise it opens a block.  block_s = the index of the block's
+ *              first site.  sigma = +1 there, then sigma_s = sigma_{s-1} * (link_s > 0 ? +1 : -1): +1 says that the
+ *              alternative of s lies on the haplotype that carries the alternative of the block's first site,
+ *              haplotype 1 of the block.
+ *   tag        per read, its sites with evidence in ascending s; those of one block form a run with H = the left to
+ *              right double sum of sigma_s * e_is starting from 0.0.  The read's block is the run with the largest |H|,
+ *              the first on ties: read_block (-1 for a read without a site), read_llr = H, read_sites = the length of
+ *              that run.  Haplotype 1 if H > 0, 2 if H < 0, else none.
+ *   vote       per site, leave-one-out: over the site's rows in key order whose read has read_block == block_s,
+ *              h = read_llr_i - sigma_s * e_is; rows with h == 0 do not count; vote_s = sum sign(h) * e_is in the
+ *              64-partial order of the links (a row that does not count adds +0.0); n_agree / n_against = the counted
+ *              rows with sign(h) * sigma_s * e_is above / below 0.
+ *   refinement (the caller's loop) `rounds` times: tag, vote, flip every sigma_s with vote_s * sigma_s < 0 at once,
+ *              then multiply every block by its first site's sigma; a last tag and vote give the outputs.  Blocks are
+ *              neither merged nor split.
+ * The site entries work on the rows in STABLE key order as nvk_allele_solve_dev takes them: val f64[n_rows * alphabet],
+ * row_read i64[n_rows] the read index of every sorted row (ascending inside a site because the sort is stable), and per
+ * site its range of rows site_lo .. site_hi i64[n_sites] (inside 0 .. n_rows, hi >= lo), site_alt i32 in
+ * 0 .. alphabet-1 (a site with another value gets zeros).  nvk_phase_links_dev: chain i32[n_sites]; writes out_link
+ * f64 and out_shared i64, every entry.  nvk_phase_votes_dev: site_block i64, site_sigma i32 (+1 / -1), read_block i64
+ * and read_llr f64 as nvk_phase_tag_dev wrote them (row_read indexes them); writes out_vote f64, out_agree and
+ * out_against i64, every entry.
+ * nvk_phase_tag_dev works on the READ-MAJOR key and val of nvk_allele_rows_dev with that call's ref_off (copied to the
+ * host and checked: starts at 0, never decreases), chunk_start and reverse, and site_pos i64[n_sites]: a read's sites are
+ * those with chunk_start <= P_s < chunk_start + R, the row of P_s is ref_off[i] + p with p = P_s - chunk_start for a
+ * forward read and R - 1 - (P_s - chunk_start) for a reverse one; forward columns need no flip.  It writes out_block
+ * i64, out_llr f64 and out_sites i64 [n_reads], every entry.
+ * No atomics: the same bits on every run.  The launches are timed under NVK_K_ALLELE.  n_sites == 0 launches nothing
+ * (and writes nothing).  2 <= alphabet <= 8, 0 < clip < inf.  NVK_ERR_INVALID for bad arguments or offsets or a NULL
+ * array.  Device pointers. */
+int nvk_phase_links_dev(nvk_ctx *ctx, int64_t n_sites, int alphabet, const int64_t *site_lo, const int64_t *site_hi,
+                        const int32_t *site_alt, const int32_t *chain, const int64_t *row_read, const double *val,
+                        double clip, double *out_link, int64_t *out_shared);
+int nvk_phase_tag_dev(nvk_ctx *ctx, int64_t n_reads, int64_t n_sites, int alphabet, const int64_t *ref_off,
+                      const int64_t *chunk_start, const int32_t *reverse, const int64_t *key, const double *val,
+                      const int64_t *site_pos, const int32_t *site_alt, const int64_t *site_block,
+                      const int32_t *site_sigma, double clip, int64_t *out_block, double *out_llr, int64_t *out_sites);
+int nvk_phase_votes_dev(nvk_ctx *ctx, int64_t n_sites, int alphabet, const int64_t *site_lo, const int64_t *site_hi,
+                        const int32_t *site_alt, const int64_t *site_block, const int32_t *site_sigma,
+                        const int64_t *row_read, const double *val, const int64_t *read_block, const double *read_llr,
+                        double clip, double *out_vote, int64_t *out_agree, int64_t *out_against);
+
 /* Model-free per-site summaries (nadavca_amd/site_levels.py: site_levels_batch): the pile-up of the reads' event levels
  * over every reference position and strand.  THE CONTRACT.  The library is built with -ffp-contract=off: every
  * expression below is a rounded operation in the order written.  Inputs are one aligned batch in the flat layout above:

@@ -92,6 +92,9 @@ SIGNATURES = {
     'nvk_kmer_reduce_dev': (_int, [_vp, _i64, _i64] + [_vp] * 6),
     'nvk_allele_rows_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 6 + [_dbl, _i64, _vp, _vp]),
     'nvk_allele_solve_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 8),
+    'nvk_phase_links_dev': (_int, [_vp, _i64, _int] + [_vp] * 6 + [_dbl, _vp, _vp]),
+    'nvk_phase_tag_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 9 + [_dbl, _vp, _vp, _vp]),
+    'nvk_phase_votes_dev': (_int, [_vp, _i64, _int] + [_vp] * 9 + [_dbl, _vp, _vp, _vp]),
     'nvk_site_level_rows_dev': (_int, [_vp, _i64, _i64] + [_vp] * 8 + [_int, _i64, _vp, _vp]),
     'nvk_site_moments_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 5),
     'nvk_site_rank_tests_dev': (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64] + [_vp] * 7),

@@ -143,21 +143,26 @@ def estimate_allele_fractions_batch(reference_num, read_batch, config=defaults.C
 
 
 def allele_fractions_of_rows(stage, ll, status, reference_num, refset, kmer_model, event_length=1.0, min_coverage=1,
-                             min_fraction=0.0, threshold=None, keep='positive'):
+                             min_fraction=0.0, threshold=None, keep='positive', sorted_rows=None):
     """The back half of ``estimate_allele_fractions_batch``, from the log-likelihood rows ``ll`` and the per-read
     ``status`` of a ``batchflow.DeviceStage`` with live reads (device tensors, as ``batchflow.likelihood_rows`` returns
     them): the ``device.allele_fractions_dev`` call, the row selection on the device and the one copy to the host.
     ``reference_num``: int32 base codes of the whole reference; ``refset``: its ReferenceSet or None; the other
-    arguments as checked there.  -> AlleleFractionBatch."""
+    arguments as checked there.  ``sorted_rows``: (sorted_key, sorted_val) of ``device.allele_sorted_rows_dev`` for the
+    same rows and ``event_length``, from a caller that needs the sorted rows itself (``phase.phase_of_rows``); the
+    rows are then not made again.  -> AlleleFractionBatch."""
     import torch
-    from .device import allele_fractions_dev, to_host
+    from .device import allele_fractions_dev, allele_solve_dev, to_host
     sa, context = stage.sa, kmer_model.context
     device = torch.device('cuda', context.device)
     L = reference_num.size
     names = None if refset is None else list(refset.names)
     codes = torch.from_numpy(reference_num).to(device)
-    fraction, lrt, half, full, cov = allele_fractions_dev(context, stage.dbatch, ll, sa.ref_start.contiguous(),
-                                                          sa.reverse.to(torch.int32), status, event_length, codes)
+    if sorted_rows is not None:
+        fraction, lrt, half, full, cov = allele_solve_dev(context, sorted_rows[0], sorted_rows[1], codes)
+    else:
+        fraction, lrt, half, full, cov = allele_fractions_dev(context, stage.dbatch, ll, sa.ref_start.contiguous(),
+                                                              sa.reverse.to(torch.int32), status, event_length, codes)
     # everything per (position, base) on the device; only the kept rows and the coverage cross to the host
     contig = None if refset is None else refset.locate(torch.arange(L, dtype=torch.int64, device=device))[0]
     near = neighbour_max(lrt.max(dim=1).values, contig, kmer_model.get_k() - 1)

@@ -549,11 +549,120 @@ def allele_fractions_dev(context, dbatch, ll, chunk_start, reverse, status, even
     plumbing), the per-position solve in another (include/nadavca_hip.h: nvk_allele_rows_dev has the contract).
     chunk_start i64 (n,), reverse i32 (n,), status i32 (n,) or None, ref_codes i32 (L,): device tensors.
     -> (fraction, lrt, ll_half, ll_full f64 (L, alphabet), coverage int64 (L,)) device tensors."""
+    _, val, sorted_key, order = allele_sorted_rows_dev(context, dbatch, ll, chunk_start, reverse, status, event_length,
+                                                       int(ref_codes.numel()))
+    return allele_solve_dev(context, sorted_key, val[order], ref_codes)
+
+
+def allele_sorted_rows_dev(context, dbatch, ll, chunk_start, reverse, status, event_length, ref_len):
+    """``allele_rows_dev`` and the stable ascending sort of its keys: -> (key, val, sorted_key, order) device tensors,
+    ``key`` and ``val`` read-major as written, ``sorted_key = key[order]``.  ``val[order]`` is what
+    ``allele_solve_dev`` and the site kernels of the phasing take."""
     import torch
-    key, val = allele_rows_dev(context, dbatch, ll, chunk_start, reverse, status, event_length,
-                               int(ref_codes.numel()))
-    key, order = torch.sort(key, stable=True)
-    return allele_solve_dev(context, key, val[order], ref_codes)
+    key, val = allele_rows_dev(context, dbatch, ll, chunk_start, reverse, status, event_length, ref_len)
+    sorted_key, order = torch.sort(key, stable=True)
+    return key, val, sorted_key, order
+
+
+# ---- phasing and haplotype tags (nadavca_amd/phase.py; include/nadavca_hip.h: nvk_phase_links_dev) ----------------
+def phase_links_dev(context, site_lo, site_hi, site_alt, chain, row_read, sorted_val, clip):
+    """Per site: (link f64 (S,), shared int64 (S,)) device tensors (nvk_phase_links_dev).  site_lo / site_hi i64 (S,):
+    the sites' ranges in the sorted rows; site_alt, chain i32 (S,); row_read i64 (rows,): the read of every sorted row;
+    sorted_val f64 (rows, alphabet)."""
+    import torch
+    lib = _lib.load()
+    S = int(site_lo.numel())
+    link = torch.zeros(S, dtype=torch.float64, device=site_lo.device)
+    shared = torch.zeros(S, dtype=torch.int64, device=site_lo.device)
+    _lib.check(lib.nvk_phase_links_dev(context.handle, S, int(sorted_val.shape[1]), _dp(site_lo), _dp(site_hi),
+                                       _dp(site_alt), _dp(chain), _dp(row_read), _dp(sorted_val), float(clip),
+                                       _dp(link), _dp(shared)), 'nvk_phase_links_dev')
+    return link, shared
+
+
+def phase_tag_dev(context, ref_off, chunk_start, reverse, key, val, site_pos, site_alt, site_block, site_sigma, clip):
+    """Per read: (read_block int64 (n,), read_llr f64 (n,), read_sites int64 (n,)) device tensors (nvk_phase_tag_dev)
+    from the READ-MAJOR ``key`` / ``val`` of ``allele_rows_dev``; -1 / 0 / 0 for a read without a site.  ref_off i64
+    (n + 1,), chunk_start i64 (n,), reverse i32 (n,); site_pos, site_block i64 (S,), site_alt, site_sigma i32 (S,)."""
+    import torch
+    lib = _lib.load()
+    n, S = int(ref_off.numel()) - 1, int(site_pos.numel())
+    dev = ref_off.device
+    block = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    llr = torch.zeros(n, dtype=torch.float64, device=dev)
+    count = torch.zeros(n, dtype=torch.int64, device=dev)
+    _lib.check(lib.nvk_phase_tag_dev(context.handle, n, S, int(val.shape[1]), _dp(ref_off), _dp(chunk_start),
+                                     _dp(reverse), _dp(key), _dp(val), _dp(site_pos), _dp(site_alt), _dp(site_block),
+                                     _dp(site_sigma), float(clip), _dp(block), _dp(llr), _dp(count)),
+               'nvk_phase_tag_dev')
+    return block, llr, count
+
+
+def phase_votes_dev(context, site_lo, site_hi, site_alt, site_block, site_sigma, row_read, sorted_val, read_block,
+                    read_llr, clip):
+    """Per site: (vote f64 (S,), n_agree int64 (S,), n_against int64 (S,)) device tensors (nvk_phase_votes_dev): the
+    leave-one-out vote of the reads tagged in the site's block.  Arguments as for ``phase_links_dev`` and as
+    ``phase_tag_dev`` returns them."""
+    import torch
+    lib = _lib.load()
+    S = int(site_lo.numel())
+    dev = site_lo.device
+    vote = torch.zeros(S, dtype=torch.float64, device=dev)
+    agree = torch.zeros(S, dtype=torch.int64, device=dev)
+    against = torch.zeros(S, dtype=torch.int64, device=dev)
+    _lib.check(lib.nvk_phase_votes_dev(context.handle, S, int(sorted_val.shape[1]), _dp(site_lo), _dp(site_hi),
+                                       _dp(site_alt), _dp(site_block), _dp(site_sigma), _dp(row_read),
+                                       _dp(sorted_val), _dp(read_block), _dp(read_llr), float(clip), _dp(vote),
+                                       _dp(agree), _dp(against)), 'nvk_phase_votes_dev')
+    return vote, agree, against
+
+
+def phase_blocks(link, shared, chain, min_shared, min_link):
+    """Blocks and starting phase from the links (integer work, torch on the tensors' device): site s is joined to
+    s - 1 iff chain, shared >= min_shared and |link| >= min_link.  -> (block int64 (S,): the index of the block's
+    first site, sigma int32 (S,): +1 at a block's first site, then sigma[s - 1] * (+1 if link > 0 else -1))."""
+    import torch
+    S = int(link.numel())
+    joined = (chain != 0) & (shared >= int(min_shared)) & (link.abs() >= float(min_link))
+    joined[:1] = False
+    idx = torch.arange(S, dtype=torch.int64, device=link.device)
+    block = torch.cummax(torch.where(joined, torch.zeros_like(idx), idx), 0).values if S else idx
+    turns = torch.cumsum((joined & ~(link > 0)).to(torch.int64), 0)
+    sigma = (1 - 2 * ((turns - turns[block]) & 1)).to(torch.int32)
+    return block, sigma
+
+
+def phase_sites_dev(context, ref_off, chunk_start, reverse, key, val, sorted_key, sorted_val, order, site_pos, site_alt,
+                    chain, clip, min_shared, min_link, rounds):
+    """The whole phasing loop on the device (include/nadavca_hip.h: nvk_phase_links_dev has the contract): links,
+    blocks and starting phase, ``rounds`` rounds of tag / vote / flip, the final tag and vote.  ``key`` / ``val``:
+    the read-major rows of ``allele_sorted_rows_dev``, ``sorted_key`` / ``order`` its sort, ``sorted_val = val[order]``;
+    site_pos i64 (S,) global and strictly ascending, site_alt i32 (S,), chain i32 (S,).  -> dict of device tensors:
+    link, shared, block, sigma, vote, n_agree, n_against (S,), read_block, read_llr, read_sites (n,) and flips
+    int64 (rounds,)."""
+    import torch
+    site_pos, site_alt, chain = site_pos.contiguous(), site_alt.contiguous(), chain.contiguous()
+    # the read of every sorted row: the last read whose offset is <= the row's read-major index
+    row_read = (torch.searchsorted(ref_off, order, right=True) - 1).contiguous()
+    site_lo = torch.searchsorted(sorted_key, site_pos).contiguous()
+    site_hi = torch.searchsorted(sorted_key, site_pos, right=True).contiguous()
+    link, shared = phase_links_dev(context, site_lo, site_hi, site_alt, chain, row_read, sorted_val, clip)
+    block, sigma = phase_blocks(link, shared, chain, min_shared, min_link)
+    flips = []
+    for r in range(int(rounds) + 1):
+        read_block, read_llr, read_sites = phase_tag_dev(context, ref_off, chunk_start, reverse, key, val, site_pos,
+                                                         site_alt, block, sigma, clip)
+        vote, agree, against = phase_votes_dev(context, site_lo, site_hi, site_alt, block, sigma, row_read, sorted_val,
+                                               read_block, read_llr, clip)
+        if r == int(rounds):
+            break
+        flip = vote * sigma < 0
+        flips.append(flip.sum())
+        sigma = torch.where(flip, -sigma, sigma)
+        sigma = (sigma * sigma[block]).contiguous()
+    flips = torch.stack(flips) if flips else torch.zeros(0, dtype=torch.int64, device=link.device)
+    return dict(link=link, shared=shared, block=block, sigma=sigma, vote=vote, n_agree=agree, n_against=against,
+                read_block=read_block, read_llr=read_llr, read_sites=read_sites, flips=flips)
 
 
 # ---- per-site event-level pile-up (nadavca_amd/site_levels.py) --------------------------------------------------
