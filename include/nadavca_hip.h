@@ -117,6 +117,16 @@ int nvk_last_retry_count(nvk_ctx *ctx, int64_t *n_reads);
  *                  kept as a safety margin around the class above.
  * CONTRACT: a read with neither NVK_TIE_ULP nor NVK_TIE_NEAR has the reference's events exactly (asserted
  * read by read in tests/test_gpu_parity_full.py on randomised models, wide bands, homopolymer-rich references).
+ * A read that carries such a bit and differs is an ARG-MAX OF THE REFERENCE'S PATH OBJECTIVE all the same: its
+ * rows are a path the reference's search allows (bands, minimum event lengths, finite posteriors), and the sum
+ * over DP rows of the log posterior boundary marginal (node.cpp:39-91) along it, evaluated in 80-bit arithmetic
+ * by the CPU restatement (oracle/: orc_path_score), reaches that of the better of the reference's double and
+ * long-double paths to within d * NVK_TIE_ULPS ulps of the reference's log score (d * 64 * 2^-52 * the largest
+ * partial sum), d the number of DP rows at which the two paths differ: each tolerant comparison of the search
+ * can cost at most one such zone, and each deviating decision leaves at least one differing row.  Proven, not
+ * assumed: tests/fuzz_cases.py::classify_difference scores every differing read of the randomised campaigns
+ * (tests/test_gpu_parity_full.py, tests/test_gpu_parity_scored.py: every built kernel variant) and fails the
+ * suite on one that loses more; the largest deficit measured is 2.5e-4 of that margin.
  * What the bits do NOT mean: that a flagged read differs.  Integer ADC samples repeat, so sequencer-shaped
  * data is full of equal and almost-equal path scores — the reference's own arithmetic meets ~25 exactly equal
  * and ~15 closer-than-2^-24 pairs of scores per config-2 read quantised to ADC steps (tests/dev/ref_tie_histogram.py)

@@ -305,13 +305,21 @@ void orc_expected_signal(void *mp, const int32_t *ref, int64_t R,
   free(owned);
 }
 
-/* ---- refine_alignment: dtw.cpp:133-228 ----------------------------------- */
-int orc_refine_alignment(void *mp, const double *sig, int64_t N64,
-                         const int32_t *ref, int64_t R64, const int32_t *cb,
-                         int64_t nb, const int32_t *ca, int64_t na,
-                         const int32_t *anc, int64_t A, int bw, int mel,
-                         int transitions, int32_t *out) {
-  const orc_model *m = (const orc_model *)mp;
+/* ---- the DP rows of refine_alignment: dtw.cpp:133-190 --------------------
+ * Bands, per-row densities and minimum event lengths, then the prefix and
+ * suffix rows.  Shared by orc_refine_alignment and orc_path_score. */
+typedef struct {
+  int N, R, rows;
+  int *bs, *be, *mels;
+  dens_t *dist;
+  row_t *pre, *suf; /* NULL when rows <= 0 */
+} refine_dp;
+
+static void refine_dp_build(refine_dp *q, const orc_model *m, const double *sig,
+                            int64_t N64, const int32_t *ref, int64_t R64,
+                            const int32_t *cb, int64_t nb, const int32_t *ca,
+                            int64_t na, const int32_t *anc, int64_t A, int bw,
+                            int mel, int transitions) {
   int N = (int)N64, R = (int)R64;
   int32_t *owned;
   seqview s = make_seq(ref, R, cb, nb, ca, na, &owned);
@@ -348,22 +356,64 @@ int orc_refine_alignment(void *mp, const double *sig, int64_t N64,
       mels[i] = mel;
     }
   }
+  free(bs0);
+  free(be0);
+  free(owned);
+
+  q->N = N;
+  q->R = R;
+  q->rows = rows;
+  q->bs = bs;
+  q->be = be;
+  q->mels = mels;
+  q->dist = dist;
+  q->pre = q->suf = NULL;
+  if (rows <= 0)
+    return;
+  row_t *pre = (row_t *)malloc(sizeof(row_t) * (size_t)rows);
+  row_t *suf = (row_t *)malloc(sizeof(row_t) * (size_t)rows);
+  pre[0] = row_new(bs[0], be[0], 0.0);
+  for (int i = 0; i + 1 < rows; i++)
+    pre[i + 1] = next_row(bs[i + 1], be[i + 1], &pre[i], &dist[i], sig, N,
+                          mels[i], 0);
+  suf[rows - 1] = row_new(bs[rows - 1], be[rows - 1], 0.0);
+  for (int i = rows - 1; i > 0; i--)
+    suf[i - 1] = next_row(bs[i - 1], be[i - 1], &suf[i], &dist[i - 1], sig, N,
+                          mels[i - 1], 1);
+  q->pre = pre;
+  q->suf = suf;
+}
+
+static void refine_dp_free(refine_dp *q) {
+  for (int r = 0; r < q->rows; r++) {
+    row_free(&q->pre[r]);
+    row_free(&q->suf[r]);
+  }
+  free(q->pre);
+  free(q->suf);
+  free(q->bs);
+  free(q->be);
+  free(q->dist);
+  free(q->mels);
+}
+
+/* ---- refine_alignment: dtw.cpp:133-228 ----------------------------------- */
+int orc_refine_alignment(void *mp, const double *sig, int64_t N64,
+                         const int32_t *ref, int64_t R64, const int32_t *cb,
+                         int64_t nb, const int32_t *ca, int64_t na,
+                         const int32_t *anc, int64_t A, int bw, int mel,
+                         int transitions, int32_t *out) {
+  refine_dp q;
+  refine_dp_build(&q, (const orc_model *)mp, sig, N64, ref, R64, cb, nb, ca, na,
+                  anc, A, bw, mel, transitions);
+  int rows = q.rows;
+  const int *bs = q.bs, *be = q.be, *mels = q.mels;
+  const row_t *pre = q.pre, *suf = q.suf;
 
   int status = 1;
   if (rows <= 0)
     goto done_early;
   {
-    row_t *pre = (row_t *)malloc(sizeof(row_t) * (size_t)rows);
-    row_t *suf = (row_t *)malloc(sizeof(row_t) * (size_t)rows);
-    pre[0] = row_new(bs[0], be[0], 0.0);
-    for (int i = 0; i + 1 < rows; i++)
-      pre[i + 1] = next_row(bs[i + 1], be[i + 1], &pre[i], &dist[i], sig, N,
-                            mels[i], 0);
-    suf[rows - 1] = row_new(bs[rows - 1], be[rows - 1], 0.0);
-    for (int i = rows - 1; i > 0; i--)
-      suf[i - 1] = next_row(bs[i - 1], be[i - 1], &suf[i], &dist[i - 1], sig, N,
-                            mels[i - 1], 1);
-
     /* posterior boundary marginals, then max-product path: node.cpp:39-91 */
     double **dp = (double **)malloc(sizeof(double *) * (size_t)rows);
     int **prev = (int **)malloc(sizeof(int *) * (size_t)rows);
@@ -431,23 +481,65 @@ int orc_refine_alignment(void *mp, const double *sig, int64_t N64,
     for (int r = 0; r < rows; r++) {
       free(dp[r]);
       free(prev[r]);
-      row_free(&pre[r]);
-      row_free(&suf[r]);
     }
     free(dp);
     free(prev);
-    free(pre);
-    free(suf);
   }
 done_early:
-  free(bs);
-  free(be);
-  free(dist);
-  free(mels);
-  free(bs0);
-  free(be0);
-  free(owned);
+  refine_dp_free(&q);
   return status;
+}
+
+/* ---- the path objective of refine_alignment: node.cpp:39-91 ---------------
+ * Scores given paths with the quantity the search above maximises: the sum
+ * over DP rows of the posterior boundary marginal prefix_r[p] + suffix_r[p] at
+ * the path's position p = path[r], added in row order as the search adds them.
+ * paths holds n_paths paths of `rows` entries each (2R with transition rows,
+ * R+1 without); path[r] is the boundary of DP row r: with transition rows the
+ * flattened events entry r; without, path[0] = ev[0][0], path[r] = ev[r-1][1].
+ * invalid[k] = 1 when the search could not have produced path k: a position
+ * outside its band, a step shorter than the row's minimum event length (the
+ * moves the search allows: from i <= p - mels[r-1], both loops above), or a
+ * posterior of -inf on the path.  Otherwise 0, score[k] the sum and max_abs[k]
+ * the largest magnitude of a partial sum.  -> the number of invalid paths. */
+int orc_path_score(void *mp, const double *sig, int64_t N64, const int32_t *ref,
+                   int64_t R64, const int32_t *cb, int64_t nb,
+                   const int32_t *ca, int64_t na, const int32_t *anc, int64_t A,
+                   int bw, int mel, int transitions, const int32_t *paths,
+                   int n_paths, double *score, double *max_abs,
+                   int32_t *invalid) {
+  refine_dp q;
+  refine_dp_build(&q, (const orc_model *)mp, sig, N64, ref, R64, cb, nb, ca, na,
+                  anc, A, bw, mel, transitions);
+  int n_bad = 0;
+  for (int k = 0; k < n_paths; k++) {
+    const int32_t *path = paths + (int64_t)k * q.rows;
+    int bad = q.rows > 0 ? 0 : 1;
+    double sum = 0.0, big = 0.0;
+    for (int r = 0; r < q.rows && !bad; r++) {
+      int p = path[r];
+      if (p < q.bs[r] || p > q.be[r] ||
+          (r > 0 && p - path[r - 1] < q.mels[r - 1])) {
+        bad = 1;
+        break;
+      }
+      double post = row_get(&q.pre[r], p) + row_get(&q.suf[r], p);
+      if (!(post > NEG_INF)) {
+        bad = 1;
+        break;
+      }
+      sum = r == 0 ? post : sum + post;
+      double a = sum < 0 ? -sum : sum;
+      if (a > big)
+        big = a;
+    }
+    invalid[k] = bad;
+    score[k] = bad ? 0.0 : sum;
+    max_abs[k] = bad ? 0.0 : big;
+    n_bad += bad;
+  }
+  refine_dp_free(&q);
+  return n_bad;
 }
 
 /* ---- estimate_log_likelihoods: dtw.cpp:37-131 ---------------------------- */

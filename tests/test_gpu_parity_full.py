@@ -6,9 +6,11 @@ C oracle releases the GIL inside its ctypes calls):
   normalisation, both alignment passes of align_signal) and config 2 quantised to ADC steps, 10 000 reads each;
 * the parity contract of include/nadavca_hip.h: a read with neither NVK_TIE_ULP nor NVK_TIE_NEAR has the
   reference's events exactly — exact ties (NVK_TIE_EXACT) included; a read that differs carries such a bit AND
-  its difference is explained (flat plateau between equal k-mer levels / the long-double referee
-  sides with the engine / the reference changes its own answer in long double) — checked on a
-  homopolymer-rich reference, on randomised models and on wide bands;
+  its difference is explained: its path scores as well as the reference's on the reference's own path objective,
+  to within the tie zone per differing row, in 80-bit arithmetic (fuzz_cases.classify_difference; the labels —
+  flat plateau between equal k-mer levels / the long-double referee sides with the engine / the reference
+  changes its own answer in long double — are diagnostics on top of that) — checked on a homopolymer-rich
+  reference, on randomised models and on wide bands;
 * config 5 shape — ~50 000-sample reads, ~5 000 bases, bandwidth 1000 — through refine_alignment and
   estimate_log_likelihoods.
 
@@ -124,10 +126,13 @@ def test_homopolymer_rich_reference_mismatches_are_flagged(oracle_port):
         exp = _oracle_refine(oracle_port, mo, cases, 100, 2, tr)
         diff = np.array([not _same(g, e) for g, e in zip(got, exp)])
         assert not np.any(diff & ((flags & TIE_LOOSE) == 0)), 'a read without a tie bit differs from the reference'
-        from fuzz_cases import classify_difference
+        from fuzz_cases import classify_difference, largest_ratio, SCORED
+        first = len(SCORED)
         for j in np.nonzero(diff)[0]:
             why = classify_difference(got[j], exp[j], cases[j], model, k, central, alphabet, 100, 2, tr)
-            assert why != 'UNEXPLAINED', (tr, j)
+            assert why != 'UNEXPLAINED', (tr, j, SCORED[-1])
+        print('homopolymer-rich, transitions=%s: largest deficit/margin of a differing read %.3g'
+              % (tr, largest_ratio(first)))
         n_x, n_u, n_n = _tie_counts(flags)
         print('homopolymer-rich, transitions=%s: %d reads, %d adjacent identical k-mer pairs, reads with tie bits %d exact / '
               '%d ulp / %d near, %d differ from the double-precision reference (%d of them without the ulp bit; all explained)'
@@ -137,9 +142,10 @@ def test_homopolymer_rich_reference_mismatches_are_flagged(oracle_port):
 def _fuzz_contract(make_batch, seed, iters, oracle_port, label, max_diff_share):
     """Shared body of the randomised contract tests: equality wherever the near-tie bit is 0 (exact ties
     included), every difference explained, bounds on the near-tie share and on the differing share."""
-    from fuzz_cases import reads_of, classify_difference
+    from fuzz_cases import reads_of, classify_difference, largest_ratio, SCORED
     from nadavca_amd import dtw, _lib
     ctx = _lib.default_context()
+    first = len(SCORED)
     n_reads = n_diff = n_x = n_n = n_u = n_diff_no_ulp = n_p = 0
     why_count = {}
     for it in range(iters):
@@ -165,14 +171,16 @@ def _fuzz_contract(make_batch, seed, iters, oracle_port, label, max_diff_share):
                 assert flags[j] & TIE_LOOSE, ('a read without a tie bit differs', it, j)
                 why = classify_difference(got[j], exp, c, fb['model'], k, central, alphabet, fb['bw'], fb['mel'],
                                           fb['tr'])
-                assert why != 'UNEXPLAINED', ('unexplained difference', it, j)
+                assert why != 'UNEXPLAINED', ('unexplained difference', it, j, SCORED[-1])
                 if why == 'flat-plateau':   # ... and the read is marked as holding such a boundary
                     assert flags[j] & TIE_PLATEAU, ('flat-plateau difference without the plateau mark', it, j)
                 why_count[why] = why_count.get(why, 0) + 1
         mg.close()
     assert n_diff <= max_diff_share * n_reads, (n_diff, n_reads)
     print('%s: %d reads, reads with tie bits %d exact / %d ulp / %d near, %d with the plateau mark; %d differ (%d of them '
-          'without the ulp bit) %s' % (label, n_reads, n_x, n_u, n_n, n_p, n_diff, n_diff_no_ulp, why_count))
+          'without the ulp bit) %s; largest deficit/margin %.3g'
+          % (label, n_reads, n_x, n_u, n_n, n_p, n_diff, n_diff_no_ulp, why_count, largest_ratio(first)))
+    return dict(reads=n_reads, differ=n_diff, why=why_count, ratio=largest_ratio(first))
 
 
 def test_random_models_contract(oracle_port):
