@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "nvk_internal.h"
+#include "pipe_plan.h"
 
 namespace {
 
@@ -303,22 +304,11 @@ int lane_submit(nvk_pipe_state *p, Lane &L, const nvk_model *model, const HostBa
   L.model = *model;
   L.model.ctx = L.ctx;
   L.alphabet = model->dm.alphabet;
-  const size_t no = (size_t)(n + 1) * 8;
-  const size_t sizes[9] = {no, no, no, no, no, (size_t)tr * 4, (size_t)tb * 4, (size_t)ta * 4, (size_t)tn * 8};
-  size_t total = 0;
-  for (int q = 0; q < 9; q++) {
-    L.at[q] = total;
-    total += (sizes[q] + 63) & ~(size_t)63;  // (a 64-byte granule keeps every array 16-byte aligned; empty arrays too)
-    if (sizes[q] == 0) total += 64;
-  }
+  const size_t total = pipe_plan::pack_layout(n, tr, tb, ta, tn, L.at);
   int rc;
   if ((rc = nvk_grow(&L.hpack, &L.hpack_cap, total, true, "lane staging"))) return rc;
   char *hp = (char *)L.hpack;
-  for (int q = 0; q < 5; q++) {  // offsets rebased to the chunk
-    int64_t *dst = (int64_t *)(hp + L.at[q]);
-    const int64_t base = src[q][a];
-    for (int64_t i = 0; i <= n; i++) dst[i] = src[q][a + i] - base;
-  }
+  pipe_plan::rebase_offsets(src, a, n, L.at, hp);  // offsets rebased to the chunk
   if (tr) memcpy(hp + L.at[5], h.ref + h.ref_off[a], (size_t)tr * 4);
   if (tb) memcpy(hp + L.at[6], h.cb + h.cb_off[a], (size_t)tb * 4);
   if (ta) memcpy(hp + L.at[7], h.ca + h.ca_off[a], (size_t)ta * 4);
@@ -416,40 +406,17 @@ int run_pipelined(nvk_model *model, int kind, int64_t n_reads, const HostBatch &
     }
     ties = p->ties.data();
   }
-  // Chunks.  What a single call can hide is bounded by its first upload (nothing to compute yet) and by how
-  // full the chip is while only the early chunks are in flight; so the chunks GROW: a small first one gets the
-  // kernels going early, each later one is NADAVCA_E2E_GROWTH (x100) times its predecessor's share of the signal
-  // bytes.  A chunk has at least NADAVCA_E2E_MIN_READS reads, and a small batch stays in one piece.
-  const int64_t total_sig = h.sig_off[n_reads];
+  // Chunks (pipe_plan.h: chunk_schedule): they grow by NADAVCA_E2E_GROWTH (x100), a chunk has at least
+  // NADAVCA_E2E_MIN_READS reads and 8 MB of signal, and a small batch stays in one piece.
   const int64_t min_reads = env_int("NADAVCA_E2E_MIN_READS", 1024, 1, 1 << 30);
-  int64_t n_chunks = env_int("NADAVCA_E2E_CHUNKS", 3, 1, 64);
-  if (total_sig * 8 < (int64_t)n_chunks * (8ll << 20)) n_chunks = total_sig * 8 / (8ll << 20);  // (8 MB pieces at least)
-  if (n_chunks > n_reads / min_reads) n_chunks = n_reads / min_reads;
-  if (n_chunks < 1) n_chunks = 1;
+  const int64_t asked = env_int("NADAVCA_E2E_CHUNKS", 3, 1, pipe_plan::MAX_CHUNKS);
   const double growth = env_int("NADAVCA_E2E_GROWTH", 200, 100, 1000) / 100.0;
-  double wsum = 0.0, w = 1.0;
-  for (int64_t c = 0; c < n_chunks; c++, w *= growth) wsum += w;
-  int64_t lo = 0;
+  int64_t bounds[2 * pipe_plan::MAX_CHUNKS];
+  const int64_t n_chunks = pipe_plan::chunk_schedule(h.sig_off, n_reads, asked, growth, min_reads, 8ll << 20, bounds);
   int first_err = NVK_OK;
   char err_txt[512] = "";
-  double wacc = 0.0;
-  w = 1.0;
-  for (int64_t c = 0; c < n_chunks && !first_err; c++, w *= growth) {
-    int64_t hi;
-    wacc += w;
-    if (c == n_chunks - 1) {
-      hi = n_reads;
-    } else {  // first read index whose signal offset reaches this chunk's cumulative share
-      const int64_t target = (int64_t)((double)total_sig * (wacc / wsum));
-      int64_t x = lo, y = n_reads;
-      while (x < y) {
-        const int64_t mid = (x + y) >> 1;
-        if (h.sig_off[mid] < target) x = mid + 1; else y = mid;
-      }
-      hi = x > lo ? x : lo + 1;
-      if (hi > n_reads) hi = n_reads;
-    }
-    if (hi <= lo) continue;
+  for (int64_t c = 0; c < n_chunks && !first_err; c++) {
+    const int64_t lo = bounds[2 * c], hi = bounds[2 * c + 1];
     Lane &L = p->lanes[c % p->n_lanes];
     rc = lane_collect(p, L, ctx);  // the lane's previous chunk: results to the caller, staging free
     L.ticket = -1;
@@ -458,7 +425,6 @@ int run_pipelined(nvk_model *model, int kind, int64_t n_reads, const HostBatch &
       first_err = rc;
       strncpy(err_txt, nvk_last_error(), sizeof err_txt - 1);
     }
-    lo = hi;
   }
   for (int i = 0; i < p->n_lanes; i++) {  // (always drain every lane, also after an error)
     rc = lane_collect(p, p->lanes[i], ctx);
