@@ -569,6 +569,60 @@ int nvk_kmer_event_stats_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, c
 int nvk_kmer_reduce_dev(nvk_ctx *ctx, int64_t n_events, int64_t n_kmers, const int64_t *key, const double *val,
                         const int64_t *len, double *out_sum, int64_t *out_samples, int64_t *out_events);
 
+/* The M-step of modified-base table training (nadavca_amd/mod_train.py: estimate_mod_model): weighted per-k-mer sample
+ * statistics over the final events of an aligned batch whose reference is CANONICAL, for the k-mers that hold the
+ * modified base.  THE CONTRACT.  The library is built with -ffp-contract=off: every expression below is a rounded
+ * operation in the order written.  Inputs are those of nvk_kmer_event_stats_dev, and
+ *   sites          per read j its sites site_off[j] .. site_off[j+1] (i64[n_reads + 1], ending at n_sites): site_pos
+ *                  i32 (a base of the reference part, strictly ascending within a read, inside [0, R_j)) and site_gamma
+ *                  f64 in [0, 1], the probability that the read carries mod_code there.  Order and ranges are the
+ *                  caller's promise; whatever the arrays hold, nothing outside them or outside a base's rows is touched.
+ *   level          f64[alphabet^k], the current means; 0 <= mod_code < alphabet
+ *   rows of base g its window is [g - central, g - central + k); m = the number of the read's sites inside it.  m == 0 or
+ *                  m > 4: no rows (the bases with m > 4 are counted into *windows_skipped).  Otherwise 2^m - 1 rows, one
+ *                  per non-empty subset `mask` in ascending mask, bit t of mask = the window's t-th site in ascending
+ *                  position.  The number of rows does not depend on the event.
+ *   counted event  exactly as nvk_kmer_event_stats_dev counts it (trim, the window inside the contexts, a non-empty
+ *                  event after clamping, every code in range, status[j] == 0 or status NULL).  The rows of an event
+ *                  that is not counted are (-1, 0.0, 0.0, 0.0, 0.0).
+ *   values         for a counted event over the samples x[s:e], n = (double)(e - s): key0 = the window's k-mer id, c0 =
+ *                  level[key0], a = sum (x[i] - c0) and b = sum (x[i] - c0) * (x[i] - c0), each an ascending loop from
+ *                  0.0, once per event.  Per mask: key = the id with mod_code at the mask's sites; d = c0 - level[key];
+ *                    sd = a + n * d                            (the sum of x - level[key])
+ *                    sq = b + (2.0 * d) * a + (n * d) * d      (the sum of its squares)
+ *                    w  = 1.0, then for t ascending over the window's sites  w = w * gamma_t  if bit t of mask is set,
+ *                         else  w = w * (1.0 - gamma_t)
+ *                  and the row is (key, w, n, sd, sq).
+ * nvk_mod_kmer_rows_dev is called twice, as nvk_meth_count_dev / nvk_meth_scores_dev are.  With out_key and out_val NULL
+ * it writes out_count i64[total_ref], the rows of every base (events, level and row_off are not read).  The caller forms
+ * row_off i64[total_ref + 1] by a cumulative sum, n_rows = its end, and calls again with out_key i64[n_rows] and out_val
+ * f64[4 n_rows] (w, n, sd, sq per row): base g of read j fills exactly [row_off[ref_off[j] + g], row_off[ref_off[j] + g +
+ * 1)).  Where that range is not inside 0 .. n_rows or its width is not the base's row count, nothing is written for the
+ * base, a device flag is raised (an integer atomic OR) and the entry returns NVK_ERR_INVALID.  windows_skipped is a HOST
+ * pointer (may be NULL), written by both calls.  ref_off, site_off, sig_off, cb_off and ca_off are copied to the host and
+ * checked (start at 0, never decrease, ref_off ends at total_ref, site_off at n_sites).
+ * nvk_mod_kmer_reduce_dev: val f64[4 n_rows] is the rows gathered into the STABLE ascending order of their keys; run_off
+ * i64[n_keys + 1] the runs of the distinct keys >= 0 in it: run_off[0] = the number of rows with a key < 0 (they come
+ * first and are skipped), run_off[n_keys] = n_rows, never decreasing (copied to the host and checked).  Per run, over its
+ * rows 0 .. c-1 in order, four sums W = sum w, Nw = sum w * n, Sd = sum w * sd, Sq = sum w * sq, each
+ *   64 partial sums starting at 0.0, row i added to sum i mod 64 in ascending i, then combined by the butterfly
+ *   p[l] = p[l] + p[l xor d] for d = 32, 16, 8, 4, 2, 1 (nvk_site_moments_dev's order).
+ * out_sum f64[4 n_keys] = (W, Nw, Sd, Sq) per run, out_rows i64[n_keys] = c; every entry is written.  The caller takes
+ * mean = level[key] + Sd / Nw and variance = Sq / Nw - (Sd / Nw)^2.
+ * No floating-point atomics: the same bits on every run.  The launches are timed under NVK_K_KMER.  k, central, alphabet
+ * and trim as for nvk_kmer_event_stats_dev; n_keys == 0 launches nothing.  NVK_ERR_INVALID for bad arguments or offsets;
+ * a data pointer may be NULL only where its array is empty.  Device pointers but windows_skipped. */
+int nvk_mod_kmer_rows_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, const double *signal,
+                          const int64_t *sig_off, const int32_t *events, const int64_t *ref_off,
+                          const int32_t *reference, const int32_t *ctx_before, const int64_t *cb_off,
+                          const int32_t *ctx_after, const int64_t *ca_off, const int32_t *status, int k, int central,
+                          int alphabet, int trim, int64_t n_sites, const int64_t *site_off, const int32_t *site_pos,
+                          const double *site_gamma, int mod_code, const double *level, int64_t n_rows,
+                          const int64_t *row_off, int64_t *out_count, int64_t *out_key, double *out_val,
+                          int64_t *windows_skipped);
+int nvk_mod_kmer_reduce_dev(nvk_ctx *ctx, int64_t n_rows, int64_t n_keys, const double *val, const int64_t *run_off,
+                            double *out_sum, int64_t *out_rows);
+
 /* Per-site allele mixtures (nadavca_amd/allele_fractions.py: estimate_allele_fractions_batch): which share of the reads
  * that cover a reference position carries a base other than the reference's.  THE CONTRACT.  Take a global reference
  * position P with reference base r = ref_codes[P], and a base b != r.

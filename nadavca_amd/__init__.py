@@ -12,6 +12,7 @@ from .seedalign import SeedAligner  # noqa: F401
 from .refset import ReferenceSet  # noqa: F401
 from .kmer_train import estimate_kmer_model  # noqa: F401
 from .call_mods import call_mods_batch  # noqa: F401
+from .mod_train import ModModelEstimate, estimate_mod_model  # noqa: F401
 from .call_indels import call_indels_batch  # noqa: F401
 from .allele_fractions import estimate_allele_fractions_batch  # noqa: F401
 from .phase import PhaseBatch, phase_reads_batch  # noqa: F401
@@ -23,4 +24,4 @@ __all__ = ['align_signal', 'align_signal_batch', 'estimate_snps', 'estimate_snps
            'ReferenceSet', 'estimate_kmer_model', 'call_mods_batch', 'call_indels_batch',
            'estimate_allele_fractions_batch', 'phase_reads_batch', 'PhaseBatch', 'site_levels_batch',
            'compare_site_levels', 'SiteLevelBatch', 'SiteComparison', 'compare_site_ranks', 'site_rank_tests_batch', 'SiteRankComparison', 'compare_site_mixtures',
-           'site_mixture_tests_batch', 'SiteMixtureComparison']
+           'site_mixture_tests_batch', 'SiteMixtureComparison', 'estimate_mod_model', 'ModModelEstimate']

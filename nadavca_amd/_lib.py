@@ -90,6 +90,9 @@ SIGNATURES = {
                                     + [_vp, _vp]),
     'nvk_kmer_event_stats_dev': (_int, [_vp, _i64, _i64] + [_vp] * 10 + [_int] * 4 + [_vp] * 4),
     'nvk_kmer_reduce_dev': (_int, [_vp, _i64, _i64] + [_vp] * 6),
+    'nvk_mod_kmer_rows_dev': (_int, [_vp, _i64, _i64] + [_vp] * 10 + [_int] * 4 + [_i64, _vp, _vp, _vp, _int, _vp, _i64]
+                              + [_vp] * 5),
+    'nvk_mod_kmer_reduce_dev': (_int, [_vp, _i64, _i64] + [_vp] * 4),
     'nvk_allele_rows_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 6 + [_dbl, _i64, _vp, _vp]),
     'nvk_allele_solve_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 8),
     'nvk_phase_links_dev': (_int, [_vp, _i64, _int] + [_vp] * 6 + [_dbl, _vp, _vp]),

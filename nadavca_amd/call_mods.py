@@ -177,6 +177,62 @@ def joint_lists(owner, pos, n_reads, first, size, mod_code):
     return hyp_off, sub_off, sub_pos, torch.full_like(sub_pos, int(mod_code)), hyp_cluster, hyp_mask
 
 
+class SiteScores:
+    """What ``score_sites`` returns, device tensors unless noted.  Per site of ``find_sites`` (read order, ascending
+    position): ``owner`` (its live read), ``pos``, ``forward``, ``crowded`` (with ``joint``: a site within k - 1 bases
+    lies in ANOTHER cluster), ``hyp`` (the log-likelihood with the site alone modified), ``llr`` (with ``joint``: the
+    marginal ratio; else ``hyp - total[owner]``), ``cluster_size`` (None without ``joint``) and ``ok`` (its read is
+    READ_OK after the scoring; the rows of ``call_mods_batch`` are the sites with it).  Per live read: ``site_off``
+    (n_live + 1,), ``total`` (the log-likelihood without a substitution) and ``status``; ``live``: a numpy array."""
+    __slots__ = ('site_off', 'owner', 'pos', 'forward', 'crowded', 'total', 'hyp', 'llr', 'cluster_size', 'status',
+                 'live', 'ok')
+
+
+def score_sites(res, config, kmer_model, codes, mod_offset, mod_code, joint, max_joint, site_prior):
+    """The part of ``call_mods_batch`` behind ``align_batch``, which ``mod_train.estimate_mod_model`` shares: the
+    pattern's occurrences in the reads of the BatchAlignment ``res`` that aligned (``find_sites``) and their ratios
+    from ONE call of the listed or the joint operator, on the device.  ``res.stage.n_live > 0``; ``config`` loaded,
+    ``kmer_model`` a KmerModel holding ``mod_code``, ``codes`` the pattern's base codes.  -> SiteScores."""
+    import torch
+    from .batchflow import hypothesis_rows
+    from .device import estimate_hypotheses_dev, estimate_joint_hypotheses_dev
+    from .readbatch import contig_local_range
+    stage = res.stage
+    sa, dbatch = stage.sa, stage.dbatch
+    start, end = contig_local_range(sa, stage.reference)
+    site_off, owner, pos, forward, crowded = find_sites(
+        dbatch.reference, dbatch.ref_off, start, end, sa.reverse, codes, mod_offset, kmer_model.get_k(),
+        keep=res.status == _lib.READ_OK, total_ref=dbatch.total_ref)
+    hyp_args = (dbatch, config['bandwidth'], config['min_event_length'], kmer_model, config['model_wobbling'])
+    llr = cluster_size = None
+    if joint:
+        cluster, first, size, cut = cluster_sites(owner, pos, kmer_model.get_k(), max_joint)
+        hyp_off, sub_off, sub_pos, sub_base, hyp_cluster, hyp_mask = joint_lists(owner, pos, stage.n_live, first, size,
+                                                                                 mod_code)
+        total, joint_ll, status = estimate_joint_hypotheses_dev(*hyp_args, hyp_off, sub_off, sub_pos, sub_base)
+        # the clusters' subsets as a dense table (column: mask; column 0: no site, the read's total)
+        values = torch.full((int(first.numel()), 1 << (int(size.max()) if int(size.numel()) else 0)), -math.inf,
+                            dtype=torch.float64, device=pos.device)
+        values[:, 0] = total[owner[first]]
+        values[hyp_cluster, hyp_mask] = joint_ll
+        rank = torch.arange(int(pos.numel()), dtype=torch.int64, device=pos.device) - first[cluster]
+        hyp = values[cluster, torch.bitwise_left_shift(torch.ones_like(rank), rank)]      # the singleton subsets
+        cluster_size = size[cluster]
+        llr = torch.where(cluster_size > 1, marginal_llr(values, size, float(site_prior))[cluster, rank],
+                          hyp - total[owner]) if int(pos.numel()) else hyp
+        crowded = cut
+    else:
+        total, hyp, status = estimate_hypotheses_dev(*hyp_args, site_off, pos, torch.full_like(pos, int(mod_code)))
+        llr = hyp - total[owner]
+    status, live, ok = hypothesis_rows('estimate_joint_hypotheses' if joint else 'estimate_hypotheses', res, status,
+                                       owner)
+    sc = SiteScores()
+    sc.site_off, sc.owner, sc.pos, sc.forward, sc.crowded = site_off, owner, pos, forward, crowded
+    sc.total, sc.hyp, sc.llr, sc.cluster_size = total, hyp, llr, cluster_size
+    sc.status, sc.live, sc.ok = status, live, ok
+    return sc
+
+
 class ModCallBatch:
     """What ``call_mods_batch`` returns: one row per occurrence of the pattern in the reference part of every read
     that aligned, in read order and ascending position within the read's orientation, as flat arrays: ``read``
@@ -279,9 +335,8 @@ def call_mods_batch(read_batch, aligner, kmer_model, pattern='CG', mod_offset=0,
     if not 0.0 < float(site_prior) < 1.0:
         raise ValueError('call_mods_batch: site_prior %r outside the open interval (0, 1)' % (site_prior,))
     import torch
-    from .batchflow import align_batch, hypothesis_rows, load_config, load_kmer_model
-    from .device import estimate_hypotheses_dev, estimate_joint_hypotheses_dev, to_host
-    from .readbatch import contig_local_range
+    from .batchflow import align_batch, load_config, load_kmer_model
+    from .device import to_host
     kmer_model = load_kmer_model(kmer_model)
     config = load_config(config)
     alphabet = kmer_model.get_alphabet_size()
@@ -297,32 +352,11 @@ def call_mods_batch(read_batch, aligner, kmer_model, pattern='CG', mod_offset=0,
     names = stage.contig_names()
     if stage.n_live == 0:
         return ModCallBatch.empty(contig_names=names, joint=joint)
-    sa, dbatch = stage.sa, stage.dbatch
-    start, end = contig_local_range(sa, stage.reference)
-    site_off, owner, pos, forward, crowded = find_sites(
-        dbatch.reference, dbatch.ref_off, start, end, sa.reverse, codes, mod_offset, kmer_model.get_k(),
-        keep=res.status == _lib.READ_OK, total_ref=dbatch.total_ref)
-    hyp_args = (dbatch, config['bandwidth'], config['min_event_length'], kmer_model, config['model_wobbling'])
-    if joint:
-        cluster, first, size, cut = cluster_sites(owner, pos, kmer_model.get_k(), max_joint)
-        hyp_off, sub_off, sub_pos, sub_base, hyp_cluster, hyp_mask = joint_lists(owner, pos, stage.n_live, first, size,
-                                                                                 mod_code)
-        total, joint_ll, status = estimate_joint_hypotheses_dev(*hyp_args, hyp_off, sub_off, sub_pos, sub_base)
-        # the clusters' subsets as a dense table (column: mask; column 0: no site, the read's total)
-        values = torch.full((int(first.numel()), 1 << (int(size.max()) if int(size.numel()) else 0)), -math.inf,
-                            dtype=torch.float64, device=pos.device)
-        values[:, 0] = total[owner[first]]
-        values[hyp_cluster, hyp_mask] = joint_ll
-        rank = torch.arange(int(pos.numel()), dtype=torch.int64, device=pos.device) - first[cluster]
-        hyp = values[cluster, torch.bitwise_left_shift(torch.ones_like(rank), rank)]                                   # the singleton subsets
-        cluster_size = size[cluster]
-        llr = torch.where(cluster_size > 1, marginal_llr(values, size, float(site_prior))[cluster, rank],
-                          hyp - total[owner]) if int(pos.numel()) else hyp
-        crowded = cut
-    else:
-        total, hyp, status = estimate_hypotheses_dev(*hyp_args, site_off, pos, torch.full_like(pos, int(mod_code)))
-    status, live, ok = hypothesis_rows('estimate_joint_hypotheses' if joint else 'estimate_hypotheses', res, status,
-                                       owner)
+    sa = stage.sa
+    sc = score_sites(res, config, kmer_model, codes, mod_offset, mod_code, joint, max_joint, site_prior)
+    owner, forward, crowded, total, hyp, status, live, ok = (sc.owner, sc.forward, sc.crowded, sc.total, sc.hyp,
+                                                             sc.status, sc.live, sc.ok)
+    llr, cluster_size = sc.llr, sc.cluster_size
     owner = owner[ok]
     if int(owner.numel()) == 0:
         return ModCallBatch.empty(status.cpu().numpy(), live, total.cpu().numpy(), names, joint=joint)

@@ -510,6 +510,106 @@ def kmer_reduce_dev(context, key, val, length, n_kmers):
     return out_sum, out_samples, out_events
 
 
+# ---- weighted per-k-mer statistics of modified-base table training (nadavca_amd/mod_train.py) --------------------
+MOD_COLUMNS = ('w', 'n', 'sd', 'sq')
+
+
+def mod_kmer_rows_dev(dbatch, context, events, status, k, central, alphabet, trim, site_off, site_pos, site_gamma,
+                      mod_code, level):
+    """Per base of ``dbatch``'s reads with 1 .. 4 of its read's sites in its k-mer window, one row per non-empty subset
+    of them (include/nadavca_hip.h: nvk_mod_kmer_rows_dev has the contract; its two calls and the cumulative sum
+    between them).  ``site_off`` int64 (n + 1,), ``site_pos`` int32 (strictly ascending within a read, inside the
+    read's reference part), ``site_gamma`` f64 in [0, 1], ``level`` f64 (alphabet^k,): device tensors; what they hold is
+    checked here (ValueError).
+    -> (key int64 (rows,), val f64 (rows, 4): w, n, sd, sq, row_off int64 (sum R + 1,), windows_skipped int)."""
+    torch = dbatch.torch
+    lib = _lib.load()
+    dev = dbatch.device
+    n, total = dbatch.n, max(dbatch.total_ref, 0)
+    site_off = site_off.to(device=dev, dtype=torch.int64).contiguous()
+    site_pos = site_pos.to(device=dev, dtype=torch.int32).contiguous()
+    site_gamma = site_gamma.to(device=dev, dtype=torch.float64).contiguous()
+    level = level.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+    n_sites = int(site_pos.numel())
+    if int(level.numel()) != int(alphabet) ** int(k):
+        raise ValueError('mod_kmer_rows_dev: level holds %d values, the table %d' % (int(level.numel()),
+                                                                                    int(alphabet) ** int(k)))
+    if int(site_off.numel()) != n + 1 or int(site_gamma.numel()) != n_sites:
+        raise ValueError('mod_kmer_rows_dev: site_off holds %d offsets for %d reads, site_gamma %d values for %d sites'
+                         % (int(site_off.numel()), n, int(site_gamma.numel()), n_sites))
+    if n_sites:
+        if not bool(((site_gamma >= 0.0) & (site_gamma <= 1.0)).all()):     # (false for a NaN too)
+            raise ValueError('mod_kmer_rows_dev: a site_gamma outside [0, 1] or not finite')
+        if not (int(site_off[0]) == 0 and int(site_off[-1]) == n_sites and bool((site_off[1:] >= site_off[:-1]).all())):
+            raise ValueError('mod_kmer_rows_dev: site_off does not start at 0, decreases or does not end at the number '
+                             'of sites')
+        owner = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), site_off[1:] - site_off[:-1],
+                                        output_size=n_sites)
+        length = (dbatch.ref_off[1:] - dbatch.ref_off[:-1])[owner]
+        if not bool(((site_pos >= 0) & (site_pos < length)).all()):
+            raise ValueError('mod_kmer_rows_dev: a site position outside its read\'s reference part')
+        if not bool(((owner[1:] != owner[:-1]) | (site_pos[1:] > site_pos[:-1])).all()):
+            raise ValueError('mod_kmer_rows_dev: site positions are not strictly ascending within a read')
+    else:       # (a placeholder element: the C-ABI takes no NULL for a batch that has reads)
+        site_pos = torch.zeros(1, dtype=torch.int32, device=dev)
+        site_gamma = torch.zeros(1, dtype=torch.float64, device=dev)
+    skipped = C.c_int64(0)
+    head = (context.handle, dbatch.n, dbatch.total_ref, _dp(dbatch.signal), _dp(dbatch.sig_off), _dp(events),
+            _dp(dbatch.ref_off), _dp(dbatch.reference), _dp(dbatch.context_before), _dp(dbatch.cb_off),
+            _dp(dbatch.context_after), _dp(dbatch.ca_off), _dp(status) if status is not None else C.c_void_p(0),
+            int(k), int(central), int(alphabet), int(trim), n_sites, _dp(site_off), _dp(site_pos), _dp(site_gamma),
+            int(mod_code), _dp(level))
+    count = torch.zeros(total, dtype=torch.int64, device=dev)
+    _lib.check(lib.nvk_mod_kmer_rows_dev(*head, 0, C.c_void_p(0), _dp(count), C.c_void_p(0), C.c_void_p(0),
+                                         C.byref(skipped)), 'nvk_mod_kmer_rows_dev')
+    row_off = torch.zeros(total + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(count, 0, out=row_off[1:])
+    n_rows = int(row_off[-1])
+    key = torch.empty(n_rows, dtype=torch.int64, device=dev)
+    val = torch.empty((n_rows, len(MOD_COLUMNS)), dtype=torch.float64, device=dev)
+    if n_rows:
+        _lib.check(lib.nvk_mod_kmer_rows_dev(*head, n_rows, _dp(row_off), C.c_void_p(0), _dp(key), _dp(val),
+                                             C.byref(skipped)), 'nvk_mod_kmer_rows_dev')
+    return key, val, row_off, int(skipped.value)
+
+
+def mod_kmer_reduce_dev(context, val, run_off):
+    """Per run of ``run_off`` (int64 (n_keys + 1,): the runs of the distinct keys >= 0 among the rows in stable key
+    order; ``val`` f64 (rows, 4) gathered into that order): (sums f64 (n_keys, 4): W, Nw, Sd, Sq, rows int64 (n_keys,))
+    device tensors (nvk_mod_kmer_reduce_dev)."""
+    import torch
+    lib = _lib.load()
+    dev = val.device
+    n_keys = int(run_off.numel()) - 1
+    if n_keys < 0 or val.dim() != 2 or int(val.shape[1]) != len(MOD_COLUMNS):
+        raise ValueError('mod_kmer_reduce_dev: val must be (rows, 4) and run_off hold at least one offset')
+    val = val.to(torch.float64).contiguous()
+    run_off = run_off.to(device=dev, dtype=torch.int64).contiguous()
+    sums = torch.empty((n_keys, len(MOD_COLUMNS)), dtype=torch.float64, device=dev)
+    rows = torch.empty(n_keys, dtype=torch.int64, device=dev)
+    _lib.check(lib.nvk_mod_kmer_reduce_dev(context.handle, int(val.shape[0]), n_keys, _dp(val), _dp(run_off),
+                                           _dp(sums), _dp(rows)), 'nvk_mod_kmer_reduce_dev')
+    return sums, rows
+
+
+def mod_kmer_stats_dev(context, dbatch, events, status, k, central, alphabet, trim, site_off, site_pos, site_gamma,
+                       mod_code, level):
+    """The weighted statistics of every k-mer that a site's window can turn into: the rows from one kernel, a stable
+    sort of their keys, a gather and the runs of the keys (torch: plumbing), the per-run sums from another.
+    -> dict of device tensors ``key`` int64 (n_keys,) ascending, ``sums`` f64 (n_keys, 4): W, Nw, Sd, Sq, ``count``
+    int64 (n_keys,), and the ints ``rows`` and ``windows_skipped``."""
+    import torch
+    key, val, _, skipped = mod_kmer_rows_dev(dbatch, context, events, status, k, central, alphabet, trim, site_off,
+                                             site_pos, site_gamma, mod_code, level)
+    skey, order = torch.sort(key, stable=True)
+    sval = val[order]
+    n_neg = (skey < 0).sum().reshape(1)
+    ukey, counts = torch.unique_consecutive(skey[skey >= 0], return_counts=True)
+    run_off = torch.cat([n_neg, n_neg + torch.cumsum(counts, 0)])
+    sums, count = mod_kmer_reduce_dev(context, sval, run_off)
+    return dict(key=ukey, sums=sums, count=count, rows=int(key.numel()), windows_skipped=skipped)
+
+
 # ---- per-site allele mixtures (nadavca_amd/allele_fractions.py) -------------------------------------------------
 def allele_rows_dev(context, dbatch, ll, chunk_start, reverse, status, event_length, ref_len):
     """Per read-major row of ``ll``: (key int64 (sum R,), val f64 (sum R, alphabet)) device tensors — the row's global
