@@ -82,9 +82,13 @@ int64_t nvk_spill_cap(nvk_ctx *ctx, int which_ws) {
 TimerScope::TimerScope(nvk_ctx *c, int kid) : ctx(c), id(kid) {
   if (ctx->timing_on) (void)hipEventRecord(ctx->ev0, ctx->stream);
 }
+void TimerScope::stop() {
+  if (ctx->timing_on && !stopped) (void)hipEventRecord(ctx->ev1, ctx->stream);
+  stopped = true;
+}
 TimerScope::~TimerScope() {
   if (ctx->timing_on) {
-    (void)hipEventRecord(ctx->ev1, ctx->stream);
+    if (!stopped) (void)hipEventRecord(ctx->ev1, ctx->stream);
     (void)hipEventSynchronize(ctx->ev1);
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) {
@@ -438,15 +442,19 @@ struct PlanHost {
   int32_t steps[1];  // [n_reads]
 };
 
-// plan a batch: metas + row table (+ for refine_alignment the lane records of kernels_align3, the launch order
-// and the step counts in that order) in ctx workspaces; ONE copy + synchronisation brings the totals and the
-// step counts to the host (ctx->h_plan)
-int plan_batch(nvk_model *model, const BatchArgs &a, int mode, PlanTotals &tot, const int **order,
-               const int32_t **steps_sorted) {
+// plan a batch: metas, the lane records of kernels_align3, the launch order and the step counts in that order — and,
+// with write_rows, the row table of the exact kernel — in ctx workspaces; ONE copy + synchronisation brings the
+// totals and the step counts to the host (ctx->h_plan).  In two halves, so that the caller does the host work that
+// does not depend on what the planner finds while the planner runs: plan_batch_queue reserves, launches — calling
+// `meanwhile` as soon as the planner itself is queued (launch_plan) — and returns; plan_batch_wait queues the copy
+// and waits for it.
+int plan_batch_queue(nvk_model *model, const BatchArgs &a, int mode, int write_rows, const int **order,
+                     const std::function<int()> *meanwhile) {
   nvk_ctx *ctx = model->ctx;
   int64_t n = a.n_reads;
   int64_t rows_total = (mode == PLAN_ALIGN_TRANS) ? 2 * a.total_ref : a.total_ref + n;
   int rc;
+  ctx->rows_current = 0;  // (whatever WS_ROWS holds belongs to an earlier batch from here on)
   if ((rc = nvk_ws_reserve(ctx, WS_META, (size_t)(n + 1) * sizeof(ReadMeta) + 64))) return rc;
   if ((rc = nvk_ws_reserve(ctx, WS_ROWS, (size_t)(rows_total + 1) * sizeof(RowParam)))) return rc;
   if ((rc = nvk_ws_reserve(ctx, WS_BANDTMP, (size_t)(2 * (a.total_ref + n) + 2) * 8))) return rc;
@@ -455,27 +463,48 @@ int plan_batch(nvk_model *model, const BatchArgs &a, int mode, PlanTotals &tot, 
   if ((rc = nvk_ws_reserve(ctx, WS_LANE_R, (size_t)(rows_total + 1) * 48))) return rc;
   if ((rc = nvk_ws_reserve(ctx, WS_OFFS, (size_t)(rows_total + 1) * sizeof(int32_t)))) return rc;
   if ((rc = nvk_ws_reserve(ctx, WS_STEPS, (size_t)(n + 1) * sizeof(int32_t)))) return rc;
+  // (launch_order's own, made here so that nothing is reserved once the planner is queued: it asks for the order and
+  // its bucket counters, far less than a page)
+  if ((rc = nvk_ws_reserve(ctx, WS_ORDER, (size_t)n * sizeof(int) + 4096))) return rc;
   if ((rc = nvk_grow(&ctx->h_plan, &ctx->h_plan_cap, sizeof(PlanHost) + (size_t)n * sizeof(int32_t), true,
                      "planner results")))
     return rc;
-  PlanHost *hp = (PlanHost *)ctx->h_plan;
   PlanTotals *d_tot = nvk_plan_totals(ctx);
   rc = launch_plan(ctx, model->dm, a, mode, (ReadMeta *)ctx->ws[WS_META],
                    (RowParam *)ctx->ws[WS_ROWS], (unsigned long long *)ctx->ws[WS_BANDTMP], d_tot,
-                   ctx->ws[WS_LANE_F], ctx->ws[WS_LANE_R], (int32_t *)ctx->ws[WS_OFFS]);
+                   ctx->ws[WS_LANE_F], ctx->ws[WS_LANE_R], (int32_t *)ctx->ws[WS_OFFS], write_rows, meanwhile);
   if (rc) return rc;
+  ctx->rows_current = write_rows ? 1 : 0;
   int *ord = nullptr;
   rc = launch_order(ctx, (const ReadMeta *)ctx->ws[WS_META], n, d_tot, &ord, (int32_t *)ctx->ws[WS_STEPS]);
   if (rc) return rc;
-  NVK_HIP(hipMemcpyAsync(&hp->tot, d_tot, sizeof(PlanTotals), hipMemcpyDeviceToHost, ctx->stream));
+  *order = ord;
+  return NVK_OK;
+}
+
+int plan_batch_wait(nvk_ctx *ctx, int64_t n, PlanTotals &tot, const int32_t **steps_sorted) {
+  PlanHost *hp = (PlanHost *)ctx->h_plan;
+  NVK_HIP(hipMemcpyAsync(&hp->tot, nvk_plan_totals(ctx), sizeof(PlanTotals), hipMemcpyDeviceToHost, ctx->stream));
   if (n) NVK_HIP(hipMemcpyAsync(hp->steps, ctx->ws[WS_STEPS], (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost,
                                 ctx->stream));
   NVK_HIP(hipStreamSynchronize(ctx->stream));
   tot = hp->tot;
-  *order = ord;
   *steps_sorted = hp->steps;
   ctx->last_cells = (int64_t)tot.cells;
   ctx->last_steps = (int64_t)tot.steps;
+  return NVK_OK;
+}
+
+// The row table for a batch that was planned without it (plan_batch_queue, write_rows 0): the planner once more, with
+// the table and without the lane records.  It rewrites the metas with the values they hold and leaves the totals, the
+// launch order and out_status — by which the exact kernel picks its reads — alone.
+int plan_rows_now(nvk_model *model, const BatchArgs &a, int mode) {
+  nvk_ctx *ctx = model->ctx;
+  if (ctx->rows_current) return NVK_OK;
+  int rc = launch_plan(ctx, model->dm, a, mode, (ReadMeta *)ctx->ws[WS_META], (RowParam *)ctx->ws[WS_ROWS],
+                       (unsigned long long *)ctx->ws[WS_BANDTMP], nullptr, nullptr, nullptr, nullptr, 1);
+  if (rc) return rc;
+  ctx->rows_current = 1;
   return NVK_OK;
 }
 
@@ -558,18 +587,30 @@ extern "C" int nvk_refine_alignment_batch_dev(
   ctx->last_ties = ctx->last_ties_exact = ctx->last_ties_near = ctx->last_ties_ulp = 0;
   const int *order = nullptr;
   const int32_t *steps_sorted = nullptr;
-  rc = plan_batch(model, a, model_transitions ? PLAN_ALIGN_TRANS : PLAN_ALIGN_PLAIN, tot, &order, &steps_sorted);
-  if (rc) return rc;
+  const bool exact_all = force && force[0] == '1';
+  const int mode = model_transitions ? PLAN_ALIGN_TRANS : PLAN_ALIGN_PLAIN;
+  // Everything up to plan_batch_wait is done before the planner is queued or while it runs: the reservations sized by
+  // the batch alone first (one that grows drains the stream, which is empty here), then the planner — with the row
+  // table only if the exact kernel serves the whole batch — and beside it the fills and the spill cap.  What is left
+  // behind the wait is what the planner's totals and step counts decide.
   // WS_TIES: per-read tie bits, then 4 class counts, then the number of reads handed to the exact kernel
   if ((rc = nvk_ws_reserve(ctx, WS_TIES, (size_t)(n_reads + 8) * sizeof(int32_t)))) return rc;
-  NVK_HIP(hipMemsetAsync(ctx->ws[WS_TIES], 0, (size_t)(n_reads + 8) * sizeof(int32_t), ctx->stream));
+  if (!exact_all && (rc = align3_reserve(ctx, n_reads))) return rc;
+  int64_t spill_cap = 0;
+  const std::function<int()> meanwhile = [&]() -> int {
+    // (the fill covers d_retry; the kernels that write these words are queued behind it)
+    NVK_HIP(hipMemsetAsync(ctx->ws[WS_TIES], 0, (size_t)(n_reads + 8) * sizeof(int32_t), ctx->stream));
+    return exact_all ? NVK_OK : align3_prepare(ctx, &spill_cap);
+  };
+  rc = plan_batch_queue(model, a, mode, exact_all ? 1 : 0, &order, &meanwhile);
+  if (rc) return rc;
+  if ((rc = plan_batch_wait(ctx, n_reads, tot, &steps_sorted))) return rc;
   ctx->ties_n = n_reads;
   ctx->ties_host = nullptr;
   int32_t *d_ties = (int32_t *)ctx->ws[WS_TIES];
   int *d_retry = (int *)(d_ties + n_reads + 4);
   const ReadMeta *metas = (const ReadMeta *)ctx->ws[WS_META];
   const RowParam *rows = (const RowParam *)ctx->ws[WS_ROWS];
-  bool exact_all = force && force[0] == '1';
   // reads in which a path decision fell inside the tie margin (include/nadavca_hip.h) and — one copy, one
   // synchronisation for both — the reads the fast kernel handed to the exact one
   int32_t tail[5] = {0, 0, 0, 0, 0};
@@ -584,17 +625,20 @@ extern "C" int nvk_refine_alignment_batch_dev(
     // fast path: plain doubles under a wave-uniform scale (bit-identical while in range);
     // reads it cannot serve come back flagged and are redone by the exact kernel below
     rc = launch_align3(ctx, a, model_transitions ? 1 : 0, metas, tot, order, steps_sorted, out_events, out_status,
-                       d_retry);
+                       d_retry, spill_cap);
     if (rc) return rc;
     if ((rc = fetch_counts())) return rc;
     ctx->last_retries = tail[4];
     if (tail[4] > 0) {
+      // (rare: the row table is made for the whole batch now, not written for nobody on every batch)
+      if ((rc = plan_rows_now(model, a, mode))) return rc;
       rc = launch_align_retry(ctx, a, model_transitions ? 1 : 0, metas, rows, tot, out_events,
                               out_status);
       if (rc) return rc;
       if ((rc = fetch_counts())) return rc;
     }
   } else {
+    if ((rc = plan_rows_now(model, a, mode))) return rc;  // (planned with the table: nothing to do)
     rc = launch_align(ctx, a, model_transitions ? 1 : 0, metas, rows, tot, out_events, out_status);
     if (rc) return rc;
     if ((rc = fetch_counts())) return rc;
@@ -618,6 +662,7 @@ int ell_run(nvk_model *model, const BatchArgs &a, int model_wobbling, double *ou
   nvk_ctx *ctx = model->ctx;
   const int64_t n = n_reads, nrow = total_ref + n;
   if ((rc = nvk_ws_reserve(ctx, WS_META, (size_t)(n + 1) * sizeof(ReadMeta) + 64))) return rc;
+  ctx->rows_current = 0;  // (WS_ROWS takes this operator's descriptors)
   if ((rc = nvk_ws_reserve(ctx, WS_ROWS, (size_t)(total_ref + 1) * sizeof(FusedParam)))) return rc;
   if ((rc = nvk_ws_reserve(ctx, WS_ROWS2, (size_t)(total_ref + 1) * sizeof(FusedParam)))) return rc;
   if ((rc = nvk_ws_reserve(ctx, WS_BP, (size_t)(3 * nrow + 16) * sizeof(int32_t)))) return rc;

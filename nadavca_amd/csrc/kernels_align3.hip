@@ -115,14 +115,20 @@ constexpr int TARGET = 250; // exponent the largest live value is moved to
 // 8-byte pieces cost a quarter of the kernel's time).  Pair p holds steps 2p and 2p+1 of the FORWARD
 // order, [pair][lane][2]; the planner makes the step count even so that the reverse sweep, which runs the
 // steps downwards, ends on a pair boundary.
+// Both carry the non-temporal bit (`nt` in the assembly): a batch's spill, 25 GB per 10 000 config-2 reads, is
+// written once and read once, far beyond L2 and the Infinity Cache, so nothing is lost by streaming it past them,
+// and a line it does not displace is one of the lane records, the signal or the bit words (measured, DESIGN.md
+// 5.1a: reverse launch -3.5 %, forward launch -1.2 %).  Nothing is handed over inside a launch, so no
+// write-through form is wanted.
+constexpr int SPILL_AUX = 2;  // the builtins' cache-policy argument: bit 1 = nt on gfx950
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void spill_store2(__amdgpu_buffer_rsrc_t rs, int lane16, int pair, double v_even,
                                              double v_odd) {
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i_t, make_double2(v_even, v_odd)), rs, lane16,
-                                         pair * 1024, 0);
+                                         pair * 1024, SPILL_AUX);
 }
 __device__ __forceinline__ double2 spill_load2(__amdgpu_buffer_rsrc_t rs, int lane16, int pair) {
-  return __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, pair * 1024, 0));
+  return __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, pair * 1024, SPILL_AUX));
 }
 
 // end of a step: the history ring's writes of this step before the next step's reads.  A team of waves
@@ -1096,9 +1102,27 @@ bool select_sweeps(int mel, bool pair, int W, int rsh, Align3Kernel k[2]) {
 
 }  // namespace
 
+// One work counter per sweep launch, so that nothing has to be zeroed between a chunk's reverse and forward
+// launch: the first 64 bytes of WS_MISC are 16 counters, zeroed together up front (align3_prepare) and again (in
+// stream order, before a reverse launch) whenever a batch of many chunks has used them all.
+constexpr int N_COUNTERS = 16;
+static_assert(N_COUNTERS % 2 == 0, "a chunk's reverse / forward pair of counters must not straddle a re-zero");
+
+int align3_reserve(nvk_ctx *ctx, int64_t n_reads) {
+  int rc = nvk_ws_reserve(ctx, WS_MISC, 256);
+  if (rc) return rc;
+  return nvk_ws_reserve(ctx, WS_RSTATE, (size_t)n_reads * sizeof(int2));
+}
+
+int align3_prepare(nvk_ctx *ctx, int64_t *spill_cap) {
+  NVK_HIP(hipMemsetAsync(ctx->ws[WS_MISC], 0, N_COUNTERS * sizeof(int), ctx->stream));
+  *spill_cap = nvk_spill_cap(ctx, WS_SPILL);
+  return NVK_OK;
+}
+
 int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadMeta *metas, const PlanTotals &tot,
                   const int *order, const int32_t *steps_sorted, int32_t *out_events, int32_t *out_status,
-                  int *d_retry) {
+                  int *d_retry, int64_t spill_cap) {
   static_assert(WS_OFFS < (int)(sizeof(ctx->ws) / sizeof(ctx->ws[0])), "workspace table too small");
   if (a.n_reads == 0) return NVK_OK;
   const int mel = a.mel;
@@ -1107,16 +1131,8 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
     return NVK_ERR_UNSUPPORTED;
   }
   const int max_c = tot.max_c < 1 ? 1 : tot.max_c;
-  int rc = nvk_ws_reserve(ctx, WS_MISC, 256);
-  if (rc) return rc;
-  // One work counter per sweep launch, so that nothing has to be zeroed between a chunk's reverse and forward
-  // launch: the first 64 bytes of WS_MISC are 16 counters, zeroed together up front and again (in stream order,
-  // before a reverse launch) whenever a batch of many chunks has used them all.
-  constexpr int N_COUNTERS = 16;
-  static_assert(N_COUNTERS % 2 == 0, "a chunk's reverse / forward pair of counters must not straddle a re-zero");
   int *counter = (int *)ctx->ws[WS_MISC];
   int launches = 0;
-  NVK_HIP(hipMemsetAsync(d_retry, 0, sizeof(int), ctx->stream));
 
   // Two launches: the LDS rings are sized by the largest skew a launch serves, so the (usual) reads
   // with c <= ALIGN1_C_CAP keep their 16 waves per CU whatever else is in the batch; wide-band reads
@@ -1134,8 +1150,7 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
   if (a.n_reads - n_wide > 0 || max_c <= ALIGN1_C_CAP)
     cls[ncls++] = Cls{max_c < ALIGN1_C_CAP ? max_c : ALIGN1_C_CAP, 1};
   if (max_c > ALIGN1_C_CAP) cls[ncls++] = Cls{max_cw < C_HARD ? max_cw : C_HARD, ALIGN3_TEAM_W};
-  rc = nvk_ws_reserve(ctx, WS_RSTATE, (size_t)a.n_reads * sizeof(int2));
-  if (rc) return rc;
+  int rc = NVK_OK;
   TimerScope ts_align(ctx, NVK_K_ALIGN);
   for (int k = 0; k < ncls; k++) {
     int c = cls[k].hi;
@@ -1181,7 +1196,8 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
     int32_t mxpad = 1;  // the longest read of the batch under the offsets the kernels use (ReadMeta::pad)
     for (int64_t q = 0; q < a.n_reads; q++) mxpad = steps_sorted[q] > mxpad ? steps_sorted[q] : mxpad;
     const int64_t bp_stride = (int64_t)((mxpad + 31) / 32 + 1) * TLk;
-    const int64_t cap = nvk_spill_cap(ctx, WS_SPILL);
+    // (the second class asks again: the first one's chunks may have grown the workspaces)
+    const int64_t cap = (k == 0) ? spill_cap : nvk_spill_cap(ctx, WS_SPILL);
 
     Align3Args g;
     g.metas = metas;
@@ -1246,7 +1262,8 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
       g.L_stride = L_stride;
       g.n_reads = (int)n_chunk;
       g.read_lo = (int)lo;
-      if (launches % N_COUNTERS == 0) NVK_HIP(hipMemsetAsync(counter, 0, N_COUNTERS * sizeof(int), ctx->stream));
+      if (launches > 0 && launches % N_COUNTERS == 0)
+        NVK_HIP(hipMemsetAsync(counter, 0, N_COUNTERS * sizeof(int), ctx->stream));
       g.counter = counter + launches % N_COUNTERS;
       hipLaunchKernelGGL(kern[0], dim3((unsigned)slots_r), dim3(TLk), lds_rev, ctx->stream, g);
       g.counter = counter + (launches + 1) % N_COUNTERS;

@@ -193,10 +193,13 @@ __device__ __forceinline__ void plan_bands_lds(const int32_t *anc, int A, int R,
 //   lo, hi   the lane's span: band + warm-up / pre-roll of the steps into and out of the row
 //   off      sh_x / sh_S once the offsets are fixed
 // The table constants are gathered once per row, in the last phase, which writes the row's RowParam and its two lane
-// records; the constants of the row above come from the neighbouring lane.
+// records; the constants of the row above come from the neighbouring lane.  Only the exact kernel (kernels_align.hip)
+// reads the RowParam table — the sweeps of kernels_align3.hip take the lane records — so it is written on request
+// (write_rows): a third of the phase's bytes, and that phase runs at the write rate of HBM.
 __device__ __forceinline__ void plan_rows_lds(const DeviceModel &dm, const PlanRead &q, int mode, double log_p_in,
                                               int c_cap, int rd, ReadMeta m, ReadMeta *metas, RowParam *rows,
-                                              Lane3 *lane_f, Lane3 *lane_r, int32_t *lane_offs, PlanShared &sh) {
+                                              bool write_rows, Lane3 *lane_f, Lane3 *lane_r, int32_t *lane_offs,
+                                              PlanShared &sh) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int32_t *ref = q.ref, *cb = q.cb, *ca = q.ca;
   const int N = q.N, R = q.R, T = q.T, nb = q.nb, na = q.na, mel = q.mel;
@@ -421,7 +424,7 @@ __device__ __forceinline__ void plan_rows_lds(const DeviceModel &dm, const PlanR
       o.off = OFF(r);
       // (without transition rows: steps r - 1 and r are consecutive bases)
       if (!trans && r > 0 && r + 1 < T) plateau |= (p.mean == o.mean) ? 1 : 0;
-      rp[r] = o;
+      if (write_rows) rp[r] = o;
       if (records) {
         if (r > 0) {  // (lane3_row reads neither lo nor hi of the rows above and below)
           p.bs = BS(r - 1);
@@ -698,7 +701,9 @@ __device__ __forceinline__ void plan_rows_global(const DeviceModel &dm, const Pl
 __global__ __launch_bounds__(PLAN_T, 5) void plan_kernel(DeviceModel dm, BatchArgs a, int mode,
                                                   double log_p_in, int c_cap, ReadMeta *metas,
                                                   RowParam *rows, unsigned long long *bandtmp,
-                                                  Lane3 *lane_f, Lane3 *lane_r, int32_t *lane_offs) {
+                                                  Lane3 *lane_f, Lane3 *lane_r, int32_t *lane_offs, int write_rows) {
+  // write_rows == 0: the RowParam table is left unwritten for the reads planned in LDS (plan_rows_global works in it
+  // and writes it regardless).  lane_f == null: no lane records — with write_rows that is the rows-only pass.
   const int rd = blockIdx.x;
   const int tid = threadIdx.x;
   __shared__ PlanShared sh;
@@ -755,7 +760,7 @@ __global__ __launch_bounds__(PLAN_T, 5) void plan_kernel(DeviceModel dm, BatchAr
     return;
   }
   if (q.R + 1 <= PLAN_BCAP && dm.n <= 0x100000000ll)  // (plan_rows_lds keeps the k-mer ids as 32-bit words)
-    plan_rows_lds(dm, q, mode, log_p_in, c_cap, rd, m, metas, rows, lane_f, lane_r, lane_offs, sh);
+    plan_rows_lds(dm, q, mode, log_p_in, c_cap, rd, m, metas, rows, write_rows != 0, lane_f, lane_r, lane_offs, sh);
   else
     plan_rows_global(dm, q, mode, log_p_in, c_cap, rd, m, metas, rows, bandtmp, lane_f, lane_r, lane_offs, sh);
 }
@@ -970,9 +975,19 @@ __device__ __forceinline__ int order_bucket(const ReadMeta &m, int max_steps) {
 }
 // (max_steps comes from the planner's totals ON THE DEVICE: the order is built behind the planner without a host
 // round trip in between)
-__global__ void order_count_kernel(const ReadMeta *metas, int n, const PlanTotals *tot, int *cnt) {
-  int rd = blockIdx.x * blockDim.x + threadIdx.x;
-  if (rd < n) atomicAdd(&cnt[order_bucket(metas[rd], tot->max_steps)], 1);
+// Both kernels count in LDS first: an atomicAdd per read on a handful of bucket counters in global memory is served
+// one read after the other (the same-address effect of DESIGN.md 5.3, item 1); a block's reads meet in its own LDS
+// counters and the block then goes to global memory once per bucket it holds reads of.
+__global__ __launch_bounds__(256) void order_count_kernel(const ReadMeta *metas, int n, const PlanTotals *tot,
+                                                          int *cnt) {
+  __shared__ int lc[ORD_N];
+  for (int b = threadIdx.x; b < ORD_N; b += blockDim.x) lc[b] = 0;
+  __syncthreads();
+  const int rd = blockIdx.x * blockDim.x + threadIdx.x;
+  if (rd < n) atomicAdd(&lc[order_bucket(metas[rd], tot->max_steps)], 1);
+  __syncthreads();
+  for (int b = threadIdx.x; b < ORD_N; b += blockDim.x)
+    if (lc[b]) atomicAdd(&cnt[b], lc[b]);
 }
 __global__ void order_scan_kernel(int *cnt) {  // one wave, two buckets per lane: cnt[b] -> first position of bucket b; cnt[ORD_N+b] = 0
   int lane = threadIdx.x;
@@ -984,13 +999,27 @@ __global__ void order_scan_kernel(int *cnt) {  // one wave, two buckets per lane
 }
 // steps_out (or null): the steps of the reads in the order they are handed out (sizes the per-read spill slots of
 // kernels_align3.hip)
-__global__ void order_fill_kernel(const ReadMeta *metas, int n, const PlanTotals *tot, int *cnt, int *order,
-                                  int32_t *steps_out) {
-  int rd = blockIdx.x * blockDim.x + threadIdx.x;
+// A block reserves one range per bucket (cnt[ORD_N + b]: the bucket's positions handed out so far) and places its
+// reads in it by their rank among the block's reads of that bucket.
+__global__ __launch_bounds__(256) void order_fill_kernel(const ReadMeta *metas, int n, const PlanTotals *tot, int *cnt,
+                                                         int *order, int32_t *steps_out) {
+  __shared__ int lc[ORD_N];  // the block's reads per bucket, then the first position of its range
+  for (int b = threadIdx.x; b < ORD_N; b += blockDim.x) lc[b] = 0;
+  __syncthreads();
+  const int rd = blockIdx.x * blockDim.x + threadIdx.x;
+  ReadMeta m;
+  int b = 0, rank = 0;
   if (rd < n) {
-    const ReadMeta m = metas[rd];
-    int b = order_bucket(m, tot->max_steps);
-    const int pos = cnt[b] + atomicAdd(&cnt[ORD_N + b], 1);
+    m = metas[rd];
+    b = order_bucket(m, tot->max_steps);
+    rank = atomicAdd(&lc[b], 1);
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < ORD_N; k += blockDim.x)
+    if (lc[k]) lc[k] = cnt[k] + atomicAdd(&cnt[ORD_N + k], lc[k]);
+  __syncthreads();
+  if (rd < n) {
+    const int pos = lc[b] + rank;
     order[pos] = rd;
     if (steps_out) steps_out[pos] = (m.status == NVK_READ_OK) ? m.pad : 0;
   }
@@ -1044,20 +1073,30 @@ int launch_order(nvk_ctx *ctx, const ReadMeta *metas, int64_t n_reads, const Pla
 
 int launch_plan(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int mode,
                 ReadMeta *metas, RowParam *rows, unsigned long long *bandtmp, PlanTotals *totals,
-                void *lane_f, void *lane_r, int32_t *lane_offs) {
-  NVK_HIP(hipMemsetAsync(totals, 0, sizeof(PlanTotals), ctx->stream));
-  if (a.n_reads == 0) return NVK_OK;
+                void *lane_f, void *lane_r, int32_t *lane_offs, int write_rows,
+                const std::function<int()> *meanwhile) {
+  // totals == null: a second pass over a planned batch (the rows-only pass), whose totals stand
+  if (totals) NVK_HIP(hipMemsetAsync(totals, 0, sizeof(PlanTotals), ctx->stream));
+  if (a.n_reads == 0) return meanwhile ? (*meanwhile)() : NVK_OK;
+  int rc = NVK_OK;
   {
     TimerScope ts(ctx, NVK_K_PLAN);
     // the transition constant comes from the host libm, like the model's ac/mc (kmer_model.cpp:77)
     const double log_p_in = log(0.01);
     hipLaunchKernelGGL(plan_kernel, dim3((unsigned)a.n_reads), dim3(PLAN_T), 0, ctx->stream, dm, a, mode,
-                       log_p_in, ALIGN1_C_CAP, metas, rows, bandtmp, (Lane3 *)lane_f, (Lane3 *)lane_r, lane_offs);
-    hipLaunchKernelGGL(plan_totals_kernel, dim3((unsigned)((a.n_reads + 255) / 256)), dim3(256), 0, ctx->stream,
-                       metas, (int)a.n_reads, ALIGN1_C_CAP, totals);
+                       log_p_in, ALIGN1_C_CAP, metas, rows, bandtmp, (Lane3 *)lane_f, (Lane3 *)lane_r, lane_offs,
+                       write_rows);
+    if (totals)
+      hipLaunchKernelGGL(plan_totals_kernel, dim3((unsigned)((a.n_reads + 255) / 256)), dim3(256), 0, ctx->stream,
+                         metas, (int)a.n_reads, ALIGN1_C_CAP, totals);
+    // the caller's host work that needs nothing of the plan: the planner is the first long kernel of a batch, and
+    // what the host does here it does not do between the planner's end and the first sweep.  (Behind stop(): with
+    // timing on the scope's end waits for the kernels, and fills queued here stay out of the timed interval.)
+    ts.stop();
+    if (meanwhile) rc = (*meanwhile)();
   }
   NVK_HIP(hipGetLastError());
-  return NVK_OK;
+  return rc;
 }
 
 int launch_plan_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobbling,

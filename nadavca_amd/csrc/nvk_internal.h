@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
 #include <vector>
 
 #include "../../include/nadavca_hip.h"
@@ -93,6 +94,9 @@ struct nvk_ctx {
   hipEvent_t ev0, ev1;
   // stats of the last batch
   int64_t last_cells, last_steps, last_spill_bytes;
+  // 1 while ws[WS_ROWS] holds the RowParam table of the batch planned last (plan_batch in api.hip clears it before it
+  // plans and sets it when the planner wrote the table); the exact align kernel is launched only with it set
+  int rows_current;
   int64_t last_retries;  // reads of the last refine batch redone by the exact kernel
   int64_t last_ties;     // reads of the last refine batch with a path decision inside the tie margin
   int64_t last_ties_exact, last_ties_near, last_ties_ulp;  // ... per class (NVK_TIE_EXACT / _NEAR / _ULP)
@@ -135,7 +139,11 @@ int nvk_ws_reserve(nvk_ctx *ctx, int which, size_t bytes);
 struct TimerScope {
   nvk_ctx *ctx;
   int id;
+  bool stopped = false;
   TimerScope(nvk_ctx *c, int kid);
+  // ends the timed interval here; the scope's end then only waits for it and reads it, so that host work between the
+  // two runs beside the kernels with timing on as it does with timing off
+  void stop();
   ~TimerScope();
 };
 
@@ -229,10 +237,15 @@ struct BatchArgs {
 enum { PLAN_ALIGN_TRANS = 0, PLAN_ALIGN_PLAIN = 1 };
 
 // lane_f / lane_r / lane_offs: where the planner leaves the per-sweep lane records of kernels_align3.hip (lane3.h),
-// or null
+// or null.  write_rows: whether the RowParam table is written — only the exact kernel (launch_align,
+// launch_align_retry) reads it; without it `rows` holds nothing to rely on (reads of more than PLAN_BCAP band rows are
+// planned in it and leave their rows there).  totals == null: a second pass over a batch already planned, which leaves
+// the device totals alone and rewrites the metas with the values they have.  meanwhile (or null): host work of the
+// caller that depends on nothing the planner finds, called once the planner is queued, so that it runs beside it.
 int launch_plan(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int mode,
                 ReadMeta *metas, RowParam *rows, unsigned long long *bandtmp, PlanTotals *totals,
-                void *lane_f, void *lane_r, int32_t *lane_offs);
+                void *lane_f, void *lane_r, int32_t *lane_offs, int write_rows,
+                const std::function<int()> *meanwhile = nullptr);
 // order[0..n) = read indices in launch order (class-major, longest first; ctx->ws[WS_ORDER]); tot_dev: the planner's
 // totals on the device; steps_out (device, n ints, or null): the reads' step counts in that order
 int launch_order(nvk_ctx *ctx, const ReadMeta *metas, int64_t n_reads, const PlanTotals *tot_dev, int **order,
@@ -283,11 +296,19 @@ int launch_align_retry(nvk_ctx *ctx, const BatchArgs &a, int transitions, const 
                        const RowParam *rows, const PlanTotals &tot, int32_t *out_events,
                        int32_t *out_status);
 // scaled-double kernel (kernels_align3.hip).  order / steps_sorted: launch order (device) and the reads' step counts
-// in that order (host), both from plan_batch; d_retry (device int, zeroed here): reads it hands to the exact kernel.
-// Asynchronous: nothing is waited for.
+// in that order (host), from plan_batch_queue / plan_batch_wait (api.hip); d_retry (device int, zero in stream order before this call): reads it
+// hands to the exact kernel.  Asynchronous: nothing is waited for.
+// What the sweeps need that depends neither on the planner's totals nor on the step counts is set up by the two calls
+// before it, so that the host does it while the planner runs and not between the planner's end and the first sweep:
+//   align3_reserve   the workspaces sized by the batch alone; before the planner is queued (a workspace that grows
+//                    drains the stream first)
+//   align3_prepare   queues the zeroing of the sweep counters and asks for the spill cap (*spill_cap: the bytes the
+//                    first class's chunks may take); after every workspace of the planner is reserved
+int align3_reserve(nvk_ctx *ctx, int64_t n_reads);
+int align3_prepare(nvk_ctx *ctx, int64_t *spill_cap);
 int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadMeta *metas, const PlanTotals &tot,
                   const int *order, const int32_t *steps_sorted, int32_t *out_events, int32_t *out_status,
-                  int *d_retry);
+                  int *d_retry, int64_t spill_cap);
 int launch_expected(nvk_ctx *ctx, const DeviceModel &dm, int64_t n_reads, int64_t total_ref,
                     const int32_t *reference, const int64_t *ref_off, const int32_t *cb,
                     const int64_t *cb_off, const int32_t *ca, const int64_t *ca_off, double *out);

@@ -12,10 +12,12 @@
 #include <vector>
 #include <random>
 #include <cstdio>
+#include <cstdlib>
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); return 2; } } while (0)
 template <class T> static T *up(const std::vector<T> &v) { T *d = nullptr; if (hipMalloc(&d, v.size() * sizeof(T) + 64) != hipSuccess) return nullptr; hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice); return d; }
 int main(int argc, char **argv) {
   const int n = 10000, bw = 150, mel = 2, k = 6;
+  const int write_rows = argc > 2 ? atoi(argv[2]) : 0;  // ubench_plan LABEL 1: with the row table of the exact kernel
   std::mt19937_64 rng(1);
   std::vector<int64_t> so{0}, ro{0}, ao{0}, bo{0}, co{0};
   std::vector<int32_t> ref, anc, cb, ca;
@@ -45,7 +47,7 @@ int main(int argc, char **argv) {
   for (int it = 0; it < 13; it++) {
     CK(hipMemset(tot, 0, sizeof(PlanTotals)));
     CK(hipEventRecord(e0, 0));
-    hipLaunchKernelGGL(plan_kernel, dim3(n), dim3(PLAN_T), 0, 0, dm, a, (int)PLAN_ALIGN_TRANS, log(0.01), ALIGN1_C_CAP, metas, rows, bandtmp, lf, lr, offs);
+    hipLaunchKernelGGL(plan_kernel, dim3(n), dim3(PLAN_T), 0, 0, dm, a, (int)PLAN_ALIGN_TRANS, log(0.01), ALIGN1_C_CAP, metas, rows, bandtmp, lf, lr, offs, write_rows);
     hipLaunchKernelGGL(plan_totals_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, metas, n, ALIGN1_C_CAP, tot);
     CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1)); CK(hipGetLastError());
     float ms; CK(hipEventElapsedTime(&ms, e0, e1));
