@@ -49,101 +49,21 @@ __device__ __forceinline__ int read_is_bad(const DeviceModel &dm, const BatchArg
   return bad;
 }
 
-// bands of the R+1 boundary rows (dtw.cpp:7-35): "later anchor overwrites", then
-// prefix-max / suffix-min.  Results are left in the low words of tbs[] / tbe[].
-__device__ void plan_bands(const int32_t *anc, int A, int R, int N, int bw,
-                           unsigned long long *tbs, unsigned long long *tbe, int lane,
-                           bool work = true) {
-  // `work`: in a multi-wave block one wave does the (wave-scan based) work, every wave takes the barriers
-  // scratch word = (anchor ordinal + 1) << 32 | payload ; atomicMax keeps the last anchor
-  for (int j = lane; work && j <= R; j += 64) {
-    tbs[j] = 0ull;
-    tbe[j] = 0ull;
-  }
-  __syncthreads();
-  for (int j = lane; work && j < A; j += 64) {
-    int s = anc[2 * j], ri = anc[2 * j + 1];
-    long long lo = (long long)s - bw;
-    long long hi = (long long)s + bw;
-    unsigned int vbs = (unsigned int)(lo > 0 ? lo : 0);  // max(0, s - bw)
-    // min(N, s + bw); a negative value cannot be packed: clamp to -1 -> flagged as bad band
-    unsigned int vbe = (unsigned int)((hi < N ? (hi < -1 ? -1 : hi) : N) + 1);
-    unsigned long long tag = ((unsigned long long)(j + 1)) << 32;
-    atomicMax(&tbs[ri], tag | vbs);
-    atomicMax(&tbe[ri], tag | vbe);
-  }
-  __syncthreads();
-  // the row table stores bands as int32 inside RowParam; first write raw per-base bands into
-  // the scratch (low words), scanning in chunks of 64 with a carry
-  int carry = 0;
-  for (int base = 0; work && base <= R; base += 64) {
-    int j = base + lane;
-    int v = 0;
-    if (j <= R) {
-      unsigned long long w = tbs[j];
-      v = (w >> 32) ? (int)(unsigned int)(w & 0xffffffffu) : 0;
-    }
-    v = max(wave_scan_max(v, lane), carry);
-    carry = __shfl(v, 63, 64);
-    if (j <= R) tbs[j] = (unsigned long long)(unsigned int)v;
-  }
-  carry = N;
-  for (int base = (R / 64) * 64; work && base >= 0; base -= 64) {
-    int j = base + lane;
-    int v = N;
-    if (j <= R) {
-      unsigned long long w = tbe[j];
-      v = (w >> 32) ? (int)(unsigned int)(w & 0xffffffffu) - 1 : N;
-    } else {
-      v = 0x7fffffff;
-    }
-    v = min(wave_scan_min_rev(v, lane), carry);
-    carry = __shfl(v, 0, 64);
-    if (j <= R) tbe[j] = (unsigned long long)(unsigned int)v;
-  }
-  __syncthreads();
-
-}
-
-// One block of PLAN_T threads per read.  What the planner keeps between its phases — the bands, the spans, the row
-// offsets — is integers of one read, so for a read of up to PLAN_BCAP band rows it stays in LDS (plan_rows_lds) and
-// the row table and the lane records are written once, complete, at the end; a longer read goes through global
-// scratch and the row table (plan_rows_global).  The choice is per read, so it is uniform for the block and every
-// wave takes every barrier of the path.
-constexpr int PLAN_T = 256;
-constexpr int PLAN_VT = 2048;    // rows whose per-row offsets fit the LDS arrays (more: uniform offsets)
-constexpr int PLAN_BCAP = 1024;  // band rows (R + 1) of a read planned in LDS
-
-struct PlanShared {
-  // plan_rows_global: k | x | S of the offsets, PLAN_VT ints each.
-  // plan_rows_lds:    x | S | bs, be (PLAN_BCAP ints each); the u64 tag|payload words of the bands, dead once bs / be
-  //                   are written, lie under x and S, which are born after them.
-  unsigned long long pool[3 * PLAN_VT / 2];
-  unsigned int ids[PLAN_BCAP];  // plan_rows_lds: the k-mer id of every base (ids below 2^32: plan_kernel)
-  unsigned long long cells;
-  int c, cw, var;
-};
-static_assert(2 * PLAN_BCAP * 8 <= 2 * PLAN_VT * 4 && 2 * PLAN_BCAP <= PLAN_VT, "LDS layout of plan_rows_lds");
-
-// one read as the planner's phases see it
-struct PlanRead {
-  const int32_t *ref, *cb, *ca, *anc;
-  int64_t r0;
-  int N, R, A, T, nb, na, bw, mel;
-};
-
-// plan_bands for a block of PLAN_T threads, in LDS: the same tag|payload words and scans, the bands left as int32
-// in bs[0..R] / be[0..R].  The two scans are independent: waves 0 and 1 run one each.
-__device__ __forceinline__ void plan_bands_lds(const int32_t *anc, int A, int R, int N, int bw,
-                                               unsigned long long *tbs, unsigned long long *tbe, int *bs, int *be,
-                                               int tid) {
+// bands of the R+1 boundary rows (dtw.cpp:7-35): "later anchor overwrites", then prefix-max / suffix-min.  The
+// `nthreads` threads of one block cooperate (tid = this thread).  tbs / tbe: R+1 scratch words each, LDS or global;
+// bs / be: where the bands go, as int32 arrays of their own or (W = the scratch words' type, bs == tbs, be == tbe) in
+// place, in the low words.  The two scans are independent: waves 0 and 1 run one each where the block has two waves.
+template <class W>
+__device__ __forceinline__ void plan_bands(const int32_t *anc, int A, int R, int N, int bw, unsigned long long *tbs,
+                                           unsigned long long *tbe, W *bs, W *be, int tid, int nthreads) {
   const int lane = tid & 63, wv = tid >> 6;
-  for (int j = tid; j <= R; j += PLAN_T) {
+  // scratch word = (anchor ordinal + 1) << 32 | payload ; atomicMax keeps the last anchor
+  for (int j = tid; j <= R; j += nthreads) {
     tbs[j] = 0ull;
     tbe[j] = 0ull;
   }
   __syncthreads();
-  for (int j = tid; j < A; j += PLAN_T) {
+  for (int j = tid; j < A; j += nthreads) {
     int s = anc[2 * j], ri = anc[2 * j + 1];
     long long lo = (long long)s - bw;
     long long hi = (long long)s + bw;
@@ -166,9 +86,10 @@ __device__ __forceinline__ void plan_bands_lds(const int32_t *anc, int A, int R,
       }
       v = max(wave_scan_max_dpp(v), carry);
       carry = __builtin_amdgcn_readlane(v, 63);
-      if (j <= R) bs[j] = v;
+      if (j <= R) bs[j] = (W)(unsigned int)v;
     }
-  } else if (wv == 1) {
+  }
+  if (wv == (nthreads > 64 ? 1 : 0)) {
     int carry = N;
     for (int base = (R / 64) * 64; base >= 0; base -= 64) {
       int j = base + 63 - lane;  // descending rows over the lanes: the suffix minimum is a prefix scan
@@ -181,14 +102,75 @@ __device__ __forceinline__ void plan_bands_lds(const int32_t *anc, int A, int R,
       }
       v = min(wave_scan_min_dpp(v), carry);
       carry = __builtin_amdgcn_readlane(v, 63);
-      if (j <= R) be[j] = v;
+      if (j <= R) be[j] = (W)(unsigned int)v;
     }
   }
   __syncthreads();
 }
 
-// A read of at most PLAN_BCAP band rows.  A row's integers are functions of the bands next to it and of its min
-// event length (with transition rows: of its parity), so every phase takes them from the bands in LDS:
+// One block of PLAN_T threads per read.  What the planner keeps between its phases — the bands, the spans, the row
+// offsets — is integers of one read.  The spans and offsets are functions of the bands, and the bands and the bases'
+// k-mer ids are all that differs between reads: for a read of up to PLAN_BCAP band rows they stay in LDS
+// (PlanStoreLds), for a longer one the bands go through global scratch and the ids are formed where they are used
+// (PlanStoreGlobal).  plan_rows is the planner, written once over such a store.  The choice is per read, so it is
+// uniform for the block and every wave takes every barrier.
+constexpr int PLAN_T = 256;
+constexpr int PLAN_VT = 2048;    // rows whose per-row offsets fit the LDS arrays (more: uniform offsets)
+constexpr int PLAN_BCAP = 1024;  // band rows (R + 1) of a read planned in LDS
+
+struct PlanShared {
+  // x | S of the offsets (PLAN_VT ints each) and, for PlanStoreLds, bs, be (PLAN_BCAP ints each) behind them; the u64
+  // tag|payload words of its bands, dead once bs / be are written, lie under x and S, which are born after them.
+  unsigned long long pool[3 * PLAN_VT / 2];
+  unsigned int ids[PLAN_BCAP];  // PlanStoreLds: the k-mer id of every base (ids below 2^32: plan_kernel)
+  unsigned long long cells;
+  int c, cw, var;
+};
+static_assert(2 * PLAN_BCAP * 8 <= 2 * PLAN_VT * 4 && 2 * PLAN_BCAP <= PLAN_VT, "LDS layout of PlanStoreLds");
+
+// one read as the planner's phases see it
+struct PlanRead {
+  const int32_t *ref, *cb, *ca, *anc;
+  int64_t r0;
+  int N, R, A, T, nb, na, bw, mel;
+};
+
+// Where a read's bands and k-mer ids are.  bands(): plan_bands into the store, by the whole block; bs(j) / be(j): the
+// band of boundary row j after it; fill_ids(first, stride): the threads that call it share the bases out, once, for
+// kid(i), the k-mer id of base i (behind the next barrier).
+struct PlanStoreLds {
+  PlanShared &sh;
+  __device__ __forceinline__ int *b() const { return (int *)sh.pool + 2 * PLAN_VT; }
+  __device__ __forceinline__ void bands(const PlanRead &q, int tid) const {
+    plan_bands(q.anc, q.A, q.R, q.N, q.bw, sh.pool, sh.pool + PLAN_BCAP, b(), b() + PLAN_BCAP, tid, PLAN_T);
+  }
+  __device__ __forceinline__ int bs(int j) const { return b()[j]; }
+  __device__ __forceinline__ int be(int j) const { return b()[PLAN_BCAP + j]; }
+  // A base's id serves its own row and, with transition rows, the two transition rows next to it, and the last phase
+  // starts at the table gathers instead of at the reference loads.
+  __device__ __forceinline__ void fill_ids(const DeviceModel &dm, const PlanRead &q, int first, int stride) const {
+    for (int i = first; i < q.R; i += stride)
+      sh.ids[i] = (unsigned int)kmer_id(dm, q.ref, q.R, q.cb, q.nb, q.ca, q.na, i);
+  }
+  __device__ __forceinline__ unsigned int kid(const DeviceModel &, const PlanRead &, int i) const { return sh.ids[i]; }
+};
+// per read 2*(R+1) u64 scratch words of bandtmp, the bands in their low words; nothing of the ids is kept, which is
+// also the path of a table of 2^32 k-mers or more
+struct PlanStoreGlobal {
+  unsigned long long *tbs, *tbe;
+  __device__ __forceinline__ void bands(const PlanRead &q, int tid) const {
+    plan_bands(q.anc, q.A, q.R, q.N, q.bw, tbs, tbe, tbs, tbe, tid, PLAN_T);
+  }
+  __device__ __forceinline__ int bs(int j) const { return (int)(unsigned int)tbs[j]; }
+  __device__ __forceinline__ int be(int j) const { return (int)(unsigned int)tbe[j]; }
+  __device__ __forceinline__ void fill_ids(const DeviceModel &, const PlanRead &, int, int) const {}
+  __device__ __forceinline__ int64_t kid(const DeviceModel &dm, const PlanRead &q, int i) const {
+    return kmer_id(dm, q.ref, q.R, q.cb, q.nb, q.ca, q.na, i);
+  }
+};
+
+// The planner of one read.  A row's integers are functions of the bands next to it and of its min event length (with
+// transition rows: of its parity), so every phase takes them from the bands in the store:
 //   bs, be   the band of the row's boundary
 //   lo, hi   the lane's span: band + warm-up / pre-roll of the steps into and out of the row
 //   off      sh_x / sh_S once the offsets are fixed
@@ -196,23 +178,22 @@ __device__ __forceinline__ void plan_bands_lds(const int32_t *anc, int A, int R,
 // records; the constants of the row above come from the neighbouring lane.  Only the exact kernel (kernels_align.hip)
 // reads the RowParam table — the sweeps of kernels_align3.hip take the lane records — so it is written on request
 // (write_rows): a third of the phase's bytes, and that phase runs at the write rate of HBM.
-__device__ __forceinline__ void plan_rows_lds(const DeviceModel &dm, const PlanRead &q, int mode, double log_p_in,
-                                              int c_cap, int rd, ReadMeta m, ReadMeta *metas, RowParam *rows,
-                                              bool write_rows, Lane3 *lane_f, Lane3 *lane_r, int32_t *lane_offs,
-                                              PlanShared &sh) {
+template <class Store>
+__device__ __forceinline__ void plan_rows(const Store st, const DeviceModel &dm, const PlanRead &q, int mode,
+                                          double log_p_in, int c_cap, int rd, ReadMeta m, ReadMeta *metas,
+                                          RowParam *rows, bool write_rows, Lane3 *lane_f, Lane3 *lane_r,
+                                          int32_t *lane_offs, PlanShared &sh) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int32_t *ref = q.ref, *cb = q.cb, *ca = q.ca;
-  const int N = q.N, R = q.R, T = q.T, nb = q.nb, na = q.na, mel = q.mel;
+  const int N = q.N, T = q.T, mel = q.mel;
   const bool trans = (mode == PLAN_ALIGN_TRANS);
   constexpr int VT = PLAN_VT;
   int *sh_x = (int *)sh.pool, *sh_S = sh_x + VT;
-  int *sh_bs = sh_S + VT, *sh_be = sh_bs + PLAN_BCAP;
-  plan_bands_lds(q.anc, q.A, R, N, q.bw, sh.pool, sh.pool + PLAN_BCAP, sh_bs, sh_be, tid);
+  st.bands(q, tid);
 
   // min event length of step r -> r + 1 (RowParam::mel)
   auto rmel = [=](int r) { return (r + 1 < T && !(trans && (r & 1))) ? mel : 0; };
-  auto BS = [=](int r) { return sh_bs[trans ? (r + 1) >> 1 : r]; };
-  auto BE = [=](int r) { return sh_be[trans ? (r + 1) >> 1 : r]; };
+  auto BS = [=](int r) { return st.bs(trans ? (r + 1) >> 1 : r); };
+  auto BE = [=](int r) { return st.be(trans ? (r + 1) >> 1 : r); };
   // forward lane of row r runs i = lo_r .. be_r, reverse lane i = hi_r .. bs_r  (see kernels_align.hip)
   auto LO = [=](int r) {
     int lo = BS(r);
@@ -231,7 +212,11 @@ __device__ __forceinline__ void plan_rows_lds(const DeviceModel &dm, const PlanR
     return hi;
   };
 
-  // --- band checks, cell count and skew (the `idle` rule: plan_rows_global) ------------------------------------
+  // --- band checks, cell count and skew -----------------------------------------------------------------------
+  // A lane starts its next row `idle` steps after it has left the previous one: the density of its first step
+  // on the new row (and, with transition rows, the one its pair partner holds for the step after) was
+  // evaluated with the old row's constants, and kernels_align3 lets those stale values pass through steps
+  // on which the lane is outside its span instead of re-evaluating them at every row switch.
   const int idle = trans ? 2 : 1;
   int badband = 0;
   long long cells = 0;
@@ -254,9 +239,12 @@ __device__ __forceinline__ void plan_rows_lds(const DeviceModel &dm, const PlanR
     atomicMax(&sh.c, cneed);
   }
   __syncthreads();
-  const int c = sh.c;
-  cells = (long long)sh.cells;
-  const bool team = (c > c_cap);  // (teams of waves: plan_rows_global)
+  const int c = sh.c;  // (sh.cells is complete too, and is read where the meta is written)
+  // A band this wide for its row spacing (skew above the main launch's cap) is served by a TEAM of waves
+  // (kernels_align3.hip): 64 * ALIGN3_TEAM_W lanes, one row each, so a lane's next row lies that many rows
+  // on and the skew it needs is that of the row pair (r - 64 W, r) — on long reads with wide bands the band
+  // moves on by more samples in 256 rows than it is wide, and the skew falls from ~28 to ~3.
+  const bool team = (c > c_cap);
   int cw = 0;
   if (team) {
     constexpr int TL = 64 * ALIGN3_TEAM_W;
@@ -273,7 +261,23 @@ __device__ __forceinline__ void plan_rows_lds(const DeviceModel &dm, const PlanR
     cw = sh.cw;
   }
 
-  // --- per-row time offsets: the fixed point of plan_rows_global, its constraint k[r] taken from the bands ------
+  // --- per-row time offsets (variable skew, used by kernels_align3.hip) ---------------------------
+  // The uniform mapping t = i + c*r pays the worst pair of rows (r - 64, r) of the read on every row.
+  // Here cell (r, i) is computed at step t = i + off[r] with the LEAST offsets that satisfy
+  //   g[r] <= off[r] - off[r-1] <= c            (neighbour values wait at most c + mel steps in LDS)
+  //   off[r] - off[r-64] >= hi[r-64] - lo[r] + 1 + idle  (a lane is free, and idle for `idle` steps, before its
+  //                                                      next row starts)
+  // (off[r] = c*r is one solution, so the least one exists and needs no more steps).  The lower bound
+  // g[r] is what keeps the neighbour's value at least one step old, age = gap + mel >= 1: 1 for a row
+  // fed without emission (mel 0), 1 - mel for a row fed by an emitting step — with transition rows the
+  // two alternate, so a pair of rows needs no skew at all — and never so low that a row would start or
+  // end before the row above it (the kernel's bookkeeping of the oldest open row relies on that order).
+  // Without transition rows, and for min event lengths above 2, g[r] = max(mel - 1, 1).
+  // With S[r] = g[1] + .. + g[r] and x[r] = off[r] - S[r] the first lower bound and the second are a
+  // prefix maximum per block of 64 rows (the second's constant k[r] = hi[r-64] - lo[r] + 1 + idle - (S[r] - S[r-64])
+  // is taken from the bands), and the upper bound is a suffix maximum of off[r] - c*r; both are iterated to
+  // the fixed point by wave 0 (2-4 rounds on config-shaped reads).  Reads with more rows than the LDS arrays
+  // hold, and team reads, keep the uniform offsets.
   const int gmin = max(mel - 1, 1);
   const bool neg_gaps = trans && mel <= 2;
   const bool fixp = !team && T <= VT && T > 64 && (neg_gaps || c > gmin);
@@ -291,13 +295,10 @@ __device__ __forceinline__ void plan_rows_lds(const DeviceModel &dm, const PlanR
     }
   }
   __syncthreads();
-  // The fixed point is wave 0's alone.  Beside it the other waves work out the k-mer id of every base, once: a
-  // base's id serves its own row and, with transition rows, the two transition rows next to it, and the last phase
-  // then starts at the table gathers instead of at the reference loads.
+  // The fixed point is wave 0's alone.  Beside it the other waves work out the k-mer id of every base, once, where
+  // the store keeps them.
   const int t0 = fixp ? 64 : 0;
-  if (tid >= t0) {
-    for (int i = tid - t0; i < R; i += PLAN_T - t0) sh.ids[i] = (unsigned int)kmer_id(dm, ref, R, cb, nb, ca, na, i);
-  }
+  if (tid >= t0) st.fill_ids(dm, q, tid - t0, PLAN_T - t0);
   {
     if (fixp && tid < 64) {  // S: inclusive prefix sum, block by block
       int carry = 0;
@@ -396,13 +397,13 @@ __device__ __forceinline__ void plan_rows_lds(const DeviceModel &dm, const PlanR
       if (trans && (r & 1)) {
         // transition step between base r/2 and r/2+1: constant log(0.01), -inf on equal means
         int i = r / 2;
-        double m1 = dm.mean[sh.ids[i]];
-        double m2 = dm.mean[sh.ids[i + 1]];
+        double m1 = dm.mean[st.kid(dm, q, i)];
+        double m2 = dm.mean[st.kid(dm, q, i + 1)];
         o.ac = (m1 == m2) ? -INFINITY : log_p_in;
         plateau |= (m1 == m2) ? 1 : 0;
       } else {
         int i = trans ? r / 2 : r;
-        const unsigned int id = sh.ids[i];
+        const auto id = st.kid(dm, q, i);
         o.mean = dm.mean[id];
         o.ac = dm.ac[id];
         o.mc = dm.mc[id];
@@ -458,240 +459,10 @@ __device__ __forceinline__ void plan_rows_lds(const DeviceModel &dm, const PlanR
     m.t_min = t_min;
     m.n_steps = t_max - t_min + 1;
     m.pad = hi_top + OFF(T - 1) - t_min + 1;  // steps under the per-row offsets ...
-    m.pad = (m.pad + 31) & ~31;               // ... in whole blocks of 32 (plan_rows_global)
-    m.cells = cells;
-    m.rsv = plateau ? 1 : 0;
-    if (badband) m.status = NVK_READ_BAD_BAND;
-    metas[rd] = m;  // (the batch totals: plan_totals_kernel)
-  }
-}
-
-// A read of more band rows than the LDS arrays hold: the bands go through bandtmp (per read 2*(R+1) u64 scratch words
-// at bandtmp[2*(ref_off+j) ...]), the rows' integers through the row table.  The band scans run on wave 0, the
-// per-row work (k-mer ids, model gathers, row records) on all waves.
-__device__ __forceinline__ void plan_rows_global(const DeviceModel &dm, const PlanRead &q, int mode, double log_p_in,
-                                                 int c_cap, int rd, ReadMeta m, ReadMeta *metas, RowParam *rows,
-                                                 unsigned long long *bandtmp, Lane3 *lane_f, Lane3 *lane_r,
-                                                 int32_t *lane_offs, PlanShared &sh) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int32_t *ref = q.ref, *cb = q.cb, *ca = q.ca, *anc = q.anc;
-  const int64_t r0 = q.r0;
-  const int N = q.N, R = q.R, A = q.A, T = q.T, nb = q.nb, na = q.na, bw = q.bw, mel = q.mel;
-  unsigned long long *tbs = bandtmp + 2 * (r0 + rd);
-  unsigned long long *tbe = tbs + (R + 1);
-  plan_bands(anc, A, R, N, bw, tbs, tbe, lane, tid < 64);
-
-  // --- row table -----------------------------------------------------------------------------
-  RowParam *rp = rows + m.row_off;
-  int badband = 0;
-  int plateau = 0;  // two adjacent bases with the same k-mer level (NVK_TIE_PLATEAU)
-  long long cells = 0;
-  for (int r = tid; r < T; r += PLAN_T) {
-    RowParam p;
-    int bidx = (mode == PLAN_ALIGN_TRANS) ? (r + 1) / 2 : r;
-    p.bs = (int)(unsigned int)tbs[bidx];
-    p.be = (int)(unsigned int)tbe[bidx];
-    if (p.be < p.bs) badband = 1;
-    cells += (long long)(p.be - p.bs + 1);
-    p.lo = p.bs;
-    p.hi = p.be;
-    p.mean = 0.0;
-    p.ac = 0.0;
-    p.mc = 0.0;
-    p.mel = 0;
-    p.off = 0;
-    if (r + 1 < T) {
-      if (mode == PLAN_ALIGN_TRANS && (r & 1)) {
-        // transition step between base r/2 and r/2+1: constant log(0.01), -inf on equal means
-        int i = r / 2;
-        double m1 = dm.mean[kmer_id(dm, ref, R, cb, nb, ca, na, i)];
-        double m2 = dm.mean[kmer_id(dm, ref, R, cb, nb, ca, na, i + 1)];
-        p.ac = (m1 == m2) ? -INFINITY : log_p_in;
-        p.mel = 0;
-        plateau |= (m1 == m2) ? 1 : 0;
-      } else {
-        int i = (mode == PLAN_ALIGN_TRANS) ? r / 2 : r;
-        int64_t id = kmer_id(dm, ref, R, cb, nb, ca, na, i);
-        p.mean = dm.mean[id];
-        p.ac = dm.ac[id];
-        p.mc = dm.mc[id];
-        p.mel = mel;
-      }
-    }
-    rp[r] = p;
-  }
-  badband = __syncthreads_or(badband);
-  if (mode != PLAN_ALIGN_TRANS)  // (without transition rows: steps r and r + 1 are consecutive bases)
-    for (int r = tid; r + 2 < T; r += PLAN_T) plateau |= (rp[r].mean == rp[r + 1].mean) ? 1 : 0;
-  plateau = __syncthreads_or(plateau);
-  cells = wave_sum(cells);
-  if (lane == 0) atomicAdd(&sh.cells, (unsigned long long)cells);
-  __syncthreads();
-
-  // --- occupancy intervals (band + warm-up + pre-roll) and skew ---------------------------------
-  // forward lane of row r runs i = lo_r .. be_r, reverse lane i = hi_r .. bs_r  (see kernels_align.hip)
-  int cneed = 1;
-  for (int r = tid; r < T; r += PLAN_T) {
-    int lo = rp[r].bs, hi = rp[r].be;
-    if (r > 0) {
-      int pm = rp[r - 1].mel;
-      lo = min(lo, rp[r - 1].bs + pm) - max(pm - 1, 0);
-    }
-    if (r + 1 < T) {
-      int pm = rp[r].mel;
-      hi = max(hi, rp[r + 1].be - pm) + max(pm - 1, 0);
-    }
-    rp[r].lo = lo;
-    rp[r].hi = hi;
-  }
-  __syncthreads();
-  // A lane starts its next row `idle` steps after it has left the previous one: the density of its first step
-  // on the new row (and, with transition rows, the one its pair partner holds for the step after) was
-  // evaluated with the old row's constants, and kernels_align3 lets those stale values pass through steps
-  // on which the lane is outside its span instead of re-evaluating them at every row switch.
-  const int idle = (mode == PLAN_ALIGN_TRANS) ? 2 : 1;
-  for (int r = 64 + tid; r < T; r += PLAN_T) {
-    int d = rp[r - 64].hi - rp[r].lo + idle;  // need 64*c > d
-    if (d >= 0) cneed = max(cneed, d / 64 + 1);
-  }
-  cneed = max(cneed, max(mel - 1, 1));
-  cneed = wave_max(cneed);
-  if (lane == 0) atomicMax(&sh.c, cneed);
-  __syncthreads();
-  const int c = sh.c;
-  cells = (long long)sh.cells;
-  // A band this wide for its row spacing (skew above the main launch's cap) is served by a TEAM of waves
-  // (kernels_align3.hip): 64 * ALIGN3_TEAM_W lanes, one row each, so a lane's next row lies that many rows
-  // on and the skew it needs is that of the row pair (r - 64 W, r) — on long reads with wide bands the band
-  // moves on by more samples in 256 rows than it is wide, and the skew falls from ~28 to ~3.
-  const bool team = (c > c_cap);
-  int cw = 0;
-  if (team) {
-    constexpr int TL = 64 * ALIGN3_TEAM_W;
-    if (tid == 0) sh.cw = max(mel - 1, 1);
-    __syncthreads();
-    int need = 1;
-    for (int r = TL + tid; r < T; r += PLAN_T) {
-      int d = rp[r - TL].hi - rp[r].lo + idle;  // need TL * cw > d
-      if (d >= 0) need = max(need, d / TL + 1);
-    }
-    need = wave_max(need);
-    if (lane == 0) atomicMax(&sh.cw, need);
-    __syncthreads();
-    cw = sh.cw;
-  }
-
-  // --- per-row time offsets (variable skew, used by kernels_align3.hip) ---------------------------
-  // The uniform mapping t = i + c*r pays the worst pair of rows (r - 64, r) of the read on every row.
-  // Here cell (r, i) is computed at step t = i + off[r] with the LEAST offsets that satisfy
-  //   g[r] <= off[r] - off[r-1] <= c            (neighbour values wait at most c + mel steps in LDS)
-  //   off[r] - off[r-64] >= hi[r-64] - lo[r] + 1 + idle  (a lane is free, and idle for `idle` steps, before its
-  //                                                      next row starts)
-  // (off[r] = c*r is one solution, so the least one exists and needs no more steps).  The lower bound
-  // g[r] is what keeps the neighbour's value at least one step old, age = gap + mel >= 1: 1 for a row
-  // fed without emission (mel 0), 1 - mel for a row fed by an emitting step — with transition rows the
-  // two alternate, so a pair of rows needs no skew at all — and never so low that a row would start or
-  // end before the row above it (the kernel's bookkeeping of the oldest open row relies on that order).
-  // Without transition rows, and for min event lengths above 2, g[r] = max(mel - 1, 1) as before.
-  // With S[r] = g[1] + .. + g[r] and x[r] = off[r] - S[r] the first lower bound and the second are a
-  // prefix maximum per block of 64 rows, and the upper bound is a suffix maximum of off[r] - c*r; both
-  // are iterated to the fixed point by wave 0 (2-4 rounds on config-shaped reads).  Reads with more
-  // rows than the LDS arrays hold keep the uniform offsets.
-  constexpr int VT = PLAN_VT;
-  int *sh_k = (int *)sh.pool, *sh_x = sh_k + VT, *sh_S = sh_x + VT;
-  const int gmin = max(mel - 1, 1);
-  const bool neg_gaps = (mode == PLAN_ALIGN_TRANS) && mel <= 2;
-  if (tid == 0) sh.var = 0;
-  __syncthreads();
-  if (!team && T <= VT && T > 64 && (neg_gaps || c > gmin)) {
-    for (int r = tid; r < T; r += PLAN_T) {
-      int g = 0;
-      if (r > 0) {
-        g = gmin;
-        if (neg_gaps) g = max(1 - rp[r - 1].mel, max(rp[r - 1].lo - rp[r].lo, rp[r - 1].hi - rp[r].hi));
-        g = min(g, c);
-      }
-      sh_S[r] = g;
-      sh_x[r] = 0;
-    }
-    __syncthreads();
-    if (tid < 64) {  // S: inclusive prefix sum, block by block
-      int carry = 0;
-      for (int b0 = 0; b0 < T; b0 += 64) {
-        const int r = b0 + lane;
-        const int v = wave_scan_add(r < T ? sh_S[r] : 0, lane) + carry;
-        if (r < T) sh_S[r] = v;
-        carry = __shfl(v, 63, 64);
-      }
-    }
-    __syncthreads();
-    for (int r = tid; r < T; r += PLAN_T)
-      sh_k[r] = (r >= 64) ? rp[r - 64].hi - rp[r].lo + 1 + idle - (sh_S[r] - sh_S[r - 64]) : 0;
-    __syncthreads();
-    if (tid < 64) {
-      const int NEG = -0x20000000;
-      bool changed = true;
-      int iter = 0;
-      while (changed && iter < 64) {
-        changed = false;
-        ++iter;
-        int carry = 0;
-        for (int b0 = 0; b0 < T; b0 += 64) {  // lower bounds, ascending
-          const int r = b0 + lane;
-          const int cur = r < T ? sh_x[r] : NEG;
-          int v = cur;
-          if (r < T && r >= 64) v = max(v, sh_x[r - 64] + sh_k[r]);
-          v = max(wave_scan_max(v, lane), carry);
-          if (r < T) {
-            changed |= (v != cur);
-            sh_x[r] = v;
-          }
-          carry = __shfl(v, 63, 64);
-        }
-        int carryz = NEG;
-        for (int b0 = ((T - 1) / 64) * 64; b0 >= 0; b0 -= 64) {  // gap limit, descending
-          const int r = b0 + lane;
-          const int cur = r < T ? sh_x[r] : 0;
-          const int U = r < T ? c * r - sh_S[r] : 0;  // off[r] - c*r = x[r] - U[r]
-          int z = r < T ? cur - U : NEG;
-          z = max(-wave_scan_min_rev(-z, lane), carryz);  // (the maximum of lanes l .. 63)
-          if (r < T) {
-            const int nx = z + U;
-            changed |= (nx != cur);
-            sh_x[r] = nx;
-          }
-          carryz = __shfl(z, 0, 64);
-        }
-        changed = __any(changed);
-      }
-      if (lane == 0) sh.var = changed ? 0 : 1;  // not converged (never seen): uniform offsets
-    }
-    __syncthreads();
-  }
-  const bool var_ok = (sh.var != 0);
-  const int x0 = var_ok ? sh_x[0] : 0;
-  const int cu = team ? cw : c;  // uniform offsets
-  for (int r = tid; r < T; r += PLAN_T) rp[r].off = var_ok ? sh_x[r] - x0 + sh_S[r] : cu * r;
-  const int off_top = var_ok ? sh_x[T - 1] - x0 + sh_S[T - 1] : cu * (T - 1);
-  // the per-sweep lane records of kernels_align3.hip, while the read's rows are still in this CU's caches
-  // (lane3.h; a kernel of its own used to re-read the whole row table for them)
-  if (lane_f && !badband) {
-    __syncthreads();  // every row's offset is written
-    lane3_rows(rp, T, N, cw, lane_f + m.row_off, lane_r + m.row_off, lane_offs + m.row_off, tid, PLAN_T);
-  }
-
-  if (tid == 0) {
-    int t_min = rp[0].lo;
-    int t_max = rp[T - 1].hi + c * (T - 1);
-    m.c = c;
-    m.cw = cw;
-    m.t_min = t_min;
-    m.n_steps = t_max - t_min + 1;
-    m.pad = rp[T - 1].hi + off_top - t_min + 1;  // steps under the per-row offsets ...
     // ... rounded up to a multiple of 32: kernels_align3 spills two steps per access, unrolls 8, rescales every
     // 16 and flushes its bit words every 32 steps, and with a whole number of each its loops need no end tests
     m.pad = (m.pad + 31) & ~31;
-    m.cells = cells;
+    m.cells = (long long)sh.cells;
     m.rsv = plateau ? 1 : 0;
     if (badband) m.status = NVK_READ_BAD_BAND;
     metas[rd] = m;  // (the batch totals: plan_totals_kernel)
@@ -702,8 +473,8 @@ __global__ __launch_bounds__(PLAN_T, 5) void plan_kernel(DeviceModel dm, BatchAr
                                                   double log_p_in, int c_cap, ReadMeta *metas,
                                                   RowParam *rows, unsigned long long *bandtmp,
                                                   Lane3 *lane_f, Lane3 *lane_r, int32_t *lane_offs, int write_rows) {
-  // write_rows == 0: the RowParam table is left unwritten for the reads planned in LDS (plan_rows_global works in it
-  // and writes it regardless).  lane_f == null: no lane records — with write_rows that is the rows-only pass.
+  // write_rows == 0: the RowParam table is left unwritten.  lane_f == null: no lane records — with write_rows that is
+  // the rows-only pass.
   const int rd = blockIdx.x;
   const int tid = threadIdx.x;
   __shared__ PlanShared sh;
@@ -759,10 +530,14 @@ __global__ __launch_bounds__(PLAN_T, 5) void plan_kernel(DeviceModel dm, BatchAr
     if (tid == 0) metas[rd] = m;
     return;
   }
-  if (q.R + 1 <= PLAN_BCAP && dm.n <= 0x100000000ll)  // (plan_rows_lds keeps the k-mer ids as 32-bit words)
-    plan_rows_lds(dm, q, mode, log_p_in, c_cap, rd, m, metas, rows, write_rows != 0, lane_f, lane_r, lane_offs, sh);
-  else
-    plan_rows_global(dm, q, mode, log_p_in, c_cap, rd, m, metas, rows, bandtmp, lane_f, lane_r, lane_offs, sh);
+  if (q.R + 1 <= PLAN_BCAP && dm.n <= 0x100000000ll) {  // (PlanStoreLds keeps the k-mer ids as 32-bit words)
+    plan_rows(PlanStoreLds{sh}, dm, q, mode, log_p_in, c_cap, rd, m, metas, rows, write_rows != 0, lane_f, lane_r,
+              lane_offs, sh);
+  } else {
+    unsigned long long *tbs = bandtmp + 2 * (r0 + rd);
+    plan_rows(PlanStoreGlobal{tbs, tbs + (q.R + 1)}, dm, q, mode, log_p_in, c_cap, rd, m, metas, rows,
+              write_rows != 0, lane_f, lane_r, lane_offs, sh);
+  }
 }
 
 // The batch totals of plan_kernel, reduced from the reads' metas.  (Every block of plan_kernel used to add its read
@@ -853,7 +628,7 @@ __global__ __launch_bounds__(64) void plan_ell_kernel(DeviceModel dm, BatchArgs 
   }
   unsigned long long *tbs = bandtmp + 2 * (r0 + rd);
   unsigned long long *tbe = tbs + (R + 1);
-  plan_bands(anc, A, R, N, a.bandwidth, tbs, tbe, lane);
+  plan_bands(anc, A, R, N, a.bandwidth, tbs, tbe, tbs, tbe, lane, 64);
 
   int32_t *bs = pl.bs + r0 + rd, *be = pl.be + r0 + rd, *rowoff = pl.rowoff + r0 + rd;
   int badband = 0;

@@ -1,7 +1,6 @@
 // Per-sweep lane records of kernels_align3.hip, one pair per DP row.  Shared by the planner, which writes them in
-// the last phase of plan_kernel (kernels_plan.hip: from the bands and offsets it holds in LDS through lane3_row, or,
-// for a read above PLAN_BCAP, from the row table through lane3_rows while the rows are still in L2 — they used to be a
-// kernel of their own that re-read the whole row table) and the sweep kernels that consume them.
+// the last phase of plan_kernel (kernels_plan.hip: row by row through lane3_row, from the bands and offsets it holds —
+// they used to be a kernel of their own that re-read the whole row table) and the sweep kernels that consume them.
 #pragma once
 #include "nvk_internal.h"
 #include "dens.h"
@@ -74,23 +73,5 @@ __device__ __forceinline__ void lane3_row(const RowParam &o, const RowParam &p, 
     b.pA = 0x40000000; b.pW = 0;
     b.end = o.hi;
     b.mg = lane3_pack(o.mel, 1 + o.mel, adv_b);
-  }
-}
-
-// the records of one read from its row table in memory: `nthreads` threads of one block cooperate (tid = this
-// thread).  rw: the read's rows, fwdl / revl / offs: where its records go (already offset to the read's first row).
-__device__ __forceinline__ void lane3_rows(const RowParam *rw, int T, int N, int cw, Lane3 *fwdl, Lane3 *revl,
-                                           int32_t *offs, int tid, int nthreads) {
-  const int top = T - 1;
-  const int ST = cw ? 64 * ALIGN3_TEAM_W : 64;  // rows between a lane's consecutive rows
-  for (int r = tid; r < T; r += nthreads) {
-    const RowParam o = rw[r];
-    Lane3 f, b;
-    const int adv_f = (r >= ST) ? o.off - rw[r - ST].off : 0;
-    const int adv_b = (r + ST <= top) ? rw[r + ST].off - o.off : 0;
-    lane3_row(o, rw[r > 0 ? r - 1 : r], r > 0, rw[r < top ? r + 1 : r], r < top, N, adv_f, adv_b, f, b);
-    fwdl[r] = f;
-    revl[r] = b;
-    offs[r] = o.off;
   }
 }

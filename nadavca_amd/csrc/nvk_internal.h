@@ -238,8 +238,7 @@ enum { PLAN_ALIGN_TRANS = 0, PLAN_ALIGN_PLAIN = 1 };
 
 // lane_f / lane_r / lane_offs: where the planner leaves the per-sweep lane records of kernels_align3.hip (lane3.h),
 // or null.  write_rows: whether the RowParam table is written — only the exact kernel (launch_align,
-// launch_align_retry) reads it; without it `rows` holds nothing to rely on (reads of more than PLAN_BCAP band rows are
-// planned in it and leave their rows there).  totals == null: a second pass over a batch already planned, which leaves
+// launch_align_retry) reads it; without it `rows` is left unwritten, for every read.  totals == null: a second pass over a batch already planned, which leaves
 // the device totals alone and rewrites the metas with the values they have.  meanwhile (or null): host work of the
 // caller that depends on nothing the planner finds, called once the planner is queued, so that it runs beside it.
 int launch_plan(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int mode,

@@ -58,7 +58,7 @@ __device__ __forceinline__ void wave_sum_n(double (&v)[N]) {
   }
 }
 
-// inclusive scans: lane l gets the sum / maximum of lanes 0 .. l, or the minimum of lanes l .. 63
+// inclusive scan: lane l gets the sum of lanes 0 .. l
 __device__ __forceinline__ int wave_scan_add(int v, int lane) {
   for (int d = 1; d < 64; d <<= 1) {
     int o = __shfl_up(v, d, 64);
@@ -66,22 +66,8 @@ __device__ __forceinline__ int wave_scan_add(int v, int lane) {
   }
   return v;
 }
-__device__ __forceinline__ int wave_scan_max(int v, int lane) {
-  for (int d = 1; d < 64; d <<= 1) {
-    int o = __shfl_up(v, d, 64);
-    if (lane >= d) v = max(v, o);
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_scan_min_rev(int v, int lane) {
-  for (int d = 1; d < 64; d <<= 1) {
-    int o = __shfl_down(v, d, 64);
-    if (lane + d < 64) v = min(v, o);
-  }
-  return v;
-}
 
-// The same inclusive scans on the DPP path: row shifts inside the 16-lane rows, then the two row broadcasts of GFX9
+// Inclusive scans (sum / maximum / minimum of lanes 0 .. l) on the DPP path: row shifts inside the 16-lane rows, then the two row broadcasts of GFX9
 // (lane 15 of a row to the next row, lane 31 to the upper half).  No trip through the LDS crossbar, which is what a
 // serial chain of scans waits for.  `ident`: the operation's neutral element, taken by lanes without a source.
 #define WAVE_SCAN_DPP_STEP(ctrl, rows) v = op(v, __builtin_amdgcn_update_dpp(ident, v, ctrl, rows, 0xf, false))

@@ -115,6 +115,20 @@ def build_cases():
     for tr in (True, False):
         cases.append(_case('team_R300_%s' % ('trans' if tr else 'plain'),
                            [_read((4, 0), 300, 200, dwell=(2, 3), jitter=10)], 200, transitions=tr))
+    # ... and a team read of more than PLAN_BCAP band rows.  (Without transition rows the read of seed (4, 1) carries
+    # NVK_TIE_ULP beside its plateau mark and differs from the oracle in two rows, which the tie contract of
+    # include/nadavca_hip.h allows and test_plan_shape does not; the read of seed (4, 2) has no tie.)
+    for tr, seed in ((True, (4, 1)), (False, (4, 2))):
+        cases.append(_case('team_R1100_%s' % ('trans' if tr else 'plain'),
+                           [_read(seed, 1100, 200, dwell=(2, 3), jitter=10)], 200, transitions=tr))
+    # the other min event lengths above PLAN_BCAP band rows: T = 1031 without transition rows, and T = PLAN_VT with
+    # them, the last size whose per-row offsets come from the fixed point
+    for mel in (0, 1, 3, 4):
+        lo = max(mel, 2)
+        cases.append(_case('mel%d_plain_R1030' % mel, [_read((3, mel, 1030), 1030, 30, dwell=(lo, lo + 2))], 30,
+                           mel=mel, transitions=False))
+        cases.append(_case('mel%d_trans_R1024' % mel, [_read((3, mel, 1024), 1024, 30, dwell=(lo, lo + 2))], 30,
+                           mel=mel, transitions=True))
     # adjacent bases with the same level: the plateau mark of last_tie_flags
     for tr in (True, False):
         cases.append(_case('plateau_%s' % ('trans' if tr else 'plain'),

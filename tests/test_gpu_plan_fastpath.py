@@ -104,8 +104,8 @@ def test_retry_after_a_plan_without_the_row_table(dtw, oracle_port, sharp):
 
 
 def test_retry_in_a_batch_with_a_read_planned_in_global_scratch(dtw, sharp):
-    """The sharp-model reads beside a read of more than PLAN_BCAP band rows (planned in global scratch, which works in
-    the row table and writes it whatever the switch says) and two short ones, twice on one context: the pass that
+    """The sharp-model reads beside a read of more than PLAN_BCAP band rows (its bands planned in global scratch; its
+    rows, like a short read's, written only on request) and two short ones, twice on one context: the pass that
     makes the table for the exact kernel goes over a batch that holds both kinds of read.  (The long read itself is
     not the one that retries: neither plan_cases nor fuzz_cases makes a read of that length that does, and searching
     seeds for one costs an oracle run of a 1000-base read each.  The exact kernel reads a long read's rows in

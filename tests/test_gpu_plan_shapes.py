@@ -95,6 +95,7 @@ def test_the_team_cases_are_team_reads(oracle_port):
     by_name = {c['name']: c for c in CASES}
     for t in ('trans', 'plain'):
         assert _skew_lower_bound(oracle_port, by_name['team_R300_%s' % t]) > 3
+        assert _skew_lower_bound(oracle_port, by_name['team_R1100_%s' % t]) > 3
         assert _skew_lower_bound(oracle_port, by_name['mel2_%s_R129' % t]) <= 3
 
 
