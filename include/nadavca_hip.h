@@ -125,8 +125,10 @@ int nvk_last_retry_count(nvk_ctx *ctx, int64_t *n_reads);
  * partial sum), d the number of DP rows at which the two paths differ: each tolerant comparison of the search
  * can cost at most one such zone, and each deviating decision leaves at least one differing row.  Proven, not
  * assumed: tests/fuzz_cases.py::classify_difference scores every differing read of the randomised campaigns
- * (tests/test_gpu_parity_full.py, tests/test_gpu_parity_scored.py: every built kernel variant) and fails the
- * suite on one that loses more; the largest deficit measured is 2.5e-4 of that margin.
+ * (tests/test_gpu_parity_full.py, tests/test_gpu_parity_scored.py) and every read of the census, which runs a named
+ * case per built kernel variant and asserts through the launch report below that the variant ran
+ * (tests/test_gpu_variant_census.py), and fails the suite on one that loses more; the largest deficit
+ * measured is 2.5e-4 of that margin.
  * What the bits do NOT mean: that a flagged read differs.  Integer ADC samples repeat, so sequencer-shaped
  * data is full of equal and almost-equal path scores — the reference's own arithmetic meets ~25 exactly equal
  * and ~15 closer-than-2^-24 pairs of scores per config-2 read quantised to ADC steps (tests/dev/ref_tie_histogram.py)
@@ -157,6 +159,53 @@ int nvk_last_tie_flags(nvk_ctx *ctx, int64_t n_reads, int32_t *out_flags);
  * The same cap bounds the traceback store of nvk_seed_extend_dev: when a batch's store is larger, its reads run in
  * chunks that fit (a single read larger than the cap runs on its own); results do not change. */
 int nvk_ctx_set_workspace_limit(nvk_ctx *ctx, int64_t bytes);
+
+/* LAUNCH REPORT: which compiled kernel variant the last call ran.  refine_alignment and the four log-likelihood
+ * operators are served by families of template instantiations that the launchers pick from the batch's shape
+ * (csrc/kernels_align3.hip: select_sweeps, csrc/kernels_align.hip: align_kernel<MEL>, csrc/kernels_ell.hip:
+ * ELL_PICK); every nvk_refine_alignment_batch_dev, nvk_estimate_log_likelihoods_batch_dev and
+ * nvk_estimate_{,joint_,edit_}hypotheses_batch_dev call clears the report of its ctx when it starts and adds one
+ * record per launch class (not per chunk: `chunks` counts them).  Host stores only; nothing is read back for it.
+ * Defined for these device-pointer calls only: the host-pointer entries (nvk_refine_alignment_batch, _submit,
+ * nvk_estimate_log_likelihoods_batch) run their chunks on private lanes and leave the ctx with an EMPTY report.
+ *   op        NVK_LAUNCH_SWEEP  a reverse/forward sweep pair of kernels_align3.hip
+ *             NVK_LAUNCH_EXACT  align_kernel<mel> (kernels_align.hip), one record per class (narrow / wide skew)
+ *             NVK_LAUNCH_ELL    ell_kernel<mel, lanes, kind> (kernels_ell.hip)
+ *   mel       min event length, the template argument
+ *   transitions  SWEEP, EXACT: transition rows on (SWEEP: the paired variant).  ELL: model_wobbling (a run-time flag)
+ *   waves     SWEEP: waves per read, 1 or 4 (a team).  EXACT: 1.  ELL: lanes per hypothesis, 8 or 16
+ *   period    SWEEP: rescale period in steps, 8, 16 or 32 (the template argument 1 << RSH).  Else 0
+ *   kind      ELL: NVK_ELL_FULL / _LISTED / _JOINT / _EDIT.  EXACT: 1 = the retry launch behind the sweeps (it
+ *             serves the reads they handed on: nvk_last_retry_count), 0 = the whole batch (NADAVCA_ALIGN_KERNEL=1).
+ *             SWEEP: 0
+ *   c         the largest skew the launch serves, after the fit into a CU's 160 KB of LDS: SWEEP, EXACT wide class:
+ *             reads above it go to the exact kernel / get NVK_READ_TOO_WIDE; ELL: c_max, NVK_READ_TOO_WIDE above it
+ *   H, SR     slots of the history ring and samples of the (per-wave) signal ring the launch was sized with
+ *   lds_bytes dynamic LDS of the launch (SWEEP: of the forward launch, the larger of the pair)
+ *   reads     reads of the launch class (EXACT retry: the reads of the class the launch scans for handed-on ones)
+ *   chunks    launches (SWEEP: launch pairs) the class was served in
+ * nvk_last_launches: up to `cap` records into out (host), *n_records = the number the call made (at most
+ * NVK_LAUNCH_CAP are kept).
+ * nvk_last_read_skews: per read of that call the planner's wavefront skew c and, for a read swept by a team of
+ * waves, its team skew cw (else 0) — ONE copy of the ReadMeta table the call left on the device; n_reads must be
+ * that call's n_reads, and a later call of any operator that plans reads on the ctx invalidates it (NVK_ERR_INVALID,
+ * as nvk_last_tie_flags does).  out_c / out_cw: i32[n_reads] on the host, either may be NULL.
+ * nvk_built_sweep_variants: the (mel, transitions, waves, period) combinations select_sweeps has a kernel pair for,
+ * asked of select_sweeps itself over mel 0..7, transitions 0/1, waves 1..8, period 1..256: out i32[4 * cap],
+ * *n_variants = how many there are.  The log-likelihood kernels are the full product mel 0..4 x lanes {8, 16} x the
+ * four kinds (40) by construction of ELL_PICK, the exact kernels mel 0..4 (5).
+ * tests/test_gpu_variant_census.py runs a named smallest case (tests/variant_cases.py) per built variant, asserts
+ * through this report that the case reached it and compares it with the CPU oracle. */
+enum { NVK_LAUNCH_SWEEP = 1, NVK_LAUNCH_EXACT = 2, NVK_LAUNCH_ELL = 3 };
+enum { NVK_ELL_FULL = 0, NVK_ELL_LISTED = 1, NVK_ELL_JOINT = 2, NVK_ELL_EDIT = 3 };
+enum { NVK_LAUNCH_CAP = 8 };
+typedef struct nvk_launch_rec {
+  int32_t op, mel, transitions, waves, period, kind, c, H, SR, lds_bytes;
+  int64_t reads, chunks;
+} nvk_launch_rec;
+int nvk_last_launches(nvk_ctx *ctx, int cap, nvk_launch_rec *out, int *n_records);
+int nvk_last_read_skews(nvk_ctx *ctx, int64_t n_reads, int32_t *out_c, int32_t *out_cw);
+int nvk_built_sweep_variants(int cap, int32_t *out, int *n_variants);
 
 /* replaces dtw.KmerModel(k, central_position, alphabet_size, mean, sigma)
  * (dtwmodule.cpp:12-13, kmer_model.cpp:6-14).  mean/sigma: host f64[n], n = alphabet^k */

@@ -60,6 +60,9 @@ SIGNATURES = {
     'nvk_last_tie_counts': (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     'nvk_last_tie_flags': (_int, [_vp, _i64, _vp]),
     'nvk_ctx_set_workspace_limit': (_int, [_vp, _i64]),
+    'nvk_last_launches': (_int, [_vp, _int, _vp, C.POINTER(_int)]),
+    'nvk_last_read_skews': (_int, [_vp, _i64, _vp, _vp]),
+    'nvk_built_sweep_variants': (_int, [_int, _vp, C.POINTER(_int)]),
     'nvk_model_create': (_int, [_vp, _int, _int, _int, _vp, _vp, _i64, C.POINTER(_vp)]),
     'nvk_model_destroy': (None, [_vp]),
     'nvk_model_info': (_int, [_vp, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int)]),
@@ -103,6 +106,18 @@ SIGNATURES = {
     'nvk_site_rank_tests_dev': (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64] + [_vp] * 7),
     'nvk_site_mixture_tests_dev': (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _int, _dbl, _vp, _vp]),
 }
+
+LAUNCH_SWEEP, LAUNCH_EXACT, LAUNCH_ELL = 1, 2, 3   # nvk_launch_rec.op
+LAUNCH_OPS = {LAUNCH_SWEEP: 'sweep', LAUNCH_EXACT: 'exact', LAUNCH_ELL: 'ell'}
+ELL_KINDS = ['full', 'listed', 'joint', 'edit']       # nvk_launch_rec.kind of an 'ell' record (NVK_ELL_*)
+LAUNCH_CAP = 8
+
+
+class LaunchRec(C.Structure):
+    """nvk_launch_rec (include/nadavca_hip.h, launch report)."""
+    _fields_ = [(n, C.c_int32) for n in ('op', 'mel', 'transitions', 'waves', 'period', 'kind', 'c', 'H', 'SR',
+                                         'lds_bytes')] + [('reads', _i64), ('chunks', _i64)]
+
 
 _lib = None
 _lock = threading.Lock()
@@ -209,6 +224,39 @@ class Context:
         check(self._lib.nvk_last_tie_flags(self.handle, int(n_reads), _vp(out.ctypes.data)), 'nvk_last_tie_flags')
         return out
 
+    def last_launches(self):
+        """The launch report of the last device-pointer refine_alignment / log-likelihood call on this context
+        (include/nadavca_hip.h): one dict per launch class with op ('sweep' | 'exact' | 'ell'), mel, transitions,
+        waves, period, kind (an 'ell' record: 'full' | 'listed' | 'joint' | 'edit'; an 'exact' one: 'retry' | 'all'),
+        c, H, SR, lds_bytes, reads, chunks.  Empty after a host-pointer call."""
+        recs = (LaunchRec * LAUNCH_CAP)()
+        n = _int()
+        check(self._lib.nvk_last_launches(self.handle, LAUNCH_CAP, C.cast(recs, _vp), C.byref(n)), 'nvk_last_launches')
+        if n.value > LAUNCH_CAP:
+            raise NadavcaHipError('nvk_last_launches: %d launch classes, %d kept' % (n.value, LAUNCH_CAP))
+        out = []
+        for r in recs[:n.value]:
+            d = {name: int(getattr(r, name)) for name, _ in LaunchRec._fields_}
+            d['op'] = LAUNCH_OPS[d['op']]
+            if d['op'] == 'ell':
+                d['kind'] = ELL_KINDS[d['kind']]
+            elif d['op'] == 'exact':
+                d['kind'] = 'retry' if d['kind'] else 'all'
+            else:
+                d['kind'] = None
+            out.append(d)
+        return out
+
+    def last_read_skews(self, n_reads):
+        """-> (c, cw) int32 arrays: per read of the last device-pointer call that planned reads on this context the
+        planner's wavefront skew and, for a read swept by a team of waves, its team skew (else 0)."""
+        import numpy as np
+        c = np.zeros(int(n_reads), dtype=np.int32)
+        cw = np.zeros(int(n_reads), dtype=np.int32)
+        check(self._lib.nvk_last_read_skews(self.handle, int(n_reads), _vp(c.ctypes.data), _vp(cw.ctypes.data)),
+              'nvk_last_read_skews')
+        return c, cw
+
     def set_workspace_limit(self, nbytes):
         check(self._lib.nvk_ctx_set_workspace_limit(self.handle, int(nbytes)), 'nvk_ctx_set_workspace_limit')
 
@@ -222,6 +270,18 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+def built_sweep_variants():
+    """-> sorted list of (mel, transitions, waves, period): the sweep kernel pairs select_sweeps
+    (csrc/kernels_align3.hip) has, as the library itself enumerates them.  Needs no GPU."""
+    import numpy as np
+    lib = load()
+    n = _int()
+    check(lib.nvk_built_sweep_variants(0, None, C.byref(n)), 'nvk_built_sweep_variants')
+    out = np.zeros((max(n.value, 1), 4), dtype=np.int32)
+    check(lib.nvk_built_sweep_variants(n.value, _vp(out.ctypes.data), C.byref(n)), 'nvk_built_sweep_variants')
+    return sorted((int(a), bool(b), int(c), int(d)) for a, b, c, d in out[:n.value])
 
 
 _default_ctx = {}

@@ -121,6 +121,7 @@ extern "C" int nvk_ctx_create(int device, nvk_ctx **out) {
   }
   memset(c, 0, sizeof *c);
   c->device = device;
+  c->meta_n = -1;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) != hipSuccess) {
     delete c;
@@ -240,6 +241,40 @@ extern "C" int nvk_last_tie_flags(nvk_ctx *ctx, int64_t n_reads, int32_t *out_fl
   NVK_HIP(hipMemcpyAsync(out_flags, ctx->ws[WS_TIES], (size_t)n_reads * sizeof(int32_t), hipMemcpyDeviceToHost,
                          ctx->stream));
   NVK_HIP(hipStreamSynchronize(ctx->stream));
+  return NVK_OK;
+}
+
+extern "C" int nvk_last_launches(nvk_ctx *ctx, int cap, nvk_launch_rec *out, int *n_records) {
+  if (!ctx || cap < 0 || (cap > 0 && !out)) return NVK_ERR_INVALID;
+  const int kept = ctx->n_launches < NVK_LAUNCH_CAP ? ctx->n_launches : NVK_LAUNCH_CAP;
+  for (int i = 0; i < kept && i < cap; i++) out[i] = ctx->launches[i];
+  if (n_records) *n_records = ctx->n_launches;
+  return NVK_OK;
+}
+
+extern "C" int nvk_last_read_skews(nvk_ctx *ctx, int64_t n_reads, int32_t *out_c, int32_t *out_cw) {
+  if (!ctx || n_reads < 0) return NVK_ERR_INVALID;
+  if (n_reads != ctx->meta_n) {
+    nvk_set_error("nvk_last_read_skews: the reads planned last on this ctx by a device-pointer call are %lld, not %lld",
+                  (long long)ctx->meta_n, (long long)n_reads);
+    return NVK_ERR_INVALID;
+  }
+  if (n_reads == 0) return NVK_OK;
+  std::vector<ReadMeta> h;
+  try {
+    h.resize((size_t)n_reads);
+  } catch (const std::bad_alloc &) {
+    nvk_set_error("out of host memory");
+    return NVK_ERR_NOMEM;
+  }
+  NVK_HIP(hipSetDevice(ctx->device));
+  NVK_HIP(hipMemcpyAsync(h.data(), ctx->ws[WS_META], (size_t)n_reads * sizeof(ReadMeta), hipMemcpyDeviceToHost,
+                         ctx->stream));
+  NVK_HIP(hipStreamSynchronize(ctx->stream));
+  for (int64_t i = 0; i < n_reads; i++) {
+    if (out_c) out_c[i] = h[(size_t)i].c;
+    if (out_cw) out_cw[i] = h[(size_t)i].cw;
+  }
   return NVK_OK;
 }
 
@@ -455,6 +490,7 @@ int plan_batch_queue(nvk_model *model, const BatchArgs &a, int mode, int write_r
   int64_t rows_total = (mode == PLAN_ALIGN_TRANS) ? 2 * a.total_ref : a.total_ref + n;
   int rc;
   ctx->rows_current = 0;  // (whatever WS_ROWS holds belongs to an earlier batch from here on)
+  ctx->meta_n = -1;       // (... and WS_META)
   if ((rc = nvk_ws_reserve(ctx, WS_META, (size_t)(n + 1) * sizeof(ReadMeta) + 64))) return rc;
   if ((rc = nvk_ws_reserve(ctx, WS_ROWS, (size_t)(rows_total + 1) * sizeof(RowParam)))) return rc;
   if ((rc = nvk_ws_reserve(ctx, WS_BANDTMP, (size_t)(2 * (a.total_ref + n) + 2) * 8))) return rc;
@@ -575,7 +611,9 @@ extern "C" int nvk_refine_alignment_batch_dev(
   int rc = dev_batch(model, n_reads, total_signal, total_ref, total_anchors, signal, sig_off, reference, ref_off,
                      ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
                      out_status, a);
-  if (rc || n_reads == 0) return rc;
+  if (rc) return rc;
+  nvk_launch_reset(model->ctx);
+  if (n_reads == 0) return rc;
   nvk_ctx *ctx = model->ctx;
   PlanTotals tot;
   // two implementations of the same operator with identical results (both parity-tested):
@@ -607,6 +645,7 @@ extern "C" int nvk_refine_alignment_batch_dev(
   if ((rc = plan_batch_wait(ctx, n_reads, tot, &steps_sorted))) return rc;
   ctx->ties_n = n_reads;
   ctx->ties_host = nullptr;
+  ctx->meta_n = n_reads;
   int32_t *d_ties = (int32_t *)ctx->ws[WS_TIES];
   int *d_retry = (int *)(d_ties + n_reads + 4);
   const ReadMeta *metas = (const ReadMeta *)ctx->ws[WS_META];
@@ -661,6 +700,7 @@ int ell_run(nvk_model *model, const BatchArgs &a, int model_wobbling, double *ou
   const int64_t n_reads = a.n_reads, total_ref = a.total_ref;
   nvk_ctx *ctx = model->ctx;
   const int64_t n = n_reads, nrow = total_ref + n;
+  nvk_launch_reset(ctx);  // (also: WS_META takes this batch's metas)
   if ((rc = nvk_ws_reserve(ctx, WS_META, (size_t)(n + 1) * sizeof(ReadMeta) + 64))) return rc;
   ctx->rows_current = 0;  // (WS_ROWS takes this operator's descriptors)
   if ((rc = nvk_ws_reserve(ctx, WS_ROWS, (size_t)(total_ref + 1) * sizeof(FusedParam)))) return rc;
@@ -684,6 +724,7 @@ int ell_run(nvk_model *model, const BatchArgs &a, int model_wobbling, double *ou
   NVK_HIP(hipStreamSynchronize(ctx->stream));
   ctx->last_cells = (int64_t)tot.cells;
   ctx->last_steps = (int64_t)tot.steps;
+  ctx->meta_n = n;
   rc = launch_ell(ctx, model->dm, a, model_wobbling ? 1 : 0, pl, tot, out_ll, out_status, hyp);
   if (rc) return rc;
   NVK_HIP(hipStreamSynchronize(ctx->stream));
@@ -702,7 +743,9 @@ extern "C" int nvk_estimate_log_likelihoods_batch_dev(
   int rc = dev_batch(model, n_reads, total_signal, total_ref, total_anchors, signal, sig_off, reference, ref_off,
                      ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
                      out_status, a);
-  if (rc || n_reads == 0) return rc;
+  if (rc) return rc;
+  nvk_launch_reset(model->ctx);
+  if (n_reads == 0) return rc;
   return ell_run(model, a, model_wobbling, out_ll, out_status, EllHyp{});
 }
 
@@ -731,6 +774,7 @@ struct HypLevel {
 int hyp_run(nvk_model *model, const BatchArgs &a, int model_wobbling, int32_t *out_status, const EllHyp &hyp,
             const HypLevel *level, bool lists_present) {
   const int64_t total_hyp = hyp.total_hyp;
+  nvk_launch_reset(model->ctx);
   if (total_hyp < 0 || !hyp.off || !hyp.out_total || (total_hyp > 0 && !hyp.out_hyp) ||
       (level && (level->total < 0 || !level->off)) || !lists_present) {
     if (level)

@@ -560,6 +560,9 @@ static int launch_align_impl(nvk_ctx *ctx, const BatchArgs &a, int transitions, 
       NVK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(64), lds, st, g);
     NVK_HIP(hipGetLastError());
+    // launch report (include/nadavca_hip.h): one record per class
+    nvk_launch_note(ctx, nvk_launch_rec{NVK_LAUNCH_EXACT, mel, transitions, 1, 0, only_retry ? 1 : 0, c, H, SR,
+                                        (int32_t)lds, n_class, 1});
   }
   NVK_HIP(hipEventRecord(ctx->ev_join, ctx->stream2));
   NVK_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));

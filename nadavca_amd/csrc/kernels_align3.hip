@@ -1102,6 +1102,29 @@ bool select_sweeps(int mel, bool pair, int W, int rsh, Align3Kernel k[2]) {
 
 }  // namespace
 
+// What select_sweeps builds, asked of select_sweeps itself (include/nadavca_hip.h): every argument over a range wider
+// than any launcher passes.
+extern "C" int nvk_built_sweep_variants(int cap, int32_t *out, int *n_variants) {
+  if (cap < 0 || (cap > 0 && !out) || !n_variants) return NVK_ERR_INVALID;
+  int n = 0;
+  Align3Kernel k[2];
+  for (int mel = 0; mel < 8; mel++)
+    for (int pair = 0; pair < 2; pair++)
+      for (int W = 1; W <= 8; W++)
+        for (int rsh = 0; rsh <= 8; rsh++) {
+          if (!select_sweeps(mel, pair != 0, W, rsh, k)) continue;
+          if (n < cap) {
+            out[4 * n] = mel;
+            out[4 * n + 1] = pair;
+            out[4 * n + 2] = W;
+            out[4 * n + 3] = 1 << rsh;
+          }
+          ++n;
+        }
+  *n_variants = n;
+  return NVK_OK;
+}
+
 // One work counter per sweep launch, so that nothing has to be zeroed between a chunk's reverse and forward
 // launch: the first 64 bytes of WS_MISC are 16 counters, zeroed together up front (align3_prepare) and again (in
 // stream order, before a reverse launch) whenever a batch of many chunks has used them all.
@@ -1226,6 +1249,7 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
     // reads the rest, so a class's chunks, slots and workgroups count only the reads it sweeps.
     const int64_t pos_lo = (W > 1) ? 0 : n_wide, pos_hi = (W > 1) ? n_wide : a.n_reads;
     int64_t lo = pos_lo;
+    int64_t n_chunks = 0;
     while (lo < pos_hi) {
       int64_t hi = lo, mx = 1;
       while (hi < pos_hi) {
@@ -1271,7 +1295,11 @@ int launch_align3(nvk_ctx *ctx, const BatchArgs &a, int transitions, const ReadM
       launches += 2;
       NVK_HIP(hipGetLastError());
       lo = hi;
+      ++n_chunks;
     }
+    // launch report (include/nadavca_hip.h): one record per class
+    nvk_launch_note(ctx, nvk_launch_rec{NVK_LAUNCH_SWEEP, mel, transitions, W, 1 << rsh, 0, c, H, SR, (int32_t)lds,
+                                        pos_hi - pos_lo, n_chunks});
   }
   // bytes the sweeps stream through HBM: 8 B written + 8 B read per (step, lane) + scales + bits
   ctx->last_spill_bytes = (int64_t)tot.steps * 64 * 16 + (int64_t)tot.steps / 16 * 8 + (int64_t)tot.steps * 8 * 2;

@@ -861,6 +861,9 @@ int ell_dispatch(nvk_ctx *ctx, const EllArgs &base, const EllHyp &hyp, bool wide
     g.ins_base = hyp.edit.ins_base;
   }
   void (*kern)(Args) = nullptr;
+  // What is built: every M of 0..4 x {8, 16} lanes per hypothesis x the four (LISTED, JOINT, EDIT) combinations launch_ell
+  // dispatches, 5 x 2 x 4 = 40 kernels, all of them reachable: M is the batch's min event length (checked by launch_ell),
+  // the lanes follow the table's k (k + 2 <= 8 or not) and the kind is the entry point.
 #define ELL_PICK(M) kern = wide_groups ? ell_kernel<M, 16, LISTED, JOINT, EDIT> : ell_kernel<M, 8, LISTED, JOINT, EDIT>
   switch (base.a.mel) {
     case 0: ELL_PICK(0); break;
@@ -878,6 +881,10 @@ int ell_dispatch(nvk_ctx *ctx, const EllArgs &base, const EllHyp &hyp, bool wide
     hipLaunchKernelGGL(kern, dim3((unsigned)slots), dim3(64), lds, ctx->stream, g);
   }
   NVK_HIP(hipGetLastError());
+  // launch report (include/nadavca_hip.h)
+  nvk_launch_note(ctx, nvk_launch_rec{NVK_LAUNCH_ELL, base.a.mel, base.wobbling, wide_groups ? 16 : 8, 0,
+                                      (int32_t)(!LISTED ? NVK_ELL_FULL : EDIT ? NVK_ELL_EDIT : JOINT ? NVK_ELL_JOINT : NVK_ELL_LISTED),
+                                      base.c_max, base.H, base.SR, (int32_t)lds, base.a.n_reads, 1});
   return NVK_OK;
 }
 }  // namespace

@@ -104,6 +104,12 @@ struct nvk_ctx {
   // where they are: null = on the device in ws[WS_TIES], else the host copy of the pipelined path (pipeline.hip)
   int64_t ties_n;
   const int32_t *ties_host;
+  // launch report (include/nadavca_hip.h): the launch classes of the last device-pointer refine / log-likelihood call
+  // (nvk_launch_reset at its start, nvk_launch_note per class) and the number of reads whose ReadMeta that call left in
+  // ws[WS_META] (nvk_last_read_skews; -1: none, or the table was taken by a later plan)
+  nvk_launch_rec launches[NVK_LAUNCH_CAP];
+  int n_launches;
+  int64_t meta_n;
   int64_t ws_limit;      // nvk_ctx_set_workspace_limit: cap on the sweep kernels' spill workspace (0 = default)
   // one pinned host block the planner's results arrive in with ONE copy + synchronisation per batch: the totals,
   // then the reads' step counts in launch order (refine_alignment; sizes the spill slots)
@@ -112,6 +118,16 @@ struct nvk_ctx {
   int spill_share;       // > 1: this ctx is one of that many lanes of a pipelined host path sharing the device
   struct nvk_pipe_state *pipe;  // lanes of the pipelined host-pointer entry points (pipeline.hip), made on first use
 };
+
+// launch report: forget the last call's records (and its metas) / add one record, counted also beyond the capacity
+inline void nvk_launch_reset(nvk_ctx *ctx) {
+  ctx->n_launches = 0;
+  ctx->meta_n = -1;
+}
+inline void nvk_launch_note(nvk_ctx *ctx, const nvk_launch_rec &r) {
+  if (ctx->n_launches < NVK_LAUNCH_CAP) ctx->launches[ctx->n_launches] = r;
+  ctx->n_launches++;
+}
 
 struct nvk_model {
   nvk_ctx *ctx;

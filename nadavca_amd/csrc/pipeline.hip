@@ -395,6 +395,7 @@ int run_pipelined(nvk_model *model, int kind, int64_t n_reads, const HostBatch &
     (void)collect_ticketed(p, p->lanes[i], ctx);
   ctx->last_cells = ctx->last_steps = ctx->last_spill_bytes = 0;
   ctx->last_retries = 0;
+  nvk_launch_reset(ctx);  // (the chunks run on the lanes' contexts: this path leaves an empty launch report)
   int32_t *ties = nullptr;
   if (kind == JOB_REFINE) {
     ctx->ties_n = -1;  // (p->ties is about to change)
@@ -495,6 +496,7 @@ extern "C" int nvk_refine_alignment_submit(nvk_model *model, int64_t n_reads, co
   NVK_HIP(hipSetDevice(ctx->device));
   nvk_pipe_state *p = nullptr;
   if ((rc = pipe_get(ctx, &p))) return rc;
+  nvk_launch_reset(ctx);  // (as run_pipelined)
   const int64_t t = p->next_ticket;
   Lane &L = p->lanes[t % p->n_lanes];
   (void)collect_ticketed(p, L, ctx);  // the batch that used this lane before (its verdict waits under its ticket)

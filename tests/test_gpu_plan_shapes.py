@@ -90,13 +90,33 @@ def _skew_lower_bound(oracle, case):
     return need
 
 
-def test_the_team_cases_are_team_reads(oracle_port):
+def _planner_skews(dtw, models, case):
+    """(c, cw) the planner gave the one read of a case: a device-pointer call, then the library's own record of the
+    batch planned last (Context.last_read_skews)."""
+    import torch
+    from nadavca_amd.device import DeviceBatch, refine_alignment_dev
+    mg, _ = models(case['model'])
+    c = case['reads'][0]
+    batch = dtw.FlatBatch([(c['signal'], c['reference'], c['context_before'], c['context_after'],
+                            c['approximate_alignment'])])
+    refine_alignment_dev(DeviceBatch(batch, torch.device('cuda', mg.context.device)), case['bandwidth'], case['mel'],
+                         mg, case['transitions'])
+    skew, team_skew = mg.context.last_read_skews(1)
+    return int(skew[0]), int(team_skew[0])
+
+
+def test_the_team_cases_are_team_reads(dtw, oracle_port, models):
     """Skew above ALIGN1_C_CAP = 3 (csrc/nvk_internal.h) is what hands a read to a team of waves."""
     by_name = {c['name']: c for c in CASES}
     for t in ('trans', 'plain'):
         assert _skew_lower_bound(oracle_port, by_name['team_R300_%s' % t]) > 3
         assert _skew_lower_bound(oracle_port, by_name['team_R1100_%s' % t]) > 3
         assert _skew_lower_bound(oracle_port, by_name['mel2_%s_R129' % t]) <= 3
+        # ... and the planner says so itself: a team skew for the team reads, none for the other
+        for name, team in (('team_R300_%s' % t, True), ('team_R1100_%s' % t, True), ('mel2_%s_R129' % t, False)):
+            c, cw = _planner_skews(dtw, models, by_name[name])
+            assert c >= _skew_lower_bound(oracle_port, by_name[name])
+            assert (c > 3 and cw >= 1) if team else (c <= 3 and cw == 0), (name, c, cw)
 
 
 def test_the_cases_reach_what_they_are_for():
