@@ -163,7 +163,7 @@ int nvk_ctx_set_workspace_limit(nvk_ctx *ctx, int64_t bytes);
 /* LAUNCH REPORT: which compiled kernel variant the last call ran.  refine_alignment and the four log-likelihood
  * operators are served by families of template instantiations that the launchers pick from the batch's shape
  * (csrc/kernels_align3.hip: select_sweeps, csrc/kernels_align.hip: align_kernel<MEL>, csrc/kernels_ell.hip:
- * ELL_PICK); every nvk_refine_alignment_batch_dev, nvk_estimate_log_likelihoods_batch_dev and
+ * ell_dispatch); every nvk_refine_alignment_batch_dev, nvk_estimate_log_likelihoods_batch_dev and
  * nvk_estimate_{,joint_,edit_}hypotheses_batch_dev call clears the report of its ctx when it starts and adds one
  * record per launch class (not per chunk: `chunks` counts them).  Host stores only; nothing is read back for it.
  * Defined for these device-pointer calls only: the host-pointer entries (nvk_refine_alignment_batch, _submit,
@@ -193,7 +193,7 @@ int nvk_ctx_set_workspace_limit(nvk_ctx *ctx, int64_t bytes);
  * nvk_built_sweep_variants: the (mel, transitions, waves, period) combinations select_sweeps has a kernel pair for,
  * asked of select_sweeps itself over mel 0..7, transitions 0/1, waves 1..8, period 1..256: out i32[4 * cap],
  * *n_variants = how many there are.  The log-likelihood kernels are the full product mel 0..4 x lanes {8, 16} x the
- * four kinds (40) by construction of ELL_PICK, the exact kernels mel 0..4 (5).
+ * four kinds (40) by construction of ell_dispatch's tables, the exact kernels mel 0..4 (5).
  * tests/test_gpu_variant_census.py runs a named smallest case (tests/variant_cases.py) per built variant, asserts
  * through this report that the case reached it and compares it with the CPU oracle. */
 enum { NVK_LAUNCH_SWEEP = 1, NVK_LAUNCH_EXACT = 2, NVK_LAUNCH_ELL = 3 };

@@ -693,7 +693,7 @@ extern "C" int nvk_refine_alignment_batch_dev(
 // estimate_log_likelihoods
 // ---------------------------------------------------------------------------------------------
 namespace {
-// plan + launch of the full matrix (hyp.kind Full, into out_ll) or of listed hypotheses (into hyp.out_*)
+// plan + launch of the full matrix (hyp.kind Full, into out_ll) or of listed hypotheses (into hyp.list.out_*)
 int ell_run(nvk_model *model, const BatchArgs &a, int model_wobbling, double *out_ll, int32_t *out_status,
             const EllHyp &hyp) {
   int rc;
@@ -769,13 +769,13 @@ struct HypLevel {
 };
 
 // What the listed-hypothesis entry points do after dev_batch, the same for every kind: the checks of the list (read j
-// owns hyp.off[j] .. hyp.off[j+1] of hyp.total_hyp hypotheses; `level`: their second level, or null) and the launch.
+// owns hyp.list.off[j] .. off[j+1] of its total_hyp hypotheses; `level`: their second level, or null) and the launch.
 // lists_present: the kind's own arrays are there wherever their level's total is positive.
 int hyp_run(nvk_model *model, const BatchArgs &a, int model_wobbling, int32_t *out_status, const EllHyp &hyp,
             const HypLevel *level, bool lists_present) {
-  const int64_t total_hyp = hyp.total_hyp;
+  const int64_t total_hyp = hyp.list.total_hyp;
   nvk_launch_reset(model->ctx);
-  if (total_hyp < 0 || !hyp.off || !hyp.out_total || (total_hyp > 0 && !hyp.out_hyp) ||
+  if (total_hyp < 0 || !hyp.list.off || !hyp.list.out_total || (total_hyp > 0 && !hyp.list.out_hyp) ||
       (level && (level->total < 0 || !level->off)) || !lists_present) {
     if (level)
       nvk_set_error("negative total_hyp / %s or NULL hypothesis / %s / output pointer", level->total_name,
@@ -797,7 +797,7 @@ int hyp_run(nvk_model *model, const BatchArgs &a, int model_wobbling, int32_t *o
   // the kernel walks every level of the list: each offsets array is checked here, on a host copy
   int rc;
   std::vector<int64_t> h_off;
-  if ((rc = nvk_fetch_offsets(model->ctx, "hypothesis", hyp.off, a.n_reads, h_off, "total_hyp", total_hyp))) return rc;
+  if ((rc = nvk_fetch_offsets(model->ctx, "hypothesis", hyp.list.off, a.n_reads, h_off, "total_hyp", total_hyp))) return rc;
   if ((rc = check_hyp_counts(h_off, a.n_reads))) return rc;
   if (level &&
       (rc = nvk_fetch_offsets(model->ctx, level->what, level->off, total_hyp, h_off, level->total_name, level->total)))
@@ -819,7 +819,7 @@ extern "C" int nvk_estimate_hypotheses_batch_dev(
                      ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
                      out_status, a);
   if (rc) return rc;
-  EllHyp hyp{EllKind::Listed, hyp_off, out_total, out_hyp, total_hyp};
+  EllHyp hyp{EllKind::Listed, {hyp_off, out_total, out_hyp, total_hyp}};
   hyp.listed = {hyp_pos, hyp_base};
   return hyp_run(model, a, model_wobbling, out_status, hyp, nullptr, total_hyp <= 0 || (hyp_pos && hyp_base));
 }
@@ -837,7 +837,7 @@ extern "C" int nvk_estimate_joint_hypotheses_batch_dev(
                      ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
                      out_status, a);
   if (rc) return rc;
-  EllHyp hyp{EllKind::Joint, hyp_off, out_total, out_hyp, total_hyp};
+  EllHyp hyp{EllKind::Joint, {hyp_off, out_total, out_hyp, total_hyp}};
   hyp.joint = {sub_off, sub_pos, sub_base};
   const HypLevel subs{"substitution", "total_sub", total_sub, sub_off};
   return hyp_run(model, a, model_wobbling, out_status, hyp, &subs, total_sub <= 0 || (sub_pos && sub_base));
@@ -856,7 +856,7 @@ extern "C" int nvk_estimate_edit_hypotheses_batch_dev(
                      ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
                      out_status, a);
   if (rc) return rc;
-  EllHyp hyp{EllKind::Edit, hyp_off, out_total, out_hyp, total_hyp};
+  EllHyp hyp{EllKind::Edit, {hyp_off, out_total, out_hyp, total_hyp}};
   hyp.edit = {edit_pos, edit_del, ins_off, ins_base};
   const HypLevel letters{"insertion", "total_ins", total_ins, ins_off};
   return hyp_run(model, a, model_wobbling, out_status, hyp, &letters,

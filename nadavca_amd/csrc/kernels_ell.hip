@@ -13,10 +13,10 @@
 //                      — or, in the JOINT variant (nvk_estimate_joint_hypotheses_batch_dev), for listed SETS of
 //                      substitutions: the rows first = max(0, p1 - back) .. last = min(R - 1, pm + fwd) of the set's
 //                      first and last substituted position, every k-mer read with all of them applied, closed at
-//                      `last` as a single one is (see "joint items" below)
+//                      `last` as a single one is (the items: ell_items.h)
 //                      — or, in the EDIT variant (nvk_estimate_edit_hypotheses_batch_dev), for listed insertions /
 //                      deletions (p, d, s): the rows around the edit of the EDITED reference, its k-mers, bands and
-//                      closing suffix row read through an index map, closed on band last + 1 (see "edit items" below)
+//                      closing suffix row read through an index map, closed on band last + 1 (the items and the map: ell_items.h)
 //
 // Mapping (not the reference's): "fused" lanes.  The reference alternates a wobble row
 // (mixture of the k-mers j-1 and j, min event length 0) with an emitting row (k-mer j).  Both
@@ -51,8 +51,10 @@
 // Quirks kept on purpose: the mixture is (g1 + g2) * exp(-2), not / 2; the
 // closing wobble row of a hypothesis lives on band row `last`, not `last + 1`.
 #include <math.h>
+#include <type_traits>
 
 #include "nvk_internal.h"
+#include "ell_items.h"
 #include "kmer.h"
 #include "wave.h"
 #include "xmath.h"
@@ -104,49 +106,15 @@ struct EllArgs {
   double *out_ll;
   int32_t *out_status;
 };
-// The listed variant (nvk_estimate_hypotheses_batch_dev): the hypotheses of read j are hyp_off[j] .. hyp_off[j+1] of
-// (hyp_pos, hyp_base) instead of all (p, b != ref[p]); out_ll is not used.  A struct of its own, so that the full
-// variant's kernel arguments stay what they are.
-struct EllListArgs : EllArgs {
-  const int64_t *hyp_off;
-  const int32_t *hyp_pos, *hyp_base;
-  double *out_total;  // [n_reads]
-  double *out_hyp;    // [total_hyp]
-};
-// The joint variant (nvk_estimate_joint_hypotheses_batch_dev): hypothesis h of the batch is the SET of substitutions
-// sub_off[h] .. sub_off[h+1] of (sub_pos, sub_base), positions strictly ascending; hyp_pos / hyp_base are not used.
-// items: total_hyp records the read's wave fills before its sweeps and takes the hypothesis loops' work from.
-struct EllJointArgs : EllListArgs {
-  const int64_t *sub_off;
-  const int32_t *sub_pos, *sub_base;
-  int4 *items;
-};
-// The edit variant (nvk_estimate_edit_hypotheses_batch_dev): hypothesis h of the batch deletes edit_del[h] bases from
-// edit_pos[h] on and puts the letters ins_off[h] .. ins_off[h+1] of ins_base in their place; items as the joint variant.
-struct EllEditArgs : EllListArgs {
-  const int32_t *edit_pos, *edit_del;
-  const int64_t *ins_off;
-  const int32_t *ins_base;
-  int4 *items;
-};
-template <bool LISTED, bool JOINT, bool EDIT>
-struct EllArgsOf { typedef EllArgs type; };
-template <>
-struct EllArgsOf<true, false, false> { typedef EllListArgs type; };
-template <>
-struct EllArgsOf<true, true, false> { typedef EllJointArgs type; };
-template <>
-struct EllArgsOf<true, true, true> { typedef EllEditArgs type; };
-// joint items: the effective substitutions (b != ref[p]) of a hypothesis as its first position p1 and one nibble per
-// offset from p1 (bit 3: substituted, bits 0-2: the letter) — at most 14 rows are re-run, so the offsets stay below
-// 14 and the alphabet below 8: two registers per lane, with the last offset in the top nibble.  A hypothesis without
-// an effective substitution is 0.
-constexpr int JOINT_ROWS = 14;  // rows a 16-lane group re-runs at most: role 0 and the closing lane take the other two
-// edit items: the hypothesis (p, d, s) with i = len(s) as its position p and a code of one nibble per inserted letter
-// (at most 13: an insertion of i letters re-runs at least i + 1 rows), i in bits 52-55 and d in bits 56-63 (so d <= 255).
-// The edited reference ref' = ref[:p] + s + ref[p+d:] has R' = R - d + i bases; its position / boundary row j comes from
-// j itself before p, from the letters for p <= j < p + i, and from j - i + d behind them.  (d, i) = (0, 0) is code 0.
-constexpr int EDIT_MAX_INS = 13, EDIT_MAX_DEL = 255;
+// A listed variant's arguments: the common ones (out_ll unused), what every listed kind has and the kind's own list, both
+// as nvk_internal.h declares them for EllHyp.  items (joint, edit; else null): total_hyp records the read's wave fills
+// before its sweeps.  The full variant takes EllArgs alone, so that its kernel arguments stay what they are.
+template <class Own>
+struct EllHypArgs : EllArgs { EllList list; Own own; int4 *items; };
+template <bool LISTED, bool JOINT, bool EDIT>  // (the kernel's three booleans -> its argument)
+using EllArgsOf = std::conditional_t<!LISTED, EllArgs, EllHypArgs<std::conditional_t<EDIT, EllEdit,
+                                                                  std::conditional_t<JOINT, EllJoint, EllListed>>>>;
+using ell_items::JOINT_ROWS;  // the packed items of the joint and the edit variant: ell_items.h
 
 // ---- one fused lane ---------------------------------------------------------------------------
 template <int MEL>
@@ -169,6 +137,9 @@ struct HypDesc {
   int has_wob;
   double wmul;          // phase C: exp(-2) on a lane with a wobble row, 0 without ...
   int wexp;             // ... and 0 / XZ: the mixture times (wmul, wexp) is the mixture or a clean zero
+  __device__ __forceinline__ void no_rows() {  // a dead lane: its bands are empty
+    wbs = 0x40000000; wbe = -0x40000000; elo = 0x40000000; ebe = -0x40000000;
+  }
 };
 
 // a + b without re-normalising the mantissa (it drifts by a few bits per step at most; the caller
@@ -314,11 +285,8 @@ __device__ void sweep_fast(const FusedParam *desc, int R, int N, int c, const do
     d.elo = max(f.wbs, MEL);
     ebs = f.ebs; soff = f.soff;
   };
-  auto dead = [&]() {
-    d.wbs = 0x40000000; d.wbe = -0x40000000; d.elo = 0x40000000; d.ebe = -0x40000000;
-  };
   d.bm = d.bac = d.bmc = 0.0; d.has_wob = 0;
-  dead();
+  d.no_rows();
   if (j < R) take(tab[j & (TABN - 1)]);
   const int t_min = __builtin_amdgcn_readfirstlane(d.wbs);
   const FusedParam &lastf = desc[R - 1];
@@ -358,7 +326,7 @@ __device__ void sweep_fast(const FusedParam *desc, int R, int N, int c, const do
         i -= 64 * c;
         st.reset();
         if (j < R) take(tab[j & (TABN - 1)]);
-        else dead();
+        else d.no_rows();
       }
       while (r_old < R && __builtin_amdgcn_readlane(j, r_old & 63) != r_old) r_old++;
     }
@@ -412,7 +380,7 @@ __device__ void sweep_fast(const FusedParam *desc, int R, int N, int c, const do
 }
 
 template <int MEL, int GL, bool LISTED, bool JOINT = false, bool EDIT = false>
-__global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, JOINT, EDIT>::type g) {
+__global__ __launch_bounds__(64, 3) void ell_kernel(EllArgsOf<LISTED, JOINT, EDIT> g) {
   static_assert(LISTED || !JOINT, "the joint variant is a listed one");
   static_assert(JOINT || !EDIT, "the edit variant takes its work from items, as the joint one");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -457,8 +425,8 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
     if constexpr (JOINT) {
       // one lane per hypothesis: check its substitutions, pack the effective ones (b != ref[p]) and file the item
       // under the lanes it needs — those of at most GL - 2 rows from the front, the others from the back
-      h0 = g.hyp_off[rd];
-      n_list = __builtin_amdgcn_readfirstlane((int)(g.hyp_off[rd + 1] - h0));
+      h0 = g.list.off[rd];
+      n_list = __builtin_amdgcn_readfirstlane((int)(g.list.off[rd + 1] - h0));
       const int back_ = dm.k - dm.central - 1, fwd_ = dm.central;
       int n_big = 0;
       bool bad = false;
@@ -466,58 +434,25 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
         const int q = q0 + lane;
         const bool have = q < n_list;
         int p1 = 0, rows = 1;
-        unsigned long long code = 0;
+        ell_items::code_t code = 0;
         if constexpr (EDIT) {
-          if (have) {
-            // (host-checked offsets: ni >= 0, and the letters read below lie inside ins_base)
-            const int64_t s0 = g.ins_off[h0 + q], ni = g.ins_off[h0 + q + 1] - s0;
-            const int d = g.edit_del[h0 + q];
-            p1 = g.edit_pos[h0 + q];
-            // a base of the read stays on either side: 1 <= p and p + d <= R - 1
-            bad = bad || p1 < 1 || d < 0 || d > EDIT_MAX_DEL || ni > EDIT_MAX_INS || p1 > R - 1 - d;
-            if (!bad) {
-              for (int t = 0; t < (int)ni; t++) {
-                const int sb = g.ins_base[s0 + t];
-                bad = bad || sb < 0 || sb >= alpha;  // (launch_ell refuses an alphabet above 8: a letter fits its nibble)
-                code |= (unsigned long long)(sb & 7) << (4 * t);
-              }
-              code |= (unsigned long long)ni << 52 | (unsigned long long)d << 56;
-              // back = 0: row p - 1 too, the band of its emitting row (boundary row p) changes
-              rows = min(R - d + (int)ni - 1, p1 + (int)ni - 1 + fwd_) - max(0, min(p1 - 1, p1 - back_)) + 1;
-              bad = bad || rows > JOINT_ROWS;
-            }
+          if (have && !bad) {
+            // (host-checked offsets: the letter count is >= 0, and the letters read lie inside ins_base)
+            const int64_t s0 = g.own.ins_off[h0 + q];
+            p1 = g.own.pos[h0 + q];
+            bad = !ell_items::edit_pack(R, alpha, back_, fwd_, p1, g.own.del[h0 + q], g.own.ins_base + s0,
+                                        g.own.ins_off[h0 + q + 1] - s0, code, rows);
           }
         } else if (have) {
-          const int64_t s1 = g.sub_off[h0 + q + 1];
-          int prev = -1, plast = 0;
-          for (int64_t s = g.sub_off[h0 + q]; s < s1; s++) {
-            const int sp = g.sub_pos[s], sb = g.sub_base[s];
-            // (prev >= -1: also sp < 0; launch_ell refuses an alphabet above 8, so a letter fits its 3 bits)
-            if (sp <= prev || sp >= R || sb < 0 || sb >= alpha) {
-              bad = true;
-              break;
-            }
-            prev = sp;
-            if (sb == g.a.reference[m.ref_off + sp]) continue;  // changes nothing: dropped
-            if (code == 0) p1 = sp;
-            if (sp - p1 >= JOINT_ROWS) {  // more rows than a group has lanes for, wherever the read ends
-              bad = true;
-              break;
-            }
-            code |= (unsigned long long)(8 | sb) << (4 * (sp - p1));
-            plast = sp;
-          }
-          if (code != 0) {
-            rows = min(R - 1, plast + fwd_) - max(0, p1 - back_) + 1;
-            code |= (unsigned long long)(plast - p1) << 60;  // (the offsets stay below 14: nibble 15 is free)
-          }
-          bad = bad || rows > JOINT_ROWS;
+          const int64_t s0 = g.own.sub_off[h0 + q];
+          bad = !ell_items::joint_pack(g.a.reference + m.ref_off, R, alpha, back_, fwd_, g.own.sub_pos + s0, g.own.sub_base + s0,
+                                       g.own.sub_off[h0 + q + 1] - s0, p1, code, rows) || bad;
         }
         const bool small = GL == 16 || rows + 2 <= GL;
         const unsigned long long ms = __ballot(have && small), mb = __ballot(have && !small);
         const unsigned long long below = (1ull << lane) - 1;
         const int slot = small ? n_small + __popcll(ms & below) : n_list - 1 - n_big - __popcll(mb & below);
-        if (have) g.items[h0 + slot] = make_int4(p1, q, (int)(unsigned)code, (int)(unsigned)(code >> 32));
+        if (have) g.items[h0 + slot] = make_int4(p1, q, ell_items::code_lo(code), ell_items::code_hi(code));
         n_small += __popcll(ms);
         n_big += __popcll(mb);
       }
@@ -526,11 +461,11 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
         continue;
       }
     } else if constexpr (LISTED) {
-      h0 = g.hyp_off[rd];
-      n_list = __builtin_amdgcn_readfirstlane((int)(g.hyp_off[rd + 1] - h0));
+      h0 = g.list.off[rd];
+      n_list = __builtin_amdgcn_readfirstlane((int)(g.list.off[rd + 1] - h0));
       bool bad = false;
       for (int q = lane; q < n_list; q += 64) {
-        const int hp = g.hyp_pos[h0 + q], hb = g.hyp_base[h0 + q];
+        const int hp = g.own.pos[h0 + q], hb = g.own.base[h0 + q];
         bad = bad || hp < 0 || hp >= R || hb < 0 || hb >= alpha;
       }
       if (__any(bad)) {
@@ -596,7 +531,7 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
     }
     const double no_snp = xm::to_log(tot);
     if constexpr (LISTED) {
-      if (lane == 0) g.out_total[rd] = no_snp;
+      if (lane == 0) g.list.out_total[rd] = no_snp;
     } else {
       for (int p = lane; p < R; p += 64) out[(size_t)p * alpha + ref[p]] = no_snp;
     }
@@ -625,30 +560,28 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
       else b0 += 64 / GL;
       int p = 0, b = 0, first = 0, last = 0, npos = 0;
       [[maybe_unused]] int hidx = 0;
-      [[maybe_unused]] unsigned long long code = 0;
-      [[maybe_unused]] int ed_i = 0, ed_d = 0;  // EDIT: inserted letters, deleted bases
+      [[maybe_unused]] ell_items::code_t code = 0;
+      [[maybe_unused]] ell_items::Edit ed = {0, 0, 0, 0};
       if constexpr (JOINT) {
         if (valid) {
           const int4 it = g.items[h0 + item];
           p = it.x;
           hidx = it.y;
-          code = ((unsigned long long)(unsigned)it.w << 32) | (unsigned)it.z;
+          code = ell_items::code_of(it.z, it.w);
           if constexpr (EDIT) {
-            ed_i = (int)(code >> 52) & 15;
-            ed_d = (int)(code >> 56);
-            first = max(0, min(p - 1, p - back));
-            last = min(R - ed_d + ed_i - 1, p + ed_i - 1 + fwd);
+            ed = ell_items::edit_unpack(p, code);
+            first = ell_items::edit_first(ed, back);
+            last = ell_items::edit_last(ed, R, fwd);
           } else {
-            const int plast = p + (int)(code >> 60);
-            first = max(0, p - back);
-            last = min(R - 1, plast + fwd);
+            first = ell_items::joint_first(p, back);
+            last = ell_items::joint_last(R, p + ell_items::joint_span(code), fwd);
           }
           npos = last - first + 1;
         }
       } else if (valid) {
         if constexpr (LISTED) {
-          p = g.hyp_pos[h0 + item];
-          b = g.hyp_base[h0 + item];
+          p = g.own.pos[h0 + item];
+          b = g.own.base[h0 + item];
         } else {
           p = item / (alpha - 1);
           int bi = item % (alpha - 1);
@@ -658,42 +591,31 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
         last = min(R - 1, p + fwd);
         npos = last - first + 1;
       }
-      // k-mer id of position `at` under the hypothesis: base p replaced by b, or (joint) the bases at p + o by those
-      // of `code`'s nibbles, or (edit) position `at` of the edited reference: its letters at p .. p + ed_i - 1, the
-      // read's bases ed_d - ed_i further on behind them
+      // k-mer id of position `at` under the hypothesis: base p replaced by b, or (joint) the bases the item
+      // substitutes, or (edit) position `at` of the edited reference, through the edit map
       auto kid = [&](int at) {
         if constexpr (EDIT)
-          return kmer_id_mapped(dm, ref, R, cb, nb, ca, na, at, [&](int &j, int &v) {
-            const unsigned o = (unsigned)(j - p);
-            v = (int)(code >> (4 * (o & 15))) & 7;
-            if (j >= p) j += ed_d - ed_i;
-            return o < (unsigned)ed_i;
-          });
+          return kmer_id_mapped(dm, ref, R, cb, nb, ca, na, at,
+                                [&](int &j, int &v) { return ell_items::edit_at(ed, j, v); });
         else if constexpr (JOINT)
-          return kmer_id(dm, ref, R, cb, nb, ca, na, at, [&](int j, int &v) {
-            const unsigned o = (unsigned)(j - p);
-            const int nib = o < (unsigned)JOINT_ROWS ? (int)(code >> (4 * o)) & 15 : 0;
-            v = nib & 7;
-            return (nib & 8) != 0;
-          });
+          return kmer_id(dm, ref, R, cb, nb, ca, na, at,
+                         [&](int j, int &v) { return ell_items::joint_at(p, code, j, v); });
         else
           return kmer_id(dm, ref, R, cb, nb, ca, na, at, [&](int j, int &v) { v = b; return j == p; });
       };
-      // boundary row r of the hypothesis' reference as a row of the read's band arrays (bs / be): itself, except EDIT,
-      // where an inserted row takes its start from the last row before the edit and its end from the first one behind
-      // it, and the rows behind the edit are the read's rows ed_d - ed_i further on
+      // boundary row r of the hypothesis' reference as a row of the read's band arrays (bs / be): itself, except EDIT
       auto row_s = [&](int r) {
-        if constexpr (EDIT) return r < p ? r : r < p + ed_i ? p - 1 : r - ed_i + ed_d;
+        if constexpr (EDIT) return ell_items::edit_row_s(ed, r);
         else return r;
       };
       auto row_e = [&](int r) {
-        if constexpr (EDIT) return r < p ? r : r < p + ed_i ? p + ed_d : r - ed_i + ed_d;
+        if constexpr (EDIT) return ell_items::edit_row_e(ed, r);
         else return r;
       };
       const bool is_pos = valid && gl >= 1 && gl <= npos;
       const bool is_fin = valid && gl == npos + 1;
       HypDesc d;
-      d.wbs = 0x40000000; d.wbe = -0x40000000; d.elo = 0x40000000; d.ebe = -0x40000000;
+      d.no_rows();
       d.has_wob = 0; d.bm = 0.0; d.bac = 0.0; d.bmc = 0.0;
       // input stream of the lane: cell i lives at pre[sbase + i] (the suffix rows follow the
       // prefix rows in the same store, g.half cells on), valid for i in [slo, shi]; every other cell
@@ -716,7 +638,7 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
         // closing lane of an edit: no quirk — the wobble row lives on band last + 1, where the prefix sweep puts it
         // (dtw.cpp:53-58), so the value is the total of the edited reference.  Boundary row last + 1 lies behind the
         // edit: it is the read's row `close`, whose band it has and whose suffix row closes the hypothesis
-        const int close = last + 1 - ed_i + ed_d;
+        const int close = ell_items::edit_close(ed, last);
         d.has_wob = (close < R && g.wobbling) ? 1 : 0;
         if (d.has_wob) idb = kid(last + 1);
         d.wbs = bs[close]; d.wbe = be[close];
@@ -749,8 +671,7 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
       const int base = valid ? bs[first] : 0;
       int steps = 0;
       if (is_fin) steps = d.wbe - base + gl + 1;
-      for (int dlt = 32; dlt >= 1; dlt >>= 1) steps = max(steps, __shfl_xor(steps, dlt, 64));
-      steps = __builtin_amdgcn_readfirstlane(steps);  // uniform trip count
+      steps = __builtin_amdgcn_readfirstlane(wave_max(steps));  // uniform trip count
       const int i0 = base - gl;
       // clamped, unsigned element offsets from uniform base pointers (scalar base + 32-bit offset)
       // byte offset of the stream's cell i from the slot's (scalar) base; the store's zero cell outside the band
@@ -820,8 +741,8 @@ __global__ __launch_bounds__(64, 3) void ell_kernel(typename EllArgsOf<LISTED, J
         acc = xm::norm(acc);
         if (RING && acc.e < xm::XZ / 2) acc = xm::zero();  // made of nothing but out-of-band values (fused_step_ring)
         // LISTED: b == ref[p] is no substitution — the total of the two sweeps, as the full matrix holds it there
-        if constexpr (JOINT) g.out_hyp[h0 + hidx] = code == 0 ? no_snp : xm::to_log(acc);
-        else if constexpr (LISTED) g.out_hyp[h0 + item] = (b == ref[p]) ? no_snp : xm::to_log(acc);
+        if constexpr (JOINT) g.list.out_hyp[h0 + hidx] = code == 0 ? no_snp : xm::to_log(acc);
+        else if constexpr (LISTED) g.list.out_hyp[h0 + item] = (b == ref[p]) ? no_snp : xm::to_log(acc);
         else out[(size_t)p * alpha + b] = xm::to_log(acc);
       }
     }
@@ -838,41 +759,20 @@ namespace {
 // instantiation for the batch's min event length and group width, `slots` blocks of one wave with `lds` bytes.
 template <bool LISTED, bool JOINT, bool EDIT>
 int ell_dispatch(nvk_ctx *ctx, const EllArgs &base, const EllHyp &hyp, bool wide_groups, int64_t slots, size_t lds) {
-  typedef typename EllArgsOf<LISTED, JOINT, EDIT>::type Args;
+  typedef EllArgsOf<LISTED, JOINT, EDIT> Args;
   Args g;
   static_cast<EllArgs &>(g) = base;
-  if constexpr (LISTED) {
-    g.hyp_off = hyp.off;
-    g.hyp_pos = hyp.listed.pos;    // (null for the variants that take their work from items)
-    g.hyp_base = hyp.listed.base;
-    g.out_total = hyp.out_total;
-    g.out_hyp = hyp.out_hyp;
-  }
-  if constexpr (JOINT) g.items = (int4 *)ctx->ws[WS_JOINT];
-  if constexpr (JOINT && !EDIT) {
-    g.sub_off = hyp.joint.sub_off;
-    g.sub_pos = hyp.joint.sub_pos;
-    g.sub_base = hyp.joint.sub_base;
-  }
-  if constexpr (EDIT) {
-    g.edit_pos = hyp.edit.pos;
-    g.edit_del = hyp.edit.del;
-    g.ins_off = hyp.edit.ins_off;
-    g.ins_base = hyp.edit.ins_base;
-  }
-  void (*kern)(Args) = nullptr;
-  // What is built: every M of 0..4 x {8, 16} lanes per hypothesis x the four (LISTED, JOINT, EDIT) combinations launch_ell
-  // dispatches, 5 x 2 x 4 = 40 kernels, all of them reachable: M is the batch's min event length (checked by launch_ell),
-  // the lanes follow the table's k (k + 2 <= 8 or not) and the kind is the entry point.
-#define ELL_PICK(M) kern = wide_groups ? ell_kernel<M, 16, LISTED, JOINT, EDIT> : ell_kernel<M, 8, LISTED, JOINT, EDIT>
-  switch (base.a.mel) {
-    case 0: ELL_PICK(0); break;
-    case 1: ELL_PICK(1); break;
-    case 2: ELL_PICK(2); break;
-    case 3: ELL_PICK(3); break;
-    default: ELL_PICK(4); break;
-  }
-#undef ELL_PICK
+  if constexpr (LISTED) g.list = hyp.list;
+  if constexpr (EDIT) g.own = hyp.edit;
+  else if constexpr (JOINT) g.own = hyp.joint;
+  else if constexpr (LISTED) g.own = hyp.listed;
+  if constexpr (LISTED) g.items = JOINT ? (int4 *)ctx->ws[WS_JOINT] : nullptr;
+  // What is built: M of 0..4 (the batch's min event length, checked by launch_ell) x {8, 16} lanes per hypothesis (the
+  // table's k: k + 2 <= 8 or not) x the four kinds (the entry point), 5 x 2 x 4 = 40 kernels, all of them reachable.
+#define ELL_PAIR(M) {ell_kernel<M, 8, LISTED, JOINT, EDIT>, ell_kernel<M, 16, LISTED, JOINT, EDIT>}
+  static void (*const kernels[5][2])(Args) = {ELL_PAIR(0), ELL_PAIR(1), ELL_PAIR(2), ELL_PAIR(3), ELL_PAIR(4)};
+#undef ELL_PAIR
+  void (*const kern)(Args) = kernels[base.a.mel][wide_groups ? 1 : 0];
   if (lds > 64 * 1024) {
     NVK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
@@ -883,7 +783,7 @@ int ell_dispatch(nvk_ctx *ctx, const EllArgs &base, const EllHyp &hyp, bool wide
   NVK_HIP(hipGetLastError());
   // launch report (include/nadavca_hip.h)
   nvk_launch_note(ctx, nvk_launch_rec{NVK_LAUNCH_ELL, base.a.mel, base.wobbling, wide_groups ? 16 : 8, 0,
-                                      (int32_t)(!LISTED ? NVK_ELL_FULL : EDIT ? NVK_ELL_EDIT : JOINT ? NVK_ELL_JOINT : NVK_ELL_LISTED),
+                                      (int32_t)hyp.kind,
                                       base.c_max, base.H, base.SR, (int32_t)lds, base.a.n_reads, 1});
   return NVK_OK;
 }
@@ -964,7 +864,7 @@ int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobb
   g.out_status = out_status;
   ctx->last_spill_bytes = (int64_t)tot.cells * 24 * 2;
   if (items) {
-    if ((rc = nvk_ws_reserve(ctx, WS_JOINT, (size_t)(hyp.total_hyp + 1) * sizeof(int4)))) return rc;
+    if ((rc = nvk_ws_reserve(ctx, WS_JOINT, (size_t)(hyp.list.total_hyp + 1) * sizeof(int4)))) return rc;
   }
   switch (hyp.kind) {
     case EllKind::Full: return ell_dispatch<false, false, false>(ctx, g, hyp, wide_groups, slots, lds);

@@ -279,22 +279,25 @@ int launch_plan_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int
                     const EllPlan &pl, unsigned long long *bandtmp, PlanTotals *totals);
 // What a launch of ell_kernel scores.  Full: every substitution of every position, into out_ll; nothing below `kind`
 // is read.  The other kinds: read j's hypotheses off[j] .. off[j+1] of a list, into out_total / out_hyp (out_ll
-// unused), the list being the members of the kind's own group.
-enum class EllKind { Full, Listed, Joint, Edit };
-struct EllHyp {
-  EllKind kind = EllKind::Full;
+// unused), the list being the kind's own struct — which is also what its kernels take as their argument.
+enum class EllKind { Full = NVK_ELL_FULL, Listed = NVK_ELL_LISTED, Joint = NVK_ELL_JOINT, Edit = NVK_ELL_EDIT };
+// Listed (nvk_estimate_hypotheses_batch_dev): hypothesis h is the substitution (pos[h], base[h])
+struct EllListed { const int32_t *pos, *base; };
+// Joint (.._joint_hypotheses_..): hypothesis h is the substitutions sub_off[h] .. sub_off[h+1] of (sub_pos, sub_base)
+struct EllJoint { const int64_t *sub_off; const int32_t *sub_pos, *sub_base; };
+// Edit (.._edit_hypotheses_..): h deletes del[h] bases from pos[h] on and inserts ins_off[h] .. ins_off[h+1] of ins_base
+struct EllEdit { const int32_t *pos, *del; const int64_t *ins_off; const int32_t *ins_base; };
+struct EllList {  // what the three listed kinds share
   const int64_t *off = nullptr;
   double *out_total = nullptr;  // [n_reads]
   double *out_hyp = nullptr;    // [off[n_reads]]
   int64_t total_hyp = 0;        // off[n_reads]; Joint and Edit keep one item per hypothesis in WS_JOINT
-  // Listed (nvk_estimate_hypotheses_batch_dev): hypothesis h is the substitution (pos[h], base[h])
-  struct { const int32_t *pos, *base; } listed = {};
-  // Joint (nvk_estimate_joint_hypotheses_batch_dev): hypothesis h is the set of substitutions sub_off[h] ..
-  // sub_off[h+1] of (sub_pos, sub_base)
-  struct { const int64_t *sub_off; const int32_t *sub_pos, *sub_base; } joint = {};
-  // Edit (nvk_estimate_edit_hypotheses_batch_dev): hypothesis h deletes del[h] bases from pos[h] on and inserts the
-  // letters ins_off[h] .. ins_off[h+1] of ins_base
-  struct { const int32_t *pos, *del; const int64_t *ins_off; const int32_t *ins_base; } edit = {};
+};
+struct EllHyp {
+  EllKind kind = EllKind::Full;
+  EllList list;
+  EllListed listed = {};  // the list of `kind`:
+  EllJoint joint = {}; EllEdit edit = {};
 };
 int launch_ell(nvk_ctx *ctx, const DeviceModel &dm, const BatchArgs &a, int wobbling,
                const EllPlan &pl, const PlanTotals &tot, double *out_ll, int32_t *out_status, const EllHyp &hyp);

@@ -1,5 +1,5 @@
 """Census of the built kernel variants: every kernel pair select_sweeps has (csrc/kernels_align3.hip), every
-align_kernel<MEL> (csrc/kernels_align.hip) and every ell_kernel<M, lanes, kind> of ELL_PICK (csrc/kernels_ell.hip) is
+align_kernel<MEL> (csrc/kernels_align.hip) and every ell_kernel<M, lanes, kind> of ell_dispatch's tables (csrc/kernels_ell.hip) is
 launched by a named smallest case of tests/variant_cases.py and compared with the CPU oracle there.
 
 Which variant a batch ran is what the library's launch report says (include/nadavca_hip.h: nvk_last_launches,
@@ -409,7 +409,7 @@ def test_ell_case(oracle_port, case):
 
 
 def test_every_built_log_likelihood_kernel_was_run_and_compared(oracle_port):
-    """ELL_PICK builds the full product (csrc/kernels_ell.hip), 40 kernels."""
+    """ell_dispatch's tables hold the full product (csrc/kernels_ell.hip), 40 kernels."""
     ran = {_run_ell(oracle_port, case)['variant'] for case in ELL}
     assert ran == {(mel, lanes, kind) for mel in range(5) for lanes in (8, 16) for kind in vc.ELL_KINDS}
     assert len(ran) == 40

@@ -39,7 +39,7 @@ def test_names_are_unique_and_say_what_the_case_is_for():
 
 
 def test_every_log_likelihood_kernel_has_a_case():
-    """ELL_PICK builds min event length 0-4 x {8, 16} lanes x the four kinds (csrc/kernels_ell.hip)."""
+    """ell_dispatch's kernel tables hold min event length 0-4 x {8, 16} lanes x the four kinds (csrc/kernels_ell.hip)."""
     have = {(c['mel'], c['lanes'], c['kind']) for c in ELL}
     assert have == set(itertools.product(range(5), (8, 16), vc.ELL_KINDS)) and len(ELL) == 40
     for c in ELL:

@@ -16,8 +16,8 @@ The variants (csrc/kernels_align3.hip, select_sweeps / launch_align3): one wave 
 + 1, so the team reads here are as short as has more than 256 rows (140 bases with transition rows, 270 without), 8-12
 samples per base, and as wide a band as the skew needs.
 
-Log-likelihood cases: ``dict(name, kind, lanes, mel, model, bandwidth, reads, ...)`` — the 40 kernels of ELL_PICK
-(csrc/kernels_ell.hip): min event length 0-4 x 8 lanes per hypothesis (k = 5) or 16 (k = 7) x full matrix / listed /
+Log-likelihood cases: ``dict(name, kind, lanes, mel, model, bandwidth, reads, ...)`` — the 40 kernels of ell_dispatch's
+tables (csrc/kernels_ell.hip): min event length 0-4 x 8 lanes per hypothesis (k = 5) or 16 (k = 7) x full matrix / listed /
 joint / edit hypotheses.  The four kinds of one (mel, lanes) share their reads."""
 import numpy as np
 
@@ -254,7 +254,7 @@ def align_cases():
 ELL_KINDS = ('full', 'listed', 'joint', 'edit')
 ELL_LANES = {8: (41, 5, 2), 16: (42, 7, 3)}   # lanes per hypothesis -> (seed, k, central) of synth_model_arrays
 ELL_BW = 200
-JOINT_ROWS = 14      # csrc/kernels_ell.hip: rows one hypothesis re-runs at most
+JOINT_ROWS = 14      # csrc/ell_items.h: rows one hypothesis re-runs at most
 ELL_C_MAX = 62       # launch_ell's largest skew: at 63 the signal ring doubles to 8192 samples and leaves 160 KB
 _ell_models = {}
 _ell_batches = {}
