@@ -72,7 +72,8 @@ enum {
   NVK_K_POSTERIOR = 6,   /* windowed posterior */
   NVK_K_RENORM = 7,      /* normalisation, per-event means, linear re-fit (align_signal's renorm loop) */
   NVK_K_METH = 8,        /* pattern occurrences and their scores (detect_meth) */
-  NVK_K_SEED = 9,        /* banded local alignment + traceback of the seed aligner (nvk_seed_extend_dev) */
+  NVK_K_SEED = 9,        /* the seed aligner: banded local alignment + traceback (nvk_seed_extend_*_dev), seed chains
+                            (nvk_seed_chain_dev) */
   NVK_K_KMER = 10,       /* per-event and per-k-mer sample statistics of k-mer table training (nvk_kmer_*_dev) */
   NVK_K_ALLELE = 11,     /* per-site allele mixtures: rows and the per-position solve (nvk_allele_*_dev) */
   NVK_K_SITE = 12,       /* per-site event-level pile-up: rows and the per-key moments (nvk_site_*_dev) */
@@ -579,6 +580,56 @@ int nvk_seed_extend_bounded_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_que
                                 const int32_t *diag, const int32_t *ref_lo, const int32_t *ref_hi, int band, int match,
                                 int mismatch, int gap_open, int gap_extend, int min_score, int32_t *out_hit,
                                 int32_t *out_pairs);
+
+/* The chaining stage of the seed aligner (seedalign.py with chain = 1): per read, the best collinear chain of its
+ * seeds, and from it a band centre for every strip of 64 read rows, which nvk_seed_extend_path_dev follows.  THE
+ * CONTRACT, integers only.  Read j has m_j = q_off[j+1] - q_off[j] bases, strand[j] as above, and the seeds
+ * seed_off[j] .. seed_off[j+1] of (seed_i, seed_p): read k-mer i equals k-mer p of the read's strand,
+ * 0 <= i < m_j, 0 <= p < 2^30, sorted ascending by (p, i) (none of this is checked: other values give other numbers,
+ * never an access out of bounds).  Seeds are numbered t = 0, 1, .. in that order.  With k, w = band (1..256),
+ * max_gap >= 1 and lookback in 1..64:
+ *   predecessor  u of t: t - lookback <= u < t, and with di = i_t - i_u, dp = p_t - p_u:
+ *                0 < di <= max_gap, 0 < dp <= max_gap, |dp - di| <= w
+ *   score        f[t] = max(k, max over predecessors u of f[u] + min(di, dp, k) - |dp - di|); pred[t] is the u that
+ *                reaches the maximum, the largest such u (the nearest seed) on a tie, and none when no predecessor's
+ *                candidate exceeds k: a chain starts at t
+ *   chain        ends at the t with the largest f, the smallest such t on a tie; its anchors are t, pred[t],
+ *                pred[pred[t]], ..: i and p both strictly increase along it
+ *   strip centre strip s = 0 .. ceil(m_j / 64) - 1 covers the rows 64 s .. 64 s + 63;
+ *                strip_diag[strip_off[j] + s] = p - i of the anchor whose i is nearest to 64 s + 32, the smaller i
+ *                on a tie
+ * out_chain i32[2 n_reads]: per read (f of the chain's end, number of anchors).  A read without seeds, or with a strand
+ * other than 0 or 1, gets (0, 0) and its entries of strip_diag are left as they were: the caller fills strip_diag
+ * (i32[total_strips]) beforehand with the centre such a read is to get.  strip_off must be the running sum of
+ * ceil(m_j / 64).  q_off, seed_off and strip_off are copied to the host and checked (start at 0, never decrease, end
+ * at total_query / total_seeds / total_strips; no read above 2^26 bases or 2^26 seeds; the strip counts).  k in 1..16.
+ * The kernel keeps f and pred in 8 bytes per seed of the ctx's workspace and is timed under NVK_K_SEED.
+ * NVK_ERR_INVALID for bad arguments, NVK_ERR_UNSUPPORTED for band > 256.  Device pointers. */
+int nvk_seed_chain_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_query, const int64_t *q_off,
+                       const int32_t *strand, int64_t total_seeds, const int64_t *seed_off, const int32_t *seed_i,
+                       const int32_t *seed_p, int k, int band, int max_gap, int lookback, int64_t total_strips,
+                       const int64_t *strip_off, int32_t *strip_diag, int32_t *out_chain);
+
+/* nvk_seed_extend_dev with a band that follows a path: the band of row i of read j is centred on
+ * d(i) = strip_diag[strip_off[j] + i / 64] instead of the read's one diag[j] (strip_off, strip_diag and total_strips as
+ * in nvk_seed_chain_dev; any int32 is a valid centre).  The same kernel body and the same rules, with
+ *   cells   (i, j), 0 <= i < m, 0 <= j < G, d(i) - w <= j - i <= d(i) + w
+ * and every "is a cell" of the rules — in E, in F and in what the traceback may stand on — meaning a cell of that
+ * row's own band.  D = (H[i-1][j-1] if (i-1, j-1) is a cell, else 0) + (q[i] == r[j] ? match : -mismatch); with one
+ * centre per read (i-1, j-1) is a cell whenever i > 0 and j > 0, so this is the rule above.  Where two strips' bands
+ * share no diagonal, no cell of the second has a neighbour in the first, and alignments start afresh there.  The
+ * traceback's DIAG step from (i, j) ends the walk where (i-1, j-1) is not a cell (its D took 0 from there).  With
+ * every centre of read j equal to d the outputs are those of nvk_seed_extend_dev with diag[j] = d.
+ * ref_lo, ref_hi: both NULL — the whole strand — or both i32[n_reads], and then the bounded rules of
+ * nvk_seed_extend_bounded_dev apply as well, with its checks.  The traceback store, its size and the chunking under
+ * nvk_ctx_set_workspace_limit's cap are nvk_seed_extend_dev's.  strip_off is copied to the host and checked as
+ * nvk_seed_chain_dev checks it.  NVK_ERR_INVALID for bad arguments (one of ref_lo / ref_hi NULL among them),
+ * NVK_ERR_UNSUPPORTED for band > 256.  Device pointers. */
+int nvk_seed_extend_path_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_query, const int32_t *query,
+                             const int64_t *q_off, const int32_t *reference, int64_t ref_len, const int32_t *strand,
+                             int64_t total_strips, const int64_t *strip_off, const int32_t *strip_diag,
+                             const int32_t *ref_lo, const int32_t *ref_hi, int band, int match, int mismatch,
+                             int gap_open, int gap_extend, int min_score, int32_t *out_hit, int32_t *out_pairs);
 
 /* The M-step of k-mer table training (nadavca_amd/kmer_train.py: estimate_kmer_model): per-k-mer sample statistics
  * over the final events of an aligned batch.  THE CONTRACT.  Inputs are one batch in the flat layout above: signal /

@@ -91,6 +91,9 @@ SIGNATURES = {
     'nvk_seed_extend_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp] + [_int] * 6 + [_vp, _vp]),
     'nvk_seed_extend_bounded_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp] + [_int] * 6
                                     + [_vp, _vp]),
+    'nvk_seed_chain_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp] + [_int] * 4 + [_i64, _vp, _vp, _vp]),
+    'nvk_seed_extend_path_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp] + [_int] * 6
+                                 + [_vp, _vp]),
     'nvk_kmer_event_stats_dev': (_int, [_vp, _i64, _i64] + [_vp] * 10 + [_int] * 4 + [_vp] * 4),
     'nvk_kmer_reduce_dev': (_int, [_vp, _i64, _i64] + [_vp] * 6),
     'nvk_mod_kmer_rows_dev': (_int, [_vp, _i64, _i64] + [_vp] * 10 + [_int] * 4 + [_i64, _vp, _vp, _vp, _int, _vp, _i64]

@@ -21,6 +21,16 @@
 // wave like the read itself, and the sweep counts its columns from ref_lo, so its inner loop is the same for both
 // entries.  The one kernel body is compiled twice (seedext_kernel<BOUNDED>): without bounds it is, instruction for
 // instruction, the kernel it was before there were any.
+//
+// nvk_seed_extend_path_dev (seedext_kernel<BOUNDED, true>) lets the band follow a path: strip s of a read has its own
+// centre, strip_diag[strip_off[j] + s] (from the seed chain, kernels_seedchain.hip), so the band's first diagonal lo
+// is a scalar per strip instead of per read.  Inside a strip nothing changes.  At a strip's first row lane 0 finds
+// its up and diagonal neighbours in the previous strip's last row at band offsets moved by delta = lo_s - lo_(s-1);
+// an offset outside 0 .. 2w is no cell (H 0, F NEG: the slot behind the row's last).  Lane 63 writes that row while
+// lane 0 still reads the previous one, which one buffer allows only for delta >= -127, so the path form keeps two
+// and alternates.  The traceback takes lo from the strip of the row it stands on.  A centre so far off that its strip
+// has no cell is pulled in to the nearest centre that still has none (path_lo): every diagonal then fits an int32.
+// With PATH false the body is the one above, and the two kernels compiled from it are unchanged.
 #include <vector>
 
 #include "nvk_internal.h"
@@ -48,6 +58,8 @@ struct SeedArgs {
   int r0, r1;                // the chunk's reads
   int *counter;
   const int32_t *ref_lo, *ref_hi;  // seedext_kernel<true>: per read, the range of its cells' j on its strand
+  const int32_t *strip_diag;       // seedext_kernel<., true>: the band centre per strip of 64 rows, read j's strips
+  const int64_t *strip_off;        // at strip_off[j] (diag is not read)
 };
 
 // a base code outside 0..3 never equals anything: -2 in the read, -1 in the reference
@@ -61,13 +73,23 @@ __device__ __forceinline__ int ref_code(const int32_t *ref, int G, int st, int j
   return c >= 0 && c <= 3 ? (st ? 3 - c : c) : -1;
 }
 
+// The first diagonal of a strip's band whose centre is d, for a read of m rows over the columns [rlo, rlo + Gr):
+// d - w, with d held to rlo - m - w .. rlo + Gr + w.  Row i has cells iff d - w <= rlo + Gr - 1 - i and
+// d + w >= rlo - i, so at either limit, as beyond it, no row 0 .. m - 1 has any.
+__device__ __forceinline__ int path_lo(int d, int w, int rlo, int Gr, int m) {
+  const int64_t c = min(max((int64_t)d, (int64_t)rlo - m - w), (int64_t)rlo + Gr + w);
+  return (int)(c - w);
+}
+
 // BOUNDED: every read has its own column range (nvk_seed_extend_bounded_dev); otherwise the range is the whole strand
-// and the compiled kernel is the one nvk_seed_extend_dev always ran.
-template <bool BOUNDED>
+// and the compiled kernel is the one nvk_seed_extend_dev always ran.  PATH: a band centre per strip
+// (nvk_seed_extend_path_dev) instead of one per read.
+template <bool BOUNDED, bool PATH>
 __global__ __launch_bounds__(64) void seedext_kernel(SeedArgs a) {
+  constexpr int NB = PATH ? 2 : 1;                  // PATH: strip s writes buffer s & 1 and reads the other
   __shared__ int32_t s_ref[64 + 2 * SEED_WMAX];     // r[jbase + x], x = lane + b
-  __shared__ int32_t s_h[2 * SEED_WMAX + 2];        // H and F of the previous strip's last row, by band offset
-  __shared__ int32_t s_f[2 * SEED_WMAX + 2];
+  __shared__ int32_t s_h[NB][2 * SEED_WMAX + 2];    // H and F of the previous strip's last row, by band offset
+  __shared__ int32_t s_f[NB][2 * SEED_WMAX + 2];
   const int lane = threadIdx.x;
   const int w = a.w, W2 = 2 * w, C = (W2 + 8) / 8;  // dwords per row: ceil((2w + 1) / 8)
   const int O = a.gap_open + a.gap_extend, X = a.gap_extend;
@@ -79,29 +101,50 @@ __global__ __launch_bounds__(64) void seedext_kernel(SeedArgs a) {
     const int64_t rd = (int64_t)a.r0 + __builtin_amdgcn_readfirstlane(atomicAdd(a.counter, lane == 0 ? 1 : 0));
     if (rd >= a.r1) return;
     __syncthreads();  // (the previous read's last reads of s_h / s_f)
-    for (int x = lane; x < 2 * SEED_WMAX + 2; x += 64) {
-      s_h[x] = 0;
-      s_f[x] = SEED_NEG;
-    }
+    for (int x = lane; x < 2 * SEED_WMAX + 2; x += 64)
+      for (int u = 0; u < NB; u++) {
+        s_h[u][x] = 0;
+        s_f[u][x] = SEED_NEG;
+      }
     const int64_t q0 = a.q_off[rd];
     const int m = (int)(a.q_off[rd + 1] - q0);
     const int st = a.strand[rd];
     const int G = a.G;
     int bh = -1, bi = -1, bj = -1;  // this lane's best cell: largest H, then smallest i, then smallest j
-    const int64_t dd = a.diag[rd];
+    const int64_t dd = PATH ? 0 : a.diag[rd];
     // the read's columns [rlo, rlo + Gr) on its strand: wave-uniform, as the read is.  Below, j counts columns from
     // rlo, so that the sweep and the traceback compare it with 0 and Gr exactly as they do for the whole reference
     // (rlo = 0, Gr = G); only the staging of the strand and what is reported add rlo back.
     const int rlo = BOUNDED ? __builtin_amdgcn_readfirstlane(a.ref_lo[rd]) : 0;
     const int Gr = BOUNDED ? __builtin_amdgcn_readfirstlane(a.ref_hi[rd]) - rlo : G;
     // any cell at all: the band [d* - w, d* + w] meets the diagonals rlo-(m-1) .. rlo+Gr-1 of the matrix
-    const bool run = (st == 0 || st == 1) && m > 0 && Gr > 0 && dd - w <= rlo + Gr - 1 &&
-                     dd + w >= rlo - (int64_t)(m - 1);
-    const int lo = run ? (int)(dd - w) : 0;  // the band's first diagonal on the strand
-    const int lor = lo - rlo;                // and counted from rlo
+    // (PATH: every strip is swept, one without a cell like any other)
+    const bool meets = (st == 0 || st == 1) && m > 0 && Gr > 0 && dd - w <= rlo + Gr - 1 &&
+                       dd + w >= rlo - (int64_t)(m - 1);
+    const bool run = PATH ? (st == 0 || st == 1) && m > 0 && Gr > 0 : meets;
+    const int lo_read = run ? (int)(dd - w) : 0;  // the band's first diagonal on the strand
+    const int lor_read = lo_read - rlo;           // and counted from rlo
+    int lo_strip = 0;                             // PATH: the same two of the strip at hand
+    const int32_t *sd = PATH ? a.strip_diag + a.strip_off[rd] : nullptr;
     uint32_t *tb = a.tb + a.tb_off[rd];
     const int n_strips = run ? (m + 63) / 64 : 0;
+    int d_next = 0;  // PATH: the next strip's centre, asked for one strip ahead of its use
+    if constexpr (PATH)
+      if (n_strips > 0) d_next = sd[0];
     for (int s = 0; s < n_strips; s++) {
+      int delta = 0;  // lo_s - lo_(s-1)
+      if constexpr (PATH) {
+        const int nlo = path_lo(__builtin_amdgcn_readfirstlane(d_next), w, rlo, Gr, m);
+        if (s + 1 < n_strips) d_next = sd[s + 1];
+        delta = s > 0 ? nlo - lo_strip : 0;
+        lo_strip = nlo;
+      }
+      const int lo = PATH ? lo_strip : lo_read, lor = PATH ? lo_strip - rlo : lor_read;
+      // a band offset of the previous strip's last row as an index of s_h / s_f: outside 0 .. 2w, the empty slot 2w + 1
+      // (one unsigned minimum: a negative x is a large unsigned one)
+      auto slot = [&](int x) { return (int)min((unsigned)x, (unsigned)(W2 + 1)); };
+      const int cur = PATH ? s & 1 : 0, prv = PATH ? cur ^ 1 : 0;
+      const int dl = lane == 0 ? delta : 0;  // what moves this lane's up neighbour's offset
       const int i = s * 64 + lane;
       const int jbase = s * 64 + lo;
       __syncthreads();  // (the previous strip's, or read's, last reads of s_ref)
@@ -111,13 +154,14 @@ __global__ __launch_bounds__(64) void seedext_kernel(SeedArgs a) {
       const int rows = min(64, m - s * 64);
       const int steps = W2 + 1 + 2 * (rows - 1);
       int h = 0, e = SEED_NEG, f = SEED_NEG;  // this lane's last cell: (i, b-1) at the next step
-      int hu_prev = s > 0 ? s_h[0] : 0;       // lane 0: the diagonal neighbour of its first cell
+      int hu_prev = s > 0 ? s_h[prv][PATH ? slot(delta) : 0] : 0;  // lane 0: the diagonal neighbour of its first cell
       uint32_t acc = 0;
       for (int t = 0; t < steps; t++) {
         int hu = dpp_ror1(h), fu = dpp_ror1(f);  // lane l-1's last cell: (i-1, b+1)
         const int b = t - 2 * lane;
-        const int x0 = min(t + 1, W2 + 1);       // lane 0's b + 1: one LDS address for the whole wave
-        const int lh = s_h[x0], lf = s_f[x0];
+        // lane 0's b + 1 (PATH: in the previous strip's offsets): one LDS address for the whole wave
+        const int x0 = PATH ? slot(t + 1 + delta) : min(t + 1, W2 + 1);
+        const int lh = s_h[prv][x0], lf = s_f[prv][x0];
         hu = lane == 0 ? lh : hu;
         fu = lane == 0 ? lf : fu;
         const int hd = hu_prev;                  // (i-1, b): what arrived one step ago
@@ -129,7 +173,8 @@ __global__ __launch_bounds__(64) void seedext_kernel(SeedArgs a) {
         const bool lok = b >= 1 && j >= 1;       // (i, j-1) is a cell
         const int eo = h - O, ex = e - X;
         const int E = lok ? max(eo, ex) : SEED_NEG;
-        const bool uok = i >= 1 && b + 1 <= W2;  // (i-1, j) is a cell
+        // (i-1, j) is a cell (PATH: its offset in the row above, b + 1 + dl, lies in 0 .. 2w; below 0 only where b is)
+        const bool uok = i >= 1 && (PATH ? (unsigned)(b + 1 + dl) <= (unsigned)W2 : b + 1 <= W2);
         const int fo = hu - O, fx = fu - X;
         const int F = uok ? max(fo, fx) : SEED_NEG;
         const int best = max(D, max(E, F));
@@ -146,8 +191,8 @@ __global__ __launch_bounds__(64) void seedext_kernel(SeedArgs a) {
         }
         if (b >= 0 && b <= W2) {
           if (lane == 63) {
-            s_h[b] = h;
-            s_f[b] = f;
+            s_h[cur][b] = h;
+            s_f[cur][b] = f;
           }
           acc |= nib << (4 * (b & 7));
           if ((b & 7) == 7 || b == W2) {
@@ -176,7 +221,14 @@ __global__ __launch_bounds__(64) void seedext_kernel(SeedArgs a) {
       // traceback from the end cell, walked by every lane alike (uniform loads); lane 0 stores pair k to slot
       // q0 + m - 1 - k, so they end up ascending
       int i = bi, j = bj, state = 0;  // 0: H, 1: E, 2: F
+      int ts = -1, lor_ts = 0;        // PATH: the strip the walk stands in, and its lor
       for (;;) {
+        if constexpr (PATH)
+          if (i >= 0 && (i >> 6) != ts) {
+            ts = i >> 6;
+            lor_ts = path_lo(__builtin_amdgcn_readfirstlane(sd[ts]), w, rlo, Gr, m) - rlo;
+          }
+        const int lor = PATH ? lor_ts : lor_read;
         const int b = j - i - lor;
         // (the rules keep the walk on cells of the band; the guard keeps every access in bounds regardless)
         if (i < 0 || j < 0 || b < 0 || b > W2 || cnt >= m) break;
@@ -225,12 +277,14 @@ __global__ __launch_bounds__(64) void seedext_kernel(SeedArgs a) {
 
 }  // namespace
 
-// both entries: ``bounded`` takes ref_lo / ref_hi (checked on the host, as q_off is), the other passes none
-static int seed_extend(const char *what, bool bounded, nvk_ctx *ctx, int64_t n_reads, int64_t total_query,
+// the three entries: ``bounded`` takes ref_lo / ref_hi (checked on the host, as q_off is), the others pass none;
+// ``path`` takes strip_off / strip_diag (strip_off checked on the host) and no diag
+static int seed_extend(const char *what, bool bounded, bool path, nvk_ctx *ctx, int64_t n_reads, int64_t total_query,
                        const int32_t *query, const int64_t *q_off, const int32_t *reference, int64_t ref_len,
-                       const int32_t *strand, const int32_t *diag, const int32_t *ref_lo, const int32_t *ref_hi,
-                       int band, int match, int mismatch, int gap_open, int gap_extend, int min_score,
-                       int32_t *out_hit, int32_t *out_pairs) {
+                       const int32_t *strand, const int32_t *diag, int64_t total_strips, const int64_t *strip_off,
+                       const int32_t *strip_diag, const int32_t *ref_lo, const int32_t *ref_hi, int band, int match,
+                       int mismatch, int gap_open, int gap_extend, int min_score, int32_t *out_hit,
+                       int32_t *out_pairs) {
   if (!ctx) {
     nvk_set_error("%s: ctx is NULL", what);
     return NVK_ERR_INVALID;
@@ -264,8 +318,24 @@ static int seed_extend(const char *what, bool bounded, nvk_ctx *ctx, int64_t n_r
                     SEED_MAX_READ);
       return NVK_ERR_INVALID;
     }
+  if (path) {
+    if (total_strips < 0 || !strip_off || (total_strips > 0 && !strip_diag)) {
+      nvk_set_error("%s: total_strips %lld out of range, or NULL strip offsets or centres", what,
+                    (long long)total_strips);
+      return NVK_ERR_INVALID;
+    }
+    std::vector<int64_t> toff;
+    if ((rc = nvk_fetch_offsets(ctx, "strip", strip_off, n_reads, toff, "total_strips", total_strips))) return rc;
+    for (int64_t r = 0; r < n_reads; r++)
+      if (toff[r + 1] - toff[r] != (off[r + 1] - off[r] + 63) / 64) {
+        nvk_set_error("%s: read %lld of %lld bases has %lld strips, not %lld", what, (long long)r,
+                      (long long)(off[r + 1] - off[r]), (long long)(toff[r + 1] - toff[r]),
+                      (long long)((off[r + 1] - off[r] + 63) / 64));
+        return NVK_ERR_INVALID;
+      }
+  }
   if (n_reads == 0) return NVK_OK;
-  if (!strand || !diag || !out_hit || (total_query > 0 && !out_pairs)) {
+  if (!strand || (!path && !diag) || !out_hit || (total_query > 0 && !out_pairs)) {
     nvk_set_error("%s: NULL strand, diagonal or output", what);
     return NVK_ERR_INVALID;
   }
@@ -323,6 +393,8 @@ static int seed_extend(const char *what, bool bounded, nvk_ctx *ctx, int64_t n_r
   a.diag = diag;
   a.ref_lo = bounded ? ref_lo : nullptr;
   a.ref_hi = bounded ? ref_hi : nullptr;
+  a.strip_diag = path ? strip_diag : nullptr;
+  a.strip_off = path ? strip_off : nullptr;
   a.w = band;
   a.match = match;
   a.mismatch = mismatch;
@@ -342,10 +414,14 @@ static int seed_extend(const char *what, bool bounded, nvk_ctx *ctx, int64_t n_r
       const int64_t want = a.r1 - a.r0, resident = (int64_t)(ctx->num_cus > 0 ? ctx->num_cus : 256) * 16;
       NVK_HIP(hipMemsetAsync(d_counter, 0, sizeof(int), ctx->stream));
       const dim3 grid((unsigned)(want < resident ? want : resident));
-      if (bounded)
-        hipLaunchKernelGGL(seedext_kernel<true>, grid, dim3(64), 0, ctx->stream, a);
+      if (path && bounded)
+        hipLaunchKernelGGL((seedext_kernel<true, true>), grid, dim3(64), 0, ctx->stream, a);
+      else if (path)
+        hipLaunchKernelGGL((seedext_kernel<false, true>), grid, dim3(64), 0, ctx->stream, a);
+      else if (bounded)
+        hipLaunchKernelGGL((seedext_kernel<true, false>), grid, dim3(64), 0, ctx->stream, a);
       else
-        hipLaunchKernelGGL(seedext_kernel<false>, grid, dim3(64), 0, ctx->stream, a);
+        hipLaunchKernelGGL((seedext_kernel<false, false>), grid, dim3(64), 0, ctx->stream, a);
       NVK_HIP(hipGetLastError());
     }
   }
@@ -358,9 +434,9 @@ extern "C" int nvk_seed_extend_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_
                                    const int32_t *strand, const int32_t *diag, int band, int match, int mismatch,
                                    int gap_open, int gap_extend, int min_score, int32_t *out_hit,
                                    int32_t *out_pairs) {
-  return seed_extend("nvk_seed_extend_dev", false, ctx, n_reads, total_query, query, q_off, reference, ref_len, strand,
-                     diag, nullptr, nullptr, band, match, mismatch, gap_open, gap_extend, min_score, out_hit,
-                     out_pairs);
+  return seed_extend("nvk_seed_extend_dev", false, false, ctx, n_reads, total_query, query, q_off, reference, ref_len,
+                     strand, diag, 0, nullptr, nullptr, nullptr, nullptr, band, match, mismatch, gap_open, gap_extend,
+                     min_score, out_hit, out_pairs);
 }
 
 extern "C" int nvk_seed_extend_bounded_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_query, const int32_t *query,
@@ -368,7 +444,22 @@ extern "C" int nvk_seed_extend_bounded_dev(nvk_ctx *ctx, int64_t n_reads, int64_
                                            const int32_t *strand, const int32_t *diag, const int32_t *ref_lo,
                                            const int32_t *ref_hi, int band, int match, int mismatch, int gap_open,
                                            int gap_extend, int min_score, int32_t *out_hit, int32_t *out_pairs) {
-  return seed_extend("nvk_seed_extend_bounded_dev", true, ctx, n_reads, total_query, query, q_off, reference, ref_len,
-                     strand, diag, ref_lo, ref_hi, band, match, mismatch, gap_open, gap_extend, min_score, out_hit,
-                     out_pairs);
+  return seed_extend("nvk_seed_extend_bounded_dev", true, false, ctx, n_reads, total_query, query, q_off, reference,
+                     ref_len, strand, diag, 0, nullptr, nullptr, ref_lo, ref_hi, band, match, mismatch, gap_open,
+                     gap_extend, min_score, out_hit, out_pairs);
+}
+
+extern "C" int nvk_seed_extend_path_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_query, const int32_t *query,
+                                        const int64_t *q_off, const int32_t *reference, int64_t ref_len,
+                                        const int32_t *strand, int64_t total_strips, const int64_t *strip_off,
+                                        const int32_t *strip_diag, const int32_t *ref_lo, const int32_t *ref_hi,
+                                        int band, int match, int mismatch, int gap_open, int gap_extend,
+                                        int min_score, int32_t *out_hit, int32_t *out_pairs) {
+  if ((ref_lo == nullptr) != (ref_hi == nullptr)) {
+    nvk_set_error("nvk_seed_extend_path_dev: ref_lo and ref_hi go together, both NULL or neither");
+    return NVK_ERR_INVALID;
+  }
+  return seed_extend("nvk_seed_extend_path_dev", ref_lo != nullptr, true, ctx, n_reads, total_query, query, q_off,
+                     reference, ref_len, strand, nullptr, total_strips, strip_off, strip_diag, ref_lo, ref_hi, band,
+                     match, mismatch, gap_open, gap_extend, min_score, out_hit, out_pairs);
 }

@@ -440,6 +440,83 @@ def seed_extend_dev(context, query, q_off, reference, strand, diagonal, band, ma
     return hit[:, 0], hit[:, 1:3], hit[:, 3], pairs[:total]
 
 
+def seed_chain_dev(context, q_off, strand, seed_off, seed_i, seed_p, strip_off, strip_diag, k, band, max_gap,
+                   lookback=64):
+    """The chaining stage of the seed aligner for every read of a batch, on the device (include/nadavca_hip.h:
+    nvk_seed_chain_dev): read j's seeds ``seed_i`` / ``seed_p`` [seed_off[j], seed_off[j+1]), on its strand and sorted
+    by (p, i), are chained, and the chain's anchors give the band centre of each strip of 64 read rows.
+    ``strip_off`` (int64, the running sum of ceil(m_j / 64)) and ``strip_diag`` (int32, one centre per strip) are
+    device tensors; ``strip_diag`` is WRITTEN IN PLACE for the reads that have a chain and left alone for the others
+    (no strand, no seeds), so it comes in filled with the centres those are to keep.
+    -> (chain score i32 (n,), anchors i32 (n,))."""
+    import torch
+    lib = _lib.load()
+    dev = q_off.device
+    n = int(q_off.numel()) - 1
+    if strip_diag.dtype != torch.int32 or not strip_diag.is_contiguous() or strip_diag.device != dev:
+        raise ValueError('seed_chain_dev: strip_diag is written in place: a contiguous int32 tensor on the device')
+    i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
+    i64 = lambda t: t.to(device=dev, dtype=torch.int64).contiguous()
+    q_off, seed_off, strip_off = i64(q_off), i64(seed_off), i64(strip_off)
+    strand, seed_i, seed_p = i32(strand), i32(seed_i), i32(seed_p)
+    n_seeds, n_strips = int(seed_i.numel()), int(strip_diag.numel())
+    if int(seed_p.numel()) != n_seeds or int(seed_off.numel()) != n + 1 or int(strip_off.numel()) != n + 1 or \
+            int(strand.numel()) != n:
+        raise ValueError('seed_chain_dev: one strand per read, n + 1 offsets each, as many seed_p as seed_i')
+    total = int(q_off[-1]) if n >= 0 else 0
+    # (a placeholder element where an array is empty: the C-ABI takes no NULL for a batch that has reads)
+    one = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = torch.zeros((max(n, 0), 2), dtype=torch.int32, device=dev)
+    _lib.check(lib.nvk_seed_chain_dev(context.handle, n, total, _dp(q_off), _dp(strand if n else one), n_seeds,
+                                      _dp(seed_off), _dp(seed_i if n_seeds else one), _dp(seed_p if n_seeds else one),
+                                      int(k), int(band), int(max_gap), int(lookback), n_strips, _dp(strip_off),
+                                      _dp(strip_diag if n_strips else one), _dp(out if n else one)),
+               'nvk_seed_chain_dev')
+    return out[:, 0], out[:, 1]
+
+
+def seed_extend_path_dev(context, query, q_off, reference, strand, strip_off, strip_diag, band, match, mismatch,
+                         gap_open, gap_extend, min_score, ref_lo=None, ref_hi=None):
+    """``seed_extend_dev`` with a band that follows a path (include/nadavca_hip.h: nvk_seed_extend_path_dev): row i of
+    read j is centred on ``strip_diag[strip_off[j] + i // 64]`` (``strip_off`` int64, the running sum of
+    ceil(m_j / 64); ``strip_diag`` int32) instead of one diagonal per read.  ``ref_lo`` / ``ref_hi`` and what is
+    returned as there."""
+    import torch
+    lib = _lib.load()
+    dev = query.device
+    n = int(q_off.numel()) - 1
+    total = int(query.numel())
+    G = int(reference.numel())
+    i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
+    query, reference, strand, strip_diag = i32(query), i32(reference), i32(strand), i32(strip_diag)
+    q_off = q_off.to(device=dev, dtype=torch.int64).contiguous()
+    strip_off = strip_off.to(device=dev, dtype=torch.int64).contiguous()
+    n_strips = int(strip_diag.numel())
+    if int(strip_off.numel()) != n + 1:
+        raise ValueError('seed_extend_path_dev: strip_off holds n + 1 offsets')
+    one = torch.zeros(1, dtype=torch.int32, device=dev)
+    if total == 0:
+        query = one
+    if G == 0:
+        reference = one
+    if n_strips == 0:
+        strip_diag = one
+    if (ref_lo is None) != (ref_hi is None) or (ref_lo is not None and (int(ref_lo.numel()) != n or
+                                                                        int(ref_hi.numel()) != n)):
+        raise ValueError('seed_extend_path_dev: ref_lo and ref_hi go together, one value per read each')
+    lo = hi = C.c_void_p(0)
+    if ref_lo is not None:
+        ref_lo, ref_hi = (i32(ref_lo), i32(ref_hi)) if n else (one, one)
+        lo, hi = _dp(ref_lo), _dp(ref_hi)
+    hit = torch.zeros((max(n, 0), 4), dtype=torch.int32, device=dev)
+    pairs = torch.empty((max(total, 1), 2), dtype=torch.int32, device=dev)
+    _lib.check(lib.nvk_seed_extend_path_dev(context.handle, n, total, _dp(query), _dp(q_off), _dp(reference), G,
+                                            _dp(strand), n_strips, _dp(strip_off), _dp(strip_diag), lo, hi, int(band),
+                                            int(match), int(mismatch), int(gap_open), int(gap_extend), int(min_score),
+                                            _dp(hit), _dp(pairs)), 'nvk_seed_extend_path_dev')
+    return hit[:, 0], hit[:, 1:3], hit[:, 3], pairs[:total]
+
+
 # ---- Chunk score accumulation and posterior, device-resident (estimator.py:199-236) ---------------------
 def consensus_accumulate_dev(context, dbatch, ll, chunk_start, reverse, status, normalization_event_length,
                              ref_len, acc=None, cov=None):

@@ -21,7 +21,18 @@ only aligned columns whose two bases are equal (alignment.py:118-138, ``alignmen
 2. Banded affine-gap local alignment around d* and 3. traceback, in the HIP kernel ``nvk_seed_extend_dev``
    (include/nadavca_hip.h states the rules; nadavca_amd/csrc/kernels_seedext.hip; with a ReferenceSet
    ``nvk_seed_extend_bounded_dev``, the same kernel held to the read's contig).  A read whose score is below
-   ``min_score`` is unaligned.  There is no CPU form of steps 2 and 3 in the package."""
+   ``min_score`` is unaligned.  There is no CPU form of steps 2 and 3 in the package.
+
+``chain=1`` (off by default) lets the band follow the read instead of standing on d*: a read whose insertions and
+deletions do not cancel drifts off any one diagonal by about (deletion rate - insertion rate) x its length, and a
+fixed band keeps only the piece that fits.  Between steps 1 and 2 the seeds of the voted strand (``strand_seeds``;
+over a ReferenceSet those inside the read's contig), sorted by (p, i) (``sort_seeds``), are chained by the HIP kernel
+``nvk_seed_chain_dev`` (kernels_seedchain.hip): f[t] = max(k, max_u f[u] + min(di, dp, k) - |dp - di|) over the 64
+seeds before t with 0 < di, dp <= ``max_gap`` and |dp - di| <= band; the best chain's anchors give every strip of 64
+read rows its own centre, p - i of the anchor nearest the strip's middle.  Steps 2 and 3 then run in
+``nvk_seed_extend_path_dev``, the same kernel body with the centre taken per strip.  Strand, vote, contig and
+``min_score`` keep their rules; a read without a chain keeps d* in every strip.  include/nadavca_hip.h states both
+contracts."""
 import numpy as np
 
 from . import _lib
@@ -29,7 +40,8 @@ from .batchflow import seg_index
 from .readbatch import BaseAlignmentBatch
 from .refset import ReferenceSet
 
-PARAMS = dict(k=14, max_occ=32, band=64, min_seeds=2, match=1, mismatch=1, gap_open=1, gap_extend=1, min_score=30)
+PARAMS = dict(k=14, max_occ=32, band=64, min_seeds=2, match=1, mismatch=1, gap_open=1, gap_extend=1, min_score=30,
+              chain=0, max_gap=500)
 
 
 def _check_params(p):
@@ -39,7 +51,8 @@ def _check_params(p):
     q = dict(PARAMS)
     q.update(p)
     ranges = dict(k=(8, 15), max_occ=(1, None), band=(1, 256), min_seeds=(1, None), match=(1, 16),
-                  mismatch=(1, 16), gap_open=(1, 16), gap_extend=(1, 16), min_score=(1, None))
+                  mismatch=(1, 16), gap_open=(1, 16), gap_extend=(1, 16), min_score=(1, None), chain=(0, 1),
+                  max_gap=(1, 1 << 26))
     for name, (lo, hi) in ranges.items():
         v = q[name]
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
@@ -69,11 +82,18 @@ class SeedHits:
     reference's end on strand 1.  ``contig`` (int32): 0 for an aligned read, -1 for an unaligned one.
     From an aligner over a ReferenceSet (``reference_set``, else None): ``contig`` is the read's contig, ``ref_idx``
     is contig-local — the strand coordinate less the contig's first one, i.e. counted from the contig's end on strand
-    1 — while ``diagonal`` and ``end`` stay in the concatenation's strand coordinates."""
+    1 — while ``diagonal`` and ``end`` stay in the concatenation's strand coordinates.
+    From an aligner with ``chain=1`` (else all four are None): ``chain_score`` and ``chain_anchors`` (int32: the score
+    of the read's seed chain and the number of seeds on it, 0 where there is none), ``strip_off`` (int64 (n + 1,)) and
+    ``strip_diagonal`` (int32): the band centre of rows 64 s .. 64 s + 63 of read j is
+    ``strip_diagonal[strip_off[j] + s]``, in the coordinates of ``diagonal``, and equals ``diagonal[j]`` for a read
+    without a chain."""
 
     def __init__(self, strand, diagonal, votes, score, end, aligned, off, read_idx, ref_idx, contig=None,
-                 reference_set=None):
+                 reference_set=None, chain_score=None, chain_anchors=None, strip_off=None, strip_diagonal=None):
         self.strand, self.diagonal, self.votes, self.score, self.end = strand, diagonal, votes, score, end
+        self.chain_score, self.chain_anchors = chain_score, chain_anchors
+        self.strip_off, self.strip_diagonal = strip_off, strip_diagonal
         self.aligned, self.off, self.read_idx, self.ref_idx = aligned, off, read_idx, ref_idx
         self.reverse = aligned & (strand == 1)
         self.contig = np.where(aligned, 0, -1).astype(np.int32) if contig is None else contig
@@ -94,7 +114,9 @@ class SeedAligner:
     else None, and ``reference_num`` its concatenation; a FASTA file of several records goes in as
     ``ReferenceSet.from_fasta(path)``); ``params`` as in ``PARAMS`` (``k`` 8..15, ``max_occ`` >= 1, ``band`` (the
     half-width w, in diagonals) 1..256, ``min_seeds`` >= 1, ``match`` / ``mismatch`` / ``gap_open`` / ``gap_extend``
-    1..16 (a gap of length l costs gap_open + l * gap_extend), ``min_score`` >= 1); out of range raises ValueError.
+    1..16 (a gap of length l costs gap_open + l * gap_extend), ``min_score`` >= 1, ``chain`` 0 or 1 (1: the band
+    follows the read's seed chain, see the module's text) and ``max_gap`` >= 1 (the chain's largest step between two
+    seeds, in read and in reference bases)); out of range raises ValueError.
     ``device``: where the reference, its k-mer index and the seeding live (default: the library's default GPU).  The
     index of both strands is built once, here.  ``align`` and ``get_base_alignments`` need a GPU device; ``seed``
     (step 1 alone) runs on any."""
@@ -156,6 +178,38 @@ class SeedAligner:
     def seed(self, read_batch):
         """Step 1 for every read of ``read_batch``, on the aligner's device: -> (strand int32, diagonal int64,
         votes int64), torch tensors of n reads; strand -1 (diagonal 0) where the read did not reach ``min_seeds``."""
+        return self._seed(read_batch)[:3]
+
+    def strand_seeds(self, read_batch):
+        """Step 1 and the seeds it voted with: -> (strand, diagonal, votes, seed_read, seed_i, seed_p): the first
+        three as ``seed`` returns them, then every seed (i, p) of each read on the strand its vote chose (all of them,
+        not only the winning window's), int64 tensors in no particular order; a read without a strand has none.  From
+        an aligner over a ReferenceSet only the seeds inside the read's contig (``contig_of``):
+        ref_lo <= p < ref_hi."""
+        import torch
+        strand, diagonal, votes, seeds = self._seed(read_batch)
+        voted = [strand[x[0]] == s for s, x in enumerate(seeds)]
+        rd, si, sp = (torch.cat([x[f][v] for x, v in zip(seeds, voted)]) for f in (0, 3, 4))
+        if self.reference_set is not None:
+            _, ref_lo, ref_hi = self.contig_of(read_batch, strand, diagonal)
+            keep = (sp >= ref_lo[rd]) & (sp < ref_hi[rd])
+            rd, si, sp = rd[keep], si[keep], sp[keep]
+        return strand, diagonal, votes, rd, si, sp
+
+    @staticmethod
+    def sort_seeds(n, seed_read, seed_i, seed_p):
+        """The seeds of ``strand_seeds`` in the order the chaining takes them: by read, then p, then i.
+        -> (seed_off int64 (n + 1,), seed_i int32, seed_p int32)."""
+        import torch
+        span = int(seed_i.max()) + 1 if seed_i.numel() else 1
+        order = torch.sort(seed_p * span + seed_i).indices       # p < 2^30, i < 2^26
+        order = order[torch.sort(seed_read[order], stable=True).indices]
+        off = torch.zeros(n + 1, dtype=torch.int64, device=seed_read.device)
+        torch.cumsum(torch.bincount(seed_read, minlength=n)[:n], 0, out=off[1:])
+        return off, seed_i[order].to(torch.int32), seed_p[order].to(torch.int32)
+
+    def _seed(self, read_batch):
+        """-> ``seed``'s three, and per strand the seeds (read, diagonal, window, i, p)."""
         import torch
         self._check_reads(read_batch)
         p = self.params
@@ -187,11 +241,12 @@ class SeedAligner:
             if n_seeds == 0:
                 votes.append(best)
                 cstar.append(best_c)
-                seeds.append((torch.zeros(0, dtype=i64, device=dev),) * 3)
+                seeds.append((torch.zeros(0, dtype=i64, device=dev),) * 5)
                 continue
             sk = torch.repeat_interleave(torch.arange(t.numel(), dtype=i64, device=dev), cnt, output_size=n_seeds)
             within = torch.arange(n_seeds, dtype=i64, device=dev) - (torch.cumsum(cnt, 0) - cnt)[sk]
-            rd, d = owner[t][sk], pos[lo[sk] + within] - inner[t][sk]
+            rd, si, sp = owner[t][sk], inner[t][sk], pos[lo[sk] + within]
+            d = sp - si
             c = torch.div(d, w, rounding_mode='floor')
             uk, un = torch.unique(rd * CR + c + C0, return_counts=True)
             cand = torch.unique(torch.cat([uk, uk - 1]))
@@ -208,7 +263,7 @@ class SeedAligner:
             best_c = torch.where(best > 0, first - torch.arange(n, dtype=i64, device=dev) * CR - C0, best_c)
             votes.append(best)
             cstar.append(best_c)
-            seeds.append((rd, d, c))
+            seeds.append((rd, d, c, si, sp))
         rev = votes[1] > votes[0]
         n_votes = torch.where(rev, votes[1], votes[0])
         c_win = torch.where(rev, cstar[1], cstar[0])
@@ -218,7 +273,7 @@ class SeedAligner:
         D0 = max_m + 1
         DR = D0 + G + 1
         sel_r, sel_d = [], []
-        for s, (rd, d, c) in enumerate(seeds):
+        for s, (rd, d, c, _, _) in enumerate(seeds):
             if rd.numel() == 0:
                 continue
             keep = (strand[rd] == s) & ((c == c_win[rd]) | (c == c_win[rd] + 1))
@@ -233,7 +288,7 @@ class SeedAligner:
             mid = (start + torch.div(per - 1, 2, rounding_mode='floor')).clamp(min=0, max=key.numel() - 1)
             med = key[mid] - torch.arange(n, dtype=i64, device=dev) * DR - D0
             diagonal = torch.where(aligned, med, diagonal)
-        return strand, diagonal, n_votes
+        return strand, diagonal, n_votes, seeds
 
     def contig_of(self, read_batch, strand, diagonal):
         """The contig rule of step 1 for a ReferenceSet aligner, on the aligner's device: ``strand`` / ``diagonal`` as
@@ -267,16 +322,36 @@ class SeedAligner:
             raise _lib.NadavcaHipError('SeedAligner.align: the extension stage runs only in the HIP kernel; this '
                                        'aligner was built on %s' % self.device)
         p, dev, i64 = self.params, self.device, torch.int64
-        strand, diagonal, votes = self.seed(read_batch)
+        ctx = _lib.default_context(dev.index or 0)
         n = read_batch.n
         q_off = torch.from_numpy(read_batch.seq_off).to(dev)
         query = torch.from_numpy(read_batch.sequence).to(dev)
+        chain = {}
+        if p['chain']:
+            strand, diagonal, votes, seed_read, seed_i, seed_p = self.strand_seeds(read_batch)
+        else:
+            strand, diagonal, votes = self.seed(read_batch)
         contig = ref_lo = ref_hi = None
         if self.reference_set is not None:
             contig, ref_lo, ref_hi = self.contig_of(read_batch, strand, diagonal)
-        score, end, count, pairs = seed_extend_dev(_lib.default_context(dev.index or 0), query, q_off, self._ref,
-                                                   strand, diagonal, p['band'], p['match'], p['mismatch'],
-                                                   p['gap_open'], p['gap_extend'], p['min_score'], ref_lo, ref_hi)
+        scoring = (p['band'], p['match'], p['mismatch'], p['gap_open'], p['gap_extend'], p['min_score'])
+        if p['chain']:
+            from .device import seed_chain_dev, seed_extend_path_dev
+            seed_off, seed_i, seed_p = self.sort_seeds(n, seed_read, seed_i, seed_p)
+            strips = torch.div(q_off[1:] - q_off[:-1] + 63, 64, rounding_mode='floor')
+            strip_off = torch.zeros(n + 1, dtype=i64, device=dev)
+            torch.cumsum(strips, 0, out=strip_off[1:])
+            # every strip starts at the voted d*: what a read keeps whose seeds give no chain
+            strip_diag = torch.repeat_interleave(diagonal.to(torch.int32), strips).contiguous()
+            chain_score, anchors = seed_chain_dev(ctx, q_off, strand, seed_off, seed_i, seed_p, strip_off, strip_diag,
+                                                  p['k'], p['band'], p['max_gap'])
+            score, end, count, pairs = seed_extend_path_dev(ctx, query, q_off, self._ref, strand, strip_off,
+                                                            strip_diag, *scoring, ref_lo, ref_hi)
+            chain = dict(chain_score=chain_score.cpu().numpy(), chain_anchors=anchors.cpu().numpy(),
+                         strip_off=strip_off.cpu().numpy(), strip_diagonal=strip_diag.cpu().numpy())
+        else:
+            score, end, count, pairs = seed_extend_dev(ctx, query, q_off, self._ref, strand, diagonal, *scoring,
+                                                       ref_lo, ref_hi)
         count = count.to(i64)
         off = torch.zeros(n + 1, dtype=i64, device=dev)
         torch.cumsum(count, 0, out=off[1:])
@@ -289,7 +364,7 @@ class SeedAligner:
             ref_idx = ref_idx - ref_lo.to(i64)[owner]
             contig = h(torch.where(aligned, contig, torch.full_like(contig, -1)))
         return SeedHits(h(strand), h(diagonal), h(votes), h(score), h(end), h(aligned), h(off), h(got[:, 0]),
-                        h(ref_idx), contig, self.reference_set)
+                        h(ref_idx), contig, self.reference_set, **chain)
 
     def get_base_alignments(self, read_batch):
         """The aligner contract of the batch workflows: -> BaseAlignmentBatch."""
