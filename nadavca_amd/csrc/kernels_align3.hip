@@ -27,7 +27,12 @@
 //   or are handed to the next row, so scores are (double, integer scale) pairs: the running maximum
 //   is kept normalised (mantissa in [0.5,1), scale G), an incoming score is shifted onto that scale
 //   before the comparison, and G travels with the score — which is all the tie tolerance of
-//   xm::gt_tol needs.
+//   xm::gt_tol needs.  The comparison itself is path_step.h: the margin of gt_tol, best * |G| * 2^-52, is a function
+//   of the maximum and is formed only in the block the wave enters when some lane's pair lies inside the 2^-24 tie
+//   margin; everywhere else "greater by more than the margin" and "greater" are the same bit as long as |G| < 2^27
+//   (the lemma in that header).  A row moves |G| by at most 1024, so reads of up to 2^17 rows are below that bound
+//   whatever their data; longer ones go to the exact kernel, and so does, as one more range guard, a read in which
+//   a lane leaves a row with |G| >= 2^26.  The last row's arg-max is treated the same way.
 //
 // Memory: spill 8 B per cell (+4 B of scale per RS steps) instead of 12 B per cell; no row table in LDS
 // (lane3_kernel prepares per-sweep lane records, a lane fetches the record of its next row through the scalar
@@ -58,7 +63,9 @@
 // the step's position in the period (a period of 32 steps: on the trip's parity); the two rare cases "first
 // row" / "last row" behind one scalar test; the signal ring's refill loaded one chunk ahead; no density
 // re-evaluation at a row switch (the planner keeps the lane idle for the steps on which stale densities
-// pass).  Tried and not kept (DESIGN.md 5.1 has the measurements): 32 forward steps per trip (128 registers),
+// pass); no tie margin carried from update to update (five vector instructions of every step, three of them at the
+// FP64 rate, and two registers: path_step.h) and no copy of the score's scale for the rare first-row case (row 0's
+// lane keeps G = 0 by itself).  Tried and not kept (DESIGN.md 5.1 has the measurements): 32 forward steps per trip (128 registers),
 // the sample of the next density read one step earlier, update bits shifted in with v_addc, the history-ring
 // read pipelined one step ahead with age-1 values by DPP, lane records prefetched into L2, 5 waves per SIMD in
 // the forward sweep.
@@ -71,6 +78,7 @@
 #include "xmath.h"
 #include "dens.h"
 #include "lane3.h"
+#include "path_step.h"
 #include "wave.h"
 
 namespace {
@@ -92,7 +100,7 @@ static_assert(FT % PF == 0 && 32 % FT == 0, "forward trip");
 static_assert(32 % PF == 0 && PF % 2 == 0 && 32 % RU == 0 && RU % 2 == 0, "the step count is a multiple of 32 (kernels_plan.hip)");
 // rescale period: 2^RSH steps (template parameter RSH, 8, 16 or 32); must exceed c + mel so that at most one
 // rescale lies inside the window a neighbour value travels through
-constexpr int GBIG = 1 << 24;  // scale of an empty running maximum (see the path step)
+using path_step::GBIG;  // scale of an empty running maximum (see the path step)
 // Largest upward move per rescale.  When the wave's largest value collapses by more than this within one
 // period (only off-path cells live, or a sharp model on a noisy signal) the running scale cannot follow
 // without sending the next densities' exponents out of range; the move is capped (no inf / NaN is ever
@@ -105,7 +113,8 @@ constexpr int DMAX = 1000;  // the density exponent (<= ~3) plus the move must s
 constexpr int TARGET = 250; // exponent the largest live value is moved to
 #define HUGE_V 0x1.0p+900
 #define MASS_TOL 1e-9          // allowed relative spread of the rows' posterior mass
-#define TIE_FLAG_REL (1.0 / (double)(1ull << NVK_TIE_BITS))  // relative margin of the tie flag (xmath.h: near_tol)
+static_assert(path_step::TIE_BITS == NVK_TIE_BITS && path_step::TIE_ULPS == NVK_TIE_ULPS, "path_step.h restates xmath.h's tie margins");
+static_assert(path_step::TIE_EXACT == NVK_TIE_EXACT && path_step::TIE_NEAR == NVK_TIE_NEAR && path_step::TIE_ULP == NVK_TIE_ULP, "path_step.h restates the tie classes");
 
 // The spill is addressed through a buffer resource: address = resource base (scalar) + scalar byte
 // offset of the step + per-lane byte offset (a constant vector register), so neither the store of the
@@ -624,7 +633,7 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
     if (PHASE == 2) {
       const int2 rs = g.rstate[rd];
       K = __builtin_amdgcn_readfirstlane(rs.x);
-      suspect = (rs.y != 0);
+      suspect = (rs.y != 0) || (T > path_step::PATH_ROWS_PROVEN);  // (path_step.h, the bound)
     }
     __syncthreads();  // (also drains the stores)
     __builtin_amdgcn_s_dcache_inv();
@@ -632,7 +641,7 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
     // ================= forward sweep: prefix rows, posterior, path DP, update bits =================
     // arg-max of the last row: best score, its margin, its scale, its cell (in registers: kept in LDS, read
     // and written by the last row's lane only, it cost 4 % — one more LDS round trip on that row's steps)
-    double fbest = 0.0, fthr = 0.0;
+    double fbest = 0.0;
     int fidx = -1, fG = 0;
     // (scalar) lanes that saw a comparison inside the tie margin, by class (include/nadavca_hip.h): the two scores
     // exactly equal (amb_x), different but within NVK_TIE_ULPS margins of xm::gt_tol — ulps of the reference's
@@ -664,9 +673,12 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
       }
       double prev = 0.0, e1 = 1.0, e2 = 1.0, e3 = 1.0;
       // path DP state of the row: running maximum of the previous row's scores (raw, as received,
-      // and normalised by 2^rho), its tolerance margin, the row's accumulated exponent G
-      double bestn = 0.0, bthr = 0.0;
-      int G = GBIG;  // scale of bestn, and so of this row's scores
+      // and normalised by 2^rho), the row's accumulated exponent G (the tolerance margin is a function of the
+      // two, formed only where a tie is near: path_step.h)
+      double bestn = 0.0;
+      // scale of bestn, and so of this row's scores.  Row 0 starts the scores at scale 0: its lane reads the zero entry
+      // on every step (Lane3::pA), so nothing ever updates its maximum and G stays the 0 it hands on.
+      int G = is_init ? 0 : GBIG;
       // Flush detector.  In a banded forward-backward pass every allowed path crosses every row
       // exactly once, so sum_i prefix[r][i] * suffix[r][i] is the SAME total for every row r.
       // Cells far below the wave's scale flush to zero here; if that ever removes mass that
@@ -750,7 +762,8 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
                   r = rn;
                   i -= nx.mg >> 12;
                   prev = 0.0;
-                  bestn = 0.0; bthr = 0.0; G = GBIG;
+                  suspect |= (abs(G) >= path_step::PATH_G_GUARD);  // path_step.h: the margin-free comparison's bound
+                  bestn = 0.0; G = GBIG;
                   if (r < T) {
                     TAKE_LANE(nx);
                     be = nx.end; lo = nx.lo;
@@ -838,9 +851,11 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
             // Scores are (double, integer scale): stored = true * 2^scale.  The running maximum is kept
             // normalised (bestn in [0.5,1), scale G); an incoming score is brought onto that scale
             // before comparing (far below -> 0, far above -> inf, both compare correctly).
+            // The margin is formed only where some lane's pair is inside the tie margin: everywhere else
+            // tdiff > margin and tdiff > 0 are the same bit (path_step.h has the lemma and its bound on G).
             const double dva = ldexp(dv, G - Gin);  // no maximum yet: G = GBIG, any dv > 0 becomes +inf
             const double tdiff = dva - bestn;
-            const bool upd = (tdiff > bthr);  // (dv == 0 outside the span: never an update)
+            bool upd = (tdiff > 0.0);  // (dv == 0 outside the span: never an update)
             // The tie flag (include/nadavca_hip.h, parity contract): the two scores are closer than 2^-24
             // relative — far more than the rounding either this engine or the reference accumulates, so a
             // read without the flag has the reference's decisions everywhere.  (A candidate of 0, or the
@@ -848,58 +863,63 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
             // the path would tie by their lost precision: this file is compiled with FP64 denormals
             // flushed, which makes them exact zeros.)
             {
-              const unsigned long long nr = __builtin_amdgcn_ballot_w64(fabs(tdiff) < dva * TIE_FLAG_REL);
-              if (nr != 0) {  // (rare, a scalar branch: the classes are sorted out off the usual path)
+              const unsigned long long nr = __builtin_amdgcn_ballot_w64(path_step::path_near(tdiff, dva));
+              if (nr != 0) {  // (rare, a scalar branch: the margin and the classes are sorted out off the usual path)
                 asm volatile("");
-                const unsigned long long zr = __builtin_amdgcn_ballot_w64(tdiff == 0.0);
-                const unsigned long long ur = __builtin_amdgcn_ballot_w64(fabs(tdiff) <= bthr * (double)NVK_TIE_ULPS);
+                const double bthr = path_step::path_margin(bestn, G);
+                // (through a ballot: as a second compare of tdiff the compiler merges it with the usual path's and
+                // carries the margin, a zero there, in two registers again)
+                upd = ((__builtin_amdgcn_ballot_w64(tdiff > bthr) >> lane) & 1) != 0;
+                const unsigned long long zr = __builtin_amdgcn_ballot_w64(path_step::path_tie_exact(tdiff));
+                const unsigned long long ur = __builtin_amdgcn_ballot_w64(path_step::path_tie_ulp(tdiff, bthr));
                 amb_x |= nr & zr;
                 amb_u |= nr & ur & ~zr;
                 amb_n |= nr & ~ur & ~zr;
               }
             }
             if (upd) {
-              bestn = __builtin_amdgcn_frexp_mant(dv);         // in [0.5, 1)
-              G = Gin - __builtin_amdgcn_frexp_exp(dv);        // its scale; -G = true exponent
-              bthr = bestn * ((double)abs(G) * 0x1.0p-52);
+              asm volatile("");  // (keeps the three instructions under the lane mask: as selects they are six)
+              path_step::path_take(dv, Gin, bestn, G);  // bestn in [0.5, 1), G its scale; -G = true exponent
             }
             bits = (bits << 1) | (upd ? 1u : 0u);  // step u ends up at bit 31 - (u & 31)
             double dpv = bestn * post;  // post is already 0 outside the band
-            int Gd = G;
             if (init_live | top_live) {  // (one scalar test for the two rare cases: the first and the last row)
               asm volatile("");
               if (init_live) {
                 if (is_init) {
                   o = IN_BAND ? ldexp(1.0, sc.L) : 0.0;
                   post = ldexp(o * suf, kap);
-                  dpv = post; Gd = 0;
+                  dpv = post;  // (on scale G = 0, see above)
                 }
               }
               if (top_live) {
-              const double da = ldexp(dpv, (fbest == 0.0) ? 0 : fG - Gd);
+              const double da = ldexp(dpv, (fbest == 0.0) ? 0 : fG - G);
+              const double fdiff = da - fbest;
+              bool fupd = (fdiff > 0.0);  // (as above: the margin only where a tie is near)
               {
-                const unsigned long long nr = __builtin_amdgcn_ballot_w64(r == top && IN_BAND && fabs(da - fbest) < da * TIE_FLAG_REL);
+                const unsigned long long nr = __builtin_amdgcn_ballot_w64(r == top && IN_BAND && path_step::path_near(fdiff, da));
                 if (nr != 0) {
                   asm volatile("");
-                  const unsigned long long zr = __builtin_amdgcn_ballot_w64(da == fbest);
-                  const unsigned long long ur = __builtin_amdgcn_ballot_w64(fabs(da - fbest) <= fthr * (double)NVK_TIE_ULPS);
+                  const double fthr = path_step::path_top_margin(fbest, fG);
+                  fupd = (fdiff > fthr);
+                  const unsigned long long zr = __builtin_amdgcn_ballot_w64(path_step::path_tie_exact(fdiff));
+                  const unsigned long long ur = __builtin_amdgcn_ballot_w64(path_step::path_tie_ulp(fdiff, fthr));
                   amb_x |= nr & zr;
                   amb_u |= nr & ur & ~zr;
                   amb_n |= nr & ~ur & ~zr;
                 }
               }
-              if (r == top && IN_BAND && (da - fbest > fthr)) {
+              if (r == top && IN_BAND && fupd) {
                 fbest = dpv;
-                fG = Gd;
+                fG = G;
                 fidx = i;
-                fthr = dpv * ((double)abs(__builtin_amdgcn_frexp_exp(dpv) - Gd) * 0x1.0p-52);
               }
               }
             }
             prev = o;
             rsum += post;
             *reinterpret_cast<double2 *>(histb + (su * (16 * TL) + gl16)) = make_double2(o, dpv);
-            *reinterpret_cast<int *>(ghistb + (su * (4 * TL) + (gl16 >> 2))) = Gd;
+            *reinterpret_cast<int *>(ghistb + (su * (4 * TL) + (gl16 >> 2))) = G;
             if ((u & 31) == 31) {
               int w = u >> 5;
               asm volatile("" : "+s"(w));  // keeps the address arithmetic inside the branch
@@ -948,6 +968,7 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
       if (r < T) {  // rows still open when the sweep ends
         smin = fmin(smin, rsum);
         smax = fmax(smax, rsum);
+        suspect |= (abs(G) >= path_step::PATH_G_GUARD);
       }
       for (int dlt = 32; dlt >= 1; dlt >>= 1) {
         smin = fmin(smin, __shfl_xor(smin, dlt, 64));
