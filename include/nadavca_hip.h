@@ -935,6 +935,76 @@ int nvk_site_mixture_tests_dev(nvk_ctx *ctx, int64_t n_rows_a, const int64_t *ke
                                const int64_t *site_key, int iterations, double min_sd_ratio, int64_t *out_counts,
                                double *out_fit);
 
+/* The base -> sample table of a read from its signal and its sequence alone (nadavca_amd/signal_map.py:
+ * signal_map_batch): event detection, then an adaptive-banded alignment of the events to the k-mer levels of the read's
+ * own bases, as nanopolish / f5c eventalign and tombo resquiggle rebuild it.  THE CONTRACT.  The library is built with
+ * -ffp-contract=off: every expression below is a rounded f64 operation in the order written; a sum over a range is an
+ * ascending loop from 0.  The CPU restatements the tests hold the kernels to bit for bit are
+ * tests/host_shims/events_host.cpp and eventalign_host.cpp.
+ *
+ * EVENT DETECTION.  Read j's samples are x = signal[sig_off[j] .. sig_off[j+1]) (n samples, normalised by the caller),
+ * w = window (1..8), fw = (double)w.
+ *   statistic   for w <= i <= n - w, over L = x[i-w .. i) and R = x[i .. i+w):
+ *                 mL = SUM(L) / fw, vL = SUM((x - mL) (x - mL)) / fw, mR and vR alike, d = mR - mL,
+ *                 s(i) = (fw * (d * d)) / ((vL + vR) + var_floor);   s(i) = 0 for every other i
+ *   border      sample i, 0 <= i < n, when i == 0, or s(i) >= threshold and s(i) > s(u) for i - w < u < i and
+ *               s(i) >= s(u) for i < u < i + w (the first of equal values wins).  threshold > 0, var_floor > 0.
+ *   event       from a border to the next border of the read or to the read's end: no event crosses two reads
+ * nvk_event_flags_dev writes out_flags i32[total_signal]: 1 at a border, else 0.  The caller lists the flat positions
+ * of the borders in ascending order (ev_pos i64[n_events]; the per-read counts are a prefix sum over the flags) and
+ * nvk_event_levels_dev writes per event e, with a = ev_pos[e], in the read that owns sample a, and b = the smaller of
+ * ev_pos[e+1] (total_signal for the last event) and that read's end: out_start = a - sig_off[read] (i32), out_len =
+ * b - a (i32), out_level = SUM(signal[a .. b)) / (double)(b - a).  sig_off is copied to the host and checked (starts
+ * at 0, never decreases, ends at total_signal, no read above 2^31 - 1 samples).  NVK_ERR_INVALID for bad arguments,
+ * NVK_ERR_UNSUPPORTED for window > 8.  Device pointers. */
+int nvk_event_flags_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_signal, const double *signal,
+                        const int64_t *sig_off, int window, double threshold, double var_floor, int32_t *out_flags);
+int nvk_event_levels_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_signal, const double *signal,
+                         const int64_t *sig_off, int64_t n_events, const int64_t *ev_pos, int32_t *out_start,
+                         int32_t *out_len, double *out_level);
+
+/* EVENT ALIGNMENT.  Read j has E events with levels e_i = level[ev_off[j] + i] and K bases with, per base,
+ * mu / ac / mc [base_off[j] + b]: the level of the base's k-mer and the constants of its Gaussian, ac = -log(sd sqrt(2
+ * pi)), mc = 1 / (2 sd sd), computed by the caller; l_stay[j] and l_step[j] are the read's transition costs (logs,
+ * computed by the caller); trim_cost and skip_cost are finite and <= 0.  NINF = -infinity.  The kernel only adds,
+ * multiplies and compares.
+ *   cells      (i, b), 0 <= i < E, 0 <= b < K;  em(i, b) = ac[b] - ((e_i - mu[b]) * (e_i - mu[b])) * mc[b]
+ *   step       = (src + l_step) + em, src = S(i-1, b-1) for b > 0, and for b == 0 the free start (double)i * trim_cost
+ *   stay       = (S(i-1, b) + l_stay) + em
+ *   skip       = S(i, b-1) + skip_cost for b > 0, NINF for b == 0 (no emission)
+ *   S(i, b)    the largest of the three, the first of equal ones in the order step, stay, skip; a neighbour outside
+ *              the matrix or outside its band is NINF
+ *   bands      E + K + 1 anti-diagonal bands of `band` cells (64 or 128), H = band / 2.  Band t has a corner (et, kt);
+ *              its cell at offset o, 0 <= o < band, is (et - o, kt + o), so band t holds cells with i + b = t - 2.
+ *              Band 0: (H - 1, -1 - H); band 1 moves down.  Band t >= 2 moves right (kt = k(t-1) + 1) when ll < ur and
+ *              down (et = e(t-1) + 1) otherwise, ll and ur being the values of band t-1 at offsets 0 and band - 1; when
+ *              both are NINF it moves right for odd t.  For this purpose alone a position (i, -1), -1 <= i < E, has
+ *              the value (double)(i + 1) * trim_cost (the trimmed column: it holds the band on the events a free start
+ *              trims and feeds no cell); every other position outside the matrix has NINF.
+ *   end        the cell (i, K-1) inside its band with the largest S(i, K-1) + (double)(E - 1 - i) * trim_cost, the
+ *              smallest i among equal ones; that sum is out_score
+ *   walk back  from the end: a skip leaves the base; a stay goes to (i-1, b); a step goes to (i-1, b-1), or ends the
+ *              walk at b == 0 (first_event = i).  A base's first event is the smallest i of its cells that the walk
+ *              leaves by step or stay; a base the walk only skips through has none (-1).
+ *   status     0 mapped; NVK_MAP_NO_EVENTS: E == 0 or K == 0; NVK_MAP_LOST: no cell of column K-1 lies in a band or
+ *              all of them are NINF, the walk leaves the bands, or more than an eighth of the bases have no event
+ *              (8 * skipped > K: the path no longer follows the signal).  status_in (i32 per read, may be NULL): a read
+ *              with a non-zero entry is not aligned and reports that entry.
+ * out_hit i32[4 n_reads]: per read (status, E, first_event, last_event); out_score f64[n_reads]; out_base_event
+ * i32[total_bases]: per base its first event, counted inside the read, or -1.  A read with non-zero status has -1 in
+ * every base, first_event = last_event = -1 and out_score = NINF.
+ * The traceback store takes band / 4 bytes per band (2 bits per cell, band-major) and one bit per band for its move;
+ * its size is bounded by nvk_ctx_set_workspace_limit's cap: when a batch's store is larger its reads run in parts that
+ * fit (a single read larger than the cap runs on its own); results do not change.  ev_off and base_off are copied to
+ * the host and checked (start at 0, never decrease, end at total_events / total_bases, no read above 2^26 events or
+ * bases).  NVK_ERR_INVALID for bad arguments, NVK_ERR_UNSUPPORTED for a band other than 64 or 128.  Device pointers. */
+enum { NVK_MAP_OK = 0, NVK_MAP_NO_EVENTS = 1, NVK_MAP_LOST = 2 };
+int nvk_event_align_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_events, const double *level,
+                        const int64_t *ev_off, int64_t total_bases, const double *mu, const double *ac,
+                        const double *mc, const int64_t *base_off, const double *l_stay, const double *l_step,
+                        const int32_t *status_in, int band, double trim_cost, double skip_cost, int32_t *out_hit,
+                        double *out_score, int32_t *out_base_event);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,8 @@ READ_BAD_INPUT = -1
 READ_BAD_BAND = -2
 READ_TOO_WIDE = -3
 
+MAP_OK, MAP_NO_EVENTS, MAP_LOST = 0, 1, 2   # NVK_MAP_*: per-read status of signal_map_batch
+
 TIE_EXACT = 1   # nvk_last_tie_flags: some path comparison of the read met two exactly equal scores
 TIE_NEAR = 2    # ... two scores closer than 2^-24 relative (beyond the class below)
 TIE_PLATEAU = 8  # structural mark: two adjacent bases with the same k-mer level (boundary unidentifiable)
@@ -108,6 +110,9 @@ SIGNATURES = {
     'nvk_site_moments_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 5),
     'nvk_site_rank_tests_dev': (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64] + [_vp] * 7),
     'nvk_site_mixture_tests_dev': (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _int, _dbl, _vp, _vp]),
+    'nvk_event_flags_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _int, _dbl, _dbl, _vp]),
+    'nvk_event_levels_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    'nvk_event_align_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _i64] + [_vp] * 7 + [_int, _dbl, _dbl, _vp, _vp, _vp]),
 }
 
 LAUNCH_SWEEP, LAUNCH_EXACT, LAUNCH_ELL = 1, 2, 3   # nvk_launch_rec.op

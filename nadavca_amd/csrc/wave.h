@@ -29,6 +29,14 @@ __device__ __forceinline__ double dpp_ror1(double v) {
   return __hiloint2double(hi, lo);
 }
 
+// value of lane (l + 1) mod 64 (DPP wave_rol:1, GFX9)
+__device__ __forceinline__ double dpp_rol1(double v) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_mov_dpp(lo, 0x134, 0xf, 0xf, false);
+  hi = __builtin_amdgcn_mov_dpp(hi, 0x134, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+
 // a value that is the same in every lane, as one the compiler knows to be (loop bounds in scalar registers)
 __device__ __forceinline__ int64_t uniform64(int64_t v) {
   const unsigned lo = __builtin_amdgcn_readfirstlane((int)(unsigned)(uint64_t)v);

@@ -1002,3 +1002,57 @@ def site_mixture_tests_dev(context, key_a, val_a, key_b, val_b, min_coverage, it
         n_sites, _dp(site_key), int(iterations), float(min_sd_ratio), _dp(counts), _dp(fit)),
         'nvk_site_mixture_tests_dev')
     return site_key, counts, fit
+
+
+# ---- signal_map_batch: event detection and event alignment (include/nadavca_hip.h) ----------------------------
+def event_flags_dev(context, signal, sig_off, window, threshold, var_floor):
+    """Where events start in the reads' normalised signals (f64 / int64 device tensors, read j at
+    [sig_off[j], sig_off[j+1])) -> int32 (total,) : 1 at a border, else 0 (nvk_event_flags_dev)."""
+    import torch
+    lib = _lib.load()
+    n, total = int(sig_off.numel()) - 1, int(signal.numel())
+    flags = torch.zeros(max(total, 1), dtype=torch.int32, device=sig_off.device)
+    if total == 0:
+        signal = torch.zeros(1, dtype=torch.float64, device=sig_off.device)
+    _lib.check(lib.nvk_event_flags_dev(context.handle, n, total, _dp(signal), _dp(sig_off), int(window),
+                                       float(threshold), float(var_floor), _dp(flags)), 'nvk_event_flags_dev')
+    return flags[:total]
+
+
+def event_levels_dev(context, signal, sig_off, ev_pos):
+    """The events that start at the flat positions ``ev_pos`` (int64, ascending) -> (start int32: the first sample,
+    counted inside the read; length int32; level f64: the mean of the samples), nvk_event_levels_dev."""
+    import torch
+    lib = _lib.load()
+    dev = sig_off.device
+    n, total, n_ev = int(sig_off.numel()) - 1, int(signal.numel()), int(ev_pos.numel())
+    start = torch.zeros(max(n_ev, 1), dtype=torch.int32, device=dev)
+    length = torch.zeros(max(n_ev, 1), dtype=torch.int32, device=dev)
+    level = torch.zeros(max(n_ev, 1), dtype=torch.float64, device=dev)
+    if n_ev:
+        _lib.check(lib.nvk_event_levels_dev(context.handle, n, total, _dp(signal), _dp(sig_off), n_ev, _dp(ev_pos),
+                                            _dp(start), _dp(length), _dp(level)), 'nvk_event_levels_dev')
+    return start[:n_ev], length[:n_ev], level[:n_ev]
+
+
+def event_align_dev(context, level, ev_off, mu, ac, mc, base_off, l_stay, l_step, status_in, band, trim_cost,
+                    skip_cost):
+    """The adaptive-banded alignment of every read's events (``level`` / ``ev_off``) to its bases' k-mer levels and
+    Gaussian constants (``mu``, ``ac``, ``mc`` / ``base_off``), nvk_event_align_dev.  Device tensors; ``l_stay`` /
+    ``l_step``: f64 per read; ``status_in``: int32 per read or None.
+    -> (hit int32 (n, 4): status, events, first event, last event; score f64 (n,); base_event int32 (bases,))."""
+    import torch
+    lib = _lib.load()
+    dev = ev_off.device
+    n, n_ev, n_base = int(ev_off.numel()) - 1, int(level.numel()), int(mu.numel())
+    hit = torch.zeros((max(n, 0), 4), dtype=torch.int32, device=dev)
+    score = torch.zeros(max(n, 1), dtype=torch.float64, device=dev)
+    base_event = torch.zeros(max(n_base, 1), dtype=torch.int32, device=dev)
+    # (a placeholder element where an array is empty: the C-ABI takes no NULL for a batch that has reads)
+    one = lambda t: t if t.numel() else torch.zeros(1, dtype=t.dtype, device=dev)
+    st = _dp(status_in) if status_in is not None and n > 0 else C.c_void_p(0)
+    _lib.check(lib.nvk_event_align_dev(context.handle, n, n_ev, _dp(one(level)), _dp(ev_off), n_base, _dp(one(mu)),
+                                       _dp(one(ac)), _dp(one(mc)), _dp(base_off), _dp(one(l_stay)), _dp(one(l_step)),
+                                       st, int(band), float(trim_cost), float(skip_cost), _dp(hit), _dp(score),
+                                       _dp(base_event)), 'nvk_event_align_dev')
+    return hit, score[:n], base_event[:n_base]

@@ -62,6 +62,17 @@ class ReadBatch:
                    cat([v[o] for v, o in zip(vals, order)], np.int64), _offsets([k.size for k in keys]))
 
 
+    @classmethod
+    def from_signals(cls, raw_signal, sig_off, sequence, seq_off):
+        """Raw signals and basecalled sequences alone, the base -> sample tables empty: what
+        ``signal_map.signal_map_batch`` fills in (``SignalMapBatch.read_batch``)."""
+        sig_off, seq_off = np.asarray(sig_off, dtype=np.int64), np.asarray(seq_off, dtype=np.int64)
+        if sig_off.ndim != 1 or sig_off.shape != seq_off.shape or sig_off.size < 1:
+            raise ValueError('ReadBatch.from_signals: sig_off and seq_off hold one offset per read and a last one')
+        none = np.zeros(0, dtype=np.int32)
+        return cls(raw_signal, sig_off, sequence, seq_off, none, none, np.zeros(sig_off.size, dtype=np.int64))
+
+
 class BaseAlignmentBatch:
     """Matched bases of all reads: pair p of read j (pairs [off[j], off[j+1])) says read base
     ``read_idx[p]`` sits on reference base ``ref_idx[p]``, both in the READ's orientation (for a
