@@ -1005,6 +1005,41 @@ int nvk_event_align_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_events, con
                         const int32_t *status_in, int band, double trim_cost, double skip_cost, int32_t *out_hit,
                         double *out_score, int32_t *out_base_event);
 
+/* SIGNAL LOCATION (signal_locate_batch).  A subsequence alignment of every query against every column of every target:
+ * query q has Q events with levels e_i = level[q_off[q] + i], already rescaled by the caller, 0 <= Q <= max_events <=
+ * 256; target t has L columns with, per column, mu / ac / mc [col_off[t] + j] (as for the event alignment above).
+ * l_stay, l_step, l_skip and trim_cost are finite and <= 0.  NINF = -infinity.  Every expression is a rounded f64
+ * operation in the order written; the kernel only adds, multiplies and compares.
+ *   cells      (i, j), 0 <= i < Q, 0 <= j < L;  em(i, j) = ac[j] - ((e_i - mu[j]) * (e_i - mu[j])) * mc[j]
+ *   candidates open = (double)i * trim_cost          the path starts here, events 0 .. i-1 trimmed
+ *              step = S(i-1, j-1) + l_step
+ *              stay = S(i-1, j) + l_stay
+ *              skip = S(i-1, j-2) + l_skip
+ *              a neighbour outside the target, or with i == 0, is NINF: nothing crosses from one target to the next
+ *   S(i, j)    = v + em(i, j), v the largest candidate, the first of equal ones in the order open, step, stay, skip.
+ *              A cell carries (start column, first event): its own (j, i) when open wins, else its source's.
+ *   end        end(i, j) = S(i, j) + (double)(Q - 1 - i) * trim_cost; a column's best is its largest end value, the
+ *              smallest i among equal ones (a column without an end value above NINF has none)
+ *   blocks     target t is cut into blocks of NVK_LOC_BLOCK = 256 columns, the last one short; blocks are numbered over
+ *              all targets in order, n_blocks = SUM ceil(L / 256).  A block's best is the largest best of its columns,
+ *              the smallest column among equal ones.
+ * Every move consumes one event, so S(i, j) depends on the columns [j - 2 i, j] alone and a target may be swept as
+ * independent tiles that overlap by 2 (max_events - 1) columns: the results do not depend on the cut, nor on
+ * max_events beyond that it bounds Q.
+ * out_score f64[n_queries * n_blocks]: the block's best end value, query-major; out_hit i32[4 * n_queries * n_blocks]:
+ * (end column inside the target, last event i, start column inside the target, first event).  A block without a best
+ * (Q == 0) has NINF and -1 four times.  q_off and col_off are copied to the host and checked (start at 0, never
+ * decrease, end at total_events / total_cols, no query above max_events events, no target above 2^30 columns);
+ * n_blocks must be the count above.  NVK_ERR_INVALID for bad arguments, NVK_ERR_UNSUPPORTED for max_events > 256;
+ * NVK_OK with nothing written for n_queries == 0 or n_targets == 0.  Device pointers. */
+enum { NVK_LOC_OK = 0, NVK_LOC_NO_EVENTS = 1, NVK_LOC_AMBIGUOUS = 2 };   /* per-read status of signal_locate_batch */
+enum { NVK_LOC_BLOCK = 256, NVK_LOC_MAX_EVENTS = 256 };
+int nvk_signal_locate_dev(nvk_ctx *ctx, int64_t n_queries, int64_t total_events, const double *level,
+                          const int64_t *q_off, int64_t n_targets, int64_t total_cols, const double *mu,
+                          const double *ac, const double *mc, const int64_t *col_off, int max_events, double l_stay,
+                          double l_step, double l_skip, double trim_cost, int64_t n_blocks, double *out_score,
+                          int32_t *out_hit);
+
 #ifdef __cplusplus
 }
 #endif

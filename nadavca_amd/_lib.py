@@ -24,6 +24,8 @@ READ_BAD_BAND = -2
 READ_TOO_WIDE = -3
 
 MAP_OK, MAP_NO_EVENTS, MAP_LOST = 0, 1, 2   # NVK_MAP_*: per-read status of signal_map_batch
+LOC_OK, LOC_NO_EVENTS, LOC_AMBIGUOUS = 0, 1, 2   # NVK_LOC_*: per-read status of signal_locate_batch
+LOC_BLOCK, LOC_MAX_EVENTS = 256, 256   # NVK_LOC_BLOCK, NVK_LOC_MAX_EVENTS
 
 TIE_EXACT = 1   # nvk_last_tie_flags: some path comparison of the read met two exactly equal scores
 TIE_NEAR = 2    # ... two scores closer than 2^-24 relative (beyond the class below)
@@ -113,6 +115,8 @@ SIGNATURES = {
     'nvk_event_flags_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _int, _dbl, _dbl, _vp]),
     'nvk_event_levels_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     'nvk_event_align_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _i64] + [_vp] * 7 + [_int, _dbl, _dbl, _vp, _vp, _vp]),
+    'nvk_signal_locate_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64] + [_vp] * 4 + [_int] + [_dbl] * 4
+                              + [_i64, _vp, _vp]),
 }
 
 LAUNCH_SWEEP, LAUNCH_EXACT, LAUNCH_ELL = 1, 2, 3   # nvk_launch_rec.op
@@ -189,6 +193,7 @@ class Context:
         check(lib.nvk_ctx_create(int(device), C.byref(h)), 'nvk_ctx_create')
         self.handle = h
         self.device = int(device)
+        self.workspace_limit = 0   # what set_workspace_limit was last given (0: the library's default)
 
     def synchronize(self):
         check(self._lib.nvk_ctx_synchronize(self.handle), 'nvk_ctx_synchronize')
@@ -267,6 +272,7 @@ class Context:
 
     def set_workspace_limit(self, nbytes):
         check(self._lib.nvk_ctx_set_workspace_limit(self.handle, int(nbytes)), 'nvk_ctx_set_workspace_limit')
+        self.workspace_limit = int(nbytes)
 
     def close(self):
         if getattr(self, 'handle', None):

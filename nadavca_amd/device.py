@@ -1056,3 +1056,26 @@ def event_align_dev(context, level, ev_off, mu, ac, mc, base_off, l_stay, l_step
                                        st, int(band), float(trim_cost), float(skip_cost), _dp(hit), _dp(score),
                                        _dp(base_event)), 'nvk_event_align_dev')
     return hit, score[:n], base_event[:n_base]
+
+
+# ---- signal_locate_batch: the dense subsequence alignment (include/nadavca_hip.h) -----------------------------
+def signal_locate_dev(context, level, q_off, mu, ac, mc, col_off, max_events, l_stay, l_step, l_skip, trim_cost):
+    """Every query's events (``level`` / ``q_off``, rescaled) against every column of every target (``mu``, ``ac``,
+    ``mc`` / ``col_off``), nvk_signal_locate_dev.  Device tensors.  -> (score f64 (queries, blocks), hit int32
+    (queries, blocks, 4): end column, last event, start column, first event), the blocks of 256 columns numbered over
+    all targets."""
+    import torch
+    lib = _lib.load()
+    dev = q_off.device
+    nq, nt = int(q_off.numel()) - 1, int(col_off.numel()) - 1
+    n_ev, n_col = int(level.numel()), int(mu.numel())
+    lens = col_off[1:] - col_off[:-1]
+    n_blocks = int(((lens + (_lib.LOC_BLOCK - 1)) // _lib.LOC_BLOCK).sum()) if nt > 0 else 0
+    score = torch.zeros((max(nq, 0), n_blocks), dtype=torch.float64, device=dev)
+    hit = torch.zeros((max(nq, 0), n_blocks, 4), dtype=torch.int32, device=dev)
+    one = lambda t: t if t.numel() else torch.zeros(1, dtype=t.dtype, device=dev)
+    _lib.check(lib.nvk_signal_locate_dev(context.handle, nq, n_ev, _dp(one(level)), _dp(q_off), nt, n_col,
+                                         _dp(one(mu)), _dp(one(ac)), _dp(one(mc)), _dp(col_off), int(max_events),
+                                         float(l_stay), float(l_step), float(l_skip), float(trim_cost), n_blocks,
+                                         _dp(one(score)), _dp(one(hit))), 'nvk_signal_locate_dev')
+    return score, hit
