@@ -1040,6 +1040,53 @@ int nvk_signal_locate_dev(nvk_ctx *ctx, int64_t n_queries, int64_t total_events,
                           double l_step, double l_skip, double trim_cost, int64_t n_blocks, double *out_score,
                           int32_t *out_hit);
 
+/* VITERBI DECODE (decode_batch).  The classic k-mer HMM decode: per read the best path of its events over the 4^k
+ * k-mer states, the base sequence the path spells and, per base, the first event of the state that owns it (the move
+ * table).  Read r has E events with levels e_i = level[ev_off[r] + i], already rescaled by the caller and finite; the
+ * table is mean / ac / mc f64[4^k], ac = -log(sd sqrt(2 pi)), mc = 1 / (2 sd sd), computed by the caller; k in 2..6,
+ * alphabet 4, central in 0..k-1; l_stay, l_step and l_skip are finite and <= 0.  NINF = -infinity.  Every expression is
+ * a rounded f64 operation in the order written; the kernel only adds, multiplies and compares.
+ *   states     a state is a k-mer id as csrc/kmer.h numbers it, the first base most significant; S = 4^k,
+ *              0 <= s < S; `div` and `mod` are those of non-negative integers
+ *   em(i, s)   = ac[s] - ((e_i - mean[s]) * (e_i - mean[s])) * mc[s]
+ *   V(0, s)    = em(0, s)
+ *   i >= 1     with P = V(i-1, .):
+ *              step: a* = the smallest a in 0..3 with the largest P[a * 4^(k-1) + s div 4]; that value + l_step
+ *              stay: P[s] + l_stay
+ *              skip: c* = the smallest c in 0..15 with the largest P[c * 4^(k-2) + s div 16]; that value + l_skip
+ *              V(i, s) = v + em(i, s), v the largest candidate, the first of equal ones in the order step, stay, skip.
+ *              The arg-maxima are taken on P, before the cost is added.
+ *   end        the smallest s with the largest V(E-1, s); that value is out_score
+ *   walk back  from (E-1, end state): a stay goes to (i-1, s), a step to (i-1, a* 4^(k-1) + s div 4), a skip to
+ *              (i-1, c* 4^(k-2) + s div 16)
+ *   sequence   the k letters of the state at event 0, the first base first; then, event after event, one letter per
+ *              step (s mod 4 of the state entered) and two per skip ((s div 4) mod 4, then s mod 4):
+ *              n_bases = k + steps + 2 skips
+ *   owner      the state at event 0 owns base `central`; a step moves the owner on by one, a skip by two.
+ *              out_base_event[b] = the smallest event at which the path is in the state that owns b; -1 for the base a
+ *              skip passes, for the first `central` bases and for the last k - 1 - central.
+ *   status     NVK_DEC_OK; NVK_DEC_NO_EVENTS: E == 0; status_in (i32 per read, may be NULL): a read with a non-zero
+ *              entry is not decoded and reports that entry.  A read that is not decoded has n_bases 0, end state -1 and
+ *              out_score NINF.
+ * out_hit i32[4 n_reads]: per read (status, E, n_bases, end state); out_score f64[n_reads]; out_seq and out_base_event
+ * i32[total_cap]: read r's n_bases entries from cap_off[r] on (what lies between them and cap_off[r+1] is scratch).
+ * cap_off[r+1] - cap_off[r] >= k + 2 (E - 1) for every read with E >= 1.
+ * The traceback store takes 4^k / 2 bytes per event but a read's first (per 16 states one 8-byte word: c*, four a* and
+ * sixteen 2-bit choices); its size is bounded by nvk_ctx_set_workspace_limit's cap, and by 4 GiB or 60 % of the free
+ * device memory, whichever is less, on a context without a limit (4 GiB: 2 566 reads of 818 events at k = 6).  When a
+ * batch's store is larger its reads run in parts that fit (a single read larger than the cap runs on its own); results
+ * do not change.  The store's workspace stays reserved, up to that cap, until the context is destroyed.  out_parts
+ * (host pointer, may be NULL): the number of parts the batch ran in.  ev_off and cap_off are
+ * copied to the host and checked (start at 0, never decrease, end at total_events / total_cap, no read above 2^26
+ * events, the capacities above).  NVK_ERR_UNSUPPORTED for k outside 2..6, NVK_ERR_INVALID for other bad arguments;
+ * NVK_OK with nothing written for n_reads == 0.  Device pointers but out_parts. */
+enum { NVK_DEC_OK = 0, NVK_DEC_NO_EVENTS = 1 };   /* per-read status of decode_batch */
+int nvk_viterbi_decode_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_events, const double *level,
+                           const int64_t *ev_off, int k, int central, const double *mean, const double *ac,
+                           const double *mc, double l_stay, double l_step, double l_skip, const int32_t *status_in,
+                           int64_t total_cap, const int64_t *cap_off, int32_t *out_hit, double *out_score,
+                           int32_t *out_seq, int32_t *out_base_event, int64_t *out_parts);
+
 #ifdef __cplusplus
 }
 #endif

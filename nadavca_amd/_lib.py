@@ -26,6 +26,7 @@ READ_TOO_WIDE = -3
 MAP_OK, MAP_NO_EVENTS, MAP_LOST = 0, 1, 2   # NVK_MAP_*: per-read status of signal_map_batch
 LOC_OK, LOC_NO_EVENTS, LOC_AMBIGUOUS = 0, 1, 2   # NVK_LOC_*: per-read status of signal_locate_batch
 LOC_BLOCK, LOC_MAX_EVENTS = 256, 256   # NVK_LOC_BLOCK, NVK_LOC_MAX_EVENTS
+DEC_OK, DEC_NO_EVENTS = 0, 1   # NVK_DEC_*: per-read status of decode_batch
 
 TIE_EXACT = 1   # nvk_last_tie_flags: some path comparison of the read met two exactly equal scores
 TIE_NEAR = 2    # ... two scores closer than 2^-24 relative (beyond the class below)
@@ -117,6 +118,8 @@ SIGNATURES = {
     'nvk_event_align_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _i64] + [_vp] * 7 + [_int, _dbl, _dbl, _vp, _vp, _vp]),
     'nvk_signal_locate_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64] + [_vp] * 4 + [_int] + [_dbl] * 4
                               + [_i64, _vp, _vp]),
+    'nvk_viterbi_decode_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _int, _int, _vp, _vp, _vp, _dbl, _dbl, _dbl, _vp, _i64]
+                               + [_vp] * 5 + [C.POINTER(_i64)]),
 }
 
 LAUNCH_SWEEP, LAUNCH_EXACT, LAUNCH_ELL = 1, 2, 3   # nvk_launch_rec.op

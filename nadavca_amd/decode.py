@@ -1,0 +1,181 @@
+"""``decode_batch``: a base sequence and its base -> sample table for every read of a ``ReadBatch``, from raw signal alone.
+
+``signal_locate_batch`` places raw signal on a reference by a dense DP against every column: it serves references of
+some 10^5 bases.  This module takes the other classic route, the k-mer HMM decode of the event-based basecallers
+(Nanocall's class): Viterbi over the 4^k k-mer states of the table and the read's events.  The decoded sequence is
+rough (about three bases in four), but it is a sequence: ``SeedAligner`` is indexed and places it on a genome of any
+size, and the Viterbi path is at the same time the base -> sample table (the "move table") that every batch workflow
+starts from.  On the device:
+
+1. per-read median / MAD normalisation (``nvk_normalize_groups_dev``) and event detection, both ``signal_map_batch``'s;
+2. a rescale by moments: the events' per-read median and MAD are mapped onto those of the table's 4^k means
+   (``locate.rescale_pooled_dev``).  A read with fewer than ``min_events`` events or a zero MAD is ``DEC_NO_EVENTS``;
+3. the operator (``nvk_viterbi_decode_dev``, contract in include/nadavca_hip.h): per read the best path's score, the
+   sequence it spells and per base the first event of the state that owns it;
+4. a compaction of the operator's outputs, which it lays out by capacity, in torch.
+
+So one operator stands where ``signal_locate_batch`` and ``signal_map_batch`` do on that route:
+
+    rb0 = ReadBatch.from_signals(raw, sig_off, np.zeros(0, np.int32), np.zeros(n + 1, np.int64))
+    dec = decode_batch(rb0)
+    rb1 = dec.read_batch(rb0)                      # decoded sequences + base -> sample tables
+    align_signal_batch(None, rb1, aligner=SeedAligner(reference, k=10))
+
+Limits: a homopolymer beyond k bases is not resolved (a step from a state to itself is a stay); leader and tail signal
+are not trimmed, they decode as bases that a local aligner leaves unaligned; 4-letter tables with k in 2..6 only, no
+RNA.
+"""
+import math
+
+import numpy as np
+
+from . import _lib, defaults
+from .batchflow import load_kmer_model, seg_index
+from .readbatch import ReadBatch
+
+DEC_OK, DEC_NO_EVENTS = _lib.DEC_OK, _lib.DEC_NO_EVENTS
+K_MIN, K_MAX = 2, 6
+
+
+class DecodeBatch:
+    """What ``decode_batch`` returns, numpy arrays.  Per read: ``status`` (DEC_OK; DEC_NO_EVENTS: fewer than
+    ``min_events`` events or events that all have one level), ``n_events``, ``n_bases`` (0 unless decoded), ``score``
+    (the best path's log-likelihood per event, NaN unless decoded), ``seq_off`` (int64, n + 1).  Flat: ``sequence``
+    (int32 base codes, read j at [seq_off[j], seq_off[j+1])) and ``map_base`` / ``map_sig`` / ``map_off`` in the layout
+    of ``ReadBatch`` — one row per base with an event, bases ascending, ``map_sig`` the first sample of that event; the
+    first ``central`` and the last k - 1 - ``central`` bases of a read and a base a skip passes have none."""
+
+    def __init__(self, status, n_events, n_bases, score, seq_off, sequence, map_base, map_sig, map_off, parts=0):
+        self.status, self.n_events, self.n_bases, self.score = status, n_events, n_bases, score
+        self.seq_off, self.sequence = seq_off, sequence
+        self.map_base, self.map_sig, self.map_off = map_base, map_sig, map_off
+        self.parts = parts   # parts the operator cut the batch into under the workspace cap
+        self.n = int(status.size)
+        self.n_decoded = int((status == DEC_OK).sum())
+
+    def read_batch(self, rb):
+        """A new ``ReadBatch`` with ``rb``'s signals, the decoded sequences and these tables.  A read that is not
+        decoded gets an empty sequence and no rows: downstream it drops out like a read the aligner did not place."""
+        if rb.n != self.n:
+            raise ValueError('DecodeBatch.read_batch: the batch holds %d reads, the decode %d' % (rb.n, self.n))
+        return ReadBatch(rb.raw_signal, rb.sig_off, self.sequence, self.seq_off, self.map_base, self.map_sig,
+                         self.map_off)
+
+
+def transition_costs(p_stay, p_skip):
+    """-> (l_stay, l_step, l_skip): the logs of p_stay, 1 - p_stay - p_skip and p_skip"""
+    if not (0.0 < p_stay < 1.0 and 0.0 < p_skip < 1.0 and p_stay + p_skip < 1.0):
+        raise ValueError('decode_batch: p_stay, p_skip and 1 - p_stay - p_skip must lie inside (0, 1)')
+    return math.log(p_stay), math.log(1.0 - p_stay - p_skip), math.log(p_skip)
+
+
+def check_table(kmer_model):
+    """The operator's limits on the table, as a ValueError that names them"""
+    alphabet, k = kmer_model.get_alphabet_size(), kmer_model.get_k()
+    if alphabet != 4:
+        raise ValueError('decode_batch: the table has %d letters; only 4-letter tables are decoded' % alphabet)
+    if not K_MIN <= k <= K_MAX:
+        raise ValueError('decode_batch: the table has k = %d; k is %d..%d' % (k, K_MIN, K_MAX))
+
+
+def state_tables_dev(kmer_model, sigma_scale, device):
+    """-> (mean, ac, mc) f64[4^k] on ``device``: the states' levels and the constants of their Gaussians with
+    sigma * ``sigma_scale``, formed as ``signal_map.base_tables_dev`` forms them"""
+    import torch
+    sd = np.asarray(kmer_model.sigma, dtype=np.float64) * float(sigma_scale)
+    tables = (np.asarray(kmer_model.mean, dtype=np.float64), -np.log(sd * math.sqrt(2.0 * math.pi)),
+              1.0 / (2.0 * sd * sd))
+    return [torch.from_numpy(np.ascontiguousarray(t)).to(device) for t in tables]
+
+
+def capacity_offsets(ev_off, k):
+    """Where the operator writes each read's bases: k + 2 (E - 1) entries for a read with events -> int64 (n + 1)"""
+    import torch
+    n_ev = ev_off[1:] - ev_off[:-1]
+    cap = torch.where(n_ev >= 1, k + 2 * (n_ev - 1), torch.zeros_like(n_ev))
+    return torch.cat([torch.zeros(1, dtype=torch.int64, device=ev_off.device), torch.cumsum(cap, 0)])
+
+
+def traceback_bytes(n_events, k):
+    """Bytes of the operator's traceback store for reads of ``n_events`` events (numpy): 4^k / 2 per event but the
+    first"""
+    return int(np.maximum(np.asarray(n_events, dtype=np.int64) - 1, 0).sum()) * (4 ** k // 2)
+
+
+class DecodeStages:
+    """The device tensors between the stages of one ``decode_batch`` call (``decode_stages``)."""
+    __slots__ = ('norm', 'sig_off', 'ev_off', 'ev_start', 'ev_level', 'mean', 'ac', 'mc', 'scaled', 'ok', 'status_in',
+                 'cap_off', 'costs', 'hit', 'path_score', 'seq', 'base_event', 'parts')
+
+
+def decode_stages(read_batch, kmer_model, p_stay, p_skip, sigma_scale, min_events, window, threshold, var_floor,
+                  timer=None):
+    """Stages 1 to 3 on the device -> DecodeStages.  ``timer(name)``: called after each stage (bench tool)."""
+    import torch
+    from .device import normalize_groups_dev, viterbi_decode_dev
+    from .locate import rescale_pooled_dev
+    from .signal_map import detect_events_dev
+    context = kmer_model.context
+    device = torch.device('cuda', context.device)
+    rb, st = read_batch, DecodeStages()
+    tick = timer if timer is not None else (lambda name: None)
+    st.costs = transition_costs(p_stay, p_skip)
+    raw = torch.from_numpy(rb.raw_signal).to(device)
+    if raw.dtype != torch.float64:
+        raw = raw.to(torch.float64)
+    st.sig_off = torch.from_numpy(rb.sig_off).to(device)
+    st.mean, st.ac, st.mc = state_tables_dev(kmer_model, sigma_scale, device)
+    tick('upload')
+    st.norm = normalize_groups_dev(context, raw, st.sig_off, out=raw)[0] if rb.n and raw.numel() else raw
+    tick('normalise')
+    _, _, st.ev_off, st.ev_start, _, st.ev_level = detect_events_dev(context, st.norm, st.sig_off, window, threshold,
+                                                                     var_floor)
+    tick('events')
+    st.scaled, st.ok = rescale_pooled_dev(context, st.ev_level, st.ev_off, st.mean, min_events)
+    st.status_in = torch.where(st.ok, DEC_OK, DEC_NO_EVENTS).to(torch.int32)
+    st.cap_off = capacity_offsets(st.ev_off, kmer_model.get_k())
+    tick('rescale')
+    st.hit, st.path_score, st.seq, st.base_event, st.parts = viterbi_decode_dev(
+        context, st.scaled, st.ev_off, kmer_model.get_k(), kmer_model.get_central_position(), st.mean, st.ac, st.mc,
+        *st.costs, st.status_in, st.cap_off)
+    tick('decode')
+    return st
+
+
+def decode_batch(read_batch, kmer_model=defaults.KMER_MODEL_FILE, p_stay=0.7, p_skip=0.01, sigma_scale=1.0,
+                 min_events=32, window=2, threshold=5.0, var_floor=0.02, context=None):
+    """A base sequence and its base -> sample table for every read of ``read_batch`` from its raw signal alone (module
+    docstring); any sequence or table the batch carries is ignored.  ``kmer_model``: a KmerModel or a path (4 letters,
+    k in 2..6, else ValueError); ``context``: the context a model loaded from a path is made on (default: the
+    process-wide one).  ``p_stay`` / ``p_skip``: the chances that an event stays in its k-mer or passes one;
+    ``sigma_scale``: the model's sigma is multiplied by it; ``min_events`` (>= 1): a read with fewer is not decoded;
+    ``window``, ``threshold``, ``var_floor``: the event detector's.  The defaults are uncalibrated: they are the values
+    at which the simulated reads of the test suite (dwell 3-17 samples, noise 0.35, the packaged 6-mer table) decode
+    best (the batch of the quality test is the tuning set), not values fitted to real data.  -> DecodeBatch."""
+    import torch
+    if isinstance(kmer_model, (str, bytes)) or hasattr(kmer_model, '__fspath__'):
+        from .kmer_model import load_kmer_model as load_on
+        kmer_model = load_on(kmer_model, context=context) if context is not None else load_kmer_model(kmer_model)
+    check_table(kmer_model)
+    if int(min_events) < 1:
+        raise ValueError('decode_batch: min_events is at least 1')
+    rb = read_batch
+    st = decode_stages(rb, kmer_model, p_stay, p_skip, sigma_scale, min_events, window, threshold, var_floor)
+    dev = st.ev_off.device
+    status, n_ev, n_bases = st.hit[:, 0], st.hit[:, 1].to(torch.int64), st.hit[:, 2].to(torch.int64)
+    ok = status == DEC_OK
+    score = torch.where(ok, st.path_score / torch.clamp(n_ev, min=1).to(torch.float64),
+                        torch.full_like(st.path_score, float('nan')))
+    # the compaction: read r's n_bases entries lie at cap_off[r]
+    seq_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(n_bases, 0)])
+    owner, inner = seg_index(seq_off)
+    at = st.cap_off[:-1][owner] + inner
+    sequence, event = st.seq[at], st.base_event[at].to(torch.int64)
+    keep = event >= 0
+    k_owner = owner[keep]
+    map_sig = st.ev_start[st.ev_off[:-1][k_owner] + event[keep]]
+    map_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev),
+                         torch.cumsum(torch.bincount(k_owner, minlength=rb.n), 0)])
+    host = lambda t: t.cpu().numpy()
+    return DecodeBatch(host(status), host(st.hit[:, 1]), host(st.hit[:, 2]), host(score), host(seq_off),
+                       host(sequence), host(inner[keep].to(torch.int32)), host(map_sig), host(map_off), st.parts)

@@ -1079,3 +1079,29 @@ def signal_locate_dev(context, level, q_off, mu, ac, mc, col_off, max_events, l_
                                          float(l_stay), float(l_step), float(l_skip), float(trim_cost), n_blocks,
                                          _dp(one(score)), _dp(one(hit))), 'nvk_signal_locate_dev')
     return score, hit
+
+
+# ---- decode_batch: the k-mer HMM Viterbi decode (include/nadavca_hip.h) ---------------------------------------
+def viterbi_decode_dev(context, level, ev_off, k, central, mean, ac, mc, l_stay, l_step, l_skip, status_in, cap_off):
+    """The best path of every read's events (``level`` / ``ev_off``, rescaled) over the 4^k states of the table
+    (``mean``, ``ac``, ``mc``), nvk_viterbi_decode_dev.  Device tensors; ``status_in``: int32 per read or None;
+    ``cap_off``: int64 (n + 1), where each read's bases are written (k + 2 (E - 1) entries at least).
+    -> (hit int32 (n, 4): status, events, bases, end state; score f64 (n,); seq int32 and base_event int32, both laid
+    out by ``cap_off``; the number of parts the traceback store was cut into)."""
+    import torch
+    lib = _lib.load()
+    dev = ev_off.device
+    n, n_ev = int(ev_off.numel()) - 1, int(level.numel())
+    total_cap = int(cap_off[-1]) if n > 0 else 0
+    hit = torch.zeros((max(n, 0), 4), dtype=torch.int32, device=dev)
+    score = torch.zeros(max(n, 1), dtype=torch.float64, device=dev)
+    seq = torch.zeros(max(total_cap, 1), dtype=torch.int32, device=dev)
+    base_event = torch.zeros(max(total_cap, 1), dtype=torch.int32, device=dev)
+    one = lambda t: t if t.numel() else torch.zeros(1, dtype=t.dtype, device=dev)
+    st = _dp(status_in) if status_in is not None and n > 0 else C.c_void_p(0)
+    parts = C.c_int64(0)
+    _lib.check(lib.nvk_viterbi_decode_dev(context.handle, n, n_ev, _dp(one(level)), _dp(ev_off), int(k), int(central),
+                                          _dp(mean), _dp(ac), _dp(mc), float(l_stay), float(l_step), float(l_skip),
+                                          st, total_cap, _dp(cap_off), _dp(hit), _dp(score), _dp(seq),
+                                          _dp(base_event), C.byref(parts)), 'nvk_viterbi_decode_dev')
+    return hit, score[:n], seq[:total_cap], base_event[:total_cap], int(parts.value)

@@ -1,0 +1,113 @@
+"""decode_batch on N bench-shaped reads (400 +- 40 bases, both strands, the simulated signal of
+``synthetic.make_read_batch``) over a random genome of ``--genome`` bases: its stages timed apart — upload,
+normalisation, event detection, the rescale onto the table's means, the operator (``nvk_viterbi_decode_dev``: the sweep
+and the walk back of every part under the workspace cap) — the operator alone in cell updates per second (4^k per
+event), the traceback store's bytes and parts, the whole call, and the chain decode_batch -> ``SeedAligner(k=10)`` ->
+align_signal_batch beside ``align_signal_batch`` with the same aligner from the simulator's own sequences and tables.
+HIP events after a warm-up; the figures are the median of ``--reps`` runs.
+`python tools/bench_decode.py [N] [--genome L] [--reps R]`."""
+import argparse
+import inspect
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+from nadavca_amd import decode, decode_batch, defaults, synthetic  # noqa: E402
+from nadavca_amd.align_signal import align_signal_batch  # noqa: E402
+from nadavca_amd.device import viterbi_decode_dev  # noqa: E402
+from nadavca_amd.kmer_model import KmerModel  # noqa: E402
+from nadavca_amd.readbatch import ReadBatch  # noqa: E402
+from nadavca_amd.seedalign import SeedAligner  # noqa: E402
+
+parser = argparse.ArgumentParser()
+parser.add_argument('n_reads', nargs='?', type=int, default=10000)
+parser.add_argument('--genome', type=int, default=100000)
+parser.add_argument('--reps', type=int, default=3)
+opts = parser.parse_args()
+
+km = KmerModel.load_from_hdf5(defaults.KMER_MODEL_FILE)
+ctx = km.context
+dev = torch.device('cuda', ctx.device)
+rb, _, genome = synthetic.make_read_batch(opts.n_reads, synthetic.load_model_arrays(), seed=7,
+                                          genome_length=opts.genome)
+bare = ReadBatch.from_signals(rb.raw_signal, rb.sig_off, np.zeros(0, np.int32), np.zeros(rb.n + 1, np.int64))
+seed = SeedAligner(genome, k=10)
+STAGES = ('upload', 'normalise', 'events', 'rescale', 'decode')
+defaults_of = inspect.signature(decode_batch).parameters   # the staged run takes decode_batch's own defaults
+args = tuple(defaults_of[name].default for name in ('p_stay', 'p_skip', 'sigma_scale', 'min_events', 'window',
+                                                    'threshold', 'var_floor'))
+
+
+def staged():
+    """-> (the stages' tensors, ms per stage by HIP events)"""
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(len(STAGES) + 1)]
+    torch.cuda.synchronize(dev)
+    marks[0].record()
+    at = iter(marks[1:])
+    st = decode.decode_stages(bare, km, *args, timer=lambda name: next(at).record())
+    torch.cuda.synchronize(dev)
+    return st, [a.elapsed_time(b) for a, b in zip(marks, marks[1:])]
+
+
+def timed(fn):
+    torch.cuda.synchronize(dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = fn()
+    e1.record()
+    torch.cuda.synchronize(dev)
+    return out, e0.elapsed_time(e1)
+
+
+def operator_alone(st):
+    return timed(lambda: viterbi_decode_dev(ctx, st.scaled, st.ev_off, km.get_k(), km.get_central_position(), st.mean,
+                                            st.ac, st.mc, *st.costs, st.status_in, st.cap_off))[1]
+
+
+whole = lambda: decode_batch(bare, kmer_model=km)
+
+
+def chain():
+    dec = whole()
+    return dec, align_signal_batch(None, dec.read_batch(bare), kmer_model=km, aligner=seed)
+
+
+staged()   # warm-up: workspaces, the allocator's blocks, first launches
+chain()
+align_signal_batch(None, rb, kmer_model=km, aligner=seed)
+rows = {k: [] for k in STAGES + ('operator', 'whole', 'chain', 'asb_table')}
+for _ in range(opts.reps):
+    st, ms = staged()
+    for k, v in zip(STAGES, ms):
+        rows[k].append(v)
+    rows['operator'].append(operator_alone(st))
+    dec, ms = timed(whole)
+    rows['whole'].append(ms)
+    (_, b), ms = timed(chain)
+    rows['chain'].append(ms)
+    a, ms = timed(lambda: align_signal_batch(None, rb, kmer_model=km, aligner=seed))
+    rows['asb_table'].append(ms)
+med = {k: float(np.median(v)) for k, v in rows.items()}
+k = km.get_k()
+n_ev = st.ev_off.cpu().numpy()
+decoded = n_ev[1:] - n_ev[:-1]
+decoded = decoded[st.ok.cpu().numpy()]
+cells = int(decoded.sum()) * 4 ** k
+store = decode.traceback_bytes(decoded, k)
+print('%d reads, %.0f events and %.0f samples each on average; k = %d, %d states; genome %d bases'
+      % (opts.n_reads, n_ev[-1] / opts.n_reads, rb.sig_off[-1] / opts.n_reads, k, 4 ** k, opts.genome))
+print('upload (raw signal, offsets, the table)        %9.2f ms' % med['upload'])
+print('normalise (nvk_normalize_groups_dev)           %9.2f ms' % med['normalise'])
+print('events (flags, prefix sums, levels)            %9.2f ms' % med['events'])
+print('rescale onto the table\'s means, capacities     %9.2f ms' % med['rescale'])
+print('operator, %3d part(s)                          %9.2f ms' % (st.parts, med['decode']))
+print('operator alone                                 %9.2f ms  (%.1f G cell updates/s; traceback store %.1f MB, '
+      '%.1f GB/s written)' % (med['operator'], cells / med['operator'] / 1e6, store / 1e6,
+                              store / med['operator'] / 1e6))
+print('decode_batch, the whole call                   %9.2f ms  (%.1f k reads/s; %d decoded, %.2f bases per event)' % (
+    med['whole'], opts.n_reads / med['whole'], dec.n_decoded, dec.n_bases.sum() / max(int(dec.n_events.sum()), 1)))
+print('decode -> SeedAligner(k=10) -> align_signal    %9.2f ms  (%d aligned)' % (med['chain'], b.n_aligned))
+print('align_signal_batch, simulator\'s sequences      %9.2f ms  (%d aligned)' % (med['asb_table'], a.n_aligned))
