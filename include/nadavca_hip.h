@@ -1087,6 +1087,58 @@ int nvk_viterbi_decode_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_events, 
                            int64_t total_cap, const int64_t *cap_off, int32_t *out_hit, double *out_score,
                            int32_t *out_seq, int32_t *out_base_event, int64_t *out_parts);
 
+/* K-MER POSTERIORS (decode_batch(qualities=True)).  The forward-backward recurrences over the same 4^k states and the
+ * same three moves as the Viterbi decode above, with sums where that one takes maxima: per event the posterior of each
+ * of the four letters at position `pos` of the state (first base = 0; pos in 0..k-1), and per read the likelihood of
+ * its events summed over all paths.  level / ev_off, k, mean / ac / mc, status_in and em(i, s) are the Viterbi
+ * contract's.  w_stay, w_step and w_skip are the moves' linear weights, each finite and in (0, 1], with
+ * max(w_stay, w_step) >= 2^-10 (the caller passes the numbers whose logs the Viterbi call takes).  Every expression is
+ * a rounded f64 operation in the order written (-ffp-contract=off); fma is the fused operation; the kernels call no
+ * library exp or log.  Q = 4^(k-1), T = 4^(k-2), S = 4^k.
+ *   EXP(g)     y = g * LOG2E (0x1.71547652b82fep+0), n = rint(y), EXP = ldexp(P(y - n), (int)n); P is the fma chain of
+ *              xm::exp2_frac_horner (csrc/xmath.h): p = c11; p = fma(p, f, c10); ...; P = fma(p, f, 1.0)
+ *   b(i, s)    = EXP(max(em(i, s), -300.0)).  With the floor a row's largest value, and the product of a forward and a
+ *              backward value at the best state, stay normal doubles; an event far from every state becomes
+ *              uninformative instead of zeroing the row
+ *   frexp      "the exponent of v": the x with v = m * 2^x, m in [0.5, 1)
+ *   forward    A(0, s) = b(0, s), X_0 = 0.  For i >= 1, with P = A(i-1, .): x = the exponent of max_s P[s];
+ *              sum4  = ((P[0 Q + q] + P[1 Q + q]) + P[2 Q + q]) + P[3 Q + q], q = s div 4;
+ *              sum16 = the same over c = 0..15 ascending, of P[c T + s div 16];
+ *              t = ((w_step * sum4) + (w_stay * P[s])) + (w_skip * sum16);
+ *              A(i, s) = ldexp(t, -x) * b(i, s);  X_i = X_(i-1) + x
+ *   backward   B(E-1, s) = 1.  For i = E-2 down to 0: W[s'] = B(i+1, s') * b(i+1, s');
+ *              G4[r] = ((W[4r] + W[4r+1]) + W[4r+2]) + W[4r+3] for r < Q;
+ *              G16[r] = ((G4[4r] + G4[4r+1]) + G4[4r+2]) + G4[4r+3] for r < T;  y = the exponent of max_s B(i+1, s);
+ *              B(i, s) = ldexp(((w_step * G4[s mod Q]) + (w_stay * W[s])) + (w_skip * G16[s mod T]), -y)
+ *              (the successors of s are the states whose Viterbi predecessor is s: by a step (s mod Q) 4 + 0..3, by a
+ *              skip (s mod T) 16 + 0..15)
+ *   sums over  (Z and the class sums) within a block of 16 consecutive states ascending, a block without a term giving
+ *   all states 0; over the T blocks v[u] the butterfly of wave_sum: for d = min(T, 64) / 2, ..., 1: v[u] = v[u] + v[u xor d]
+ *              for every u at once; for T = 256 the four groups of 64 blocks then join as (g0 + g1) + (g2 + g3)
+ *   outputs    C_x(i) = the sum of A(i, s) * B(i, s) over the states whose letter at pos is x;
+ *              out_marg[4 (ev_off[r] + i) + x] = C_x / (((C_0 + C_1) + C_2) + C_3): self-normalised, no exponent enters.
+ *              out_z[2 r] = the sum of A(E-1, .), out_z[2 r + 1] = (double)X_(E-1): log Z = log(out_z[2 r]) +
+ *              out_z[2 r + 1] ln 2 is left to the caller.
+ *              out_status[r] = NVK_DEC_OK; NVK_DEC_NO_EVENTS: E == 0; else the read's non-zero status_in entry.  A read
+ *              that is not processed writes no marginals and reports out_z = (0, 0).
+ * out_marg f64[4 total_events], out_z f64[2 n_reads], out_status i32[n_reads].
+ * The forward sweep keeps every A(i, .) in a row store of 8 * 4^k bytes per event, which the backward sweep, a second
+ * launch, reads back.  The store's size is bounded by nvk_ctx_set_workspace_limit's cap, and by 16 GiB or 60 % of the
+ * free device memory, whichever is less, on a context without a limit (at k = 6 a read of 816 events takes 26.7 MB:
+ * 4 GiB would hold 160 such reads, fewer workgroups than the device has CUs; 16 GiB holds 640).  When a batch's store
+ * is larger its reads run in parts that fit, the forward and the backward sweep of a part before the next part's (a
+ * single read larger than the cap runs on its own); results do not change.  The store shares the Viterbi store's
+ * workspace, which stays reserved, up to that cap, until the context is destroyed.  out_parts (host pointer, may be
+ * NULL): the number of parts.  out_ms (host pointer to two doubles, may be NULL): the milliseconds of the forward and of
+ * the backward launches, summed over the parts, by HIP events; with it the call waits for every part before it starts
+ * the next.  ev_off is copied to the host and checked (starts at 0, never decreases, ends at total_events, no read
+ * above 2^26 events).  NVK_ERR_UNSUPPORTED for k outside 2..6, NVK_ERR_INVALID for other bad arguments; NVK_OK with
+ * nothing written for n_reads == 0.  Device pointers but out_parts and out_ms. */
+int nvk_kmer_posterior_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_events, const double *level,
+                           const int64_t *ev_off, int k, int pos, const double *mean, const double *ac,
+                           const double *mc, double w_stay, double w_step, double w_skip, const int32_t *status_in,
+                           double *out_marg, double *out_z, int32_t *out_status, int64_t *out_parts, double *out_ms);
+
 #ifdef __cplusplus
 }
 #endif

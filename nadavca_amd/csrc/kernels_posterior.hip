@@ -1,0 +1,452 @@
+// Forward-backward over the 4^k k-mer states for decode_batch(qualities=True) (nadavca_amd/decode.py): per event the
+// posterior of each of the four letters at one position of the state, and per read the likelihood of its events summed
+// over all paths.  The rules are those of include/nadavca_hip.h (nvk_kmer_posterior_dev); the CPU restatement the tests
+// hold these kernels to is tests/host_shims/posterior_host.cpp, which keeps the full S x E matrices.
+//
+// Both sweeps follow the Viterbi sweep of kernels_decode.hip: one workgroup per read, T = S / 16 threads (1, 4, 16, 64
+// or 256 for k = 2..6), thread u owns the 16 consecutive states 16 u .. 16 u + 15, whose table entries stay in
+// registers for the whole read, and one barrier per event.
+//
+// THE FORWARD SWEEP is the Viterbi sweep with sums where that one takes maxima: per event a thread reads the 16 skip
+// predecessors c T + u and the four times four step predecessors a Q + 4 u + g of the previous row from LDS (two padded
+// row buffers, as there), forms 16 emissions and writes its 16 values of A(i, .) to LDS and, as eight 16-byte pairs,
+// to the row store in global memory.  The row is rescaled by the exponent of the previous row's largest value: every
+// wave leaves its own largest value in LDS before the barrier, and every thread joins the waves' values after it.
+//
+// THE BACKWARD SWEEP is a launch of its own.  B and W = B * b stay in registers; the successors factorise as the
+// predecessors do (by a step (s mod Q) 4 + 0..3, by a skip (s mod T) 16 + 0..15), so the threads share only the sums
+// G4 of four and G16 of sixteen consecutive W: thread u writes G4[4 u .. 4 u + 3] (already times w_step) and G16[u]
+// (times w_skip) and reads 16 consecutive entries of each.  It asks for its own 16 values of A(i, .) from the row store
+// first, evaluates the emissions while they arrive, then forms the four class sums of A * B, and the waves' class sums
+// and their largest B go to LDS before the event's barrier; thread 0 joins them after it and writes the event's four
+// marginals.
+//
+// THE ROW STORE takes 8 * 4^k bytes per event (32 KB at k = 6), the rows of a read one after another from
+// ev_off[r] - ev_off[r0] on, r0 the part's first read.  Inside a row the layout is the sweeps' own: state 16 u + 2 q + h
+// lies at q 2 T + 2 u + h, so that one 16-byte access per lane covers 1 KB of consecutive memory per wave (with a
+// thread's 16 values side by side every lane of an access would touch another 128-byte line).  The store is the seed
+// aligner's traceback workspace, as the Viterbi store is; the host cuts a batch into parts whose rows fit the cap and
+// runs the forward and the backward sweep of a part before the next part's.
+//
+// No atomics, no scratch, no library exp or log: EXP is rint, the fma chain of xm::exp2_frac_horner and ldexp.  With
+// -ffp-contract=off every value is the rounded operation the contract writes, on the device as on the host.
+#include <vector>
+
+#include "nvk_internal.h"
+#include "xmath.h"
+
+namespace {
+
+constexpr int POST_MAX_EVENTS = 1 << 26;  // per read
+constexpr int POST_PAD = 2;               // doubles of padding after every 16 entries of a row in LDS
+constexpr double POST_EM_FLOOR = -300.0;
+constexpr double POST_MIN_MOVE = 0x1p-10;  // max(w_stay, w_step) is at least this
+
+struct PostArgs {
+  const double *level;  // the events' levels, read r at ev_off[r]
+  const int64_t *ev_off;
+  const double *mean, *ac, *mc;  // the table, f64[4^k]
+  const int32_t *status_in;      // per read or null
+  double w_stay, w_step, w_skip;
+  double *out_marg, *out_z;
+  int32_t *out_status;
+  double *rows;  // the row store: the part's first read starts at double 0
+  int r0;        // the part's first read
+  int pos;
+};
+
+// Where the j-th of a thread's 16 values lies in a row of the store, from the thread's first pair on: the threads'
+// pairs (j, j + 1) side by side, so that the 16-byte accesses of a wave's lanes are consecutive, 1 KB per instruction
+template <int T>
+__device__ __forceinline__ constexpr int post_store_at(int j) { return (j >> 1) * 2 * T + (j & 1); }
+
+// where entry s lies in a padded row
+__device__ __forceinline__ constexpr int post_at(int s) { return s + (s >> 4) * POST_PAD; }
+
+// EXP of the contract
+__device__ __forceinline__ double post_exp(double g) {
+  const double y = g * xm::LOG2E;
+  const double n = rint(y);
+  return ldexp(xm::exp2_frac_horner(y - n), (int)n);
+}
+
+// b(i, s) for a level e
+__device__ __forceinline__ double post_emission(double e, double mean, double ac, double mc) {
+  const double d = e - mean;
+  return post_exp(fmax(ac - (d * d) * mc, POST_EM_FLOOR));
+}
+
+// the butterfly of wave_sum over the W lanes of a workgroup's wave that hold a thread (W = min(T, 64))
+template <int W>
+__device__ __forceinline__ double post_wave_sum(double v) {
+#pragma unroll
+  for (int d = W / 2; d >= 1; d >>= 1) v = v + __shfl_xor(v, d, 64);
+  return v;
+}
+template <int W>
+__device__ __forceinline__ double post_wave_max(double v) {
+#pragma unroll
+  for (int d = W / 2; d >= 1; d >>= 1) v = fmax(v, __shfl_xor(v, d, 64));
+  return v;
+}
+// the waves' values of a sum over all states, joined: (g0 + g1) + (g2 + g3) for four waves
+template <int NW>
+__device__ __forceinline__ double post_join_sum(const double *g, int stride) {
+  if (NW == 1) return g[0];
+  return (g[0] + g[stride]) + (g[2 * stride] + g[3 * stride]);
+}
+template <int NW>
+__device__ __forceinline__ double post_join_max(const double *g) {
+  double m = g[0];
+#pragma unroll
+  for (int w = 1; w < NW; w++) m = fmax(m, g[w]);
+  return m;
+}
+
+// status of read rd, as both sweeps see it
+__device__ __forceinline__ int post_status(const PostArgs &a, int64_t rd, int E) {
+  const int status = a.status_in ? a.status_in[rd] : 0;
+  return (status == 0 && E == 0) ? NVK_DEC_NO_EVENTS : status;
+}
+
+template <int K>
+__global__ __launch_bounds__((1 << (2 * K)) / 16) void posterior_forward_kernel(PostArgs a) {
+  constexpr int S = 1 << (2 * K), T = S / 16, Q = S / 4, ROW = S + T * POST_PAD;
+  constexpr int W = T < 64 ? T : 64, NW = T / W;
+  __shared__ __attribute__((aligned(16))) double row[2][ROW];
+  __shared__ double wave_top[2][NW];  // per wave the largest value of the row it wrote
+  __shared__ double wave_z[NW];
+  const int u = threadIdx.x, wave = u / W;
+  const int64_t rd = (int64_t)a.r0 + blockIdx.x;
+  const int64_t ev0 = a.ev_off[rd];
+  const int E = (int)(a.ev_off[rd + 1] - ev0);
+  const int status = post_status(a, rd, E);
+  if (status != 0) {
+    if (u == 0) {
+      a.out_status[rd] = status;
+      a.out_z[2 * rd] = 0.0;
+      a.out_z[2 * rd + 1] = 0.0;
+    }
+    return;
+  }
+  const double *lev = a.level + ev0;
+  const double w_stay = a.w_stay, w_step = a.w_step, w_skip = a.w_skip;
+  double *store = a.rows + (ev0 - a.ev_off[a.r0]) * (int64_t)S + 2 * u;
+
+  double A[16], mean[16], ac[16], mc[16];
+  double e = lev[0];
+  double top = 0.0;
+#pragma unroll
+  for (int j = 0; j < 16; j++) {
+    mean[j] = a.mean[16 * u + j];
+    ac[j] = a.ac[16 * u + j];
+    mc[j] = a.mc[16 * u + j];
+    A[j] = post_emission(e, mean[j], ac[j], mc[j]);
+    row[0][post_at(16 * u) + j] = A[j];
+    store[post_store_at<T>(j)] = A[j];
+    top = fmax(top, A[j]);
+  }
+  top = post_wave_max<W>(top);
+  if ((u & (W - 1)) == 0) wave_top[0][wave] = top;
+  __syncthreads();
+  long long X = 0;
+  for (int i = 1; i < E; i++) {
+    const double *P = row[(i - 1) & 1];
+    double *N = row[i & 1];
+    e = lev[i];
+    const int x = __builtin_amdgcn_frexp_exp(post_join_max<NW>(wave_top[(i - 1) & 1]));
+    // skip: the 16 predecessors c T + u, shared by all the thread's states
+    double sum16 = P[post_at(u)];
+#pragma unroll
+    for (int c = 1; c < 16; c++) sum16 = sum16 + P[post_at(c * T + u)];
+    const double sk = w_skip * sum16;
+    // step: per group g of four states the 4 predecessors a Q + 4 u + g
+    double st[4];
+#pragma unroll
+    for (int g = 0; g < 4; g++) st[g] = P[post_at(4 * u) + g];
+#pragma unroll
+    for (int c = 1; c < 4; c++) {
+#pragma unroll
+      for (int g = 0; g < 4; g++) st[g] = st[g] + P[post_at(c * Q + 4 * u) + g];
+    }
+#pragma unroll
+    for (int g = 0; g < 4; g++) st[g] = w_step * st[g];
+    double *out = store + (int64_t)i * S;
+    top = 0.0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const double t = (st[j >> 2] + w_stay * A[j]) + sk;
+      A[j] = ldexp(t, -x) * post_emission(e, mean[j], ac[j], mc[j]);
+      N[post_at(16 * u) + j] = A[j];
+      out[post_store_at<T>(j)] = A[j];
+      top = fmax(top, A[j]);
+    }
+    top = post_wave_max<W>(top);
+    if ((u & (W - 1)) == 0) wave_top[i & 1][wave] = top;
+    X += x;
+    __syncthreads();
+  }
+  // Z: the thread's 16 values ascending, the butterfly over the wave, the waves joined
+  double z = A[0];
+#pragma unroll
+  for (int j = 1; j < 16; j++) z = z + A[j];
+  z = post_wave_sum<W>(z);
+  if ((u & (W - 1)) == 0) wave_z[wave] = z;
+  __syncthreads();
+  if (u == 0) {
+    a.out_status[rd] = NVK_DEC_OK;
+    a.out_z[2 * rd] = post_join_sum<NW>(wave_z, 1);
+    a.out_z[2 * rd + 1] = (double)X;
+  }
+}
+
+// (two waves per SIMD asked for: with the row in flight across the emissions the compiler otherwise takes 266 registers
+// and one)
+template <int K>
+__global__ __launch_bounds__((1 << (2 * K)) / 16) __attribute__((amdgpu_waves_per_eu(2))) void
+posterior_backward_kernel(PostArgs a) {
+  constexpr int S = 1 << (2 * K), T = S / 16, Q = S / 4;
+  constexpr int W = T < 64 ? T : 64, NW = T / W;
+  __shared__ __attribute__((aligned(16))) double G4[2][Q + (Q >> 4) * POST_PAD + POST_PAD];  // w_step * G4
+  __shared__ __attribute__((aligned(16))) double G16[2][T + (T >> 4) * POST_PAD + POST_PAD];  // w_skip * G16
+  __shared__ double wave_top[2][NW];     // per wave the largest B of the event
+  __shared__ double wave_cls[2][4][NW];  // per wave the four class sums of the event
+  const int u = threadIdx.x, wave = u / W;
+  const int64_t rd = (int64_t)a.r0 + blockIdx.x;
+  const int64_t ev0 = a.ev_off[rd];
+  const int E = (int)(a.ev_off[rd + 1] - ev0);
+  if (post_status(a, rd, E) != 0) return;
+  const double *lev = a.level + ev0;
+  const double w_stay = a.w_stay, w_step = a.w_step, w_skip = a.w_skip;
+  const double *store = a.rows + (ev0 - a.ev_off[a.r0]) * (int64_t)S + 2 * u;
+  double *marg = a.out_marg + 4 * ev0;
+  // the letter at `pos`: the thread's 16 states differ in the last two letters only
+  const int mode = a.pos == K - 1 ? 0 : a.pos == K - 2 ? 1 : 2;
+  const int own = (a.pos < K - 2) ? ((16 * u) >> (2 * (K - 1 - a.pos))) & 3 : 0;  // mode 2: the letter of all 16
+
+  double B[16], mean[16], ac[16], mc[16];
+#pragma unroll
+  for (int j = 0; j < 16; j++) {
+    mean[j] = a.mean[16 * u + j];
+    ac[j] = a.ac[16 * u + j];
+    mc[j] = a.mc[16 * u + j];
+    B[j] = 1.0;
+  }
+  for (int i = E - 1; i >= 0; i--) {
+    const int p = i & 1;
+    const double *in = store + (int64_t)i * S;
+    // (the event's row is asked for first and used last: the emissions below run while it arrives)
+    double av[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) av[j] = in[post_store_at<T>(j)];
+    double Wv[16];
+    if (i > 0) {
+      double top = B[0];
+#pragma unroll
+      for (int j = 1; j < 16; j++) top = fmax(top, B[j]);
+      top = post_wave_max<W>(top);
+      if ((u & (W - 1)) == 0) wave_top[p][wave] = top;
+      const double e = lev[i];
+#pragma unroll
+      for (int j = 0; j < 16; j++) Wv[j] = B[j] * post_emission(e, mean[j], ac[j], mc[j]);
+      double g4[4];
+#pragma unroll
+      for (int g = 0; g < 4; g++) g4[g] = ((Wv[4 * g] + Wv[4 * g + 1]) + Wv[4 * g + 2]) + Wv[4 * g + 3];
+      const double g16 = ((g4[0] + g4[1]) + g4[2]) + g4[3];
+#pragma unroll
+      for (int g = 0; g < 4; g++) G4[p][post_at(4 * u) + g] = w_step * g4[g];
+      G16[p][post_at(u)] = w_skip * g16;
+    }
+    double ab[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) ab[j] = av[j] * B[j];
+    // the class sums of the thread's states, ascending inside a class
+    double cls[4];
+    if (mode == 0) {
+#pragma unroll
+      for (int x = 0; x < 4; x++) cls[x] = ((ab[x] + ab[4 + x]) + ab[8 + x]) + ab[12 + x];
+    } else if (mode == 1) {
+#pragma unroll
+      for (int x = 0; x < 4; x++) cls[x] = ((ab[4 * x] + ab[4 * x + 1]) + ab[4 * x + 2]) + ab[4 * x + 3];
+    } else {
+      double all = ab[0];
+#pragma unroll
+      for (int j = 1; j < 16; j++) all = all + ab[j];
+#pragma unroll
+      for (int x = 0; x < 4; x++) cls[x] = (x == own) ? all : 0.0;
+    }
+#pragma unroll
+    for (int d = W / 2; d >= 1; d >>= 1) {
+      double o[4];
+#pragma unroll
+      for (int x = 0; x < 4; x++) o[x] = __shfl_xor(cls[x], d, 64);
+#pragma unroll
+      for (int x = 0; x < 4; x++) cls[x] = cls[x] + o[x];
+    }
+    if ((u & (W - 1)) == 0) {
+#pragma unroll
+      for (int x = 0; x < 4; x++) wave_cls[p][x][wave] = cls[x];
+    }
+    __syncthreads();
+    if (u == 0) {
+      double C[4];
+#pragma unroll
+      for (int x = 0; x < 4; x++) C[x] = post_join_sum<NW>(&wave_cls[p][x][0], 1);
+      const double total = ((C[0] + C[1]) + C[2]) + C[3];
+#pragma unroll
+      for (int x = 0; x < 4; x++) marg[4 * (int64_t)i + x] = C[x] / total;
+    }
+    if (i > 0) {
+      const int y = __builtin_amdgcn_frexp_exp(post_join_max<NW>(wave_top[p]));
+#pragma unroll
+      for (int j = 0; j < 16; j++) {
+        const int s = 16 * u + j;
+        const double t = (G4[p][post_at(s & (Q - 1))] + w_stay * Wv[j]) + G16[p][post_at(s & (T - 1))];
+        B[j] = ldexp(t, -y);
+      }
+    }
+  }
+}
+
+template <int K>
+void launch_forward(const PostArgs &a, int n, hipStream_t stream) {
+  constexpr int T = (1 << (2 * K)) / 16;
+  hipLaunchKernelGGL(posterior_forward_kernel<K>, dim3((unsigned)n), dim3(T), 0, stream, a);
+}
+template <int K>
+void launch_backward(const PostArgs &a, int n, hipStream_t stream) {
+  constexpr int T = (1 << (2 * K)) / 16;
+  hipLaunchKernelGGL(posterior_backward_kernel<K>, dim3((unsigned)n), dim3(T), 0, stream, a);
+}
+
+void launch_sweep(bool forward, int k, const PostArgs &a, int n, hipStream_t stream) {
+  switch (k) {
+    case 2: forward ? launch_forward<2>(a, n, stream) : launch_backward<2>(a, n, stream); break;
+    case 3: forward ? launch_forward<3>(a, n, stream) : launch_backward<3>(a, n, stream); break;
+    case 4: forward ? launch_forward<4>(a, n, stream) : launch_backward<4>(a, n, stream); break;
+    case 5: forward ? launch_forward<5>(a, n, stream) : launch_backward<5>(a, n, stream); break;
+    default: forward ? launch_forward<6>(a, n, stream) : launch_backward<6>(a, n, stream); break;
+  }
+}
+
+}  // namespace
+
+extern "C" int nvk_kmer_posterior_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_events, const double *level,
+                                      const int64_t *ev_off, int k, int pos, const double *mean, const double *ac,
+                                      const double *mc, double w_stay, double w_step, double w_skip,
+                                      const int32_t *status_in, double *out_marg, double *out_z, int32_t *out_status,
+                                      int64_t *out_parts, double *out_ms) {
+  const char *what = "nvk_kmer_posterior_dev";
+  if (out_parts) *out_parts = 0;
+  if (out_ms) out_ms[0] = out_ms[1] = 0.0;
+  if (!ctx) {
+    nvk_set_error("%s: ctx is NULL", what);
+    return NVK_ERR_INVALID;
+  }
+  if (k < 2 || k > 6) {
+    nvk_set_error("%s: k %d is outside 2..6", what, k);
+    return NVK_ERR_UNSUPPORTED;
+  }
+  if (pos < 0 || pos >= k) {
+    nvk_set_error("%s: pos %d is outside 0..k-1 (k %d)", what, pos, k);
+    return NVK_ERR_INVALID;
+  }
+  if (n_reads < 0 || n_reads > 0x7fffffff || total_events < 0) {
+    nvk_set_error("%s: n_reads %lld or total_events %lld out of range", what, (long long)n_reads,
+                  (long long)total_events);
+    return NVK_ERR_INVALID;
+  }
+  const double weights[3] = {w_stay, w_step, w_skip};
+  for (double w : weights)
+    if (!(w > 0.0 && w <= 1.0)) {
+      nvk_set_error("%s: w_stay %g, w_step %g or w_skip %g is not a finite value in (0, 1]", what, w_stay, w_step,
+                    w_skip);
+      return NVK_ERR_INVALID;
+    }
+  if (!((w_stay > w_step ? w_stay : w_step) >= POST_MIN_MOVE)) {
+    nvk_set_error("%s: w_stay %g and w_step %g are both below 2^-10", what, w_stay, w_step);
+    return NVK_ERR_INVALID;
+  }
+  if (!ev_off || (total_events > 0 && !level) || !mean || !ac || !mc) {
+    nvk_set_error("%s: NULL levels, offsets or table", what);
+    return NVK_ERR_INVALID;
+  }
+  NVK_HIP(hipSetDevice(ctx->device));
+  std::vector<int64_t> eoff;
+  int rc = nvk_fetch_offsets(ctx, "event", ev_off, n_reads, eoff, "total_events", total_events);
+  if (rc) return rc;
+  for (int64_t r = 0; r < n_reads; r++)
+    if (eoff[r + 1] - eoff[r] > POST_MAX_EVENTS) {
+      nvk_set_error("%s: read %lld has %lld events, above %d", what, (long long)r, (long long)(eoff[r + 1] - eoff[r]),
+                    POST_MAX_EVENTS);
+      return NVK_ERR_INVALID;
+    }
+  if (n_reads == 0) return NVK_OK;
+  if ((total_events > 0 && !out_marg) || !out_z || !out_status) {
+    nvk_set_error("%s: NULL output", what);
+    return NVK_ERR_INVALID;
+  }
+  // parts of reads whose rows fit the cap (a read larger than the cap on its own makes a part of one; a read the
+  // kernels skip takes its rows all the same: its status is on the device).  A context without a limit stops at
+  // 16 GiB: at k = 6 a read of 816 events takes 26.7 MB, so 4 GiB would hold 160 reads, fewer workgroups than the
+  // device has CUs, and 16 GiB holds 640, two for every CU and more
+  int64_t cap_b = nvk_spill_cap(ctx, WS_SEED_TB);
+  if (ctx->ws_limit <= 0 && cap_b > ((int64_t)16 << 30)) cap_b = (int64_t)16 << 30;
+  const int64_t S = (int64_t)1 << (2 * k);
+  const int64_t cap_rows = cap_b / (8 * S);
+  std::vector<int64_t> cut(1, 0);
+  int64_t need_rows = 1;
+  for (int64_t r = 0; r < n_reads; r++) {
+    const int64_t c0 = cut.back();
+    if (r > c0 && eoff[r + 1] - eoff[c0] > cap_rows) {
+      need_rows = need_rows > eoff[r] - eoff[c0] ? need_rows : eoff[r] - eoff[c0];
+      cut.push_back(r);
+    }
+  }
+  need_rows = need_rows > eoff[n_reads] - eoff[cut.back()] ? need_rows : eoff[n_reads] - eoff[cut.back()];
+  cut.push_back(n_reads);
+  // (the seed aligner's traceback workspace serves, as for the Viterbi store: the three never run at once on a context)
+  if ((rc = nvk_ws_reserve(ctx, WS_SEED_TB, (size_t)need_rows * (size_t)S * 8))) return rc;
+  PostArgs a;
+  a.level = level;
+  a.ev_off = ev_off;
+  a.mean = mean;
+  a.ac = ac;
+  a.mc = mc;
+  a.status_in = status_in;
+  a.w_stay = w_stay;
+  a.w_step = w_step;
+  a.w_skip = w_skip;
+  a.out_marg = out_marg;
+  a.out_z = out_z;
+  a.out_status = out_status;
+  a.rows = (double *)ctx->ws[WS_SEED_TB];
+  a.pos = pos;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  if (out_ms)
+    for (hipEvent_t &e : ev) NVK_HIP(hipEventCreate(&e));
+  for (size_t c = 0; c + 1 < cut.size(); c++) {
+    a.r0 = (int)cut[c];
+    const int n = (int)(cut[c + 1] - cut[c]);
+    if (out_ms) NVK_HIP(hipEventRecord(ev[0], ctx->stream));
+    launch_sweep(true, k, a, n, ctx->stream);
+    NVK_HIP(hipGetLastError());
+    if (out_ms) NVK_HIP(hipEventRecord(ev[1], ctx->stream));
+    launch_sweep(false, k, a, n, ctx->stream);
+    NVK_HIP(hipGetLastError());
+    if (out_ms) {
+      NVK_HIP(hipEventRecord(ev[2], ctx->stream));
+      NVK_HIP(hipEventSynchronize(ev[2]));
+      float ms = 0.f;
+      NVK_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+      out_ms[0] += (double)ms;
+      NVK_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
+      out_ms[1] += (double)ms;
+    }
+  }
+  NVK_HIP(hipStreamSynchronize(ctx->stream));
+  if (out_ms)
+    for (hipEvent_t e : ev) NVK_HIP(hipEventDestroy(e));
+  if (out_parts) *out_parts = (int64_t)cut.size() - 1;
+  return NVK_OK;
+}

@@ -12,7 +12,12 @@ starts from.  On the device:
    (``locate.rescale_pooled_dev``).  A read with fewer than ``min_events`` events or a zero MAD is ``DEC_NO_EVENTS``;
 3. the operator (``nvk_viterbi_decode_dev``, contract in include/nadavca_hip.h): per read the best path's score, the
    sequence it spells and per base the first event of the state that owns it;
-4. a compaction of the operator's outputs, which it lays out by capacity, in torch.
+4. a compaction of the operator's outputs, which it lays out by capacity, in torch;
+5. with ``qualities=True`` the forward-backward operator (``nvk_kmer_posterior_dev``): per event the posterior of each
+   letter at the state's ``central`` position, summed over ALL paths, and log Z per read.  A base takes the largest
+   posterior of its own letter over its dwell (``base_post``), and ``quality`` is its Phred value cut to 0..60, counted
+   on a fixed table of thresholds.  The scale is ordered, not calibrated: the transition weights are guesses, and on the
+   simulated reads it is over-confident above Q20.
 
 So one operator stands where ``signal_locate_batch`` and ``signal_map_batch`` do on that route:
 
@@ -43,15 +48,40 @@ class DecodeBatch:
     (the best path's log-likelihood per event, NaN unless decoded), ``seq_off`` (int64, n + 1).  Flat: ``sequence``
     (int32 base codes, read j at [seq_off[j], seq_off[j+1])) and ``map_base`` / ``map_sig`` / ``map_off`` in the layout
     of ``ReadBatch`` — one row per base with an event, bases ascending, ``map_sig`` the first sample of that event; the
-    first ``central`` and the last k - 1 - ``central`` bases of a read and a base a skip passes have none."""
+    first ``central`` and the last k - 1 - ``central`` bases of a read and a base a skip passes have none.
+    With ``qualities=True`` (else None): ``loglik`` per read (log Z per event, NaN unless decoded; ``score - loglik`` is
+    the log posterior of the whole Viterbi path per event) and, flat and aligned with ``sequence``, ``base_post`` (f64:
+    the largest posterior of the base's letter over its dwell; a base a skip passes takes the smaller of its two
+    neighbours' values, the bases before the first and after the last base with an event the nearest one's) and
+    ``quality`` (uint8, 0..60: the number of thresholds 1 - 10^(-j/10), j = 1..60, that ``base_post`` reaches)."""
 
-    def __init__(self, status, n_events, n_bases, score, seq_off, sequence, map_base, map_sig, map_off, parts=0):
+    def __init__(self, status, n_events, n_bases, score, seq_off, sequence, map_base, map_sig, map_off, parts=0,
+                 loglik=None, base_post=None, quality=None, post_parts=0):
         self.status, self.n_events, self.n_bases, self.score = status, n_events, n_bases, score
         self.seq_off, self.sequence = seq_off, sequence
         self.map_base, self.map_sig, self.map_off = map_base, map_sig, map_off
         self.parts = parts   # parts the operator cut the batch into under the workspace cap
+        self.loglik, self.base_post, self.quality = loglik, base_post, quality
+        self.post_parts = post_parts   # ... and the forward-backward operator its own
         self.n = int(status.size)
         self.n_decoded = int((status == DEC_OK).sum())
+
+    def write_fastq(self, path, names=None):
+        """The decoded reads as FASTQ: letters ``ACGT``, quality character ``chr(33 + quality)``; a read that did not
+        decode is left out.  ``names``: one per read of the batch (default ``read_<index>``).  -> reads written"""
+        if self.quality is None:
+            raise ValueError('DecodeBatch.write_fastq: no qualities; call decode_batch(..., qualities=True)')
+        if names is not None and len(names) != self.n:
+            raise ValueError('DecodeBatch.write_fastq: %d names for %d reads' % (len(names), self.n))
+        letters = np.frombuffer(b'ACGT', dtype=np.uint8)[self.sequence].tobytes().decode('ascii')
+        marks = (self.quality + np.uint8(33)).tobytes().decode('ascii')
+        decoded = np.nonzero(self.status == DEC_OK)[0]
+        with open(path, 'w') as out:
+            for r in decoded:
+                lo, hi = int(self.seq_off[r]), int(self.seq_off[r + 1])
+                out.write('@%s\n%s\n+\n%s\n' % (names[r] if names is not None else 'read_%d' % r, letters[lo:hi],
+                                                marks[lo:hi]))
+        return int(decoded.size)
 
     def read_batch(self, rb):
         """A new ``ReadBatch`` with ``rb``'s signals, the decoded sequences and these tables.  A read that is not
@@ -60,6 +90,11 @@ class DecodeBatch:
             raise ValueError('DecodeBatch.read_batch: the batch holds %d reads, the decode %d' % (rb.n, self.n))
         return ReadBatch(rb.raw_signal, rb.sig_off, self.sequence, self.seq_off, self.map_base, self.map_sig,
                          self.map_off)
+
+
+# quality[b] = the number of these that base_post[b] reaches.  Computed once, here, in numpy f64: the device only
+# compares against them, so a host restatement with the same table agrees in every integer
+PHRED_THRESHOLDS = 1.0 - np.power(10.0, -np.arange(1, 61, dtype=np.float64) / 10.0)
 
 
 def transition_costs(p_stay, p_skip):
@@ -100,6 +135,47 @@ def traceback_bytes(n_events, k):
     """Bytes of the operator's traceback store for reads of ``n_events`` events (numpy): 4^k / 2 per event but the
     first"""
     return int(np.maximum(np.asarray(n_events, dtype=np.int64) - 1, 0).sum()) * (4 ** k // 2)
+
+
+def transition_weights(p_stay, p_skip):
+    """-> (w_stay, w_step, w_skip): the very numbers whose logs ``transition_costs`` takes"""
+    return p_stay, 1.0 - p_stay - p_skip, p_skip
+
+
+def row_store_bytes(n_events, k):
+    """Bytes of the forward-backward operator's row store for reads of ``n_events`` events (numpy): 8 * 4^k per event"""
+    return int(np.asarray(n_events, dtype=np.int64).sum()) * 8 * 4 ** k
+
+
+def base_qualities_dev(marg, z, ok, n_ev, ev_off, map_off, owner, keep, sequence, event):
+    """The forward-backward operator's outputs as per-read and per-base values, in torch on the device -> (loglik per
+    read, base_post and quality per base).  ``owner`` / ``keep`` / ``event``: per base its read, whether it has an event,
+    and that event; ``map_off``: the reads' offsets into the bases with an event (the rows)."""
+    import torch
+    dev = marg.device
+    loglik = torch.where(ok, (torch.log(z[:, 0]) + z[:, 1] * math.log(2.0)) / torch.clamp(n_ev, min=1).to(torch.float64),
+                         torch.full_like(z[:, 0], float('nan')))
+    n_rows = int(map_off[-1])
+    if n_rows == 0:
+        return loglik, torch.zeros(0, dtype=torch.float64, device=dev), torch.zeros(0, dtype=torch.uint8, device=dev)
+    # per event of a decoded read the row whose dwell it lies in: the rows' first events ascend, and a read's first
+    # event is a row's
+    first = torch.zeros(int(ev_off[-1]), dtype=torch.int64, device=dev)
+    first[ev_off[:-1][owner[keep]] + event[keep]] = 1
+    used = ok[seg_index(ev_off)[0]]
+    row_of = (torch.cumsum(first, 0) - 1)[used]
+    value = marg[used].gather(1, sequence[keep][row_of].to(torch.int64)[:, None])[:, 0]
+    rows = torch.zeros(n_rows, dtype=torch.float64, device=dev).scatter_reduce(0, row_of, value, 'amax',
+                                                                              include_self=False)
+    # a base without an event: the rows before and after it in its own read
+    before = torch.cumsum(keep.to(torch.int64), 0) - 1
+    after = before + 1
+    has_before, has_after = before >= map_off[:-1][owner], after < map_off[1:][owner]
+    v_before, v_after = rows[torch.clamp(before, min=0)], rows[torch.clamp(after, max=n_rows - 1)]
+    base_post = torch.where(keep | ~has_after, v_before,
+                            torch.where(has_before, torch.minimum(v_before, v_after), v_after))
+    thresholds = torch.from_numpy(PHRED_THRESHOLDS).to(dev)
+    return loglik, base_post, torch.searchsorted(thresholds, base_post, right=True).to(torch.uint8)
 
 
 class DecodeStages:
@@ -143,7 +219,7 @@ def decode_stages(read_batch, kmer_model, p_stay, p_skip, sigma_scale, min_event
 
 
 def decode_batch(read_batch, kmer_model=defaults.KMER_MODEL_FILE, p_stay=0.7, p_skip=0.01, sigma_scale=1.0,
-                 min_events=32, window=2, threshold=5.0, var_floor=0.02, context=None):
+                 min_events=32, window=2, threshold=5.0, var_floor=0.02, context=None, qualities=False):
     """A base sequence and its base -> sample table for every read of ``read_batch`` from its raw signal alone (module
     docstring); any sequence or table the batch carries is ignored.  ``kmer_model``: a KmerModel or a path (4 letters,
     k in 2..6, else ValueError); ``context``: the context a model loaded from a path is made on (default: the
@@ -151,7 +227,9 @@ def decode_batch(read_batch, kmer_model=defaults.KMER_MODEL_FILE, p_stay=0.7, p_
     ``sigma_scale``: the model's sigma is multiplied by it; ``min_events`` (>= 1): a read with fewer is not decoded;
     ``window``, ``threshold``, ``var_floor``: the event detector's.  The defaults are uncalibrated: they are the values
     at which the simulated reads of the test suite (dwell 3-17 samples, noise 0.35, the packaged 6-mer table) decode
-    best (the batch of the quality test is the tuning set), not values fitted to real data.  -> DecodeBatch."""
+    best (the batch of the quality test is the tuning set), not values fitted to real data.  ``qualities``: also run
+    the forward-backward operator and fill ``loglik``, ``base_post`` and ``quality`` (stage 5 of the module docstring);
+    the other results do not change.  -> DecodeBatch."""
     import torch
     if isinstance(kmer_model, (str, bytes)) or hasattr(kmer_model, '__fspath__'):
         from .kmer_model import load_kmer_model as load_on
@@ -177,5 +255,15 @@ def decode_batch(read_batch, kmer_model=defaults.KMER_MODEL_FILE, p_stay=0.7, p_
     map_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev),
                          torch.cumsum(torch.bincount(k_owner, minlength=rb.n), 0)])
     host = lambda t: t.cpu().numpy()
+    extra = {}
+    if qualities:
+        from .device import kmer_posterior_dev
+        marg, z, _, post_parts = kmer_posterior_dev(
+            kmer_model.context, st.scaled, st.ev_off, kmer_model.get_k(), kmer_model.get_central_position(), st.mean,
+            st.ac, st.mc, *transition_weights(p_stay, p_skip), st.status_in)
+        loglik, base_post, quality = base_qualities_dev(marg, z, ok, n_ev, st.ev_off, map_off, owner, keep, sequence,
+                                                        event)
+        extra = dict(loglik=host(loglik), base_post=host(base_post), quality=host(quality), post_parts=post_parts)
     return DecodeBatch(host(status), host(st.hit[:, 1]), host(st.hit[:, 2]), host(score), host(seq_off),
-                       host(sequence), host(inner[keep].to(torch.int32)), host(map_sig), host(map_off), st.parts)
+                       host(sequence), host(inner[keep].to(torch.int32)), host(map_sig), host(map_off), st.parts,
+                       **extra)

@@ -1105,3 +1105,29 @@ def viterbi_decode_dev(context, level, ev_off, k, central, mean, ac, mc, l_stay,
                                           st, total_cap, _dp(cap_off), _dp(hit), _dp(score), _dp(seq),
                                           _dp(base_event), C.byref(parts)), 'nvk_viterbi_decode_dev')
     return hit, score[:n], seq[:total_cap], base_event[:total_cap], int(parts.value)
+
+
+def kmer_posterior_dev(context, level, ev_off, k, pos, mean, ac, mc, w_stay, w_step, w_skip, status_in, timing=False):
+    """The forward-backward sums of every read's events (``level`` / ``ev_off``, rescaled) over the 4^k states of the
+    table (``mean``, ``ac``, ``mc``), nvk_kmer_posterior_dev.  Device tensors; ``pos``: the letter position of the state
+    the marginals are taken over (first base = 0); ``w_stay`` / ``w_step`` / ``w_skip``: the moves' linear weights;
+    ``status_in``: int32 per read or None.
+    -> (marg f64 (events, 4): per event the posterior of each letter at ``pos``; z f64 (n, 2): the scaled sum of the
+    last forward row and its binary exponent, log Z = log(z[:, 0]) + z[:, 1] ln 2; status int32 (n,); the number of
+    parts the row store was cut into) and, with ``timing``, the milliseconds of the forward and backward launches."""
+    import torch
+    lib = _lib.load()
+    dev = ev_off.device
+    n, n_ev = int(ev_off.numel()) - 1, int(level.numel())
+    marg = torch.zeros((max(n_ev, 1), 4), dtype=torch.float64, device=dev)
+    z = torch.zeros((max(n, 1), 2), dtype=torch.float64, device=dev)
+    status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    one = lambda t: t if t.numel() else torch.zeros(1, dtype=t.dtype, device=dev)
+    st = _dp(status_in) if status_in is not None and n > 0 else C.c_void_p(0)
+    parts, ms = C.c_int64(0), (C.c_double * 2)(0.0, 0.0)
+    _lib.check(lib.nvk_kmer_posterior_dev(context.handle, n, n_ev, _dp(one(level)), _dp(ev_off), int(k), int(pos),
+                                          _dp(mean), _dp(ac), _dp(mc), float(w_stay), float(w_step), float(w_skip), st,
+                                          _dp(marg), _dp(z), _dp(status), C.byref(parts), ms if timing else None),
+               'nvk_kmer_posterior_dev')
+    out = (marg[:n_ev], z[:n], status[:n], int(parts.value))
+    return out + ((float(ms[0]), float(ms[1])),) if timing else out

@@ -1,0 +1,143 @@
+"""nvk_kmer_posterior_dev against its CPU restatement (tests/host_shims/posterior_host.cpp: the full matrices, the
+sums over all states on arrays), bit for bit in every f64 and i32, for k = 2..6 and so for every workgroup size of the
+two sweeps (1, 4, 16, 64 and 256 threads).  The cases are tests/decode_ref.py's (E = 0, 1, 2, 3, 64, 65 and 300, a
+``status_in`` entry) with ``pos`` 0, ``central`` and k - 1, the three extreme cases of tests/posterior_ref.py, and at
+k = 6 the packaged table and 64 simulated reads, whole and cut into parts by the workspace limit."""
+import math
+
+import numpy as np
+import pytest
+
+import decode_ref as D
+import posterior_ref as P
+import signal_map_ref as R
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope='module')
+def host(tmp_path_factory):
+    return P.build_host(tmp_path_factory.mktemp('posterior_host'))
+
+
+@pytest.fixture(scope='module')
+def ctx():
+    from nadavca_amd import _lib
+    return _lib.default_context()
+
+
+@pytest.fixture(scope='module')
+def simulated(host, tmp_path_factory):
+    """-> (the k = 6 case, the shim's results for it at pos = central)"""
+    case, _ = D.simulated_case(R.build_host(tmp_path_factory.mktemp('map_host')))
+    return case, P.run_host(host, case, case['central'], threads=8)
+
+
+def bits(x):
+    return np.ascontiguousarray(x, dtype=np.float64).view(np.int64)
+
+
+def run_dev(ctx, case, pos, **over):
+    """-> (marg, z, status, parts) as numpy arrays"""
+    import torch
+    from nadavca_amd.device import kmer_posterior_dev
+    dev = torch.device('cuda', ctx.device)
+    c = dict(case, **over)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    w = c['w'] if 'w' in c else tuple(math.exp(x) for x in c['costs'])
+    st = None if c['status_in'] is None else t(c['status_in'])
+    out = kmer_posterior_dev(ctx, t(c['level']), t(c['ev_off']), c['k'], pos, t(c['mean']), t(c['ac']), t(c['mc']), *w,
+                             st)
+    return tuple(x.cpu().numpy() for x in out[:3]) + (out[3],)
+
+
+def assert_same(got, want, name):
+    for what, a, b in zip(('marg', 'z'), got[:2], want[:2]):
+        assert a.shape == b.shape, (name, what, a.shape, b.shape)
+        bad = np.argwhere(bits(a) != bits(b))
+        assert bad.size == 0, (name, what, bad.shape[0], bad[:5].tolist())
+    assert np.array_equal(got[2], want[2]), (name, 'status')
+
+
+@pytest.mark.parametrize('k', [2, 3, 4, 5, 6])
+def test_constructed_cases(ctx, host, k):
+    for name, case in D.kernel_cases(k):
+        for pos in sorted({0, case['central'], k - 1}):
+            got = run_dev(ctx, case, pos)
+            assert_same(got, P.run_host(host, case, pos), '%s pos %d' % (name, pos))
+            assert got[3] == 1
+    name, case = D.kernel_cases(k)[0]
+    assert np.diff(case['ev_off']).tolist() == D.KERNEL_LENGTHS + [33]
+    marg, z, status, _ = run_dev(ctx, case, 0)
+    assert status.tolist() == [D.DEC_NO_EVENTS] + [0] * len(D.KERNEL_LENGTHS[1:]) + [7]
+    assert (z[[0, -1]] == 0.0).all() and (z[1:-1, 0] > 0.0).all() and (marg[-33:] == 0.0).all()
+    total = ((marg[:-33, 0] + marg[:-33, 1]) + marg[:-33, 2]) + marg[:-33, 3]
+    assert (np.abs(total - 1.0) <= 4 * np.finfo(np.float64).eps).all()
+
+
+@pytest.mark.parametrize('pos', [0, 1])
+def test_extreme_cases(ctx, host, pos):
+    for name, case in P.extreme_cases():
+        got = run_dev(ctx, case, pos)
+        assert_same(got, P.run_host(host, case, pos), name)
+        assert np.isfinite(got[0]).all() and np.isfinite(got[1]).all()
+    cases = dict(P.extreme_cases())
+    assert P.log_z(run_dev(ctx, cases['narrow sigma'], pos)[1])[0] < -1100.0
+    assert P.log_z(run_dev(ctx, cases['large ac'], pos)[1])[0] > 710.0
+
+
+def test_packaged_table_and_simulated_reads(ctx, simulated):
+    case, want = simulated
+    assert case['k'] == 6 and case['ev_off'].size - 1 == 64 and (want[2] == 0).all()
+    got = run_dev(ctx, case, case['central'])
+    assert_same(got, want, 'k 6')
+    assert got[3] == 1
+
+
+def test_small_workspace_limits_change_nothing(ctx, simulated):
+    """The k = 6 batch under limits that cut it into at least three and at least seven parts, and under one smaller
+    than its largest read's rows (every read a part of its own): the same bits as in one piece."""
+    case, want = simulated
+    per_read = np.diff(case['ev_off']) * (8 * 4 ** 6)
+    try:
+        for limit, least in ((int(per_read.sum()) // 3, 3), (int(per_read.sum()) // 7, 7), (int(per_read.max()) - 8, 64)):
+            ctx.set_workspace_limit(limit)
+            got = run_dev(ctx, case, case['central'])
+            assert got[3] >= least and (least < 64 or got[3] == 64), (limit, got[3])
+            assert_same(got, want, 'limit %d' % limit)
+    finally:
+        ctx.set_workspace_limit(0)
+
+
+def test_bad_arguments(ctx):
+    from nadavca_amd._lib import NadavcaHipError
+    name, case = D.kernel_cases(3)[0]
+    run_dev(ctx, case, 1)
+    big = dict(case, k=7, mean=np.zeros(4 ** 7), ac=np.zeros(4 ** 7), mc=np.ones(4 ** 7))
+    with pytest.raises(NadavcaHipError, match='outside 2..6'):
+        run_dev(ctx, big, 0)
+    with pytest.raises(NadavcaHipError):
+        run_dev(ctx, dict(big, k=1), 0)
+    for pos in (-1, 3):
+        with pytest.raises(ValueError, match='pos'):
+            run_dev(ctx, case, pos)
+    good = tuple(math.exp(x) for x in case['costs'])
+    for at in range(3):
+        for bad in (0.0, 1.5, float('nan'), -0.25, float('inf')):
+            w = list(good)
+            w[at] = bad
+            with pytest.raises(ValueError):
+                run_dev(ctx, case, 1, w=tuple(w))
+    with pytest.raises(ValueError, match='2\\^-10'):
+        run_dev(ctx, case, 1, w=(2.0 ** -11, 2.0 ** -11, 0.5))
+    run_dev(ctx, case, 1, w=(2.0 ** -10, 2.0 ** -11, 0.5))
+    ev_off = case['ev_off'].copy()
+    ev_off[2] = ev_off[3] + 1               # descending offsets
+    with pytest.raises(ValueError):
+        run_dev(ctx, case, 1, ev_off=ev_off)
+
+
+def test_no_reads(ctx):
+    name, case = D.kernel_cases(3)[0]
+    marg, z, status, parts = run_dev(ctx, case, 1, level=np.zeros(0), ev_off=np.zeros(1, np.int64), status_in=None)
+    assert marg.shape == (0, 4) and z.shape == (0, 2) and status.size == 0 and parts == 0

@@ -4,8 +4,11 @@ normalisation, event detection, the rescale onto the table's means, the operator
 and the walk back of every part under the workspace cap) — the operator alone in cell updates per second (4^k per
 event), the traceback store's bytes and parts, the whole call, and the chain decode_batch -> ``SeedAligner(k=10)`` ->
 align_signal_batch beside ``align_signal_batch`` with the same aligner from the simulator's own sequences and tables.
-HIP events after a warm-up; the figures are the median of ``--reps`` runs.
-`python tools/bench_decode.py [N] [--genome L] [--reps R]`."""
+HIP events after a warm-up; the figures are the median of ``--reps`` runs.  ``--qualities``: also the forward-backward
+operator of ``decode_batch(qualities=True)`` (``nvk_kmer_posterior_dev``) -- its forward and backward launches apart,
+its parts and row-store bytes with the bytes-over-bandwidth floor -- and the whole call with qualities beside the plain
+one of the same session.
+`python tools/bench_decode.py [N] [--genome L] [--reps R] [--qualities] [--limit-gib G]`."""
 import argparse
 import inspect
 import os
@@ -17,7 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 from nadavca_amd import decode, decode_batch, defaults, synthetic  # noqa: E402
 from nadavca_amd.align_signal import align_signal_batch  # noqa: E402
-from nadavca_amd.device import viterbi_decode_dev  # noqa: E402
+from nadavca_amd.device import kmer_posterior_dev, viterbi_decode_dev  # noqa: E402
 from nadavca_amd.kmer_model import KmerModel  # noqa: E402
 from nadavca_amd.readbatch import ReadBatch  # noqa: E402
 from nadavca_amd.seedalign import SeedAligner  # noqa: E402
@@ -26,10 +29,14 @@ parser = argparse.ArgumentParser()
 parser.add_argument('n_reads', nargs='?', type=int, default=10000)
 parser.add_argument('--genome', type=int, default=100000)
 parser.add_argument('--reps', type=int, default=3)
+parser.add_argument('--qualities', action='store_true')
+parser.add_argument('--limit-gib', type=float, default=0.0, help='workspace limit of the context (0: the default caps)')
 opts = parser.parse_args()
 
 km = KmerModel.load_from_hdf5(defaults.KMER_MODEL_FILE)
 ctx = km.context
+if opts.limit_gib > 0:
+    ctx.set_workspace_limit(int(opts.limit_gib * 2 ** 30))
 dev = torch.device('cuda', ctx.device)
 rb, _, genome = synthetic.make_read_batch(opts.n_reads, synthetic.load_model_arrays(), seed=7,
                                           genome_length=opts.genome)
@@ -67,7 +74,16 @@ def operator_alone(st):
                                             st.ac, st.mc, *st.costs, st.status_in, st.cap_off))[1]
 
 
+def posterior_alone(st):
+    """-> (ms of the call, (ms of the forward launches, ms of the backward launches), parts)"""
+    out, ms = timed(lambda: kmer_posterior_dev(ctx, st.scaled, st.ev_off, km.get_k(), km.get_central_position(), st.mean,
+                                               st.ac, st.mc, *decode.transition_weights(args[0], args[1]),
+                                               st.status_in, timing=True))
+    return ms, out[4], out[3]
+
+
 whole = lambda: decode_batch(bare, kmer_model=km)
+whole_q = lambda: decode_batch(bare, kmer_model=km, qualities=True)
 
 
 def chain():
@@ -78,7 +94,9 @@ def chain():
 staged()   # warm-up: workspaces, the allocator's blocks, first launches
 chain()
 align_signal_batch(None, rb, kmer_model=km, aligner=seed)
-rows = {k: [] for k in STAGES + ('operator', 'whole', 'chain', 'asb_table')}
+rows = {k: [] for k in STAGES + ('operator', 'whole', 'chain', 'asb_table', 'post', 'forward', 'backward', 'whole_q')}
+if opts.qualities:
+    whole_q()
 for _ in range(opts.reps):
     st, ms = staged()
     for k, v in zip(STAGES, ms):
@@ -90,7 +108,13 @@ for _ in range(opts.reps):
     rows['chain'].append(ms)
     a, ms = timed(lambda: align_signal_batch(None, rb, kmer_model=km, aligner=seed))
     rows['asb_table'].append(ms)
-med = {k: float(np.median(v)) for k, v in rows.items()}
+    if opts.qualities:
+        ms, (fwd, bwd), post_parts = posterior_alone(st)
+        rows['post'].append(ms)
+        rows['forward'].append(fwd)
+        rows['backward'].append(bwd)
+        rows['whole_q'].append(timed(whole_q)[1])
+med = {k: float(np.median(v)) for k, v in rows.items() if v}
 k = km.get_k()
 n_ev = st.ev_off.cpu().numpy()
 decoded = n_ev[1:] - n_ev[:-1]
@@ -111,3 +135,14 @@ print('decode_batch, the whole call                   %9.2f ms  (%.1f k reads/s;
     med['whole'], opts.n_reads / med['whole'], dec.n_decoded, dec.n_bases.sum() / max(int(dec.n_events.sum()), 1)))
 print('decode -> SeedAligner(k=10) -> align_signal    %9.2f ms  (%d aligned)' % (med['chain'], b.n_aligned))
 print('align_signal_batch, simulator\'s sequences      %9.2f ms  (%d aligned)' % (med['asb_table'], a.n_aligned))
+if opts.qualities:
+    HBM_GBS = 8000.0   # the MI355X's HBM3E peak, GB/s
+    rows_b = decode.row_store_bytes(decoded, k)
+    print('posterior operator alone, %3d part(s)          %9.2f ms  (forward launches %.2f ms, backward launches %.2f ms; '
+          '%.1f G cell updates/s each way)' % (post_parts, med['post'], med['forward'], med['backward'],
+                                               cells / med['post'] / 1e6 * 2))
+    print('    row store %.1f GB written and read back: %.1f GB/s forward, %.1f GB/s backward; floor at %.0f GB/s: %.1f ms '
+          'each way' % (rows_b / 1e9, rows_b / med['forward'] / 1e6, rows_b / med['backward'] / 1e6, HBM_GBS,
+                        rows_b / HBM_GBS / 1e6))
+    print('decode_batch(qualities=True), the whole call   %9.2f ms  (%.1f k reads/s; plain call above: %.2f ms)'
+          % (med['whole_q'], opts.n_reads / med['whole_q'], med['whole']))
