@@ -410,6 +410,21 @@ int nvk_fetch_offsets(nvk_ctx *ctx, const char *what, const int64_t *off, int64_
   return NVK_OK;
 }
 
+int check_log_costs(const char *what, const char *names, std::initializer_list<double> v) {
+  for (double c : v)
+    if (!(c <= 0.0) || c * 0.0 != 0.0) {
+      double x[4] = {0.0, 0.0, 0.0, 0.0};
+      size_t i = 0;
+      for (double d : v)
+        if (i < 4) x[i++] = d;
+      char text[192];
+      snprintf(text, sizeof(text), names, x[0], x[1], x[2], x[3]);
+      nvk_set_error("%s: %s is not a finite value <= 0", what, text);
+      return NVK_ERR_INVALID;
+    }
+  return NVK_OK;
+}
+
 int check_common(nvk_model *model, int64_t n_reads, int bandwidth, int mel) {
   if (!model) {
     nvk_set_error("model handle is NULL");

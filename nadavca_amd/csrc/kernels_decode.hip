@@ -32,18 +32,13 @@
 // -ffp-contract=off every score is the rounded operation the contract writes, on the device as on the host.
 #include <vector>
 
+#include "kmer_hmm.h"
 #include "nvk_internal.h"
+#include "part_cut.h"
 
 namespace {
 
-constexpr int DEC_MAX_EVENTS = 1 << 26;  // per read
-constexpr int DEC_PAD = 2;               // doubles of padding after every 16 states of a row in LDS
-
-struct DecodeArgs {
-  const double *level;  // the events' levels, read r at ev_off[r]
-  const int64_t *ev_off;
-  const double *mean, *ac, *mc;  // the table, f64[4^k]
-  const int32_t *status_in;      // per read or null
+struct DecodeArgs : HmmIn {
   const int64_t *cap_off;
   double l_stay, l_step, l_skip;
   int32_t *out_hit;  // 4 per read: status, events, bases, end state
@@ -56,25 +51,19 @@ struct DecodeArgs {
   int k, central;
 };
 
-__device__ __forceinline__ double dec_neg_inf() { return __longlong_as_double(0xfff0000000000000ll); }
-
-// where state s lies in a padded row
-__device__ __forceinline__ constexpr int dec_at(int s) { return s + (s >> 4) * DEC_PAD; }
-
 template <int K>
-__global__ __launch_bounds__((1 << (2 * K)) / 16) void decode_sweep_kernel(DecodeArgs a) {
-  constexpr int S = 1 << (2 * K), T = S / 16, Q = S / 4, ROW = S + T * DEC_PAD;
-  __shared__ __attribute__((aligned(16))) double row[2][ROW];
+__global__ __launch_bounds__(KmerHmm<K>::T) void decode_sweep_kernel(DecodeArgs a) {
+  constexpr int T = KmerHmm<K>::T, Q = KmerHmm<K>::Q;
+  __shared__ __attribute__((aligned(16))) double row[2][KmerHmm<K>::ROW];
   const int u = threadIdx.x;
   const int64_t rd = (int64_t)a.r0 + blockIdx.x;
   const int64_t ev0 = a.ev_off[rd];
   const int E = (int)(a.ev_off[rd + 1] - ev0);
-  int status = a.status_in ? a.status_in[rd] : 0;
-  if (status == 0 && E == 0) status = NVK_DEC_NO_EVENTS;
+  const int status = hmm_status(a, rd, E);
   if (status != 0) {
     if (u == 0) {
       *(int4 *)(a.out_hit + 4 * rd) = make_int4(status, E, 0, -1);
-      a.out_score[rd] = dec_neg_inf();
+      a.out_score[rd] = nvk_neg_inf();
     }
     return;
   }
@@ -84,14 +73,14 @@ __global__ __launch_bounds__((1 << (2 * K)) / 16) void decode_sweep_kernel(Decod
 
   double V[16], mean[16], ac[16], mc[16];
   double e = lev[0];
+  // (hmm_load_table's loop written out: through the helper this kernel comes out with other register counts)
 #pragma unroll
   for (int j = 0; j < 16; j++) {
     mean[j] = a.mean[16 * u + j];
     ac[j] = a.ac[16 * u + j];
     mc[j] = a.mc[16 * u + j];
-    const double d = e - mean[j];
-    V[j] = ac[j] - (d * d) * mc[j];
-    row[0][dec_at(16 * u) + j] = V[j];
+    V[j] = gauss_log(e, mean[j], ac[j], mc[j]);
+    row[0][hmm_at(16 * u) + j] = V[j];
   }
   __syncthreads();
   for (int i = 1; i < E; i++) {
@@ -99,11 +88,11 @@ __global__ __launch_bounds__((1 << (2 * K)) / 16) void decode_sweep_kernel(Decod
     double *N = row[i & 1];
     e = lev[i];
     // skip: the 16 predecessors c T + u, shared by all the thread's states
-    double sk = P[dec_at(u)];
+    double sk = P[hmm_at(u)];
     unsigned long long word = 0;
 #pragma unroll
     for (int c = 1; c < 16; c++) {
-      const double v = P[dec_at(c * T + u)];
+      const double v = P[hmm_at(c * T + u)];
       if (v > sk) {
         sk = v;
         word = (unsigned long long)c;
@@ -113,12 +102,12 @@ __global__ __launch_bounds__((1 << (2 * K)) / 16) void decode_sweep_kernel(Decod
     // step: per group g of four states the 4 predecessors a Q + 4 u + g
     double st[4];
 #pragma unroll
-    for (int g = 0; g < 4; g++) st[g] = P[dec_at(4 * u) + g];
+    for (int g = 0; g < 4; g++) st[g] = P[hmm_at(4 * u) + g];
 #pragma unroll
     for (int x = 1; x < 4; x++) {
 #pragma unroll
       for (int g = 0; g < 4; g++) {
-        const double v = P[dec_at(x * Q + 4 * u) + g];
+        const double v = P[hmm_at(x * Q + 4 * u) + g];
         if (v > st[g]) {
           st[g] = v;
           word = (word & ~(3ull << (4 + 2 * g))) | ((unsigned long long)x << (4 + 2 * g));
@@ -129,8 +118,7 @@ __global__ __launch_bounds__((1 << (2 * K)) / 16) void decode_sweep_kernel(Decod
     for (int g = 0; g < 4; g++) st[g] = st[g] + l_step;
 #pragma unroll
     for (int j = 0; j < 16; j++) {
-      const double d = e - mean[j];
-      const double em = ac[j] - (d * d) * mc[j];
+      const double em = gauss_log(e, mean[j], ac[j], mc[j]);
       const double stay = V[j] + l_stay;
       double v = st[j >> 2];
       unsigned long long w = 0;
@@ -144,7 +132,7 @@ __global__ __launch_bounds__((1 << (2 * K)) / 16) void decode_sweep_kernel(Decod
       }
       V[j] = v + em;
       word |= w << (12 + 2 * j);
-      N[dec_at(16 * u) + j] = V[j];
+      N[hmm_at(16 * u) + j] = V[j];
     }
     tb[(int64_t)(i - 1) * T + u] = word;
     __syncthreads();
@@ -217,12 +205,6 @@ __global__ __launch_bounds__(64) void decode_walk_kernel(DecodeArgs a) {
   hit[2] = (int32_t)n;
 }
 
-template <int K>
-void launch_sweep(const DecodeArgs &a, hipStream_t stream) {
-  constexpr int T = (1 << (2 * K)) / 16;
-  hipLaunchKernelGGL(decode_sweep_kernel<K>, dim3((unsigned)(a.r1 - a.r0)), dim3(T), 0, stream, a);
-}
-
 }  // namespace
 
 extern "C" int nvk_viterbi_decode_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_events, const double *level,
@@ -233,42 +215,26 @@ extern "C" int nvk_viterbi_decode_dev(nvk_ctx *ctx, int64_t n_reads, int64_t tot
                                       int64_t *out_parts) {
   const char *what = "nvk_viterbi_decode_dev";
   if (out_parts) *out_parts = 0;
-  if (!ctx) {
-    nvk_set_error("%s: ctx is NULL", what);
-    return NVK_ERR_INVALID;
-  }
-  if (k < 2 || k > 6) {
-    nvk_set_error("%s: k %d is outside 2..6", what, k);
-    return NVK_ERR_UNSUPPORTED;
-  }
-  if (central < 0 || central >= k) {
-    nvk_set_error("%s: central %d is outside 0..k-1 (k %d)", what, central, k);
-    return NVK_ERR_INVALID;
-  }
-  if (n_reads < 0 || n_reads > 0x7fffffff || total_events < 0 || total_cap < 0) {
+  int rc = hmm_check_entry(what, ctx, k, "central", central, n_reads, total_events, level, ev_off, mean, ac, mc);
+  if (rc) return rc;
+  if (total_cap < 0) {
     nvk_set_error("%s: n_reads %lld, total_events %lld or total_cap %lld out of range", what, (long long)n_reads,
                   (long long)total_events, (long long)total_cap);
     return NVK_ERR_INVALID;
   }
-  const double costs[3] = {l_stay, l_step, l_skip};
-  for (double c : costs)
-    if (!(c <= 0.0) || c * 0.0 != 0.0) {
-      nvk_set_error("%s: l_stay %g, l_step %g or l_skip %g is not a finite value <= 0", what, l_stay, l_step, l_skip);
-      return NVK_ERR_INVALID;
-    }
-  if (!ev_off || !cap_off || (total_events > 0 && !level) || !mean || !ac || !mc) {
+  if (!cap_off) {
     nvk_set_error("%s: NULL levels, offsets or table", what);
     return NVK_ERR_INVALID;
   }
+  if ((rc = check_log_costs(what, "l_stay %g, l_step %g or l_skip %g", {l_stay, l_step, l_skip}))) return rc;
   NVK_HIP(hipSetDevice(ctx->device));
   std::vector<int64_t> eoff, coff;
-  int rc = nvk_fetch_offsets(ctx, "event", ev_off, n_reads, eoff, "total_events", total_events);
-  if (rc) return rc;
+  if ((rc = nvk_fetch_offsets(ctx, "event", ev_off, n_reads, eoff, "total_events", total_events))) return rc;
   if ((rc = nvk_fetch_offsets(ctx, "capacity", cap_off, n_reads, coff, "total_cap", total_cap))) return rc;
   for (int64_t r = 0; r < n_reads; r++) {
     const int64_t E = eoff[r + 1] - eoff[r], cap = coff[r + 1] - coff[r];
-    if (E > DEC_MAX_EVENTS) {
-      nvk_set_error("%s: read %lld has %lld events, above %d", what, (long long)r, (long long)E, DEC_MAX_EVENTS);
+    if (E > HMM_MAX_EVENTS) {
+      nvk_set_error("%s: read %lld has %lld events, above %d", what, (long long)r, (long long)E, HMM_MAX_EVENTS);
       return NVK_ERR_INVALID;
     }
     if (E >= 1 && cap < k + 2 * (E - 1)) {
@@ -295,18 +261,8 @@ extern "C" int nvk_viterbi_decode_dev(nvk_ctx *ctx, int64_t n_reads, int64_t tot
   // device than that however large the batch
   int64_t cap_b = nvk_spill_cap(ctx, WS_SEED_TB);
   if (ctx->ws_limit <= 0 && cap_b > ((int64_t)4 << 30)) cap_b = (int64_t)4 << 30;
-  const int64_t cap_w = cap_b / 8;
-  std::vector<int64_t> cut(1, 0);
-  int64_t need_w = 1;
-  for (int64_t r = 0; r < n_reads; r++) {
-    const int64_t c0 = cut.back();
-    if (r > c0 && tb_off[r + 1] - tb_off[c0] > cap_w) {
-      need_w = need_w > tb_off[r] - tb_off[c0] ? need_w : tb_off[r] - tb_off[c0];
-      cut.push_back(r);
-    }
-  }
-  need_w = need_w > tb_off[n_reads] - tb_off[cut.back()] ? need_w : tb_off[n_reads] - tb_off[cut.back()];
-  cut.push_back(n_reads);
+  std::vector<int64_t> cut;
+  const int64_t need_w = cut_parts(tb_off, cap_b / 8, cut);
   // (the seed aligner's traceback workspaces serve: the two never run at once on a context)
   if ((rc = nvk_ws_reserve(ctx, WS_SEED_TB, (size_t)need_w * 8))) return rc;
   if ((rc = nvk_ws_reserve(ctx, WS_SEED_OFF, ((size_t)n_reads + 1) * sizeof(int64_t) + 64))) return rc;
@@ -314,12 +270,7 @@ extern "C" int nvk_viterbi_decode_dev(nvk_ctx *ctx, int64_t n_reads, int64_t tot
   NVK_HIP(hipMemcpyAsync(d_tb_off, tb_off.data(), tb_off.size() * sizeof(int64_t), hipMemcpyHostToDevice,
                          ctx->stream));
   DecodeArgs a;
-  a.level = level;
-  a.ev_off = ev_off;
-  a.mean = mean;
-  a.ac = ac;
-  a.mc = mc;
-  a.status_in = status_in;
+  (HmmIn &)a = HmmIn{level, ev_off, mean, ac, mc, status_in};
   a.cap_off = cap_off;
   a.l_stay = l_stay;
   a.l_step = l_step;
@@ -336,13 +287,10 @@ extern "C" int nvk_viterbi_decode_dev(nvk_ctx *ctx, int64_t n_reads, int64_t tot
     a.r1 = (int)cut[c + 1];
     a.tb = (unsigned long long *)ctx->ws[WS_SEED_TB];
     a.tb_base = tb_off[cut[c]];
-    switch (k) {
-      case 2: launch_sweep<2>(a, ctx->stream); break;
-      case 3: launch_sweep<3>(a, ctx->stream); break;
-      case 4: launch_sweep<4>(a, ctx->stream); break;
-      case 5: launch_sweep<5>(a, ctx->stream); break;
-      default: launch_sweep<6>(a, ctx->stream); break;
-    }
+    hmm_dispatch_k(k, [&](auto kc) {
+      constexpr int K = decltype(kc)::value;
+      hipLaunchKernelGGL(decode_sweep_kernel<K>, dim3((unsigned)(a.r1 - a.r0)), dim3(KmerHmm<K>::T), 0, ctx->stream, a);
+    });
     NVK_HIP(hipGetLastError());
     hipLaunchKernelGGL(decode_walk_kernel, dim3((unsigned)((a.r1 - a.r0 + 63) / 64)), dim3(64), 0, ctx->stream, a);
     NVK_HIP(hipGetLastError());

@@ -26,7 +26,9 @@
 // -ffp-contract=off every score is the rounded operation the contract writes, on the device as on the host.
 #include <vector>
 
+#include "kmer_hmm.h"
 #include "nvk_internal.h"
+#include "part_cut.h"
 #include "wave.h"
 
 namespace {
@@ -49,8 +51,6 @@ struct EventAlignArgs {
   int r0;                    // the part's first read
 };
 
-__device__ __forceinline__ double neg_inf() { return __longlong_as_double(0xfff0000000000000ll); }
-
 __device__ __forceinline__ double lane_value(double v, int lane) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
@@ -60,7 +60,7 @@ __device__ __forceinline__ double lane_value(double v, int lane) {
 // the band's cells moved by d offsets (-1, 0, 1): out[c] at lane l = the cell at offset 64 c + l + d, -inf outside
 template <int CPL>
 __device__ __forceinline__ void band_shift(const double (&v)[CPL], int d, int lane, double (&out)[CPL]) {
-  const double NINF = neg_inf();
+  const double NINF = nvk_neg_inf();
   if (d == 0) {
 #pragma unroll
     for (int c = 0; c < CPL; c++) out[c] = v[c];
@@ -82,7 +82,7 @@ __device__ __forceinline__ void band_shift(const double (&v)[CPL], int d, int la
 template <int CPL>
 __global__ __launch_bounds__(64) void event_align_kernel(EventAlignArgs a) {
   constexpr int BAND = 64 * CPL, H = BAND / 2, W = 2 * CPL;  // W: traceback words per band
-  const double NINF = neg_inf();
+  const double NINF = nvk_neg_inf();
   const int lane = threadIdx.x;
   const int64_t rd = (int64_t)a.r0 + blockIdx.x;
   const int64_t ev0 = a.ev_off[rd], b0 = a.base_off[rd];
@@ -149,8 +149,7 @@ __global__ __launch_bounds__(64) void event_align_kernel(EventAlignArgs a) {
           at_j[c] = j;
         }
       }
-      const double d = c_lev[c] - c_mu[c];
-      const double em = c_ac[c] - d * d * c_mc[c];
+      const double em = gauss_log(c_lev[c], c_mu[c], c_ac[c], c_mc[c]);
       const double src = j == 0 ? (double)i * trim : diag[c];
       const double step = (src + l_step) + em;
       const double stay = (up[c] + l_stay) + em;
@@ -286,10 +285,7 @@ extern "C" int nvk_event_align_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_
     nvk_set_error("%s: band %d is not one of the compiled widths 64 and 128", what, band);
     return NVK_ERR_UNSUPPORTED;
   }
-  if (!(trim_cost <= 0.0) || !(skip_cost <= 0.0) || trim_cost * 0.0 != 0.0 || skip_cost * 0.0 != 0.0) {
-    nvk_set_error("%s: trim_cost %g or skip_cost %g is not a finite value <= 0", what, trim_cost, skip_cost);
-    return NVK_ERR_INVALID;
-  }
+  if (int rc = check_log_costs(what, "trim_cost %g or skip_cost %g", {trim_cost, skip_cost})) return rc;
   if (!ev_off || !base_off || (total_events > 0 && !level) || (total_bases > 0 && (!mu || !ac || !mc))) {
     nvk_set_error("%s: NULL levels, offsets or base tables", what);
     return NVK_ERR_INVALID;
@@ -319,18 +315,8 @@ extern "C" int nvk_event_align_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_
     tb_off[r + 1] = tb_off[r] + nb * W + (nb + 63) / 64;
   }
   // parts of reads whose store fits the cap (a read larger than the cap on its own makes a part of one)
-  const int64_t cap_w = nvk_spill_cap(ctx, WS_SEED_TB) / 8;
-  std::vector<int64_t> cut(1, 0);
-  int64_t need_w = 1;
-  for (int64_t r = 0; r < n_reads; r++) {
-    const int64_t c0 = cut.back();
-    if (r > c0 && tb_off[r + 1] - tb_off[c0] > cap_w) {
-      need_w = need_w > tb_off[r] - tb_off[c0] ? need_w : tb_off[r] - tb_off[c0];
-      cut.push_back(r);
-    }
-  }
-  need_w = need_w > tb_off[n_reads] - tb_off[cut.back()] ? need_w : tb_off[n_reads] - tb_off[cut.back()];
-  cut.push_back(n_reads);
+  std::vector<int64_t> cut;
+  const int64_t need_w = cut_parts(tb_off, nvk_spill_cap(ctx, WS_SEED_TB) / 8, cut);
   // (the seed aligner's traceback workspaces serve: the two never run at once on a context)
   if ((rc = nvk_ws_reserve(ctx, WS_SEED_TB, (size_t)need_w * 8))) return rc;
   if ((rc = nvk_ws_reserve(ctx, WS_SEED_OFF, ((size_t)n_reads + 1) * sizeof(int64_t) + 64))) return rc;

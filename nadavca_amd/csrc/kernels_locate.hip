@@ -20,6 +20,7 @@
 // operation the contract writes, on the device as on the host.
 #include <vector>
 
+#include "kmer_hmm.h"
 #include "nvk_internal.h"
 #include "wave.h"
 
@@ -47,14 +48,12 @@ struct LocateArgs {
   int32_t *out_hit;
 };
 
-__device__ __forceinline__ double loc_neg_inf() { return __longlong_as_double(0xfff0000000000000ll); }
-
 // CPL columns per lane: a tile of T = 64 CPL columns, the last V of them valid
 template <int CPL, int V>
 __global__ __launch_bounds__(64) void locate_kernel(LocateArgs a) {
   constexpr int T = 64 * CPL, H = T - V, G = NVK_LOC_BLOCK / CPL;  // G: lanes per block of the output
   static_assert(V % NVK_LOC_BLOCK == 0 && H % CPL == 0 && (H / CPL) % G == 0, "blocks start at lane groups");
-  const double NINF = loc_neg_inf();
+  const double NINF = nvk_neg_inf();
   const int lane = threadIdx.x;
   const int64_t id = blockIdx.x;
   const int64_t q = a.q0 + id / a.n_tiles;
@@ -91,8 +90,7 @@ __global__ __launch_bounds__(64) void locate_kernel(LocateArgs a) {
       const double s2 = c >= 2 ? S[c >= 2 ? c - 2 : 0] : (c == 1 ? p1 : p2);
       const int r1 = c >= 1 ? src[c >= 1 ? c - 1 : 0] : q1;
       const int r2 = c >= 2 ? src[c >= 2 ? c - 2 : 0] : (c == 1 ? q1 : q2);
-      const double d = e - mu[c];
-      const double em = ac[c] - (d * d) * mc[c];
+      const double em = gauss_log(e, mu[c], ac[c], mc[c]);
       double v = open;
       int s = ((lane * CPL + c) << 8) | i;
       const double step = s1 + l_step, stay = S[c] + l_stay, skip = s2 + l_skip;
@@ -173,13 +171,9 @@ extern "C" int nvk_signal_locate_dev(nvk_ctx *ctx, int64_t n_queries, int64_t to
     nvk_set_error("%s: max_events %d is above %d", what, max_events, (int)NVK_LOC_MAX_EVENTS);
     return NVK_ERR_UNSUPPORTED;
   }
-  const double costs[4] = {l_stay, l_step, l_skip, trim_cost};
-  for (double c : costs)
-    if (!(c <= 0.0) || c * 0.0 != 0.0) {
-      nvk_set_error("%s: l_stay %g, l_step %g, l_skip %g or trim_cost %g is not a finite value <= 0", what, l_stay,
-                    l_step, l_skip, trim_cost);
-      return NVK_ERR_INVALID;
-    }
+  if (int rc = check_log_costs(what, "l_stay %g, l_step %g, l_skip %g or trim_cost %g",
+                               {l_stay, l_step, l_skip, trim_cost}))
+    return rc;
   if (!q_off || !col_off || (total_events > 0 && !level) || (total_cols > 0 && (!mu || !ac || !mc))) {
     nvk_set_error("%s: NULL levels, offsets or column tables", what);
     return NVK_ERR_INVALID;

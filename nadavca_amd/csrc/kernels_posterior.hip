@@ -32,21 +32,17 @@
 // -ffp-contract=off every value is the rounded operation the contract writes, on the device as on the host.
 #include <vector>
 
+#include "kmer_hmm.h"
 #include "nvk_internal.h"
+#include "part_cut.h"
 #include "xmath.h"
 
 namespace {
 
-constexpr int POST_MAX_EVENTS = 1 << 26;  // per read
-constexpr int POST_PAD = 2;               // doubles of padding after every 16 entries of a row in LDS
 constexpr double POST_EM_FLOOR = -300.0;
 constexpr double POST_MIN_MOVE = 0x1p-10;  // max(w_stay, w_step) is at least this
 
-struct PostArgs {
-  const double *level;  // the events' levels, read r at ev_off[r]
-  const int64_t *ev_off;
-  const double *mean, *ac, *mc;  // the table, f64[4^k]
-  const int32_t *status_in;      // per read or null
+struct PostArgs : HmmIn {
   double w_stay, w_step, w_skip;
   double *out_marg, *out_z;
   int32_t *out_status;
@@ -60,9 +56,6 @@ struct PostArgs {
 template <int T>
 __device__ __forceinline__ constexpr int post_store_at(int j) { return (j >> 1) * 2 * T + (j & 1); }
 
-// where entry s lies in a padded row
-__device__ __forceinline__ constexpr int post_at(int s) { return s + (s >> 4) * POST_PAD; }
-
 // EXP of the contract
 __device__ __forceinline__ double post_exp(double g) {
   const double y = g * xm::LOG2E;
@@ -72,8 +65,7 @@ __device__ __forceinline__ double post_exp(double g) {
 
 // b(i, s) for a level e
 __device__ __forceinline__ double post_emission(double e, double mean, double ac, double mc) {
-  const double d = e - mean;
-  return post_exp(fmax(ac - (d * d) * mc, POST_EM_FLOOR));
+  return post_exp(fmax(gauss_log(e, mean, ac, mc), POST_EM_FLOOR));
 }
 
 // the butterfly of wave_sum over the W lanes of a workgroup's wave that hold a thread (W = min(T, 64))
@@ -103,24 +95,17 @@ __device__ __forceinline__ double post_join_max(const double *g) {
   return m;
 }
 
-// status of read rd, as both sweeps see it
-__device__ __forceinline__ int post_status(const PostArgs &a, int64_t rd, int E) {
-  const int status = a.status_in ? a.status_in[rd] : 0;
-  return (status == 0 && E == 0) ? NVK_DEC_NO_EVENTS : status;
-}
-
 template <int K>
-__global__ __launch_bounds__((1 << (2 * K)) / 16) void posterior_forward_kernel(PostArgs a) {
-  constexpr int S = 1 << (2 * K), T = S / 16, Q = S / 4, ROW = S + T * POST_PAD;
-  constexpr int W = T < 64 ? T : 64, NW = T / W;
-  __shared__ __attribute__((aligned(16))) double row[2][ROW];
+__global__ __launch_bounds__(KmerHmm<K>::T) void posterior_forward_kernel(PostArgs a) {
+  constexpr int S = KmerHmm<K>::S, T = KmerHmm<K>::T, Q = KmerHmm<K>::Q, W = KmerHmm<K>::W, NW = KmerHmm<K>::NW;
+  __shared__ __attribute__((aligned(16))) double row[2][KmerHmm<K>::ROW];
   __shared__ double wave_top[2][NW];  // per wave the largest value of the row it wrote
   __shared__ double wave_z[NW];
   const int u = threadIdx.x, wave = u / W;
   const int64_t rd = (int64_t)a.r0 + blockIdx.x;
   const int64_t ev0 = a.ev_off[rd];
   const int E = (int)(a.ev_off[rd + 1] - ev0);
-  const int status = post_status(a, rd, E);
+  const int status = hmm_status(a, rd, E);
   if (status != 0) {
     if (u == 0) {
       a.out_status[rd] = status;
@@ -136,16 +121,12 @@ __global__ __launch_bounds__((1 << (2 * K)) / 16) void posterior_forward_kernel(
   double A[16], mean[16], ac[16], mc[16];
   double e = lev[0];
   double top = 0.0;
-#pragma unroll
-  for (int j = 0; j < 16; j++) {
-    mean[j] = a.mean[16 * u + j];
-    ac[j] = a.ac[16 * u + j];
-    mc[j] = a.mc[16 * u + j];
+  hmm_load_table(a, u, mean, ac, mc, [&](int j) {
     A[j] = post_emission(e, mean[j], ac[j], mc[j]);
-    row[0][post_at(16 * u) + j] = A[j];
+    row[0][hmm_at(16 * u) + j] = A[j];
     store[post_store_at<T>(j)] = A[j];
     top = fmax(top, A[j]);
-  }
+  });
   top = post_wave_max<W>(top);
   if ((u & (W - 1)) == 0) wave_top[0][wave] = top;
   __syncthreads();
@@ -156,18 +137,18 @@ __global__ __launch_bounds__((1 << (2 * K)) / 16) void posterior_forward_kernel(
     e = lev[i];
     const int x = __builtin_amdgcn_frexp_exp(post_join_max<NW>(wave_top[(i - 1) & 1]));
     // skip: the 16 predecessors c T + u, shared by all the thread's states
-    double sum16 = P[post_at(u)];
+    double sum16 = P[hmm_at(u)];
 #pragma unroll
-    for (int c = 1; c < 16; c++) sum16 = sum16 + P[post_at(c * T + u)];
+    for (int c = 1; c < 16; c++) sum16 = sum16 + P[hmm_at(c * T + u)];
     const double sk = w_skip * sum16;
     // step: per group g of four states the 4 predecessors a Q + 4 u + g
     double st[4];
 #pragma unroll
-    for (int g = 0; g < 4; g++) st[g] = P[post_at(4 * u) + g];
+    for (int g = 0; g < 4; g++) st[g] = P[hmm_at(4 * u) + g];
 #pragma unroll
     for (int c = 1; c < 4; c++) {
 #pragma unroll
-      for (int g = 0; g < 4; g++) st[g] = st[g] + P[post_at(c * Q + 4 * u) + g];
+      for (int g = 0; g < 4; g++) st[g] = st[g] + P[hmm_at(c * Q + 4 * u) + g];
     }
 #pragma unroll
     for (int g = 0; g < 4; g++) st[g] = w_step * st[g];
@@ -177,7 +158,7 @@ __global__ __launch_bounds__((1 << (2 * K)) / 16) void posterior_forward_kernel(
     for (int j = 0; j < 16; j++) {
       const double t = (st[j >> 2] + w_stay * A[j]) + sk;
       A[j] = ldexp(t, -x) * post_emission(e, mean[j], ac[j], mc[j]);
-      N[post_at(16 * u) + j] = A[j];
+      N[hmm_at(16 * u) + j] = A[j];
       out[post_store_at<T>(j)] = A[j];
       top = fmax(top, A[j]);
     }
@@ -203,19 +184,18 @@ __global__ __launch_bounds__((1 << (2 * K)) / 16) void posterior_forward_kernel(
 // (two waves per SIMD asked for: with the row in flight across the emissions the compiler otherwise takes 266 registers
 // and one)
 template <int K>
-__global__ __launch_bounds__((1 << (2 * K)) / 16) __attribute__((amdgpu_waves_per_eu(2))) void
+__global__ __launch_bounds__(KmerHmm<K>::T) __attribute__((amdgpu_waves_per_eu(2))) void
 posterior_backward_kernel(PostArgs a) {
-  constexpr int S = 1 << (2 * K), T = S / 16, Q = S / 4;
-  constexpr int W = T < 64 ? T : 64, NW = T / W;
-  __shared__ __attribute__((aligned(16))) double G4[2][Q + (Q >> 4) * POST_PAD + POST_PAD];  // w_step * G4
-  __shared__ __attribute__((aligned(16))) double G16[2][T + (T >> 4) * POST_PAD + POST_PAD];  // w_skip * G16
+  constexpr int S = KmerHmm<K>::S, T = KmerHmm<K>::T, Q = KmerHmm<K>::Q, W = KmerHmm<K>::W, NW = KmerHmm<K>::NW;
+  __shared__ __attribute__((aligned(16))) double G4[2][Q + (Q >> 4) * HMM_PAD + HMM_PAD];  // w_step * G4
+  __shared__ __attribute__((aligned(16))) double G16[2][T + (T >> 4) * HMM_PAD + HMM_PAD];  // w_skip * G16
   __shared__ double wave_top[2][NW];     // per wave the largest B of the event
   __shared__ double wave_cls[2][4][NW];  // per wave the four class sums of the event
   const int u = threadIdx.x, wave = u / W;
   const int64_t rd = (int64_t)a.r0 + blockIdx.x;
   const int64_t ev0 = a.ev_off[rd];
   const int E = (int)(a.ev_off[rd + 1] - ev0);
-  if (post_status(a, rd, E) != 0) return;
+  if (hmm_status(a, rd, E) != 0) return;
   const double *lev = a.level + ev0;
   const double w_stay = a.w_stay, w_step = a.w_step, w_skip = a.w_skip;
   const double *store = a.rows + (ev0 - a.ev_off[a.r0]) * (int64_t)S + 2 * u;
@@ -225,13 +205,7 @@ posterior_backward_kernel(PostArgs a) {
   const int own = (a.pos < K - 2) ? ((16 * u) >> (2 * (K - 1 - a.pos))) & 3 : 0;  // mode 2: the letter of all 16
 
   double B[16], mean[16], ac[16], mc[16];
-#pragma unroll
-  for (int j = 0; j < 16; j++) {
-    mean[j] = a.mean[16 * u + j];
-    ac[j] = a.ac[16 * u + j];
-    mc[j] = a.mc[16 * u + j];
-    B[j] = 1.0;
-  }
+  hmm_load_table(a, u, mean, ac, mc, [&](int j) { B[j] = 1.0; });
   for (int i = E - 1; i >= 0; i--) {
     const int p = i & 1;
     const double *in = store + (int64_t)i * S;
@@ -254,8 +228,8 @@ posterior_backward_kernel(PostArgs a) {
       for (int g = 0; g < 4; g++) g4[g] = ((Wv[4 * g] + Wv[4 * g + 1]) + Wv[4 * g + 2]) + Wv[4 * g + 3];
       const double g16 = ((g4[0] + g4[1]) + g4[2]) + g4[3];
 #pragma unroll
-      for (int g = 0; g < 4; g++) G4[p][post_at(4 * u) + g] = w_step * g4[g];
-      G16[p][post_at(u)] = w_skip * g16;
+      for (int g = 0; g < 4; g++) G4[p][hmm_at(4 * u) + g] = w_step * g4[g];
+      G16[p][hmm_at(u)] = w_skip * g16;
     }
     double ab[16];
 #pragma unroll
@@ -301,32 +275,21 @@ posterior_backward_kernel(PostArgs a) {
 #pragma unroll
       for (int j = 0; j < 16; j++) {
         const int s = 16 * u + j;
-        const double t = (G4[p][post_at(s & (Q - 1))] + w_stay * Wv[j]) + G16[p][post_at(s & (T - 1))];
+        const double t = (G4[p][hmm_at(s & (Q - 1))] + w_stay * Wv[j]) + G16[p][hmm_at(s & (T - 1))];
         B[j] = ldexp(t, -y);
       }
     }
   }
 }
 
-template <int K>
-void launch_forward(const PostArgs &a, int n, hipStream_t stream) {
-  constexpr int T = (1 << (2 * K)) / 16;
-  hipLaunchKernelGGL(posterior_forward_kernel<K>, dim3((unsigned)n), dim3(T), 0, stream, a);
-}
-template <int K>
-void launch_backward(const PostArgs &a, int n, hipStream_t stream) {
-  constexpr int T = (1 << (2 * K)) / 16;
-  hipLaunchKernelGGL(posterior_backward_kernel<K>, dim3((unsigned)n), dim3(T), 0, stream, a);
-}
-
 void launch_sweep(bool forward, int k, const PostArgs &a, int n, hipStream_t stream) {
-  switch (k) {
-    case 2: forward ? launch_forward<2>(a, n, stream) : launch_backward<2>(a, n, stream); break;
-    case 3: forward ? launch_forward<3>(a, n, stream) : launch_backward<3>(a, n, stream); break;
-    case 4: forward ? launch_forward<4>(a, n, stream) : launch_backward<4>(a, n, stream); break;
-    case 5: forward ? launch_forward<5>(a, n, stream) : launch_backward<5>(a, n, stream); break;
-    default: forward ? launch_forward<6>(a, n, stream) : launch_backward<6>(a, n, stream); break;
-  }
+  hmm_dispatch_k(k, [&](auto kc) {
+    constexpr int K = decltype(kc)::value;
+    if (forward)
+      hipLaunchKernelGGL(posterior_forward_kernel<K>, dim3((unsigned)n), dim3(KmerHmm<K>::T), 0, stream, a);
+    else
+      hipLaunchKernelGGL(posterior_backward_kernel<K>, dim3((unsigned)n), dim3(KmerHmm<K>::T), 0, stream, a);
+  });
 }
 
 }  // namespace
@@ -339,23 +302,8 @@ extern "C" int nvk_kmer_posterior_dev(nvk_ctx *ctx, int64_t n_reads, int64_t tot
   const char *what = "nvk_kmer_posterior_dev";
   if (out_parts) *out_parts = 0;
   if (out_ms) out_ms[0] = out_ms[1] = 0.0;
-  if (!ctx) {
-    nvk_set_error("%s: ctx is NULL", what);
-    return NVK_ERR_INVALID;
-  }
-  if (k < 2 || k > 6) {
-    nvk_set_error("%s: k %d is outside 2..6", what, k);
-    return NVK_ERR_UNSUPPORTED;
-  }
-  if (pos < 0 || pos >= k) {
-    nvk_set_error("%s: pos %d is outside 0..k-1 (k %d)", what, pos, k);
-    return NVK_ERR_INVALID;
-  }
-  if (n_reads < 0 || n_reads > 0x7fffffff || total_events < 0) {
-    nvk_set_error("%s: n_reads %lld or total_events %lld out of range", what, (long long)n_reads,
-                  (long long)total_events);
-    return NVK_ERR_INVALID;
-  }
+  int rc = hmm_check_entry(what, ctx, k, "pos", pos, n_reads, total_events, level, ev_off, mean, ac, mc);
+  if (rc) return rc;
   const double weights[3] = {w_stay, w_step, w_skip};
   for (double w : weights)
     if (!(w > 0.0 && w <= 1.0)) {
@@ -367,18 +315,13 @@ extern "C" int nvk_kmer_posterior_dev(nvk_ctx *ctx, int64_t n_reads, int64_t tot
     nvk_set_error("%s: w_stay %g and w_step %g are both below 2^-10", what, w_stay, w_step);
     return NVK_ERR_INVALID;
   }
-  if (!ev_off || (total_events > 0 && !level) || !mean || !ac || !mc) {
-    nvk_set_error("%s: NULL levels, offsets or table", what);
-    return NVK_ERR_INVALID;
-  }
   NVK_HIP(hipSetDevice(ctx->device));
   std::vector<int64_t> eoff;
-  int rc = nvk_fetch_offsets(ctx, "event", ev_off, n_reads, eoff, "total_events", total_events);
-  if (rc) return rc;
+  if ((rc = nvk_fetch_offsets(ctx, "event", ev_off, n_reads, eoff, "total_events", total_events))) return rc;
   for (int64_t r = 0; r < n_reads; r++)
-    if (eoff[r + 1] - eoff[r] > POST_MAX_EVENTS) {
+    if (eoff[r + 1] - eoff[r] > HMM_MAX_EVENTS) {
       nvk_set_error("%s: read %lld has %lld events, above %d", what, (long long)r, (long long)(eoff[r + 1] - eoff[r]),
-                    POST_MAX_EVENTS);
+                    HMM_MAX_EVENTS);
       return NVK_ERR_INVALID;
     }
   if (n_reads == 0) return NVK_OK;
@@ -393,27 +336,12 @@ extern "C" int nvk_kmer_posterior_dev(nvk_ctx *ctx, int64_t n_reads, int64_t tot
   int64_t cap_b = nvk_spill_cap(ctx, WS_SEED_TB);
   if (ctx->ws_limit <= 0 && cap_b > ((int64_t)16 << 30)) cap_b = (int64_t)16 << 30;
   const int64_t S = (int64_t)1 << (2 * k);
-  const int64_t cap_rows = cap_b / (8 * S);
-  std::vector<int64_t> cut(1, 0);
-  int64_t need_rows = 1;
-  for (int64_t r = 0; r < n_reads; r++) {
-    const int64_t c0 = cut.back();
-    if (r > c0 && eoff[r + 1] - eoff[c0] > cap_rows) {
-      need_rows = need_rows > eoff[r] - eoff[c0] ? need_rows : eoff[r] - eoff[c0];
-      cut.push_back(r);
-    }
-  }
-  need_rows = need_rows > eoff[n_reads] - eoff[cut.back()] ? need_rows : eoff[n_reads] - eoff[cut.back()];
-  cut.push_back(n_reads);
+  std::vector<int64_t> cut;
+  const int64_t need_rows = cut_parts(eoff, cap_b / (8 * S), cut);
   // (the seed aligner's traceback workspace serves, as for the Viterbi store: the three never run at once on a context)
   if ((rc = nvk_ws_reserve(ctx, WS_SEED_TB, (size_t)need_rows * (size_t)S * 8))) return rc;
   PostArgs a;
-  a.level = level;
-  a.ev_off = ev_off;
-  a.mean = mean;
-  a.ac = ac;
-  a.mc = mc;
-  a.status_in = status_in;
+  (HmmIn &)a = HmmIn{level, ev_off, mean, ac, mc, status_in};
   a.w_stay = w_stay;
   a.w_step = w_step;
   a.w_skip = w_skip;

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "nvk_internal.h"
+#include "part_cut.h"
 #include "wave.h"
 
 namespace {
@@ -366,18 +367,8 @@ static int seed_extend(const char *what, bool bounded, bool path, nvk_ctx *ctx, 
     tb_off[r + 1] = tb_off[r] + (st[r] == 0 || st[r] == 1 ? (m + 63) / 64 * row_dw : 0);
   }
   // chunks of reads whose store fits the cap (a read larger than the cap on its own makes a chunk of one)
-  const int64_t cap_dw = nvk_spill_cap(ctx, WS_SEED_TB) / 4;
-  std::vector<int64_t> cut(1, 0);
-  int64_t need_dw = 1;
-  for (int64_t r = 0; r < n_reads; r++) {
-    const int64_t c0 = cut.back();
-    if (r > c0 && tb_off[r + 1] - tb_off[c0] > cap_dw) {
-      need_dw = need_dw > tb_off[r] - tb_off[c0] ? need_dw : tb_off[r] - tb_off[c0];
-      cut.push_back(r);
-    }
-  }
-  need_dw = need_dw > tb_off[n_reads] - tb_off[cut.back()] ? need_dw : tb_off[n_reads] - tb_off[cut.back()];
-  cut.push_back(n_reads);
+  std::vector<int64_t> cut;
+  const int64_t need_dw = cut_parts(tb_off, nvk_spill_cap(ctx, WS_SEED_TB) / 4, cut);
   if ((rc = nvk_ws_reserve(ctx, WS_SEED_TB, (size_t)need_dw * 4))) return rc;
   if ((rc = nvk_ws_reserve(ctx, WS_SEED_OFF, ((size_t)n_reads + 1) * sizeof(int64_t) + 64))) return rc;
   int64_t *d_tb_off = (int64_t *)ctx->ws[WS_SEED_OFF];

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <functional>
+#include <initializer_list>
 #include <vector>
 
 #include "../../include/nadavca_hip.h"
@@ -198,6 +199,8 @@ inline unsigned grid_of(int64_t items, int64_t per_block) {
   return (unsigned)(want < 65535 * 16 ? want : 65535 * 16);
 }
 
+__device__ __forceinline__ double nvk_neg_inf() { return __longlong_as_double(0xfff0000000000000ll); }
+
 // the read that owns flat position g: the rd with off[rd] <= g < off[rd + 1], by binary search over off[0..n]
 __device__ __forceinline__ int64_t owner_of(const int64_t *off, int64_t n, int64_t g) {
   int64_t lo = 0, hi = n;
@@ -226,6 +229,9 @@ int check_offsets(const char *what, const int64_t *off, int64_t n);
 // check_offsets; with total_name, the offsets must also end at `total`, the argument of that name
 int nvk_fetch_offsets(nvk_ctx *ctx, const char *what, const int64_t *off, int64_t n, std::vector<int64_t> &h_off,
                       const char *total_name = nullptr, int64_t total = 0);
+// log costs: every value of v finite and <= 0, else an error "<what>: <names> is not ..." with `names` a printf
+// format that takes the values as %g, in order (at most four)
+int check_log_costs(const char *what, const char *names, std::initializer_list<double> v);
 // the model handle and the ranges of n_reads, bandwidth and min_event_length
 int check_common(nvk_model *model, int64_t n_reads, int bandwidth, int mel);
 // the per-site two-sample entries (nvk_site_rank_tests_dev, nvk_site_mixture_tests_dev): ctx, the three counts >= 0

@@ -9,7 +9,8 @@ starts from.  On the device:
 
 1. per-read median / MAD normalisation (``nvk_normalize_groups_dev``) and event detection, both ``signal_map_batch``'s;
 2. a rescale by moments: the events' per-read median and MAD are mapped onto those of the table's 4^k means
-   (``locate.rescale_pooled_dev``).  A read with fewer than ``min_events`` events or a zero MAD is ``DEC_NO_EVENTS``;
+   (``rawsignal.rescale_by_moments_dev``, one group for every read).  A read with fewer than ``min_events`` events or a
+   zero MAD is ``DEC_NO_EVENTS``;
 3. the operator (``nvk_viterbi_decode_dev``, contract in include/nadavca_hip.h): per read the best path's score, the
    sequence it spells and per base the first event of the state that owns it;
 4. a compaction of the operator's outputs, which it lays out by capacity, in torch;
@@ -35,7 +36,9 @@ import math
 import numpy as np
 
 from . import _lib, defaults
-from .batchflow import load_kmer_model, seg_index
+from .batchflow import seg_index
+from .rawsignal import (SignalEvents, gaussian_constants, map_rows_dev, offsets_of, rescale_by_moments_dev,
+                        resolve_kmer_model, signal_events_dev, transition_costs, transition_weights)
 from .readbatch import ReadBatch
 
 DEC_OK, DEC_NO_EVENTS = _lib.DEC_OK, _lib.DEC_NO_EVENTS
@@ -97,13 +100,6 @@ class DecodeBatch:
 PHRED_THRESHOLDS = 1.0 - np.power(10.0, -np.arange(1, 61, dtype=np.float64) / 10.0)
 
 
-def transition_costs(p_stay, p_skip):
-    """-> (l_stay, l_step, l_skip): the logs of p_stay, 1 - p_stay - p_skip and p_skip"""
-    if not (0.0 < p_stay < 1.0 and 0.0 < p_skip < 1.0 and p_stay + p_skip < 1.0):
-        raise ValueError('decode_batch: p_stay, p_skip and 1 - p_stay - p_skip must lie inside (0, 1)')
-    return math.log(p_stay), math.log(1.0 - p_stay - p_skip), math.log(p_skip)
-
-
 def check_table(kmer_model):
     """The operator's limits on the table, as a ValueError that names them"""
     alphabet, k = kmer_model.get_alphabet_size(), kmer_model.get_k()
@@ -117,9 +113,7 @@ def state_tables_dev(kmer_model, sigma_scale, device):
     """-> (mean, ac, mc) f64[4^k] on ``device``: the states' levels and the constants of their Gaussians with
     sigma * ``sigma_scale``, formed as ``signal_map.base_tables_dev`` forms them"""
     import torch
-    sd = np.asarray(kmer_model.sigma, dtype=np.float64) * float(sigma_scale)
-    tables = (np.asarray(kmer_model.mean, dtype=np.float64), -np.log(sd * math.sqrt(2.0 * math.pi)),
-              1.0 / (2.0 * sd * sd))
+    tables = (np.asarray(kmer_model.mean, dtype=np.float64),) + gaussian_constants(kmer_model.sigma, sigma_scale)
     return [torch.from_numpy(np.ascontiguousarray(t)).to(device) for t in tables]
 
 
@@ -128,18 +122,13 @@ def capacity_offsets(ev_off, k):
     import torch
     n_ev = ev_off[1:] - ev_off[:-1]
     cap = torch.where(n_ev >= 1, k + 2 * (n_ev - 1), torch.zeros_like(n_ev))
-    return torch.cat([torch.zeros(1, dtype=torch.int64, device=ev_off.device), torch.cumsum(cap, 0)])
+    return offsets_of(cap)
 
 
 def traceback_bytes(n_events, k):
     """Bytes of the operator's traceback store for reads of ``n_events`` events (numpy): 4^k / 2 per event but the
     first"""
     return int(np.maximum(np.asarray(n_events, dtype=np.int64) - 1, 0).sum()) * (4 ** k // 2)
-
-
-def transition_weights(p_stay, p_skip):
-    """-> (w_stay, w_step, w_skip): the very numbers whose logs ``transition_costs`` takes"""
-    return p_stay, 1.0 - p_stay - p_skip, p_skip
 
 
 def row_store_bytes(n_events, k):
@@ -178,36 +167,27 @@ def base_qualities_dev(marg, z, ok, n_ev, ev_off, map_off, owner, keep, sequence
     return loglik, base_post, torch.searchsorted(thresholds, base_post, right=True).to(torch.uint8)
 
 
-class DecodeStages:
+class DecodeStages(SignalEvents):
     """The device tensors between the stages of one ``decode_batch`` call (``decode_stages``)."""
-    __slots__ = ('norm', 'sig_off', 'ev_off', 'ev_start', 'ev_level', 'mean', 'ac', 'mc', 'scaled', 'ok', 'status_in',
-                 'cap_off', 'costs', 'hit', 'path_score', 'seq', 'base_event', 'parts')
+    __slots__ = ('mean', 'ac', 'mc', 'scaled', 'ok', 'status_in', 'cap_off', 'costs', 'hit', 'path_score', 'seq',
+                 'base_event', 'parts')
 
 
 def decode_stages(read_batch, kmer_model, p_stay, p_skip, sigma_scale, min_events, window, threshold, var_floor,
                   timer=None):
     """Stages 1 to 3 on the device -> DecodeStages.  ``timer(name)``: called after each stage (bench tool)."""
     import torch
-    from .device import normalize_groups_dev, viterbi_decode_dev
-    from .locate import rescale_pooled_dev
-    from .signal_map import detect_events_dev
+    from .device import viterbi_decode_dev
     context = kmer_model.context
     device = torch.device('cuda', context.device)
     rb, st = read_batch, DecodeStages()
     tick = timer if timer is not None else (lambda name: None)
-    st.costs = transition_costs(p_stay, p_skip)
-    raw = torch.from_numpy(rb.raw_signal).to(device)
-    if raw.dtype != torch.float64:
-        raw = raw.to(torch.float64)
-    st.sig_off = torch.from_numpy(rb.sig_off).to(device)
+    st.costs = transition_costs(p_stay, p_skip, 'decode_batch')
     st.mean, st.ac, st.mc = state_tables_dev(kmer_model, sigma_scale, device)
-    tick('upload')
-    st.norm = normalize_groups_dev(context, raw, st.sig_off, out=raw)[0] if rb.n and raw.numel() else raw
-    tick('normalise')
-    _, _, st.ev_off, st.ev_start, _, st.ev_level = detect_events_dev(context, st.norm, st.sig_off, window, threshold,
-                                                                     var_floor)
-    tick('events')
-    st.scaled, st.ok = rescale_pooled_dev(context, st.ev_level, st.ev_off, st.mean, min_events)
+    signal_events_dev(rb, context, window, threshold, var_floor, tick, into=st)
+    pool_off = torch.tensor([0, int(st.mean.numel())], dtype=torch.int64, device=device)
+    st.scaled, _, _, st.ok = rescale_by_moments_dev(context, st.ev_level, st.ev_off, st.mean, pool_off,
+                                                    min_events=min_events)
     st.status_in = torch.where(st.ok, DEC_OK, DEC_NO_EVENTS).to(torch.int32)
     st.cap_off = capacity_offsets(st.ev_off, kmer_model.get_k())
     tick('rescale')
@@ -231,9 +211,7 @@ def decode_batch(read_batch, kmer_model=defaults.KMER_MODEL_FILE, p_stay=0.7, p_
     the forward-backward operator and fill ``loglik``, ``base_post`` and ``quality`` (stage 5 of the module docstring);
     the other results do not change.  -> DecodeBatch."""
     import torch
-    if isinstance(kmer_model, (str, bytes)) or hasattr(kmer_model, '__fspath__'):
-        from .kmer_model import load_kmer_model as load_on
-        kmer_model = load_on(kmer_model, context=context) if context is not None else load_kmer_model(kmer_model)
+    kmer_model = resolve_kmer_model(kmer_model, context)
     check_table(kmer_model)
     if int(min_events) < 1:
         raise ValueError('decode_batch: min_events is at least 1')
@@ -245,15 +223,11 @@ def decode_batch(read_batch, kmer_model=defaults.KMER_MODEL_FILE, p_stay=0.7, p_
     score = torch.where(ok, st.path_score / torch.clamp(n_ev, min=1).to(torch.float64),
                         torch.full_like(st.path_score, float('nan')))
     # the compaction: read r's n_bases entries lie at cap_off[r]
-    seq_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(n_bases, 0)])
+    seq_off = offsets_of(n_bases)
     owner, inner = seg_index(seq_off)
     at = st.cap_off[:-1][owner] + inner
     sequence, event = st.seq[at], st.base_event[at].to(torch.int64)
-    keep = event >= 0
-    k_owner = owner[keep]
-    map_sig = st.ev_start[st.ev_off[:-1][k_owner] + event[keep]]
-    map_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev),
-                         torch.cumsum(torch.bincount(k_owner, minlength=rb.n), 0)])
+    map_base, map_sig, map_off, keep, _ = map_rows_dev(owner, inner, event, st.ev_start, st.ev_off, rb.n)
     host = lambda t: t.cpu().numpy()
     extra = {}
     if qualities:
@@ -265,5 +239,5 @@ def decode_batch(read_batch, kmer_model=defaults.KMER_MODEL_FILE, p_stay=0.7, p_
                                                         event)
         extra = dict(loglik=host(loglik), base_post=host(base_post), quality=host(quality), post_parts=post_parts)
     return DecodeBatch(host(status), host(st.hit[:, 1]), host(st.hit[:, 2]), host(score), host(seq_off),
-                       host(sequence), host(inner[keep].to(torch.int32)), host(map_sig), host(map_off), st.parts,
+                       host(sequence), host(map_base), host(map_sig), host(map_off), st.parts,
                        **extra)

@@ -11,6 +11,17 @@ def _dp(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _one(t):
+    """``t``, or a placeholder element where it is empty: the C-ABI takes no NULL for a batch that has reads"""
+    import torch
+    return t if t.numel() else torch.zeros(1, dtype=t.dtype, device=t.device)
+
+
+def _opt(t, n):
+    """The pointer of an optional per-read array: NULL for None and for a batch without reads"""
+    return _dp(t) if t is not None and n > 0 else C.c_void_p(0)
+
+
 def to_host(t):
     """A device tensor as a numpy array through page-locked host memory (torch keeps a cache of such blocks, so a
     caller that drops the previous batch's result gets the block back: no page faults on fresh memory, the copy at
@@ -1048,13 +1059,10 @@ def event_align_dev(context, level, ev_off, mu, ac, mc, base_off, l_stay, l_step
     hit = torch.zeros((max(n, 0), 4), dtype=torch.int32, device=dev)
     score = torch.zeros(max(n, 1), dtype=torch.float64, device=dev)
     base_event = torch.zeros(max(n_base, 1), dtype=torch.int32, device=dev)
-    # (a placeholder element where an array is empty: the C-ABI takes no NULL for a batch that has reads)
-    one = lambda t: t if t.numel() else torch.zeros(1, dtype=t.dtype, device=dev)
-    st = _dp(status_in) if status_in is not None and n > 0 else C.c_void_p(0)
-    _lib.check(lib.nvk_event_align_dev(context.handle, n, n_ev, _dp(one(level)), _dp(ev_off), n_base, _dp(one(mu)),
-                                       _dp(one(ac)), _dp(one(mc)), _dp(base_off), _dp(one(l_stay)), _dp(one(l_step)),
-                                       st, int(band), float(trim_cost), float(skip_cost), _dp(hit), _dp(score),
-                                       _dp(base_event)), 'nvk_event_align_dev')
+    _lib.check(lib.nvk_event_align_dev(context.handle, n, n_ev, _dp(_one(level)), _dp(ev_off), n_base, _dp(_one(mu)),
+                                       _dp(_one(ac)), _dp(_one(mc)), _dp(base_off), _dp(_one(l_stay)),
+                                       _dp(_one(l_step)), _opt(status_in, n), int(band), float(trim_cost),
+                                       float(skip_cost), _dp(hit), _dp(score), _dp(base_event)), 'nvk_event_align_dev')
     return hit, score[:n], base_event[:n_base]
 
 
@@ -1073,11 +1081,10 @@ def signal_locate_dev(context, level, q_off, mu, ac, mc, col_off, max_events, l_
     n_blocks = int(((lens + (_lib.LOC_BLOCK - 1)) // _lib.LOC_BLOCK).sum()) if nt > 0 else 0
     score = torch.zeros((max(nq, 0), n_blocks), dtype=torch.float64, device=dev)
     hit = torch.zeros((max(nq, 0), n_blocks, 4), dtype=torch.int32, device=dev)
-    one = lambda t: t if t.numel() else torch.zeros(1, dtype=t.dtype, device=dev)
-    _lib.check(lib.nvk_signal_locate_dev(context.handle, nq, n_ev, _dp(one(level)), _dp(q_off), nt, n_col,
-                                         _dp(one(mu)), _dp(one(ac)), _dp(one(mc)), _dp(col_off), int(max_events),
+    _lib.check(lib.nvk_signal_locate_dev(context.handle, nq, n_ev, _dp(_one(level)), _dp(q_off), nt, n_col,
+                                         _dp(_one(mu)), _dp(_one(ac)), _dp(_one(mc)), _dp(col_off), int(max_events),
                                          float(l_stay), float(l_step), float(l_skip), float(trim_cost), n_blocks,
-                                         _dp(one(score)), _dp(one(hit))), 'nvk_signal_locate_dev')
+                                         _dp(_one(score)), _dp(_one(hit))), 'nvk_signal_locate_dev')
     return score, hit
 
 
@@ -1097,13 +1104,12 @@ def viterbi_decode_dev(context, level, ev_off, k, central, mean, ac, mc, l_stay,
     score = torch.zeros(max(n, 1), dtype=torch.float64, device=dev)
     seq = torch.zeros(max(total_cap, 1), dtype=torch.int32, device=dev)
     base_event = torch.zeros(max(total_cap, 1), dtype=torch.int32, device=dev)
-    one = lambda t: t if t.numel() else torch.zeros(1, dtype=t.dtype, device=dev)
-    st = _dp(status_in) if status_in is not None and n > 0 else C.c_void_p(0)
     parts = C.c_int64(0)
-    _lib.check(lib.nvk_viterbi_decode_dev(context.handle, n, n_ev, _dp(one(level)), _dp(ev_off), int(k), int(central),
-                                          _dp(mean), _dp(ac), _dp(mc), float(l_stay), float(l_step), float(l_skip),
-                                          st, total_cap, _dp(cap_off), _dp(hit), _dp(score), _dp(seq),
-                                          _dp(base_event), C.byref(parts)), 'nvk_viterbi_decode_dev')
+    _lib.check(lib.nvk_viterbi_decode_dev(context.handle, n, n_ev, _dp(_one(level)), _dp(ev_off), int(k),
+                                          int(central), _dp(mean), _dp(ac), _dp(mc), float(l_stay), float(l_step),
+                                          float(l_skip), _opt(status_in, n), total_cap, _dp(cap_off), _dp(hit),
+                                          _dp(score), _dp(seq), _dp(base_event), C.byref(parts)),
+               'nvk_viterbi_decode_dev')
     return hit, score[:n], seq[:total_cap], base_event[:total_cap], int(parts.value)
 
 
@@ -1122,12 +1128,10 @@ def kmer_posterior_dev(context, level, ev_off, k, pos, mean, ac, mc, w_stay, w_s
     marg = torch.zeros((max(n_ev, 1), 4), dtype=torch.float64, device=dev)
     z = torch.zeros((max(n, 1), 2), dtype=torch.float64, device=dev)
     status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-    one = lambda t: t if t.numel() else torch.zeros(1, dtype=t.dtype, device=dev)
-    st = _dp(status_in) if status_in is not None and n > 0 else C.c_void_p(0)
     parts, ms = C.c_int64(0), (C.c_double * 2)(0.0, 0.0)
-    _lib.check(lib.nvk_kmer_posterior_dev(context.handle, n, n_ev, _dp(one(level)), _dp(ev_off), int(k), int(pos),
-                                          _dp(mean), _dp(ac), _dp(mc), float(w_stay), float(w_step), float(w_skip), st,
-                                          _dp(marg), _dp(z), _dp(status), C.byref(parts), ms if timing else None),
-               'nvk_kmer_posterior_dev')
+    _lib.check(lib.nvk_kmer_posterior_dev(context.handle, n, n_ev, _dp(_one(level)), _dp(ev_off), int(k), int(pos),
+                                          _dp(mean), _dp(ac), _dp(mc), float(w_stay), float(w_step), float(w_skip),
+                                          _opt(status_in, n), _dp(marg), _dp(z), _dp(status), C.byref(parts),
+                                          ms if timing else None), 'nvk_kmer_posterior_dev')
     out = (marg[:n_ev], z[:n], status[:n], int(parts.value))
     return out + ((float(ms[0]), float(ms[1])),) if timing else out

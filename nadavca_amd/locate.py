@@ -10,8 +10,9 @@ column of both strands: it serves references of up to some 10^5 bases, there is 
    ``signal_map_batch``'s own;
 3. the column tables of the targets — per contig its forward strand, then its reverse complement — by
    ``signal_map.base_tables_dev``;
-4. a rescale by moments: the events' per-read median and MAD are mapped onto those of ALL columns pooled (there is no
-   sequence to take them from).  A read with fewer than ``min_events`` events or a zero MAD is ``LOC_NO_EVENTS``;
+4. a rescale by moments (``rawsignal.rescale_by_moments_dev``): the events' per-read median and MAD are mapped onto
+   those of ALL columns pooled (there is no sequence to take them from).  A read with fewer than ``min_events`` events
+   or a zero MAD is ``LOC_NO_EVENTS``;
 5. chunks: a read of E events is cut into nc = ceil(E / max_events) chunks at (E * c) // nc, each one query;
 6. the operator (``nvk_signal_locate_dev``, contract in include/nadavca_hip.h): per (query, block of 256 columns) the
    best path's end value, end, start and trimmed events.  The queries run in parts whose block table fits a cap;
@@ -38,7 +39,9 @@ import math
 import numpy as np
 
 from . import _lib, defaults
-from .batchflow import load_kmer_model, seg_index
+from .batchflow import seg_index
+from .rawsignal import (SignalEvents, offsets_of, rescale_by_moments_dev, resolve_kmer_model, signal_events_dev,
+                        transition_costs)
 from .readbatch import BaseAlignmentBatch, ReadBatch
 from .refset import ReferenceSet
 
@@ -141,30 +144,10 @@ def block_tables(col_off):
     column) per block, int64 tensors."""
     import torch
     lens = col_off[1:] - col_off[:-1]
-    blk_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=col_off.device),
-                         torch.cumsum((lens + (BLOCK - 1)) // BLOCK, 0)])
+    blk_off = offsets_of((lens + (BLOCK - 1)) // BLOCK)
     target, inner = seg_index(blk_off)
     lo = inner * BLOCK
     return target, lo, torch.minimum(lo + BLOCK, lens[target])
-
-
-def rescale_pooled_dev(context, level, ev_off, mu, min_events):
-    """Stage 4 -> (scaled levels, ok bool per read).  The medians and MADs are ``nvk_normalize_groups_dev``'s exact
-    selections."""
-    import torch
-    from .device import normalize_groups_dev
-    dev = ev_off.device
-    n_ev = ev_off[1:] - ev_off[:-1]
-    one = lambda t: t if t.numel() else torch.zeros(1, dtype=torch.float64, device=dev)
-    _, cs_e = normalize_groups_dev(context, one(level), ev_off)
-    pool_off = torch.tensor([0, int(mu.numel())], dtype=torch.int64, device=dev)
-    _, cs_l = normalize_groups_dev(context, one(mu), pool_off)
-    ok = (n_ev >= int(min_events)) & (cs_e[:, 1] > 0) & (int(mu.numel()) > 0)
-    med_l, mad_l = cs_l[0, 0], cs_l[0, 1]
-    scale = mad_l / torch.where(ok, cs_e[:, 1], torch.ones_like(cs_e[:, 1]))
-    owner, _ = seg_index(ev_off, int(level.numel()))
-    scaled = (level - cs_e[:, 0][owner]) * scale[owner] + med_l
-    return scaled, ok
 
 
 def cut_chunks(n_ev, ok, max_events):
@@ -173,7 +156,7 @@ def cut_chunks(n_ev, ok, max_events):
     import torch
     E = torch.where(ok, n_ev, torch.zeros_like(n_ev))
     nc = (E + (max_events - 1)) // max_events
-    chunk_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=E.device), torch.cumsum(nc, 0)])
+    chunk_off = offsets_of(nc)
     read, c = seg_index(chunk_off)
     first = (E[read] * c) // nc[read]
     return chunk_off, read, first, (E[read] * (c + 1)) // nc[read] - first
@@ -280,18 +263,10 @@ def chain_chunks(chunk_off, target, start, end, first_event, last_event, margin,
     return status, anchor, joined
 
 
-class LocateStages:
+class LocateStages(SignalEvents):
     """The device tensors between the stages of one ``signal_locate_batch`` call (``signal_locate_stages``)."""
-    __slots__ = ('norm', 'sig_off', 'ev_off', 'ev_level', 'mu', 'ac', 'mc', 'col_off', 'scaled', 'ok', 'chunk_off',
-                 'chunk_read', 'chunk_first', 'chunk_events', 'q_off', 'q_level', 'blk', 'best', 'second', 'margin',
-                 'hit', 'parts', 'n_blocks', 'costs')
-
-
-def transition_costs(p_stay, p_skip):
-    """-> (l_stay, l_step, l_skip): the logs of p_stay, 1 - p_stay - p_skip and p_skip"""
-    if not (0.0 < p_stay < 1.0 and 0.0 < p_skip < 1.0 and p_stay + p_skip < 1.0):
-        raise ValueError('signal_locate_batch: p_stay, p_skip and 1 - p_stay - p_skip must lie inside (0, 1)')
-    return math.log(p_stay), math.log(1.0 - p_stay - p_skip), math.log(p_skip)
+    __slots__ = ('mu', 'ac', 'mc', 'col_off', 'scaled', 'ok', 'chunk_off', 'chunk_read', 'chunk_first', 'chunk_events',
+                 'q_off', 'q_level', 'blk', 'best', 'second', 'margin', 'hit', 'parts', 'n_blocks', 'costs')
 
 
 def signal_locate_stages(read_batch, targets, kmer_model, max_events, min_events, p_stay, p_skip, sigma_scale,
@@ -299,35 +274,28 @@ def signal_locate_stages(read_batch, targets, kmer_model, max_events, min_events
     """Stages 1 to 7 on the device -> LocateStages.  ``targets``: what ``target_tables`` returned; ``timer(name)``:
     called after each stage (bench tool)."""
     import torch
-    from .device import normalize_groups_dev
-    from .signal_map import base_tables_dev, detect_events_dev
+    from .signal_map import base_tables_dev
     context = kmer_model.context
     device = torch.device('cuda', context.device)
     rb, st = read_batch, LocateStages()
     tick = timer if timer is not None else (lambda name: None)
-    raw = torch.from_numpy(rb.raw_signal).to(device)
-    if raw.dtype != torch.float64:
-        raw = raw.to(torch.float64)
-    st.sig_off = torch.from_numpy(rb.sig_off).to(device)
     _, codes, col_off, _ = targets
     st.col_off = torch.from_numpy(col_off).to(device)
     sequence = torch.from_numpy(codes).to(device)
-    tick('upload')
-    st.norm = normalize_groups_dev(context, raw, st.sig_off, out=raw)[0] if rb.n and raw.numel() else raw
-    tick('normalise')
-    _, _, st.ev_off, _, _, st.ev_level = detect_events_dev(context, st.norm, st.sig_off, window, threshold, var_floor)
-    tick('events')
+    signal_events_dev(rb, context, window, threshold, var_floor, tick, into=st)
     st.mu, st.ac, st.mc = base_tables_dev(kmer_model, sequence, st.col_off, sigma_scale)
     tick('tables')
-    st.scaled, st.ok = rescale_pooled_dev(context, st.ev_level, st.ev_off, st.mu, min_events)
+    pool_off = torch.tensor([0, int(st.mu.numel())], dtype=torch.int64, device=device)
+    st.scaled, _, _, st.ok = rescale_by_moments_dev(context, st.ev_level, st.ev_off, st.mu, pool_off,
+                                                    min_events=min_events)
     st.chunk_off, st.chunk_read, st.chunk_first, st.chunk_events = cut_chunks(st.ev_off[1:] - st.ev_off[:-1], st.ok,
                                                                                max_events)
     # the queries' levels end to end: the events of the reads that take part
     owner, _ = seg_index(st.ev_off, int(st.ev_level.numel()))
     st.q_level = st.scaled[st.ok[owner]].contiguous()
-    st.q_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=device), torch.cumsum(st.chunk_events, 0)])
+    st.q_off = offsets_of(st.chunk_events)
     tick('rescale')
-    st.costs = transition_costs(p_stay, p_skip)
+    st.costs = transition_costs(p_stay, p_skip, 'signal_locate_batch')
     (st.blk, st.best, st.second, st.margin, st.hit), st.parts = locate_queries_dev(
         context, st.q_level, st.q_off, st.mu, st.ac, st.mc, st.col_off, max_events, *st.costs, trim_cost)
     st.n_blocks = int(block_tables(st.col_off)[0].numel())
@@ -348,9 +316,7 @@ def signal_locate_batch(read_batch, reference, kmer_model=defaults.KMER_MODEL_FI
     prototype used on the simulated reads of the test suite (dwell 3-17 samples, noise 0.35, the packaged 6-mer table,
     a 3 000-base genome), not values fitted to real data.  -> LocateBatch."""
     import torch
-    if isinstance(kmer_model, (str, bytes)) or hasattr(kmer_model, '__fspath__'):
-        from .kmer_model import load_kmer_model as load_on
-        kmer_model = load_on(kmer_model, context=context) if context is not None else load_kmer_model(kmer_model)
+    kmer_model = resolve_kmer_model(kmer_model, context)
     if not 1 <= int(max_events) <= _lib.LOC_MAX_EVENTS:
         raise ValueError('signal_locate_batch: max_events is 1..%d' % _lib.LOC_MAX_EVENTS)
     if int(min_events) < 1:

@@ -21,10 +21,10 @@ With ``SeedAligner`` for the approximate alignment every workflow then runs from
 """
 import math
 
-import numpy as np
-
 from . import _lib, defaults
-from .batchflow import load_kmer_model, seg_index
+from .batchflow import seg_index
+from .rawsignal import (SignalEvents, gaussian_constants, map_rows_dev, rescale_by_moments_dev, resolve_kmer_model,
+                        signal_events_dev)
 from .readbatch import ReadBatch
 
 MAP_OK, MAP_NO_EVENTS, MAP_LOST = _lib.MAP_OK, _lib.MAP_NO_EVENTS, _lib.MAP_LOST
@@ -70,8 +70,7 @@ def base_tables_dev(kmer_model, sequence, seq_off, sigma_scale):
     n, total = int(seq_off.numel()) - 1, int(sequence.numel())
     alphabet = kmer_model.get_alphabet_size()
     codes = torch.where((sequence < 0) | (sequence >= alphabet), torch.zeros_like(sequence), sequence).contiguous()
-    sd = np.asarray(kmer_model.sigma, dtype=np.float64) * float(sigma_scale)
-    tables = (None, -np.log(sd * math.sqrt(2.0 * math.pi)), 1.0 / (2.0 * sd * sd))
+    tables = (None,) + gaussian_constants(kmer_model.sigma, sigma_scale)
     none = torch.zeros(1, dtype=torch.int32, device=dev)
     none_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     out = []
@@ -90,7 +89,7 @@ def base_tables_dev(kmer_model, sequence, seq_off, sigma_scale):
     return out
 
 
-def transition_costs(n_events, n_bases):
+def dwell_costs(n_events, n_bases):
     """-> (l_stay, l_step) f64 per read from its event and base counts (tensors):
     p_stay = max(1 - 1 / max(E / K, 1.0001), 0.05), l_stay = log p_stay, l_step = log max(1 - p_stay - 1e-10, 1e-3)."""
     import torch
@@ -99,75 +98,29 @@ def transition_costs(n_events, n_bases):
     return torch.log(p_stay), torch.log(torch.clamp(1.0 - p_stay - 1e-10, min=1e-3))
 
 
-class SignalMapStages:
+class SignalMapStages(SignalEvents):
     """The device tensors between the stages of one ``signal_map_batch`` call (``signal_map_stages``)."""
-    __slots__ = ('norm', 'sig_off', 'seq_off', 'flags', 'ev_pos', 'ev_off', 'ev_start', 'ev_len', 'ev_level', 'mu',
-                 'ac', 'mc', 'status_in', 'shift', 'scale', 'scaled', 'l_stay', 'l_step', 'hit', 'path_score',
-                 'base_event')
-
-
-def detect_events_dev(context, norm, sig_off, window, threshold, var_floor):
-    """Stage 2 on normalised signals -> (flags, ev_pos, ev_off, ev_start, ev_len, ev_level), device tensors."""
-    import torch
-    from .device import event_flags_dev, event_levels_dev
-    flags = event_flags_dev(context, norm, sig_off, window, threshold, var_floor)
-    ev_pos = torch.nonzero(flags).reshape(-1)
-    before = torch.cat([torch.zeros(1, dtype=torch.int64, device=flags.device), torch.cumsum(flags, 0)])
-    ev_off = before[sig_off].contiguous()
-    start, length, level = event_levels_dev(context, norm, sig_off, ev_pos)
-    return flags, ev_pos, ev_off, start, length, level
-
-
-def rescale_by_moments_dev(context, level, ev_off, mu, seq_off):
-    """Stage 3: per read the events' levels mapped so that their median and MAD are those of the read's expected
-    levels, both from ``nvk_normalize_groups_dev``'s exact selections.  -> (scaled levels, shift, scale, status int32:
-    MAP_NO_EVENTS where a read has no event, no base or a zero MAD of its events)."""
-    import torch
-    from .device import normalize_groups_dev
-    n = int(ev_off.numel()) - 1
-    n_ev, n_base = ev_off[1:] - ev_off[:-1], seq_off[1:] - seq_off[:-1]
-    one = lambda t: t if t.numel() else torch.zeros(1, dtype=torch.float64, device=ev_off.device)
-    _, cs_e = normalize_groups_dev(context, one(level), ev_off)
-    _, cs_l = normalize_groups_dev(context, one(mu), seq_off)
-    ok = (n_ev > 0) & (n_base > 0) & (cs_e[:, 1] > 0)
-    status = torch.where(ok, 0, MAP_NO_EVENTS).to(torch.int32)
-    scale = torch.where(ok, cs_l[:, 1] / torch.where(ok, cs_e[:, 1], torch.ones_like(cs_e[:, 1])),
-                        torch.ones(n, dtype=torch.float64, device=ev_off.device))
-    med_e = torch.where(ok, cs_e[:, 0], torch.zeros_like(scale))
-    med_l = torch.where(ok, cs_l[:, 0], torch.zeros_like(scale))
-    owner, _ = seg_index(ev_off, int(level.numel()))
-    scaled = (level - med_e[owner]) * scale[owner] + med_l[owner]
-    return scaled, med_l - med_e * scale, scale, status
+    __slots__ = ('seq_off', 'mu', 'ac', 'mc', 'status_in', 'shift', 'scale', 'scaled', 'l_stay', 'l_step', 'hit',
+                 'path_score', 'base_event')
 
 
 def signal_map_stages(read_batch, kmer_model, window, threshold, var_floor, band, sigma_scale, trim_cost, skip_cost,
                       timer=None):
     """The four stages on the device -> SignalMapStages.  ``timer(name)``: called after each stage (bench tool)."""
     import torch
-    from .device import event_align_dev, normalize_groups_dev
+    from .device import event_align_dev
     context = kmer_model.context
     device = torch.device('cuda', context.device)
     rb, st = read_batch, SignalMapStages()
     tick = timer if timer is not None else (lambda name: None)
-    raw = torch.from_numpy(rb.raw_signal).to(device)
-    if raw.dtype != torch.float64:
-        raw = raw.to(torch.float64)
-    st.sig_off = torch.from_numpy(rb.sig_off).to(device)
     st.seq_off = torch.from_numpy(rb.seq_off).to(device)
     sequence = torch.from_numpy(rb.sequence).to(device)
-    tick('upload')
-    if rb.n and raw.numel():
-        st.norm, _ = normalize_groups_dev(context, raw, st.sig_off, out=raw)
-    else:
-        st.norm = raw
-    tick('normalise')
-    st.flags, st.ev_pos, st.ev_off, st.ev_start, st.ev_len, st.ev_level = detect_events_dev(
-        context, st.norm, st.sig_off, window, threshold, var_floor)
-    tick('events')
+    signal_events_dev(rb, context, window, threshold, var_floor, tick, into=st)
     st.mu, st.ac, st.mc = base_tables_dev(kmer_model, sequence, st.seq_off, sigma_scale)
-    st.scaled, st.shift, st.scale, st.status_in = rescale_by_moments_dev(context, st.ev_level, st.ev_off, st.mu,
-                                                                         st.seq_off)
-    st.l_stay, st.l_step = transition_costs(st.ev_off[1:] - st.ev_off[:-1], st.seq_off[1:] - st.seq_off[:-1])
+    # (a read with no event, no base or a zero MAD of its events is not aligned)
+    st.scaled, st.shift, st.scale, ok = rescale_by_moments_dev(context, st.ev_level, st.ev_off, st.mu, st.seq_off)
+    st.status_in = torch.where(ok, 0, MAP_NO_EVENTS).to(torch.int32)
+    st.l_stay, st.l_step = dwell_costs(st.ev_off[1:] - st.ev_off[:-1], st.seq_off[1:] - st.seq_off[:-1])
     tick('rescale')
     st.hit, st.path_score, st.base_event = event_align_dev(
         context, st.scaled, st.ev_off, st.mu, st.ac, st.mc, st.seq_off, st.l_stay, st.l_step, st.status_in, band,
@@ -190,9 +143,7 @@ def signal_map_batch(read_batch, kmer_model=defaults.KMER_MODEL_FILE, window=2, 
     to real data.  -> SignalMapBatch.  A read that is not mapped gets no rows: downstream it has no anchors and is
     not live, like a read the aligner did not place."""
     import torch
-    if isinstance(kmer_model, (str, bytes)) or hasattr(kmer_model, '__fspath__'):
-        from .kmer_model import load_kmer_model as load_on
-        kmer_model = load_on(kmer_model, context=context) if context is not None else load_kmer_model(kmer_model)
+    kmer_model = resolve_kmer_model(kmer_model, context)
     if band not in (64, 128):
         raise ValueError('signal_map_batch: band is 64 or 128')
     rb = read_batch
@@ -207,12 +158,7 @@ def signal_map_batch(read_batch, kmer_model=defaults.KMER_MODEL_FILE, window=2, 
                         torch.full_like(st.path_score, float('nan')))
     total_bases = int(rb.seq_off[-1])
     owner, inner = seg_index(st.seq_off, total_bases)
-    keep = st.base_event >= 0
-    k_owner = owner[keep]
-    map_base = inner[keep].to(torch.int32)
-    map_sig = st.ev_start[st.ev_off[:-1][k_owner] + st.base_event[keep].to(torch.int64)]
-    map_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=owner.device),
-                         torch.cumsum(torch.bincount(k_owner, minlength=rb.n), 0)])
+    map_base, map_sig, map_off, _, _ = map_rows_dev(owner, inner, st.base_event, st.ev_start, st.ev_off, rb.n)
     host = lambda t: t.cpu().numpy()
     ev = (host(st.ev_off), host(st.ev_start), host(st.ev_len), host(st.ev_level)) if events else (None,) * 4
     return SignalMapBatch(host(status), host(st.hit[:, 1]), host(score), host(st.shift), host(st.scale),
