@@ -251,6 +251,43 @@ int nvk_refine_alignment_batch_dev(nvk_model *model, int64_t n_reads, int64_t to
                                    int model_transitions, int32_t *out_events,
                                    int32_t *out_status);
 
+/* PLAN ONCE, SWEEP AGAIN.  Before its sweeps a refine call plans the batch: bands, lane records, launch order and step
+ * counts, about 3 % of a 10 000-read call, plus a round trip to the host that the sweeps wait for.  That plan is a
+ * function of the read GEOMETRY only — n_reads, the three totals, sig_off, reference, ref_off, both contexts and their
+ * offsets, anchors and anc_off, bandwidth, min_event_length, model_transitions and the model — and of no sample.  A
+ * caller that aligns one resident batch again and again (align, re-fit the signal in place, align again) says so with
+ * a token:
+ *   nvk_plan_token_new   a fresh token: process-wide, monotonic, never 0.  Thread-safe.
+ *   nvk_refine_alignment_batch_dev_keyed   nvk_refine_alignment_batch_dev with a token as its last argument.
+ * CONTRACT: one token stands for ONE IMMUTABLE GEOMETRY.  Between two calls with the same token the arrays and scalars
+ * listed above hold the same values at the same addresses; the samples behind `signal` (and the pointer itself) may
+ * change freely, and so may the output arrays.  A caller that changes any of the geometry takes a new token.  The
+ * addresses alone never identify a batch (an allocator gives the next batch of the same shape the same ones); they
+ * are compared as a cross-check only.
+ * A ctx holds at most one plan: that of the last keyed call that planned on it.  A keyed call whose token, model,
+ * scalars, totals and addresses equal the held plan's sweeps from it: no planner and no order kernels are launched
+ * (NVK_K_PLAN counts none), and nothing is copied or waited for before the sweeps are queued.  Any other call plans
+ * as ever and, if its token is not 0, leaves its plan behind; that is never an error.  Token 0 — which is what
+ * nvk_refine_alignment_batch_dev passes, and with it the lanes of the host-pointer entries — never reuses and leaves
+ * no plan.  The held plan is dropped by whatever overwrites it: another refine call that plans, any of the
+ * log-likelihood operators, a workspace of the plan that has to grow; a destroyed model's plan can never match again.
+ * Results, status, tie flags, batch statistics and the launch report of a call that reused are those of one that
+ * planned, bit for bit (tests/test_gpu_plan_reuse.py).
+ * NADAVCA_PLAN_REUSE=0 (read at every call) makes every call plan.  NADAVCA_ALIGN_KERNEL=1 plans with the exact
+ * kernel's row table; a plan made in one of the two modes serves only calls in that mode.
+ *   nvk_last_plan_reused   *reused = 1 if the last refine call on the ctx swept from a held plan, else 0 */
+uint64_t nvk_plan_token_new(void);
+int nvk_refine_alignment_batch_dev_keyed(nvk_model *model, int64_t n_reads, int64_t total_signal,
+                                         int64_t total_ref, int64_t total_anchors, const double *signal,
+                                         const int64_t *sig_off, const int32_t *reference,
+                                         const int64_t *ref_off, const int32_t *ctx_before,
+                                         const int64_t *cb_off, const int32_t *ctx_after,
+                                         const int64_t *ca_off, const int32_t *anchors,
+                                         const int64_t *anc_off, int bandwidth, int min_event_length,
+                                         int model_transitions, int32_t *out_events,
+                                         int32_t *out_status, uint64_t plan_token);
+int nvk_last_plan_reused(nvk_ctx *ctx, int *reused);
+
 /* The same operator for a STREAM of batches (T_e2e of SURVEY.md 8d: host arrays in, host arrays out, the PCIe
  * copies hidden behind the kernels).  The reference pays its copy-in / copy-out around every call
  * (dtwmodule.cpp:19-28); here nvk_refine_alignment_submit uploads batch k+1 and returns at once with a ticket

@@ -77,6 +77,9 @@ SIGNATURES = {
     'nvk_refine_alignment_submit': (_int, [_vp, _i64] + [_vp] * 10 + [_int, _int, _int, _vp, _vp, _vp, C.POINTER(_i64)]),
     'nvk_refine_alignment_wait': (_int, [_vp, _i64]),
     'nvk_refine_alignment_batch_dev': (_int, _BATCH_DEV + [_vp, _vp]),
+    'nvk_plan_token_new': (C.c_uint64, []),
+    'nvk_refine_alignment_batch_dev_keyed': (_int, _BATCH_DEV + [_vp, _vp, C.c_uint64]),
+    'nvk_last_plan_reused': (_int, [_vp, C.POINTER(_int)]),
     'nvk_estimate_log_likelihoods_batch': (_int, [_vp, _i64] + [_vp] * 10 + [_int, _int, _int, _vp, _vp]),
     'nvk_estimate_log_likelihoods_batch_dev': (_int, _BATCH_DEV + [_vp, _vp]),
     'nvk_estimate_hypotheses_batch_dev': (_int, _BATCH_DEV + [_i64] + [_vp] * 6),
@@ -234,6 +237,13 @@ class Context:
                     reads_tie_ambiguous=e.value, reads_tie_exact=f.value, reads_tie_near=g.value,
                     reads_tie_ulp=h.value)
 
+    def last_plan_reused(self):
+        """Whether the last refine_alignment call on this context swept from the plan an earlier call with the same
+        batch token left (include/nadavca_hip.h: plan once, sweep again) and so launched no planner."""
+        r = _int()
+        check(self._lib.nvk_last_plan_reused(self.handle, C.byref(r)), 'nvk_last_plan_reused')
+        return bool(r.value)
+
     def last_tie_flags(self, n_reads):
         """Per read of the last refine_alignment batch: TIE_EXACT | TIE_NEAR | TIE_ULP where a path comparison fell
         inside the tie margin (include/nadavca_hip.h, parity contract)."""
@@ -289,6 +299,11 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+def plan_token_new():
+    """A fresh batch token (nvk_plan_token_new): process-wide, never 0.  Needs no GPU."""
+    return int(load().nvk_plan_token_new())
 
 
 def built_sweep_variants():

@@ -7,12 +7,23 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <new>
 #include <vector>
 
 #include "nvk_internal.h"
 
 static thread_local char g_err[512] = "";
+
+// process-wide serial numbers, never 0 and never handed out twice: batch tokens and model ids (plan_key.h)
+static uint64_t next_serial() {
+  static std::atomic<uint64_t> serial{0};
+  uint64_t v;
+  do v = serial.fetch_add(1, std::memory_order_relaxed) + 1; while (v == 0);
+  return v;
+}
+
+extern "C" uint64_t nvk_plan_token_new(void) { return next_serial(); }
 
 void nvk_set_error(const char *fmt, ...) {
   va_list ap;
@@ -60,6 +71,10 @@ int nvk_ws_reserve(nvk_ctx *ctx, int which, size_t bytes) {
     NVK_HIP(hipStreamSynchronize(ctx->stream));
     NVK_HIP(hipStreamSynchronize(ctx->stream2));
   }
+  // (a held plan lies in these blocks — WS_MISC: its totals, WS_ROWS: its row table — and goes with the one that moves)
+  if (which == WS_META || which == WS_LANE_F || which == WS_LANE_R || which == WS_OFFS || which == WS_ORDER ||
+      which == WS_STEPS || which == WS_MISC || which == WS_ROWS)
+    plan_key::clear(ctx->plan_key);
   return nvk_grow(&ctx->ws[which], &ctx->ws_bytes[which], bytes, false, "workspace");
 }
 
@@ -211,6 +226,12 @@ extern "C" int nvk_last_retry_count(nvk_ctx *ctx, int64_t *n_reads) {
   return NVK_OK;
 }
 
+extern "C" int nvk_last_plan_reused(nvk_ctx *ctx, int *reused) {
+  if (!ctx || !reused) return NVK_ERR_INVALID;
+  *reused = ctx->plan_reused;
+  return NVK_OK;
+}
+
 extern "C" int nvk_last_tie_count(nvk_ctx *ctx, int64_t *n_reads) {
   if (!ctx || !n_reads) return NVK_ERR_INVALID;
   *n_reads = ctx->last_ties;
@@ -331,6 +352,7 @@ extern "C" int nvk_model_create(nvk_ctx *ctx, int k, int central_position, int a
   }
   memset(m, 0, sizeof *m);
   m->ctx = ctx;
+  m->id = next_serial();  // (a destroyed model's plan dies with its id: no later model has it)
   size_t bytes = (size_t)n * sizeof(double);
   int rc;
   if ((rc = nvk_alloc((void **)&m->d_mean, bytes, false, "k-mer table")) ||
@@ -504,6 +526,7 @@ int plan_batch_queue(nvk_model *model, const BatchArgs &a, int mode, int write_r
   int64_t n = a.n_reads;
   int64_t rows_total = (mode == PLAN_ALIGN_TRANS) ? 2 * a.total_ref : a.total_ref + n;
   int rc;
+  plan_key::clear(ctx->plan_key);  // (the plan held so far is overwritten from here on)
   ctx->rows_current = 0;  // (whatever WS_ROWS holds belongs to an earlier batch from here on)
   ctx->meta_n = -1;       // (... and WS_META)
   if ((rc = nvk_ws_reserve(ctx, WS_META, (size_t)(n + 1) * sizeof(ReadMeta) + 64))) return rc;
@@ -544,6 +567,18 @@ int plan_batch_wait(nvk_ctx *ctx, int64_t n, PlanTotals &tot, const int32_t **st
   ctx->last_cells = (int64_t)tot.cells;
   ctx->last_steps = (int64_t)tot.steps;
   return NVK_OK;
+}
+
+// What plan_batch_queue + plan_batch_wait hand their caller, taken from the plan the ctx holds (ctx->plan_key matches
+// the call): the planner's results are a function of the read geometry alone, the workspaces and the pinned block
+// still hold them, so nothing is launched, copied or waited for.
+void plan_batch_held(nvk_ctx *ctx, PlanTotals &tot, const int **order, const int32_t **steps_sorted) {
+  const PlanHost *hp = (const PlanHost *)ctx->h_plan;
+  tot = hp->tot;
+  *steps_sorted = hp->steps;
+  *order = (const int *)ctx->ws[WS_ORDER];
+  ctx->last_cells = (int64_t)tot.cells;
+  ctx->last_steps = (int64_t)tot.steps;
 }
 
 // The row table for a batch that was planned without it (plan_batch_queue, write_rows 0): the planner once more, with
@@ -615,19 +650,20 @@ extern "C" int nvk_expected_signal_batch(nvk_model *model, int64_t n_reads,
 // ---------------------------------------------------------------------------------------------
 // refine_alignment
 // ---------------------------------------------------------------------------------------------
-extern "C" int nvk_refine_alignment_batch_dev(
+extern "C" int nvk_refine_alignment_batch_dev_keyed(
     nvk_model *model, int64_t n_reads, int64_t total_signal, int64_t total_ref,
     int64_t total_anchors, const double *signal, const int64_t *sig_off, const int32_t *reference,
     const int64_t *ref_off, const int32_t *ctx_before, const int64_t *cb_off,
     const int32_t *ctx_after, const int64_t *ca_off, const int32_t *anchors,
     const int64_t *anc_off, int bandwidth, int min_event_length, int model_transitions,
-    int32_t *out_events, int32_t *out_status) {
+    int32_t *out_events, int32_t *out_status, uint64_t plan_token) {
   BatchArgs a;
   int rc = dev_batch(model, n_reads, total_signal, total_ref, total_anchors, signal, sig_off, reference, ref_off,
                      ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off, bandwidth, min_event_length,
                      out_status, a);
   if (rc) return rc;
   nvk_launch_reset(model->ctx);
+  model->ctx->plan_reused = 0;
   if (n_reads == 0) return rc;
   nvk_ctx *ctx = model->ctx;
   PlanTotals tot;
@@ -655,9 +691,24 @@ extern "C" int nvk_refine_alignment_batch_dev(
     NVK_HIP(hipMemsetAsync(ctx->ws[WS_TIES], 0, (size_t)(n_reads + 8) * sizeof(int32_t), ctx->stream));
     return exact_all ? NVK_OK : align3_prepare(ctx, &spill_cap);
   };
-  rc = plan_batch_queue(model, a, mode, exact_all ? 1 : 0, &order, &meanwhile);
-  if (rc) return rc;
-  if ((rc = plan_batch_wait(ctx, n_reads, tot, &steps_sorted))) return rc;
+  // A batch planned before under the same token (include/nadavca_hip.h: one token, one immutable geometry) and still
+  // held by the ctx is not planned again: the sweeps are queued with nothing asked of the device first.  Decided
+  // behind the reservations above, which drop the key if they move a block the plan lies in.
+  // NADAVCA_PLAN_REUSE=0 (read per call, like NADAVCA_ALIGN_KERNEL): plan every call.
+  const char *reuse_env = getenv("NADAVCA_PLAN_REUSE");
+  const plan_key::Key want = {plan_token, model->id, bandwidth, min_event_length, model_transitions ? 1 : 0,
+                              exact_all ? 1 : 0, n_reads, total_signal, total_ref, total_anchors,
+                              {sig_off, reference, ref_off, ctx_before, cb_off, ctx_after, ca_off, anchors, anc_off}};
+  if (!(reuse_env && reuse_env[0] == '0') && plan_key::matches(ctx->plan_key, want)) {
+    if ((rc = meanwhile())) return rc;
+    plan_batch_held(ctx, tot, &order, &steps_sorted);
+    ctx->plan_reused = 1;
+  } else {
+    rc = plan_batch_queue(model, a, mode, exact_all ? 1 : 0, &order, &meanwhile);
+    if (rc) return rc;
+    if ((rc = plan_batch_wait(ctx, n_reads, tot, &steps_sorted))) return rc;
+    if (plan_token) ctx->plan_key = want;
+  }
   ctx->ties_n = n_reads;
   ctx->ties_host = nullptr;
   ctx->meta_n = n_reads;
@@ -704,6 +755,20 @@ extern "C" int nvk_refine_alignment_batch_dev(
   return NVK_OK;
 }
 
+extern "C" int nvk_refine_alignment_batch_dev(
+    nvk_model *model, int64_t n_reads, int64_t total_signal, int64_t total_ref,
+    int64_t total_anchors, const double *signal, const int64_t *sig_off, const int32_t *reference,
+    const int64_t *ref_off, const int32_t *ctx_before, const int64_t *cb_off,
+    const int32_t *ctx_after, const int64_t *ca_off, const int32_t *anchors,
+    const int64_t *anc_off, int bandwidth, int min_event_length, int model_transitions,
+    int32_t *out_events, int32_t *out_status) {
+  // token 0: plans every call and leaves no plan behind
+  return nvk_refine_alignment_batch_dev_keyed(model, n_reads, total_signal, total_ref, total_anchors, signal, sig_off,
+                                              reference, ref_off, ctx_before, cb_off, ctx_after, ca_off, anchors,
+                                              anc_off, bandwidth, min_event_length, model_transitions, out_events,
+                                              out_status, 0);
+}
+
 // ---------------------------------------------------------------------------------------------
 // estimate_log_likelihoods
 // ---------------------------------------------------------------------------------------------
@@ -716,6 +781,7 @@ int ell_run(nvk_model *model, const BatchArgs &a, int model_wobbling, double *ou
   nvk_ctx *ctx = model->ctx;
   const int64_t n = n_reads, nrow = total_ref + n;
   nvk_launch_reset(ctx);  // (also: WS_META takes this batch's metas)
+  plan_key::clear(ctx->plan_key);  // (... and WS_ORDER its order: a refine plan held so far is gone)
   if ((rc = nvk_ws_reserve(ctx, WS_META, (size_t)(n + 1) * sizeof(ReadMeta) + 64))) return rc;
   ctx->rows_current = 0;  // (WS_ROWS takes this operator's descriptors)
   if ((rc = nvk_ws_reserve(ctx, WS_ROWS, (size_t)(total_ref + 1) * sizeof(FusedParam)))) return rc;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/nadavca_hip.h"
+#include "plan_key.h"
 
 // ----- device-side tables ---------------------------------------------------------------
 // One entry per DP row r of a read.  A "row" is a boundary line of the banded matrix
@@ -116,6 +117,12 @@ struct nvk_ctx {
   // then the reads' step counts in launch order (refine_alignment; sizes the spill slots)
   void *h_plan;
   size_t h_plan_cap;
+  // The plan this ctx holds (plan_key.h): set when a keyed refine call has planned, while WS_META, WS_LANE_F,
+  // WS_LANE_R, WS_OFFS, WS_ORDER, WS_STEPS, the device totals and h_plan still hold what its planner left; cleared by
+  // whatever plans anew (plan_batch_queue, ell_run) or lets one of those blocks go (nvk_ws_reserve).  rows_current
+  // goes on saying whether WS_ROWS holds that plan's row table.
+  plan_key::Key plan_key;
+  int plan_reused;       // the last refine call on this ctx swept from the held plan (nvk_last_plan_reused)
   int spill_share;       // > 1: this ctx is one of that many lanes of a pipelined host path sharing the device
   struct nvk_pipe_state *pipe;  // lanes of the pipelined host-pointer entry points (pipeline.hip), made on first use
 };
@@ -134,6 +141,7 @@ struct nvk_model {
   nvk_ctx *ctx;
   DeviceModel dm;
   double *d_mean, *d_ac, *d_mc;
+  uint64_t id;  // process-wide, never reused: what a plan key names the model by
 };
 
 

@@ -39,7 +39,28 @@ def to_host(t):
 
 
 class DeviceBatch:
-    """A flat batch (nadavca_amd.dtw.FlatBatch / synthetic.Batch layout) copied to one GPU."""
+    """A flat batch (nadavca_amd.dtw.FlatBatch / synthetic.Batch layout) copied to one GPU.
+
+    ``plan_token`` names the batch's geometry to the library (include/nadavca_hip.h: plan once, sweep again): the
+    first ``refine_alignment_dev`` of the batch plans it, later ones with the same settings sweep from that plan for
+    as long as the context holds it.  ``signal`` may be rewritten or replaced between calls; see
+    ``geometry_changed``."""
+
+    GEOMETRY = ('sig_off', 'reference', 'ref_off', 'context_before', 'cb_off', 'context_after', 'ca_off', 'anchors',
+                'anc_off', 'n', 'total_signal', 'total_ref', 'total_anchors')
+
+    def __setattr__(self, name, value):
+        object.__setattr__(self, name, value)
+        if name in self.GEOMETRY and 'plan_token' in self.__dict__:   # (a geometry field replaced after construction)
+            self.geometry_changed()
+
+    def geometry_changed(self):
+        """Take a new plan token: the next ``refine_alignment_dev`` plans again.  To be called after the VALUES of a
+        geometry field were changed in place — ``sig_off``, ``reference``, ``ref_off``, ``context_before``,
+        ``cb_off``, ``context_after``, ``ca_off``, ``anchors``, ``anc_off`` (the planner reads all of them; the counts
+        ``n`` and ``total_*`` follow from the offsets).  Assigning a new tensor to one of these attributes does it by
+        itself; ``signal`` is no geometry."""
+        object.__setattr__(self, 'plan_token', _lib.plan_token_new())
 
     def __init__(self, batch, device):
         import torch
@@ -60,6 +81,7 @@ class DeviceBatch:
         self.total_signal = int(batch.sig_off[-1])
         self.total_ref = int(batch.ref_off[-1])
         self.total_anchors = int(batch.anc_off[-1])
+        self.geometry_changed()
         torch.cuda.synchronize(self.device)
 
     @classmethod
@@ -93,6 +115,7 @@ class DeviceBatch:
         self.anc_off = sa.anc_off.to(dev).contiguous()
         self.total_ref = int(sa.ref_off[-1])
         self.total_anchors = int(sa.anc_off[-1])
+        self.geometry_changed()
         return self
 
     def pointers(self):
@@ -115,17 +138,18 @@ class DeviceBatch:
 
 def refine_alignment_dev(dbatch, bandwidth, min_event_length, kmer_model, model_transitions,
                          events=None, status=None):
-    """Device in, device out: -> (events int32 (sum R, 2), status int32 (n,)) torch tensors."""
+    """Device in, device out: -> (events int32 (sum R, 2), status int32 (n,)) torch tensors.  The batch's plan token
+    goes with the call, so a batch aligned again with the same settings is not planned again (DeviceBatch)."""
     torch = dbatch.torch
     lib = _lib.load()
     if events is None:
         events = torch.zeros((dbatch.total_ref, 2), dtype=torch.int32, device=dbatch.device)
     if status is None:
         status = torch.zeros(dbatch.n, dtype=torch.int32, device=dbatch.device)
-    _lib.check(lib.nvk_refine_alignment_batch_dev(
+    _lib.check(lib.nvk_refine_alignment_batch_dev_keyed(
         kmer_model.handle, dbatch.n, dbatch.total_signal, dbatch.total_ref, dbatch.total_anchors,
         *dbatch.pointers(), int(bandwidth), int(min_event_length), int(bool(model_transitions)),
-        _dp(events), _dp(status)), 'nvk_refine_alignment_batch_dev')
+        _dp(events), _dp(status), getattr(dbatch, 'plan_token', 0)), 'nvk_refine_alignment_batch_dev_keyed')
     return events, status
 
 
