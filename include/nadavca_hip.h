@@ -1176,6 +1176,37 @@ int nvk_kmer_posterior_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_events, 
                            const double *mc, double w_stay, double w_step, double w_skip, const int32_t *status_in,
                            double *out_marg, double *out_z, int32_t *out_status, int64_t *out_parts, double *out_ms);
 
+/* K-MER EXPECTATIONS (decode_batch(fit=n)).  The E-step of a Baum-Welch fit over the same states, moves and sweeps as
+ * the posteriors above: per read the expected number of each move and the posterior-weighted moments of its events'
+ * levels against the states' means.  The inputs are nvk_kmer_posterior_dev's without `pos`; EXP, b, frexp, forward (A,
+ * X), backward (B, W, G4, G16) and the rule for sums over all states are that contract's, and the forward sweep is its
+ * own kernel, so out_z's bits are that call's.  Every expression is a rounded f64 operation in the order written; the
+ * kernels call no library exp or log and use no atomics.  x_i = level[ev_off[r] + i].
+ *   per event  i = E-1 down to 0, every sum over all states by the rule above:
+ *              D  = sum of A(i, s) * B(i, s)
+ *              m0 = sum of (A(i, s) * B(i, s)) * mc[s];  m1 = sum of ((A * B) * mc[s]) * mean[s];
+ *              m2 = sum of (((A * B) * mc[s]) * mean[s]) * mean[s]
+ *              M0 += m0 / D;  Mx += (m0 / D) * x_i;  Mxx += ((m0 / D) * x_i) * x_i;
+ *              Mm += m1 / D;  Mxm += (m1 / D) * x_i;  Mmm += m2 / D
+ *              F += 1.0 when the largest em(i, s) over s is <= -300.0 (every b(i, .) sits on the floor: the event's
+ *              Gaussian moments are the floor's, not the model's)
+ *   per move   i -> i + 1, for i < E-1, with W, G4 and G16 those the backward recurrence forms from event i + 1:
+ *              n_stay = sum of A(i, s) * (w_stay * W[s]);  n_step = sum of A(i, s) * (w_step * G4[s mod Q]);
+ *              n_skip = sum of A(i, s) * (w_skip * G16[s mod T]);  t = (n_stay + n_step) + n_skip;
+ *              N_stay += n_stay / t;  N_step += n_step / t;  N_skip += n_skip / t
+ *              (ratios inside one event: no exponent enters; the three shares of a move sum to 1, so the three N sum
+ *              to E - 1 up to rounding)
+ *   order      every accumulator starts at 0.0 and takes its terms with i descending
+ * out_stats f64[10 n_reads]: per read (M0, Mx, Mxx, Mm, Mxm, Mmm, N_stay, N_step, N_skip, F).  out_z, out_status,
+ * out_parts and out_ms ([0] the forward launches, [1] the counts launches) are nvk_kmer_posterior_dev's; a read that is
+ * not processed writes no stats and reports out_z = (0, 0).  The row store, its cap, the cut into parts (results do not
+ * change), the checks and the return codes are that call's.  Device pointers but out_parts and out_ms. */
+int nvk_kmer_expectations_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_events, const double *level,
+                              const int64_t *ev_off, int k, const double *mean, const double *ac, const double *mc,
+                              double w_stay, double w_step, double w_skip, const int32_t *status_in,
+                              double *out_stats, double *out_z, int32_t *out_status, int64_t *out_parts,
+                              double *out_ms);
+
 #ifdef __cplusplus
 }
 #endif

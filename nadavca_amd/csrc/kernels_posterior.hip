@@ -28,6 +28,9 @@
 // aligner's traceback workspace, as the Viterbi store is; the host cuts a batch into parts whose rows fit the cap and
 // runs the forward and the backward sweep of a part before the next part's.
 //
+// THE COUNTS SWEEP of nvk_kmer_expectations_dev (decode_batch(fit=n)) stands where the backward sweep does and is
+// described at its kernel; its CPU restatement is tests/host_shims/expect_host.cpp.
+//
 // No atomics, no scratch, no library exp or log: EXP is rint, the fma chain of xm::exp2_frac_horner and ldexp.  With
 // -ffp-contract=off every value is the rounded operation the contract writes, on the device as on the host.
 #include <vector>
@@ -282,24 +285,191 @@ posterior_backward_kernel(PostArgs a) {
   }
 }
 
-void launch_sweep(bool forward, int k, const PostArgs &a, int n, hipStream_t stream) {
+// THE COUNTS SWEEP (nvk_kmer_expectations_dev) is the backward sweep with the E-step's sums where that one forms the
+// letter marginals: the same layout, recurrence, G4 / G16 buffers and one barrier per event.  Per event it reduces
+// seven sums over all states instead of four -- D and the three moment sums of A * B, and for the move i -> i + 1 the
+// three numerators -- and the largest em of the event.  The move's terms of event i + 1 are still there when row i
+// arrives: W in the registers the last iteration left it in (it is overwritten only after the stay terms are formed),
+// w_step * G4 and w_skip * G16 in the LDS buffers of the other parity, which the barrier of iteration i + 1 published
+// and nobody writes before the barrier of iteration i.  Thread 0 keeps the read's ten accumulators and takes every
+// event's shares after its barrier, so the events enter descending; out_marg of PostArgs is out_stats here.
+constexpr int CNT_SUMS = 7;  // D, m0, m1, m2, n_stay, n_step, n_skip
+
+template <int K>
+__global__ __launch_bounds__(KmerHmm<K>::T) __attribute__((amdgpu_waves_per_eu(2))) void
+posterior_counts_kernel(PostArgs a) {
+  constexpr int S = KmerHmm<K>::S, T = KmerHmm<K>::T, Q = KmerHmm<K>::Q, W = KmerHmm<K>::W, NW = KmerHmm<K>::NW;
+  __shared__ __attribute__((aligned(16))) double G4[2][Q + (Q >> 4) * HMM_PAD + HMM_PAD];  // w_step * G4
+  __shared__ __attribute__((aligned(16))) double G16[2][T + (T >> 4) * HMM_PAD + HMM_PAD];  // w_skip * G16
+  __shared__ __attribute__((aligned(16))) double SW[S];  // w_stay * W, every thread's own 16 in the row store's layout
+  __shared__ double wave_top[2][NW];            // per wave the largest B of the event
+  __shared__ double wave_em[2][NW];             // per wave the largest em of the event
+  __shared__ double wave_acc[2][CNT_SUMS][NW];  // per wave the seven sums of the event
+  __shared__ double read_acc[10];               // the read's accumulators
+  const int u = threadIdx.x, wave = u / W;
+  const int64_t rd = (int64_t)a.r0 + blockIdx.x;
+  const int64_t ev0 = a.ev_off[rd];
+  const int E = (int)(a.ev_off[rd + 1] - ev0);
+  if (hmm_status(a, rd, E) != 0) return;
+  const double *lev = a.level + ev0;
+  const double w_stay = a.w_stay, w_step = a.w_step, w_skip = a.w_skip;
+  const double *store = a.rows + (ev0 - a.ev_off[a.r0]) * (int64_t)S + 2 * u;
+
+  double *sw = SW + 2 * u;
+  // where the successors' sums of the thread's 16 states lie: s mod Q and s mod T are 16 consecutive entries from a
+  // multiple of 16 on, or (Q or T below 16) the entries j mod Q, j mod T of the first block -- one address and
+  // constant offsets, not 16 addresses in registers
+  const int q0 = hmm_at((16 * u) & (Q - 1)), t0 = hmm_at((16 * u) & (T - 1));
+  double B[16], mean[16], ac[16], mc[16];
+  hmm_load_table(a, u, mean, ac, mc, [&](int j) { B[j] = 1.0; });
+  // (thread 0's alone, in LDS so that they cost no thread a register: M0, Mx, Mxx, Mm, Mxm, Mmm, N_stay, N_step,
+  // N_skip, F)
+  if (u == 0) {
+#pragma unroll
+    for (int x = 0; x < 10; x++) read_acc[x] = 0.0;
+  }
+  for (int i = E - 1; i >= 0; i--) {
+    const int p = i & 1;
+    const double *in = store + (int64_t)i * S;
+    double av[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) av[j] = in[post_store_at<T>(j)];
+    double acc[CNT_SUMS];
+    // the move i -> i + 1: W, w_step * G4 and w_skip * G16 of event i + 1
+    if (i < E - 1) {
+      const double *g4 = G4[p ^ 1], *g16 = G16[p ^ 1];
+      acc[4] = av[0] * sw[post_store_at<T>(0)];
+      acc[5] = av[0] * g4[q0];
+      acc[6] = av[0] * g16[t0];
+#pragma unroll
+      for (int j = 1; j < 16; j++) {
+        acc[4] = acc[4] + av[j] * sw[post_store_at<T>(j)];
+        acc[5] = acc[5] + av[j] * g4[q0 + (j & (Q - 1))];
+        acc[6] = acc[6] + av[j] * g16[t0 + (j & (T - 1))];
+      }
+    } else {
+      acc[4] = acc[5] = acc[6] = 0.0;
+    }
+    // D and the moment sums of A * B, the thread's states ascending
+    {
+      const double ab = av[0] * B[0];
+      const double t0 = ab * mc[0];
+      const double t1 = t0 * mean[0];
+      acc[0] = ab;
+      acc[1] = t0;
+      acc[2] = t1;
+      acc[3] = t1 * mean[0];
+    }
+#pragma unroll
+    for (int j = 1; j < 16; j++) {
+      const double ab = av[j] * B[j];
+      const double t0 = ab * mc[j];
+      const double t1 = t0 * mean[j];
+      acc[0] = acc[0] + ab;
+      acc[1] = acc[1] + t0;
+      acc[2] = acc[2] + t1;
+      acc[3] = acc[3] + t1 * mean[j];
+    }
+#pragma unroll
+    for (int d = W / 2; d >= 1; d >>= 1) {
+      double o[CNT_SUMS];
+#pragma unroll
+      for (int x = 0; x < CNT_SUMS; x++) o[x] = __shfl_xor(acc[x], d, 64);
+#pragma unroll
+      for (int x = 0; x < CNT_SUMS; x++) acc[x] = acc[x] + o[x];
+    }
+    if ((u & (W - 1)) == 0) {
+#pragma unroll
+      for (int x = 0; x < CNT_SUMS; x++) wave_acc[p][x][wave] = acc[x];
+    }
+    // (the row is done with: the emissions of the next backward step take its registers)
+    const double e = lev[i];
+    double emx, Wv[16];
+    if (i > 0) {
+      double top = B[0];
+#pragma unroll
+      for (int j = 1; j < 16; j++) top = fmax(top, B[j]);
+      top = post_wave_max<W>(top);
+      if ((u & (W - 1)) == 0) wave_top[p][wave] = top;
+      emx = gauss_log(e, mean[0], ac[0], mc[0]);
+      Wv[0] = B[0] * post_exp(fmax(emx, POST_EM_FLOOR));
+#pragma unroll
+      for (int j = 1; j < 16; j++) {
+        const double g = gauss_log(e, mean[j], ac[j], mc[j]);
+        emx = fmax(emx, g);
+        Wv[j] = B[j] * post_exp(fmax(g, POST_EM_FLOOR));
+      }
+      double g4[4];
+#pragma unroll
+      for (int g = 0; g < 4; g++) g4[g] = ((Wv[4 * g] + Wv[4 * g + 1]) + Wv[4 * g + 2]) + Wv[4 * g + 3];
+      const double g16 = ((g4[0] + g4[1]) + g4[2]) + g4[3];
+#pragma unroll
+      for (int g = 0; g < 4; g++) G4[p][hmm_at(4 * u) + g] = w_step * g4[g];
+      G16[p][hmm_at(u)] = w_skip * g16;
+    } else {
+      emx = gauss_log(e, mean[0], ac[0], mc[0]);
+#pragma unroll
+      for (int j = 1; j < 16; j++) emx = fmax(emx, gauss_log(e, mean[j], ac[j], mc[j]));
+    }
+    emx = post_wave_max<W>(emx);
+    if ((u & (W - 1)) == 0) wave_em[p][wave] = emx;
+    __syncthreads();
+    if (u == 0) {
+      double C[CNT_SUMS];
+#pragma unroll
+      for (int x = 0; x < CNT_SUMS; x++) C[x] = post_join_sum<NW>(&wave_acc[p][x][0], 1);
+      const double g0 = C[1] / C[0], g1 = C[2] / C[0], g2 = C[3] / C[0];
+      read_acc[0] = read_acc[0] + g0;
+      read_acc[1] = read_acc[1] + g0 * e;
+      read_acc[2] = read_acc[2] + (g0 * e) * e;
+      read_acc[3] = read_acc[3] + g1;
+      read_acc[4] = read_acc[4] + g1 * e;
+      read_acc[5] = read_acc[5] + g2;
+      if (post_join_max<NW>(wave_em[p]) <= POST_EM_FLOOR) read_acc[9] = read_acc[9] + 1.0;
+      if (i < E - 1) {
+        const double total = (C[4] + C[5]) + C[6];
+        read_acc[6] = read_acc[6] + C[4] / total;
+        read_acc[7] = read_acc[7] + C[5] / total;
+        read_acc[8] = read_acc[8] + C[6] / total;
+      }
+    }
+    if (i > 0) {
+      const int y = __builtin_amdgcn_frexp_exp(post_join_max<NW>(wave_top[p]));
+#pragma unroll
+      for (int j = 0; j < 16; j++) {
+        const double stay = w_stay * Wv[j];
+        sw[post_store_at<T>(j)] = stay;
+        B[j] = ldexp((G4[p][q0 + (j & (Q - 1))] + stay) + G16[p][t0 + (j & (T - 1))], -y);
+      }
+    }
+  }
+  if (u == 0) {
+    double *out = a.out_marg + 10 * rd;
+#pragma unroll
+    for (int x = 0; x < 10; x++) out[x] = read_acc[x];
+  }
+}
+
+enum { SWEEP_FORWARD, SWEEP_BACKWARD, SWEEP_COUNTS };
+
+void launch_sweep(int sweep, int k, const PostArgs &a, int n, hipStream_t stream) {
   hmm_dispatch_k(k, [&](auto kc) {
     constexpr int K = decltype(kc)::value;
-    if (forward)
+    if (sweep == SWEEP_FORWARD)
       hipLaunchKernelGGL(posterior_forward_kernel<K>, dim3((unsigned)n), dim3(KmerHmm<K>::T), 0, stream, a);
-    else
+    else if (sweep == SWEEP_BACKWARD)
       hipLaunchKernelGGL(posterior_backward_kernel<K>, dim3((unsigned)n), dim3(KmerHmm<K>::T), 0, stream, a);
+    else
+      hipLaunchKernelGGL(posterior_counts_kernel<K>, dim3((unsigned)n), dim3(KmerHmm<K>::T), 0, stream, a);
   });
 }
 
-}  // namespace
-
-extern "C" int nvk_kmer_posterior_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_events, const double *level,
-                                      const int64_t *ev_off, int k, int pos, const double *mean, const double *ac,
-                                      const double *mc, double w_stay, double w_step, double w_skip,
-                                      const int32_t *status_in, double *out_marg, double *out_z, int32_t *out_status,
-                                      int64_t *out_parts, double *out_ms) {
-  const char *what = "nvk_kmer_posterior_dev";
+// the two entries: the forward sweep of a part, then `second` (the backward or the counts sweep) on its rows.
+// `out`: the marginals or the stats
+int run_sweeps(const char *what, int second, nvk_ctx *ctx, int64_t n_reads, int64_t total_events, const double *level,
+               const int64_t *ev_off, int k, int pos, const double *mean, const double *ac, const double *mc,
+               double w_stay, double w_step, double w_skip, const int32_t *status_in, double *out, double *out_z,
+               int32_t *out_status, int64_t *out_parts, double *out_ms) {
   if (out_parts) *out_parts = 0;
   if (out_ms) out_ms[0] = out_ms[1] = 0.0;
   int rc = hmm_check_entry(what, ctx, k, "pos", pos, n_reads, total_events, level, ev_off, mean, ac, mc);
@@ -325,7 +495,7 @@ extern "C" int nvk_kmer_posterior_dev(nvk_ctx *ctx, int64_t n_reads, int64_t tot
       return NVK_ERR_INVALID;
     }
   if (n_reads == 0) return NVK_OK;
-  if ((total_events > 0 && !out_marg) || !out_z || !out_status) {
+  if ((total_events > 0 && !out) || !out_z || !out_status) {
     nvk_set_error("%s: NULL output", what);
     return NVK_ERR_INVALID;
   }
@@ -338,14 +508,14 @@ extern "C" int nvk_kmer_posterior_dev(nvk_ctx *ctx, int64_t n_reads, int64_t tot
   const int64_t S = (int64_t)1 << (2 * k);
   std::vector<int64_t> cut;
   const int64_t need_rows = cut_parts(eoff, cap_b / (8 * S), cut);
-  // (the seed aligner's traceback workspace serves, as for the Viterbi store: the three never run at once on a context)
+  // (the seed aligner's traceback workspace serves, as for the Viterbi store: they never run at once on a context)
   if ((rc = nvk_ws_reserve(ctx, WS_SEED_TB, (size_t)need_rows * (size_t)S * 8))) return rc;
   PostArgs a;
   (HmmIn &)a = HmmIn{level, ev_off, mean, ac, mc, status_in};
   a.w_stay = w_stay;
   a.w_step = w_step;
   a.w_skip = w_skip;
-  a.out_marg = out_marg;
+  a.out_marg = out;
   a.out_z = out_z;
   a.out_status = out_status;
   a.rows = (double *)ctx->ws[WS_SEED_TB];
@@ -357,10 +527,10 @@ extern "C" int nvk_kmer_posterior_dev(nvk_ctx *ctx, int64_t n_reads, int64_t tot
     a.r0 = (int)cut[c];
     const int n = (int)(cut[c + 1] - cut[c]);
     if (out_ms) NVK_HIP(hipEventRecord(ev[0], ctx->stream));
-    launch_sweep(true, k, a, n, ctx->stream);
+    launch_sweep(SWEEP_FORWARD, k, a, n, ctx->stream);
     NVK_HIP(hipGetLastError());
     if (out_ms) NVK_HIP(hipEventRecord(ev[1], ctx->stream));
-    launch_sweep(false, k, a, n, ctx->stream);
+    launch_sweep(second, k, a, n, ctx->stream);
     NVK_HIP(hipGetLastError());
     if (out_ms) {
       NVK_HIP(hipEventRecord(ev[2], ctx->stream));
@@ -377,4 +547,24 @@ extern "C" int nvk_kmer_posterior_dev(nvk_ctx *ctx, int64_t n_reads, int64_t tot
     for (hipEvent_t e : ev) NVK_HIP(hipEventDestroy(e));
   if (out_parts) *out_parts = (int64_t)cut.size() - 1;
   return NVK_OK;
+}
+
+}  // namespace
+
+extern "C" int nvk_kmer_posterior_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_events, const double *level,
+                                      const int64_t *ev_off, int k, int pos, const double *mean, const double *ac,
+                                      const double *mc, double w_stay, double w_step, double w_skip,
+                                      const int32_t *status_in, double *out_marg, double *out_z, int32_t *out_status,
+                                      int64_t *out_parts, double *out_ms) {
+  return run_sweeps("nvk_kmer_posterior_dev", SWEEP_BACKWARD, ctx, n_reads, total_events, level, ev_off, k, pos, mean,
+                    ac, mc, w_stay, w_step, w_skip, status_in, out_marg, out_z, out_status, out_parts, out_ms);
+}
+
+extern "C" int nvk_kmer_expectations_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_events, const double *level,
+                                         const int64_t *ev_off, int k, const double *mean, const double *ac,
+                                         const double *mc, double w_stay, double w_step, double w_skip,
+                                         const int32_t *status_in, double *out_stats, double *out_z,
+                                         int32_t *out_status, int64_t *out_parts, double *out_ms) {
+  return run_sweeps("nvk_kmer_expectations_dev", SWEEP_COUNTS, ctx, n_reads, total_events, level, ev_off, k, 0, mean,
+                    ac, mc, w_stay, w_step, w_skip, status_in, out_stats, out_z, out_status, out_parts, out_ms);
 }

@@ -20,6 +20,11 @@ starts from.  On the device:
    on a fixed table of thresholds.  The scale is ordered, not calibrated: the transition weights are guesses, and on the
    simulated reads it is over-confident above Q20.
 
+With ``fit=n`` n rounds of a Baum-Welch fit run between stages 2 and 3 (nadavca_amd/decode_fit.py: the E-step is
+``nvk_kmer_expectations_dev``, the M-step numpy on the host): per read a scale and shift on the stage-2 levels, pooled
+over the batch a factor on the table's sigma and the move weights.  Stages 3 to 5 then run on the fitted levels, table
+constants and weights, unchanged.
+
 So one operator stands where ``signal_locate_batch`` and ``signal_map_batch`` do on that route:
 
     rb0 = ReadBatch.from_signals(raw, sig_off, np.zeros(0, np.int32), np.zeros(n + 1, np.int64))
@@ -35,7 +40,7 @@ import math
 
 import numpy as np
 
-from . import _lib, defaults
+from . import _lib, decode_fit, defaults
 from .batchflow import seg_index
 from .rawsignal import (SignalEvents, gaussian_constants, map_rows_dev, offsets_of, rescale_by_moments_dev,
                         resolve_kmer_model, signal_events_dev, transition_costs, transition_weights)
@@ -56,16 +61,19 @@ class DecodeBatch:
     the log posterior of the whole Viterbi path per event) and, flat and aligned with ``sequence``, ``base_post`` (f64:
     the largest posterior of the base's letter over its dwell; a base a skip passes takes the smaller of its two
     neighbours' values, the bases before the first and after the last base with an event the nearest one's) and
-    ``quality`` (uint8, 0..60: the number of thresholds 1 - 10^(-j/10), j = 1..60, that ``base_post`` reaches)."""
+    ``quality`` (uint8, 0..60: the number of thresholds 1 - 10^(-j/10), j = 1..60, that ``base_post`` reaches).
+    With ``fit=n`` or ``fit_start`` (else None): ``fit``, the ``decode_fit.DecodeFit`` the other results were computed
+    with."""
 
     def __init__(self, status, n_events, n_bases, score, seq_off, sequence, map_base, map_sig, map_off, parts=0,
-                 loglik=None, base_post=None, quality=None, post_parts=0):
+                 loglik=None, base_post=None, quality=None, post_parts=0, fit=None):
         self.status, self.n_events, self.n_bases, self.score = status, n_events, n_bases, score
         self.seq_off, self.sequence = seq_off, sequence
         self.map_base, self.map_sig, self.map_off = map_base, map_sig, map_off
         self.parts = parts   # parts the operator cut the batch into under the workspace cap
         self.loglik, self.base_post, self.quality = loglik, base_post, quality
         self.post_parts = post_parts   # ... and the forward-backward operator its own
+        self.fit = fit
         self.n = int(status.size)
         self.n_decoded = int((status == DEC_OK).sum())
 
@@ -169,13 +177,15 @@ def base_qualities_dev(marg, z, ok, n_ev, ev_off, map_off, owner, keep, sequence
 
 class DecodeStages(SignalEvents):
     """The device tensors between the stages of one ``decode_batch`` call (``decode_stages``)."""
-    __slots__ = ('mean', 'ac', 'mc', 'scaled', 'ok', 'status_in', 'cap_off', 'costs', 'hit', 'path_score', 'seq',
-                 'base_event', 'parts')
+    __slots__ = ('mean', 'ac', 'mc', 'scaled', 'ok', 'status_in', 'cap_off', 'costs', 'weights', 'hit', 'path_score',
+                 'seq', 'base_event', 'parts', 'fit')
 
 
 def decode_stages(read_batch, kmer_model, p_stay, p_skip, sigma_scale, min_events, window, threshold, var_floor,
-                  timer=None):
-    """Stages 1 to 3 on the device -> DecodeStages.  ``timer(name)``: called after each stage (bench tool)."""
+                  timer=None, fit=None):
+    """Stages 1 to 3 on the device -> DecodeStages.  ``timer(name)``: called after each stage (bench tool).  ``fit``:
+    None, or (rounds, groups, start) of ``decode_fit``: the fit runs after stage 2, and ``scaled``, the table
+    constants, ``costs`` and ``weights`` are then the fitted ones."""
     import torch
     from .device import viterbi_decode_dev
     context = kmer_model.context
@@ -183,6 +193,7 @@ def decode_stages(read_batch, kmer_model, p_stay, p_skip, sigma_scale, min_event
     rb, st = read_batch, DecodeStages()
     tick = timer if timer is not None else (lambda name: None)
     st.costs = transition_costs(p_stay, p_skip, 'decode_batch')
+    st.weights, st.fit = transition_weights(p_stay, p_skip), None
     st.mean, st.ac, st.mc = state_tables_dev(kmer_model, sigma_scale, device)
     signal_events_dev(rb, context, window, threshold, var_floor, tick, into=st)
     pool_off = torch.tensor([0, int(st.mean.numel())], dtype=torch.int64, device=device)
@@ -191,6 +202,17 @@ def decode_stages(read_batch, kmer_model, p_stay, p_skip, sigma_scale, min_event
     st.status_in = torch.where(st.ok, DEC_OK, DEC_NO_EVENTS).to(torch.int32)
     st.cap_off = capacity_offsets(st.ev_off, kmer_model.get_k())
     tick('rescale')
+    if fit is not None:
+        rounds, groups, start = fit
+        if start is not None and start.scale.shape != (rb.n,):
+            raise ValueError('decode_batch: fit_start holds %d reads, the batch %d' % (start.scale.size, rb.n))
+        st.fit = decode_fit.fit_on_device(st, kmer_model, rounds, groups, sigma_scale, p_stay, p_skip, start)
+        st.costs = transition_costs(st.fit.p_stay, st.fit.p_skip, 'decode_batch')
+        st.weights = transition_weights(st.fit.p_stay, st.fit.p_skip)
+        st.mean, st.ac, st.mc = state_tables_dev(kmer_model, st.fit.sigma_scale, device)
+        st.scaled = decode_fit.fitted_levels_dev(st.scaled, seg_index(st.ev_off, int(st.scaled.numel()))[0],
+                                                 st.fit.scale, st.fit.shift)
+        tick('fit')
     st.hit, st.path_score, st.seq, st.base_event, st.parts = viterbi_decode_dev(
         context, st.scaled, st.ev_off, kmer_model.get_k(), kmer_model.get_central_position(), st.mean, st.ac, st.mc,
         *st.costs, st.status_in, st.cap_off)
@@ -199,7 +221,8 @@ def decode_stages(read_batch, kmer_model, p_stay, p_skip, sigma_scale, min_event
 
 
 def decode_batch(read_batch, kmer_model=defaults.KMER_MODEL_FILE, p_stay=0.7, p_skip=0.01, sigma_scale=1.0,
-                 min_events=32, window=2, threshold=5.0, var_floor=0.02, context=None, qualities=False):
+                 min_events=32, window=2, threshold=5.0, var_floor=0.02, context=None, qualities=False, fit=0,
+                 fit_params=decode_fit.FIT_PARAMS, fit_start=None):
     """A base sequence and its base -> sample table for every read of ``read_batch`` from its raw signal alone (module
     docstring); any sequence or table the batch carries is ignored.  ``kmer_model``: a KmerModel or a path (4 letters,
     k in 2..6, else ValueError); ``context``: the context a model loaded from a path is made on (default: the
@@ -209,14 +232,21 @@ def decode_batch(read_batch, kmer_model=defaults.KMER_MODEL_FILE, p_stay=0.7, p_
     at which the simulated reads of the test suite (dwell 3-17 samples, noise 0.35, the packaged 6-mer table) decode
     best (the batch of the quality test is the tuning set), not values fitted to real data.  ``qualities``: also run
     the forward-backward operator and fill ``loglik``, ``base_post`` and ``quality`` (stage 5 of the module docstring);
-    the other results do not change.  -> DecodeBatch."""
+    the other results do not change.  ``fit``: rounds of the Baum-Welch fit (module docstring; 0: none, and nothing
+    changes); ``fit_params``: what it fits, a choice of 'scale' (per read, scale and shift), 'sigma' (pooled, the factor
+    on sigma) and 'moves' (pooled, ``p_stay`` / ``p_skip``), the rest staying at the arguments; ``fit_start``: the
+    ``DecodeBatch.fit`` of an earlier call on the same batch, whose per-read scale and shift the reads start from (its
+    pooled values are passed as ``sigma_scale``, ``p_stay`` and ``p_skip``; with ``fit=0`` they are only applied).
+    -> DecodeBatch."""
     import torch
     kmer_model = resolve_kmer_model(kmer_model, context)
     check_table(kmer_model)
     if int(min_events) < 1:
         raise ValueError('decode_batch: min_events is at least 1')
+    rounds, groups = decode_fit.check_params(fit, fit_params)
     rb = read_batch
-    st = decode_stages(rb, kmer_model, p_stay, p_skip, sigma_scale, min_events, window, threshold, var_floor)
+    st = decode_stages(rb, kmer_model, p_stay, p_skip, sigma_scale, min_events, window, threshold, var_floor,
+                       fit=(rounds, groups, fit_start) if rounds > 0 or fit_start is not None else None)
     dev = st.ev_off.device
     status, n_ev, n_bases = st.hit[:, 0], st.hit[:, 1].to(torch.int64), st.hit[:, 2].to(torch.int64)
     ok = status == DEC_OK
@@ -234,10 +264,10 @@ def decode_batch(read_batch, kmer_model=defaults.KMER_MODEL_FILE, p_stay=0.7, p_
         from .device import kmer_posterior_dev
         marg, z, _, post_parts = kmer_posterior_dev(
             kmer_model.context, st.scaled, st.ev_off, kmer_model.get_k(), kmer_model.get_central_position(), st.mean,
-            st.ac, st.mc, *transition_weights(p_stay, p_skip), st.status_in)
+            st.ac, st.mc, *st.weights, st.status_in)
         loglik, base_post, quality = base_qualities_dev(marg, z, ok, n_ev, st.ev_off, map_off, owner, keep, sequence,
                                                         event)
         extra = dict(loglik=host(loglik), base_post=host(base_post), quality=host(quality), post_parts=post_parts)
     return DecodeBatch(host(status), host(st.hit[:, 1]), host(st.hit[:, 2]), host(score), host(seq_off),
-                       host(sequence), host(map_base), host(map_sig), host(map_off), st.parts,
+                       host(sequence), host(map_base), host(map_sig), host(map_off), st.parts, fit=st.fit,
                        **extra)

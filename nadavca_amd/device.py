@@ -1159,3 +1159,27 @@ def kmer_posterior_dev(context, level, ev_off, k, pos, mean, ac, mc, w_stay, w_s
                                           ms if timing else None), 'nvk_kmer_posterior_dev')
     out = (marg[:n_ev], z[:n], status[:n], int(parts.value))
     return out + ((float(ms[0]), float(ms[1])),) if timing else out
+
+
+def kmer_expectations_dev(context, level, ev_off, k, mean, ac, mc, w_stay, w_step, w_skip, status_in, timing=False):
+    """The E-step of a Baum-Welch fit on every read's events, nvk_kmer_expectations_dev: the arguments of
+    ``kmer_posterior_dev`` without ``pos``.
+    -> (stats f64 (n, 10): per read M0, Mx, Mxx, Mm, Mxm, Mmm (the posterior-weighted moments of the levels x against the
+    states' means, each term times the state's mc), N_stay, N_step, N_skip (the expected moves) and the number of events
+    whose every emission sits on the floor; a read that is not processed has zeros; z and status as
+    ``kmer_posterior_dev``'s, z bit for bit; the number of parts) and, with ``timing``, the milliseconds of the forward
+    and counts launches."""
+    import torch
+    lib = _lib.load()
+    dev = ev_off.device
+    n, n_ev = int(ev_off.numel()) - 1, int(level.numel())
+    stats = torch.zeros((max(n, 1), 10), dtype=torch.float64, device=dev)
+    z = torch.zeros((max(n, 1), 2), dtype=torch.float64, device=dev)
+    status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    parts, ms = C.c_int64(0), (C.c_double * 2)(0.0, 0.0)
+    _lib.check(lib.nvk_kmer_expectations_dev(context.handle, n, n_ev, _dp(_one(level)), _dp(ev_off), int(k), _dp(mean),
+                                             _dp(ac), _dp(mc), float(w_stay), float(w_step), float(w_skip),
+                                             _opt(status_in, n), _dp(stats), _dp(z), _dp(status), C.byref(parts),
+                                             ms if timing else None), 'nvk_kmer_expectations_dev')
+    out = (stats[:n], z[:n], status[:n], int(parts.value))
+    return out + ((float(ms[0]), float(ms[1])),) if timing else out

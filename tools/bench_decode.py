@@ -7,8 +7,10 @@ align_signal_batch beside ``align_signal_batch`` with the same aligner from the 
 HIP events after a warm-up; the figures are the median of ``--reps`` runs.  ``--qualities``: also the forward-backward
 operator of ``decode_batch(qualities=True)`` (``nvk_kmer_posterior_dev``) -- its forward and backward launches apart,
 its parts and row-store bytes with the bytes-over-bandwidth floor -- and the whole call with qualities beside the plain
-one of the same session.
-`python tools/bench_decode.py [N] [--genome L] [--reps R] [--qualities] [--limit-gib G]`."""
+one of the same session.  ``--fit R``: also ``decode_batch(fit=R)`` -- the E-step operator (``nvk_kmer_expectations_dev``)
+of every round and of the closing pass with its forward and counts launches apart, the host's share of the fit (the
+M-steps, the copies, the levels and tables of every round), and the whole call with the fit beside the plain one.
+`python tools/bench_decode.py [N] [--genome L] [--reps R] [--qualities] [--fit R] [--limit-gib G]`."""
 import argparse
 import inspect
 import os
@@ -18,7 +20,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
-from nadavca_amd import decode, decode_batch, defaults, synthetic  # noqa: E402
+from nadavca_amd import decode, decode_batch, decode_fit, defaults, synthetic  # noqa: E402
 from nadavca_amd.align_signal import align_signal_batch  # noqa: E402
 from nadavca_amd.device import kmer_posterior_dev, viterbi_decode_dev  # noqa: E402
 from nadavca_amd.kmer_model import KmerModel  # noqa: E402
@@ -30,6 +32,7 @@ parser.add_argument('n_reads', nargs='?', type=int, default=10000)
 parser.add_argument('--genome', type=int, default=100000)
 parser.add_argument('--reps', type=int, default=3)
 parser.add_argument('--qualities', action='store_true')
+parser.add_argument('--fit', type=int, default=0, help='rounds of decode_batch(fit=R) to time (0: none)')
 parser.add_argument('--limit-gib', type=float, default=0.0, help='workspace limit of the context (0: the default caps)')
 opts = parser.parse_args()
 
@@ -82,7 +85,16 @@ def posterior_alone(st):
     return ms, out[4], out[3]
 
 
+def fit_alone(st):
+    """-> (ms of the fit, per E-step (forward ms, counts ms), the DecodeFit)"""
+    launches = []
+    fit, ms = timed(lambda: decode_fit.fit_on_device(st, km, opts.fit, decode_fit.FIT_PARAMS, args[2], args[0], args[1],
+                                                     timer=lambda name, t: launches.append(t)))
+    return ms, list(zip(launches[0::2], launches[1::2])), fit
+
+
 whole = lambda: decode_batch(bare, kmer_model=km)
+whole_f = lambda: decode_batch(bare, kmer_model=km, fit=opts.fit)
 whole_q = lambda: decode_batch(bare, kmer_model=km, qualities=True)
 
 
@@ -97,6 +109,9 @@ align_signal_batch(None, rb, kmer_model=km, aligner=seed)
 rows = {k: [] for k in STAGES + ('operator', 'whole', 'chain', 'asb_table', 'post', 'forward', 'backward', 'whole_q')}
 if opts.qualities:
     whole_q()
+if opts.fit:
+    whole_f()
+fit_rows = []
 for _ in range(opts.reps):
     st, ms = staged()
     for k, v in zip(STAGES, ms):
@@ -114,6 +129,9 @@ for _ in range(opts.reps):
         rows['forward'].append(fwd)
         rows['backward'].append(bwd)
         rows['whole_q'].append(timed(whole_q)[1])
+    if opts.fit:
+        ms, launches, fitted = fit_alone(st)
+        fit_rows.append([ms] + [t for pair in launches for t in pair] + [timed(whole_f)[1]])
 med = {k: float(np.median(v)) for k, v in rows.items() if v}
 k = km.get_k()
 n_ev = st.ev_off.cpu().numpy()
@@ -146,3 +164,13 @@ if opts.qualities:
                         rows_b / HBM_GBS / 1e6))
     print('decode_batch(qualities=True), the whole call   %9.2f ms  (%.1f k reads/s; plain call above: %.2f ms)'
           % (med['whole_q'], opts.n_reads / med['whole_q'], med['whole']))
+if opts.fit:
+    med_f = np.median(np.array(fit_rows), axis=0)
+    print('fit alone, %d round(s) and the closing pass       %9.2f ms  (%d part(s) per E-step; sigma_scale %.4f, p_stay %.4f, '
+          'p_skip %.5f)' % (opts.fit, med_f[0], fitted.parts, fitted.sigma_scale, fitted.p_stay, fitted.p_skip))
+    for r in range(opts.fit + 1):
+        print('    %s: forward launches %8.2f ms, counts launches %8.2f ms'
+              % ('round %d' % (r + 1) if r < opts.fit else 'closing', med_f[1 + 2 * r], med_f[2 + 2 * r]))
+    print('    host share (M-steps, copies, levels and tables)  %7.2f ms' % (med_f[0] - med_f[1:-1].sum()))
+    print('decode_batch(fit=%d), the whole call               %9.2f ms  (%.1f k reads/s; plain call above: %.2f ms)'
+          % (opts.fit, med_f[-1], opts.n_reads / med_f[-1], med['whole']))
