@@ -1207,6 +1207,34 @@ int nvk_kmer_expectations_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_event
                               double *out_stats, double *out_z, int32_t *out_status, int64_t *out_parts,
                               double *out_ms);
 
+/* K-MER STATE MOMENTS (estimate_decode_model).  The part of Baum-Welch that adapts the table: per state the posterior
+ * weight of the batch's events and the first two moments of their levels under it.  The inputs are
+ * nvk_kmer_expectations_dev's; EXP, b, frexp, forward (A, X), backward (B, W, G4, G16) and the rule for sums over all
+ * states are that contract's, and the forward sweep is the same kernel, so out_z's bits are nvk_kmer_posterior_dev's.
+ * Every expression is a rounded f64 operation in the order written; the kernels call no library exp or log and use no
+ * atomics.  x_i = level[ev_off[r] + i], S = 4^k.
+ *   per event   i = E-1 down to 0:
+ *               D   = sum over all states of A(i,s) * B(i,s)          (the expectations contract's D, same bits)
+ *               inv = 1.0 / D
+ *               g   = (A(i,s) * B(i,s)) * inv
+ *               G0[s] = G0[s] + g;   G1[s] = G1[s] + g * x_i;   G2[s] = G2[s] + (g * x_i) * x_i
+ *               every accumulator starts at 0.0 and takes its terms with i descending
+ *   per batch   tot[m][s] starts at 0.0 and takes the reads with status NVK_DEC_OK in ascending read order:
+ *               tot[m][s] = tot[m][s] + G_m[s] of the read.  A read that is not processed adds nothing.
+ * out_moments f64[3 * 4^k], laid out [m][s]; out_z, out_status, out_parts as nvk_kmer_posterior_dev;
+ * out_ms (may be NULL): three doubles, the forward, the moments and the reduce launches summed over the parts.
+ * The moments sweep leaves every read's 3 S sums in a slab of a workspace of its own (the part's reads times 24 * 4^k
+ * bytes) and a third launch chains the part's slabs, in read order, onto the totals the parts before it left; the
+ * totals are zeroed on the stream when the call starts.  So the result does not depend on the cut into parts.  A read
+ * counts in the cut with its rows and its slab (its events and three rows more), so that rows plus slabs stay under
+ * the row store's cap; the store, the cap, the checks and the return codes are nvk_kmer_posterior_dev's (NVK_OK with
+ * nothing written for n_reads == 0).  Device pointers but out_parts and out_ms. */
+int nvk_kmer_state_moments_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_events, const double *level,
+                               const int64_t *ev_off, int k, const double *mean, const double *ac, const double *mc,
+                               double w_stay, double w_step, double w_skip, const int32_t *status_in,
+                               double *out_moments, double *out_z, int32_t *out_status, int64_t *out_parts,
+                               double *out_ms);
+
 #ifdef __cplusplus
 }
 #endif

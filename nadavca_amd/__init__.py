@@ -23,10 +23,12 @@ from .signal_map import SignalMapBatch, signal_map_batch  # noqa: F401
 from .locate import LocateBatch, signal_locate_batch  # noqa: F401
 from .decode import DecodeBatch, decode_batch  # noqa: F401
 from .decode_fit import DecodeFit  # noqa: F401
+from .decode_train import DecodeModelEstimate, estimate_decode_model  # noqa: F401
 
 __all__ = ['align_signal', 'align_signal_batch', 'estimate_snps', 'estimate_snps_batch', 'dtw', 'SeedAligner',
            'ReferenceSet', 'estimate_kmer_model', 'call_mods_batch', 'call_indels_batch',
            'estimate_allele_fractions_batch', 'phase_reads_batch', 'PhaseBatch', 'site_levels_batch',
            'compare_site_levels', 'SiteLevelBatch', 'SiteComparison', 'compare_site_ranks', 'site_rank_tests_batch', 'SiteRankComparison', 'compare_site_mixtures',
            'site_mixture_tests_batch', 'SiteMixtureComparison', 'estimate_mod_model', 'ModModelEstimate', 'signal_map_batch',
-           'SignalMapBatch', 'signal_locate_batch', 'LocateBatch', 'decode_batch', 'DecodeBatch', 'DecodeFit']
+           'SignalMapBatch', 'signal_locate_batch', 'LocateBatch', 'decode_batch', 'DecodeBatch', 'DecodeFit',
+           'estimate_decode_model', 'DecodeModelEstimate']

@@ -127,6 +127,8 @@ SIGNATURES = {
                                + [_vp] * 3 + [C.POINTER(_i64), C.POINTER(_dbl)]),
     'nvk_kmer_expectations_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _int, _vp, _vp, _vp, _dbl, _dbl, _dbl, _vp]
                                   + [_vp] * 3 + [C.POINTER(_i64), C.POINTER(_dbl)]),
+    'nvk_kmer_state_moments_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _int, _vp, _vp, _vp, _dbl, _dbl, _dbl, _vp]
+                                   + [_vp] * 3 + [C.POINTER(_i64), C.POINTER(_dbl)]),
 }
 
 LAUNCH_SWEEP, LAUNCH_EXACT, LAUNCH_ELL = 1, 2, 3   # nvk_launch_rec.op

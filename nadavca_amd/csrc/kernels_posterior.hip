@@ -29,10 +29,13 @@
 // runs the forward and the backward sweep of a part before the next part's.
 //
 // THE COUNTS SWEEP of nvk_kmer_expectations_dev (decode_batch(fit=n)) stands where the backward sweep does and is
-// described at its kernel; its CPU restatement is tests/host_shims/expect_host.cpp.
+// described at its kernel; its CPU restatement is tests/host_shims/expect_host.cpp.  THE MOMENTS SWEEP of
+// nvk_kmer_state_moments_dev (estimate_decode_model, nadavca_amd/decode_train.py) and the reduction of its slabs
+// likewise; their restatement is tests/host_shims/moments_host.cpp.
 //
 // No atomics, no scratch, no library exp or log: EXP is rint, the fma chain of xm::exp2_frac_horner and ldexp.  With
 // -ffp-contract=off every value is the rounded operation the contract writes, on the device as on the host.
+#include <algorithm>
 #include <vector>
 
 #include "kmer_hmm.h"
@@ -450,7 +453,124 @@ posterior_counts_kernel(PostArgs a) {
   }
 }
 
-enum { SWEEP_FORWARD, SWEEP_BACKWARD, SWEEP_COUNTS };
+// THE MOMENTS SWEEP (nvk_kmer_state_moments_dev) is the backward sweep with the per-state accumulation where that one
+// forms the letter marginals: the same layout, recurrence, G4 / G16 buffers and one barrier per event.  D needs the
+// whole workgroup: the thread's 16 products A * B are formed before the barrier, their sum goes through the wave
+// butterfly to LDS as the counts sweep's acc[0] does (so D has that sweep's bits), and after the barrier every thread
+// joins the waves' values, forms 1 / D and updates the 48 accumulators of its 16 states.
+//
+// The accumulators, 3 S doubles (96 KB at k = 6), lie in LDS, every thread's own 16 of each moment in the row store's
+// layout (pairs side by side, one 16-byte access per lane covering 1 KB per wave: no bank conflicts); nobody else
+// touches them, so they need no barrier.  With G4 / G16 that is 119 KB at k = 6: one workgroup per CU, one wave per
+// SIMD, and a lane may take up to 512 registers.  Nothing else runs on the CU to hide the row's latency behind, so the
+// row of event i - 1 is asked for at the top of iteration i and used one iteration later.  `out_marg` of PostArgs is
+// the part's slab buffer here: the workgroup of read r0 + b writes its 3 S sums to slab b, laid out [m][s].
+template <int K>
+__global__ __launch_bounds__(KmerHmm<K>::T) void posterior_moments_kernel(PostArgs a) {
+  constexpr int S = KmerHmm<K>::S, T = KmerHmm<K>::T, Q = KmerHmm<K>::Q, W = KmerHmm<K>::W, NW = KmerHmm<K>::NW;
+  __shared__ __attribute__((aligned(16))) double G4[2][Q + (Q >> 4) * HMM_PAD + HMM_PAD];  // w_step * G4
+  __shared__ __attribute__((aligned(16))) double G16[2][T + (T >> 4) * HMM_PAD + HMM_PAD];  // w_skip * G16
+  __shared__ __attribute__((aligned(16))) double ACC[3][S];  // G0, G1, G2 in the row store's layout
+  __shared__ double wave_top[2][NW];  // per wave the largest B of the event
+  __shared__ double wave_d[2][NW];    // per wave the sum of A * B of the event
+  const int u = threadIdx.x, wave = u / W;
+  const int64_t rd = (int64_t)a.r0 + blockIdx.x;
+  const int64_t ev0 = a.ev_off[rd];
+  const int E = (int)(a.ev_off[rd + 1] - ev0);
+  if (hmm_status(a, rd, E) != 0) return;
+  const double *lev = a.level + ev0;
+  const double w_stay = a.w_stay, w_step = a.w_step, w_skip = a.w_skip;
+  const double *store = a.rows + (ev0 - a.ev_off[a.r0]) * (int64_t)S + 2 * u;
+  const int q0 = hmm_at((16 * u) & (Q - 1)), t0 = hmm_at((16 * u) & (T - 1));
+  double *acc = &ACC[0][0] + 2 * u;
+
+  double B[16], mean[16], ac[16], mc[16], nx[16];
+  hmm_load_table(a, u, mean, ac, mc, [&](int j) {
+    B[j] = 1.0;
+    nx[j] = store[(int64_t)(E - 1) * S + post_store_at<T>(j)];
+  });
+#pragma unroll
+  for (int m = 0; m < 3; m++) {
+#pragma unroll
+    for (int j = 0; j < 16; j++) acc[m * S + post_store_at<T>(j)] = 0.0;
+  }
+  for (int i = E - 1; i >= 0; i--) {
+    const int p = i & 1;
+    double av[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) av[j] = nx[j];
+    if (i > 0) {
+      const double *in = store + (int64_t)(i - 1) * S;
+#pragma unroll
+      for (int j = 0; j < 16; j++) nx[j] = in[post_store_at<T>(j)];
+    }
+    const double e = lev[i];
+    double Wv[16];
+    if (i > 0) {
+      double top = B[0];
+#pragma unroll
+      for (int j = 1; j < 16; j++) top = fmax(top, B[j]);
+      top = post_wave_max<W>(top);
+      if ((u & (W - 1)) == 0) wave_top[p][wave] = top;
+#pragma unroll
+      for (int j = 0; j < 16; j++) Wv[j] = B[j] * post_emission(e, mean[j], ac[j], mc[j]);
+      double g4[4];
+#pragma unroll
+      for (int g = 0; g < 4; g++) g4[g] = ((Wv[4 * g] + Wv[4 * g + 1]) + Wv[4 * g + 2]) + Wv[4 * g + 3];
+      const double g16 = ((g4[0] + g4[1]) + g4[2]) + g4[3];
+#pragma unroll
+      for (int g = 0; g < 4; g++) G4[p][hmm_at(4 * u) + g] = w_step * g4[g];
+      G16[p][hmm_at(u)] = w_skip * g16;
+    }
+    // the thread's 16 products, their sum ascending, the butterfly over the wave
+    double ab[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) ab[j] = av[j] * B[j];
+    double d = ab[0];
+#pragma unroll
+    for (int j = 1; j < 16; j++) d = d + ab[j];
+    d = post_wave_sum<W>(d);
+    if ((u & (W - 1)) == 0) wave_d[p][wave] = d;
+    __syncthreads();
+    const double inv = 1.0 / post_join_sum<NW>(wave_d[p], 1);
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      double *at = acc + post_store_at<T>(j);
+      const double g = ab[j] * inv;
+      const double gx = g * e;
+      at[0] = at[0] + g;
+      at[S] = at[S] + gx;
+      at[2 * S] = at[2 * S] + gx * e;
+    }
+    if (i > 0) {
+      const int y = __builtin_amdgcn_frexp_exp(post_join_max<NW>(wave_top[p]));
+#pragma unroll
+      for (int j = 0; j < 16; j++)
+        B[j] = ldexp((G4[p][q0 + (j & (Q - 1))] + w_stay * Wv[j]) + G16[p][t0 + (j & (T - 1))], -y);
+    }
+  }
+  double *slab = a.out_marg + (int64_t)blockIdx.x * (3 * S) + 16 * u;
+#pragma unroll
+  for (int m = 0; m < 3; m++) {
+#pragma unroll
+    for (int j = 0; j < 16; j++) slab[m * S + j] = acc[m * S + post_store_at<T>(j)];
+  }
+}
+
+// The batch's totals, one thread per entry of [m][s]: the part's reads ascending, those the sweeps did not process
+// left out, continuing the total the previous part left (zeroed on the stream at the start of the call).  One chain of
+// additions per entry over the whole batch, so the cut into parts changes nothing.
+__global__ __launch_bounds__(256) void state_moments_reduce_kernel(const double *slab, const int32_t *status, int r0,
+                                                                   int n, int n3, double *tot) {
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  if (x >= n3) return;
+  double t = tot[x];
+  for (int r = 0; r < n; r++)
+    if (status[r0 + r] == NVK_DEC_OK) t = t + slab[(int64_t)r * n3 + x];
+  tot[x] = t;
+}
+
+enum { SWEEP_FORWARD, SWEEP_BACKWARD, SWEEP_COUNTS, SWEEP_MOMENTS };
 
 void launch_sweep(int sweep, int k, const PostArgs &a, int n, hipStream_t stream) {
   hmm_dispatch_k(k, [&](auto kc) {
@@ -459,19 +579,25 @@ void launch_sweep(int sweep, int k, const PostArgs &a, int n, hipStream_t stream
       hipLaunchKernelGGL(posterior_forward_kernel<K>, dim3((unsigned)n), dim3(KmerHmm<K>::T), 0, stream, a);
     else if (sweep == SWEEP_BACKWARD)
       hipLaunchKernelGGL(posterior_backward_kernel<K>, dim3((unsigned)n), dim3(KmerHmm<K>::T), 0, stream, a);
-    else
+    else if (sweep == SWEEP_COUNTS)
       hipLaunchKernelGGL(posterior_counts_kernel<K>, dim3((unsigned)n), dim3(KmerHmm<K>::T), 0, stream, a);
+    else
+      hipLaunchKernelGGL(posterior_moments_kernel<K>, dim3((unsigned)n), dim3(KmerHmm<K>::T), 0, stream, a);
   });
 }
 
-// the two entries: the forward sweep of a part, then `second` (the backward or the counts sweep) on its rows.
-// `out`: the marginals or the stats
+// the three entries: the forward sweep of a part, then `second` (the backward, the counts or the moments sweep) on its
+// rows.  `out`: the marginals, the stats or the moments' totals.  The moments sweep leaves one slab of 3 S doubles per
+// read of the part in a workspace of its own, which counts in the cut (a read takes its events and three more rows),
+// and a third launch chains the slabs into `out`
 int run_sweeps(const char *what, int second, nvk_ctx *ctx, int64_t n_reads, int64_t total_events, const double *level,
                const int64_t *ev_off, int k, int pos, const double *mean, const double *ac, const double *mc,
                double w_stay, double w_step, double w_skip, const int32_t *status_in, double *out, double *out_z,
                int32_t *out_status, int64_t *out_parts, double *out_ms) {
   if (out_parts) *out_parts = 0;
+  const bool moments = second == SWEEP_MOMENTS;
   if (out_ms) out_ms[0] = out_ms[1] = 0.0;
+  if (out_ms && moments) out_ms[2] = 0.0;
   int rc = hmm_check_entry(what, ctx, k, "pos", pos, n_reads, total_events, level, ev_off, mean, ac, mc);
   if (rc) return rc;
   const double weights[3] = {w_stay, w_step, w_skip};
@@ -495,7 +621,7 @@ int run_sweeps(const char *what, int second, nvk_ctx *ctx, int64_t n_reads, int6
       return NVK_ERR_INVALID;
     }
   if (n_reads == 0) return NVK_OK;
-  if ((total_events > 0 && !out) || !out_z || !out_status) {
+  if (((total_events > 0 || moments) && !out) || !out_z || !out_status) {
     nvk_set_error("%s: NULL output", what);
     return NVK_ERR_INVALID;
   }
@@ -507,7 +633,21 @@ int run_sweeps(const char *what, int second, nvk_ctx *ctx, int64_t n_reads, int6
   if (ctx->ws_limit <= 0 && cap_b > ((int64_t)16 << 30)) cap_b = (int64_t)16 << 30;
   const int64_t S = (int64_t)1 << (2 * k);
   std::vector<int64_t> cut;
-  const int64_t need_rows = cut_parts(eoff, cap_b / (8 * S), cut);
+  int64_t need_rows = 1, need_slabs = 0;
+  if (moments) {
+    // a read's slab is three rows' worth: cut on events + 3 per read, then size the two workspaces from the cut
+    std::vector<int64_t> uoff(eoff);
+    for (int64_t r = 0; r <= n_reads; r++) uoff[(size_t)r] += 3 * r;
+    cut_parts(uoff, cap_b / (8 * S), cut);
+    for (size_t c = 0; c + 1 < cut.size(); c++) {
+      need_rows = std::max(need_rows, eoff[(size_t)cut[c + 1]] - eoff[(size_t)cut[c]]);
+      need_slabs = std::max(need_slabs, cut[c + 1] - cut[c]);
+    }
+    if ((rc = nvk_ws_reserve(ctx, WS_STATE_MOM, (size_t)need_slabs * 3 * (size_t)S * 8))) return rc;
+    NVK_HIP(hipMemsetAsync(out, 0, 3 * (size_t)S * 8, ctx->stream));
+  } else {
+    need_rows = cut_parts(eoff, cap_b / (8 * S), cut);
+  }
   // (the seed aligner's traceback workspace serves, as for the Viterbi store: they never run at once on a context)
   if ((rc = nvk_ws_reserve(ctx, WS_SEED_TB, (size_t)need_rows * (size_t)S * 8))) return rc;
   PostArgs a;
@@ -515,12 +655,12 @@ int run_sweeps(const char *what, int second, nvk_ctx *ctx, int64_t n_reads, int6
   a.w_stay = w_stay;
   a.w_step = w_step;
   a.w_skip = w_skip;
-  a.out_marg = out;
+  a.out_marg = moments ? (double *)ctx->ws[WS_STATE_MOM] : out;
   a.out_z = out_z;
   a.out_status = out_status;
   a.rows = (double *)ctx->ws[WS_SEED_TB];
   a.pos = pos;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   if (out_ms)
     for (hipEvent_t &e : ev) NVK_HIP(hipEventCreate(&e));
   for (size_t c = 0; c + 1 < cut.size(); c++) {
@@ -532,14 +672,25 @@ int run_sweeps(const char *what, int second, nvk_ctx *ctx, int64_t n_reads, int6
     if (out_ms) NVK_HIP(hipEventRecord(ev[1], ctx->stream));
     launch_sweep(second, k, a, n, ctx->stream);
     NVK_HIP(hipGetLastError());
+    if (out_ms) NVK_HIP(hipEventRecord(ev[2], ctx->stream));
+    if (moments) {
+      const int n3 = 3 * (int)S;
+      hipLaunchKernelGGL(state_moments_reduce_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, ctx->stream,
+                         (const double *)a.out_marg, (const int32_t *)out_status, a.r0, n, n3, out);
+      NVK_HIP(hipGetLastError());
+    }
     if (out_ms) {
-      NVK_HIP(hipEventRecord(ev[2], ctx->stream));
-      NVK_HIP(hipEventSynchronize(ev[2]));
+      if (moments) NVK_HIP(hipEventRecord(ev[3], ctx->stream));
+      NVK_HIP(hipEventSynchronize(ev[moments ? 3 : 2]));
       float ms = 0.f;
       NVK_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
       out_ms[0] += (double)ms;
       NVK_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
       out_ms[1] += (double)ms;
+      if (moments) {
+        NVK_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
+        out_ms[2] += (double)ms;
+      }
     }
   }
   NVK_HIP(hipStreamSynchronize(ctx->stream));
@@ -567,4 +718,13 @@ extern "C" int nvk_kmer_expectations_dev(nvk_ctx *ctx, int64_t n_reads, int64_t 
                                          int32_t *out_status, int64_t *out_parts, double *out_ms) {
   return run_sweeps("nvk_kmer_expectations_dev", SWEEP_COUNTS, ctx, n_reads, total_events, level, ev_off, k, 0, mean,
                     ac, mc, w_stay, w_step, w_skip, status_in, out_stats, out_z, out_status, out_parts, out_ms);
+}
+
+extern "C" int nvk_kmer_state_moments_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_events, const double *level,
+                                          const int64_t *ev_off, int k, const double *mean, const double *ac,
+                                          const double *mc, double w_stay, double w_step, double w_skip,
+                                          const int32_t *status_in, double *out_moments, double *out_z,
+                                          int32_t *out_status, int64_t *out_parts, double *out_ms) {
+  return run_sweeps("nvk_kmer_state_moments_dev", SWEEP_MOMENTS, ctx, n_reads, total_events, level, ev_off, k, 0, mean,
+                    ac, mc, w_stay, w_step, w_skip, status_in, out_moments, out_z, out_status, out_parts, out_ms);
 }

@@ -77,7 +77,7 @@ struct DeviceModel {
 // ----- host-side objects ------------------------------------------------------------------
 enum { WS_META = 0, WS_ROWS = 1, WS_BANDTMP = 2, WS_SPILL = 3, WS_BP = 4, WS_MISC = 5, WS_ROWS2 = 6, WS_STAGE = 7,
        WS_SPILL_B = 8, WS_STAGE_B = 9, WS_BP_B = 10, WS_LANE_F = 11, WS_LANE_R = 12, WS_ORDER = 13, WS_OFFS = 14, WS_TIES = 15, WS_RSTATE = 16, WS_STEPS = 17,
-       WS_SEED_TB = 18, WS_SEED_OFF = 19, WS_JOINT = 20, WS_SEED_CHAIN = 21, WS_COUNT = 22 };
+       WS_SEED_TB = 18, WS_SEED_OFF = 19, WS_JOINT = 20, WS_SEED_CHAIN = 21, WS_STATE_MOM = 22, WS_COUNT = 23 };
 
 struct nvk_ctx {
   int device;

@@ -38,7 +38,8 @@ the log-likelihood of the stage-2 levels under one normalisation of the weights 
 convention would show up as a fall).
 
 Limits: c and the weights are pooled, not per read; there is no drift term (alpha and beta are constant over a read);
-the table itself is not re-estimated (``estimate_kmer_model`` does that from aligned reads).
+the table itself is not re-estimated (``estimate_decode_model`` does that from raw signal, ``estimate_kmer_model`` from
+aligned reads).
 """
 import math
 

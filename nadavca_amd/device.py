@@ -1183,3 +1183,26 @@ def kmer_expectations_dev(context, level, ev_off, k, mean, ac, mc, w_stay, w_ste
                                              ms if timing else None), 'nvk_kmer_expectations_dev')
     out = (stats[:n], z[:n], status[:n], int(parts.value))
     return out + ((float(ms[0]), float(ms[1])),) if timing else out
+
+
+def kmer_state_moments_dev(context, level, ev_off, k, mean, ac, mc, w_stay, w_step, w_skip, status_in, timing=False):
+    """The per-state E-step of a Baum-Welch re-estimation of the table, nvk_kmer_state_moments_dev: the arguments of
+    ``kmer_expectations_dev``.
+    -> (moments f64 (3, 4^k): per state the posterior weight G0 of the batch's events, G1 = SUM g x and G2 = SUM g x^2
+    over them, the reads that were processed summed in ascending order; z and status as ``kmer_posterior_dev``'s, z bit
+    for bit; the number of parts) and, with ``timing``, the milliseconds of the forward, moments and reduce launches."""
+    import torch
+    lib = _lib.load()
+    dev = ev_off.device
+    n, n_ev = int(ev_off.numel()) - 1, int(level.numel())
+    moments = torch.zeros((3, 4 ** int(k)), dtype=torch.float64, device=dev)
+    z = torch.zeros((max(n, 1), 2), dtype=torch.float64, device=dev)
+    status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    parts, ms = C.c_int64(0), (C.c_double * 3)(0.0, 0.0, 0.0)
+    _lib.check(lib.nvk_kmer_state_moments_dev(context.handle, n, n_ev, _dp(_one(level)), _dp(ev_off), int(k), _dp(mean),
+                                              _dp(ac), _dp(mc), float(w_stay), float(w_step), float(w_skip),
+                                              _opt(status_in, n), _dp(moments), _dp(z), _dp(status), C.byref(parts),
+                                              C.cast(ms, C.POINTER(C.c_double)) if timing else None),
+               'nvk_kmer_state_moments_dev')
+    out = (moments, z[:n], status[:n], int(parts.value))
+    return out + ((float(ms[0]), float(ms[1]), float(ms[2])),) if timing else out
