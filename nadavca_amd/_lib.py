@@ -47,6 +47,14 @@ _dbl = C.c_double
 # min_event_length and the operator's switch
 _BATCH_DEV = [_vp, _i64, _i64, _i64, _i64] + [_vp] * 10 + [_int, _int, _int]
 
+
+def _kmer_sweeps(pos=False):
+    """The three operators on the k-mer forward-backward: context, n_reads, total_events, level, ev_off, k (and
+    ``pos``), the table, the three weights, status_in, the operator's output, out_z, out_status, out_parts, out_ms"""
+    return [_vp, _i64, _i64, _vp, _vp, _int] + [_int] * pos + [_vp] * 3 + [_dbl] * 3 + [_vp] * 4 \
+        + [C.POINTER(_i64), C.POINTER(_dbl)]
+
+
 # every symbol include/nadavca_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     'nvk_last_error': (C.c_char_p, []),
@@ -123,12 +131,9 @@ SIGNATURES = {
                               + [_i64, _vp, _vp]),
     'nvk_viterbi_decode_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _int, _int, _vp, _vp, _vp, _dbl, _dbl, _dbl, _vp, _i64]
                                + [_vp] * 5 + [C.POINTER(_i64)]),
-    'nvk_kmer_posterior_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _int, _int, _vp, _vp, _vp, _dbl, _dbl, _dbl, _vp]
-                               + [_vp] * 3 + [C.POINTER(_i64), C.POINTER(_dbl)]),
-    'nvk_kmer_expectations_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _int, _vp, _vp, _vp, _dbl, _dbl, _dbl, _vp]
-                                  + [_vp] * 3 + [C.POINTER(_i64), C.POINTER(_dbl)]),
-    'nvk_kmer_state_moments_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _int, _vp, _vp, _vp, _dbl, _dbl, _dbl, _vp]
-                                   + [_vp] * 3 + [C.POINTER(_i64), C.POINTER(_dbl)]),
+    'nvk_kmer_posterior_dev': (_int, _kmer_sweeps(pos=True)),
+    'nvk_kmer_expectations_dev': (_int, _kmer_sweeps()),
+    'nvk_kmer_state_moments_dev': (_int, _kmer_sweeps()),
 }
 
 LAUNCH_SWEEP, LAUNCH_EXACT, LAUNCH_ELL = 1, 2, 3   # nvk_launch_rec.op

@@ -117,12 +117,17 @@ def check_table(kmer_model):
         raise ValueError('decode_batch: the table has k = %d; k is %d..%d' % (k, K_MIN, K_MAX))
 
 
-def state_tables_dev(kmer_model, sigma_scale, device):
-    """-> (mean, ac, mc) f64[4^k] on ``device``: the states' levels and the constants of their Gaussians with
+def tables_dev(mean, sigma, sigma_scale, device):
+    """-> (mean, ac, mc) f64 on ``device``: the levels and the constants of their Gaussians with
     sigma * ``sigma_scale``, formed as ``signal_map.base_tables_dev`` forms them"""
     import torch
-    tables = (np.asarray(kmer_model.mean, dtype=np.float64),) + gaussian_constants(kmer_model.sigma, sigma_scale)
+    tables = (np.asarray(mean, dtype=np.float64),) + gaussian_constants(sigma, sigma_scale)
     return [torch.from_numpy(np.ascontiguousarray(t)).to(device) for t in tables]
+
+
+def state_tables_dev(kmer_model, sigma_scale, device):
+    """``tables_dev`` of the model's 4^k states"""
+    return tables_dev(kmer_model.mean, kmer_model.sigma, sigma_scale, device)
 
 
 def capacity_offsets(ev_off, k):

@@ -170,28 +170,35 @@ def fit_loop(e_step, n_events, eligible, rounds, params, sigma_scale, p_stay, p_
                      stats[:, 6:9].copy(), stats[:, 9].astype(np.int64), parts, params)
 
 
+def device_e_step(context, scaled, owner, ev_off, status_in, k, tables, timer=None, names=('forward', 'counts')):
+    """The ``e_step`` of ``fit_loop`` on the device, for stage-2 levels ``scaled`` and their reads ``owner``.
+    ``tables(sigma_scale)`` -> (mean, ac, mc) on the device; ``timer(name, ms)``: called with the two launches'
+    milliseconds of every call, under ``names``."""
+    from .device import kmer_expectations_dev
+
+    def e_step(scale, shift, c, ps, pk):
+        level = fitted_levels_dev(scaled, owner, scale, shift)
+        out = kmer_expectations_dev(context, level, ev_off, k, *tables(c), *transition_weights(ps, pk), status_in,
+                                    timing=timer is not None)
+        if timer is not None:
+            for name, ms in zip(names, out[4]):
+                timer(name, ms)
+        return out[0].cpu().numpy(), out[1].cpu().numpy(), out[3]
+    return e_step
+
+
 def fit_on_device(st, kmer_model, rounds, params, sigma_scale, p_stay, p_skip, start=None, timer=None):
     """The fit of a ``DecodeStages`` after its stage 2 (``st.scaled``, ``st.ev_off``, ``st.status_in``) -> DecodeFit.
     ``start``: a DecodeFit whose per-read ``scale`` and ``shift`` the reads start from; ``timer(name, ms)``: called
     with the forward and counts launches' milliseconds of every E-step (bench tool)."""
     from .batchflow import seg_index
     from .decode import state_tables_dev
-    from .device import kmer_expectations_dev
-    context, dev = kmer_model.context, st.ev_off.device
+    dev = st.ev_off.device
     owner, _ = seg_index(st.ev_off, int(st.scaled.numel()))
     n_events = (st.ev_off[1:] - st.ev_off[:-1]).cpu().numpy()
     eligible = st.ok.cpu().numpy()
-
-    def e_step(scale, shift, c, ps, pk):
-        level = fitted_levels_dev(st.scaled, owner, scale, shift)
-        mean, ac, mc = state_tables_dev(kmer_model, c, dev)
-        out = kmer_expectations_dev(context, level, st.ev_off, kmer_model.get_k(), mean, ac, mc,
-                                    *transition_weights(ps, pk), st.status_in, timing=timer is not None)
-        if timer is not None:
-            timer('forward', out[4][0])
-            timer('counts', out[4][1])
-        return out[0].cpu().numpy(), out[1].cpu().numpy(), out[3]
-
+    e_step = device_e_step(kmer_model.context, st.scaled, owner, st.ev_off, st.status_in, kmer_model.get_k(),
+                           lambda c: state_tables_dev(kmer_model, c, dev), timer)
     return fit_loop(e_step, n_events, eligible, rounds, params, sigma_scale, p_stay, p_skip,
                     None if start is None else start.scale, None if start is None else start.shift)
 

@@ -35,7 +35,7 @@ defaults are uncalibrated.
 import numpy as np
 
 from . import decode_fit, defaults
-from .rawsignal import gaussian_constants, transition_weights
+from .rawsignal import transition_weights
 
 UPDATE = ('mean', 'sd')
 
@@ -126,31 +126,20 @@ def train_loop(fit_e_step, moments_step, n_events, eligible, mean, sigma, rounds
 def device_steps(context, scaled, ev_off, status_in, k, timer=None):
     """The two E-steps of ``train_loop`` on the device, for stage-2 levels ``scaled`` (device tensors) -> (fit_e_step,
     moments_step).  ``timer(name, ms)``: called with the launches' milliseconds of every call (bench tool)."""
-    import torch
     from .batchflow import seg_index
-    from .device import kmer_expectations_dev, kmer_state_moments_dev
+    from .decode import tables_dev
+    from .device import kmer_state_moments_dev
     dev = ev_off.device
     owner, _ = seg_index(ev_off, int(scaled.numel()))
 
-    def tables(mean, sigma, c):
-        arrays = (np.asarray(mean, dtype=np.float64),) + gaussian_constants(sigma, c)
-        return [torch.from_numpy(np.ascontiguousarray(t)).to(dev) for t in arrays]
-
     def fit_e_step(mean, sigma):
-        def e_step(scale, shift, c, ps, pk):
-            level = decode_fit.fitted_levels_dev(scaled, owner, scale, shift)
-            out = kmer_expectations_dev(context, level, ev_off, k, *tables(mean, sigma, c), *transition_weights(ps, pk),
-                                        status_in, timing=timer is not None)
-            if timer is not None:
-                timer('fit forward', out[4][0])
-                timer('fit counts', out[4][1])
-            return out[0].cpu().numpy(), out[1].cpu().numpy(), out[3]
-        return e_step
+        return decode_fit.device_e_step(context, scaled, owner, ev_off, status_in, k,
+                                        lambda c: tables_dev(mean, sigma, c, dev), timer, ('fit forward', 'fit counts'))
 
     def moments_step(mean, sigma, scale, shift, c, ps, pk):
         level = decode_fit.fitted_levels_dev(scaled, owner, scale, shift)
-        out = kmer_state_moments_dev(context, level, ev_off, k, *tables(mean, sigma, c), *transition_weights(ps, pk),
-                                     status_in, timing=timer is not None)
+        out = kmer_state_moments_dev(context, level, ev_off, k, *tables_dev(mean, sigma, c, dev),
+                                     *transition_weights(ps, pk), status_in, timing=timer is not None)
         if timer is not None:
             for name, ms in zip(('forward', 'moments', 'reduce'), out[4]):
                 timer(name, ms)

@@ -1137,6 +1137,24 @@ def viterbi_decode_dev(context, level, ev_off, k, central, mean, ac, mc, l_stay,
     return hit, score[:n], seq[:total_cap], base_event[:total_cap], int(parts.value)
 
 
+def _kmer_sweeps_dev(entry, context, level, ev_off, k, mean, ac, mc, weights, status_in, out, n_ms, pos=None):
+    """One of the three operators on the k-mer forward-backward (``entry``: its symbol; ``out``: its own output tensor,
+    zeroed; ``n_ms``: how many launches it times; ``pos``: the posterior entry's)
+    -> (z (n, 2), status (n,), parts, ms)"""
+    import torch
+    lib = _lib.load()
+    dev = ev_off.device
+    n, n_ev = int(ev_off.numel()) - 1, int(level.numel())
+    z = torch.zeros((max(n, 1), 2), dtype=torch.float64, device=dev)
+    status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    parts, ms = C.c_int64(0), (C.c_double * n_ms)()
+    _lib.check(getattr(lib, entry)(context.handle, n, n_ev, _dp(_one(level)), _dp(ev_off), int(k),
+                                   *(() if pos is None else (int(pos),)), _dp(mean), _dp(ac), _dp(mc),
+                                   *(float(w) for w in weights), _opt(status_in, n), _dp(out), _dp(z), _dp(status),
+                                   C.byref(parts), C.cast(ms, C.POINTER(C.c_double)) if n_ms else None), entry)
+    return z[:n], status[:n], int(parts.value), tuple(float(t) for t in ms)
+
+
 def kmer_posterior_dev(context, level, ev_off, k, pos, mean, ac, mc, w_stay, w_step, w_skip, status_in, timing=False):
     """The forward-backward sums of every read's events (``level`` / ``ev_off``, rescaled) over the 4^k states of the
     table (``mean``, ``ac``, ``mc``), nvk_kmer_posterior_dev.  Device tensors; ``pos``: the letter position of the state
@@ -1146,19 +1164,12 @@ def kmer_posterior_dev(context, level, ev_off, k, pos, mean, ac, mc, w_stay, w_s
     last forward row and its binary exponent, log Z = log(z[:, 0]) + z[:, 1] ln 2; status int32 (n,); the number of
     parts the row store was cut into) and, with ``timing``, the milliseconds of the forward and backward launches."""
     import torch
-    lib = _lib.load()
-    dev = ev_off.device
-    n, n_ev = int(ev_off.numel()) - 1, int(level.numel())
-    marg = torch.zeros((max(n_ev, 1), 4), dtype=torch.float64, device=dev)
-    z = torch.zeros((max(n, 1), 2), dtype=torch.float64, device=dev)
-    status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-    parts, ms = C.c_int64(0), (C.c_double * 2)(0.0, 0.0)
-    _lib.check(lib.nvk_kmer_posterior_dev(context.handle, n, n_ev, _dp(_one(level)), _dp(ev_off), int(k), int(pos),
-                                          _dp(mean), _dp(ac), _dp(mc), float(w_stay), float(w_step), float(w_skip),
-                                          _opt(status_in, n), _dp(marg), _dp(z), _dp(status), C.byref(parts),
-                                          ms if timing else None), 'nvk_kmer_posterior_dev')
-    out = (marg[:n_ev], z[:n], status[:n], int(parts.value))
-    return out + ((float(ms[0]), float(ms[1])),) if timing else out
+    n_ev = int(level.numel())
+    marg = torch.zeros((max(n_ev, 1), 4), dtype=torch.float64, device=ev_off.device)
+    z, status, parts, ms = _kmer_sweeps_dev('nvk_kmer_posterior_dev', context, level, ev_off, k, mean, ac, mc,
+                                            (w_stay, w_step, w_skip), status_in, marg, 2 * bool(timing), pos)
+    out = (marg[:n_ev], z, status, parts)
+    return out + (ms,) if timing else out
 
 
 def kmer_expectations_dev(context, level, ev_off, k, mean, ac, mc, w_stay, w_step, w_skip, status_in, timing=False):
@@ -1170,19 +1181,12 @@ def kmer_expectations_dev(context, level, ev_off, k, mean, ac, mc, w_stay, w_ste
     ``kmer_posterior_dev``'s, z bit for bit; the number of parts) and, with ``timing``, the milliseconds of the forward
     and counts launches."""
     import torch
-    lib = _lib.load()
-    dev = ev_off.device
-    n, n_ev = int(ev_off.numel()) - 1, int(level.numel())
-    stats = torch.zeros((max(n, 1), 10), dtype=torch.float64, device=dev)
-    z = torch.zeros((max(n, 1), 2), dtype=torch.float64, device=dev)
-    status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-    parts, ms = C.c_int64(0), (C.c_double * 2)(0.0, 0.0)
-    _lib.check(lib.nvk_kmer_expectations_dev(context.handle, n, n_ev, _dp(_one(level)), _dp(ev_off), int(k), _dp(mean),
-                                             _dp(ac), _dp(mc), float(w_stay), float(w_step), float(w_skip),
-                                             _opt(status_in, n), _dp(stats), _dp(z), _dp(status), C.byref(parts),
-                                             ms if timing else None), 'nvk_kmer_expectations_dev')
-    out = (stats[:n], z[:n], status[:n], int(parts.value))
-    return out + ((float(ms[0]), float(ms[1])),) if timing else out
+    n = int(ev_off.numel()) - 1
+    stats = torch.zeros((max(n, 1), 10), dtype=torch.float64, device=ev_off.device)
+    z, status, parts, ms = _kmer_sweeps_dev('nvk_kmer_expectations_dev', context, level, ev_off, k, mean, ac, mc,
+                                            (w_stay, w_step, w_skip), status_in, stats, 2 * bool(timing))
+    out = (stats[:n], z, status, parts)
+    return out + (ms,) if timing else out
 
 
 def kmer_state_moments_dev(context, level, ev_off, k, mean, ac, mc, w_stay, w_step, w_skip, status_in, timing=False):
@@ -1192,17 +1196,8 @@ def kmer_state_moments_dev(context, level, ev_off, k, mean, ac, mc, w_stay, w_st
     over them, the reads that were processed summed in ascending order; z and status as ``kmer_posterior_dev``'s, z bit
     for bit; the number of parts) and, with ``timing``, the milliseconds of the forward, moments and reduce launches."""
     import torch
-    lib = _lib.load()
-    dev = ev_off.device
-    n, n_ev = int(ev_off.numel()) - 1, int(level.numel())
-    moments = torch.zeros((3, 4 ** int(k)), dtype=torch.float64, device=dev)
-    z = torch.zeros((max(n, 1), 2), dtype=torch.float64, device=dev)
-    status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-    parts, ms = C.c_int64(0), (C.c_double * 3)(0.0, 0.0, 0.0)
-    _lib.check(lib.nvk_kmer_state_moments_dev(context.handle, n, n_ev, _dp(_one(level)), _dp(ev_off), int(k), _dp(mean),
-                                              _dp(ac), _dp(mc), float(w_stay), float(w_step), float(w_skip),
-                                              _opt(status_in, n), _dp(moments), _dp(z), _dp(status), C.byref(parts),
-                                              C.cast(ms, C.POINTER(C.c_double)) if timing else None),
-               'nvk_kmer_state_moments_dev')
-    out = (moments, z[:n], status[:n], int(parts.value))
-    return out + ((float(ms[0]), float(ms[1]), float(ms[2])),) if timing else out
+    moments = torch.zeros((3, 4 ** int(k)), dtype=torch.float64, device=ev_off.device)
+    z, status, parts, ms = _kmer_sweeps_dev('nvk_kmer_state_moments_dev', context, level, ev_off, k, mean, ac, mc,
+                                            (w_stay, w_step, w_skip), status_in, moments, 3 * bool(timing))
+    out = (moments, z, status, parts)
+    return out + (ms,) if timing else out

@@ -1,14 +1,11 @@
-"""The CPU side of the ``decode_batch(fit=n)`` tests: the restatement of tests/host_shims/expect_host.cpp on numpy
+"""The CPU side of the ``decode_batch(fit=n)`` tests: the restatement of tests/host_shims/kmer_fb_host.cpp on numpy
 arrays, the rules of nvk_kmer_expectations_dev once more as a log-domain Baum-Welch E-step in plain numpy
 (``logaddexp``, no scaling, every move summed at the state it enters; small k), the M-step of
 nadavca_amd/decode_fit.py with per-read Python loops, the workflow on ``decode_ref.cpu_decode`` (``cpu_fit``), and the
 case drawn from the HMM itself that the CPU tests share."""
 import contextlib
-import ctypes as C
 import math
 import os
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -21,53 +18,27 @@ LN2 = math.log(2.0)
 Q_FLOOR = 2.0 ** -9
 STAT_NAMES = ('M0', 'Mx', 'Mxx', 'Mm', 'Mxm', 'Mmm', 'N_stay', 'N_step', 'N_skip', 'floored')
 
-_p = lambda x: x.ctypes.data
-_a = lambda x, dt: np.ascontiguousarray(x, dtype=dt)
-
 
 class ExpectHost:
     def __init__(self, lib):
-        self._f = lib.kmer_expectations_host
-        self._f.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_double] * 3 \
-            + [C.c_void_p] * 4
-        self._f.restype = None
+        self._f = P.sweep_entry(lib, 'kmer_expectations_host')
 
     def expectations(self, level, ev_off, k, mean, ac, mc, w_stay, w_step, w_skip, status_in=None, threads=1):
         """-> (stats f64 (n, 10), z f64 (n, 2), status i32 (n,)); a read that is not processed has zeros.  ``threads``:
         the reads are independent; more than one spreads them over that many calls at once."""
-        level, mean, ac, mc = (_a(x, np.float64) for x in (level, mean, ac, mc))
-        ev_off = _a(ev_off, np.int64)
-        n = ev_off.size - 1
+        n = np.size(ev_off) - 1
         stats = np.zeros((max(n, 1), 10), dtype=np.float64)
-        z, status = np.zeros((max(n, 1), 2), dtype=np.float64), np.zeros(max(n, 1), dtype=np.int32)
-        st = None if status_in is None else _a(status_in, np.int32)
-
-        def run(lo, hi):
-            # (the offsets stay the batch's: the call starts at read lo of every per-read array)
-            self._f(hi - lo, _p(level), _p(ev_off[lo:]), k, _p(mean), _p(ac), _p(mc), w_stay, w_step, w_skip,
-                    None if st is None else _p(st[lo:]), _p(stats[lo:]), _p(z[lo:]), _p(status[lo:]))
-
-        if threads <= 1 or n < 2:
-            run(0, n)
-        else:
-            cuts = [n * t // (4 * threads) for t in range(4 * threads + 1)]
-            with ThreadPoolExecutor(threads) as pool:
-                list(pool.map(lambda c: run(*c), [(a, b) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]))
-        return stats[:n], z[:n], status[:n]
+        z, status = P.spread_reads(self._f, level, ev_off, k, None, (mean, ac, mc), (w_stay, w_step, w_skip), status_in,
+                                   stats, threads)
+        return stats[:n], z, status
 
 
 def build_host(directory):
-    so = os.path.join(str(directory), 'expect_host.so')
-    subprocess.run(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC',
-                    os.path.join(ROOT, 'tests', 'host_shims', 'expect_host.cpp'), '-o', so], check=True)
-    return ExpectHost(C.CDLL(so))
+    return ExpectHost(P.build_shim(directory))
 
 
 def run_host(host, case, w=None, **kw):
-    """The shim on a case of ``decode_ref.pack``; the weights default to exp of the case's costs"""
-    w = tuple(math.exp(c) for c in case['costs']) if w is None else w
-    return host.expectations(case['level'], case['ev_off'], case['k'], case['mean'], case['ac'], case['mc'], *w,
-                             status_in=case['status_in'], **kw)
+    return P.run_case(host.expectations, case, w, **kw)
 
 
 def python_expectations(level, k, mean, ac, mc, w_stay, w_step, w_skip):
@@ -76,24 +47,9 @@ def python_expectations(level, k, mean, ac, mc, w_stay, w_step, w_skip):
     predecessor, the move's weight, the emission and beta of the entered state) where the kernel sums at the state it
     leaves -> (stats (10,), log Z)"""
     level = np.asarray(level, dtype=np.float64)
-    E, S = level.size, 4 ** k
-    mean, ac, mc = (np.asarray(x, dtype=np.float64) for x in (mean, ac, mc))
-    s = np.arange(S)
-    pred = np.stack([a * 4 ** (k - 1) + s // 4 for a in range(4)] + [s] + [c * 4 ** (k - 2) + s // 16 for c in range(16)])
-    lw = np.log(np.array([w_step] * 4 + [w_stay] + [w_skip] * 16))[:, None]
-    em = ac[None, :] - ((level[:, None] - mean[None, :]) * (level[:, None] - mean[None, :])) * mc[None, :]
-    lb = np.maximum(em, P.EM_FLOOR)
-    la = np.zeros((E, S))
-    la[0] = lb[0]
-    for i in range(1, E):
-        la[i] = np.logaddexp.reduce(la[i - 1][pred] + lw, axis=0) + lb[i]
-    lbeta = np.zeros((E, S))
-    for i in range(E - 2, -1, -1):
-        term = lw + (lb[i + 1] + lbeta[i + 1])[None, :]
-        acc = np.full(S, -np.inf)
-        for row_pred, row_term in zip(pred, term):
-            np.logaddexp.at(acc, row_pred, row_term)
-        lbeta[i] = acc
+    E = level.size
+    mean, mc = (np.asarray(x, dtype=np.float64) for x in (mean, mc))
+    em, lb, la, lbeta, pred, lw = P.log_alpha_beta(level, k, mean, ac, mc, w_stay, w_step, w_skip)
     g = la + lbeta
     gamma = np.exp(g - np.logaddexp.reduce(g, axis=1)[:, None])
     g0, g1, g2 = (gamma * mc).sum(axis=1), (gamma * mc * mean).sum(axis=1), (gamma * mc * mean * mean).sum(axis=1)

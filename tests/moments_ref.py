@@ -1,4 +1,4 @@
-"""The CPU side of the ``estimate_decode_model`` tests: the restatement of tests/host_shims/moments_host.cpp on numpy
+"""The CPU side of the ``estimate_decode_model`` tests: the restatement of tests/host_shims/kmer_fb_host.cpp on numpy
 arrays, the rules of nvk_kmer_state_moments_dev once more as a log-domain forward-backward in plain numpy
 (``logaddexp``, no scaling; small k), the M-step and the loop of nadavca_amd/decode_train.py with per-state Python
 loops, the workflow on ``decode_ref.cpu_events`` (``cpu_train``), and the displaced table of the HMM case that the
@@ -6,8 +6,6 @@ tests share."""
 import ctypes as C
 import math
 import os
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -18,16 +16,10 @@ import signal_map_ref as R
 
 ROOT = R.ROOT
 
-_p = lambda x: x.ctypes.data
-_a = lambda x, dt: np.ascontiguousarray(x, dtype=dt)
-
 
 class MomentsHost:
     def __init__(self, lib):
-        self._f = lib.kmer_state_moments_host
-        self._f.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_double] * 3 \
-            + [C.c_void_p] * 4
-        self._f.restype = None
+        self._f = P.sweep_entry(lib, 'kmer_state_moments_host')
         self._total = lib.state_moments_total_host
         self._total.argtypes = [C.c_int64, C.c_int64] + [C.c_void_p] * 3
         self._total.restype = None
@@ -36,70 +28,33 @@ class MomentsHost:
         """-> (moments f64 (3, S): the batch's totals; z f64 (n, 2); status i32 (n,); per_read f64 (n, 3, S): every
         read's own G, zeros for a read that is not processed).  ``threads``: the reads are independent up to the
         totals; more than one spreads them over that many calls at once."""
-        level, mean, ac, mc = (_a(x, np.float64) for x in (level, mean, ac, mc))
-        ev_off = _a(ev_off, np.int64)
-        n, S = ev_off.size - 1, 4 ** k
+        n, S = np.size(ev_off) - 1, 4 ** k
         per_read = np.zeros((max(n, 1), 3, S), dtype=np.float64)
-        z, status = np.zeros((max(n, 1), 2), dtype=np.float64), np.zeros(max(n, 1), dtype=np.int32)
-        st = None if status_in is None else _a(status_in, np.int32)
-
-        def run(lo, hi):
-            # (the offsets stay the batch's: the call starts at read lo of every per-read array)
-            self._f(hi - lo, _p(level), _p(ev_off[lo:]), k, _p(mean), _p(ac), _p(mc), w_stay, w_step, w_skip,
-                    None if st is None else _p(st[lo:]), _p(per_read[lo:]), _p(z[lo:]), _p(status[lo:]))
-
-        if threads <= 1 or n < 2:
-            run(0, n)
-        else:
-            cuts = [n * t // (4 * threads) for t in range(4 * threads + 1)]
-            with ThreadPoolExecutor(threads) as pool:
-                list(pool.map(lambda c: run(*c), [(a, b) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]))
+        z, status = P.spread_reads(self._f, level, ev_off, k, None, (mean, ac, mc), (w_stay, w_step, w_skip), status_in,
+                                   per_read, threads)
         total = np.zeros((3, S), dtype=np.float64)
-        self._total(n, 3 * S, _p(per_read), _p(status), _p(total))
-        return total, z[:n], status[:n], per_read[:n]
+        self._total(n, 3 * S, per_read.ctypes.data, np.ascontiguousarray(status).ctypes.data, total.ctypes.data)
+        return total, z, status, per_read[:n]
 
 
 def build_host(directory):
-    so = os.path.join(str(directory), 'moments_host.so')
-    subprocess.run(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC',
-                    os.path.join(ROOT, 'tests', 'host_shims', 'moments_host.cpp'), '-o', so], check=True)
-    return MomentsHost(C.CDLL(so))
+    return MomentsHost(P.build_shim(directory))
 
 
 def run_host(host, case, w=None, **kw):
-    """The shim on a case of ``decode_ref.pack``; the weights default to exp of the case's costs"""
-    w = tuple(math.exp(c) for c in case['costs']) if w is None else w
-    return host.moments(case['level'], case['ev_off'], case['k'], case['mean'], case['ac'], case['mc'], *w,
-                        status_in=case['status_in'], **kw)
+    return P.run_case(host.moments, case, w, **kw)
 
 
 def python_moments(level, k, mean, ac, mc, w_stay, w_step, w_skip):
     """The rules of nvk_kmer_state_moments_dev for ONE read with events in the log domain, without scaling: the
     posteriors gamma(i, s) from alpha + beta, and their sums over the events -> (G (3, S), log Z)"""
     level = np.asarray(level, dtype=np.float64)
-    E, S = level.size, 4 ** k
-    mean, ac, mc = (np.asarray(x, dtype=np.float64) for x in (mean, ac, mc))
-    s = np.arange(S)
-    pred = np.stack([a * 4 ** (k - 1) + s // 4 for a in range(4)] + [s] + [c * 4 ** (k - 2) + s // 16 for c in range(16)])
-    lw = np.log(np.array([w_step] * 4 + [w_stay] + [w_skip] * 16))[:, None]
-    em = ac[None, :] - ((level[:, None] - mean[None, :]) * (level[:, None] - mean[None, :])) * mc[None, :]
-    lb = np.maximum(em, P.EM_FLOOR)
-    la = np.zeros((E, S))
-    la[0] = lb[0]
-    for i in range(1, E):
-        la[i] = np.logaddexp.reduce(la[i - 1][pred] + lw, axis=0) + lb[i]
-    lbeta = np.zeros((E, S))
-    for i in range(E - 2, -1, -1):
-        term = lw + (lb[i + 1] + lbeta[i + 1])[None, :]
-        acc = np.full(S, -np.inf)
-        for row_pred, row_term in zip(pred, term):
-            np.logaddexp.at(acc, row_pred, row_term)
-        lbeta[i] = acc
+    _, _, la, lbeta, _, _ = P.log_alpha_beta(level, k, mean, ac, mc, w_stay, w_step, w_skip)
     g = la + lbeta
     gamma = np.exp(g - np.logaddexp.reduce(g, axis=1)[:, None])
     G = np.stack([gamma.sum(axis=0), (gamma * level[:, None]).sum(axis=0),
                   (gamma * level[:, None] * level[:, None]).sum(axis=0)])
-    return G, float(np.logaddexp.reduce(la[E - 1]))
+    return G, float(np.logaddexp.reduce(la[-1]))
 
 
 # ---- the M-step and the loop, with per-state loops -------------------------------------------------------------------

@@ -1,4 +1,5 @@
-"""The CPU side of the posterior tests: the restatement of tests/host_shims/posterior_host.cpp on numpy arrays, the rules
+"""The CPU side of the posterior tests: the restatement of tests/host_shims/kmer_fb_host.cpp on numpy arrays (the shim,
+the spreading of reads over threads and the log-domain alpha and beta serve expect_ref and moments_ref too), the rules
 of nvk_kmer_posterior_dev once more as a log-domain forward-backward in plain numpy (``logaddexp``, no scaling; small
 k), what ``decode_batch(qualities=True)`` does with the operator's outputs in numpy with per-read loops
 (``cpu_qualities``), the measures of the quality claim, and the constructed cases the test files share."""
@@ -29,49 +30,75 @@ def weights(p_stay, p_skip):
     return p_stay, 1.0 - p_stay - p_skip, p_skip
 
 
+def build_shim(directory):
+    """tests/host_shims/kmer_fb_host.cpp, compiled once per directory -> the CDLL"""
+    so = os.path.join(str(directory), 'kmer_fb_host.so')
+    if not os.path.exists(so):
+        subprocess.run(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC',
+                        os.path.join(ROOT, 'tests', 'host_shims', 'kmer_fb_host.cpp'), '-o', so], check=True)
+    return C.CDLL(so)
+
+
+def sweep_entry(lib, name, pos=False):
+    """An entry of the shim that takes the sweeps' arguments (``pos``: after k, as the posterior entry does)"""
+    f = getattr(lib, name)
+    f.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int] + [C.c_int] * pos + [C.c_void_p] * 3 \
+        + [C.c_double] * 3 + [C.c_void_p] * 4
+    f.restype = None
+    return f
+
+
+def spread_reads(f, level, ev_off, k, pos, tables, w, status_in, out, threads):
+    """An entry of ``sweep_entry`` on a batch.  ``out``: the entry's own output, zeroed; indexed by read unless it is
+    per event (the posterior's marginals, ``pos`` not None).  ``threads``: the reads are independent; more than one
+    spreads them over that many calls at once -> (z f64 (n, 2), status i32 (n,))"""
+    level, mean, ac, mc = (_a(x, np.float64) for x in (level,) + tuple(tables))
+    ev_off = _a(ev_off, np.int64)
+    n = ev_off.size - 1
+    z, status = np.zeros((max(n, 1), 2), dtype=np.float64), np.zeros(max(n, 1), dtype=np.int32)
+    st = None if status_in is None else _a(status_in, np.int32)
+
+    def run(lo, hi):
+        # (the offsets stay the batch's: the call starts at read lo of every per-read array)
+        f(hi - lo, _p(level), _p(ev_off[lo:]), k, *(() if pos is None else (pos,)), _p(mean), _p(ac), _p(mc), *w,
+          None if st is None else _p(st[lo:]), _p(out if pos is not None else out[lo:]), _p(z[lo:]), _p(status[lo:]))
+
+    if threads <= 1 or n < 2:
+        run(0, n)
+    else:
+        cuts = [n * t // (4 * threads) for t in range(4 * threads + 1)]
+        with ThreadPoolExecutor(threads) as pool:
+            list(pool.map(lambda c: run(*c), [(a, b) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]))
+    return z[:n], status[:n]
+
+
 class PosteriorHost:
     def __init__(self, lib):
-        self._f = lib.kmer_posterior_host
-        self._f.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 \
-            + [C.c_double] * 3 + [C.c_void_p] * 4
-        self._f.restype = None
+        self._f = sweep_entry(lib, 'kmer_posterior_host', pos=True)
 
     def posterior(self, level, ev_off, k, pos, mean, ac, mc, w_stay, w_step, w_skip, status_in=None, threads=1):
         """-> (marg f64 (events, 4), z f64 (n, 2), status i32 (n,)).  ``threads``: the reads are independent; more than
         one spreads them over that many calls at once."""
-        level, mean, ac, mc = (_a(x, np.float64) for x in (level, mean, ac, mc))
-        ev_off = _a(ev_off, np.int64)
-        n = ev_off.size - 1
-        marg = np.zeros((max(level.size, 1), 4), dtype=np.float64)
-        z, status = np.zeros((max(n, 1), 2), dtype=np.float64), np.zeros(max(n, 1), dtype=np.int32)
-        st = None if status_in is None else _a(status_in, np.int32)
-
-        def run(lo, hi):
-            # (the offsets stay the batch's: the call starts at read lo of every per-read array)
-            self._f(hi - lo, _p(level), _p(ev_off[lo:]), k, pos, _p(mean), _p(ac), _p(mc), w_stay, w_step, w_skip,
-                    None if st is None else _p(st[lo:]), _p(marg), _p(z[lo:]), _p(status[lo:]))
-
-        if threads <= 1 or n < 2:
-            run(0, n)
-        else:
-            cuts = [n * t // (4 * threads) for t in range(4 * threads + 1)]
-            with ThreadPoolExecutor(threads) as pool:
-                list(pool.map(lambda c: run(*c), [(a, b) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]))
-        return marg[:level.size], z[:n], status[:n]
+        events = np.size(level)
+        marg = np.zeros((max(events, 1), 4), dtype=np.float64)
+        z, status = spread_reads(self._f, level, ev_off, k, pos, (mean, ac, mc), (w_stay, w_step, w_skip), status_in,
+                                 marg, threads)
+        return marg[:events], z, status
 
 
 def build_host(directory):
-    so = os.path.join(str(directory), 'posterior_host.so')
-    subprocess.run(['g++', '-O2', '-std=c++17', '-ffp-contract=off', '-shared', '-fPIC',
-                    os.path.join(ROOT, 'tests', 'host_shims', 'posterior_host.cpp'), '-o', so], check=True)
-    return PosteriorHost(C.CDLL(so))
+    return PosteriorHost(build_shim(directory))
+
+
+def run_case(method, case, w=None, pos=None, **kw):
+    """A shim's method on a case of ``decode_ref.pack``; the weights default to exp of the case's costs"""
+    w = tuple(math.exp(c) for c in case['costs']) if w is None else w
+    return method(case['level'], case['ev_off'], case['k'], *(() if pos is None else (pos,)), case['mean'], case['ac'],
+                  case['mc'], *w, status_in=case['status_in'], **kw)
 
 
 def run_host(host, case, pos, w=None, **kw):
-    """The shim on a case of ``decode_ref.pack``; the weights default to exp of the case's costs"""
-    w = tuple(math.exp(c) for c in case['costs']) if w is None else w
-    return host.posterior(case['level'], case['ev_off'], case['k'], pos, case['mean'], case['ac'], case['mc'], *w,
-                          status_in=case['status_in'], **kw)
+    return run_case(host.posterior, case, w, pos, **kw)
 
 
 def log_z(z):
@@ -81,15 +108,19 @@ def log_z(z):
         return np.log(z[:, 0]) + z[:, 1] * LN2
 
 
-def python_posterior(level, k, pos, mean, ac, mc, w_stay, w_step, w_skip):
-    """The rules of nvk_kmer_posterior_dev for ONE read with events in the log domain, without scaling: every
-    predecessor and successor of every state looked up flat and joined by logaddexp -> (marg (E, 4), log Z)"""
-    E, S = len(level), 4 ** k
+def log_alpha_beta(level, k, mean, ac, mc, w_stay, w_step, w_skip):
+    """The forward-backward of the three operators for ONE read with events in the log domain, without scaling: every
+    predecessor and successor of every state looked up flat and joined by logaddexp -> (em (E, S) before the floor, lb
+    after it, log alpha, log beta, pred (21, S): per move the state it comes from, lw (21, 1): the moves' log
+    weights)"""
+    level = np.asarray(level, dtype=np.float64)
+    E, S = level.size, 4 ** k
     mean, ac, mc = (np.asarray(x, dtype=np.float64) for x in (mean, ac, mc))
     s = np.arange(S)
     pred = np.stack([a * 4 ** (k - 1) + s // 4 for a in range(4)] + [s] + [c * 4 ** (k - 2) + s // 16 for c in range(16)])
     lw = np.log(np.array([w_step] * 4 + [w_stay] + [w_skip] * 16))[:, None]
-    lb = np.array([np.maximum(ac - ((e - mean) * (e - mean)) * mc, EM_FLOOR) for e in np.asarray(level, np.float64)])
+    em = ac[None, :] - ((level[:, None] - mean[None, :]) * (level[:, None] - mean[None, :])) * mc[None, :]
+    lb = np.maximum(em, EM_FLOOR)
     la = np.zeros((E, S))
     la[0] = lb[0]
     for i in range(1, E):
@@ -102,10 +133,17 @@ def python_posterior(level, k, pos, mean, ac, mc, w_stay, w_step, w_skip):
         for row_pred, row_term in zip(pred, term):
             np.logaddexp.at(acc, row_pred, row_term)
         lbeta[i] = acc
-    letter = (s >> (2 * (k - 1 - pos))) & 3
+    return em, lb, la, lbeta, pred, lw
+
+
+def python_posterior(level, k, pos, mean, ac, mc, w_stay, w_step, w_skip):
+    """The rules of nvk_kmer_posterior_dev for ONE read with events: the letter marginals from alpha + beta of
+    ``log_alpha_beta`` -> (marg (E, 4), log Z)"""
+    _, _, la, lbeta, _, _ = log_alpha_beta(level, k, mean, ac, mc, w_stay, w_step, w_skip)
+    letter = (np.arange(4 ** k) >> (2 * (k - 1 - pos))) & 3
     g = la + lbeta
     cls = np.stack([np.logaddexp.reduce(g[:, letter == x], axis=1) for x in range(4)], axis=1)
-    return np.exp(cls - np.logaddexp.reduce(cls, axis=1)[:, None]), float(np.logaddexp.reduce(la[E - 1]))
+    return np.exp(cls - np.logaddexp.reduce(cls, axis=1)[:, None]), float(np.logaddexp.reduce(la[-1]))
 
 
 # ---- the workflow on the operator's outputs ------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""nvk_kmer_expectations_dev against its CPU restatement (tests/host_shims/expect_host.cpp: the full matrices, the sums
+"""nvk_kmer_expectations_dev against its CPU restatement (tests/host_shims/kmer_fb_host.cpp: the full matrices, the sums
 over all states on arrays, the events descending), bit for bit in the ten stats, z and status, for k = 2..6 and so for
 every workgroup size of the counts sweep (1, 4, 16, 64 and 256 threads).  The cases are tests/decode_ref.py's (E = 0, 1,
 2, 3, 64, 65 and 300, a ``status_in`` entry), the three extreme cases of tests/posterior_ref.py, and at k = 6 the

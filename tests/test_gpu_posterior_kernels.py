@@ -1,4 +1,4 @@
-"""nvk_kmer_posterior_dev against its CPU restatement (tests/host_shims/posterior_host.cpp: the full matrices, the
+"""nvk_kmer_posterior_dev against its CPU restatement (tests/host_shims/kmer_fb_host.cpp: the full matrices, the
 sums over all states on arrays), bit for bit in every f64 and i32, for k = 2..6 and so for every workgroup size of the
 two sweeps (1, 4, 16, 64 and 256 threads).  The cases are tests/decode_ref.py's (E = 0, 1, 2, 3, 64, 65 and 300, a
 ``status_in`` entry) with ``pos`` 0, ``central`` and k - 1, the three extreme cases of tests/posterior_ref.py, and at

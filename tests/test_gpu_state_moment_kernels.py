@@ -1,4 +1,4 @@
-"""nvk_kmer_state_moments_dev against its CPU restatement (tests/host_shims/moments_host.cpp: the full matrices, D on
+"""nvk_kmer_state_moments_dev against its CPU restatement (tests/host_shims/kmer_fb_host.cpp: the full matrices, D on
 arrays, the events descending, the reads ascending), bit for bit in the 3 x 4^k moments, z and status, for k = 2..6 and
 so for every workgroup size of the moments sweep (1, 4, 16, 64 and 256 threads).  The cases are tests/decode_ref.py's
 (E = 0, 1, 2, 3, 64, 65 and 300, a ``status_in`` entry), the three extreme cases of tests/posterior_ref.py, and at k = 6
