@@ -857,6 +857,35 @@ int nvk_phase_votes_dev(nvk_ctx *ctx, int64_t n_sites, int alphabet, const int64
                         const int64_t *row_read, const double *val, const int64_t *read_block, const double *read_llr,
                         double clip, double *out_vote, int64_t *out_agree, int64_t *out_against);
 
+/* Per-site modification frequencies over sets of rows (nadavca_amd/phase_mods.py: phase_mods_batch,
+ * mod_site_frequencies).  THE CONTRACT.  The library is built with -ffp-contract=off: every expression below is a
+ * rounded operation in the order written.
+ *   rows       val f64[n_rows]: one log-likelihood ratio d per row ("modified" against "canonical", as call_mods_batch
+ *              writes it), in the caller's order; group i32[n_rows], or NULL: every row is group 0
+ *   sites      s = 0 .. n_sites-1, each a range of rows site_lo[s] .. site_hi[s] (i64, inside 0 .. n_rows, hi >= lo; a
+ *              range that leaves 0 .. n_rows is cut to it, so no call reads outside val)
+ *   sets       q = 0 .. n_sets-1 (1 <= n_sets <= 8), each a mask set_mask[q] (u32) over the groups: set q of a site holds
+ *              the site's rows whose group g is in 0 .. 31 with bit g of set_mask[q] set.  A row whose d is not a number
+ *              and a row whose group is outside 0 .. 31 are in no set.
+ *   value      e = min(max(d, -clip), clip): -inf gives -clip, +inf gives +clip
+ *   estimate   per (site, set), over the values of the set's rows: t, u, L(f) = sum t(f, e_i), g(f) = sum u(f, e_i) and
+ *              the estimate f^ exactly as nvk_allele_solve_dev defines them: f^ = 0 unless g(0) > 0; f^ = 1 if
+ *              g(1) >= 0; otherwise 52 bisection steps on [0, 1] (lo = m when g(m) > 0, else hi = m) and
+ *              f^ = (lo + hi) / 2.  L(f^) is evaluated as (the sum of the positive e_i) + (the sum of the logarithms);
+ *              exp of a positive number is never formed.
+ *   sums       every sum runs over the SITE's rows in row order as 64 interleaved partial sums: row j of the site (not
+ *              of the set) goes to sum j mod 64, ascending j; a row outside the set adds +0.0; wave_sum's butterfly adds
+ *              the partial sums up.  No atomics: the same bits on every run, and the same bits whether the kernel keeps
+ *              a site's rows in registers or reads them again.
+ *   outputs    laid out [site][set], every entry written: out_count i64 = the rows of the set, out_fraction f64 = f^,
+ *              out_ll f64 = L(f^), 0 where f^ = 0 (and so where the set is empty)
+ * All sets of a site are solved in one launch, which is timed under NVK_K_ALLELE.  n_sites == 0 launches nothing (and
+ * writes nothing).  0 < clip < inf.  NVK_ERR_INVALID for bad arguments or a NULL array that is not empty (val may be NULL
+ * only where n_rows == 0; group may always be).  Device pointers. */
+int nvk_mod_site_solve_dev(nvk_ctx *ctx, int64_t n_sites, int64_t n_rows, const int64_t *site_lo, const int64_t *site_hi,
+                           const double *val, const int32_t *group, int n_sets, const uint32_t *set_mask, double clip,
+                           int64_t *out_count, double *out_fraction, double *out_ll);
+
 /* Model-free per-site summaries (nadavca_amd/site_levels.py: site_levels_batch): the pile-up of the reads' event levels
  * over every reference position and strand.  THE CONTRACT.  The library is built with -ffp-contract=off: every
  * expression below is a rounded operation in the order written.  Inputs are one aligned batch in the flat layout above:

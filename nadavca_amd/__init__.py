@@ -16,6 +16,7 @@ from .mod_train import ModModelEstimate, estimate_mod_model  # noqa: F401
 from .call_indels import call_indels_batch  # noqa: F401
 from .allele_fractions import estimate_allele_fractions_batch  # noqa: F401
 from .phase import PhaseBatch, phase_reads_batch  # noqa: F401
+from .phase_mods import PhasedModBatch, mod_site_frequencies, phase_mods_batch  # noqa: F401
 from .site_levels import SiteComparison, SiteLevelBatch, compare_site_levels, site_levels_batch  # noqa: F401
 from .site_ranks import SiteRankComparison, compare_site_ranks, site_rank_tests_batch  # noqa: F401
 from .site_mixtures import SiteMixtureComparison, compare_site_mixtures, site_mixture_tests_batch  # noqa: F401
@@ -27,7 +28,8 @@ from .decode_train import DecodeModelEstimate, estimate_decode_model  # noqa: F4
 
 __all__ = ['align_signal', 'align_signal_batch', 'estimate_snps', 'estimate_snps_batch', 'dtw', 'SeedAligner',
            'ReferenceSet', 'estimate_kmer_model', 'call_mods_batch', 'call_indels_batch',
-           'estimate_allele_fractions_batch', 'phase_reads_batch', 'PhaseBatch', 'site_levels_batch',
+           'estimate_allele_fractions_batch', 'phase_reads_batch', 'PhaseBatch', 'phase_mods_batch', 'PhasedModBatch',
+           'mod_site_frequencies', 'site_levels_batch',
            'compare_site_levels', 'SiteLevelBatch', 'SiteComparison', 'compare_site_ranks', 'site_rank_tests_batch', 'SiteRankComparison', 'compare_site_mixtures',
            'site_mixture_tests_batch', 'SiteMixtureComparison', 'estimate_mod_model', 'ModModelEstimate', 'signal_map_batch',
            'SignalMapBatch', 'signal_locate_batch', 'LocateBatch', 'decode_batch', 'DecodeBatch', 'DecodeFit',

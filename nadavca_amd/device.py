@@ -877,6 +877,37 @@ def phase_sites_dev(context, ref_off, chunk_start, reverse, key, val, sorted_key
                 read_block=read_block, read_llr=read_llr, read_sites=read_sites, flips=flips)
 
 
+# ---- per-site modification frequencies over sets of rows (nadavca_amd/phase_mods.py) -------------------------------
+def mod_site_solve_dev(context, site_lo, site_hi, val, group, set_mask, clip):
+    """Per (site, set): (count int64, fraction f64, ll f64), each (S, n_sets), device tensors (include/nadavca_hip.h:
+    nvk_mod_site_solve_dev).  site_lo / site_hi i64 (S,): the sites' ranges of rows; val f64 (rows,): the rows'
+    log-likelihood ratios; group i32 (rows,) or None (every row is group 0); set_mask: 1 .. 8 integers in 0 .. 2^32 - 1,
+    set q holds the rows whose group's bit is set in ``set_mask[q]``."""
+    import torch
+    lib = _lib.load()
+    dev = site_lo.device
+    masks = [int(m) for m in np.asarray(set_mask).reshape(-1)]
+    if any(not 0 <= m < 1 << 32 for m in masks):
+        raise ValueError('mod_site_solve_dev: a set mask outside 0 .. 2^32 - 1')
+    S, n_rows, Q = int(site_lo.numel()), int(val.numel()), len(masks)
+    if int(site_hi.numel()) != S or (group is not None and int(group.numel()) != n_rows):
+        raise ValueError('mod_site_solve_dev: site_hi or group does not match site_lo or val in length')
+    if site_lo.dtype != torch.int64 or site_hi.dtype != torch.int64 or val.dtype != torch.float64 \
+            or (group is not None and group.dtype != torch.int32):
+        raise ValueError('mod_site_solve_dev: site_lo / site_hi int64, val float64, group int32')
+    # uint32 bit patterns held in an int32 tensor
+    mask = torch.from_numpy(np.array(masks, dtype=np.uint32).view(np.int32)).to(dev)
+    count = torch.zeros((S, Q), dtype=torch.int64, device=dev)
+    fraction = torch.zeros((S, Q), dtype=torch.float64, device=dev)
+    ll = torch.zeros((S, Q), dtype=torch.float64, device=dev)
+    site_lo, site_hi, val = site_lo.contiguous(), site_hi.contiguous(), val.contiguous()
+    group = None if group is None else group.contiguous()
+    _lib.check(lib.nvk_mod_site_solve_dev(
+        context.handle, S, n_rows, _dp(site_lo), _dp(site_hi), _opt(val, n_rows), _opt(group, n_rows), Q, _dp(mask),
+        float(clip), _dp(count), _dp(fraction), _dp(ll)), 'nvk_mod_site_solve_dev')
+    return count, fraction, ll
+
+
 # ---- per-site event-level pile-up (nadavca_amd/site_levels.py) --------------------------------------------------
 SITE_COLUMNS = ('level', 'stdv', 'dwell', 'resid')
 

@@ -503,3 +503,85 @@ def make_mixed_read_batch(n, haplotypes, weights, seed=0, model=None, length=400
     info = dict(haplotype=np.array(which, dtype=np.int32), reverse=np.array(revs, dtype=bool),
                 start=np.array(starts, dtype=np.int64))
     return rb, truth, info
+
+
+def make_phased_modified_read_batch(n, haplotypes, weights, modified, model5, seed=0, pattern='CG', mod_offset=0,
+                                    mod_code=4, length=400, spread=40, dwell=(3, 17), noise=0.35, anchor_density=1.0,
+                                    jitter=0, both_strands=True, raw_scale=12.0, raw_shift=90.0, raw_dtype=np.int16):
+    """``make_mixed_read_batch`` with modified bases: the haplotypes differ by substitutions, and ``modified[h]`` lists
+    the FORWARD coordinates x of the occurrences of ``pattern`` on haplotype h that are modified, on both strands.
+    ``pattern`` (over ACGT) must equal its own reverse complement, so that an occurrence at x on the forward strand is
+    one on the reverse strand too: the modified bases are the forward strand's base x + mod_offset and the reverse
+    strand's base paired with forward x + len(pattern) - 1 - mod_offset (for ``CG``: the C at x, and the C paired
+    with the G at x + 1).  ``model5``: a table whose alphabet holds ``mod_code`` (the tuple of ``load_model_arrays``;
+    ``kmer_train.extend_kmer_model`` makes one).  The truth of each strand is built from the haplotype's canonical
+    bases; a read's signal is drawn from its TRUTH sequence with ``model5``, its basecalled sequence is canonical.
+    The other arguments, the draws of a read (haplotype, length, start, dwells, noise, anchors from
+    ``default_rng([seed, i])``) and the result (ReadBatch, truth, info) are ``make_mixed_read_batch``'s: ``info`` holds
+    the read's ``haplotype``, ``reverse`` and ``start``."""
+    from .readbatch import ReadBatch, BaseAlignmentBatch
+    what = 'make_phased_modified_read_batch'
+    haps = [np.asarray(h, dtype=np.int64).reshape(-1) for h in haplotypes]
+    if not haps or any(h.size != haps[0].size for h in haps):
+        raise ValueError('%s: the haplotypes must be of one length' % what)
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.size != len(haps) or not (w >= 0).all() or not w.sum() > 0:
+        raise ValueError('%s: one non-negative weight per haplotype, not all zero' % what)
+    w = w / w.sum()
+    k, central, alphabet, mean, sigma = model5
+    if not 4 <= mod_code < alphabet:
+        raise ValueError('%s: the table has no code %d' % (what, mod_code))
+    pat = np.array([{'A': 0, 'C': 1, 'G': 2, 'T': 3}[c] for c in pattern], dtype=np.int64)
+    m = int(pat.size)
+    if not 0 <= int(mod_offset) < m:
+        raise ValueError('%s: mod_offset %r outside the pattern %r' % (what, mod_offset, pattern))
+    if not np.array_equal(pat, 3 - pat[::-1]):
+        raise ValueError('%s: the pattern %r is not its own reverse complement' % (what, pattern))
+    if len(modified) != len(haps):
+        raise ValueError('%s: one list of modified occurrences per haplotype' % what)
+    G = haps[0].size
+    strands = []      # per haplotype: (canonical, truth) of the forward and of the reverse strand
+    for h, sites in zip(haps, modified):
+        x = np.asarray(sites, dtype=np.int64).reshape(-1)
+        if ((x < 0) | (x + m > G)).any() or any(not np.array_equal(h[a:a + m], pat) for a in x.tolist()):
+            raise ValueError('%s: a modified occurrence is not one of %r on its haplotype' % (what, pattern))
+        fwd, rev = h, 3 - h[::-1]
+        t_fwd, t_rev = fwd.copy(), rev.copy()
+        t_fwd[x + int(mod_offset)] = mod_code
+        t_rev[G - 1 - (x + m - 1 - int(mod_offset))] = mod_code
+        strands.append(((fwd, t_fwd), (rev, t_rev)))
+    first_strands = (haps[0], 3 - haps[0][::-1])
+    seqs, pairs, raws, mbase, msig, which, revs, starts = [], [], [], [], [], [], [], []
+    for i in range(n):
+        rng = np.random.default_rng([seed, i])
+        h = int(rng.choice(len(haps), p=w))
+        L = int(min(G, max(1, length + rng.integers(-spread, spread + 1))))
+        x0 = int(rng.integers(0, G - L + 1))
+        reverse = bool(both_strands and i % 2)
+        seq, tseq = (s[x0:x0 + L] for s in strands[h][reverse])
+        ids = kmer_ids(tseq, 0, L, k, central, alphabet)
+        dw = rng.integers(dwell[0], dwell[1] + 1, L)
+        first = np.concatenate([[0], np.cumsum(dw)])
+        x = np.clip(np.repeat(mean[ids], dw) + rng.normal(0.0, noise, int(first[-1])), -5.0, 5.0)
+        raw = raw_scale * x + raw_shift
+        raws.append(np.rint(raw).astype(raw_dtype) if np.issubdtype(raw_dtype, np.integer)
+                    else raw.astype(raw_dtype))
+        keep = np.nonzero(rng.random(L) < anchor_density)[0]
+        at = np.clip(first[keep] + rng.integers(-jitter, jitter + 1, keep.size), 0, int(first[-1]) - 1)
+        mbase.append(keep)
+        msig.append(np.maximum.accumulate(at) if at.size else at)
+        same = np.nonzero(seq == first_strands[reverse][x0:x0 + L])[0]
+        pairs.append(np.stack([same, x0 + same], axis=1).astype(np.int64))
+        seqs.append(seq.astype(np.int32))
+        which.append(h)
+        revs.append(reverse)
+        starts.append(x0)
+    off = lambda xs: np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.int64)
+    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dtype=dt)
+    rb = ReadBatch(cat(raws, raw_dtype), off(raws), cat(seqs, np.int32), off(seqs), cat(mbase, np.int64),
+                   cat(msig, np.int64), off(mbase))
+    truth = BaseAlignmentBatch(cat([p[:, 0] for p in pairs], np.int64), cat([p[:, 1] for p in pairs], np.int64),
+                               off(pairs), np.array(revs, dtype=bool))
+    info = dict(haplotype=np.array(which, dtype=np.int32), reverse=np.array(revs, dtype=bool),
+                start=np.array(starts, dtype=np.int64))
+    return rb, truth, info
