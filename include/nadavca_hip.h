@@ -455,7 +455,9 @@ int nvk_estimate_edit_hypotheses_batch_dev(
  *   reverse strand: column b -> alphabet-1-b and rows flipped,
  *   acc[chunk_start[j] + p][b] += ll'[p][b],  coverage[chunk_start[j] + p] += 1.
  * ll/reference/ref_off as produced by nvk_estimate_log_likelihoods_batch(_dev).
- * Reads with status != 0 are skipped.  All pointers are device pointers; acc f64
+ * Reads with status != 0 are skipped (status NULL: every read counts); positions outside [0, ref_len) are
+ * dropped.  normalization_event_length is finite and not 0 (NVK_ERR_INVALID otherwise: a NaN would make every sum
+ * NaN, an infinity every sum 0).  All pointers are device pointers; acc f64
  * [ref_len*alphabet] and coverage i64[ref_len] are accumulated into (not zeroed). */
 int nvk_consensus_accumulate_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, int alphabet,
                                  const double *ll, const int32_t *reference,

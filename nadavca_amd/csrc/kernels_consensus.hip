@@ -90,7 +90,7 @@ extern "C" int nvk_consensus_accumulate_dev(nvk_ctx *ctx, int64_t n_reads, int64
                                             double normalization_event_length, int64_t ref_len,
                                             double *acc, int64_t *coverage) {
   if (!ctx || n_reads < 0 || total_ref < 0 || alphabet < 2 || alphabet > 8 || ref_len < 0 ||
-      !(normalization_event_length != 0.0)) {
+      !isfinite(normalization_event_length) || normalization_event_length == 0.0) {
     nvk_set_error("nvk_consensus_accumulate_dev: bad argument");
     return NVK_ERR_INVALID;
   }

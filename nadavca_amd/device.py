@@ -558,7 +558,8 @@ def consensus_accumulate_dev(context, dbatch, ll, chunk_start, reverse, status, 
     """Normalise, strand-correct and scatter-add the per-read log-likelihood rows ``ll`` (as written by
     ``estimate_log_likelihoods_dev``) into the per-position sums ``acc`` (ref_len, alphabet) f64 and the
     coverage ``cov`` (ref_len,) i64 — torch tensors on the batch's device, created zeroed when not given,
-    accumulated into otherwise.  chunk_start i64 (n,), reverse i32 (n,), status i32 (n,) device tensors."""
+    accumulated into otherwise.  chunk_start i64 (n,), reverse i32 (n,), status i32 (n,) device tensors; ``status``
+    None: every read counts."""
     torch = dbatch.torch
     lib = _lib.load()
     alpha = int(ll.shape[1])
@@ -568,7 +569,7 @@ def consensus_accumulate_dev(context, dbatch, ll, chunk_start, reverse, status, 
         cov = torch.zeros(int(ref_len), dtype=torch.int64, device=dbatch.device)
     _lib.check(lib.nvk_consensus_accumulate_dev(
         context.handle, dbatch.n, dbatch.total_ref, alpha, _dp(ll), _dp(dbatch.reference), _dp(dbatch.ref_off),
-        _dp(chunk_start), _dp(reverse), _dp(status), float(normalization_event_length), int(ref_len),
+        _dp(chunk_start), _dp(reverse), _opt(status, dbatch.n), float(normalization_event_length), int(ref_len),
         _dp(acc), _dp(cov)), 'nvk_consensus_accumulate_dev')
     return acc, cov
 
