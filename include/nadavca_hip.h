@@ -208,6 +208,15 @@ int nvk_last_launches(nvk_ctx *ctx, int cap, nvk_launch_rec *out, int *n_records
 int nvk_last_read_skews(nvk_ctx *ctx, int64_t n_reads, int32_t *out_c, int32_t *out_cw);
 int nvk_built_sweep_variants(int cap, int32_t *out, int *n_variants);
 
+/* SELF-TEST of a helper no result can check.  The sweeps of csrc/kernels_align3.hip move their running scale by the
+ * largest exponent the wave holds, taken with wave_max_i (csrc/wave.h: the maximum of the wave's 64 lanes in a scalar
+ * register, on the DPP path).  A rescale by any common power of two is exact, so a wrong maximum changes no event —
+ * at worst it hands a read to the exact kernel — and no comparison of results can see it.
+ * nvk_selftest_wave_max: one small kernel in which wave w reduces in[w][0..63] with that very function and stores
+ * out[w].  in: i32[n][64], out: i32[n], both DEVICE pointers; synchronous.  tests/test_gpu_wave_max.py compares it
+ * with the host's maximum of each row. */
+int nvk_selftest_wave_max(nvk_ctx *ctx, const int32_t *in, int64_t n, int32_t *out);
+
 /* replaces dtw.KmerModel(k, central_position, alphabet_size, mean, sigma)
  * (dtwmodule.cpp:12-13, kmer_model.cpp:6-14).  mean/sigma: host f64[n], n = alphabet^k */
 int nvk_model_create(nvk_ctx *ctx, int k, int central_position, int alphabet_size,

@@ -76,6 +76,7 @@ SIGNATURES = {
     'nvk_last_launches': (_int, [_vp, _int, _vp, C.POINTER(_int)]),
     'nvk_last_read_skews': (_int, [_vp, _i64, _vp, _vp]),
     'nvk_built_sweep_variants': (_int, [_int, _vp, C.POINTER(_int)]),
+    'nvk_selftest_wave_max': (_int, [_vp, _vp, _i64, _vp]),
     'nvk_model_create': (_int, [_vp, _int, _int, _int, _vp, _vp, _i64, C.POINTER(_vp)]),
     'nvk_model_destroy': (None, [_vp]),
     'nvk_model_info': (_int, [_vp, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int)]),
@@ -294,6 +295,22 @@ class Context:
         check(self._lib.nvk_last_read_skews(self.handle, int(n_reads), _vp(c.ctypes.data), _vp(cw.ctypes.data)),
               'nvk_last_read_skews')
         return c, cw
+
+    def selftest_wave_max(self, rows):
+        """nvk_selftest_wave_max: ``rows`` int32 [n, 64] -> int32 [n], what wave_max_i (csrc/wave.h), the function
+        behind the sweeps' rescale decision, returns for each row of 64 lanes."""
+        import numpy as np
+        import torch
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        if rows.ndim != 2 or rows.shape[1] != 64:
+            raise ValueError('selftest_wave_max: rows must be [n, 64]')
+        dev = torch.device('cuda', self.device)
+        d_in = torch.from_numpy(rows).to(dev)
+        d_out = torch.zeros(rows.shape[0], dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        check(self._lib.nvk_selftest_wave_max(self.handle, _vp(d_in.data_ptr()), rows.shape[0], _vp(d_out.data_ptr())),
+              'nvk_selftest_wave_max')
+        return d_out.cpu().numpy()
 
     def set_workspace_limit(self, nbytes):
         check(self._lib.nvk_ctx_set_workspace_limit(self.handle, int(nbytes)), 'nvk_ctx_set_workspace_limit')

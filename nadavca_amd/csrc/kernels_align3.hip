@@ -65,10 +65,13 @@
 // re-evaluation at a row switch (the planner keeps the lane idle for the steps on which stale densities
 // pass); no tie margin carried from update to update (five vector instructions of every step, three of them at the
 // FP64 rate, and two registers: path_step.h) and no copy of the score's scale for the rare first-row case (row 0's
-// lane keeps G = 0 by itself).  Tried and not kept (DESIGN.md 5.1 has the measurements): 32 forward steps per trip (128 registers),
+// lane keeps G = 0 by itself); no trip through the LDS crossbar for the wave's largest exponent at the rescale steps
+// (wave_max_i, wave.h: six DPP maxima and a v_readlane where a butterfly of six ds_bpermute_b32 was, each waited
+// for).  Tried and not kept (DESIGN.md 5.1 and 5.1a have the measurements): 32 forward steps per trip (128 registers),
 // the sample of the next density read one step earlier, update bits shifted in with v_addc, the history-ring
 // read pipelined one step ahead with age-1 values by DPP, lane records prefetched into L2, 5 waves per SIMD in
-// the forward sweep.
+// the forward sweep, the first prefetch loads in step order (a wait by count on every even step instead of one
+// drain per trip), the reverse sweep's scale word loaded one period ahead.
 #include <math.h>
 
 #include <new>
@@ -232,11 +235,6 @@ __device__ __forceinline__ double emission_product(double e, double e1, double e
   return P;
 }
 
-__device__ __forceinline__ int wave_max_i(int v) {  // result in a scalar register
-  for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-  return __builtin_amdgcn_readfirstlane(v);
-}
-
 // running scale: L(u) = L(u-1) + delta_u; delta is nonzero only on rescale steps
 struct Scale {
   int L;        // current log-scale
@@ -268,7 +266,7 @@ struct Scale {
 // reverse sweep — no path search, half the registers — runs with 6 waves per SIMD instead of 4 (one launch,
 // both sweeps per wave, was measured and not kept: DESIGN.md 5).  Launch bounds, waves per SIMD:
 constexpr int LB = 4;           // forward sweep
-constexpr int LB_REV = 7;       // (73 registers wanted, 72 allowed: two spilled ones outside the step loop; 6.45 against 6.59 ms at 6)
+constexpr int LB_REV = 7;       // (72 registers allowed; config 2's kernel takes 70 and has no scratch since wave_max_i went the DPP way; 6.45 against 6.59 ms at 6)
 constexpr int LB_REV_TEAM = 6;  // (the team's reverse sweep: 80 registers; 5 and 4 measured the same within noise)
 //
 // W: waves per read.  1 — the mapping above.  W > 1 (wide bands: ReadMeta::cw != 0) — a
@@ -718,6 +716,11 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
       int init_live = 1;  // (uniform, scalar registers) row 0 is still being swept
       int top_live = (top < TL) ? 1 : 0;  // the last row has been started
 
+      // The prefetch ring: PF / 2 loads of 16 bytes in flight, PF steps ahead.  (The scheduler issues these first
+      // loads last slot first, so on the way in cur_v[0] is the youngest and the wait at the head of a trip, which
+      // has to hold on that way too, is for ALL loads in flight, vmcnt(0), where PF / 2 - 1 could stay out.  A
+      // scheduling barrier behind each load here keeps them in step order and turns that wait into vmcnt(3) on
+      // every even step — measured SLOWER, forward launch +0.7 %, and not kept: DESIGN.md 5.1a.)
       double2 cur_v[PF / 2];
 #pragma unroll
       for (int q = 0; q < PF / 2; q++) cur_v[q] = spill_load2(spill_rs, lane16, q);

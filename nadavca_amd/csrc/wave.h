@@ -99,3 +99,9 @@ __device__ __forceinline__ int wave_scan_max_dpp(int v) {
 __device__ __forceinline__ int wave_scan_min_dpp(int v) {
   return wave_scan_dpp(v, 0x7fffffff, [](int a, int b) { return min(a, b); });
 }
+
+// Maximum of the wave in a scalar register: the last lane of the DPP scan (six v_max_i32_dpp and one v_readlane_b32;
+// the butterfly of wave_max is six ds_bpermute_b32, each waited for, on the chain of whoever calls it once per
+// rescale period).  Needs all 64 lanes enabled, as every DPP read of a neighbour does; nvk_selftest_wave_max
+// (include/nadavca_hip.h) runs this very function against a host maximum.
+__device__ __forceinline__ int wave_max_i(int v) { return __builtin_amdgcn_readlane(wave_scan_max_dpp(v), 63); }
