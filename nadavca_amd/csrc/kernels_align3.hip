@@ -67,7 +67,16 @@
 // FP64 rate, and two registers: path_step.h) and no copy of the score's scale for the rare first-row case (row 0's
 // lane keeps G = 0 by itself); no trip through the LDS crossbar for the wave's largest exponent at the rescale steps
 // (wave_max_i, wave.h: six DPP maxima and a v_readlane where a butterfly of six ds_bpermute_b32 was, each waited
-// for).  Tried and not kept (DESIGN.md 5.1 and 5.1a have the measurements): 32 forward steps per trip (128 registers),
+// for); with one wave per read no vector test for "some lane is past its row" on every step and no ballot loop over
+// the lanes that are — the rows are left in row order (SWITCH ORDER, kernels_plan.hip), so the step compares the
+// oldest open row's sample index with its band end as two scalars and the block serves that row's lane, with no
+// per-lane masks carried through it ("an emitting lane switched" is the served lane's parity, "first row" / "last row"
+// / the oldest open row come from the scalar row counter, the bound on G travels with the row mass), no search for
+// the oldest open row, and no wait right behind the record's scalar loads (unconditional, index clamped, the record
+// made inert where the lane gets no row: the row's bookkeeping runs under their latency); a lane found past its row's
+// end at a rescale step sends the read to the exact kernel.  (The teams keep the ballot form: changing that block
+// made a lockstep step slower.)
+// Tried and not kept (DESIGN.md 5.1 and 5.1a have the measurements): 32 forward steps per trip (128 registers),
 // the sample of the next density read one step earlier, update bits shifted in with v_addc, the history-ring
 // read pipelined one step ahead with age-1 values by DPP, lane records prefetched into L2, 5 waves per SIMD in
 // the forward sweep, the first prefetch loads in step order (a wait by count on every even step instead of one
@@ -401,6 +410,8 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
       int r_old = (W == 1) ? top : max(wave_max_i(r), -1);  // the oldest open row of this wave
       // sample index of the oldest open row (scalar); no row at all: a value no refill test reaches
       int i_old = (r_old >= 0) ? __builtin_amdgcn_readlane(i, r_old & 63) : 0x40000000;
+      // (one wave per read) the band start of that row, where its lane leaves it: read with i_old when r_old moves
+      int e_old = (r_old >= 0) ? __builtin_amdgcn_readlane(bs, r_old & 63) : -0x40000000;
       int filled_lo = (i_old / CH + 1) * CH;
       while (i_old - 3 < filled_lo) {
         filled_lo -= CH;
@@ -454,6 +465,56 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
         }
         if (PAIR && age == 1 && u > 1) cq = ldexp(cq, -sc.d_last);  // exact: the constant is back
         shift_now = (age == 0 && u > 0) ? sc.d_last : 0;
+        if constexpr (W == 1) {
+          // The row switch as a scalar event (one wave per read).  The rows are left in row order (SWITCH ORDER,
+          // kernels_plan.hip), so the lane that leaves its row next is the one that holds the oldest open row: the
+          // step compares two scalars and the block serves "while the oldest open row is past its start".  What
+          // the ballot form carried per lane — "took a new row", "first row" — follows from the row counter.
+          if (i_old < e_old) {
+            int sw_em = 0;  // (scalar) an emitting lane has taken a new row: the served lane's parity
+            do {
+              const int fl = r_old & 63;
+              const int rn = r_old - 64;  // the row that lane takes
+              // (unconditional, index clamped: the bookkeeping below runs under the load's latency)
+              Lane3 nx = lane3_sload(revl + max(rn, 0));
+              // No row left for that lane (rn < 0): the clamped record made inert — never inside a span (pA, pW: the
+              // lane's values stay zero whatever its other fields say) and never past its start (the guard at the
+              // rescale steps).  As a mask behind the compiler's back: written as a condition it becomes a branch
+              // that takes the load, and the wait for it, along.
+              const int nm = __builtin_amdgcn_readfirstlane(rn) >> 31;
+              nx.bs = (nx.bs & ~nm) | (-0x40000000 & nm);
+              nx.pA = (nx.pA & ~nm) | (0x40000000 & nm);
+              nx.pW &= ~nm;
+              if (lane == fl) {
+                r = rn;
+                prev = 0.0;
+                i += nx.mg >> 12;
+                TAKE_LANE(nx);
+                hi = nx.end;
+              }
+              if (PAIR) sw_em |= ~nm & (fl ^ 1);  // (bit 0: the reverse sweep's emitting lanes are the even ones)
+              r_old -= 1;
+              // (no open row left: a sample index neither this test nor a refill test ever reaches; both lanes
+              // read, then chosen: a conditional v_readlane is a branch)
+              const int io = __builtin_amdgcn_readlane(i, r_old & 63), eo = __builtin_amdgcn_readlane(bs, r_old & 63);
+              i_old = (r_old >= 0) ? io : 0x40000000;
+              e_old = (r_old >= 0) ? eo : -0x40000000;
+            } while (i_old < e_old);
+            if (PAIR) {  // see the team's form below
+              if (sw_em & 1) {
+                const double pmn = pair_swap(mean), pac = pair_swap(ac2), pmc = pair_swap(mc2);
+                const int ip = pair_swap(i);
+                if (!em) { mean = pmn; ac2 = pac; mc2 = pmc; }
+                ia = (em ? i - 1 : ip - 2) - ((u & 1) ? 0 : 1);
+              }
+            }
+            // (from the row counter, as sign bits: r_old == top; 0 <= r_old < 64)
+            unsigned blk = (unsigned)r_old >> 6;
+            blk = (unsigned)__builtin_amdgcn_readfirstlane((int)blk);
+            init_live = (int)((unsigned)(top - r_old - 1) >> 31);
+            row0_live = (int)((blk - 1u) >> 31);
+          }
+        } else {
         bool fin = (i < bs);
         if (__any(fin)) {
           bool redo = false;  // this lane has taken a new row
@@ -509,6 +570,7 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
           init_live &= (__builtin_amdgcn_readlane(r, top & 63) == top) ? 1 : 0;
           row0_live = (__builtin_amdgcn_readfirstlane(r) == 0) ? 1 : 0;
         }
+        }
         {
           // (a younger row may be one sample beyond the oldest one; PAIR: and its partner evaluates one
           // sample further ahead)
@@ -554,7 +616,8 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
         if (init_live | row0_live) {  // (one scalar test for the two rare cases: the first and the last row)
           asm volatile("");
           if (init_live) {
-            if (is_init) o = ACTIVE_R ? ldexp(1.0, sc.L) : 0.0;
+            // (one wave per read: the lane's row number says it; a team carries the flag as before)
+            if ((W == 1) ? (r == top) : is_init) o = ACTIVE_R ? ldexp(1.0, sc.L) : 0.0;
           }
           if (row0_live) {  // row 0 lives on lane 0; only its kmax is read
             if (o != 0.0) kmax = max(kmax, __builtin_amdgcn_frexp_exp(o) - sc.L);
@@ -581,6 +644,8 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
           // (range guard of the values themselves: here only — an inf or NaN between two rescale steps
           // reaches the posterior sums of its row and fails the row-mass check)
           suspect |= !(o <= HUGE_V);
+          // (the switch order's guard: a lane still on a row it is past was not the oldest one when it left)
+          if (W == 1) suspect |= (i < bs);
           int mx;
           if (W == 1) {
             mx = wave_max_i((o != 0.0) ? __builtin_amdgcn_frexp_exp(o) : -0x40000000);
@@ -686,6 +751,7 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
       int r_old = min(64 * wv, T);  // the oldest open row of this wave
       // sample index of the oldest open row (scalar): t_min for row 0 (offs[0] = 0)
       int i_old = (r_old < T) ? __builtin_amdgcn_readfirstlane(i) : -0x40000000;
+      int e_old = (r_old < T) ? __builtin_amdgcn_readfirstlane(be) : 0x40000000;  // (one wave per read) its band end
       int filled_hi = ((i_old - MEL - 1) > 0 ? (i_old - MEL - 1) / CH : 0) * CH;
       while (i_old + 2 >= filled_hi) {
         for (int w = lane; w < CH; w += 64) {
@@ -749,6 +815,51 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
             }
             if (PAIR && age == 1 && u > 1) cq = ldexp(cq, -sc.d_last);
             shift_now = (age == 0 && u > 0) ? sc.d_last : 0;
+            if constexpr (W == 1) {
+              if (i_old > e_old) {  // see the reverse sweep
+                int sw_em = 0;
+                do {
+                  const int fl = r_old & 63;
+                  const int rn = r_old + 64;  // the row that lane takes
+                  Lane3 nx = lane3_sload(fwdl + min(rn, top));
+                  // (no row left for that lane: the clamped record made inert, see the reverse sweep)
+                  const int nm = __builtin_amdgcn_readfirstlane(top - rn) >> 31;
+                  nx.end = (nx.end & ~nm) | (0x40000000 & nm);
+                  nx.pA = (nx.pA & ~nm) | (0x40000000 & nm);
+                  nx.pW &= ~nm;
+                  if (lane == fl) {
+                    // (the verdict of path_step.h's bound on G travels with the row mass: a sum no row can have)
+                    smin = fmin(smin, (abs(G) >= path_step::PATH_G_GUARD) ? -1.0 : rsum);
+                    smax = fmax(smax, rsum);
+                    rsum = 0.0;
+                    r = rn;
+                    prev = 0.0;
+                    bestn = 0.0; G = GBIG;
+                    i -= nx.mg >> 12;
+                    TAKE_LANE(nx);
+                    be = nx.end; lo = nx.lo;
+                  }
+                  if (PAIR) sw_em |= ~nm & fl;  // (bit 0: the forward sweep's emitting lanes are the odd ones)
+                  r_old += 1;
+                  const int io = __builtin_amdgcn_readlane(i, r_old & 63), eo = __builtin_amdgcn_readlane(be, r_old & 63);
+                  i_old = (r_old < T) ? io : -0x40000000;
+                  e_old = (r_old < T) ? eo : 0x40000000;
+                } while (i_old > e_old);
+                if (PAIR) {
+                  if (sw_em & 1) {
+                    const double pmn = pair_swap(mean), pac = pair_swap(ac2), pmc = pair_swap(mc2);
+                    const int ip = pair_swap(i);
+                    if (!em) { mean = pmn; ac2 = pac; mc2 = pmc; }
+                    ia = (em ? i : ip + 1) + ((u & 1) ? 0 : 1);
+                  }
+                }
+                // (from the row counter, as sign bits: r_old == 0; r_old <= top < r_old + 64)
+                unsigned blk = (unsigned)(top - r_old) >> 6;
+                blk = (unsigned)__builtin_amdgcn_readfirstlane((int)blk);
+                init_live = (int)((unsigned)(r_old - 1) >> 31);
+                top_live = (int)((blk - 1u) >> 31);
+              }
+            } else {
             bool fin = (i > be);
             if (__any(fin)) {
               bool redo = false;
@@ -799,6 +910,7 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
               i_old = (r_old < T) ? __builtin_amdgcn_readlane(i, r_old & 63) : -0x40000000;
               init_live &= (__builtin_amdgcn_readfirstlane(r) == 0) ? 1 : 0;
               top_live = (__builtin_amdgcn_readlane(r, top & 63) == top) ? 1 : 0;
+            }
             }
             {
               const int need_max = i_old + (PAIR ? 2 : 1);  // (PAIR: the partner evaluates one sample further ahead)
@@ -889,7 +1001,7 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
             if (init_live | top_live) {  // (one scalar test for the two rare cases: the first and the last row)
               asm volatile("");
               if (init_live) {
-                if (is_init) {
+                if ((W == 1) ? (r == 0) : is_init) {  // (see the reverse sweep)
                   o = IN_BAND ? ldexp(1.0, sc.L) : 0.0;
                   post = ldexp(o * suf, kap);
                   dpv = post;  // (on scale G = 0, see above)
@@ -938,6 +1050,7 @@ __global__ __launch_bounds__(64 * W, PHASE == 1 ? (W > 1 ? LB_REV_TEAM : LB_REV)
             }
             if (age == RS - 1) {
               suspect |= !(o <= HUGE_V);
+              if (W == 1) suspect |= (i > be);  // (the switch order's guard, see the reverse sweep)
               int mx;
               if (W == 1) {
                 mx = wave_max_i((o != 0.0) ? __builtin_amdgcn_frexp_exp(o) : -0x40000000);

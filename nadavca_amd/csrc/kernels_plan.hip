@@ -273,6 +273,24 @@ __device__ __forceinline__ void plan_rows(const Store st, const DeviceModel &dm,
   // two alternate, so a pair of rows needs no skew at all — and never so low that a row would start or
   // end before the row above it (the kernel's bookkeeping of the oldest open row relies on that order).
   // Without transition rows, and for min event lengths above 2, g[r] = max(mel - 1, 1).
+  //
+  // SWITCH ORDER.  The sweeps of kernels_align3.hip (one wave per read) serve a row switch as a scalar event
+  // of the oldest open row, which needs the rows to be LEFT in row order: row r is left after step off[r] + BE(r)
+  // (reverse sweep: before step off[r] + BS(r)), so
+  //     off[r] - off[r-1] >= BE(r-1) - BE(r)   and   off[r] - off[r-1] >= BS(r-1) - BS(r)          (*)
+  // must hold for every r.  It does, in every plan mode:
+  //   - plan_bands makes the band starts a prefix maximum and the band ends a suffix minimum, so BS and BE are
+  //     non-decreasing in r and the right-hand sides of (*) are <= 0 — also where the ends are flat, clipped to N
+  //     or to 0 on many rows: equal ends leave in the order of the offsets;
+  //   - the uniform offsets (teams, long reads, no fixed point) differ by c or cw >= 1;
+  //   - the least offsets differ by at least g[r] (x is a prefix maximum, so non-decreasing), and the cap min(g, c)
+  //     only ever lowers g to c >= 1.  g[r] >= 0 leaves nothing to show.  g[r] < 0 is possible only with transition
+  //     rows at min event length 2, for an odd row r = 2k + 1 fed by the emitting step of row 2k: there
+  //       HI(r-1) = max(be[k], be[k+1] - 2) + 1, HI(r) = be[k+1]  =>  HI(r-1) - HI(r) = max(be[k] - be[k+1] + 1, -1)
+  //       LO(r-1) = bs[k], LO(r) = min(bs[k+1], bs[k] + 2) - 1    =>  LO(r-1) - LO(r) = max(bs[k] - bs[k+1] + 1, -1)
+  //     and g[r] is at least both, i.e. at least BE(r-1) - BE(r) + 1 and BS(r-1) - BS(r) + 1.
+  // tests/test_switch_order_cpu.py restates this on the host; the sweeps themselves hold a lane that is found past
+  // its row's end at a rescale step to account (the read goes to the exact kernel).
   // With S[r] = g[1] + .. + g[r] and x[r] = off[r] - S[r] the first lower bound and the second are a
   // prefix maximum per block of 64 rows (the second's constant k[r] = hi[r-64] - lo[r] + 1 + idle - (S[r] - S[r-64])
   // is taken from the bands), and the upper bound is a suffix maximum of off[r] - c*r; both are iterated to
