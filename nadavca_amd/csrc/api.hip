@@ -481,6 +481,41 @@ int check_site_samples(const char *what, nvk_ctx *ctx, int64_t n_rows_a, const i
   return NVK_OK;
 }
 
+int check_read_rows(const char *what, nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, const int64_t *ref_off,
+                    std::initializer_list<ReadRowsArray> arrays, bool *nothing_to_do) {
+  *nothing_to_do = true;
+  if (!ctx || n_reads < 0 || n_reads > 0x7fffffff || total_ref < 0) {
+    nvk_set_error("%s: invalid argument", what);
+    return NVK_ERR_INVALID;
+  }
+  if (n_reads == 0) {
+    if (total_ref != 0) {
+      nvk_set_error("%s: total_ref %lld with no reads", what, (long long)total_ref);
+      return NVK_ERR_INVALID;
+    }
+    return NVK_OK;
+  }
+  bool offs = ref_off;
+  for (const auto &x : arrays) offs = offs && x.off;
+  if (!offs) {
+    nvk_set_error("%s: offsets are NULL", what);
+    return NVK_ERR_INVALID;
+  }
+  NVK_HIP(hipSetDevice(ctx->device));
+  std::vector<int64_t> off;
+  int rc;
+  if ((rc = nvk_fetch_offsets(ctx, "reference", ref_off, n_reads, off, "total_ref", total_ref))) return rc;
+  for (const auto &x : arrays) {
+    if ((rc = nvk_fetch_offsets(ctx, x.name, x.off, n_reads, off))) return rc;
+    if (off[n_reads] > 0 && !x.data) {  // (a data array may be NULL only when its offsets end at 0)
+      nvk_set_error("%s: %s is NULL", what, x.name);
+      return NVK_ERR_INVALID;
+    }
+  }
+  *nothing_to_do = total_ref == 0;
+  return NVK_OK;
+}
+
 namespace {
 
 // The prologue of the two device-pointer operators: their argument checks, the device, and the batch as

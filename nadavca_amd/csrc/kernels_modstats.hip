@@ -14,8 +14,8 @@
 // wave (wave_sum_n, the order of nvk_site_moments_dev).  Two runs give the same bits, and the numpy restatement of the tests
 // gives them too.
 //
-// Work split of the row pass: ONE WAVE PER READ, its lanes over the read's bases 64 at a time, as kmer_event_kernel:
-// offsets, status and the base pointers of the read's site list are wave-uniform.  A lane finds the sites of its window
+// Work split of the row pass: one wave per read, its lanes over the read's bases (read_rows.h); the base pointers of
+// the read's site list are wave-uniform with the rest of its view.  A lane finds the sites of its window
 // by a binary search over the read's site positions (a read holds tens of sites; neighbouring lanes walk the same few
 // cache lines) and reads at most five entries from there.  An event's samples are read once, whatever the number of
 // rows: a and b are sums around the canonical window's level c0, and the sums around another level c follow from
@@ -32,47 +32,35 @@
 
 #include "nvk_internal.h"
 #include "kmer.h"
+#include "read_rows.h"
 #include "wave.h"
 
 namespace {
 
 constexpr int NT = 256;
-constexpr int MAX_K = 16;    // longest k-mer whose key fits the checks below (alphabet^k <= 2^31)
 constexpr int MAX_SITES = 4; // sites of one window at most: 2^4 - 1 rows
 constexpr int NCOL = 4;      // w, n, sd, sq
 
-// one wave per read (grid-stride), its lanes over the read's bases.  FILL false: out_count per base; true: the rows.
+// the row pass of read_rows.h.  FILL false: out_count per base; true: the rows.  A read that did not align has its
+// rows counted and written with key -1.
 // info[0]: the bases with more than MAX_SITES sites in their window; info[1]: set where row_off disagrees.
 template <bool FILL>
-__global__ __launch_bounds__(NT) void mod_rows_kernel(int64_t n_reads, const double *signal, const int64_t *sig_off,
-                                                      const int32_t *events, const int64_t *ref_off,
-                                                      const int32_t *reference, const int32_t *ctx_before,
-                                                      const int64_t *cb_off, const int32_t *ctx_after,
-                                                      const int64_t *ca_off, const int32_t *status, int k, int central,
-                                                      int alphabet, int trim, const int64_t *site_off,
-                                                      const int32_t *site_pos, const double *site_gamma, int mod_code,
-                                                      const double *level, int64_t n_rows, const int64_t *row_off,
-                                                      int64_t *out_count, int64_t *out_key, double *out_val,
-                                                      unsigned long long *info) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t waves = (int64_t)gridDim.x * (NT / 64);
+__global__ __launch_bounds__(NT) void mod_rows_kernel(int64_t n_reads, ReadArrays arrays, const int32_t *events,
+                                                      const int32_t *reference, int k, int central, int alphabet,
+                                                      int trim, const int64_t *site_off, const int32_t *site_pos,
+                                                      const double *site_gamma, int mod_code, const double *level,
+                                                      int64_t n_rows, const int64_t *row_off, int64_t *out_count,
+                                                      int64_t *out_key, double *out_val, unsigned long long *info) {
   const DeviceModel dm{k, central, alphabet, 0, nullptr, nullptr, nullptr};  // (kmer.h reads the window's shape only)
   int skipped = 0;
-  for (int64_t rd = (int64_t)blockIdx.x * (NT / 64) + wave; rd < n_reads; rd += waves) {
-    // the read's arrays; sizes of one read fit 32 bits (the C-ABI's reads are below 2^31 samples and bases)
-    const int64_t r0 = ref_off[rd];
-    const int R = (int)(ref_off[rd + 1] - r0);
-    const int S = (int)(site_off[rd + 1] - site_off[rd]);
-    const int32_t *sp = site_pos + site_off[rd];
-    const double *sg = site_gamma + site_off[rd];
-    const bool live = !status || status[rd] == NVK_READ_OK;
-    const double *x = signal + sig_off[rd];
-    const int N = (int)(sig_off[rd + 1] - sig_off[rd]);
-    const int B = (int)(cb_off[rd + 1] - cb_off[rd]);
-    const int A = (int)(ca_off[rd + 1] - ca_off[rd]);
-    const int32_t *ref = reference + r0, *cb = ctx_before + cb_off[rd], *ca = ctx_after + ca_off[rd];
-    for (int g = lane; g < R; g += 64) {
+  for_each_read<int, RV_SIGNAL | RV_CONTEXTS>(arrays, n_reads, [&](const ReadView<int> &v) {
+    const int64_t r0 = v.r0;
+    const int R = v.R;
+    const int S = (int)(site_off[v.rd + 1] - site_off[v.rd]);
+    const int32_t *sp = site_pos + site_off[v.rd];
+    const double *sg = site_gamma + site_off[v.rd];
+    const int32_t *ref = reference + r0;
+    for_each_base(v, [&](int g) {
       const int p0 = g - central;  // first base of the window, reference-part coordinates
       // the read's sites inside [p0, p0 + k): the first MAX_SITES of them, and whether there is one more
       int lo = 0, hi = S;
@@ -104,28 +92,27 @@ __global__ __launch_bounds__(NT) void mod_rows_kernel(int64_t n_reads, const dou
       const int cnt = over ? 0 : (1 << m) - 1;
       if (!FILL) {
         out_count[r0 + g] = cnt;
-        continue;
+        return;
       }
       const int64_t row0 = row_off[r0 + g], row1 = row_off[r0 + g + 1];
       if (row0 < 0 || row1 > n_rows || row1 - row0 != cnt) {  // the caller's width is not this pass's: write nothing
         atomicOr(info + 1, 1ull);
-        continue;
+        return;
       }
-      if (cnt == 0) continue;
+      if (cnt == 0) return;
       // the event, counted under kmer_event_kernel's conditions: its sums around the canonical window's level
       int64_t key0 = -1;
       int len = 0;
       double c0 = 0.0, a = 0.0, b = 0.0;
-      if (live && g >= trim && g < R - trim && p0 >= -B && p0 + k - 1 < R + A) {
-        int s = events[2 * (r0 + g)], e = events[2 * (r0 + g) + 1];
-        s = s < 0 ? 0 : (s > N ? N : s);  // numpy slice clamping, as event_means_kernel
-        e = e < 0 ? 0 : (e > N ? N : e);
-        if (e > s) key0 = kmer_id_checked(dm, ref, R, cb, B, ca, A, g);
+      if (v.live && counted_base(g, R, trim) && window_inside(g, k, central, R, v.B, v.A)) {
+        int s, e;
+        event_span(events, r0 + g, v.N, s, e);
+        if (e > s) key0 = kmer_id_checked(dm, ref, R, v.cb, v.B, v.ca, v.A, g);
         if (key0 >= 0) {
           len = e - s;
           c0 = level[key0];
           for (int i = s; i < e; i++) {
-            const double dv = x[i] - c0;
+            const double dv = v.x[i] - c0;
             a = a + dv;
             b = b + dv * dv;
           }
@@ -169,10 +156,10 @@ __global__ __launch_bounds__(NT) void mod_rows_kernel(int64_t n_reads, const dou
         dst[2] = sd;
         dst[3] = sq;
       }
-    }
-  }
+    });
+  });
   skipped = wave_sum(skipped);
-  if (lane == 0 && skipped) atomicAdd(info, (unsigned long long)skipped);
+  if ((threadIdx.x & 63) == 0 && skipped) atomicAdd(info, (unsigned long long)skipped);
 }
 
 // one wave per run (grid-stride): the four weighted sums of its rows and their number
@@ -201,17 +188,6 @@ __global__ __launch_bounds__(NT) void mod_reduce_kernel(int64_t n_keys, const do
   }
 }
 
-// alphabet^k, or -1 when k / alphabet are outside the served range
-int64_t table_size(int k, int alphabet) {
-  if (k < 1 || k > MAX_K || alphabet < 1 || alphabet > 64) return -1;
-  int64_t n = 1;
-  for (int i = 0; i < k; i++) {
-    n *= alphabet;
-    if (n > ((int64_t)1 << 31)) return -1;
-  }
-  return n;
-}
-
 }  // namespace
 
 extern "C" int nvk_mod_kmer_rows_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, const double *signal,
@@ -224,11 +200,11 @@ extern "C" int nvk_mod_kmer_rows_dev(nvk_ctx *ctx, int64_t n_reads, int64_t tota
                                      int64_t *out_key, double *out_val, int64_t *windows_skipped) {
   const char *what = "nvk_mod_kmer_rows_dev";
   if (windows_skipped) *windows_skipped = 0;
-  if (!ctx || n_reads < 0 || n_reads > 0x7fffffff || total_ref < 0 || n_sites < 0 || n_rows < 0) {
+  if (n_sites < 0 || n_rows < 0) {
     nvk_set_error("%s: invalid argument", what);
     return NVK_ERR_INVALID;
   }
-  if (table_size(k, alphabet) < 0 || central < 0 || central >= k || trim < 0) {
+  if (kmer_table_size(k, alphabet) < 0 || central < 0 || central >= k || trim < 0) {
     nvk_set_error("%s: k %d, central %d, alphabet %d, trim %d outside the served range (1 <= k, 0 <= central < k, "
                   "alphabet^k <= 2^31, trim >= 0)", what, k, central, alphabet, trim);
     return NVK_ERR_INVALID;
@@ -242,38 +218,24 @@ extern "C" int nvk_mod_kmer_rows_dev(nvk_ctx *ctx, int64_t n_reads, int64_t tota
     nvk_set_error("%s: out_key, out_val and row_off go together", what);
     return NVK_ERR_INVALID;
   }
+  bool nothing;
+  int rc = check_read_rows(what, ctx, n_reads, total_ref, ref_off, {{"signal", sig_off, signal},
+                           {"context_before", cb_off, ctx_before}, {"context_after", ca_off, ctx_after}}, &nothing);
+  if (rc) return rc;
   if (n_reads == 0) {
-    if (total_ref != 0 || n_sites != 0 || (fill && n_rows != 0)) {
-      nvk_set_error("%s: total_ref %lld, n_sites %lld, n_rows %lld with no reads", what, (long long)total_ref,
-                    (long long)n_sites, (long long)n_rows);
+    if (n_sites != 0 || (fill && n_rows != 0)) {
+      nvk_set_error("%s: n_sites %lld, n_rows %lld with no reads", what, (long long)n_sites, (long long)n_rows);
       return NVK_ERR_INVALID;
     }
     return NVK_OK;
   }
-  if (!sig_off || !ref_off || !cb_off || !ca_off || !site_off) {
-    nvk_set_error("%s: offsets are NULL", what);
-    return NVK_ERR_INVALID;
-  }
-  NVK_HIP(hipSetDevice(ctx->device));
   std::vector<int64_t> off;
-  int rc;
-  if ((rc = nvk_fetch_offsets(ctx, "reference", ref_off, n_reads, off, "total_ref", total_ref))) return rc;
   if ((rc = nvk_fetch_offsets(ctx, "site", site_off, n_reads, off, "n_sites", n_sites))) return rc;
-  // (a data array may be NULL only when its offsets end at 0)
-  const struct { const char *name; const int64_t *off; const void *data; } arr[3] = {
-      {"signal", sig_off, signal}, {"context_before", cb_off, ctx_before}, {"context_after", ca_off, ctx_after}};
-  for (const auto &x : arr) {
-    if ((rc = nvk_fetch_offsets(ctx, x.name, x.off, n_reads, off))) return rc;
-    if (off[n_reads] > 0 && !x.data) {
-      nvk_set_error("%s: %s is NULL", what, x.name);
-      return NVK_ERR_INVALID;
-    }
-  }
   if (n_sites > 0 && (!site_pos || !site_gamma)) {
     nvk_set_error("%s: NULL site_pos or site_gamma", what);
     return NVK_ERR_INVALID;
   }
-  if (total_ref == 0) {
+  if (nothing) {
     if (fill && n_rows != 0) {
       nvk_set_error("%s: n_rows %lld with no bases", what, (long long)n_rows);
       return NVK_ERR_INVALID;
@@ -290,11 +252,12 @@ extern "C" int nvk_mod_kmer_rows_dev(nvk_ctx *ctx, int64_t n_reads, int64_t tota
   NVK_HIP(hipMemsetAsync(info, 0, 2 * sizeof(unsigned long long), ctx->stream));
   {
     TimerScope ts(ctx, NVK_K_KMER);
+    const ReadArrays arrays = {ref_off, status, nullptr, nullptr, signal, sig_off, ctx_before, cb_off, ctx_after,
+                               ca_off};
     auto kernel = fill ? mod_rows_kernel<true> : mod_rows_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(grid_of(n_reads, NT / 64)), dim3(NT), 0, ctx->stream, n_reads, signal, sig_off,
-                       events, ref_off, reference, ctx_before, cb_off, ctx_after, ca_off, status, k, central, alphabet,
-                       trim, site_off, site_pos, site_gamma, mod_code, level, n_rows, row_off, out_count, out_key,
-                       out_val, info);
+    hipLaunchKernelGGL(kernel, dim3(grid_of(n_reads, NT / 64)), dim3(NT), 0, ctx->stream, n_reads, arrays, events,
+                       reference, k, central, alphabet, trim, site_off, site_pos, site_gamma, mod_code, level, n_rows,
+                       row_off, out_count, out_key, out_val, info);
   }
   NVK_HIP(hipGetLastError());
   unsigned long long h_info[2] = {0, 0};
@@ -341,12 +304,8 @@ extern "C" int nvk_mod_kmer_reduce_dev(nvk_ctx *ctx, int64_t n_rows, int64_t n_k
                   (long long)n_rows);
     return NVK_ERR_INVALID;
   }
-  {
-    TimerScope ts(ctx, NVK_K_KMER);
+  return nvk_timed(ctx, NVK_K_KMER, [&] {
     hipLaunchKernelGGL(mod_reduce_kernel, dim3(grid_of(n_keys, NT / 64)), dim3(NT), 0, ctx->stream, n_keys, val,
                        run_off, out_sum, out_rows);
-  }
-  NVK_HIP(hipGetLastError());
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return NVK_OK;
+  });
 }

@@ -18,6 +18,7 @@
 
 #include "nvk_internal.h"
 #include "npsum.h"
+#include "read_rows.h"
 
 namespace {
 
@@ -224,10 +225,8 @@ __global__ void event_means_kernel(int64_t n_reads, int64_t total_ref, const dou
   double m = nan("");
   if (!status || status[rd] == 0) {
     const int64_t N = sig_off[rd + 1] - sig_off[rd];
-    int64_t s = events[2 * g], e = events[2 * g + 1];
-    // numpy slice semantics for in-range non-negative indices; an empty event has mean NaN
-    s = s < 0 ? 0 : (s > N ? N : s);
-    e = e < 0 ? 0 : (e > N ? N : e);
+    int64_t s, e;
+    event_span(events, g, N, s, e);  // an empty event has mean NaN
     if (e > s) m = np_sum(signal + sig_off[rd] + s, e - s) / (double)(e - s);
   }
   out[g] = m;

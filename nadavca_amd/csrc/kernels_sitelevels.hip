@@ -12,13 +12,10 @@
 // are a lane's loop over its rows in ascending order followed by a butterfly over the wave.  Two runs give the same
 // bits, and the numpy restatement of the tests gives them too.
 //
-// Work split of the row pass: ONE WAVE PER READ, its lanes over the read's bases 64 at a time, as kmer_event_kernel:
-// offsets, status, strand and start are wave-uniform, and at every step of the sample loop the wave's loads fall in one
-// run of about 64 events' samples.  A lane reads its event twice, once for the sum and once for the squared
-// deviations; the second pass hits the lines the first one fetched, so the pass moves the signal's 8 B per sample from
-// memory once, plus 8 B of events and 8 B of expected level in and 40 B out per base.  An event of more than 128
-// samples takes numpy's pairwise walk; site_long_event_kernel serves it after the main pass, as long_event_kernel
-// does for the k-mer statistics, so that the main kernel's registers hold no walk state.
+// Work split of the row pass: one wave per read, its lanes over the read's bases, and a second pass for the rare
+// event of more than 128 samples (read_rows.h).  A lane reads its event twice, once for the sum and once for the
+// squared deviations; the second pass hits the lines the first one fetched, so the pass moves the signal's 8 B per
+// sample from memory once, plus 8 B of events and 8 B of expected level in and 40 B out per base.
 //
 // Work split of the moments: ONE WAVE PER KEY (grid-stride).  The key's rows are contiguous after the sort; their
 // range comes from two wave-uniform binary searches, lane l takes rows l, l + 64, ..., and the n_val columns are
@@ -34,6 +31,7 @@
 
 #include "nvk_internal.h"
 #include "npsum.h"
+#include "read_rows.h"
 #include "wave.h"
 
 namespace {
@@ -54,72 +52,55 @@ __device__ __forceinline__ void event_level_stdv(const double *xs, int64_t n, do
   stdv = sqrt(ss / (double)n);
 }
 
-// one wave per read (grid-stride), its lanes over the read's bases.  An event of more than 128 samples gets its key
-// and dwell here and level, stdv and resid from site_long_event_kernel.
-__global__ __launch_bounds__(NT) void site_rows_kernel(int64_t n_reads, const double *signal, const int64_t *sig_off,
-                                                       const int32_t *events, const int64_t *ref_off,
-                                                       const double *expected, const int64_t *chunk_start,
-                                                       const int32_t *reverse, const int32_t *status, int trim,
-                                                       int64_t ref_len, int64_t *out_key, double *out_val) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t waves = (int64_t)gridDim.x * (NT / 64);
-  for (int64_t rd = (int64_t)blockIdx.x * (NT / 64) + wave; rd < n_reads; rd += waves) {
-    const int64_t r0 = ref_off[rd];
-    const int64_t R = ref_off[rd + 1] - r0;
-    if (R <= 0) continue;
-    const bool live = !status || status[rd] == NVK_READ_OK;
-    const double *x = signal + sig_off[rd];
-    const int64_t N = sig_off[rd + 1] - sig_off[rd];
-    const bool rev = reverse[rd] != 0;
-    const int64_t start = chunk_start[rd];
-    for (int64_t g = lane; g < R; g += 64) {
+// the row pass of read_rows.h.  An event of more than 128 samples gets its key and dwell here and level, stdv and
+// resid from the second pass.
+__global__ __launch_bounds__(NT) void site_rows_kernel(int64_t n_reads, ReadArrays arrays, const int32_t *events,
+                                                       const double *expected, int trim, int64_t ref_len,
+                                                       int64_t *out_key, double *out_val) {
+  for_each_read<int64_t, RV_SIGNAL | RV_STRAND>(arrays, n_reads, [&](const ReadView<int64_t> &v) {
+    for_each_base(v, [&](int64_t g) {
       int64_t key = -1;
       double level = 0.0, stdv = 0.0, dwell = 0.0, resid = 0.0;
-      const int64_t pos = start + (rev ? R - 1 - g : g);
-      if (live && g >= trim && g < R - trim && pos >= 0 && pos < ref_len) {
-        int64_t s = events[2 * (r0 + g)], e = events[2 * (r0 + g) + 1];
-        s = s < 0 ? 0 : (s > N ? N : s);  // numpy slice clamping, as event_means_kernel
-        e = e < 0 ? 0 : (e > N ? N : e);
+      const int64_t pos = v.start + (v.rev ? v.R - 1 - g : g);
+      if (v.live && counted_base(g, v.R, trim) && pos >= 0 && pos < ref_len) {
+        int64_t s, e;
+        event_span(events, v.r0 + g, v.N, s, e);
         if (e > s) {
-          key = 2 * pos + (rev ? 1 : 0);
+          key = 2 * pos + (v.rev ? 1 : 0);
           dwell = (double)(e - s);
-          if (e - s <= 128) {  // else: site_long_event_kernel
-            event_level_stdv<false>(x + s, e - s, level, stdv);
-            resid = level - expected[r0 + g];
+          if (e - s <= 128) {  // else: the second pass
+            event_level_stdv<false>(v.x + s, e - s, level, stdv);
+            resid = level - expected[v.r0 + g];
           }
         }
       }
-      out_key[r0 + g] = key;
-      double *dst = out_val + (size_t)(r0 + g) * NCOL;
+      out_key[v.r0 + g] = key;
+      double *dst = out_val + (size_t)(v.r0 + g) * NCOL;
       dst[0] = level;
       dst[1] = stdv;
       dst[2] = dwell;
       dst[3] = resid;
-    }
-  }
+    });
+  });
 }
 
-// level, stdv and resid of the counted events of more than 128 samples: one thread per event, the read found by a
-// binary search
-__global__ __launch_bounds__(NT) void site_long_event_kernel(int64_t n_reads, int64_t total_ref, const double *signal,
-                                                             const int64_t *sig_off, const int32_t *events,
-                                                             const int64_t *ref_off, const double *expected,
-                                                             const int64_t *key, double *out_val) {
-  for (int64_t g = (int64_t)blockIdx.x * NT + threadIdx.x; g < total_ref; g += (int64_t)gridDim.x * NT) {
+// the second pass (long_event_kernel): level, stdv and resid of a counted event of more than 128 samples
+struct LongSiteLevel {
+  const double *expected;
+  double *out_val;
+  __device__ int64_t length(int64_t g) const {
+    const double dwell = out_val[(size_t)g * NCOL + 2];
+    return dwell > 128.0 ? (int64_t)dwell : 0;
+  }
+  __device__ void operator()(int64_t g, const double *xs, int64_t n) const {
     double *dst = out_val + (size_t)g * NCOL;
-    if (key[g] < 0 || !(dst[2] > 128.0)) continue;
-    const int64_t rd = owner_of(ref_off, n_reads, g);
-    const int64_t N = sig_off[rd + 1] - sig_off[rd];
-    int64_t s = events[2 * g];
-    s = s < 0 ? 0 : (s > N ? N : s);
     double level, stdv;
-    event_level_stdv<true>(signal + sig_off[rd] + s, (int64_t)dst[2], level, stdv);
+    event_level_stdv<true>(xs, n, level, stdv);
     dst[0] = level;
     dst[1] = stdv;
     dst[3] = level - expected[g];
   }
-}
+};
 
 // one wave per key (grid-stride): the count, and per column the mean and the sum of squared deviations of its rows
 template <int V>
@@ -173,52 +154,25 @@ extern "C" int nvk_site_level_rows_dev(nvk_ctx *ctx, int64_t n_reads, int64_t to
                                        const int32_t *status, int trim, int64_t ref_len, int64_t *out_key,
                                        double *out_val) {
   const char *what = "nvk_site_level_rows_dev";
-  if (!ctx || n_reads < 0 || n_reads > 0x7fffffff || total_ref < 0) {
-    nvk_set_error("%s: invalid argument", what);
-    return NVK_ERR_INVALID;
-  }
   if (trim < 0 || ref_len < 0 || ref_len > ((int64_t)1 << 61)) {
     nvk_set_error("%s: trim %d, ref_len %lld outside the served range (trim >= 0, 0 <= ref_len <= 2^61)", what, trim,
                   (long long)ref_len);
     return NVK_ERR_INVALID;
   }
-  if (n_reads == 0) {
-    if (total_ref != 0) {
-      nvk_set_error("%s: total_ref %lld with no reads", what, (long long)total_ref);
-      return NVK_ERR_INVALID;
-    }
-    return NVK_OK;
-  }
-  if (!sig_off || !ref_off) {
-    nvk_set_error("%s: offsets are NULL", what);
-    return NVK_ERR_INVALID;
-  }
-  NVK_HIP(hipSetDevice(ctx->device));
-  std::vector<int64_t> off;
-  int rc;
-  if ((rc = nvk_fetch_offsets(ctx, "reference", ref_off, n_reads, off, "total_ref", total_ref))) return rc;
-  if ((rc = nvk_fetch_offsets(ctx, "signal", sig_off, n_reads, off))) return rc;
-  // (a data array may be NULL only when its offsets end at 0)
-  if (off[n_reads] > 0 && !signal) {
-    nvk_set_error("%s: signal is NULL", what);
-    return NVK_ERR_INVALID;
-  }
-  if (total_ref == 0) return NVK_OK;
+  bool nothing;
+  int rc = check_read_rows(what, ctx, n_reads, total_ref, ref_off, {{"signal", sig_off, signal}}, &nothing);
+  if (rc || nothing) return rc;
   if (!events || !expected || !chunk_start || !reverse || !out_key || !out_val) {
     nvk_set_error("%s: NULL events, expected, chunk_start, reverse or output", what);
     return NVK_ERR_INVALID;
   }
-  {
-    TimerScope ts(ctx, NVK_K_SITE);
-    hipLaunchKernelGGL(site_rows_kernel, dim3(grid_of(n_reads, NT / 64)), dim3(NT), 0, ctx->stream, n_reads, signal,
-                       sig_off, events, ref_off, expected, chunk_start, reverse, status, trim, ref_len, out_key,
-                       out_val);
-    hipLaunchKernelGGL(site_long_event_kernel, dim3(grid_of(total_ref, NT)), dim3(NT), 0, ctx->stream, n_reads,
-                       total_ref, signal, sig_off, events, ref_off, expected, (const int64_t *)out_key, out_val);
-  }
-  NVK_HIP(hipGetLastError());
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return NVK_OK;
+  return nvk_timed(ctx, NVK_K_SITE, [&] {
+    const ReadArrays arrays = {ref_off, status, chunk_start, reverse, signal, sig_off};
+    hipLaunchKernelGGL(site_rows_kernel, dim3(grid_of(n_reads, NT / 64)), dim3(NT), 0, ctx->stream, n_reads, arrays,
+                       events, expected, trim, ref_len, out_key, out_val);
+    hipLaunchKernelGGL(long_event_kernel, dim3(grid_of(total_ref, NT)), dim3(NT), 0, ctx->stream, n_reads, total_ref,
+                       signal, sig_off, events, ref_off, (const int64_t *)out_key, LongSiteLevel{expected, out_val});
+  });
 }
 
 extern "C" int nvk_site_moments_dev(nvk_ctx *ctx, int64_t n_rows, int64_t n_keys, int n_val, const int64_t *key,
@@ -234,27 +188,10 @@ extern "C" int nvk_site_moments_dev(nvk_ctx *ctx, int64_t n_rows, int64_t n_keys
     return NVK_ERR_INVALID;
   }
   NVK_HIP(hipSetDevice(ctx->device));
-  {
-    TimerScope ts(ctx, NVK_K_SITE);
-    const dim3 grid(grid_of(n_keys, NT / 64)), block(NT);
-#define NVK_SITE_CASE(V)                                                                                            \
-  case V:                                                                                                           \
-    hipLaunchKernelGGL(site_moments_kernel<V>, grid, block, 0, ctx->stream, n_rows, n_keys, key, val, out_count,    \
-                       out_mean, out_m2);                                                                           \
-    break;
-    switch (n_val) {
-      NVK_SITE_CASE(1)
-      NVK_SITE_CASE(2)
-      NVK_SITE_CASE(3)
-      NVK_SITE_CASE(4)
-      NVK_SITE_CASE(5)
-      NVK_SITE_CASE(6)
-      NVK_SITE_CASE(7)
-      NVK_SITE_CASE(8)
-    }
-#undef NVK_SITE_CASE
-  }
-  NVK_HIP(hipGetLastError());
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return NVK_OK;
+  return nvk_timed(ctx, NVK_K_SITE, [&] {
+    dispatch_int<1, 8>(n_val, [&](auto v) {
+      hipLaunchKernelGGL(site_moments_kernel<decltype(v)::value>, dim3(grid_of(n_keys, NT / 64)), dim3(NT), 0,
+                         ctx->stream, n_rows, n_keys, key, val, out_count, out_mean, out_m2);
+    });
+  });
 }

@@ -65,3 +65,15 @@ __device__ __forceinline__ int64_t kmer_id_checked(const DeviceModel &dm, const 
   }
   return id;
 }
+
+// alphabet^k, the entries of a k-mer table, or -1 when k / alphabet are outside the served range
+constexpr int MAX_K = 16;  // longest k-mer whose key fits the check below (alphabet^k <= 2^31)
+inline int64_t kmer_table_size(int k, int alphabet) {
+  if (k < 1 || k > MAX_K || alphabet < 1 || alphabet > 64) return -1;
+  int64_t n = 1;
+  for (int i = 0; i < k; i++) {
+    n *= alphabet;
+    if (n > ((int64_t)1 << 31)) return -1;
+  }
+  return n;
+}

@@ -7,8 +7,8 @@
 // of the k-mer statistics are never stored.  The walk's stack is in registers: every access to it is an unrolled
 // select over its 8 frames, so it needs no scratch memory (a walk with indexed stack arrays cost event_means_kernel
 // 112 B of scratch per lane and linfit_kernel 166 VGPRs).
-// Resource use (gfx950, -Rpass-analysis=kernel-resource-usage): kmer_event_kernel 72 / 74 VGPRs and 72 / 74 SGPRs
-// (pass 1 / pass 2), long_event_kernel 82 / 84 VGPRs and 99 / 101 SGPRs, kmer_reduce_kernel 86 VGPRs and 99 SGPRs;
+// Resource use (gfx950, -Rpass-analysis=kernel-resource-usage): kmer_event_kernel 72 / 74 VGPRs and 78 / 80 SGPRs
+// (pass 1 / pass 2), its long_event_kernel 82 / 84 VGPRs and 99 / 103 SGPRs, kmer_reduce_kernel 86 VGPRs and 99 SGPRs;
 // no LDS, no scratch, no spills.
 #pragma once
 #include <hip/hip_runtime.h>

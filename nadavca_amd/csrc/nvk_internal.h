@@ -5,6 +5,7 @@
 
 #include <functional>
 #include <initializer_list>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/nadavca_hip.h"
@@ -182,6 +183,31 @@ struct TimerScope {
     }                                                                                  \
   } while (0)
 
+// the close of an entry: `launch()` under a TimerScope of kernel class kid, then the launch error, then the stream
+template <class Launch>
+inline int nvk_timed(nvk_ctx *ctx, int kid, Launch &&launch) {
+  {
+    TimerScope ts(ctx, kid);
+    launch();
+  }
+  NVK_HIP(hipGetLastError());
+  NVK_HIP(hipStreamSynchronize(ctx->stream));
+  return NVK_OK;
+}
+
+// f(std::integral_constant<int, V>{}) for the V in LO .. HI that equals v: a run-time count as a template parameter;
+// false, and no call, when v is outside
+template <int LO, int HI, class F>
+inline bool dispatch_int(int v, F &&f) {
+  if constexpr (LO > HI) {
+    return false;
+  } else {
+    if (v != LO) return dispatch_int<LO + 1, HI>(v, f);
+    f(std::integral_constant<int, LO>{});
+    return true;
+  }
+}
+
 // scoped temporary device buffer of the host-pointer entry points: max(bytes, 16) bytes, filled from host src
 // (when not null) on stream s, freed when it goes out of scope
 struct NvkTmp {
@@ -247,6 +273,12 @@ int check_common(nvk_model *model, int64_t n_reads, int bandwidth, int mel);
 int check_site_samples(const char *what, nvk_ctx *ctx, int64_t n_rows_a, const int64_t *key_a, const double *val_a,
                        int64_t n_rows_b, const int64_t *key_b, const double *val_b, int64_t n_sites,
                        const int64_t *site_key);
+// the per-read row entries (read_rows.h): ctx, n_reads in 0 .. 2^31-1, total_ref >= 0 and 0 with no reads; ref_off on
+// the device, fetched, checked and ending at total_ref; every array of `arrays` with its offsets fetched and checked,
+// its data NULL only when they end at 0.  *nothing_to_do: the checks passed and there is no base to serve.
+struct ReadRowsArray { const char *name; const int64_t *off; const void *data; };
+int check_read_rows(const char *what, nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, const int64_t *ref_off,
+                    std::initializer_list<ReadRowsArray> arrays, bool *nothing_to_do);
 
 // ----- launchers (kernels_*.hip) ------------------------------------------------------------
 struct BatchArgs {

@@ -9,11 +9,12 @@ import numpy as np
 import pytest
 
 import allele_ref
+import read_rows_case
 
 pytestmark = pytest.mark.gpu
 
 REF_LEN = 120
-CACHED_ROWS = 128     # positions of up to this many rows keep exp(-|d|) in registers (kernels_allele.hip: 64 * CACHE)
+CACHED_ROWS = 128     # positions of up to this many rows keep exp(-|d|) in registers (mix_mle.h: 64 * MIX_CACHE)
 
 
 def build_case(alpha, seed):
@@ -137,6 +138,60 @@ def test_kernels_against_the_restatement(ctx, alpha, event_length):
     # a second call returns the same bits
     again = [t.cpu().numpy() for t in device.allele_fractions_dev(ctx, dbatch, ll, start, reverse, status,
                                                                   event_length, codes)]
+    for x, y in zip(got, again):
+        assert np.array_equal(x, y, equal_nan=True)
+
+
+@pytest.mark.parametrize('with_status', [True, False])
+def test_rows_on_the_read_view_shapes(ctx, with_status):
+    """The batch of read_rows_case.py: reads without bases (the last read among them), a dead read between live ones,
+    reads off either end of the reference, a read count that leaves a block part empty."""
+    from nadavca_amd import device
+    case = read_rows_case.build()
+    dbatch, ll, start, reverse, status, _ = on_device(case, ctx)
+    st = case['status'] if with_status else None
+    want_key, want_val = allele_ref.rows(case['ll'], case['reference'], case['ref_off'], case['start'],
+                                         case['reverse'], st, 2.5, read_rows_case.REF_LEN)
+    key, val = device.allele_rows_dev(ctx, dbatch, ll, start, reverse, status if with_status else None, 2.5,
+                                      read_rows_case.REF_LEN)
+    key = key.cpu().numpy()
+    assert np.array_equal(key, want_key) and np.array_equal(val.cpu().numpy(), want_val)
+    off = case['ref_off']
+    assert (key[off[1]:off[2]] >= 0).any() == (not with_status)          # the dead read between two live ones
+    assert (key[off[0]:off[1]] >= 0).all() and (key[off[2]:off[3]] >= 0).all()
+    assert (key[off[6]:off[7]] < 0).sum() == 3 and (key[off[9]:off[10]] < 0).sum() == 50    # off either end
+
+
+@pytest.mark.parametrize('alpha', [2, 4, 8])
+def test_solve_at_the_edges_of_the_cached_rows(ctx, alpha):
+    """Positions of 0, 1, 64, 128, 129 and 200 rows (64: one row per lane; 128: the last size whose rows stay in
+    registers).  At every position the first alternative base has its maximum inside (0, 1), so it is bisected, while
+    the others, all negative, end after the first sweep."""
+    import torch
+    from nadavca_amd import device
+    rng = np.random.default_rng(60 + alpha)
+    sizes = [0, 1, 64, CACHED_ROWS, CACHED_ROWS + 1, 200]
+    key = np.repeat(np.arange(len(sizes)), sizes).astype(np.int64)
+    ref_codes = rng.integers(0, alpha, len(sizes)).astype(np.int32)
+    val = -np.abs(rng.normal(0.0, 6.0, (key.size, alpha))) - 1e-3
+    first_alt = np.where(ref_codes == 0, 1, 0)
+    sign = np.where(rng.random(key.size) < 0.4, 1.0, -1.0)
+    val[np.arange(key.size), first_alt[key]] = sign * rng.normal(6.0, 2.0, key.size)
+    val[0, first_alt[1]] = 4.0                                # the single row, of position 1: f^ = 1
+    dev = torch.device('cuda', ctx.device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    got = [t.cpu().numpy() for t in device.allele_solve_dev(ctx, up(key), up(val), up(ref_codes))]
+    fraction, lrt, half, full, cov = got
+    assert cov.tolist() == sizes
+    P, b, D, valid, coverage = allele_ref.sites(key, val, ref_codes)
+    allele_ref.check_against(allele_ref.solve(D, valid), fraction[P, b], lrt[P, b], half[P, b], full[P, b], D, valid,
+                             'alphabet %d, edge sizes' % alpha)
+    for p in range(2, len(sizes)):
+        assert 0.0 < fraction[p, first_alt[p]] < 1.0, p
+        rest = [a for a in range(alpha) if a != ref_codes[p] and a != first_alt[p]]
+        assert (fraction[p, rest] == 0).all() and (lrt[p, rest] == 0).all(), p
+    assert fraction[1, first_alt[1]] == 1.0 and (fraction[0] == 0).all()
+    again = [t.cpu().numpy() for t in device.allele_solve_dev(ctx, up(key), up(val), up(ref_codes))]
     for x, y in zip(got, again):
         assert np.array_equal(x, y, equal_nan=True)
 

@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import read_rows_case
 from kmer_stats_ref import kmer_stats_of
 from test_kmer_train_cpu import RECOVERY_MIN_EVENTS, RECOVERY_READS, RECOVERY_SEED, recovery_start
 
@@ -136,6 +137,26 @@ def test_long_events_and_crowded_kmers(tables):
     got = _check(dbatch, model.context, events, status, 1, 0, 0)
     assert got['e'].max() > 8192
     _check(dbatch, model.context, events, status, 6, 2, 1)
+
+
+def test_statistics_on_the_read_view_shapes(tables):
+    """The batch of read_rows_case.py: reads without bases or samples, a dead read between live ones, trim beyond half a
+    read, every clamp of an event, events around 128 samples, a read count that leaves a block part empty."""
+    import torch
+    from nadavca_amd import synthetic
+    from nadavca_amd.device import DeviceBatch
+    case = read_rows_case.build()
+    model = tables['models'][6]
+    dbatch = DeviceBatch(synthetic.Batch(case['cases']), 'cuda:%d' % model.context.device)
+    events = torch.from_numpy(case['events']).to(dbatch.device)
+    status = torch.from_numpy(case['status']).to(dbatch.device)
+    for k, central in ((6, 2), (1, 0), (3, 2)):
+        for trim in (0, read_rows_case.TRIM):
+            got = _check(dbatch, model.context, events, status, k, central, trim)
+            assert got['e'].sum() > 100
+    every = _check(dbatch, model.context, events, None, 1, 0, 0)           # status NULL: the dead reads count too
+    live = _check(dbatch, model.context, events, status, 1, 0, 0)
+    assert every['e'].sum() > live['e'].sum() and every['N'].sum() > live['N'].sum() > 4 * 300
 
 
 def _recovery_batch(tables):

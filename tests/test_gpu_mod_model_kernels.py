@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import read_rows_case
 from mod_model_ref import mod_reduce, mod_rows_of, mod_stats
 
 pytestmark = pytest.mark.gpu
@@ -123,6 +124,39 @@ def test_rows_equal_the_restatement_on_the_constructed_batch(ctx, constructed, k
                                          c['site_pos'], c['site_gamma'], mod_code, level)
     assert np.array_equal(key.cpu().numpy(), exp_key) and np.array_equal(_bits(val.cpu().numpy()), _bits(exp_val))
     torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize('k,central', [(6, 2), (3, 1)])
+def test_rows_on_the_read_view_shapes(ctx, k, central):
+    """The batch of read_rows_case.py: reads without bases or samples, a dead read between live ones (its rows are
+    written with key -1), trim beyond half a read, every clamp of an event, events around 128 samples, a read count
+    that leaves a block part empty."""
+    import torch
+    from nadavca_amd import synthetic
+    from nadavca_amd.device import DeviceBatch, mod_kmer_rows_dev
+    case = read_rows_case.build()
+    batch = synthetic.Batch(case['cases'])
+    dbatch = DeviceBatch(batch, 'cuda:%d' % ctx.device)
+    up = lambda a: torch.from_numpy(a).to(dbatch.device)
+    level = np.random.default_rng(7 * k).normal(0.0, 1.0, 5 ** k)
+    for trim in (0, read_rows_case.TRIM):
+        for status in (case['status'], None):
+            key, val, row_off, skipped = mod_kmer_rows_dev(dbatch, ctx, up(case['events']),
+                                                           None if status is None else up(status), k, central, 5, trim,
+                                                           up(case['site_off']), up(case['site_pos']),
+                                                           up(case['site_gamma']), 4, up(level))
+            exp_count, exp_key, exp_val, exp_skipped = mod_rows_of(batch, case['events'], status, k, central, 5, trim,
+                                                                   case['site_off'], case['site_pos'],
+                                                                   case['site_gamma'], 4, level)
+            row_off = row_off.cpu().numpy()
+            assert np.array_equal(np.diff(row_off), exp_count) and skipped == exp_skipped
+            assert np.array_equal(key.cpu().numpy(), exp_key)
+            assert np.array_equal(_bits(val.cpu().numpy()), _bits(exp_val))
+            # the dead read between two live ones has rows, and they count only without a status
+            off = case['ref_off']
+            dead = key.cpu().numpy()[row_off[off[1]]:row_off[off[2]]]
+            assert dead.size > 0 and (dead >= 0).any() == (status is None)
+            assert (exp_key >= 0).sum() > 20
 
 
 def test_reduction_on_hand_made_rows(ctx):

@@ -1,6 +1,6 @@
 """nvk_mod_site_solve_dev on the GPU against its numpy restatement (tests/mod_sites_ref.py), with the tolerances of
 ``allele_ref.check_against`` and the counts exact.  The sites have 0, 1, 2, 63, 64, 65, 128, 129, 130 and 300 rows: the
-partial-sum boundary at 64 and the boundary of the rows the kernel keeps in registers, 64 * CACHE = 128, from both
+partial-sum boundary at 64 and the boundary of the rows the kernel keeps in registers, 64 * MIX_CACHE = 128, from both
 sides."""
 import ctypes as C
 
@@ -13,7 +13,7 @@ import mod_sites_ref
 pytestmark = pytest.mark.gpu
 
 CLIP = 30.0
-CACHED_ROWS = 128          # 64 * CACHE of csrc/kernels_modsites.hip
+CACHED_ROWS = 128          # 64 * MIX_CACHE of csrc/mix_mle.h
 SIZES = [0, 1, 2, 63, 64, 65, 128, 129, 130, 300, 40, 40, 12, 70, 200]
 ALL_POSITIVE, ALL_NEGATIVE, SPECIAL, MIXED_LONG, SPECIAL_LONG = 10, 11, 12, 13, 14
 
@@ -89,6 +89,23 @@ def test_the_four_sets_against_the_restatement(ctx):
     # the planted shares show: group 1 above group 2 at every large site
     big = [9, 13, 14]
     assert (fraction[big, 1] > 0.6).all() and (fraction[big, 2] < 0.4).all()
+
+
+def test_one_set_bisected_beside_one_that_is_not(ctx):
+    """Sites of 0, 1, 64, 128, 129 and 200 rows; group 1 mixes both signs, so its set has its maximum inside (0, 1) and
+    is bisected; group 0 is all positive, so its set ends after the first sweep with f^ = 1; a third set is empty."""
+    rng = np.random.default_rng(49)
+    sizes = [0, 1, 64, CACHED_ROWS, CACHED_ROWS + 1, 200]
+    lo = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+    hi = np.cumsum(sizes).astype(np.int64)
+    n = int(hi[-1])
+    group = (np.arange(n) % 2).astype(np.int32)
+    val = np.where(rng.random(n) < 0.4, 1.0, -1.0) * rng.normal(6.0, 2.0, n)
+    val[group == 0] = np.abs(val[group == 0]) + 0.5
+    count, fraction, ll, _ = solve_and_check(ctx, lo, hi, val, group, (0b010, 0b001, 0b100), 'edge sizes')
+    assert np.array_equal(count.sum(1), sizes) and (count[:, 2] == 0).all()
+    assert ((fraction[2:, 0] > 0) & (fraction[2:, 0] < 1)).all() and (fraction[1:, 1] == 1.0).all()
+    assert (fraction[:, 2] == 0).all() and (fraction[0] == 0).all()
 
 
 @pytest.mark.parametrize('n_sets', [1, 2, 3, 5, 6, 7, 8])

@@ -7,6 +7,7 @@ import types
 import numpy as np
 import pytest
 
+import read_rows_case
 import site_levels_ref
 
 pytestmark = pytest.mark.gpu
@@ -119,6 +120,31 @@ def test_rows_against_the_restatement(ctx, case, trim, with_status):
     key2, val2 = device.site_level_rows_dev(ctx, dbatch, events, expected, start, reverse,
                                             status if with_status else None, trim, REF_LEN)
     assert np.array_equal(key2.cpu().numpy(), key) and same_bits(val2.cpu().numpy(), val)
+
+
+@pytest.mark.parametrize('trim,with_status', [(0, True), (read_rows_case.TRIM, True), (0, False)])
+def test_rows_on_the_read_view_shapes(ctx, trim, with_status):
+    """The batch of read_rows_case.py: reads without bases or samples, a dead read between live ones, trim beyond half a
+    read, every clamp of an event, events around 128 samples, a read count that leaves a block part empty."""
+    from nadavca_amd import device
+    case = read_rows_case.build()
+    dbatch, events, expected, start, reverse, status = on_device(case, ctx)
+    want_key, want_val = site_levels_ref.rows(case['signal'], case['sig_off'], case['events'], case['ref_off'],
+                                              case['expected'], case['start'], case['reverse'],
+                                              case['status'] if with_status else None, trim, read_rows_case.REF_LEN)
+    key, val = device.site_level_rows_dev(ctx, dbatch, events, expected, start, reverse,
+                                          status if with_status else None, trim, read_rows_case.REF_LEN)
+    key, val = key.cpu().numpy(), val.cpu().numpy()
+    assert np.array_equal(key, want_key)
+    assert same_bits(val, want_val)
+    counted = key >= 0
+    for length in read_rows_case.EVENT_LENGTHS:
+        assert (val[counted, 2] == length).any(), length
+    off = case['ref_off']
+    assert not counted[off[4]:off[5]].any()                              # the read without samples
+    assert counted[off[1]:off[2]].any() == (not with_status)             # the dead read between two live ones
+    assert counted[off[0]:off[1]].any() and counted[off[2]:off[3]].any()
+    assert counted[off[5]:off[6]].any() == (trim == 0)
 
 
 def test_site_levels_dev_is_rows_sort_moments(ctx, case):
