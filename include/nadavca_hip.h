@@ -868,6 +868,42 @@ int nvk_phase_votes_dev(nvk_ctx *ctx, int64_t n_sites, int alphabet, const int64
                         const int64_t *row_read, const double *val, const int64_t *read_block, const double *read_llr,
                         double clip, double *out_vote, int64_t *out_agree, int64_t *out_against);
 
+/* Phasing across weak sites (phase_reads_batch with span > 1; csrc/kernels_phasespan.hip).  THE CONTRACT, in the terms
+ * of the phasing contract above.
+ *   span links nvk_phase_span_links_dev: for site s and w = 1 .. span with s - w >= site_first_s, out_link[s * span +
+ *              w - 1] and out_shared[s * span + w - 1] are exactly the link and shared of the contract above taken between
+ *              the sites s - w and s (e1 at s - w, e2 at s).  site_first i64[n_sites]: the index of the first site of
+ *              s's contig (or of whatever stretch of sites the caller allows links inside); it takes the place of
+ *              chain.  The sum runs over the rows of site s in key order, row j into partial sum j mod 64, a row that is
+ *              not shared adds +0.0, and the partials are added by wave_sum's butterfly.  Every other entry is 0, and
+ *              every entry of out_link f64[n_sites * span] and out_shared i64[n_sites * span] is written.  Column w = 1
+ *              therefore has the bits of nvk_phase_links_dev wherever chain_s != 0.  1 <= span <= 8; the other argument
+ *              rules are those of nvk_phase_links_dev.
+ *   forest     (integer work, done by the caller on the device: device.phase_forest) candidate w of site s qualifies
+ *              when s - w >= site_first_s, shared >= min_shared and |link| >= min_link.  parent_s = s - w*, w* the
+ *              qualifying candidate with the largest |link|, the smallest w on ties; -1 without one.  block_s = the
+ *              root of s, sigma_s = the product of (link > 0 ? +1 : -1) along the path to it.  Greedy: every site takes
+ *              its strongest earlier neighbour; this is no maximum spanning tree.  A block is no interval of sites any
+ *              more: a site without a qualifying link stays a singleton inside the block that its neighbours form.
+ *   tag blocks nvk_phase_tag_blocks_dev, the arguments of nvk_phase_tag_dev, ANY block array: per read, for every
+ *              block b that owns at least one of the read's sites with evidence, H_b = the left to right double sum of
+ *              sigma_s * e_is over those sites in ascending s, starting from 0.0.  The read's block is the one with
+ *              the largest |H_b|, the smallest block index on ties; read_llr = that H, read_sites = the number of its
+ *              sites, -1 / 0 / 0 for a read without a site.  Where every block is an interval of sites labelled by its
+ *              first site this is nvk_phase_tag_dev's answer bit for bit.
+ *   vote, refinement: as above (nvk_phase_votes_dev serves any block array; "its first site" is the root).
+ * No atomics: the same bits on every run.  The launches are timed under NVK_K_ALLELE.  n_sites == 0 launches nothing
+ * (and writes nothing).  NVK_ERR_INVALID for bad arguments or offsets or a NULL array.  Device pointers. */
+int nvk_phase_span_links_dev(nvk_ctx *ctx, int64_t n_sites, int span, int alphabet, const int64_t *site_lo,
+                             const int64_t *site_hi, const int32_t *site_alt, const int64_t *site_first,
+                             const int64_t *row_read, const double *val, double clip, double *out_link,
+                             int64_t *out_shared);
+int nvk_phase_tag_blocks_dev(nvk_ctx *ctx, int64_t n_reads, int64_t n_sites, int alphabet, const int64_t *ref_off,
+                             const int64_t *chunk_start, const int32_t *reverse, const int64_t *key, const double *val,
+                             const int64_t *site_pos, const int32_t *site_alt, const int64_t *site_block,
+                             const int32_t *site_sigma, double clip, int64_t *out_block, double *out_llr,
+                             int64_t *out_sites);
+
 /* Per-site modification frequencies over sets of rows (nadavca_amd/phase_mods.py: phase_mods_batch,
  * mod_site_frequencies).  THE CONTRACT.  The library is built with -ffp-contract=off: every expression below is a
  * rounded operation in the order written.

@@ -121,6 +121,8 @@ SIGNATURES = {
     'nvk_phase_links_dev': (_int, [_vp, _i64, _int] + [_vp] * 6 + [_dbl, _vp, _vp]),
     'nvk_phase_tag_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 9 + [_dbl, _vp, _vp, _vp]),
     'nvk_phase_votes_dev': (_int, [_vp, _i64, _int] + [_vp] * 9 + [_dbl, _vp, _vp, _vp]),
+    'nvk_phase_span_links_dev': (_int, [_vp, _i64, _int, _int] + [_vp] * 6 + [_dbl, _vp, _vp]),
+    'nvk_phase_tag_blocks_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 9 + [_dbl, _vp, _vp, _vp]),
     'nvk_mod_site_solve_dev': (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _int, _vp, _dbl, _vp, _vp, _vp]),
     'nvk_site_level_rows_dev': (_int, [_vp, _i64, _i64] + [_vp] * 8 + [_int, _i64, _vp, _vp]),
     'nvk_site_moments_dev': (_int, [_vp, _i64, _i64, _int] + [_vp] * 5),

@@ -845,26 +845,123 @@ def phase_blocks(link, shared, chain, min_shared, min_link):
     return block, sigma
 
 
+def check_span(what, span):
+    """``span`` as ``phase_reads_batch`` takes it -> int in 1 .. 8, or ValueError."""
+    if isinstance(span, bool) or not isinstance(span, (int, np.integer)) or not 1 <= span <= 8:
+        raise ValueError('%s: span %r is not an integer in 1 .. 8' % (what, span))
+    return int(span)
+
+
+def phase_span_links_dev(context, site_lo, site_hi, site_alt, site_first, row_read, sorted_val, clip, span):
+    """Per site and w = 1 .. span: (link f64 (S, span), shared int64 (S, span)) device tensors
+    (nvk_phase_span_links_dev): column w - 1 holds the link between the sites s - w and s, 0 where s - w lies before
+    site_first[s].  site_first i64 (S,): the first site of every site's contig; the other arguments as for
+    ``phase_links_dev``."""
+    import torch
+    lib = _lib.load()
+    S, span = int(site_lo.numel()), check_span('phase_span_links_dev', span)
+    link = torch.zeros((S, span), dtype=torch.float64, device=site_lo.device)
+    shared = torch.zeros((S, span), dtype=torch.int64, device=site_lo.device)
+    _lib.check(lib.nvk_phase_span_links_dev(context.handle, S, span, int(sorted_val.shape[1]), _dp(site_lo),
+                                            _dp(site_hi), _dp(site_alt), _dp(site_first), _dp(row_read),
+                                            _dp(sorted_val), float(clip), _dp(link), _dp(shared)),
+               'nvk_phase_span_links_dev')
+    return link, shared
+
+
+def phase_tag_blocks_dev(context, ref_off, chunk_start, reverse, key, val, site_pos, site_alt, site_block, site_sigma,
+                         clip):
+    """``phase_tag_dev`` for ANY block array (nvk_phase_tag_blocks_dev): a read's block is the one with the largest |H|
+    over all of the read's sites in that block, the smallest block index on ties.  Arguments and results as there."""
+    import torch
+    lib = _lib.load()
+    n, S = int(ref_off.numel()) - 1, int(site_pos.numel())
+    dev = ref_off.device
+    block = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    llr = torch.zeros(n, dtype=torch.float64, device=dev)
+    count = torch.zeros(n, dtype=torch.int64, device=dev)
+    _lib.check(lib.nvk_phase_tag_blocks_dev(context.handle, n, S, int(val.shape[1]), _dp(ref_off), _dp(chunk_start),
+                                            _dp(reverse), _dp(key), _dp(val), _dp(site_pos), _dp(site_alt),
+                                            _dp(site_block), _dp(site_sigma), float(clip), _dp(block), _dp(llr),
+                                            _dp(count)), 'nvk_phase_tag_blocks_dev')
+    return block, llr, count
+
+
+def phase_forest(link, shared, site_first, min_shared, min_link):
+    """Parents, blocks and starting phase from the span links (integer work, torch on the tensors' device, CPU tensors
+    included).  link f64 (S, span), shared int64 (S, span), site_first int64 (S,).  Candidate w = 1 .. span of site s
+    qualifies when s - w >= site_first[s], shared >= min_shared and |link| >= min_link; parent[s] = s - w* for the
+    qualifying candidate with the largest |link| (the smallest w on ties), -1 without one.  A parent is an earlier
+    site, so this is a forest; roots and signs come from pointer jumping in ceil(log2 S) gathers.
+    -> (parent int64 (S,), block int64 (S,): the root, sigma int32 (S,): the product of (+1 if link > 0 else -1) along
+    the path to the root).  With span 1 block and sigma are ``phase_blocks``'."""
+    import torch
+    S, span = int(link.shape[0]), int(link.shape[1])
+    dev = link.device
+    idx = torch.arange(S, dtype=torch.int64, device=dev)
+    w = torch.arange(1, span + 1, dtype=torch.int64, device=dev)
+    ok = (idx[:, None] - w[None, :] >= site_first.to(torch.int64)[:, None]) & (shared >= int(min_shared)) \
+        & (link.abs() >= float(min_link))
+    if S == 0 or span == 0:
+        return idx - 1, idx, torch.ones(S, dtype=torch.int32, device=dev)
+    mag = torch.where(ok, link.abs(), torch.full_like(link, -1.0))
+    top = mag.max(dim=1).values
+    has = top >= 0.0
+    # the smallest w among the candidates that reach the maximum
+    w_star = torch.where(ok & (mag == top[:, None]), w[None, :].expand(S, span),
+                         torch.full((S, span), span + 1, dtype=torch.int64, device=dev)).min(dim=1).values
+    w_star = torch.where(has, w_star, torch.ones_like(w_star))
+    parent = torch.where(has, idx - w_star, torch.full_like(idx, -1))
+    chosen = link.gather(1, (w_star - 1)[:, None])[:, 0]
+    ptr = torch.where(has, parent, idx)
+    turn = (has & ~(chosen > 0)).to(torch.int64)         # the parity of the -1 links on the path from s to ptr[s]
+    for _ in range(max(S - 1, 1).bit_length()):
+        turn = turn ^ turn[ptr]
+        ptr = ptr[ptr]
+    return parent, ptr, (1 - 2 * turn).to(torch.int32)
+
+
 def phase_sites_dev(context, ref_off, chunk_start, reverse, key, val, sorted_key, sorted_val, order, site_pos, site_alt,
-                    chain, clip, min_shared, min_link, rounds):
+                    chain, clip, min_shared, min_link, rounds, *, span=1):
     """The whole phasing loop on the device (include/nadavca_hip.h: nvk_phase_links_dev has the contract): links,
     blocks and starting phase, ``rounds`` rounds of tag / vote / flip, the final tag and vote.  ``key`` / ``val``:
     the read-major rows of ``allele_sorted_rows_dev``, ``sorted_key`` / ``order`` its sort, ``sorted_val = val[order]``;
     site_pos i64 (S,) global and strictly ascending, site_alt i32 (S,), chain i32 (S,).  -> dict of device tensors:
     link, shared, block, sigma, vote, n_agree, n_against (S,), read_block, read_llr, read_sites (n,) and flips
-    int64 (rounds,)."""
+    int64 (rounds,).
+    ``span`` = 1: every site is linked to the site before it only.  ``span`` = 2 .. 8 (nvk_phase_span_links_dev has
+    the contract): every site is linked to the ``span`` sites before it, back to the last site with chain 0, and
+    joined to the strongest qualifying one (``phase_forest``); the tags come from nvk_phase_tag_blocks_dev, since a
+    block is no interval then.  The dict gains parent int64 (S,), span_link f64 and span_shared int64 (S, span); link
+    and shared stay the column of the site before."""
     import torch
+    span = check_span('phase_sites_dev', span)
     site_pos, site_alt, chain = site_pos.contiguous(), site_alt.contiguous(), chain.contiguous()
     # the read of every sorted row: the last read whose offset is <= the row's read-major index
     row_read = (torch.searchsorted(ref_off, order, right=True) - 1).contiguous()
     site_lo = torch.searchsorted(sorted_key, site_pos).contiguous()
     site_hi = torch.searchsorted(sorted_key, site_pos, right=True).contiguous()
-    link, shared = phase_links_dev(context, site_lo, site_hi, site_alt, chain, row_read, sorted_val, clip)
-    block, sigma = phase_blocks(link, shared, chain, min_shared, min_link)
+    more = {}
+    if span == 1:
+        link, shared = phase_links_dev(context, site_lo, site_hi, site_alt, chain, row_read, sorted_val, clip)
+        block, sigma = phase_blocks(link, shared, chain, min_shared, min_link)
+        tag_dev = phase_tag_dev
+    else:
+        idx = torch.arange(int(site_pos.numel()), dtype=torch.int64, device=site_pos.device)
+        # the last site at or before s whose chain is 0 (site 0 opens a chain whatever its flag)
+        site_first = torch.cummax(torch.where(chain != 0, torch.zeros_like(idx), idx), 0).values.contiguous() \
+            if idx.numel() else idx
+        span_link, span_shared = phase_span_links_dev(context, site_lo, site_hi, site_alt, site_first, row_read,
+                                                      sorted_val, clip, span)
+        parent, block, sigma = phase_forest(span_link, span_shared, site_first, min_shared, min_link)
+        block, sigma = block.contiguous(), sigma.contiguous()
+        link, shared = span_link[:, 0].contiguous(), span_shared[:, 0].contiguous()
+        more = dict(parent=parent, span_link=span_link, span_shared=span_shared)
+        tag_dev = phase_tag_blocks_dev
     flips = []
     for r in range(int(rounds) + 1):
-        read_block, read_llr, read_sites = phase_tag_dev(context, ref_off, chunk_start, reverse, key, val, site_pos,
-                                                         site_alt, block, sigma, clip)
+        read_block, read_llr, read_sites = tag_dev(context, ref_off, chunk_start, reverse, key, val, site_pos,
+                                                   site_alt, block, sigma, clip)
         vote, agree, against = phase_votes_dev(context, site_lo, site_hi, site_alt, block, sigma, row_read, sorted_val,
                                                read_block, read_llr, clip)
         if r == int(rounds):
@@ -875,7 +972,7 @@ def phase_sites_dev(context, ref_off, chunk_start, reverse, key, val, sorted_key
         sigma = (sigma * sigma[block]).contiguous()
     flips = torch.stack(flips) if flips else torch.zeros(0, dtype=torch.int64, device=link.device)
     return dict(link=link, shared=shared, block=block, sigma=sigma, vote=vote, n_agree=agree, n_against=against,
-                read_block=read_block, read_llr=read_llr, read_sites=read_sites, flips=flips)
+                read_block=read_block, read_llr=read_llr, read_sites=read_sites, flips=flips, **more)
 
 
 # ---- per-site modification frequencies over sets of rows (nadavca_amd/phase_mods.py) -------------------------------

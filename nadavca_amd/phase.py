@@ -3,8 +3,10 @@
 ``estimate_allele_fractions_batch`` computes a log-likelihood ratio d for every read over every site and keeps only
 the per-site mixture.  This workflow keeps which read carried which base: adjacent sites are linked through the reads
 that cover both, linked sites form blocks with a phase per site, every read is tagged with the block and haplotype its
-evidence supports, and the phases are refined by the leave-one-out votes of the tagged reads.  The contract is in
-include/nadavca_hip.h (nvk_phase_links_dev), the kernels in csrc/kernels_phase.hip, the loop in
+evidence supports, and the phases are refined by the leave-one-out votes of the tagged reads.  With ``span`` > 1 a site
+is linked to the ``span`` sites before it and joined to the strongest of them, so that a weak site neither cuts a block
+nor passes a random sign on.  The contract is in include/nadavca_hip.h (nvk_phase_links_dev,
+nvk_phase_span_links_dev), the kernels in csrc/kernels_phase.hip and csrc/kernels_phasespan.hip, the loop in
 ``device.phase_sites_dev``.  Single process only, as the allele workflow."""
 import os
 
@@ -20,9 +22,12 @@ class PhaseBatch:
     ``refset.ReferenceSet``; 0 and None otherwise), ``position`` (forward, contig-local), ``ref_base``, ``alt_base``
     (codes 0..3), ``phase`` (int8: +1 where the alternative lies on haplotype 1 of the site's block, the haplotype that
     carries the alternative of the block's first site; -1 on haplotype 2), ``block`` (the index of the block's first
-    site), ``phase_set`` (the contig-local position of that site), ``block_size``, ``link`` and ``shared`` (the
-    log-likelihood ratio "same haplotype as the previous site" against "the other one" and the reads it rests on; both 0
-    at the first site of a contig), ``vote``, ``n_agree``, ``n_against`` (the leave-one-out vote of the
+    site, the root of the site's tree), ``phase_set`` (the contig-local position of that site), ``block_size``,
+    ``link`` and ``shared`` (the log-likelihood ratio "same haplotype as the previous site" against "the other one" and
+    the reads it rests on; both 0 at the first site of a contig), ``parent`` (the index of the site this one was
+    joined to: the site before it with ``span`` = 1, one of the ``span`` sites before it otherwise; -1 at a block's
+    first site), ``parent_link`` and ``parent_shared`` (the link to that site and its reads; 0 without a parent),
+    ``vote``, ``n_agree``, ``n_against`` (the leave-one-out vote of the
     reads tagged in the block, under the final phases), ``fraction``, ``lrt``, ``coverage`` (of the (position,
     alternative) row of ``fractions``; fraction and lrt 0 where that row has fraction 0).  ``gt``: '1|0' for phase +1,
     '0|1' for -1.
@@ -30,25 +35,28 @@ class PhaseBatch:
     ``read_phase_set`` (of the read's block; -1 without one), ``read_llr`` (the signed evidence H for haplotype 1),
     ``read_sites`` (the read's sites in its block).  A read that is not live or meets no site has 0 / -1 / -1 / 0 / 0.
     ``fractions``: the AlleleFractionBatch of the same rows; ``flips_per_round``: the sites flipped in each round of
-    the refinement."""
+    the refinement; ``span``: the ``span`` the batch was made with (with ``span`` > 1 a block need not be an interval
+    of sites: a site without a strong link stays a block of its own inside the block of its neighbours)."""
 
     SITE_FIELDS = ('contig', 'position', 'ref_base', 'alt_base', 'phase', 'block', 'phase_set', 'block_size', 'link',
-                   'shared', 'vote', 'n_agree', 'n_against', 'fraction', 'lrt', 'coverage')
+                   'shared', 'vote', 'n_agree', 'n_against', 'fraction', 'lrt', 'coverage', 'parent', 'parent_link',
+                   'parent_shared')
     READ_FIELDS = ('haplotype', 'read_contig', 'read_phase_set', 'read_llr', 'read_sites')
 
-    def __init__(self, sites, reads, fractions, flips_per_round, contig_names=None):
+    def __init__(self, sites, reads, fractions, flips_per_round, contig_names=None, span=1):
         for f in self.SITE_FIELDS:
             setattr(self, f, sites[f])
         for f in self.READ_FIELDS:
             setattr(self, f, reads[f])
         self.fractions, self.flips_per_round, self.contig_names = fractions, list(flips_per_round), contig_names
+        self.span = int(span)
 
     @classmethod
-    def empty(cls, n_reads, ref_len=0, rounds=0, threshold=None, contig_names=None, fractions=None):
+    def empty(cls, n_reads, ref_len=0, rounds=0, threshold=None, contig_names=None, fractions=None, span=1):
         """No site; every read untagged."""
         if fractions is None:
             fractions = AlleleFractionBatch.empty(ref_len, threshold, contig_names)
-        return cls(_site_table(0), _read_table(int(n_reads)), fractions, [0] * int(rounds), contig_names)
+        return cls(_site_table(0), _read_table(int(n_reads)), fractions, [0] * int(rounds), contig_names, span)
 
     def __len__(self):
         return int(self.position.size)
@@ -67,15 +75,21 @@ class PhaseBatch:
     def write_sites_tsv(self, file):
         """Header, then one tab-separated row per site: contig (by name where the batch has names), position, ref, alt,
         gt, phase_set, block_size, link, shared, vote, n_agree, n_against, fraction, lrt (floats as ``repr`` gives
-        them), coverage, to ``file``, a path or a text file."""
+        them), coverage, to ``file``, a path or a text file.  A batch made with ``span`` > 1 appends parent (the
+        contig-local position of the site this one was joined to, '.' without one) and parent_link."""
         label, gt = self._label(), self.gt
+        if self.span > 1:
+            more = lambda t: '\t%s\t%r' % ('.' if self.parent[t] < 0 else str(int(self.position[self.parent[t]])),
+                                            float(self.parent_link[t]))
+        else:
+            more = lambda t: ''
         _write(file, 'contig\tposition\tref\talt\tgt\tphase_set\tblock_size\tlink\tshared\tvote\tn_agree\tn_against\t'
-                     'fraction\tlrt\tcoverage\n',
-               ('%s\t%d\t%s\t%s\t%s\t%d\t%d\t%r\t%d\t%r\t%d\t%d\t%r\t%r\t%d\n'
+                     'fraction\tlrt\tcoverage%s\n' % ('\tparent\tparent_link' if self.span > 1 else ''),
+               ('%s\t%d\t%s\t%s\t%s\t%d\t%d\t%r\t%d\t%r\t%d\t%d\t%r\t%r\t%d%s\n'
                 % (label(int(self.contig[t])), self.position[t], 'ACGT'[self.ref_base[t]], 'ACGT'[self.alt_base[t]],
                    gt[t], self.phase_set[t], self.block_size[t], float(self.link[t]), self.shared[t],
                    float(self.vote[t]), self.n_agree[t], self.n_against[t], float(self.fraction[t]),
-                   float(self.lrt[t]), self.coverage[t]) for t in range(len(self))))
+                   float(self.lrt[t]), self.coverage[t], more(t)) for t in range(len(self))))
 
     def write_reads_tsv(self, file):
         """Header, then one tab-separated row per read of the ReadBatch: its index, ``H1`` / ``H2`` / ``none``, the
@@ -101,7 +115,7 @@ def _write(file, header, lines):
 _SITE_DTYPES = dict(contig=np.int32, position=np.int64, ref_base=np.int8, alt_base=np.int8, phase=np.int8,
                     block=np.int64, phase_set=np.int64, block_size=np.int64, link=np.float64, shared=np.int64,
                     vote=np.float64, n_agree=np.int64, n_against=np.int64, fraction=np.float64, lrt=np.float64,
-                    coverage=np.int64)
+                    coverage=np.int64, parent=np.int64, parent_link=np.float64, parent_shared=np.int64)
 
 
 def _site_table(S):
@@ -175,7 +189,7 @@ def _check_sites(sites, reference_num, refset):
 
 def phase_reads_batch(reference_num, read_batch, config=defaults.CONFIG_FILE, kmer_model=defaults.KMER_MODEL_FILE,
                       aligner=None, threshold=None, sites=None, min_fraction=0.25, min_coverage=8, event_length=1.0,
-                      clip=30.0, min_shared=3, min_link=2.0, rounds=2):
+                      clip=30.0, min_shared=3, min_link=2.0, rounds=2, span=1):
     """Phase the heterozygous sites of the sample and tag every read with its haplotype.
     The front end is ``estimate_allele_fractions_batch``'s (``batchflow.device_stage`` 'pooled', then
     ``batchflow.likelihood_rows``); the rows are normalised, strand-corrected and sorted ONCE and serve both the
@@ -184,11 +198,16 @@ def phase_reads_batch(reference_num, read_batch, config=defaults.CONFIG_FILE, km
     local) for a ``refset.ReferenceSet``; ``threshold`` may then be None.  Then ``device.phase_sites_dev`` (links,
     blocks, ``rounds`` rounds of tag / vote / flip: include/nadavca_hip.h, nvk_phase_links_dev) and one copy of its
     results to the host.  Over a ReferenceSet a chain never crosses a contig, and positions are contig-local and named.
-    ``clip`` bounds one read's evidence at one site (nats); two adjacent sites are joined when at least ``min_shared``
-    reads cover both and |link| >= ``min_link``.  ``clip``, ``min_link``, ``min_shared`` and ``threshold`` have NO
-    calibrated values: only synthetic levels have been scored with them.  ``event_length``, ``min_fraction``,
+    ``clip`` bounds one read's evidence at one site (nats); two sites are joined when at least ``min_shared``
+    reads cover both and |link| >= ``min_link``.  ``span`` (1 .. 8): a site is linked to the ``span`` sites before it
+    in its contig and joined to the one with the largest |link| among those that qualify (the nearest on ties); with
+    the default 1 only to the site before it, so that a weak site splits a block.  ``clip``, ``min_link``,
+    ``min_shared``, ``span`` and ``threshold`` have NO calibrated values: only synthetic levels have been scored with
+    them.  ``event_length``, ``min_fraction``,
     ``min_coverage``: as for ``estimate_allele_fractions_batch`` (``min_fraction`` bounds the fraction on both sides).
-    Only adjacent sites are linked: a weak site splits a block, and blocks are not merged across a weak link.
+    The joining is greedy (every site takes its strongest earlier neighbour inside ``span``; no maximum spanning tree
+    is sought), blocks are neither merged nor split during the refinement, and two variants inside one k-mer still
+    bias each other's evidence.
     Alphabet 4 only; single process only.  -> PhaseBatch."""
     what = 'phase_reads_batch'
     event_length, clip, min_fraction, min_link = float(event_length), float(clip), float(min_fraction), float(min_link)
@@ -203,6 +222,8 @@ def phase_reads_batch(reference_num, read_batch, config=defaults.CONFIG_FILE, km
     for name, v in (('min_coverage', min_coverage), ('min_shared', min_shared), ('rounds', rounds)):
         if isinstance(v, bool) or int(v) != v or v < 0:
             raise ValueError('%s: %s %r is not an integer >= 0' % (what, name, v))
+    from .device import check_span
+    span = check_span(what, span)
     if threshold is None:
         if sites is None:
             raise ValueError('%s needs a threshold to select sites with, or sites' % what)
@@ -231,14 +252,15 @@ def phase_reads_batch(reference_num, read_batch, config=defaults.CONFIG_FILE, km
     stage = device_stage(read_batch, reference_num if refset is None else refset, config, kmer_model, aligner,
                          'pooled')
     if stage.n_live == 0 or L == 0:
-        return PhaseBatch.empty(n_reads, L, rounds, threshold, names)
+        return PhaseBatch.empty(n_reads, L, rounds, threshold, names, span=span)
     ll, status, _ = likelihood_rows(stage, config, kmer_model)
     return phase_of_rows(stage, ll, status, reference_num, refset, kmer_model, n_reads, threshold, sites, min_fraction,
-                         int(min_coverage), event_length, clip, int(min_shared), min_link, int(rounds))
+                         int(min_coverage), event_length, clip, int(min_shared), min_link, int(rounds), span)
 
 
 def phase_of_rows(stage, ll, status, reference_num, refset, kmer_model, n_reads, threshold=None, sites=None,
-                  min_fraction=0.25, min_coverage=8, event_length=1.0, clip=30.0, min_shared=3, min_link=2.0, rounds=2):
+                  min_fraction=0.25, min_coverage=8, event_length=1.0, clip=30.0, min_shared=3, min_link=2.0, rounds=2,
+                  span=1):
     """The back half of ``phase_reads_batch``, from the log-likelihood rows ``ll`` and the per-read ``status`` of a
     ``batchflow.DeviceStage`` with live reads (device tensors, as ``batchflow.likelihood_rows`` returns them).
     ``reference_num``: int32 base codes of the whole reference; ``refset``: its ReferenceSet or None; ``n_reads``: the
@@ -246,7 +268,8 @@ def phase_of_rows(stage, ll, status, reference_num, refset, kmer_model, n_reads,
     arguments as checked there.  -> PhaseBatch."""
     import torch
     from .allele_fractions import allele_fractions_of_rows
-    from .device import allele_sorted_rows_dev, phase_sites_dev, to_host
+    from .device import allele_sorted_rows_dev, check_span, phase_sites_dev, to_host
+    span = check_span('phase_of_rows', span)
     sa, context = stage.sa, kmer_model.context
     device = torch.device('cuda', context.device)
     L = reference_num.size
@@ -266,7 +289,7 @@ def phase_of_rows(stage, ll, status, reference_num, refset, kmer_model, n_reads,
         P, alt = sites
     S = int(P.size)
     if S == 0:
-        return PhaseBatch.empty(n_reads, L, rounds, threshold, names, fractions)
+        return PhaseBatch.empty(n_reads, L, rounds, threshold, names, fractions, span)
     contig = np.zeros(S, dtype=np.int32)
     local = P
     if refset is not None:
@@ -277,9 +300,15 @@ def phase_of_rows(stage, ll, status, reference_num, refset, kmer_model, n_reads,
     chain[1:][contig[1:] != contig[:-1]] = 0        # a chain never crosses a contig
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
     got = phase_sites_dev(context, stage.dbatch.ref_off, chunk_start, reverse, key, val, sorted_key, sorted_val, order,
-                          up(P), up(alt), up(chain), clip, min_shared, min_link, rounds)
+                          up(P), up(alt), up(chain), clip, min_shared, min_link, rounds, span=span)
     # one copy to the host (every integer here is exact in a double)
     site_cols = ('link', 'shared', 'block', 'sigma', 'vote', 'n_agree', 'n_against')
+    if span > 1:
+        # the link a site was joined by: column parent's distance - 1 of its row (a root reads column 0 and is masked)
+        at = (torch.arange(S, device=device) - got['parent'] - 1).clamp(0, span - 1)[:, None]
+        got['parent_link'], got['parent_shared'] = got['span_link'].gather(1, at)[:, 0], \
+            got['span_shared'].gather(1, at)[:, 0]
+        site_cols += ('parent', 'parent_link', 'parent_shared')
     read_cols = ('read_block', 'read_llr', 'read_sites')
     n_live = int(sa.live.numel())
     flat = to_host(torch.cat([got[c].double() for c in site_cols + read_cols]
@@ -302,6 +331,14 @@ def phase_of_rows(stage, ll, status, reference_num, refset, kmer_model, n_reads,
         t[c] = np.ascontiguousarray(site[c])
     for c in ('shared', 'n_agree', 'n_against'):
         t[c] = site[c].astype(np.int64)
+    if span > 1:
+        t['parent'] = site['parent'].astype(np.int64)
+    else:
+        t['parent'] = np.where(block != np.arange(S), np.arange(S) - 1, -1).astype(np.int64)
+        site['parent_link'], site['parent_shared'] = site['link'], site['shared']
+    joined = t['parent'] >= 0
+    t['parent_link'] = np.where(joined, site['parent_link'], 0.0)
+    t['parent_shared'] = np.where(joined, site['parent_shared'], 0).astype(np.int64)
     # the (position, alternative) rows of the fractions; a pair without a row has fraction 0
     t['coverage'] = fractions.position_coverage[P].astype(np.int64)
     code = row_global * 4 + fractions.alt_base
@@ -318,4 +355,4 @@ def phase_of_rows(stage, ll, status, reference_num, refset, kmer_model, n_reads,
     r['haplotype'][live] = np.where(read['read_llr'] > 0, 1, np.where(read['read_llr'] < 0, 2, 0))
     r['read_contig'][live[has]] = contig[rb[has]]
     r['read_phase_set'][live[has]] = t['position'][rb[has]]
-    return PhaseBatch(t, r, fractions, flips, names)
+    return PhaseBatch(t, r, fractions, flips, names, span)

@@ -223,12 +223,12 @@ def mod_site_frequencies_of_rows(mods, solve, clip=30.0, device='cpu'):
 def phase_mods_batch(reference_num, read_batch, aligner, kmer_model, mod_model, pattern='CG', mod_offset=0, mod_code=4,
                      config=defaults.CONFIG_FILE, renorm_rounds=defaults.RENORM_ROUNDS, joint=True, max_joint=4,
                      site_prior=0.5, clip=30.0, min_tagged=4, threshold=None, sites=None, min_fraction=0.25,
-                     min_coverage=8, min_shared=3, min_link=2.0, rounds=2):
+                     min_coverage=8, min_shared=3, min_link=2.0, rounds=2, span=1):
     """Per occurrence of ``pattern`` and strand: the modification frequency of all reads, of the reads of haplotype 1
     and of haplotype 2, and the likelihood-ratio contrast of the two.
     ``phase_reads_batch`` runs with the canonical 4-letter ``kmer_model`` (``threshold``, ``sites``, ``min_fraction``,
-    ``min_coverage``, ``min_shared``, ``min_link``, ``rounds``: its arguments) and ``call_mods_batch`` with the
-    5-letter ``mod_model`` (``pattern``, ``mod_offset``, ``mod_code``, ``renorm_rounds``, ``joint``, ``max_joint``,
+    ``min_coverage``, ``min_shared``, ``min_link``, ``rounds``, ``span``: its arguments) and ``call_mods_batch`` with
+    the 5-letter ``mod_model`` (``pattern``, ``mod_offset``, ``mod_code``, ``renorm_rounds``, ``joint``, ``max_joint``,
     ``site_prior``: its arguments), both unchanged, on the same ``aligner`` and the same ``read_batch``, which
     neither alters: two front ends per batch.  Then the calls' rows go to the device, are sorted stably by (contig,
     position, strand) and tagged with their read's haplotype (``site_phase_sets``), and one call of
@@ -241,9 +241,9 @@ def phase_mods_batch(reference_num, read_batch, aligner, kmer_model, mod_model, 
     not an error.  Single process only.  -> PhasedModBatch."""
     from .batchflow import load_config, load_kmer_model
     from .call_mods import call_mods_batch
-    from .device import mod_site_solve_dev
+    from .device import check_span, mod_site_solve_dev
     from .phase import phase_reads_batch
-    clip = float(clip)
+    clip, span = float(clip), check_span('phase_mods_batch', span)
     if not 0.0 < clip < float('inf'):
         raise ValueError('phase_mods_batch: clip %r is not a positive finite number' % clip)
     if isinstance(min_tagged, bool) or int(min_tagged) != min_tagged or min_tagged < 0:
@@ -253,7 +253,7 @@ def phase_mods_batch(reference_num, read_batch, aligner, kmer_model, mod_model, 
     # signal), so both read the caller's
     phase = phase_reads_batch(reference_num, read_batch, config=config, kmer_model=kmer_model, aligner=aligner,
                               threshold=threshold, sites=sites, min_fraction=min_fraction, min_coverage=min_coverage,
-                              min_shared=min_shared, min_link=min_link, rounds=rounds)
+                              min_shared=min_shared, min_link=min_link, rounds=rounds, span=span)
     mods = call_mods_batch(read_batch, aligner, mod_model, pattern=pattern, mod_offset=mod_offset, mod_code=mod_code,
                            config=config, renorm_rounds=renorm_rounds, joint=joint, max_joint=max_joint,
                            site_prior=site_prior)
