@@ -1311,6 +1311,55 @@ int nvk_kmer_state_moments_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_even
                                double *out_moments, double *out_z, int32_t *out_status, int64_t *out_parts,
                                double *out_ms);
 
+/* REPEAT COUNT (count_repeats_batch).  The best path of an item's events over a short chain of k-mer states with one
+ * back edge, the loop of a tandem repeat: how often the path goes round the loop is the repeat's copy number less the
+ * copies the chain spells out.  Chain c has N = st_off[c+1] - st_off[c] states, 3 <= N <= NVK_REP_MAX_STATES = 256,
+ * with, per state, mu / ac / mc [st_off[c] + j] (as for the event alignment above), and four integers chain_par[4 c ..
+ * 4 c + 3] = (lp_from, lp_to, m1, m2) with 0 <= lp_to < lp_from < m2 <= N - 1 and 1 <= m1 <= m2: the back edge goes
+ * from state lp_from to state lp_to; m1 and m2 are marks (for a repeat: its first state and the first state after it).
+ * Item t is items[3 t .. 3 t + 2] = (chain, ev_lo, ev_hi): the E = ev_hi - ev_lo events e_i = level[ev_lo + i],
+ * already rescaled by the caller; items may share events (the usual pair: the two strands of one read).  l_stay,
+ * l_step, l_skip and trim_cost are finite and <= 0.  NINF = -infinity.  Every expression is a rounded f64 operation in
+ * the order written; the kernel only adds, multiplies and compares.
+ *   cells      (i, j), 0 <= i < E, 0 <= j < N;  em(i, j) = ac[j] - ((e_i - mu[j]) * (e_i - mu[j])) * mc[j]
+ *   candidates open = (double)i * trim_cost          j == 0 only: the path starts here, events 0 .. i-1 trimmed
+ *              step = S(i-1, j-1) + l_step
+ *              loop = S(i-1, lp_from) + l_step       j == lp_to only: the back edge is taken by a step, never a skip
+ *              stay = S(i-1, j) + l_stay
+ *              skip = S(i-1, j-2) + l_skip
+ *              a source outside the chain, or with i == 0, is NINF
+ *   S(i, j)    = v + em(i, j), v the largest candidate, the first of equal ones in the order open, step, loop, stay,
+ *              skip.  A cell without a candidate above NINF is NINF; it carries nothing and feeds no cell that counts.
+ *   carried    instead of a traceback, by every cell from the source of its winning candidate:
+ *              loops   the source's, + 1 when loop wins; 0 when open wins
+ *              first   the source's; i when open wins
+ *              marks   for q = 1, 2 the pair (v_q, i_q): the source's; (v, i) when j >= m_q and the winning source state
+ *                      is below m_q (open counts as state -1): the candidate value and the event with which the path
+ *                      enters the states from m_q on.  Unset: (NINF, -1).  The loop's source lies below m2 and its
+ *                      target below it, so going round the loop sets no mark anew.
+ *   end        end(i) = S(i, N-1) + (double)(E - 1 - i) * trim_cost; the result is the largest end value, the smallest
+ *              i among equal ones: `last`
+ *   status     NVK_REP_OK; NVK_REP_NO_EVENTS: E == 0; NVK_REP_NO_PATH: no end value above NINF (fewer events than the
+ *              shortest way through the chain); status_in (i32 per item, may be NULL): an item with a non-zero entry
+ *              is not run and reports that entry.
+ * out_hit i32[8 n_items]: per item (status, E, first, last, loops, i1, i2, 0), the carried values of (last, N-1);
+ * out_score f64[4 n_items]: (end(last), S(last, N-1), v1, v2).  An item that is not NVK_REP_OK has -1 in first, last,
+ * loops, i1 and i2 and NINF in its four scores.  v1 - first * trim_cost is what the path scored before the first mark,
+ * v2 - v1 between the marks, S(last, N-1) - v2 from the second mark on.
+ * One wave per item, the chain's tables and the row in registers: no workspace.  st_off, chain_par and items are copied
+ * to the host and checked (the offsets start at 0, never decrease and end at total_states; the chain integers as above;
+ * every item's chain below n_chains and 0 <= ev_lo <= ev_hi <= total_events, no item above 2^26 events).
+ * NVK_ERR_UNSUPPORTED for a chain above 256 states, NVK_ERR_INVALID for other bad arguments; NVK_OK with nothing
+ * written for n_items == 0.  out_ms (host pointer to one double, may be NULL): the milliseconds of the launches, by HIP
+ * events.  Device pointers but out_ms; out_hit and out_score aligned to 16 bytes. */
+enum { NVK_REP_OK = 0, NVK_REP_NO_EVENTS = 1, NVK_REP_NO_PATH = 2 };   /* per-item status of count_repeats_batch */
+enum { NVK_REP_MAX_STATES = 256 };
+int nvk_repeat_count_dev(nvk_ctx *ctx, int64_t n_items, const int64_t *items, int64_t total_events,
+                         const double *level, int64_t n_chains, int64_t total_states, const double *mu,
+                         const double *ac, const double *mc, const int64_t *st_off, const int32_t *chain_par,
+                         double l_stay, double l_step, double l_skip, double trim_cost, const int32_t *status_in,
+                         int32_t *out_hit, double *out_score, double *out_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,8 @@ from .locate import LocateBatch, signal_locate_batch  # noqa: F401
 from .decode import DecodeBatch, decode_batch  # noqa: F401
 from .decode_fit import DecodeFit  # noqa: F401
 from .decode_train import DecodeModelEstimate, estimate_decode_model  # noqa: F401
+from .repeats import (RepeatCountBatch, RepeatItems, RepeatLocus, count_repeats_batch, repeat_chain,  # noqa: F401
+                      repeat_items)
 
 __all__ = ['align_signal', 'align_signal_batch', 'estimate_snps', 'estimate_snps_batch', 'dtw', 'SeedAligner',
            'ReferenceSet', 'estimate_kmer_model', 'call_mods_batch', 'call_indels_batch',
@@ -33,4 +35,5 @@ __all__ = ['align_signal', 'align_signal_batch', 'estimate_snps', 'estimate_snps
            'compare_site_levels', 'SiteLevelBatch', 'SiteComparison', 'compare_site_ranks', 'site_rank_tests_batch', 'SiteRankComparison', 'compare_site_mixtures',
            'site_mixture_tests_batch', 'SiteMixtureComparison', 'estimate_mod_model', 'ModModelEstimate', 'signal_map_batch',
            'SignalMapBatch', 'signal_locate_batch', 'LocateBatch', 'decode_batch', 'DecodeBatch', 'DecodeFit',
-           'estimate_decode_model', 'DecodeModelEstimate']
+           'estimate_decode_model', 'DecodeModelEstimate', 'count_repeats_batch', 'RepeatCountBatch', 'RepeatLocus',
+           'RepeatItems', 'repeat_chain', 'repeat_items']

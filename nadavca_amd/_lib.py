@@ -27,6 +27,8 @@ MAP_OK, MAP_NO_EVENTS, MAP_LOST = 0, 1, 2   # NVK_MAP_*: per-read status of sign
 LOC_OK, LOC_NO_EVENTS, LOC_AMBIGUOUS = 0, 1, 2   # NVK_LOC_*: per-read status of signal_locate_batch
 LOC_BLOCK, LOC_MAX_EVENTS = 256, 256   # NVK_LOC_BLOCK, NVK_LOC_MAX_EVENTS
 DEC_OK, DEC_NO_EVENTS = 0, 1   # NVK_DEC_*: per-read status of decode_batch
+REP_OK, REP_NO_EVENTS, REP_NO_PATH = 0, 1, 2   # NVK_REP_*: per-item status of count_repeats_batch
+REP_MAX_STATES = 256   # NVK_REP_MAX_STATES
 
 TIE_EXACT = 1   # nvk_last_tie_flags: some path comparison of the read met two exactly equal scores
 TIE_NEAR = 2    # ... two scores closer than 2^-24 relative (beyond the class below)
@@ -138,6 +140,8 @@ SIGNATURES = {
     'nvk_kmer_posterior_dev': (_int, _kmer_sweeps(pos=True)),
     'nvk_kmer_expectations_dev': (_int, _kmer_sweeps()),
     'nvk_kmer_state_moments_dev': (_int, _kmer_sweeps()),
+    'nvk_repeat_count_dev': (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64] + [_vp] * 5 + [_dbl] * 4 + [_vp] * 3
+                             + [C.POINTER(_dbl)]),
 }
 
 LAUNCH_SWEEP, LAUNCH_EXACT, LAUNCH_ELL = 1, 2, 3   # nvk_launch_rec.op

@@ -1330,3 +1330,27 @@ def kmer_state_moments_dev(context, level, ev_off, k, mean, ac, mc, w_stay, w_st
                                             (w_stay, w_step, w_skip), status_in, moments, 3 * bool(timing))
     out = (moments, z, status, parts)
     return out + (ms,) if timing else out
+
+
+# ---- count_repeats_batch: the Viterbi path over a chain with a loop (include/nadavca_hip.h) -------------------
+def repeat_count_dev(context, level, items, mu, ac, mc, st_off, chain_par, l_stay, l_step, l_skip, trim_cost,
+                     status_in=None, timing=False):
+    """Every item's events (``items`` int64 (n, 3): chain, ev_lo, ev_hi into ``level``, rescaled) over its chain of
+    states (``mu``, ``ac``, ``mc`` / ``st_off``; ``chain_par`` int32 (chains, 4): lp_from, lp_to, m1, m2),
+    nvk_repeat_count_dev.  Device tensors; ``status_in``: int32 per item or None.
+    -> (hit int32 (n, 8): status, events, first event, last event, loops, i1, i2, 0; score f64 (n, 4): end value,
+    S(last, N-1), v1, v2) and, with ``timing``, the milliseconds of the launches."""
+    import torch
+    lib = _lib.load()
+    dev = st_off.device
+    n, n_chains = int(items.shape[0]), int(st_off.numel()) - 1
+    hit = torch.zeros((n, 8), dtype=torch.int32, device=dev)
+    score = torch.zeros((n, 4), dtype=torch.float64, device=dev)
+    ms = C.c_double(0.0)
+    _lib.check(lib.nvk_repeat_count_dev(context.handle, n, _dp(_one(items.reshape(-1))), int(level.numel()),
+                                        _dp(_one(level)), n_chains, int(mu.numel()), _dp(_one(mu)), _dp(_one(ac)),
+                                        _dp(_one(mc)), _dp(st_off), _dp(_one(chain_par.reshape(-1))), float(l_stay),
+                                        float(l_step), float(l_skip), float(trim_cost), _opt(status_in, n),
+                                        _dp(_one(hit.reshape(-1))), _dp(_one(score.reshape(-1))),
+                                        C.byref(ms) if timing else None), 'nvk_repeat_count_dev')
+    return (hit, score, float(ms.value)) if timing else (hit, score)
