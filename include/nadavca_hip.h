@@ -868,7 +868,7 @@ int nvk_phase_votes_dev(nvk_ctx *ctx, int64_t n_sites, int alphabet, const int64
                         const int64_t *row_read, const double *val, const int64_t *read_block, const double *read_llr,
                         double clip, double *out_vote, int64_t *out_agree, int64_t *out_against);
 
-/* Phasing across weak sites (phase_reads_batch with span > 1; csrc/kernels_phasespan.hip).  THE CONTRACT, in the terms
+/* Phasing across weak sites (phase_reads_batch with span > 1; csrc/kernels_phase.hip).  THE CONTRACT, in the terms
  * of the phasing contract above.
  *   span links nvk_phase_span_links_dev: for site s and w = 1 .. span with s - w >= site_first_s, out_link[s * span +
  *              w - 1] and out_shared[s * span + w - 1] are exactly the link and shared of the contract above taken between

@@ -96,16 +96,11 @@ extern "C" int nvk_consensus_accumulate_dev(nvk_ctx *ctx, int64_t n_reads, int64
   }
   NVK_HIP(hipSetDevice(ctx->device));
   if (total_ref == 0 || n_reads == 0) return NVK_OK;
-  {
-    TimerScope ts(ctx, NVK_K_CONSENSUS);
-    unsigned blocks = (unsigned)((total_ref + 255) / 256);
-    hipLaunchKernelGGL(consensus_kernel, dim3(blocks), dim3(256), 0, ctx->stream, n_reads, total_ref,
-                       alphabet, ll, reference, ref_off, chunk_start, reverse, status,
+  return nvk_timed(ctx, NVK_K_CONSENSUS, [&] {
+    hipLaunchKernelGGL(consensus_kernel, dim3((unsigned)((total_ref + 255) / 256)), dim3(256), 0, ctx->stream,
+                       n_reads, total_ref, alphabet, ll, reference, ref_off, chunk_start, reverse, status,
                        1.0 / normalization_event_length, ref_len, acc, (long long *)coverage);
-  }
-  NVK_HIP(hipGetLastError());
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return NVK_OK;
+  });
 }
 
 extern "C" int nvk_posterior_segments_dev(nvk_ctx *ctx, int64_t len, int64_t n_segments,
@@ -118,13 +113,8 @@ extern "C" int nvk_posterior_segments_dev(nvk_ctx *ctx, int64_t len, int64_t n_s
   }
   NVK_HIP(hipSetDevice(ctx->device));
   if (len == 0 || n_segments == 0) return NVK_OK;
-  {
-    TimerScope ts(ctx, NVK_K_POSTERIOR);
-    unsigned blocks = (unsigned)((len + 127) / 128);
-    hipLaunchKernelGGL(posterior_kernel, dim3(blocks), dim3(128), 0, ctx->stream, len, n_segments,
-                       seg_off, alphabet, k, snp_prior, ll, reference, out);
-  }
-  NVK_HIP(hipGetLastError());
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return NVK_OK;
+  return nvk_timed(ctx, NVK_K_POSTERIOR, [&] {
+    hipLaunchKernelGGL(posterior_kernel, dim3((unsigned)((len + 127) / 128)), dim3(128), 0, ctx->stream, len,
+                       n_segments, seg_off, alphabet, k, snp_prior, ll, reference, out);
+  });
 }

@@ -124,15 +124,11 @@ extern "C" int nvk_meth_count_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_r
     nvk_set_error("nvk_meth_count_dev: out_count is NULL");
     return NVK_ERR_INVALID;
   }
-  {
-    TimerScope ts(ctx, NVK_K_METH);
+  return nvk_timed(ctx, NVK_K_METH, [&] {
     hipLaunchKernelGGL(meth_kernel<false>, dim3(grid_of(n_reads, NT / 64)), dim3(NT), 0, ctx->stream, n_reads,
                        reference, ref_off, means, (const double *)nullptr, status, pattern, pattern_len, out_count,
                        (const int64_t *)nullptr, (int64_t *)nullptr, (double *)nullptr, (double *)nullptr);
-  }
-  NVK_HIP(hipGetLastError());
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return NVK_OK;
+  });
 }
 
 extern "C" int nvk_meth_scores_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_ref, const int32_t *reference,
@@ -154,13 +150,9 @@ extern "C" int nvk_meth_scores_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_
     nvk_set_error("nvk_meth_scores_dev: NULL output");
     return NVK_ERR_INVALID;
   }
-  {
-    TimerScope ts(ctx, NVK_K_METH);
+  return nvk_timed(ctx, NVK_K_METH, [&] {
     hipLaunchKernelGGL(meth_kernel<true>, dim3(grid_of(n_reads, NT / 64)), dim3(NT), 0, ctx->stream, n_reads,
                        reference, ref_off, means, expected, status, pattern, pattern_len, (int64_t *)nullptr,
                        occ_off, out_pos, out_scores, out_aggregate);
-  }
-  NVK_HIP(hipGetLastError());
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return NVK_OK;
+  });
 }

@@ -26,9 +26,6 @@ namespace {
 constexpr int NT = 256;
 constexpr int MAX_SETS = 8;
 
-// min(max(d, -clip), clip); -inf gives -clip (and so does a d that is not a number, whose row is in no set)
-__device__ __forceinline__ double clipped(double d, double clip) { return d > -clip ? (d < clip ? d : clip) : -clip; }
-
 // a row of a site as mix_mle sees it: one value for every set, and bit q of m says whether the row is in set q
 struct SiteRow {
   double dv, sv;

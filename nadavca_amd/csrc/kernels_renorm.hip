@@ -345,15 +345,10 @@ extern "C" int nvk_splev_groups_dev(nvk_ctx *ctx, int64_t n_groups, const double
   }
   if (n_groups == 0) return NVK_OK;
   NVK_HIP(hipSetDevice(ctx->device));
-  {
-    TimerScope ts(ctx, NVK_K_RENORM);
-    const unsigned blocks = grid_of(n_groups, 1);
-    hipLaunchKernelGGL(splev_groups_kernel, dim3(blocks), dim3(NT), 0, ctx->stream, n_groups, x, grp_off, t, c,
-                       knot_off, k, out);
-  }
-  NVK_HIP(hipGetLastError());
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return NVK_OK;
+  return nvk_timed(ctx, NVK_K_RENORM, [&] {
+    hipLaunchKernelGGL(splev_groups_kernel, dim3(grid_of(n_groups, 1)), dim3(NT), 0, ctx->stream, n_groups, x,
+                       grp_off, t, c, knot_off, k, out);
+  });
 }
 
 extern "C" int nvk_normalize_groups_dev(nvk_ctx *ctx, int64_t n_groups, const double *raw,
@@ -401,15 +396,10 @@ extern "C" int nvk_normalize_groups_dev(nvk_ctx *ctx, int64_t n_groups, const do
       return NVK_OK;
     }
   }
-  {
-    TimerScope ts(ctx, NVK_K_RENORM);
-    const unsigned blocks = grid_of(n_groups, 1);
-    hipLaunchKernelGGL(normalize_groups_kernel, dim3(blocks), dim3(NT), 0, ctx->stream, n_groups, raw,
+  return nvk_timed(ctx, NVK_K_RENORM, [&] {
+    hipLaunchKernelGGL(normalize_groups_kernel, dim3(grid_of(n_groups, 1)), dim3(NT), 0, ctx->stream, n_groups, raw,
                        grp_off, out, centre_scale);
-  }
-  NVK_HIP(hipGetLastError());
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return NVK_OK;
+  });
 }
 
 extern "C" int nvk_select_hist_dev(nvk_ctx *ctx, const double *x, int64_t n, int mode, double centre,
@@ -465,15 +455,10 @@ extern "C" int nvk_event_means_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_
   }
   if (total_ref == 0) return NVK_OK;
   NVK_HIP(hipSetDevice(ctx->device));
-  {
-    TimerScope ts(ctx, NVK_K_RENORM);
-    const unsigned blocks = (unsigned)((total_ref + 255) / 256);
-    hipLaunchKernelGGL(event_means_kernel, dim3(blocks), dim3(256), 0, ctx->stream, n_reads, total_ref,
-                       signal, sig_off, events, ref_off, status, out_means);
-  }
-  NVK_HIP(hipGetLastError());
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return NVK_OK;
+  return nvk_timed(ctx, NVK_K_RENORM, [&] {
+    hipLaunchKernelGGL(event_means_kernel, dim3((unsigned)((total_ref + 255) / 256)), dim3(256), 0, ctx->stream,
+                       n_reads, total_ref, signal, sig_off, events, ref_off, status, out_means);
+  });
 }
 
 extern "C" int nvk_linfit_rescale_dev(nvk_ctx *ctx, int64_t n_reads, const double *expected,
@@ -490,15 +475,10 @@ extern "C" int nvk_linfit_rescale_dev(nvk_ctx *ctx, int64_t n_reads, const doubl
     if (rc) return rc;
     out_fit = (double *)ctx->ws[WS_BANDTMP];
   }
-  {
-    TimerScope ts(ctx, NVK_K_RENORM);
+  return nvk_timed(ctx, NVK_K_RENORM, [&] {
     hipLaunchKernelGGL(linfit_kernel, dim3((unsigned)((n_reads + 63) / 64)), dim3(64), 0, ctx->stream, n_reads,
                        expected, means, ref_off, status, out_fit);
-    const unsigned blocks = grid_of(n_reads, 1);
-    hipLaunchKernelGGL(rescale_kernel, dim3(blocks), dim3(NT), 0, ctx->stream, n_reads, (const double *)out_fit,
-                       ref_off, status, signal, sig_off);
-  }
-  NVK_HIP(hipGetLastError());
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return NVK_OK;
+    hipLaunchKernelGGL(rescale_kernel, dim3(grid_of(n_reads, 1)), dim3(NT), 0, ctx->stream, n_reads,
+                       (const double *)out_fit, ref_off, status, signal, sig_off);
+  });
 }

@@ -314,13 +314,9 @@ extern "C" int nvk_site_mixture_tests_dev(nvk_ctx *ctx, int64_t n_rows_a, const 
     return NVK_ERR_INVALID;
   }
   NVK_HIP(hipSetDevice(ctx->device));
-  {
-    TimerScope ts(ctx, NVK_K_SITE);
+  return nvk_timed(ctx, NVK_K_SITE, [&] {
     hipLaunchKernelGGL(site_mixture_tests_kernel, dim3(grid_of(n_sites, NT / 64)), dim3(NT), 0, ctx->stream, n_rows_a,
                        key_a, val_a, n_rows_b, key_b, val_b, n_sites, site_key, iterations, min_sd_ratio, out_counts,
                        out_fit);
-  }
-  NVK_HIP(hipGetLastError());
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return NVK_OK;
+  });
 }

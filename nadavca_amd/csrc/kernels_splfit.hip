@@ -136,15 +136,10 @@ extern "C" int nvk_spline_fit_dev(nvk_ctx *ctx, int64_t n_reads, int64_t total_r
   int rc = nvk_ws_reserve(ctx, WS_BANDTMP, (size_t)(2 * total_ref + 2) * sizeof(double));
   if (rc) return rc;
   double *xs = (double *)ctx->ws[WS_BANDTMP], *ys = xs + total_ref + 1;
-  {
-    TimerScope ts(ctx, NVK_K_RENORM);
-    const unsigned blocks = (unsigned)(n_reads < 65535 * 16 ? n_reads : 65535 * 16);
-    hipLaunchKernelGGL(select_sort_kernel, dim3(blocks), dim3(64), 0, ctx->stream, n_reads, means, expected,
-                       ref_off, status, xs, ys, out_fit);
+  return nvk_timed(ctx, NVK_K_RENORM, [&] {
+    hipLaunchKernelGGL(select_sort_kernel, dim3(grid_of(n_reads, 1)), dim3(64), 0, ctx->stream, n_reads, means,
+                       expected, ref_off, status, xs, ys, out_fit);
     hipLaunchKernelGGL(first_pass_kernel, dim3((unsigned)((n_reads + 63) / 64)), dim3(64), 0, ctx->stream,
                        n_reads, (const double *)xs, (const double *)ys, ref_off, out_t, out_c, out_fit);
-  }
-  NVK_HIP(hipGetLastError());
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  return NVK_OK;
+  });
 }

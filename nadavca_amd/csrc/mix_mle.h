@@ -22,6 +22,10 @@
 constexpr int MIX_CACHE = 2;    // rows per lane whose exp(-|d|) stay in registers: sites of up to 64 * MIX_CACHE rows
 constexpr int MIX_BISECT = 52;  // bisection steps on [0, 1]
 
+// a row's log-likelihood ratio as the site kernels take it (the mixtures here, the phase kernels' evidence):
+// min(max(d, -clip), clip); -inf and a d that is not a number give -clip
+__device__ __forceinline__ double clipped(double d, double clip) { return d > -clip ? (d < clip ? d : clip) : -clip; }
+
 // exp(-|d|) in [0, 1] carrying the sign of the case: + for d > 0, - otherwise (-0.0 for d = -inf)
 __device__ __forceinline__ double signed_e(double d) { return copysign(exp(-fabs(d)), d > 0.0 ? 1.0 : -1.0); }
 

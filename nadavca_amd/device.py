@@ -320,7 +320,7 @@ def event_means_dev(dbatch, context, events, status=None):
     out = torch.zeros(dbatch.total_ref, dtype=torch.float64, device=dbatch.device)
     _lib.check(lib.nvk_event_means_dev(
         context.handle, dbatch.n, dbatch.total_ref, _dp(dbatch.signal), _dp(dbatch.sig_off), _dp(events),
-        _dp(dbatch.ref_off), _dp(status) if status is not None else C.c_void_p(0), _dp(out)),
+        _dp(dbatch.ref_off), _opt(status, dbatch.n), _dp(out)),
         'nvk_event_means_dev')
     return out
 
@@ -333,7 +333,7 @@ def linfit_rescale_dev(dbatch, context, expected, means, status=None):
     fit = torch.zeros((dbatch.n, 2), dtype=torch.float64, device=dbatch.device)
     _lib.check(lib.nvk_linfit_rescale_dev(
         context.handle, dbatch.n, _dp(expected), _dp(means), _dp(dbatch.ref_off),
-        _dp(status) if status is not None else C.c_void_p(0), _dp(dbatch.signal), _dp(dbatch.sig_off),
+        _opt(status, dbatch.n), _dp(dbatch.signal), _dp(dbatch.sig_off),
         _dp(fit)), 'nvk_linfit_rescale_dev')
     return fit
 
@@ -352,7 +352,7 @@ def spline_fit_dev(context, means, expected, ref_off, status=None):
     fit = torch.empty(n, dtype=torch.int32, device=means.device)
     _lib.check(lib.nvk_spline_fit_dev(
         context.handle, n, int(means.numel()), _dp(means), _dp(expected), _dp(ref_off),
-        _dp(status) if status is not None else C.c_void_p(0), _dp(t), _dp(c), _dp(fit)), 'nvk_spline_fit_dev')
+        _opt(status, n), _dp(t), _dp(c), _dp(fit)), 'nvk_spline_fit_dev')
     return t, c, fit
 
 
@@ -415,7 +415,7 @@ def meth_scores_dev(context, reference, ref_off, means, expected, status, patter
     m = int(pat.numel())
     if m == 0:
         pat = torch.zeros(1, dtype=torch.int32, device=dev)
-    st = _dp(status) if status is not None else C.c_void_p(0)
+    st = _opt(status, n)
     count = torch.zeros(max(n, 0), dtype=torch.int64, device=dev)
     _lib.check(lib.nvk_meth_count_dev(context.handle, n, total_ref, _dp(reference), _dp(ref_off), _dp(means), st,
                                       _dp(pat), m, _dp(count)), 'nvk_meth_count_dev')
@@ -601,7 +601,7 @@ def kmer_event_stats_dev(dbatch, context, events, status, k, central, alphabet, 
     _lib.check(lib.nvk_kmer_event_stats_dev(
         context.handle, dbatch.n, dbatch.total_ref, _dp(dbatch.signal), _dp(dbatch.sig_off), _dp(events),
         _dp(dbatch.ref_off), _dp(dbatch.reference), _dp(dbatch.context_before), _dp(dbatch.cb_off),
-        _dp(dbatch.context_after), _dp(dbatch.ca_off), _dp(status) if status is not None else C.c_void_p(0),
+        _dp(dbatch.context_after), _dp(dbatch.ca_off), _opt(status, dbatch.n),
         int(k), int(central), int(alphabet), int(trim), _dp(level) if level is not None else C.c_void_p(0),
         _dp(key), _dp(val), _dp(length)), 'nvk_kmer_event_stats_dev')
     return key, val, length
@@ -669,7 +669,7 @@ def mod_kmer_rows_dev(dbatch, context, events, status, k, central, alphabet, tri
     skipped = C.c_int64(0)
     head = (context.handle, dbatch.n, dbatch.total_ref, _dp(dbatch.signal), _dp(dbatch.sig_off), _dp(events),
             _dp(dbatch.ref_off), _dp(dbatch.reference), _dp(dbatch.context_before), _dp(dbatch.cb_off),
-            _dp(dbatch.context_after), _dp(dbatch.ca_off), _dp(status) if status is not None else C.c_void_p(0),
+            _dp(dbatch.context_after), _dp(dbatch.ca_off), _opt(status, dbatch.n),
             int(k), int(central), int(alphabet), int(trim), n_sites, _dp(site_off), _dp(site_pos), _dp(site_gamma),
             int(mod_code), _dp(level))
     count = torch.zeros(total, dtype=torch.int64, device=dev)
@@ -736,7 +736,7 @@ def allele_rows_dev(context, dbatch, ll, chunk_start, reverse, status, event_len
     val = torch.empty((n, alpha), dtype=torch.float64, device=dbatch.device)
     _lib.check(lib.nvk_allele_rows_dev(
         context.handle, dbatch.n, dbatch.total_ref, alpha, _dp(ll), _dp(dbatch.reference), _dp(dbatch.ref_off),
-        _dp(chunk_start), _dp(reverse), _dp(status) if status is not None else C.c_void_p(0), float(event_length),
+        _dp(chunk_start), _dp(reverse), _opt(status, dbatch.n), float(event_length),
         int(ref_len), _dp(key), _dp(val)), 'nvk_allele_rows_dev')
     return key, val
 
@@ -793,10 +793,9 @@ def phase_links_dev(context, site_lo, site_hi, site_alt, chain, row_read, sorted
     return link, shared
 
 
-def phase_tag_dev(context, ref_off, chunk_start, reverse, key, val, site_pos, site_alt, site_block, site_sigma, clip):
-    """Per read: (read_block int64 (n,), read_llr f64 (n,), read_sites int64 (n,)) device tensors (nvk_phase_tag_dev)
-    from the READ-MAJOR ``key`` / ``val`` of ``allele_rows_dev``; -1 / 0 / 0 for a read without a site.  ref_off i64
-    (n + 1,), chunk_start i64 (n,), reverse i32 (n,); site_pos, site_block i64 (S,), site_alt, site_sigma i32 (S,)."""
+def _phase_tag(entry, context, ref_off, chunk_start, reverse, key, val, site_pos, site_alt, site_block, site_sigma,
+               clip):
+    """The two tag entries (``entry``: the symbol's name): the same arguments, the same results."""
     import torch
     lib = _lib.load()
     n, S = int(ref_off.numel()) - 1, int(site_pos.numel())
@@ -804,11 +803,18 @@ def phase_tag_dev(context, ref_off, chunk_start, reverse, key, val, site_pos, si
     block = torch.full((n,), -1, dtype=torch.int64, device=dev)
     llr = torch.zeros(n, dtype=torch.float64, device=dev)
     count = torch.zeros(n, dtype=torch.int64, device=dev)
-    _lib.check(lib.nvk_phase_tag_dev(context.handle, n, S, int(val.shape[1]), _dp(ref_off), _dp(chunk_start),
-                                     _dp(reverse), _dp(key), _dp(val), _dp(site_pos), _dp(site_alt), _dp(site_block),
-                                     _dp(site_sigma), float(clip), _dp(block), _dp(llr), _dp(count)),
-               'nvk_phase_tag_dev')
+    _lib.check(getattr(lib, entry)(context.handle, n, S, int(val.shape[1]), _dp(ref_off), _dp(chunk_start),
+                                   _dp(reverse), _dp(key), _dp(val), _dp(site_pos), _dp(site_alt), _dp(site_block),
+                                   _dp(site_sigma), float(clip), _dp(block), _dp(llr), _dp(count)), entry)
     return block, llr, count
+
+
+def phase_tag_dev(context, ref_off, chunk_start, reverse, key, val, site_pos, site_alt, site_block, site_sigma, clip):
+    """Per read: (read_block int64 (n,), read_llr f64 (n,), read_sites int64 (n,)) device tensors (nvk_phase_tag_dev)
+    from the READ-MAJOR ``key`` / ``val`` of ``allele_rows_dev``; -1 / 0 / 0 for a read without a site.  ref_off i64
+    (n + 1,), chunk_start i64 (n,), reverse i32 (n,); site_pos, site_block i64 (S,), site_alt, site_sigma i32 (S,)."""
+    return _phase_tag('nvk_phase_tag_dev', context, ref_off, chunk_start, reverse, key, val, site_pos, site_alt,
+                      site_block, site_sigma, clip)
 
 
 def phase_votes_dev(context, site_lo, site_hi, site_alt, site_block, site_sigma, row_read, sorted_val, read_block,
@@ -873,18 +879,8 @@ def phase_tag_blocks_dev(context, ref_off, chunk_start, reverse, key, val, site_
                          clip):
     """``phase_tag_dev`` for ANY block array (nvk_phase_tag_blocks_dev): a read's block is the one with the largest |H|
     over all of the read's sites in that block, the smallest block index on ties.  Arguments and results as there."""
-    import torch
-    lib = _lib.load()
-    n, S = int(ref_off.numel()) - 1, int(site_pos.numel())
-    dev = ref_off.device
-    block = torch.full((n,), -1, dtype=torch.int64, device=dev)
-    llr = torch.zeros(n, dtype=torch.float64, device=dev)
-    count = torch.zeros(n, dtype=torch.int64, device=dev)
-    _lib.check(lib.nvk_phase_tag_blocks_dev(context.handle, n, S, int(val.shape[1]), _dp(ref_off), _dp(chunk_start),
-                                            _dp(reverse), _dp(key), _dp(val), _dp(site_pos), _dp(site_alt),
-                                            _dp(site_block), _dp(site_sigma), float(clip), _dp(block), _dp(llr),
-                                            _dp(count)), 'nvk_phase_tag_blocks_dev')
-    return block, llr, count
+    return _phase_tag('nvk_phase_tag_blocks_dev', context, ref_off, chunk_start, reverse, key, val, site_pos, site_alt,
+                      site_block, site_sigma, clip)
 
 
 def phase_forest(link, shared, site_first, min_shared, min_link):
@@ -1022,7 +1018,7 @@ def site_level_rows_dev(context, dbatch, events, expected, chunk_start, reverse,
     _lib.check(lib.nvk_site_level_rows_dev(
         context.handle, dbatch.n, dbatch.total_ref, _dp(dbatch.signal), _dp(dbatch.sig_off), _dp(events),
         _dp(dbatch.ref_off), _dp(expected), _dp(chunk_start), _dp(reverse),
-        _dp(status) if status is not None else C.c_void_p(0), int(trim), int(ref_len), _dp(key), _dp(val)),
+        _opt(status, dbatch.n), int(trim), int(ref_len), _dp(key), _dp(val)),
         'nvk_site_level_rows_dev')
     return key, val
 

@@ -6,7 +6,7 @@ that cover both, linked sites form blocks with a phase per site, every read is t
 evidence supports, and the phases are refined by the leave-one-out votes of the tagged reads.  With ``span`` > 1 a site
 is linked to the ``span`` sites before it and joined to the strongest of them, so that a weak site neither cuts a block
 nor passes a random sign on.  The contract is in include/nadavca_hip.h (nvk_phase_links_dev,
-nvk_phase_span_links_dev), the kernels in csrc/kernels_phase.hip and csrc/kernels_phasespan.hip, the loop in
+nvk_phase_span_links_dev), the kernels of either span in csrc/kernels_phase.hip, the loop in
 ``device.phase_sites_dev``.  Single process only, as the allele workflow."""
 import os
 

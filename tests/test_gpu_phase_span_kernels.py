@@ -1,8 +1,10 @@
-"""GPU tests of the span kernels (csrc/kernels_phasespan.hip) through the C-ABI on constructed rows, no DP: the span
-links against nvk_phase_links_dev (column 1, bit for bit) and against the numpy restatement (tests/phase_span_ref.py),
-the tags over arbitrary block arrays against nvk_phase_tag_dev on interval blocks (bit for bit) and against the
-restatement on interleaved ones, the whole loop of ``device.phase_sites_dev(span=3)``, and the invalid-argument
-returns.  The builders are those of tests/test_gpu_phase_kernels.py."""
+"""GPU tests of the span entries (csrc/kernels_phase.hip) through the C-ABI on constructed rows, no DP: the span links
+against nvk_phase_links_dev (the one-column instantiation of the same kernel against the 2-, 4- and 8-column ones:
+column 1, bit for bit; the chain form against the site_first form; site 0 with its chain flag set) and against the numpy
+restatement (tests/phase_span_ref.py), the tags over arbitrary block arrays against nvk_phase_tag_dev on interval
+blocks (bit for bit) and against the restatement on interleaved ones, the whole loop of
+``device.phase_sites_dev(span=3)``, and the invalid-argument returns.  The builders are those of
+tests/test_gpu_phase_kernels.py."""
 import ctypes as C
 
 import numpy as np
@@ -149,6 +151,43 @@ def test_span_links_on_sites_with_few_rows(ctx):
         empty = has.sum(axis=0) == 0
         assert (link[empty] == 0.0).all() and (shared[empty] == 0).all()
     assert (shared > 0).sum() > 20 and shared.max() == 3
+
+
+def chain_links(ctx, rows, chain):
+    from nadavca_amd import device
+    return [t.cpu().numpy() for t in device.phase_links_dev(
+        ctx, rows.lo, rows.hi, rows.site_alt, rows.up(np.asarray(chain, dtype=np.int32)), rows.row_read,
+        rows.sorted_val, CLIP)]
+
+
+@pytest.mark.parametrize('alpha', [4, 5])
+def test_site_0_with_its_chain_flag_set(ctx, alpha):
+    """nvk_phase_links_dev reads no site before site 0 whatever chain[0] says: 0.0 / 0 there, the other sites as with
+    chain[0] = 0."""
+    rows = Rows(ctx, build_case(alpha, 40 + alpha))
+    link, shared = chain_links(ctx, rows, [1] * 10)
+    want_link, want_shared = chain_links(ctx, rows, [0] + [1] * 9)
+    assert link.view(np.int64)[0] == 0 and shared[0] == 0
+    assert np.array_equal(link[1:].view(np.int64), want_link[1:].view(np.int64))
+    assert np.array_equal(shared[1:], want_shared[1:]) and shared.tolist() == [0, 129, 65, 64, 62, 1, 3, 9, 9, 0]
+
+
+@pytest.mark.parametrize('alpha', [4, 5])
+def test_the_chain_form_and_the_site_first_form_agree(ctx, alpha):
+    """nvk_phase_links_dev(chain) and nvk_phase_span_links_dev(site_first of that chain, span 1) are one kernel told
+    the sites' first sites in two ways: every bit of link and shared agrees."""
+    rows = Rows(ctx, build_case(alpha, 40 + alpha))
+    breaks = [0, 1, 1, 0, 0, 1, 1, 1, 1, 1]             # two chain breaks in a row
+    for chain in (CHAIN, [0] + [1] * 9, breaks):
+        link, shared = chain_links(ctx, rows, chain)
+        span_link, span_shared = rows.span_links(ctx, first_of_chain(chain), 1)
+        assert span_link.shape == (10, 1) and span_shared.shape == (10, 1)
+        assert np.array_equal(link.view(np.int64), span_link[:, 0].view(np.int64)), chain
+        assert np.array_equal(shared, span_shared[:, 0]), chain
+        served = np.array(chain) != 0
+        assert (shared[~served] == 0).all() and (link[~served].view(np.int64) == 0).all()
+        assert (shared[served] > 0).sum() >= 5
+    assert shared.tolist() == [0, 129, 65, 0, 0, 1, 3, 9, 9, 0]
 
 
 @pytest.mark.parametrize('alpha', [4, 5])

@@ -232,4 +232,4 @@ def test_new_entries_declared_bound_and_exported():
     for f in ('phase_span_links_dev', 'phase_tag_blocks_dev', 'phase_forest', 'phase_sites_dev', 'check_span'):
         assert callable(getattr(device, f))
     makefile = open(os.path.join(ROOT, 'nadavca_amd', 'csrc', 'Makefile')).read()
-    assert 'kernels_phasespan.hip' in makefile
+    assert 'kernels_phase.hip' in makefile                      # the span kernels live with the other phase kernels
