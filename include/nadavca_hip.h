@@ -1360,6 +1360,61 @@ int nvk_repeat_count_dev(nvk_ctx *ctx, int64_t n_items, const int64_t *items, in
                          double l_stay, double l_step, double l_skip, double trim_cost, const int32_t *status_in,
                          int32_t *out_hit, double *out_score, double *out_ms);
 
+/* REPEAT LIKELIHOODS (count_repeats_batch(layers=n)).  Beside the best path of REPEAT COUNT, the sum over all paths: for
+ * every c in 0 .. L-1 the likelihood of an item's events summed over the paths that go round the chain's loop exactly
+ * c times.  items, level, the chains (mu / ac / mc, st_off, chain_par), status_in and em(i, j) are the REPEAT COUNT
+ * contract's, with its checks of chains and items; the marks m1 and m2 are checked and not used.  w_stay, w_step,
+ * w_skip and w_trim are the moves' and the trim's linear weights, each finite and in (0, 1], with max(w_stay, w_step)
+ * >= 2^-10 (the caller passes the numbers whose logs the Viterbi call takes).  layers = L, 1 <= L <=
+ * NVK_REP_MAX_LAYERS = 128.  EXP, the floor b(i, j) = EXP(max(em(i, j), -300.0)) and "the exponent of v" are the K-MER
+ * POSTERIORS contract's.  Every expression is a rounded f64 operation in the order written (-ffp-contract=off); no
+ * library exp or log.
+ *   trellis    (i, c, j): event i, layer c = the trips round the loop so far, chain state j.  Values are kept scaled:
+ *              A^(i, ., .) = A(i, ., .) * 2^(-X_i).  z_c is the scaled sum over the paths of layer c that have ended
+ *              in state N-1, the events after their last one trimmed at w_trim each; o_i the scaled weight w_trim^i
+ *              of opening at event i.
+ *   row 0      A^(0, 0, 0) = b(0, 0), every other cell +0.0; o_0 = 1.0, X_0 = 0, z_c = A^(0, c, N-1)
+ *   row i >= 1 with P = A^(i-1, ., .):
+ *              x = the exponent of the largest of P over all layers and states and of z_c over all layers (0 when
+ *                  all of them are 0)
+ *              o_i = ldexp(o_(i-1) * w_trim, -x)
+ *              t = (((w_step * P[c][j-1]) + (w_step * P[c-1][lp_from])) + (w_stay * P[c][j])) + (w_skip * P[c][j-2]);
+ *                  the second term counts only at j == lp_to and c >= 1: the back edge is taken by a step only; a term
+ *                  that does not exist (a source outside the chain, no loop term, layer -1) is +0.0
+ *              A^(i, c, j) = (ldexp(t, -x) + q) * b(i, j), q = o_i at (c, j) = (0, 0) and +0.0 elsewhere
+ *              z_c = ldexp(z_c * w_trim, -x) + A^(i, c, N-1);  X_i = X_(i-1) + x
+ *              A path that would need layer L is dropped, not pooled into the last layer.
+ *   outputs    out_z f64[n_items * L]: item t's z_c after the last event at [t L + c]; out_x f64[n_items]:
+ *              (double)X_(E-1); log L(loops = c) = log(out_z) + out_x ln 2 is left to the caller.
+ *              out_status i32[n_items]: NVK_REP_OK; NVK_REP_NO_EVENTS: E == 0; NVK_REP_NO_PATH: every z_c is 0; else the
+ *              item's non-zero status_in entry.  An item that is not run (no events, a status_in entry) writes zeros
+ *              to out_z and out_x.
+ * THE SCALE.  The z_c take part in x because they, unlike the cells, do not shrink with the emissions: a path that
+ * has ended pays w_trim per later event where a live one pays about w * b, and after three events whose every
+ * emission sits on the floor a z_c scaled by the cells alone would be e^900 w_trim^3 times the largest cell, above
+ * the largest double.  With x as above every scaled value of row i-1 is below 1 after the ldexp, a row's sum has at
+ * most four terms of weight <= 1, and b <= EXP(max ac): nothing overflows; nor does o_i, which is at most e^300 times
+ * the largest cell of its row because A^(i, 0, 0) >= o_i b(i, 0).  What can happen is
+ * underflow, and it is harmless: a value vanishes only when it is 2^-1022 of the largest, in a likelihood that holds
+ * the largest as a term.  That largest value M of a row is a positive normal double whenever the row before it had
+ * one and w_stay >= 2^-10: a stay keeps the cell that held it, M_i >= w_stay b M_(i-1) >= 2^-10 e^-300 / 2, and a z_c
+ * stays through w_trim alone (a w_trim below 2^-1021 can flush it).  With w_stay < 2^-10 <= w_step the same holds for
+ * every cell but those of state N-1, which alone has no step out: a row whose weight sits in that state alone, with a
+ * w_stay below 2^-588, can vanish; x is then 0, the z_c keep what had ended, and the call reports what is left
+ * (NVK_REP_NO_PATH when nothing is).  Row 0 has b(0, 0) >= e^-300.
+ * One workgroup per item, ceil(L / LB) waves of 64 with LB = 32 layers per wave for chains of up to 64 states and 16
+ * above; rows in registers, no workspace, no atomics.  No sum crosses lanes: the result does not depend on an order of
+ * lanes or waves.  NVK_ERR_UNSUPPORTED for L above 128 or a chain above 256 states, NVK_ERR_INVALID for other bad
+ * arguments; NVK_OK with nothing written for n_items == 0.  out_ms as in nvk_repeat_count_dev.  Device pointers but
+ * out_ms. */
+enum { NVK_REP_MAX_LAYERS = 128 };
+int nvk_repeat_likelihoods_dev(nvk_ctx *ctx, int64_t n_items, const int64_t *items, int64_t total_events,
+                               const double *level, int64_t n_chains, int64_t total_states, const double *mu,
+                               const double *ac, const double *mc, const int64_t *st_off, const int32_t *chain_par,
+                               double w_stay, double w_step, double w_skip, double w_trim, int layers,
+                               const int32_t *status_in, double *out_z, double *out_x, int32_t *out_status,
+                               double *out_ms);
+
 #ifdef __cplusplus
 }
 #endif

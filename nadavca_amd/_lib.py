@@ -29,6 +29,7 @@ LOC_BLOCK, LOC_MAX_EVENTS = 256, 256   # NVK_LOC_BLOCK, NVK_LOC_MAX_EVENTS
 DEC_OK, DEC_NO_EVENTS = 0, 1   # NVK_DEC_*: per-read status of decode_batch
 REP_OK, REP_NO_EVENTS, REP_NO_PATH = 0, 1, 2   # NVK_REP_*: per-item status of count_repeats_batch
 REP_MAX_STATES = 256   # NVK_REP_MAX_STATES
+REP_MAX_LAYERS = 128   # NVK_REP_MAX_LAYERS
 
 TIE_EXACT = 1   # nvk_last_tie_flags: some path comparison of the read met two exactly equal scores
 TIE_NEAR = 2    # ... two scores closer than 2^-24 relative (beyond the class below)
@@ -142,6 +143,8 @@ SIGNATURES = {
     'nvk_kmer_state_moments_dev': (_int, _kmer_sweeps()),
     'nvk_repeat_count_dev': (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64] + [_vp] * 5 + [_dbl] * 4 + [_vp] * 3
                              + [C.POINTER(_dbl)]),
+    'nvk_repeat_likelihoods_dev': (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64] + [_vp] * 5 + [_dbl] * 4 + [_int]
+                                   + [_vp] * 4 + [C.POINTER(_dbl)]),
 }
 
 LAUNCH_SWEEP, LAUNCH_EXACT, LAUNCH_ELL = 1, 2, 3   # nvk_launch_rec.op

@@ -43,7 +43,6 @@
 
 namespace {
 
-constexpr double POST_EM_FLOOR = -300.0;
 constexpr double POST_MIN_MOVE = 0x1p-10;  // max(w_stay, w_step) is at least this
 
 struct PostArgs : HmmIn {
@@ -59,13 +58,6 @@ struct PostArgs : HmmIn {
 // pairs (j, j + 1) side by side, so that the 16-byte accesses of a wave's lanes are consecutive, 1 KB per instruction
 template <int T>
 __device__ __forceinline__ constexpr int post_store_at(int j) { return (j >> 1) * 2 * T + (j & 1); }
-
-// EXP of the contract
-__device__ __forceinline__ double post_exp(double g) {
-  const double y = g * xm::LOG2E;
-  const double n = rint(y);
-  return ldexp(xm::exp2_frac_horner(y - n), (int)n);
-}
 
 // b(i, s) for a level e
 __device__ __forceinline__ double post_emission(double e, double mean, double ac, double mc) {

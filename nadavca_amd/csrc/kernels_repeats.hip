@@ -20,12 +20,10 @@
 
 #include "kmer_hmm.h"
 #include "nvk_internal.h"
+#include "rep_chain.h"
 #include "wave.h"
 
 namespace {
-
-constexpr int REP_MIN_STATES = 3;
-constexpr int REP_MAX_EVENTS = 1 << 26;  // per item
 
 struct RepArgs {
   const int64_t *items;  // per item (chain, ev_lo, ev_hi)
@@ -53,13 +51,9 @@ __device__ __forceinline__ RepCell rep_ror1(const RepCell &c) {
                  dpp_ror1(c.first), dpp_ror1(c.i1), dpp_ror1(c.i2)};
 }
 
-// the value lane `l` holds, l wave-uniform
-__device__ __forceinline__ double rep_readlane(double v, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
+// the cell lane `l` holds, l wave-uniform
 __device__ __forceinline__ RepCell rep_readlane(const RepCell &c, int l) {
-  return RepCell{rep_readlane(c.S, l),           rep_readlane(c.v1, l),           rep_readlane(c.v2, l),
+  return RepCell{::rep_readlane(c.S, l),         ::rep_readlane(c.v1, l),         ::rep_readlane(c.v2, l),
                  __builtin_amdgcn_readlane(c.loops, l), __builtin_amdgcn_readlane(c.first, l),
                  __builtin_amdgcn_readlane(c.i1, l),    __builtin_amdgcn_readlane(c.i2, l)};
 }
@@ -82,9 +76,6 @@ __device__ __forceinline__ RepCell rep_slot(const RepCell (&cell)[SPL], int slot
   }
   return r;
 }
-
-// the instantiation that serves a chain of N states
-__host__ __device__ constexpr int rep_spl(int N) { return N <= 64 ? 1 : N <= 128 ? 2 : 4; }
 
 __device__ __forceinline__ void rep_write(const RepArgs &a, int64_t it, int status, int E, int first, int last,
                                           int loops, int i1, int i2, double end, double s_last, double v1, double v2) {
@@ -138,7 +129,7 @@ __global__ __launch_bounds__(64) void repeat_count_kernel(RepArgs a) {
     const double mine = lane < nb ? lev[i0 + lane] : 0.0;
     for (int t = 0; t < nb; t++) {
       const int i = i0 + t;
-      const double e = rep_readlane(mine, t);
+      const double e = ::rep_readlane(mine, t);
       const double open = (double)i * trim, tail = (double)(E - 1 - i) * trim;
       // the previous row's loop source, and the previous lane's last two states of the previous row
       const RepCell from = rep_readlane(rep_slot<SPL>(cell, from_slot), from_lane);
@@ -246,42 +237,9 @@ extern "C" int nvk_repeat_count_dev(nvk_ctx *ctx, int64_t n_items, const int64_t
     nvk_set_error("%s: NULL items, levels, offsets, chain tables or output", what);
     return NVK_ERR_INVALID;
   }
-  NVK_HIP(hipSetDevice(ctx->device));
-  std::vector<int64_t> soff;
-  int rc = nvk_fetch_offsets(ctx, "state", st_off, n_chains, soff, "total_states", total_states);
-  if (rc) return rc;
-  std::vector<int32_t> par((size_t)n_chains * 4);
-  std::vector<int64_t> item((size_t)n_items * 3);
-  if (n_chains > 0)
-    NVK_HIP(hipMemcpyAsync(par.data(), chain_par, par.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  NVK_HIP(hipMemcpyAsync(item.data(), items, item.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  NVK_HIP(hipStreamSynchronize(ctx->stream));
-  for (int64_t c = 0; c < n_chains; c++) {
-    const int64_t N = soff[c + 1] - soff[c];
-    const int32_t lp_from = par[4 * c], lp_to = par[4 * c + 1], m1 = par[4 * c + 2], m2 = par[4 * c + 3];
-    if (N > NVK_REP_MAX_STATES) {
-      nvk_set_error("%s: chain %lld has %lld states, above %d", what, (long long)c, (long long)N,
-                    (int)NVK_REP_MAX_STATES);
-      return NVK_ERR_UNSUPPORTED;
-    }
-    if (N < REP_MIN_STATES || !(0 <= lp_to && lp_to < lp_from && lp_from < m2 && m2 <= N - 1 && 1 <= m1 && m1 <= m2)) {
-      nvk_set_error("%s: chain %lld of %lld states has (lp_from, lp_to, m1, m2) = (%d, %d, %d, %d); wanted are at "
-                    "least %d states, 0 <= lp_to < lp_from < m2 <= N - 1 and 1 <= m1 <= m2", what, (long long)c,
-                    (long long)N, lp_from, lp_to, m1, m2, REP_MIN_STATES);
-      return NVK_ERR_INVALID;
-    }
-  }
-  bool used[5] = {false, false, false, false, false};   // by states per lane
-  for (int64_t t = 0; t < n_items; t++) {
-    const int64_t c = item[3 * t], lo = item[3 * t + 1], hi = item[3 * t + 2];
-    if (c < 0 || c >= n_chains || lo < 0 || hi < lo || hi > total_events || hi - lo > REP_MAX_EVENTS) {
-      nvk_set_error("%s: item %lld is (chain %lld, events %lld .. %lld); there are %lld chains and %lld events, and an "
-                    "item takes at most %d", what, (long long)t, (long long)c, (long long)lo, (long long)hi,
-                    (long long)n_chains, (long long)total_events, REP_MAX_EVENTS);
-      return NVK_ERR_INVALID;
-    }
-    used[rep_spl((int)(soff[c + 1] - soff[c]))] = true;
-  }
+  bool used[5];   // by states per lane
+  if (int rc = rep_check_batch(what, ctx, n_items, items, total_events, n_chains, total_states, st_off, chain_par, used))
+    return rc;
   RepArgs a;
   a.items = items;
   a.level = level;

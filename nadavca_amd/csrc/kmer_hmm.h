@@ -1,11 +1,13 @@
 // The k-mer HMM as the Viterbi sweep (kernels_decode.hip) and the forward-backward sweeps (kernels_posterior.hip) lay
 // it out, stated once: 4^k states, one workgroup per read, thread u owning the 16 consecutive states 16 u .. 16 u + 15
 // with their table entries in registers, rows of the trellis in LDS padded by HMM_PAD doubles after every 16 entries
-// (kernels_decode.hip says why); the shared part of the entries' arguments and checks; the Gaussian log density.
+// (kernels_decode.hip says why); the shared part of the entries' arguments and checks; the Gaussian log density, and
+// the emission floor and EXP of the linear-domain sweeps.
 #pragma once
 #include <type_traits>
 
 #include "nvk_internal.h"
+#include "xmath.h"
 
 constexpr int HMM_MAX_EVENTS = 1 << 26;  // per read
 constexpr int HMM_PAD = 2;               // doubles of padding after every 16 entries of a row in LDS
@@ -51,6 +53,15 @@ __device__ __forceinline__ void hmm_load_table(const HmmIn &in, int u, double (&
 __device__ __forceinline__ double gauss_log(double e, double mean, double ac, double mc) {
   const double d = e - mean;
   return ac - (d * d) * mc;
+}
+
+// The linear-domain sweeps (kernels_posterior.hip, kernels_repeatlik.hip): an emission below the floor counts as the
+// floor, and EXP of the K-MER POSTERIORS contract (include/nadavca_hip.h)
+constexpr double POST_EM_FLOOR = -300.0;
+__device__ __forceinline__ double post_exp(double g) {
+  const double y = g * xm::LOG2E;
+  const double n = rint(y);
+  return ldexp(xm::exp2_frac_horner(y - n), (int)n);
 }
 
 // f(std::integral_constant<int, K>{}) for the K that k is, 2..6 (checked by hmm_check_entry)

@@ -1350,3 +1350,28 @@ def repeat_count_dev(context, level, items, mu, ac, mc, st_off, chain_par, l_sta
                                         _dp(_one(hit.reshape(-1))), _dp(_one(score.reshape(-1))),
                                         C.byref(ms) if timing else None), 'nvk_repeat_count_dev')
     return (hit, score, float(ms.value)) if timing else (hit, score)
+
+
+def repeat_likelihoods_dev(context, level, items, mu, ac, mc, st_off, chain_par, w_stay, w_step, w_skip, w_trim, layers,
+                           status_in=None, timing=False):
+    """The likelihood of every item's events summed over the paths that go round its chain's loop exactly c times, for
+    c = 0 .. ``layers`` - 1, nvk_repeat_likelihoods_dev: the arguments of ``repeat_count_dev`` with the moves' and the
+    trim's linear weights (the numbers whose logs that call takes).
+    -> (z f64 (n, layers), x f64 (n,): log L(loops = c) = log(z[:, c]) + x ln 2; status int32 (n,)) and, with
+    ``timing``, the milliseconds of the launches."""
+    import torch
+    lib = _lib.load()
+    dev = st_off.device
+    n, n_chains, layers = int(items.shape[0]), int(st_off.numel()) - 1, int(layers)
+    z = torch.zeros((n, max(layers, 1)), dtype=torch.float64, device=dev)
+    x = torch.zeros(n, dtype=torch.float64, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    ms = C.c_double(0.0)
+    _lib.check(lib.nvk_repeat_likelihoods_dev(context.handle, n, _dp(_one(items.reshape(-1))), int(level.numel()),
+                                              _dp(_one(level)), n_chains, int(mu.numel()), _dp(_one(mu)),
+                                              _dp(_one(ac)), _dp(_one(mc)), _dp(st_off),
+                                              _dp(_one(chain_par.reshape(-1))), float(w_stay), float(w_step),
+                                              float(w_skip), float(w_trim), layers, _opt(status_in, n),
+                                              _dp(_one(z.reshape(-1))), _dp(_one(x)), _dp(_one(status)),
+                                              C.byref(ms) if timing else None), 'nvk_repeat_likelihoods_dev')
+    return (z, x, status, float(ms.value)) if timing else (z, x, status)

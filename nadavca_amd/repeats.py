@@ -14,12 +14,20 @@ holds beyond those the chain spells out.  On the device:
    sample window each entry names (``repeat_items`` makes them from base alignments);
 5. the operator (``nvk_repeat_count_dev``, contract in include/nadavca_hip.h): per item the best path's score, how
    often it went round the loop, and where and with what score it crossed into the repeat and out of it;
-6. the better strand per (read, locus), forward on ties, and the per-part scores, in numpy on the host.
+6. the better strand per (read, locus), forward on ties, and the per-part scores, in numpy on the host;
+7. with ``layers=n``: the likelihood of every count c0 .. c0 + n - 1 for the chosen item of every pair
+   (``nvk_repeat_likelihoods_dev``: the forward sum over all paths that go round the loop exactly c times, the count
+   as a second dimension of the trellis), and from it, in numpy on the host, the posterior over the window under a
+   flat prior, its mode, mean and confidence; ``RepeatCountBatch.genotypes`` combines the reads of a locus into
+   diploid genotype likelihoods through a stutter kernel.
 
 The copy number of a path is ``c0 + loops``, c0 = ceil(k / u) + 1 the copies the chain spells out (u the unit's length):
 alleles below c0 copies all count as c0.
 
-Limits: a Viterbi count, no likelihood per count; one repeat unit per locus, no interruptions; the loop is taken by a
+Limits: the per-count posterior is ordered, not calibrated (on the tests' batch the true count has a posterior below
+0.01 on 9 of 64 reads), and the most likely count is no better a count than Viterbi's; the window of counts starts at
+c0; ``genotypes`` is diploid only, its three parameters are uncalibrated, and a read cut off inside the repeat is left
+out rather than used as a lower bound; one repeat unit per locus, no interruptions; the loop is taken by a
 step only; alleles below c0 are not told apart; 4-letter tables, no RNA; the defaults are uncalibrated (the values at
 which the simulated reads of the test suite count best); the event detector makes about two events per base, and an
 extra event sometimes goes round the loop instead of staying: counts lean upwards a little (25 copies: median 25.5
@@ -30,10 +38,11 @@ import math
 import numpy as np
 
 from . import _lib, defaults
-from .rawsignal import rescale_by_moments_dev, resolve_kmer_model, signal_events_dev, transition_costs
+from .rawsignal import (rescale_by_moments_dev, resolve_kmer_model, signal_events_dev, transition_costs,
+                        transition_weights)
 
 REP_OK, REP_NO_EVENTS, REP_NO_PATH = _lib.REP_OK, _lib.REP_NO_EVENTS, _lib.REP_NO_PATH
-MAX_STATES = _lib.REP_MAX_STATES
+MAX_STATES, MAX_LAYERS = _lib.REP_MAX_STATES, _lib.REP_MAX_LAYERS
 _LETTERS = {'A': 0, 'C': 1, 'G': 2, 'T': 3}
 
 
@@ -195,6 +204,50 @@ def split_counts(counts, min_gain=8.0):
     return [(float(np.median(x[:c])), c), (float(np.median(x[c:])), int(x.size) - c)]
 
 
+def genotype_table(post, stutter=0.5, decay=0.5, outlier=0.01):
+    """The log-likelihood of every diploid genotype over a window of n counts, from the reads' posteriors ``post``
+    (f64 (reads, n), rows summing to 1) -> G f64 (n, n), [a1, a2] for a1 <= a2 and -inf below the diagonal.  A read
+    of allele a shows count c with K[c | a] = 1 - stutter at c = a and stutter / 2 * (1 - decay) * decay^(|c - a| - 1)
+    elsewhere, each column renormalised over the window; l_r(a) = (1 - outlier) * SUM_c K[c | a] post_r[c] +
+    outlier / n; G(a1, a2) = SUM_r log(l_r(a1) / 2 + l_r(a2) / 2), the reads summed in ascending order."""
+    post = np.asarray(post, dtype=np.float64)
+    n = post.shape[1]
+    if not (0.0 <= stutter < 1.0 and 0.0 < decay < 1.0 and 0.0 <= outlier < 1.0):
+        raise ValueError('genotype_table: stutter and outlier lie in [0, 1), decay in (0, 1)')
+    d = np.abs(np.arange(n)[:, None] - np.arange(n)[None, :])        # [c, a]
+    K = np.where(d == 0, 1.0 - stutter, stutter / 2.0 * (1.0 - decay) * decay ** np.maximum(d - 1, 0))
+    K = K / K.sum(axis=0, keepdims=True)
+    like = (1.0 - outlier) * (post @ K) + outlier / n                # [r, a]
+    G = np.full((n, n), -np.inf)
+    for a1 in range(n):
+        with np.errstate(divide='ignore'):
+            terms = np.log(0.5 * like[:, a1:a1 + 1] + 0.5 * like[:, a1:])
+        G[a1, a1:] = np.cumsum(terms, axis=0)[-1] if terms.shape[0] else 0.0
+    return G
+
+
+def likelihood_fields(c0_of_pair, status, z, x, lik_status):
+    """The per-pair fields ``count_repeats_batch(layers=n)`` adds, numpy on the host, from the likelihood operator's
+    outputs (``z`` (pairs, n), ``x`` (pairs,), ``lik_status``) -> dict of RepeatCountBatch.LIK_FIELDS.  log L =
+    np.log(z) + x * log 2; the posterior: the row less its largest value, np.exp, divided by the sum in ascending
+    order."""
+    n, L = z.shape
+    ok = (status == REP_OK) & (lik_status == REP_OK)
+    with np.errstate(divide='ignore'):
+        loglik = np.where(ok[:, None], np.log(z) + x[:, None] * math.log(2.0), np.nan)
+    safe = np.where(ok[:, None], loglik, 0.0)
+    w = np.exp(safe - safe.max(axis=1, keepdims=True)) if n else np.zeros((0, L))
+    post = w / np.cumsum(w, axis=1)[:, -1:]
+    counts = c0_of_pair[:, None] + np.arange(L)[None, :]
+    top = post.argmax(axis=1) if n else np.zeros(0, dtype=np.int64)
+    nan = lambda v: np.where(ok, v, np.nan)
+    return dict(count_loglik=loglik, count_post=np.where(ok[:, None], post, np.nan),
+                count_map=np.where(ok, c0_of_pair + top, -1),
+                count_mean=nan(np.cumsum(post * counts, axis=1)[:, -1] if n else np.zeros(0)),
+                count_conf=nan(post[np.arange(n), top]),
+                clipped=ok & ((top == L - 1) | (post[:, L - 1] > 1e-3)))
+
+
 class RepeatCountBatch:
     """What ``count_repeats_batch`` returns, numpy arrays with one entry per (read, locus) pair: ``read``, ``locus``,
     ``strand`` (0 forward, 1 reverse: the better-scoring one, forward on ties, or the one the item named), ``status``
@@ -205,15 +258,27 @@ class RepeatCountBatch:
     ``left_score`` / ``repeat_score`` / ``right_score`` (per event: before the repeat, inside it, after it, in the order
     the read passes them), ``repeat_start`` / ``repeat_end`` (the samples, inside the read, of the events with which
     the path enters the repeat and leaves it; -1 unless REP_OK), ``spanning`` (REP_OK, both marks crossed and, when
-    ``min_flank_score`` was given, both flank scores at or above it).  ``loci``: the loci, ``c0``: per locus."""
+    ``min_flank_score`` was given, both flank scores at or above it).  ``loci``: the loci, ``c0``: per locus.
+
+    With ``layers=n`` (else ``layers`` is 0 and these are None), per pair over the window of the n counts c0 .. c0 + n -
+    1: ``count_loglik`` (f64 (pairs, n): the log-likelihood of the pair's events summed over all paths of that count,
+    -inf where the sum is 0; NaN rows unless REP_OK), ``count_post`` (the same normalised per row under a flat prior
+    over the window), ``count_map`` (the most likely count, the smallest of equal ones; -1 unless REP_OK),
+    ``count_mean`` (the posterior mean), ``count_conf`` (the posterior of ``count_map``: it orders reads by how far the
+    count can be trusted and is not a calibrated probability), ``clipped`` (``count_map`` is the window's last count,
+    or the last count's posterior exceeds 1e-3: the window was too small for this read)."""
 
     FIELDS = ('read', 'locus', 'strand', 'status', 'count', 'loops', 'n_events', 'first', 'last', 'score', 'margin',
               'left_score', 'repeat_score', 'right_score', 'repeat_start', 'repeat_end', 'spanning')
+    LIK_FIELDS = ('count_loglik', 'count_post', 'count_map', 'count_mean', 'count_conf', 'clipped')
 
-    def __init__(self, loci, c0, kernel_ms=None, **fields):
+    def __init__(self, loci, c0, kernel_ms=None, layers=0, lik_ms=None, **fields):
         self.loci, self.c0, self.kernel_ms = list(loci), np.asarray(c0, dtype=np.int64), kernel_ms
+        self.layers, self.lik_ms = int(layers), lik_ms
         for f in self.FIELDS:
             setattr(self, f, fields[f])
+        for f in self.LIK_FIELDS:
+            setattr(self, f, fields[f] if self.layers else None)
         self.n = int(self.read.size)
 
     def locus_table(self):
@@ -238,10 +303,41 @@ class RepeatCountBatch:
             out.append(split_counts(counts, min_gain if max_alleles == 2 else float('inf')))
         return out
 
+    def genotypes(self, stutter=0.5, decay=0.5, outlier=0.01):
+        """The diploid genotype of every locus from the per-count posteriors of its spanning, unclipped pairs
+        (``genotype_table``; a batch made with ``layers``, else ValueError).  -> per locus None (no usable pair) or a
+        dict: ``alleles`` (the best pair of counts, a1 <= a2), ``loglik`` (its G), ``margin`` (nats over the second-best
+        pair; inf in a window of one count), ``het_margin`` (the best heterozygote's G less the best homozygote's; -inf
+        in a window of one count), ``reads`` (the pairs used), ``table`` (G, f64 (n, n): [a1 - c0, a2 - c0], -inf below
+        the diagonal).  ``stutter``, ``decay`` and ``outlier`` are UNCALIBRATED: round numbers at which the simulated
+        batch of the test suite genotypes right, fitted to no real data.  A read cut off inside the repeat is left
+        out, not used as a lower bound."""
+        if not self.layers:
+            raise ValueError('RepeatCountBatch.genotypes: the batch was made without layers')
+        out = []
+        for li in range(len(self.loci)):
+            use = (self.locus == li) & self.spanning & ~self.clipped & (self.count_map >= 0)
+            if not use.any():
+                out.append(None)
+                continue
+            table = genotype_table(self.count_post[use], stutter, decay, outlier)
+            n, c0 = self.layers, int(self.c0[li])
+            order = np.argsort(-table, axis=None, kind='stable')
+            a1, a2 = divmod(int(order[0]), n)
+            het = np.triu(np.ones((n, n), dtype=bool), 1)
+            best_het = float(table[het].max()) if n > 1 else -np.inf
+            out.append(dict(alleles=(c0 + a1, c0 + a2), loglik=float(table[a1, a2]),
+                            margin=float(table[a1, a2] - table.flat[order[1]]) if n > 1 else np.inf,
+                            het_margin=best_het - float(np.diag(table).max()), reads=int(use.sum()), table=table))
+        return out
+
     def write_tsv(self, path, names=None):
-        """One line per (read, locus) pair -> lines written.  ``names``: one per read (default ``read_<index>``)."""
+        """One line per (read, locus) pair -> lines written.  ``names``: one per read (default ``read_<index>``).  A
+        batch made with ``layers`` appends ``count_map``, ``count_mean``, ``count_conf`` and ``clipped``."""
         cols = ('status', 'count', 'loops', 'n_events', 'score', 'margin', 'left_score', 'repeat_score',
                 'right_score', 'repeat_start', 'repeat_end', 'spanning')
+        if self.layers:
+            cols += ('count_map', 'count_mean', 'count_conf', 'clipped')
         with open(path, 'w') as out:
             out.write('\t'.join(('read', 'locus', 'strand') + cols) + '\n')
             for p in range(self.n):
@@ -271,10 +367,12 @@ def chain_tables(loci, kmer_model):
 
 
 def pair_results(loci, c0, read, locus, strand_of, hit, score, ev_lo, ev_start, trim_cost, min_flank_score,
-                 kernel_ms=None):
+                 kernel_ms=None, layers=0, likelihoods=None):
     """Stage 6, numpy: the operator's per-item outputs -> RepeatCountBatch.  ``strand_of``: None when every pair owns
     two items (forward, reverse: items 2 p and 2 p + 1), else the strand of each pair's single item; ``ev_lo``: the
-    items' first events in the flat ``ev_start``."""
+    items' first events in the flat ``ev_start``.  With ``layers``, ``likelihoods(pick, status)`` runs the likelihood
+    operator on every pair's chosen item (``pick``: its index; ``status``: the pair's, its ``status_in``) -> (z, x,
+    status, milliseconds or None), numpy."""
     n = int(read.size)
     if strand_of is None:
         end = score[:, 0].reshape(n, 2)
@@ -301,7 +399,12 @@ def pair_results(loci, c0, read, locus, strand_of, hit, score, ev_lo, ev_start, 
     if min_flank_score is not None:
         with np.errstate(invalid='ignore'):
             spanning &= (left >= min_flank_score) & (right >= min_flank_score)
-    return RepeatCountBatch(loci, c0, kernel_ms, read=read, locus=locus, strand=strand, status=status,
+    extra, lik_ms = {}, None
+    if layers:
+        z, x, lik_status, lik_ms = likelihoods(pick, status)
+        extra = likelihood_fields(c0[locus], status, z, x, lik_status)
+    return RepeatCountBatch(loci, c0, kernel_ms, layers, lik_ms, **extra, read=read, locus=locus, strand=strand,
+                            status=status,
                             count=np.where(ok, c0[locus] + loops, -1) if n else np.zeros(0, np.int64), loops=loops,
                             n_events=h[:, 1], first=first, last=last, score=path, margin=margin, left_score=left,
                             repeat_score=inner, right_score=right, repeat_start=sample(i1), repeat_end=sample(i2),
@@ -310,7 +413,7 @@ def pair_results(loci, c0, read, locus, strand_of, hit, score, ev_lo, ev_start, 
 
 def count_repeats_batch(read_batch, loci, kmer_model=defaults.KMER_MODEL_FILE, items=None, p_stay=0.8, p_skip=0.01,
                         sigma_scale=0.5, trim_cost=math.log(0.01), min_events=32, window=2, threshold=5.0,
-                        var_floor=0.02, min_flank_score=None, context=None, timer=None):
+                        var_floor=0.02, min_flank_score=None, context=None, timer=None, layers=0):
     """The copy number of every locus of ``loci`` (``RepeatLocus``) in every read of ``read_batch``, from its raw
     signal alone (module docstring); any sequence or table the batch carries is ignored.  ``kmer_model``: a KmerModel
     or a path (4 letters); ``context``: the context a model loaded from a path is made on.  ``items``: None — every
@@ -323,11 +426,17 @@ def count_repeats_batch(read_batch, loci, kmer_model=defaults.KMER_MODEL_FILE, i
     spanning (a read that ends inside the repeat is not told by its path's score, which the repeat's events dominate,
     but by its worse flank).  The defaults are uncalibrated: the values at which the simulated reads of the test suite
     (dwell 3-17 samples, noise 0.35, the packaged 6-mer table) count best.  ``timer(name)``: called after each stage
-    (bench tool).  -> RepeatCountBatch."""
+    (bench tool).  ``layers``: 0, or the number n <= 128 of counts c0 .. c0 + n - 1 whose likelihoods, summed over all
+    paths, the chosen item of every pair gets beside its Viterbi count (``nvk_repeat_likelihoods_dev``, with
+    exp(trim_cost) as the trim's weight): the ``count_*`` fields and ``clipped`` of the result, and what
+    ``RepeatCountBatch.genotypes`` stands on.  -> RepeatCountBatch."""
     import torch
     from .decode import tables_dev
-    from .device import repeat_count_dev
+    from .device import repeat_count_dev, repeat_likelihoods_dev
     kmer_model = resolve_kmer_model(kmer_model, context)
+    layers = int(layers)
+    if not 0 <= layers <= MAX_LAYERS:
+        raise ValueError('count_repeats_batch: layers is 0 (no likelihoods) or at most %d' % MAX_LAYERS)
     if int(min_events) < 1:
         raise ValueError('count_repeats_batch: min_events is at least 1')
     if not (trim_cost <= 0.0 and math.isfinite(trim_cost)):
@@ -350,7 +459,8 @@ def count_repeats_batch(read_batch, loci, kmer_model=defaults.KMER_MODEL_FILE, i
         hit = np.tile(np.array([REP_NO_EVENTS, 0, -1, -1, -1, -1, -1, 0], dtype=np.int32), (n_items, 1))
         return pair_results(loci, c0, read, locus, None if items is None else items.reverse, hit,
                             np.full((n_items, 4), -np.inf), np.zeros(n_items, dtype=np.int64),
-                            np.zeros(0, dtype=np.int64), trim_cost, min_flank_score)
+                            np.zeros(0, dtype=np.int64), trim_cost, min_flank_score, None, layers,
+                            lambda pick, status: (np.zeros((n, layers)), np.zeros(n), status, None))
     ctx = kmer_model.context
     device = torch.device('cuda', ctx.device)
     tick = timer if timer is not None else (lambda name: None)
@@ -381,8 +491,17 @@ def count_repeats_batch(read_batch, loci, kmer_model=defaults.KMER_MODEL_FILE, i
                            timing=timer is not None)
     tick('count')
     host = lambda t: t.cpu().numpy()
+
+    def likelihoods(pick, status):
+        lik = repeat_likelihoods_dev(ctx, scaled, triples[torch.from_numpy(pick).to(device)].contiguous(), mu, ac, mc,
+                                     torch.from_numpy(st_off).to(device), torch.from_numpy(chain_par).to(device),
+                                     *transition_weights(p_stay, p_skip), math.exp(trim_cost), layers,
+                                     torch.from_numpy(status.astype(np.int32)).to(device), timing=timer is not None)
+        tick('likelihoods')
+        return host(lik[0]), host(lik[1]), host(lik[2]), lik[3] if timer is not None else None
+
     res = pair_results(loci, c0, read, locus, None if items is None else items.reverse, host(out[0]), host(out[1]),
                        host(triples[:, 1]), host(ev.ev_start), trim_cost, min_flank_score,
-                       out[2] if timer is not None else None)
+                       out[2] if timer is not None else None, layers, likelihoods)
     tick('results')
     return res

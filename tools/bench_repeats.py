@@ -4,8 +4,11 @@ both strands, the simulated signal of ``synthetic.make_read_spec``; n drawn from
 locus on both strands): its stages timed apart by HIP events — upload, normalisation, event detection, the rescale
 onto the table's means, the items, the operator (``nvk_repeat_count_dev``) and the host's stage 6 — the operator's own
 launch time and items per second, the counts it finds, and beside them the front end of ``decode_batch`` (the same
-four stages before its operator) on the same batch.  After a warm-up; the figures are the median of ``--reps`` runs.
-`python tools/bench_repeats.py [N] [--copies a,b] [--loci m] [--reps R]`."""
+four stages before its operator) on the same batch.  With ``--layers n`` the call with ``layers=n`` is timed too, in
+the same session: its stage (``nvk_repeat_likelihoods_dev`` on every pair's chosen item), the operator's own launch
+time and cell updates per second (cells = events x layers x states), the whole call beside the plain one, and what
+``genotypes()`` makes of it.  After a warm-up; the figures are the median of ``--reps`` runs.
+`python tools/bench_repeats.py [N] [--copies a,b] [--loci m] [--reps R] [--layers n]`."""
 import argparse
 import inspect
 import os
@@ -24,6 +27,7 @@ parser.add_argument('n_reads', nargs='?', type=int, default=10000)
 parser.add_argument('--copies', default='10,25', help='the alleles, copies of the unit; reads take them in turn')
 parser.add_argument('--loci', type=int, default=1)
 parser.add_argument('--reps', type=int, default=3)
+parser.add_argument('--layers', type=int, default=0, help='also time the call with layers=n (0: not)')
 opts = parser.parse_args()
 alleles = [int(x) for x in opts.copies.split(',')]
 
@@ -51,6 +55,7 @@ copies = np.array(copies)
 bare = ReadBatch.from_signals(np.concatenate(raws), np.concatenate([[0], np.cumsum([x.size for x in raws])]),
                               np.zeros(0, np.int32), np.zeros(len(raws) + 1, np.int64))
 STAGES = ('upload', 'normalise', 'events', 'rescale', 'items', 'count', 'results')
+STAGES_LIK = STAGES[:-1] + ('likelihoods', 'results')
 FRONT = ('upload', 'normalise', 'events', 'rescale', 'decode')
 
 
@@ -66,6 +71,7 @@ def staged(stages, run):
 
 
 count = lambda timer: count_repeats_batch(bare, loci, kmer_model=km, timer=timer)
+count_lik = lambda timer: count_repeats_batch(bare, loci, kmer_model=km, timer=timer, layers=opts.layers)
 defaults_of = inspect.signature(decode_batch).parameters
 front_args = tuple(defaults_of[name].default for name in ('p_stay', 'p_skip', 'sigma_scale', 'min_events', 'window',
                                                           'threshold', 'var_floor'))
@@ -73,12 +79,18 @@ front = lambda timer: decode.decode_stages(bare, km, *front_args, timer=timer)
 
 staged(STAGES, count)   # warm-up: workspaces, the allocator's blocks, first launches
 staged(FRONT, front)
-rows, kernel, front_rows = [], [], []
+if opts.layers:
+    staged(STAGES_LIK, count_lik)
+rows, kernel, front_rows, lik_rows, lik_kernel = [], [], [], [], []
 for _ in range(opts.reps):
     res, ms = staged(STAGES, count)
     rows.append(ms)
     kernel.append(res.kernel_ms)
     front_rows.append(staged(FRONT, front)[1])
+    if opts.layers:
+        with_lik, ms = staged(STAGES_LIK, count_lik)
+        lik_rows.append(ms)
+        lik_kernel.append(with_lik.lik_ms)
 med, kernel_ms = np.median(np.array(rows), axis=0), float(np.median(kernel))
 front_ms = np.median(np.array(front_rows), axis=0)
 n_items = 2 * opts.n_reads * len(loci)
@@ -106,3 +118,18 @@ print('strand right for %d of %d reads; counts per allele (median, min-max): %s'
                                     res.count[ok & (copies[res.read] == n)].min(),
                                     res.count[ok & (copies[res.read] == n)].max()) for n in alleles)))
 print('alleles():', res.alleles()[0])
+if opts.layers:
+    lik_med, lik_ms = np.median(np.array(lik_rows), axis=0), float(np.median(lik_kernel))
+    cells = float(with_lik.n_events[with_lik.status == 0].sum()) * opts.layers * n_states
+    print('--- layers=%d: one item per pair, %d items' % (opts.layers, with_lik.n))
+    print('%-46s %9.2f ms' % ('likelihoods stage (items, call, to the host)', lik_med[STAGES_LIK.index('likelihoods')]))
+    print('%-46s %9.2f ms  (%.1f G cell updates/s)' % ('operator, its launches alone (HIP events)', lik_ms,
+                                                       cells / lik_ms / 1e6))
+    print('%-46s %9.2f ms  (%.1f k reads/s; the plain call: %.2f ms)'
+          % ('count_repeats_batch(layers=%d), the whole call' % opts.layers, lik_med.sum(),
+             opts.n_reads / lik_med.sum(), med.sum()))
+    lik_own = with_lik.locus == 0
+    print('count_map equals count on %d of %d pairs of the reads\' own locus; %d clipped'
+          % (int((with_lik.count_map == with_lik.count)[lik_own].sum()), int(lik_own.sum()),
+             int(with_lik.clipped[lik_own].sum())))
+    print('genotypes():', {k: v for k, v in with_lik.genotypes()[0].items() if k != 'table'})
